@@ -22,6 +22,9 @@ rocprofv3 PMC passes), `cpu_baseline` (oracle/bitnuc_avx2.c on one core: `value`
 oracle's output for the same seeded stream; a mismatch makes the run exit 3), `config.library_csrc_sha16` (the hash the timed
 library reports for its sources) and, as the LAST key, `configs` (the fraction of every BASELINE config measured in this run).
 
+--dump-outputs DIR writes what the last timed step computed (its encode's packed words, its decode's bases) to DIR/*.npy, so that
+two builds run with the same arguments -- the same seeded input -- can be compared output for output (dump_outputs).
+
 Process model
   python bench.py --gpus N            (no launcher)  the parent touches no GPU: it starts
         `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child process,
@@ -81,7 +84,14 @@ def parse_args(argv=None):
     ap.add_argument("--probe", action="store_true", help="also time pure streaming kernels (the box's own HBM rates) when --no-extras is given")
     ap.add_argument("--traffic-child", choices=["codec"], default=None, help=argparse.SUPPRESS)  # the workload run under rocprofv3 --pmc
     ap.add_argument("--inject-stall", type=int, default=-1, help=argparse.SUPPRESS)  # test hook: this rank never joins the side collectives
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (the packed words its encode wrote, "
+                    "the bases its decode wrote) to DIR/*.npy as float64 / float32: every element when it fits in 48 MiB, else a fixed seeded sample with its indices")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.rehearse_cpu:
+        ap.error("--dump-outputs needs the GPU path (a --rehearse-cpu step computes nothing)")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------
@@ -242,6 +252,44 @@ def all_slots_check(torch, full, lw, world, slot_first_word, seed, rehearse=Fals
         if not good:
             return {"all_slots_ok": False, "first_bad_slot": s_}
     return {"all_slots_ok": True, "first_bad_slot": None}
+
+
+DUMP_WORDS = 1 << 20   # --dump-outputs: packed words kept (16 MiB of values + 8 MiB of indices)
+DUMP_BASES = 1 << 21   # ... and decoded bases kept (8 MiB of values + 16 MiB of indices)
+
+
+def dump_outputs(torch, out_dir, words, back, n, nw, rank, world):
+    """--dump-outputs: what the last timed step handed its caller, as .npy files that two builds given the same arguments (the
+    same seeded input stream) can be compared with element for element.  encode_words.npy: the packed u64 words the encode wrote,
+    one row of [low 32 bits, high 32 bits] per word in float64 (exact); decode_bases.npy: the ASCII bases the decode wrote, float32.
+    Every element when it fits, else a fixed seeded sample (always with the first and last element); *_index.npy holds the
+    element indices (float64).  A multi-rank run writes each rank's shard with a _rank<r> suffix, 1 / world of the sample each."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(SEED)
+    sfx = f"_rank{rank}" if world > 1 else ""
+
+    def pick(total, k):
+        if total <= k:
+            return np.arange(total, dtype=np.int64)
+        inner = np.sort(rng.choice(total - 2, size=k - 2, replace=False, shuffle=False).astype(np.int64)) + 1
+        return np.concatenate([[0], inner, [total - 1]]).astype(np.int64)
+
+    def gather(t, idx):
+        return t.index_select(0, torch.from_numpy(idx).to(t.device)).cpu().numpy()
+
+    wi, bi = pick(nw, DUMP_WORDS // world), pick(n, DUMP_BASES // world)  # 48 MiB for the whole job
+    w = gather(words, wi).view(np.uint64)
+    arrays = {"encode_words": np.stack([(w & 0xFFFFFFFF).astype(np.float64), (w >> 32).astype(np.float64)], axis=1),
+              "encode_words_index": wi.astype(np.float64),
+              "decode_bases": gather(back, bi).astype(np.float32),
+              "decode_bases_index": bi.astype(np.float64)}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), a)
+    return {"dir": os.path.abspath(out_dir), "files": sorted(name + sfx + ".npy" for name in arrays),
+            "words": f"{wi.size} of {nw}" + (" (seeded sample)" if wi.size < nw else ""),
+            "bases": f"{bi.size} of {n}" + (" (seeded sample)" if bi.size < n else "")}
 
 
 def carve_buffers(torch, dev, n, nw, R, separate):
@@ -603,6 +651,8 @@ def run_rank(args, real_stdout, traffic):
         # parity guard inside the bench: the last step's round trip must be the identity
         r_last = (args.steps - 1) % R if args.warm_decode else ((args.steps - 1) % R + 1) % R
         assert torch.equal(seqs[r_last], backs[r_last]), "decode(encode(x)) != x"
+        if args.dump_outputs:  # what the last timed step computed: its encode wrote words[(K - 1) % R], its decode backs[r_last]
+            state["line_extra"]["dump_outputs"] = dump_outputs(torch, args.dump_outputs, words[(args.steps - 1) % R], backs[r_last], n, nw, rank, world)
         # what the timed launches left for buffer set r_last (stream seed SEED + r_last), copied out now -- after the timed region,
         # before the side measurements reuse the buffers -- for the word-for-word comparison with the CPU oracle (cpu_baseline)
         if rank == 0 and not args.no_cpu_baseline and args.steps + args.warmup >= R:

@@ -8,6 +8,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 
@@ -65,3 +67,39 @@ def test_world_size_mismatch_is_refused():
     env = dict(os.environ, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, BENCH, "--gpus", "4", "--rehearse-cpu"], capture_output=True, text=True, timeout=120, env=env)
     assert r.returncode != 0 and "WORLD_SIZE" in (r.stderr + r.stdout)
+
+
+def test_steps_and_dump_outputs_arguments_are_checked():
+    """--steps is the number of timed steps (at least one: ms_per_step is the timed time over it); --dump-outputs needs a step that computes."""
+    r = subprocess.run([sys.executable, BENCH, "--steps", "0", "--rehearse-cpu"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr
+    r = subprocess.run([sys.executable, BENCH, "--rehearse-cpu", "--dump-outputs", "never_written"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--dump-outputs" in r.stderr and not os.path.exists("never_written")
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_last_steps_results(tmp_path, oracle):
+    """--dump-outputs DIR writes what the last timed step computed: the words its encode wrote (set (K - 1) % 3, seed SEED + 2 for K = 3) and
+    the bases its decode wrote (set 0, seed SEED): every word of 93,751 (the tail word included) and a seeded sample of the 3,000,007 bases,
+    each against the oracle; a second run with the same arguments writes the same files."""
+    import numpy as np
+    n, seed = 3_000_007, 0xB17C0DE
+    runs = []
+    for d in ("a", "b"):
+        rc, lines, err = run("--gpus", "1", "--steps", "3", "--warmup", "1", "--bases", str(n), "--no-extras", "--no-traffic", "--no-cpu-baseline",
+                             "--dump-outputs", str(tmp_path / d), timeout=600)
+        assert rc == 0, err[-3000:]
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and len(line["dump_outputs"]["files"]) == 4
+        runs.append({f[:-4]: np.load(tmp_path / d / f) for f in os.listdir(tmp_path / d)})
+    a, b = runs
+    assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
+    assert {k: v.dtype for k, v in a.items()} == {"encode_words": np.float64, "encode_words_index": np.float64,
+                                                  "decode_bases": np.float32, "decode_bases_index": np.float64}
+    words = oracle.encode(oracle.nucgen(n, seed + 2))
+    assert np.array_equal(a["encode_words_index"], np.arange(words.size))
+    assert np.array_equal(a["encode_words"][:, 0], (words & 0xFFFFFFFF).astype(np.float64))
+    assert np.array_equal(a["encode_words"][:, 1], (words >> np.uint64(32)).astype(np.float64))
+    bi = a["decode_bases_index"].astype(np.int64)
+    assert bi.size == 1 << 21 and bi[0] == 0 and bi[-1] == n - 1 and bool((np.diff(bi) > 0).all())
+    assert np.array_equal(a["decode_bases"], oracle.nucgen(n, seed)[bi].astype(np.float32))

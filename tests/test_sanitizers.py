@@ -2,6 +2,8 @@
 buffers.  GPU AddressSanitizer is not available on this pool; the device side is covered by
 guard-word checks in tests/test_gpu_parity.py."""
 import os
+import platform
+import shutil
 import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,7 +22,7 @@ def test_oracle_under_asan_ubsan(tmp_path):
     assert "sanitizer harness ok" in out.stdout
 
 
-def _build_and_run_host_harness(tmp_path, tag, san_flags, env_extra):
+def _build_and_run_host_harness(tmp_path, tag, san_flags, env_extra, no_aslr=False):
     exe = str(tmp_path / f"host_sanitize_{tag}")
     obj = str(tmp_path / f"oracle_{tag}.o")
     subprocess.run(["gcc", "-O1", "-g", "-std=c11", "-D_POSIX_C_SOURCE=200809L", *san_flags, "-c",
@@ -28,7 +30,15 @@ def _build_and_run_host_harness(tmp_path, tag, san_flags, env_extra):
     cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", *san_flags, os.path.join(ROOT, "tests", "c", "host_sanitize.cpp"), obj, "-o", exe, "-lpthread"]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=dict(os.environ, **env_extra))
+    env = dict(os.environ, **env_extra)
+    out = None
+    setarch = shutil.which("setarch")
+    if no_aslr and setarch:  # this process only: address randomisation off (the machine's setting is untouched)
+        out = subprocess.run([setarch, platform.machine(), "-R", exe], capture_output=True, text=True, timeout=900, env=env)
+        if out.stderr.startswith("setarch:"):  # the personality call itself was refused: run as is
+            out = None
+    if out is None:
+        out = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-6000:]
     assert "host sanitizer harness ok" in out.stdout
 
@@ -43,5 +53,7 @@ def test_product_host_code_under_asan_ubsan(tmp_path):
 
 def test_product_host_pool_under_tsan(tmp_path):
     """The same harness under ThreadSanitizer: the pool's mutex / condition-variable protocol (blocking and asynchronous jobs,
-    1..9 threads, destruction with a job outstanding) has no data race."""
-    _build_and_run_host_harness(tmp_path, "tsan", ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=1:second_deadlock_stack=1"})
+    1..9 threads, destruction with a job outstanding) has no data race.  The harness runs with address randomisation off: this
+    compiler's TSan runtime knows a fixed memory layout, and on kernels with 32 bits of mmap randomisation the executable can
+    land outside it ("FATAL: ThreadSanitizer: unexpected memory mapping") before a line of the harness runs."""
+    _build_and_run_host_harness(tmp_path, "tsan", ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=1:second_deadlock_stack=1"}, no_aslr=True)
