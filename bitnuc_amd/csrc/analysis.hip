@@ -45,6 +45,23 @@ int bitnuc_base_counts(bitnuc_ctx *c, const uint64_t *words, size_t n_words, siz
     return BITNUC_OK;
 }
 
+// the pairs from `done` on: four contiguous words per lane
+static int hdist_words_rest(bitnuc_ctx *c, bool query_mode, const unsigned long long *a, const unsigned long long *b, uint64_t query,
+                            size_t done, size_t count, size_t len, uint8_t *d_dist, bitnuc_err *err) {
+    const size_t rest = count - done;
+    const unsigned grid = grid_for(c, (rest / 4 + kBlock - 1) / kBlock + 1);
+    if (query_mode) hdist_words_kernel<true><<<grid, kBlock, 0, c->stream>>>(a + done, nullptr, query, rest, (unsigned)len, d_dist + done);
+    else hdist_words_kernel<false><<<grid, kBlock, 0, c->stream>>>(a + done, b + done, 0, rest, (unsigned)len, d_dist + done);
+    HIPCHK(hipGetLastError());
+    return BITNUC_OK;
+}
+
+#ifdef BITNUC_SWEEP_VARIANTS
+namespace {
+#include "evidence/analysis_launch.h" // the formulation that lost its A/B: the hook below
+} // namespace
+#endif
+
 static int hdist_words_launch(bitnuc_ctx *c, bool query_mode, const uint64_t *d_a, const uint64_t *d_b, uint64_t query,
                               size_t count, size_t len, uint8_t *d_dist, bitnuc_err *err) {
     clear_err(err);
@@ -55,8 +72,9 @@ static int hdist_words_launch(bitnuc_ctx *c, bool query_mode, const uint64_t *d_
         (!query_mode && (reinterpret_cast<uintptr_t>(d_b) & 7))) return fail(err, BITNUC_UNSUPPORTED);
     DeviceGuard g(c->device);
     const unsigned long long *a = reinterpret_cast<const unsigned long long *>(d_a), *b = reinterpret_cast<const unsigned long long *>(d_b);
+    BITNUC_EVIDENCE(if (evidence::wants_hdist_words(c)) return hdist_words_rest(c, query_mode, a, b, query, 0, count, len, d_dist, err);)
     size_t done = 0;
-    if (knobs(c).hdist_words_impl == 1 && aligned16(d_a) && (query_mode || aligned16(d_b)) && (reinterpret_cast<uintptr_t>(d_dist) & 3) == 0 && count >= 256) {
+    if (aligned16(d_a) && (query_mode || aligned16(d_b)) && (reinterpret_cast<uintptr_t>(d_dist) & 3) == 0 && count >= 256) {
         // whole 256-word wave tiles through the coalesced kernel (one tile per wave: the hardware dispatcher walks them)
         const unsigned long long tiles = count / 256;
         const unsigned grid = grid_for(c, (tiles + kBlock / 64 - 1) / (kBlock / 64));
@@ -66,12 +84,7 @@ static int hdist_words_launch(bitnuc_ctx *c, bool query_mode, const uint64_t *d_
         done = (size_t)tiles * 256;
         if (done == count) return BITNUC_OK;
     }
-    const size_t rest = count - done;
-    const unsigned grid = grid_for(c, (rest / 4 + kBlock - 1) / kBlock + 1);
-    if (query_mode) hdist_words_kernel<true><<<grid, kBlock, 0, c->stream>>>(a + done, nullptr, query, rest, (unsigned)len, d_dist + done);
-    else hdist_words_kernel<false><<<grid, kBlock, 0, c->stream>>>(a + done, b + done, 0, rest, (unsigned)len, d_dist + done);
-    HIPCHK(hipGetLastError());
-    return BITNUC_OK;
+    return hdist_words_rest(c, query_mode, a, b, query, done, count, len, d_dist, err);
 }
 
 int bitnuc_hdist_pairs_dev(bitnuc_ctx *c, const uint64_t *d_a, const uint64_t *d_b, size_t count, size_t len, uint8_t *d_dist, bitnuc_err *err) {

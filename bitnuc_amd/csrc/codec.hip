@@ -19,68 +19,17 @@ namespace {
 
 // ---- kernel-variant tables -------------------------------------------------------
 // The product library ships the variants that are in use: the tuned defaults (encode 39, decode 22), the plain
-// reference shape (0) and an earlier default (3).  The other 43 and the lane-per-base ballot formulation are
-// measurement evidence (profiles/): they are compiled only with -DBITNUC_SWEEP_VARIANTS, into
-// libbitnuc_hip_sweep.so, which tools/sweep*.py and the all-variants parity test load.
+// reference shape (0) and an earlier default (3).  The other 43, the 16-byte-store and LDS-transpose forms and the
+// lane-per-base ballot formulation are measurement evidence (profiles/): evidence/codec_launch.h, compiled only into the
+// evidence build, libbitnuc_hip_sweep.so, which tools/sweep*.py and the all-variants parity test load.
 //              id  UNROLL BLOCK NTLD   NTST   XPOSE  XCD
-#ifdef BITNUC_SWEEP_VARIANTS
-#define BITNUC_VARIANTS(X)                            \
-    X(0, 4, 256, false, false, false, false)          \
-    X(1, 4, 256, true, true, false, false)            \
-    X(2, 2, 256, true, true, false, false)            \
-    X(3, 2, 256, true, false, false, false)           \
-    X(4, 2, 256, false, false, false, false)          \
-    X(5, 4, 256, true, false, false, false)           \
-    X(6, 1, 256, true, false, false, false)           \
-    X(7, 2, 512, true, false, false, false)           \
-    X(8, 2, 1024, true, false, false, false)          \
-    X(9, 4, 256, false, false, true, false)           \
-    X(10, 4, 256, true, true, true, false)            \
-    X(11, 4, 256, true, false, true, false)           \
-    X(12, 2, 256, true, false, false, true)           \
-    X(13, 4, 256, false, false, false, true)          \
-    X(14, 2, 128, true, false, false, false)          \
-    X(15, 8, 256, true, false, false, false)          \
-    X(16, 4, 512, false, false, false, false)         \
-    X(17, 2, 512, false, false, false, false)         \
-    X(18, 4, 256, false, true, false, false)          \
-    X(19, 4, 512, true, false, true, false)           \
-    X(20, 1, 256, false, false, false, false)         \
-    X(21, 1, 512, true, false, false, false)          \
-    X(22, 2, 256, false, true, false, false)          \
-    X(23, 4, 1024, false, false, false, false)        \
-    X(24, 2, 256, false, false, false, true)          \
-    X(25, 4, 256, true, false, false, true)           \
-    X(26, 8, 256, false, false, false, true)          \
-    X(27, 4, 512, false, false, false, true)          \
-    X(28, 4, 256, false, false, true, true)           \
-    X(29, 1, 256, false, false, false, true)          \
-    X(30, 2, 256, true, true, false, true)            \
-    X(31, 4, 256, true, true, false, true)            \
-    X(32, 8, 256, true, true, false, false)           \
-    X(33, 4, 512, true, true, false, false)           \
-    X(34, 4, 256, false, true, false, true)           \
-    X(35, 4, 128, true, true, false, false)           \
-    X(36, 2, 64, true, false, false, false)           \
-    X(37, 4, 128, true, false, false, false)          \
-    X(38, 1, 128, true, false, false, false)          \
-    X(39, 2, 128, true, true, false, true)            \
-    X(40, 4, 128, true, true, false, true)            \
-    X(41, 2, 512, true, true, false, true)            \
-    X(42, 1, 256, true, true, false, true)            \
-    X(43, 2, 128, true, false, false, true)           \
-    X(44, 1, 128, true, true, false, true)            \
-    X(45, 1, 512, true, true, false, true)            \
-    X(46, 1, 1024, true, true, false, true)
-#else
 #define BITNUC_VARIANTS(X)                            \
     X(0, 4, 256, false, false, false, false)          \
     X(3, 2, 256, true, false, false, false)           \
     X(22, 2, 256, false, true, false, false)          \
     X(39, 2, 128, true, true, false, true)
-#endif
-constexpr int kNumVariants = 47;    // ids 0..46; which of them this build holds: variant_info(id).built
-[[maybe_unused]] constexpr int kBallotVariant = 100; // encode only: lane-per-base + ballot (sweep build; set_variant("encode", 100))
+constexpr int kNumVariants = 47;    // ids 0..46; which of them this build holds: codec_variant_built
+constexpr int kBallotVariant = 100; // encode only: lane-per-base + ballot (evidence build; set_variant("encode", 100))
 // defaults from the sustained (back-to-back) pair sweeps in profiles/ (10^9 bases, one tile per
 // workgroup, interleaved rounds in one process, decode reading words written two steps
 // earlier so that none of its input is Infinity-Cache resident -- what bench.py times):
@@ -94,140 +43,74 @@ constexpr int kNumVariants = 47;    // ids 0..46; which of them this build holds
 // 0.4019 vs 0.4024 ms, profiles/r02_encode_variant_stability.txt): a choice of attribution, not of speed.
 static_assert(kDefaultEnc == 39 && kDefaultDec == 22, "runtime.h holds the defaults the context starts with");
 
-struct VariantInfo { int unroll, block; bool ntld, ntst, xpose, xcd, built; };
-constexpr VariantInfo variant_info(int id) {
-    switch (id) {
-#define X(vid, U, B, NL, NS, XP, XC) case vid: return VariantInfo{U, B, NL, NS, XP, XC, true};
-        BITNUC_VARIANTS(X)
-#undef X
-    default: return VariantInfo{0, 0, false, false, false, false, false};
-    }
+// lds: bytes of unused dynamic LDS that only limit how many workgroups a CU holds (the evidence build's dyn_lds, tools/ab_occupancy.py)
+template <int UNROLL, int BLOCK, bool NTLD, bool NTST, bool XPOSE, bool XCD>
+hipError_t launch_encode_t(bitnuc_ctx *c, const uint8_t *seq, uint32_t *out32, unsigned long long len,
+                           unsigned long long *slot, bool al, int lds = 0) {
+    const unsigned long long tile = (unsigned long long)BLOCK * UNROLL;
+    const unsigned grid = grid_for(c, (len >> 4) / tile + 1, BLOCK);
+    if (al) encode_kernel<UNROLL, BLOCK, NTLD, NTST, true, XPOSE, XCD><<<grid, BLOCK, lds, c->stream>>>(seq, out32, len, slot);
+    else if constexpr (!XPOSE) encode_kernel<UNROLL, BLOCK, NTLD, NTST, false, false, XCD><<<grid, BLOCK, lds, c->stream>>>(seq, out32, len, slot);
+    return hipGetLastError();
 }
 
 template <int UNROLL, int BLOCK, bool NTLD, bool NTST, bool XPOSE, bool XCD>
-hipError_t launch_encode_t(bitnuc_ctx *c, const uint8_t *seq, uint32_t *out32, unsigned long long len,
-                           unsigned long long *slot, bool al) {
+hipError_t launch_decode_t(bitnuc_ctx *c, const uint32_t *in32, uint8_t *out, unsigned long long n_bases, bool al, int lds = 0) {
     const unsigned long long tile = (unsigned long long)BLOCK * UNROLL;
-    const unsigned grid = grid_for(c, (len >> 4) / tile + 1, BLOCK);
-    // knobs(c).dyn_lds (evidence build, tools/ab_occupancy.py): unused dynamic LDS that only limits how many workgroups a CU holds
-    if (al) encode_kernel<UNROLL, BLOCK, NTLD, NTST, true, XPOSE, XCD><<<grid, BLOCK, knobs(c).dyn_lds, c->stream>>>(seq, out32, len, slot);
-    else if constexpr (!XPOSE) encode_kernel<UNROLL, BLOCK, NTLD, NTST, false, false, XCD><<<grid, BLOCK, knobs(c).dyn_lds, c->stream>>>(seq, out32, len, slot);
+    const unsigned grid = grid_for(c, (n_bases >> 4) / tile + 1, BLOCK);
+    if (al) decode_kernel<UNROLL, BLOCK, NTLD, NTST, true, XPOSE, XCD><<<grid, BLOCK, lds, c->stream>>>(in32, out, n_bases);
+    else decode_kernel<UNROLL, BLOCK, NTLD, NTST, false, XPOSE, XCD><<<grid, BLOCK, lds, c->stream>>>(in32, out, n_bases);
     return hipGetLastError();
 }
 
-constexpr int kQuadFirst = 47, kQuadLast = 62; // encode variants of the evidence build's encode_quad_kernel
-#ifdef BITNUC_SWEEP_VARIANTS
-// encode variants 47..62 (evidence build): encode_quad_kernel (16-byte stores by a register quad transpose, 4 rounds per wave).
-// id - 47: bit 0 = nt loads, bit 1 = nt stores, bit 2 = XCD-contiguous tile order, bit 3 = 256 (not 128) threads per workgroup.
-template <int BLOCK>
-hipError_t launch_encode_quad_t(bitnuc_ctx *c, int mode, const uint8_t *seq, uint32_t *out32, unsigned long long len, unsigned long long *slot) {
-    const unsigned grid = grid_for(c, (len >> 4) / ((unsigned long long)BLOCK * 4) + 1, BLOCK);
-#define QUAD(NL, NS, XC) encode_quad_kernel<BLOCK, NL, NS, XC><<<grid, BLOCK, 0, c->stream>>>(seq, out32, len, slot)
-    switch (mode & 7) {
-    case 0: QUAD(false, false, false); break;
-    case 1: QUAD(true, false, false); break;
-    case 2: QUAD(false, true, false); break;
-    case 3: QUAD(true, true, false); break;
-    case 4: QUAD(false, false, true); break;
-    case 5: QUAD(true, false, true); break;
-    case 6: QUAD(false, true, true); break;
-    default: QUAD(true, true, true); break;
+constexpr bool shipped_variant(int id) {
+    switch (id) {
+#define X(vid, U, B, NL, NS, XP, XC) case vid: return true;
+        BITNUC_VARIANTS(X)
+#undef X
+    default: return false;
     }
-#undef QUAD
-    return hipGetLastError();
 }
+
+// the shipped variant v (the evidence build: with `lds`)
+hipError_t encode_shipped(bitnuc_ctx *c, int v, const uint8_t *seq, uint32_t *o, unsigned long long len, unsigned long long *slot, int lds = 0) {
+    switch (v) {
+#define X(id, U, B, NL, NS, XP, XC) \
+    case id: static_assert(!XP, "a shipped LDS-transpose variant needs the aligned-buffer fallback"); return launch_encode_t<U, B, NL, NS, XP, XC>(c, seq, o, len, slot, aligned16(seq), lds);
+        BITNUC_VARIANTS(X)
+#undef X
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t decode_shipped(bitnuc_ctx *c, int v, const uint32_t *i, uint8_t *out, unsigned long long n_bases, int lds = 0) {
+    switch (v) {
+#define X(id, U, B, NL, NS, XP, XC) \
+    case id: static_assert(!XP, "a shipped LDS-transpose variant needs the aligned-buffer fallback"); return launch_decode_t<U, B, NL, NS, XP, XC>(c, i, out, n_bases, aligned16(out), lds);
+        BITNUC_VARIANTS(X)
+#undef X
+    default: return hipErrorInvalidValue;
+    }
+}
+
+#ifdef BITNUC_SWEEP_VARIANTS
+#include "evidence/codec_launch.h" // the variants that lost their A/B: the hooks below
 #endif
 
 hipError_t launch_encode(bitnuc_ctx *c, const uint8_t *seq, uint64_t *out, unsigned long long len, unsigned long long *slot) {
-    uint32_t *o = reinterpret_cast<uint32_t *>(out);
-    const bool in_al = aligned16(seq), out_al = aligned16(out);
-#ifdef BITNUC_SWEEP_VARIANTS
-    if (c->enc_variant >= kQuadFirst && c->enc_variant <= kQuadLast && in_al && out_al) {
-        const int mode = c->enc_variant - kQuadFirst;
-        return (mode & 8) ? launch_encode_quad_t<256>(c, mode, seq, o, len, slot) : launch_encode_quad_t<128>(c, mode, seq, o, len, slot);
-    }
-#endif
-#ifdef BITNUC_SWEEP_VARIANTS
-    if (c->enc_variant == kBallotVariant) { // lane-per-base + ballot formulation (evidence variant)
-        const unsigned grid = grid_for(c, ((len + 63) / 64 + (kBlock / 64) * 4 - 1) / ((kBlock / 64) * 4));
-        encode_ballot_kernel<4><<<grid, kBlock, 0, c->stream>>>(seq, reinterpret_cast<unsigned long long *>(out), len, slot);
-        return hipGetLastError();
-    }
-#endif
-    int v = c->enc_variant;
-    if (v >= kQuadFirst) v = kDefaultEnc; // a quad variant asked for unaligned buffers: the default kernel handles any alignment
-    // the LDS-transpose variant needs 16-byte aligned buffers on both sides
-    if (variant_info(v).xpose && !(in_al && out_al)) v = kDefaultEnc;
-    switch (v) {
-#define X(id, U, B, NL, NS, XP, XC) \
-    case id: return launch_encode_t<U, B, NL, NS, XP, XC>(c, seq, o, len, slot, XP ? true : in_al);
-        BITNUC_VARIANTS(X)
-#undef X
-    default: return hipErrorInvalidValue;
-    }
+    BITNUC_EVIDENCE(if (evidence::wants_encode(c)) return evidence::launch_encode(c, seq, out, len, slot);)
+    return encode_shipped(c, c->enc_variant, seq, reinterpret_cast<uint32_t *>(out), len, slot);
 }
-
-template <int UNROLL, int BLOCK, bool NTLD, bool NTST, bool XPOSE, bool XCD>
-hipError_t launch_decode_t(bitnuc_ctx *c, const uint32_t *in32, uint8_t *out, unsigned long long n_bases, bool al) {
-    const unsigned long long tile = (unsigned long long)BLOCK * UNROLL;
-    const unsigned grid = grid_for(c, (n_bases >> 4) / tile + 1, BLOCK);
-    if (al) decode_kernel<UNROLL, BLOCK, NTLD, NTST, true, XPOSE, XCD><<<grid, BLOCK, knobs(c).dyn_lds, c->stream>>>(in32, out, n_bases);
-    else decode_kernel<UNROLL, BLOCK, NTLD, NTST, false, XPOSE, XCD><<<grid, BLOCK, knobs(c).dyn_lds, c->stream>>>(in32, out, n_bases);
-    return hipGetLastError();
-}
-
-constexpr int kX2First = 47, kX2Last = 54; // decode variants of the evidence build's decode_x2_kernel
-#ifdef BITNUC_SWEEP_VARIANTS
-// decode variants 47..54: decode_x2_kernel (8-byte loads + LDS transpose) for the whole 2 KiB wave tiles, the default
-// decode_kernel for what is left.  id - 47: bit 0 = nt loads, bit 1 = plain (not nt) stores, bit 2 = 2 words in flight per lane.
-template <int UNROLL>
-hipError_t launch_decode_x2_t(bitnuc_ctx *c, int mode, const unsigned long long *w, uint8_t *out, unsigned long long tiles) {
-    constexpr int B = 256;
-    const unsigned long long per = (unsigned long long)(B / 64) * UNROLL;
-    const unsigned grid = (unsigned)((tiles + per - 1) / per);
-    switch (mode & 3) {
-    case 0: decode_x2_kernel<B, UNROLL, false, true><<<grid, B, 0, c->stream>>>(w, out, tiles); break;
-    case 1: decode_x2_kernel<B, UNROLL, true, true><<<grid, B, 0, c->stream>>>(w, out, tiles); break;
-    case 2: decode_x2_kernel<B, UNROLL, false, false><<<grid, B, 0, c->stream>>>(w, out, tiles); break;
-    default: decode_x2_kernel<B, UNROLL, true, false><<<grid, B, 0, c->stream>>>(w, out, tiles); break;
-    }
-    return hipGetLastError();
-}
-#endif
 
 hipError_t launch_decode(bitnuc_ctx *c, const uint64_t *ebuf, uint8_t *out, unsigned long long n_bases) {
-    const bool in_al = aligned16(ebuf), out_al = aligned16(out);
-#ifdef BITNUC_SWEEP_VARIANTS
-    if (c->dec_variant >= kX2First && c->dec_variant <= kX2Last && out_al) {
-        const unsigned long long tiles = n_bases >> 11; // whole 2 KiB (64-word) wave tiles
-        if (tiles) {
-            const int mode = c->dec_variant - kX2First;
-            const unsigned long long *w = reinterpret_cast<const unsigned long long *>(ebuf);
-            const hipError_t rc = (mode & 4) ? launch_decode_x2_t<2>(c, mode, w, out, tiles) : launch_decode_x2_t<1>(c, mode, w, out, tiles);
-            if (rc != hipSuccess) return rc;
-        }
-        const unsigned long long done = tiles << 11;
-        if (done == n_bases) return hipSuccess;
-        return launch_decode_t<2, 256, false, true, false, false>(c, reinterpret_cast<const uint32_t *>(ebuf) + (done >> 4), out + done, n_bases - done, true);
-    }
-#endif
-    const uint32_t *i = reinterpret_cast<const uint32_t *>(ebuf);
-    int v = c->dec_variant;
-    if (v >= kX2First) v = kDefaultDec; // x2 asked for an unaligned output: the default kernel handles any alignment
-    if (variant_info(v).xpose && !in_al) v = kDefaultDec;
-    switch (v) {
-#define X(id, U, B, NL, NS, XP, XC) \
-    case id: return launch_decode_t<U, B, NL, NS, XP, XC>(c, i, out, n_bases, out_al);
-        BITNUC_VARIANTS(X)
-#undef X
-    default: return hipErrorInvalidValue;
-    }
+    BITNUC_EVIDENCE(if (evidence::wants_decode(c)) return evidence::launch_decode(c, ebuf, out, n_bases);)
+    return decode_shipped(c, c->dec_variant, reinterpret_cast<const uint32_t *>(ebuf), out, n_bases);
 }
 } // namespace
 
 namespace bitnuc_rt {
-bool codec_variant_built(int id) { return (kEvidenceBuild && id >= kQuadFirst && id <= kQuadLast) || variant_info(id).built; }
-bool codec_decode_variant_ok(int id) { return (kEvidenceBuild && id >= kX2First && id <= kX2Last) || variant_info(id).built; }
+bool codec_variant_built(int id) { return shipped_variant(id) BITNUC_EVIDENCE(|| evidence::encode_variant(id)); }
+bool codec_decode_variant_ok(int id) { return shipped_variant(id) BITNUC_EVIDENCE(|| evidence::decode_variant(id)); }
 int codec_num_variants() { return kNumVariants; }
 int codec_ballot_variant() { return kEvidenceBuild ? kBallotVariant : -1; }
 } // namespace bitnuc_rt
@@ -372,6 +255,7 @@ int bitnuc_stream_probe_dev(bitnuc_ctx *c, int mode, const void *d_src, void *d_
     clear_err(err);
     if (int st = check_ctx(c, err)) return st;
     DeviceGuard g(c->device);
+    BITNUC_EVIDENCE(if ((mode & 7) == 5) return evidence::probe_window_shape(c, mode, d_src, d_dst, bytes, err);)
     const unsigned long long n16 = bytes / 16;
     const bool ntl = (mode & 8) != 0, nts = (mode & 16) != 0, u2 = (mode & 32) != 0;
     const unsigned grid = grid_for(c, n16 / (kBlock * (u2 ? 2 : 4)) + 1);
@@ -407,21 +291,6 @@ int bitnuc_stream_probe_dev(bitnuc_ctx *c, int mode, const void *d_src, void *d_
         probe_dec_shape_kernel<2, 256, false, true><<<g4, 256, 0, c->stream>>>(static_cast<const uint32_t *>(d_src), dst, n16);
         break;
     }
-#ifdef BITNUC_SWEEP_VARIANTS
-    case 5: { // the every-window kernel's shape: `bytes` of ASCII-side input, 8 x as many bytes written.  bit 4: nt stores, bit 5: interleaved map, bits 6-7: rounds per trip 1 / 2 / 4
-        if (!d_src || !d_dst || !aligned16(d_src) || !aligned16(d_dst)) return fail(err, BITNUC_UNSUPPORTED);
-        const unsigned long long rounds = (bytes >> 10) & ~3ull;
-        const int U = 1 << ((mode >> 6) & 3);
-        const unsigned g5 = grid_for(c, (rounds + (unsigned long long)U * 4 - 1) / ((unsigned long long)U * 4));
-#define WIN(NS, UU, MP) probe_win_shape_kernel<NS, UU, MP><<<g5, kBlock, 0, c->stream>>>(src, dst, rounds)
-#define WIN_U(NS, MP) do { if (U == 1) WIN(NS, 1, MP); else if (U == 2) WIN(NS, 2, MP); else WIN(NS, 4, MP); } while (0)
-        if (mode & 32) { if (nts) WIN_U(true, 1); else WIN_U(false, 1); }
-        else { if (nts) WIN_U(true, 0); else WIN_U(false, 0); }
-#undef WIN_U
-#undef WIN
-        break;
-    }
-#endif
     default:
         return fail(err, BITNUC_UNSUPPORTED);
     }

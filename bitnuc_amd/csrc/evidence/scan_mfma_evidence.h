@@ -10,7 +10,7 @@
 
 constexpr int kScanPartials = 1024; // accumulators of the one-trip-per-wave fused count (context-owned, zero between calls)
 
-// The query's side of the product, built on the host (kmer.hip: scan_mfma_table) and passed BY VALUE in the kernel arguments (1.5 KiB:
+// The query's side of the product, built on the host (evidence/kmer_launch.h: scan_mfma_table) and passed BY VALUE in the kernel arguments (1.5 KiB:
 // a hipGraph node keeps its own copy).  w[rho][4 s + i]: K-step s = 2 b + e (load b, 8-position group e), dword i of the lane's 16-byte
 // operand, for the row whose windows start rho bases into the lane's 16.  Byte t of dwords {0, 1} (2, 3) belongs to position
 // 16 b + 8 e + t (+ 4): dword 0 / 2 holds channels A (low nibble) and C, dword 1 / 3 channels G and T; a nibble is 1.0 (0b0010)
@@ -108,7 +108,7 @@ kmer_scan_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, uns
     const int scale_a = !BIAS ? 127 : 127 + 8 * (int)((m32 & 3u) == 3u ? 0u : (m32 & 3u)); // E8M0: 2^(8 (rho & 3)) for rho & 3 < 3
     f32x16 c0;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) c0[i] = BIAS && PACK == 1 ? tab.c[i & 3] : 0.f; // 2^23, or 2^23 + k 2^(8 (i & 3)) when the table counts matches DOWN from k (kmer.hip: scan_mfma_table)
+    for (int i = 0; i < 16; ++i) c0[i] = BIAS && PACK == 1 ? tab.c[i & 3] : 0.f; // 2^23, or 2^23 + k 2^(8 (i & 3)) when the table counts matches DOWN from k (evidence/kmer_launch.h: scan_mfma_table)
     if constexpr (BIAS && PACK == 1) asm volatile("" : "+v"(c0)); // sixteen registers used as an untied C operand (a splat constant is re-materialised by 16 v_mov per round)
     const i32x8 bias_a = {lane < 32 ? 2 : 0, 0, 0, 0, 0, 0, 0, 0};                                   // PACK 2: nibble 0 of K-block 0 = 1.0, every row
     const i32x8 bias_b = {0x22222222, 0x22222222, 0x22222222, 0x22222222, 0, 0, 0, 0};              // ... x ones, scale 2^23
@@ -367,7 +367,7 @@ kmer_count_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, un
     const int scale_a = EMIT == 0 ? 127 : 127 + (jrow == 3u ? 1 : 6 * (int)jrow);
     f32x16 c0;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) c0[i] = EMIT == 0 ? 0.f : tab.c[i & 3]; // kmer.hip: count_mfma_table
+    for (int i = 0; i < 16; ++i) c0[i] = EMIT == 0 ? 0.f : tab.c[i & 3]; // scan_mfma_host.h: count_mfma_table
     if constexpr (EMIT != 0) asm volatile("" : "+v"(c0)); // sixteen registers used as an untied C operand (scan_mfma_emit's note)
     // where group g of the trip lives: region (half e, parity g & 1), entry g >> 1
     const unsigned wr0 = (lane & 1u) * kRegion + 16u * (lane >> 1);                 // the lane's own group l of round u: + 2 kRegion e + 512 u

@@ -6,8 +6,10 @@
 //   analysis.hip  base counts, many-pair hdist, split_packed                                         (analysis_device.h)
 //   comm.hip      RCCL all-gather of the packed words, xGMI link probe
 // Each kernel header is included by exactly one of them; what they share on the device is device_prims.h.
-// csrc/evidence/*.h hold the kernels that lost their A/B: the kernel headers include them only under -DBITNUC_SWEEP_VARIANTS
-// (libbitnuc_hip_sweep.so); the product library never sees them.
+// csrc/evidence/*.h hold what lost its A/B, compiled only under -DBITNUC_SWEEP_VARIANTS (libbitnuc_hip_sweep.so): the kernel headers
+// include its kernels (*_evidence.h), and each unit includes its launch dispatch (*_launch.h) once.  A product launcher that has
+// alternatives starts with one BITNUC_EVIDENCE(if (evidence::wants_<x>(c, ...)) return evidence::launch_<x>(c, ...);) line;
+// wants_<x> is false when every knob it reads holds its shipped value, so with default knobs both builds run the code after it.
 #pragma once
 #include "../../include/bitnuc_hip.h"
 
@@ -32,6 +34,24 @@ constexpr size_t kDefaultHostCutoff = (size_t)1 << 20;       // encode, hdist
 constexpr size_t kDefaultHostCutoffDecode = (size_t)1 << 19; // decode
 constexpr int kDefaultEnc = 39, kDefaultDec = 22;            // codec.hip: the variant tables
 
+// The shipped values of the launch parameters the evidence build can turn (SweepKnobs' defaults): the product's launch code uses these.
+constexpr int kKmerBlock = 256;    // threads per workgroup of the dense-batch kernel and the unaligned scan
+constexpr int kDenseUnroll = 1;    // dense batch: items in flight per wave
+constexpr int kDensePolicy = 3;    // dense batch and sliding windows: bit0 nt loads, bit1 nt stores
+constexpr bool kSlideNt = (kDensePolicy & 2) != 0; // the sliding kernels' nt stores
+constexpr int kSlideRounds = 1;    // kmer_slide_kernel: rounds per wave trip
+constexpr int kSlide2Rounds = 4;   // kmer_slide2_kernel: 1 KiB rounds per wave trip
+constexpr int kScanUnroll = 4;     // unaligned scan: rounds per wave (grid size)
+constexpr int kScanSegRounds = 4;  // kmer_scan_seg_mfma_kernel: rounds per wave trip
+constexpr int kScanSegBlock = 64;  // ... threads per workgroup
+constexpr int kCountRounds = 4;    // kmer_count3_mfma_kernel: rounds per trip
+constexpr int kCountGrid = 12;     // ... workgroups per CU
+constexpr int kFixedStream = 1;    // encode_fixed_kernel (back-to-back reads): cut the tile's 2-bit stream
+constexpr int kPlanTiles = 1;      // decode_batch_plan_kernel: tiles per wave trip
+constexpr int kPlanStore = 2;      // ... store policy
+constexpr int kPlanEncBlock = 256; // encode_batch_plan_kernel: threads per workgroup
+constexpr int kPlanEncTiles = 1;   // ... tiles per wave trip
+
 // Selectors of ALTERNATIVE FORMULATIONS -- the ones that lost their A/B (profiles/README.md) and timing-only ablations.  The product
 // context does not hold them: knobs(c) is this struct's defaults, a compile-time constant, and bitnuc_ctx_set_variant() answers -2 to
 // anything but the shipped value.  Only the evidence build (-DBITNUC_SWEEP_VARIANTS, libbitnuc_hip_sweep.so: tools/ and the variant
@@ -41,44 +61,44 @@ struct SweepKnobs {
     int batch_dense = 1;         // stride == k batches use kmer_dense_kernel (0: the general strided kernel)
     int batch_slide = 1;         // stride 1 (every window of a sequence), 2, 4, 8, 16 batches use the sliding kernels (0: the general strided kernel)
     int slide_impl = 1;          // stride-1 windows: 1 = line-aligned rounds of 1024 windows (kmer_slide2_kernel), 0 = rounds of 992 (kmer_slide_kernel)
-    int slide_rounds = 1;        // kmer_slide_kernel: consecutive rounds per wave trip (1, 2, 4, 8)
-    int slide2_rounds = 4;       // kmer_slide2_kernel: consecutive 1 KiB rounds per wave trip (1, 2, 4)
-    int dense_policy = 3, scan_policy = 3; // bit0: nt loads, bit1: nt stores
-    int kmer_block = 256;        // threads per workgroup of the dense-batch and scan kernels: 64, 128 or 256
-    int dense_unroll = 1;        // items (64 k-mers = 2 dwordx4 per lane) in flight per wave: 1, 2 or 4
-    int scan_unroll = 4;         // rounds (1 KiB loads) in flight per wave: 1, 2 or 4
+    int slide_rounds = kSlideRounds;        // kmer_slide_kernel: consecutive rounds per wave trip (1, 2, 4, 8)
+    int slide2_rounds = kSlide2Rounds;       // kmer_slide2_kernel: consecutive 1 KiB rounds per wave trip (1, 2, 4)
+    int dense_policy = kDensePolicy, scan_policy = 3; // bit0: nt loads, bit1: nt stores
+    int kmer_block = kKmerBlock;        // threads per workgroup of the dense-batch and scan kernels: 64, 128 or 256
+    int dense_unroll = kDenseUnroll;        // items (64 k-mers = 2 dwordx4 per lane) in flight per wave: 1, 2 or 4
+    int scan_unroll = kScanUnroll;         // rounds (1 KiB loads) in flight per wave: 1, 2 or 4
     int scan_impl = 8;           // the one-hot contraction on the matrix cores: 8 = in the fused count's tiling (kmer_scan_seg_mfma_kernel: four MFMAs per 1024 windows + two v_permlane32_swap, ships:
                                  // profiles/r05_ab_scan_seg.txt), 7 = the natural-layout tiling (kmer_scan_mfma_kernel: six MFMAs, round 5's first form, profiles/r05_ab_scan_mfma*.txt);
                                  // the bit-plane forms (v_alignbit + v_bcnt per window, VALU-issue bound): 1 = line-aligned rounds of 1024 windows, two-LUT planes + scalar halo
                                  // (kmer_scan2_kernel GEN 1: shipped in round 4), 6 = the same with rounds 2-3's plane build (GEN 0), 0 = rounds of 992 windows (kmer_scan_kernel),
                                  // 2 / 3 / 4 / 5 = kmer_scan3_kernel (a wave owns 12 / 20 / 16 / 32 consecutive rounds: slower, profiles/r04_ab_scan3.txt)
-    int scan_mfma_unroll = 4;    // kmer_scan_mfma_kernel: consecutive 1 KiB rounds per wave trip: 2, 3 or 4 (profiles/r05_ab_scan_trip_length.txt)
+    int scan_mfma_unroll = kScanSegRounds;    // kmer_scan_mfma_kernel: consecutive 1 KiB rounds per wave trip: 2, 3 or 4 (profiles/r05_ab_scan_trip_length.txt)
     int scan_mfma_grid = 4;      // ... bounded-grid form (scan_mfma_persist 1): workgroups per CU (profiles/r05_ab_scan_grid*.txt: flatter from idle, 2.5-5 % slower settled)
     int scan_mfma_policy = 3;    // ... bit 0: nt loads (stores are nt)
     int scan_mfma_shift = 4;     // ... the shifted operands: 0 = two more global loads, 1 = the bytes through a wave-private LDS strip, 2 = DPP + scalar halo,
                                  //     3 = the one-hot operands through the strip, 4 = ... with the lane's own operands kept in registers (ships)
-    int scan_mfma_block = 64;        // ... kmer_scan_seg_mfma_kernel: threads per workgroup: 64 (one wave: ships), 128, 256 (trips of four rounds only)
+    int scan_mfma_block = kScanSegBlock;    // ... kmer_scan_seg_mfma_kernel: threads per workgroup: 64 (one wave: ships), 128, 256 (trips of four rounds only)
     int scan_mfma_ch3 = 0;           // ... the shipped scan's tiling with three channels per base instead of four (kmer_scan_seg3_mfma_kernel: three MFMAs per 1024 windows), evidence build
     int scan_mfma_match = 0;         // ... the query's side of the product: 0 = 1.0 on the channels that DIFFER from the query's base (three of four), 1 = -1.0 on the one that EQUALS it, counted down from k (a third of the non-zero entries)
     int scan_mfma_count_emit = 2;    // ... its own tiling's results -> count: 0 = v_cmp + s_bcnt1 per register, 1 = threshold fields inside the product (v_or3 + v_bitop3 + v_bcnt per four windows), 2 = 1 + the next trip loaded into the same registers (ships)
     int scan_mfma_count_form = 2;    // ... the fused count: 2 = segments of 32 windows with three channels per base (kmer_count3_mfma_kernel: 3 MFMAs per 1024 windows, ships), 1 = four channels (kmer_count_mfma_kernel: 4 MFMAs), 0 = the scan's natural-layout tiling (6)
-    int scan_mfma_count_rounds = 4;  // kmer_count3_mfma_kernel / kmer_count_mfma_kernel: rounds per trip (2, 3, 4); the four-channel form shipped with 3 (six waves share a SIMD)
-    int scan_mfma_count_grid = 12;   // ... workgroups per CU (the four-channel form shipped with 18: three generations of the six resident ones)
+    int scan_mfma_count_rounds = kCountRounds;  // kmer_count3_mfma_kernel / kmer_count_mfma_kernel: rounds per trip (2, 3, 4); the four-channel form shipped with 3 (six waves share a SIMD)
+    int scan_mfma_count_grid = kCountGrid;   // ... workgroups per CU (the four-channel form shipped with 18: three generations of the six resident ones)
     int scan_mfma_count_persist = 1; // ... the fused count: 1 = a resident grid (ships), 0 = one trip per wave (two atomics per workgroup at the accumulator and the ticket)
     int scan_mfma_persist = 0;   // ... 1 = a resident grid walks the trips with register prefetch, 0 = one trip per wave
     int scan_mfma_pack = 1;      // ... f32 -> u8: 0 = v_cvt_pk_u8_f32, 1 = 2^23 bias + row scales (copied), 2 = ... (bias by a seventh instruction)
     int hdist_tiled = 0;         // bulk hdist: 1 = grid-stride at tile granularity (16 KiB of each operand per workgroup trip), 0 = at thread granularity
     int hdist_words_impl = 1;    // many-pair / one-query hdist: 1 = coalesced loads + bpermute for whole 256-word tiles, 0 = four contiguous words per lane
-    int fixed_stream = 1;        // encode_fixed (back-to-back reads): 1 = cut the tile's 2-bit stream
+    int fixed_stream = kFixedStream;        // encode_fixed (back-to-back reads): 1 = cut the tile's 2-bit stream
     int fixed_dec_strip = 2;     // decode_fixed (back-to-back reads): 0 = byte scatter, 1 = bit strip with per-lane 64-bit positions, 2 = the plan decode's tile body with arithmetic lookups
     int owner_est = 3;           // block_owner_kernel's first guess: 0 = 128-bit division, 1 = double, 2 = exact 0.64 fixed-point multiply-high, 3 = 2 or 0 by average sequence length
     int batch_tables_impl = 1;   // table-driven ragged batches: 1 = one asynchronous pass emits the layout plan into context scratch, then the plan kernels; 0 = tile records + O(1) lookup kernels
     int batch_host_plan = 1;     // host-pointer ragged-batch calls build a layout plan (bitnuc_batch_plan) and use the plan kernels (0: the table-driven form)
     int plan_dec_lines = 0;      // plan decode: 0 = word tiles with shared edge lines (decode_batch_plan_kernel: ships), 1 = line-owning, 2 = chunk-owning tiles (decode_batch_plan_lines_kernel: slower, profiles/r04_ab_plan_lines.txt)
-    int plan_tiles = 1;          // decode_batch_plan_kernel: consecutive tiles per wave trip (1, 2 or 4)
-    int plan_store = 2;          // decode_batch_plan_kernel's whole-chunk store policy: 0 nt, 1 plain, 2 plain on the shared edge lines + nt elsewhere
-    int plan_enc_block = 256;    // threads per workgroup of the plan encode (64, 128, 256)
-    int plan_enc_tiles = 1;      // encode_batch_plan_kernel: consecutive tiles per wave trip (1, 2 or 4)
+    int plan_tiles = kPlanTiles;          // decode_batch_plan_kernel: consecutive tiles per wave trip (1, 2 or 4)
+    int plan_store = kPlanStore;          // decode_batch_plan_kernel's whole-chunk store policy: 0 nt, 1 plain, 2 plain on the shared edge lines + nt elsewhere
+    int plan_enc_block = kPlanEncBlock;    // threads per workgroup of the plan encode (64, 128, 256)
+    int plan_enc_tiles = kPlanEncTiles;      // encode_batch_plan_kernel: consecutive tiles per wave trip (1, 2 or 4)
     int plan_enc_abl = 0;        // timing-only ablations of the plan encode's loads (see plan_enc_issue)
     int batch_abl = 0;           // timing-only ablation mask of the second table-driven formulation (tools/ab_batch_ablate.py)
 };
@@ -203,14 +223,17 @@ inline bool on_host(const bitnuc_ctx *c, size_t n, bool decode = false) {
 
 // Alternative formulations that lost their A/B (profiles/) stay in the source as evidence, but only the evidence build
 // (-DBITNUC_SWEEP_VARIANTS, libbitnuc_hip_sweep.so: tools/ and the variant tests) instantiates them; in the product a
-// set_variant() to anything but the shipped value returns -2 and changes nothing.
+// set_variant() to anything but the shipped value returns -2 and changes nothing.  BITNUC_EVIDENCE(...) is its argument in
+// the evidence build and nothing in the product: the one hook line of each launcher (see the top of this file).
 #ifdef BITNUC_SWEEP_VARIANTS
+#define BITNUC_EVIDENCE(...) __VA_ARGS__
 constexpr bool kEvidenceBuild = true;
 inline const SweepKnobs &knobs(const bitnuc_ctx *c) { return c->sweep; }
 #else
+#define BITNUC_EVIDENCE(...)
 constexpr bool kEvidenceBuild = false;
 constexpr SweepKnobs kShipped{};
-inline constexpr const SweepKnobs &knobs(const bitnuc_ctx *) { return kShipped; } // a constant: the launch code's branches on it fold away
+inline constexpr const SweepKnobs &knobs(const bitnuc_ctx *) { return kShipped; } // set_sweep_key's answer to a query
 #endif
 
 // ---- cross-unit entry points that are not part of the C ABI ------------------------------------------------------------

@@ -23,7 +23,7 @@
 // Common to both: a wave round is 1 KiB of windows at a 1 KiB aligned offset; lane l loads its natural 16 bytes at 16 l, expands them ONCE and writes the operands to
 // a wave-private LDS strip, from which lane (n = l & 31, h = l >> 5) reads back the 16-byte operand of each K-step (aligned, conflict-free: even and odd 16-byte
 // groups live in regions 16 banks apart).  A trip is U consecutive rounds + the 32-byte halo after them.  The query's side of the product is built on the host
-// (kmer.hip) and passed BY VALUE in the kernel arguments (a hipGraph node keeps its own copy), together with the values the accumulators start at.
+// (scan_mfma_host.h) and passed BY VALUE in the kernel arguments (a hipGraph node keeps its own copy), together with the values the accumulators start at.
 //
 // Packing 16 f32 results into 16 bytes costs 2 instructions per 4 windows instead of 4: the accumulator starts at 2^23 (the integer d then sits in the low mantissa
 // bits) and A's rows carry the E8M0 block scale 2^(8 (m & 3)) for m & 3 < 3, so three results OR together into bytes 0-2 and a v_perm drops the fourth into byte 3.
@@ -35,6 +35,7 @@
 #pragma once
 #include "device_prims.h"
 #include "kmer_device.h" // wave_shl1
+#include "scan_mfma_host.h"
 
 namespace bitnuc_dev {
 
@@ -112,8 +113,7 @@ __device__ __forceinline__ uint32_t scan_tail_windows(const uint8_t *__restrict_
 // windows cover are 4 K-steps of 16, nothing multiplies zeros: 4 MFMAs per 1024 windows.  Lane (n, h) of K-step j needs the one-hot operand of bases
 // 32 n + 16 j + 8 h .. + 8: half h of the 16-byte group 2 n + j -- not the lane's own group, so all four operands come from the strip, which keeps the halves
 // and the even / odd groups in separate regions (a K-step's 32 reads are then 32 consecutive 16-byte entries: conflict-free).
-// w[delta + 8][4 j + i]: dword i of K-step j for the row with delta = m - 8 h (i = position - m only depends on it), built on the host (kmer.hip: count_mfma_table).
-struct CountMfmaTable { uint32_t w[40][16]; float c[4]; }; // c[r & 3]: where result register r's accumulator starts
+// w[delta + 8][4 j + i]: dword i of K-step j for the row with delta = m - 8 h (i = position - m only depends on it): CountMfmaTable, scan_mfma_host.h.
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // The distance bytes.  Lane (n, h) ends up holding windows 32 n + 8 q + 4 h + i (q = r >> 2, i = r & 3), i.e. after the 2^23-bias pack one dword per q with four
@@ -223,7 +223,7 @@ kmer_scan_seg_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n,
 // CU's four SIMDs); every partial sum is an integer below 2^24: exact.  tau >= k (no window can miss) gets an all-zero table.
 // A bounded grid (one arrival per workgroup at the accumulator's ticket) whose waves walk trips; the NEXT trip's loads are issued as soon as this trip's bytes
 // are in the strip, into the same registers, and fly during the matrix phase.
-struct Count3MfmaTable { uint32_t w[64][12]; float c[4]; };
+// The query's operand: Count3MfmaTable, scan_mfma_host.h.
 
 // 16 bases (four ASCII dwords) -> their 16 (A, C) bytes and their 16 G nibbles (the three-channel operands)
 __device__ __forceinline__ void expand3(const u32x4 &x, u32x4 &ac, uint32_t &g0, uint32_t &g1) {

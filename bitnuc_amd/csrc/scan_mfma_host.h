@@ -1,0 +1,109 @@
+// scan_mfma_host.h -- the host side of the matrix-core scan and count (scan_mfma_device.h): the query's operand tables the kernels take
+// as arguments, and the query's bit-planes of the bit-plane scan.  Plain C++ (no HIP): tests/c/host_sanitize.cpp runs the builders
+// under AddressSanitizer / UndefinedBehaviorSanitizer.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+
+namespace bitnuc_dev {
+struct CountMfmaTable { uint32_t w[40][16]; float c[4]; }; // c[r & 3]: where result register r's accumulator starts
+struct Count3MfmaTable { uint32_t w[64][12]; float c[4]; };
+} // namespace bitnuc_dev
+
+namespace bitnuc_host {
+using bitnuc_dev::CountMfmaTable;
+using bitnuc_dev::Count3MfmaTable;
+
+// de-interleave a packed query into its two bit-planes (bit i = low / high code bit of base i)
+inline void query_planes(uint64_t query, size_t k, uint32_t *ql, uint32_t *qh) {
+    *ql = *qh = 0;
+    for (unsigned i = 0; i < k; ++i) {
+        *ql |= (uint32_t)((query >> (2 * i)) & 1) << i;
+        *qh |= (uint32_t)((query >> (2 * i + 1)) & 1) << i;
+    }
+}
+
+// The query's operand of the segment tiling with four channels per base (CountMfmaTable below; the shipped scan, the four-channel count of the
+// evidence build): row m of K-block h only depends on delta = m - 8 h.
+// thresholded (kmer_count_mfma_kernel's EMIT 1, 2): result register r (rows with m & 3 = r & 3 = j) must end at 2^23 + (32 + tau - d) 2^(6 j) for j < 3 and at
+// 2 d - 2 tau - 1 for j = 3 (scan_mfma_device.h).  match = false: the entries mark the channels that DIFFER from the query's base (-1.0 for j < 3, +1.0 for j = 3)
+// and the accumulators start at 2^23 + (32 + tau) 2^(6 j) / -(2 tau + 1).  match = true: they mark the channel that EQUALS it (+1.0 / -1.0: a third of the non-zero
+// entries), d = k - matches, and the accumulators start at 2^23 + (32 + tau - k) 2^(6 j) / 2 k - 2 tau - 1.  A threshold no window can miss (tau >= k) gets the
+// all-zero table and the start values of tau = k: every field reads 32, every j = 3 result -1.
+inline void count_mfma_table(uint64_t query, size_t k, CountMfmaTable *t, bool thresholded = false, unsigned tau = 0, bool match = false) {
+    uint8_t lo[128], hi[128]; // [32 + i]
+    memset(lo, 0, sizeof lo);
+    memset(hi, 0, sizeof hi);
+    const bool all = thresholded && tau >= k;
+    for (size_t i = 0; i < k && !all; ++i) {
+        const unsigned q = (unsigned)((query >> (2 * i)) & 3);
+        if (thresholded && match) {
+            lo[32 + i] = (uint8_t)((q == 0 ? 0x02 : 0) | (q == 1 ? 0x20 : 0));
+            hi[32 + i] = (uint8_t)((q == 2 ? 0x02 : 0) | (q == 3 ? 0x20 : 0));
+        } else {
+            lo[32 + i] = (uint8_t)((q != 0 ? 0x02 : 0) | (q != 1 ? 0x20 : 0));
+            hi[32 + i] = (uint8_t)((q != 2 ? 0x02 : 0) | (q != 3 ? 0x20 : 0));
+        }
+    }
+    const unsigned te = all ? (unsigned)k : tau; // tau < k <= 32 otherwise
+    for (int j = 0; j < 4; ++j) {
+        if (!thresholded) t->c[j] = 0.f;
+        else if (j < 3) t->c[j] = 8388608.f + (float)((match ? 32u + te - (unsigned)k : 32u + te) << (6 * j));
+        else t->c[j] = match ? (float)(2 * (int)k - 2 * (int)te - 1) : -(float)(2 * te + 1);
+    }
+    if (all) for (int j = 0; j < 3; ++j) t->c[j] = 8388608.f + (float)(32u << (6 * j)), t->c[3] = -1.f;
+    for (int d = -8; d < 32; ++d)
+        for (int j = 0; j < 4; ++j)
+            for (int i = 0; i < 4; ++i) {
+                const int p0 = 16 * j + 4 * (i >> 1); // position of byte 0 of this dword, relative to 32 n + 8 h
+                const uint8_t *src = (i & 1) ? hi : lo;
+                uint32_t w = 0;
+                for (int b = 0; b < 4; ++b) w |= (uint32_t)src[32 + p0 + b - d] << (8 * b);
+                // the sign bit of every non-zero nibble (0b0010 -> 0b1010) where the row counts DOWN: j < 3 with differing channels, j = 3 with equal ones
+                if (thresholded && ((((d + 8) & 3) != 3) != match)) w |= w << 2;
+                t->w[d + 8][4 * j + i] = w;
+            }
+}
+
+// ... and of the three-channel count (Count3MfmaTable below): per lane (row m = lane & 31, K-block h = lane >> 5) and K-step, the 32 nibbles that meet
+// the lane's operand -- K-steps 0 / 1: the (A, C) bytes of positions 32 s + 16 h + b; K-step 2: the G nibbles of positions 32 h .. + 31, byte b holding positions 8 (b >> 2) + (b & 3) and that + 4.
+// d = #(q_i != T) + sum over the window of v(q_i, channel) x[channel], v = -1 on channel q for q in {A, C, G}, +1 on all three for q = T; rows with m & 3 < 3 carry
+// -v and start at 2^23 + (32 + tau - #(q_i != T)) 2^(6 j) (they end at 32 + tau - d), rows with m & 3 = 3 carry v at scale 2 and start at 2 #(q_i != T) - 2 tau - 1.
+// distance = true (evidence build's three-channel scan): every row carries v and starts at 2^23 + #(q_i != T) 2^(8 j) (j = 3: 2^23 + #): the product is d itself.
+inline void count3_mfma_table(uint64_t query, size_t k, unsigned tau, Count3MfmaTable *t, bool distance = false) {
+    const bool all = !distance && tau >= k;
+    unsigned non_t = 0;
+    for (size_t i = 0; i < k; ++i) non_t += ((query >> (2 * i)) & 3) != 3;
+    auto nibble = [&](int m, int p, unsigned ch) -> uint32_t {
+        const int i = p - m;
+        if (all || i < 0 || i >= (int)k) return 0u;
+        const unsigned q = (unsigned)((query >> (2 * i)) & 3);
+        const int v = q == 3 ? 1 : (ch == q ? -1 : 0);
+        const int e = distance || (m & 3) == 3 ? v : -v;
+        return e == 0 ? 0u : e > 0 ? 0x2u : 0xAu;
+    };
+    for (int lane = 0; lane < 64; ++lane) {
+        const int m = lane & 31, h = lane >> 5;
+        for (int s = 0; s < 3; ++s)
+            for (int i = 0; i < 4; ++i) {
+                uint32_t w = 0;
+                for (int bb = 0; bb < 4; ++bb) {
+                    const int b = 4 * i + bb;
+                    const int gp = 32 * h + 8 * (b >> 2) + (b & 3); // K-step 2, byte b of the lane's 16: bases gp (low nibble) and gp + 4 (high nibble) of positions 32 h .. + 31
+                    const uint32_t lo = s < 2 ? nibble(m, 32 * s + 16 * h + b, 0) : nibble(m, gp, 2);
+                    const uint32_t hi = s < 2 ? nibble(m, 32 * s + 16 * h + b, 1) : nibble(m, gp + 4, 2);
+                    w |= (lo | hi << 4) << (8 * bb);
+                }
+                t->w[lane][4 * s + i] = w;
+            }
+    }
+    if (distance) {
+        for (int j = 0; j < 4; ++j) t->c[j] = 8388608.f + (float)(non_t << (j == 3 ? 0 : 8 * j));
+        return;
+    }
+    for (int j = 0; j < 3; ++j) t->c[j] = 8388608.f + (float)((all ? 32u : 32u + tau - non_t) << (6 * j));
+    t->c[3] = all ? -1.f : (float)(2 * (int)non_t - 2 * (int)tau - 1);
+}
+
+} // namespace bitnuc_host

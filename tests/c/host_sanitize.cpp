@@ -4,11 +4,14 @@
 //                           so that any over-read / over-write is caught, checked against the oracle;
 //   * csrc/host_pool.h   -- the staging pool of the pipelined host-pointer path (mutex + two condition variables, a blocking
 //                           and an asynchronous job form), hammered in the call pattern of encode_pipelined / decode_pipelined:
-//                           sizes around the 1 MiB serial threshold and the 4096-byte slice edges, 1..9 threads.
-// Built twice by tests/test_sanitizers.py: -fsanitize=address,undefined and -fsanitize=thread.  Neither header needs HIP.
+//                           sizes around the 1 MiB serial threshold and the 4096-byte slice edges, 1..9 threads;
+//   * csrc/scan_mfma_host.h -- the query operand tables of the matrix-core scan and count (count_mfma_table, count3_mfma_table),
+//                           built into exact-size heap objects for every k, the threshold edges and random queries.
+// Built twice by tests/test_sanitizers.py: -fsanitize=address,undefined and -fsanitize=thread.  No header needs HIP.
 // The reference's single-thread contract is src/utils/unpacking/avx.rs:37 (its only static); these threads only move bytes.
 #include "../../bitnuc_amd/csrc/host_pool.h"
 #include "../../bitnuc_amd/csrc/host_word.h"
+#include "../../bitnuc_amd/csrc/scan_mfma_host.h"
 #include "../../oracle/bitnuc_oracle.h"
 
 #include <atomic>
@@ -161,8 +164,45 @@ static void task_thread_checks() {
     { TaskThread idle; } // never used
 }
 
+// The table builders index the query's planes at src[32 + p0 + b - d] (d = -8 .. 31) and the lanes' operand positions: every k, the
+// threshold's edges and random queries, into exact-size heap objects.  A threshold no window can miss (tau >= k) gives all-zero words and
+// the start values of tau = k: 2^23 + 32 * 2^(6 j) for j < 3, -1 for j = 3.
+static void table_checks() {
+    using bitnuc_host::CountMfmaTable;
+    using bitnuc_host::Count3MfmaTable;
+    CountMfmaTable *t = static_cast<CountMfmaTable *>(malloc(sizeof(CountMfmaTable)));
+    Count3MfmaTable *t3 = static_cast<Count3MfmaTable *>(malloc(sizeof(Count3MfmaTable)));
+    for (size_t k = 1; k <= 32; ++k) {
+        const unsigned taus[] = {0u, 1u, (unsigned)k - 1, (unsigned)k, (unsigned)k + 1, 0xFFFFFFFFu};
+        for (int qi = 0; qi < 8; ++qi) {
+            const uint64_t query = qi == 0 ? 0 : qi == 1 ? ~0ull : (((uint64_t)rnd() << 32) | rnd());
+            uint32_t ql, qh;
+            bitnuc_host::query_planes(query, k, &ql, &qh);
+            for (size_t i = 0; i < k; ++i) CHECK(((ql >> i) & 1) == ((query >> (2 * i)) & 1) && ((qh >> i) & 1) == ((query >> (2 * i + 1)) & 1));
+            bitnuc_host::count_mfma_table(query, k, t); // the scan's operand: no threshold, accumulators from 0
+            for (int j = 0; j < 4; ++j) CHECK(t->c[j] == 0.f);
+            for (unsigned tau : taus)
+                for (int match = 0; match < 2; ++match) {
+                    bitnuc_host::count_mfma_table(query, k, t, true, tau, match != 0);
+                    bitnuc_host::count3_mfma_table(query, k, tau, t3);
+                    if (tau < k) continue;
+                    for (int j = 0; j < 4; ++j) {
+                        const float want = j < 3 ? 8388608.f + (float)(32u << (6 * j)) : -1.f;
+                        CHECK(t->c[j] == want && t3->c[j] == want);
+                    }
+                    for (size_t r = 0; r < 40; ++r) for (uint32_t w : t->w[r]) CHECK(w == 0);
+                    for (size_t r = 0; r < 64; ++r) for (uint32_t w : t3->w[r]) CHECK(w == 0);
+                }
+            bitnuc_host::count3_mfma_table(query, k, 0u, t3, true); // the evidence build's three-channel scan
+        }
+    }
+    free(t);
+    free(t3);
+}
+
 int main() {
     host_word_checks();
+    table_checks();
     task_thread_checks();
     for (int t = 1; t <= 9; t += 2) pool_checks(t, t);
     pool_checks(8, 3);

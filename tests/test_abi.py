@@ -142,12 +142,17 @@ def test_product_library_holds_no_evidence_kernels():
     # resident grid); their other operand / pack / trip / tiling / channel forms are evidence
     assert set(re.findall(r"kmer_scan_seg_mfma_kernel<([^>]*)>", product)) == {"3, 4, 64"} and "kmer_scan_mfma_kernel<" not in product
     assert set(re.findall(r"kmer_count3_mfma_kernel<([^>]*)>", product)) == {"4, true"} and "kmer_count_mfma_kernel<" not in product
+    # the sliding kernels ship with nt stores (dense_policy 3) and one round per trip, the bulk hdist at thread granularity (hdist_tiled 0);
+    # their other forms are evidence
+    assert set(re.findall(r"kmer_slide_kernel<([^>]*)>", product)) == {f"{s}, true, 1" for s in (1, 2, 4, 8, 16)}
+    assert set(re.findall(r"\bhdist_kernel<([^>]*)>", product)) == {"false"}
     leaked = [n for n in names if n + "<" in product or n + "(" in product]
     assert not leaked, leaked
     if os.path.exists(build.LIB_SWEEP) and not build.is_stale(build.LIB_SWEEP):
         sweep = subprocess.run(["nm", "-C", build.LIB_SWEEP], capture_output=True, text=True).stdout
         missing = [n for n in names if n not in sweep]
         assert not missing, missing
+        assert "kmer_slide_kernel<16, false, 1>" in sweep and "hdist_kernel<true>" in sweep
 
 
 def test_no_oracle_in_product():
