@@ -286,6 +286,26 @@ class Context:
             _raise(err)
         return out
 
+    def kmer_hdist_scan_packed(self, words, n_bases, k, query):
+        """kmer_hdist_scan of the packed sequence `words` holding `n_bases` bases, without decoding it -> np.uint8 distances."""
+        w = _as_u64(words)
+        n = int(n_bases)
+        nwin = n - k + 1 if (n >= k and k > 0) else 0
+        out = np.empty(nwin, dtype=np.uint8)
+        err = L.BitnucErr()
+        if self._lib.bitnuc_kmer_hdist_scan_packed(self._h, _ptr(w), w.size, n, int(k), C.c_uint64(query), _ptr(out), C.byref(err)) != L.OK:
+            _raise(err)
+        return out
+
+    def kmer_hdist_count_packed(self, words, n_bases, k, query, tau):
+        """Number of windows of the packed sequence `words` (`n_bases` bases) with Hamming distance <= tau to the query."""
+        w = _as_u64(words)
+        out = C.c_uint64(0)
+        err = L.BitnucErr()
+        if self._lib.bitnuc_kmer_hdist_count_packed(self._h, _ptr(w), w.size, int(n_bases), int(k), C.c_uint64(query), int(tau), C.byref(out), C.byref(err)) != L.OK:
+            _raise(err)
+        return out.value
+
     # -- analysis on packed words (src/utils/analysis.rs, hamming/scalar.rs) ------------------
     def base_counts(self, words, n_bases):
         """[A, C, G, T] counts of a packed sequence (BaseCount::base_counts, analysis.rs:23-39)."""
@@ -486,6 +506,14 @@ class Context:
     def kmer_hdist_count_dev(self, d_ref, n, k, query, tau, d_count):
         """Number of windows with Hamming distance <= tau to the query (fused scan, no distance bytes written) -> *d_count (u64)."""
         self._call_dev(self._lib.bitnuc_kmer_hdist_count_dev, _dev_ptr(d_ref), int(n), int(k), C.c_uint64(query), int(tau), _dev_ptr(d_count))
+
+    def kmer_hdist_scan_packed_dev(self, d_words, n_words, n, k, query, d_dist):
+        """The scan on packed words in device memory (8-byte aligned) -> n - k + 1 distance bytes at d_dist (any byte offset)."""
+        self._call_dev(self._lib.bitnuc_kmer_hdist_scan_packed_dev, _dev_ptr(d_words), int(n_words), int(n), int(k), C.c_uint64(query), _dev_ptr(d_dist))
+
+    def kmer_hdist_count_packed_dev(self, d_words, n_words, n, k, query, tau, d_count):
+        """The fused count on packed words in device memory -> *d_count (u64)."""
+        self._call_dev(self._lib.bitnuc_kmer_hdist_count_packed_dev, _dev_ptr(d_words), int(n_words), int(n), int(k), C.c_uint64(query), int(tau), _dev_ptr(d_count))
 
     def hdist_dev(self, d_a, na, d_b, nb, n_bases, d_result):
         self._call_dev(self._lib.bitnuc_hdist_dev, _dev_ptr(d_a), int(na), _dev_ptr(d_b), int(nb), int(n_bases), _dev_ptr(d_result))
@@ -775,6 +803,10 @@ def as_2bit_batch(kmers, k, stride=None, count=None):
 
 def kmer_hdist_scan(ref, k, query):
     return default_context().kmer_hdist_scan(ref, k, query)
+
+
+def kmer_hdist_scan_packed(words, n_bases, k, query):
+    return default_context().kmer_hdist_scan_packed(words, n_bases, k, query)
 
 
 def split_packed(ebuf, slen, idx, lbuf, rbuf, canonical=False):

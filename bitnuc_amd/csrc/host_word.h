@@ -134,4 +134,24 @@ static inline uint32_t hdist_small(const uint64_t *a, const uint64_t *b, size_t 
     return total;
 }
 
+// the window of k <= 32 bases starting at base j of a packed sequence (base i at bits 2 (i mod 32) of words[i / 32]); bits above 2 k are junk
+static inline uint64_t packed_window(const uint64_t *words, size_t j, size_t k) {
+    const unsigned sh = 2u * (unsigned)(j & 31);
+    uint64_t x = words[j >> 5] >> sh;
+    if ((j & 31) + k > 32) x |= words[(j >> 5) + 1] << (64 - sh);
+    return x;
+}
+
+// the sliding Hamming scan of a packed sequence below the cutoff: dist[j] = hdist_scalar(window j, query, k), j in 0 .. n - k + 1 (1 <= k <= min(n, 32))
+static inline void kmer_hdist_scan_packed_small(const uint64_t *words, size_t n, size_t k, uint64_t query, uint8_t *dist) {
+    for (size_t j = 0; j + k <= n; ++j) dist[j] = (uint8_t)hdist_word(packed_window(words, j, k), query, k);
+}
+
+// ... and its fused count: the number of windows with distance <= tau
+static inline uint64_t kmer_hdist_count_packed_small(const uint64_t *words, size_t n, size_t k, uint64_t query, unsigned tau) {
+    uint64_t hits = 0;
+    for (size_t j = 0; j + k <= n; ++j) hits += hdist_word(packed_window(words, j, k), query, k) <= tau;
+    return hits;
+}
+
 } // namespace bitnuc_host

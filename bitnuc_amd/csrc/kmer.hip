@@ -1,10 +1,11 @@
 // kmer.hip -- k-mer compositions of the hot path behind the C ABI (include/bitnuc_hip.h): batched as_2bit over many
 // <= 32-mers (BASELINE config 3, README.md:52-56), every window of a sequence (src/lib.rs:170-173), the sliding pack +
 // Hamming scan (config 5: packing/mod.rs:80-110 o hamming/scalar.rs:11-48) and bulk hdist (hamming/multi.rs:121-160).
-// Kernels: kmer_device.h; config 5 on the matrix cores: scan_mfma_device.h.
+// Kernels: kmer_device.h; config 5 on the matrix cores: scan_mfma_device.h; the same scan and count on packed words: scan_packed_device.h.
 #include "runtime.h"
 #include "kmer_device.h"
 #include "scan_mfma_device.h"
+#include "scan_packed_device.h"
 #include "scan_mfma_host.h"
 #include "host_word.h"
 #include "host_pipe.h"
@@ -192,6 +193,50 @@ hipError_t launch_count(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, u
     if (al) return count3_t<kCountRounds>(c, ref, n, k, query, tau, res, slot, kCountGrid);
     // unaligned reference pointer: the bit-plane scan with unaligned 16-byte loads
     return count_scan2_t<false, false, 1, 0>(c, ref, n, k, query, tau, res, slot);
+}
+
+// ---- the scan and its fused count on packed words (scan_packed_device.h).  d_words is 8-byte aligned (checked by the callers); at 8 mod 16 the rounds
+// start one word later and the tail threads take the first 32 windows (skip = 32), so both alignments run the same kernel.
+hipError_t launch_scan_packed(bitnuc_ctx *c, const uint64_t *words, size_t n, size_t k, uint64_t query, uint8_t *dist) {
+    PackedScanTable t;
+    scan_packed_table(query, k, &t);
+    const unsigned skip = aligned16(words) ? 0u : 32u;
+    const unsigned long long nr = n > skip ? n - skip : 0;
+    const unsigned long long rounds = nr >= 1056 ? (nr - 32) >> 10 : 0;
+    packed_scan_mfma_kernel<<<(unsigned)(rounds / 4 + 1), kPackedBlockScan, 0, c->stream>>>(words, n, skip, (unsigned)k, query, dist, t);
+    return hipGetLastError();
+}
+
+// a bounded grid of kCountGrid workgroups per CU, as the ASCII count; its own accumulator and ticket (d_acc[6], d_tickets[3])
+hipError_t launch_count_packed(bitnuc_ctx *c, const uint64_t *words, size_t n, size_t k, uint64_t query, unsigned tau, unsigned long long *res) {
+    Count3MfmaTable t;
+    count3_packed_table(query, k, tau, &t);
+    const unsigned skip = aligned16(words) ? 0u : 32u;
+    const unsigned long long nr = n > skip ? n - skip : 0;
+    const unsigned long long rounds = nr >= 1056 ? (nr - 32) >> 10 : 0;
+    const unsigned long long want = rounds / ((kBlock / 64) * 4ull) + 1, cap = (unsigned long long)c->num_cu * (unsigned)kCountGrid;
+    packed_count3_mfma_kernel<<<(unsigned)(want < cap ? want : cap), kBlock, 0, c->stream>>>(words, n, skip, (unsigned)k, query, tau, res, c->d_acc + 6, c->d_tickets + 3, t);
+    return hipGetLastError();
+}
+
+// the packed calls' argument checks, in the header's order: k, the word count, no windows (*no_windows), then pointers
+int check_packed(const void *words, size_t n_words, size_t n, size_t k, bool *no_windows, bitnuc_err *err) {
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
+    *no_windows = k == 0 || n < k;
+    if (*no_windows) return BITNUC_OK;
+    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    return BITNUC_OK;
+}
+
+// host-pointer packed calls: chunks of whole words; chunk w0 holds the windows [32 w0, 32 (w0 + cw)) and the k - 1 bases after them (one more word)
+constexpr size_t kPackedChunkWords = kHostChunk / 32;
+struct PackedChunk { size_t w0, words, bases, nwin; };
+inline PackedChunk packed_chunk(size_t w0, size_t n, size_t k) {
+    const size_t first = 32 * w0, nwin = n - k + 1;
+    const size_t w = nwin - first < 32 * kPackedChunkWords ? nwin - first : 32 * kPackedChunkWords;
+    const size_t bases = w + k - 1;
+    return PackedChunk{w0, words_for(bases), bases, w};
 }
 
 // ---- host-pointer k-mer calls through the pipelined staging of host_pipe.h ---------------------------------------------------
@@ -436,6 +481,83 @@ int bitnuc_hdist(bitnuc_ctx *c, const uint64_t *a, size_t na, const uint64_t *b,
         total += part; // u32 wrap-around like the reference's accumulator (multi.rs:130)
     }
     *out = total;
+    return BITNUC_OK;
+}
+
+int bitnuc_kmer_hdist_scan_packed_dev(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, uint64_t query, uint8_t *d_dist, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    bool none;
+    if (int st = check_packed(d_words, n_words, n, k, &none, err)) return st;
+    if (none) return BITNUC_OK;
+    if (!d_dist) return fail(err, BITNUC_UNSUPPORTED);
+    DeviceGuard g(c->device);
+    HIPCHK(launch_scan_packed(c, d_words, n, k, query, d_dist));
+    return BITNUC_OK;
+}
+
+int bitnuc_kmer_hdist_count_packed_dev(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *d_count,
+                                       bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    bool none;
+    if (int st = check_packed(d_words, n_words, n, k, &none, err)) return st;
+    if (!d_count || (reinterpret_cast<uintptr_t>(d_count) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    DeviceGuard g(c->device);
+    if (none) {
+        HIPCHK(hipMemsetAsync(d_count, 0, sizeof(uint64_t), c->stream));
+        return BITNUC_OK;
+    }
+    HIPCHK(launch_count_packed(c, d_words, n, k, query, tau, reinterpret_cast<unsigned long long *>(d_count)));
+    return BITNUC_OK;
+}
+
+int bitnuc_kmer_hdist_scan_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, uint64_t query, uint8_t *dist, bitnuc_err *err) {
+    clear_err(err);
+    bool none;
+    if (int st = check_packed(words, n_words, n, k, &none, err)) return st;
+    if (none) return BITNUC_OK;
+    if (!dist) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, n)) { bitnuc_host::kmer_hdist_scan_packed_small(words, n, k, query, dist); return BITNUC_OK; }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    if (int st = ensure_scratch(c, 0, (kPackedChunkWords + 1) * 8, err)) return st;
+    if (int st = ensure_scratch(c, 2, 32 * kPackedChunkWords, err)) return st;
+    for (size_t w0 = 0; 32 * w0 < n - k + 1; w0 += kPackedChunkWords) {
+        const PackedChunk ch = packed_chunk(w0, n, k);
+        HIPCHK(hipMemcpyAsync(c->scratch[0], words + w0, ch.words * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(launch_scan_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), ch.bases, k, query, c->scratch[2]));
+        HIPCHK(hipMemcpyAsync(dist + 32 * w0, c->scratch[2], ch.nwin, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    return BITNUC_OK;
+}
+
+int bitnuc_kmer_hdist_count_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *count,
+                                   bitnuc_err *err) {
+    clear_err(err);
+    bool none;
+    if (int st = check_packed(words, n_words, n, k, &none, err)) return st;
+    if (!count) return fail(err, BITNUC_UNSUPPORTED);
+    if (none) { *count = 0; return BITNUC_OK; }
+    if (on_host(c, n)) { *count = bitnuc_host::kmer_hdist_count_packed_small(words, n, k, query, tau); return BITNUC_OK; }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    if (int st = ensure_scratch(c, 0, (kPackedChunkWords + 1) * 8, err)) return st;
+    if (int st = ensure_scratch(c, 1, 64, err)) return st;
+    uint64_t total = 0;
+    for (size_t w0 = 0; 32 * w0 < n - k + 1; w0 += kPackedChunkWords) {
+        const PackedChunk ch = packed_chunk(w0, n, k);
+        HIPCHK(hipMemcpyAsync(c->scratch[0], words + w0, ch.words * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(launch_count_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), ch.bases, k, query, tau, reinterpret_cast<unsigned long long *>(c->scratch[1])));
+        uint64_t part = 0;
+        HIPCHK(hipMemcpyAsync(&part, c->scratch[1], 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        total += part;
+    }
+    *count = total;
     return BITNUC_OK;
 }
 

@@ -1,7 +1,7 @@
 // runtime.h -- internal interface between the translation units of libbitnuc_hip.so (not installed, not part of the C ABI):
 //   runtime.hip   the context: device + stream, error slots and their lifetime, scratch, knobs       (this header's functions)
 //   codec.hip     bulk encode / decode, the single-word API, the pipelined host-pointer path, probes  (codec_device.h)
-//   kmer.hip      k-mer batches, sliding scan (matrix cores), bulk hdist                             (kmer_device.h, scan_mfma_device.h)
+//   kmer.hip      k-mer batches, sliding scan (matrix cores, ASCII and packed input), bulk hdist     (kmer_device.h, scan_mfma_device.h, scan_packed_device.h)
 //   batch.hip     ragged / planned / fixed-length batches of reads                                   (batch_device.h)
 //   analysis.hip  base counts, many-pair hdist, split_packed                                         (analysis_device.h)
 //   comm.hip      RCCL all-gather of the packed words, xGMI link probe
@@ -129,8 +129,8 @@ struct bitnuc_ctx {
     bool scratch_in_graph[8] = {false, false, false, false, false, false, false, false}; // handed to a launch recorded into a hipGraph: never freed before the context
     std::vector<uint8_t *> retired_scratch; // ... outgrown since: alive until bitnuc_ctx_destroy (a replay still writes through them)
     uint32_t *d_sink = nullptr;
-    unsigned long long *d_acc = nullptr; // accumulators of the single-launch reductions, zero between launches: [0..2] base_counts C,G,T; [4] hdist (u32); [5] scan count
-    unsigned *d_tickets = nullptr;       // [0] base_counts, [1] hdist, [2] scan count: arrival counters, zero between launches
+    unsigned long long *d_acc = nullptr; // accumulators of the single-launch reductions, zero between launches: [0..2] base_counts C,G,T; [4] hdist (u32); [5] scan count; [6] packed scan count
+    unsigned *d_tickets = nullptr;       // [0] base_counts, [1] hdist, [2] scan count, [3] packed scan count: arrival counters, zero between launches
     unsigned reduce_blocks = 512;        // base_counts: resident grid (2 workgroups per CU)
     unsigned hdist_blocks = 256;         // bulk hdist: resident grid (1 workgroup per CU: 8 loads in flight per thread; profiles/r03_ab_hdist_grid.txt)
     // ---- knobs (bitnuc_ctx_set_variant): what an integrator may turn ----

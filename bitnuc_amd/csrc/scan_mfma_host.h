@@ -9,11 +9,13 @@
 namespace bitnuc_dev {
 struct CountMfmaTable { uint32_t w[40][16]; float c[4]; }; // c[r & 3]: where result register r's accumulator starts
 struct Count3MfmaTable { uint32_t w[64][12]; float c[4]; };
+struct PackedScanTable { uint32_t w[34][16]; float c[4]; }; // w[m - 2 h + 2]: the packed scan's rows only depend on m - 2 h (scan_packed_table)
 } // namespace bitnuc_dev
 
 namespace bitnuc_host {
 using bitnuc_dev::CountMfmaTable;
 using bitnuc_dev::Count3MfmaTable;
+using bitnuc_dev::PackedScanTable;
 
 // de-interleave a packed query into its two bit-planes (bit i = low / high code bit of base i)
 inline void query_planes(uint64_t query, size_t k, uint32_t *ql, uint32_t *qh) {
@@ -101,6 +103,69 @@ inline void count3_mfma_table(uint64_t query, size_t k, unsigned tau, Count3Mfma
     if (distance) {
         for (int j = 0; j < 4; ++j) t->c[j] = 8388608.f + (float)(non_t << (j == 3 ? 0 : 8 * j));
         return;
+    }
+    for (int j = 0; j < 3; ++j) t->c[j] = 8388608.f + (float)((all ? 32u : 32u + tau - non_t) << (6 * j));
+    t->c[3] = all ? -1.f : (float)(2 * (int)non_t - 2 * (int)tau - 1);
+}
+
+// ---- the packed scan and count (scan_packed_device.h): the same products, with the one-hot operand built from 2-bit codes ----------------------------
+// A packed dword holds 16 bases; s_t = (x >> 2 t) & 0x03030303 puts bases t, t + 4, t + 8, t + 12 into its byte lanes, and one v_perm LUT per
+// channel pair turns those codes into nibbles.  The K order below is the order that front end produces.
+
+// The scan (four channels per base).  Lane (row m, K-block h), K-step j, dword d, byte q: position 16 j + 4 q + 2 h + (d >> 1) of the segment (half h of a
+// 16-base group is its bases with (b & 3) >> 1 == h), low nibble channel A (d even) / G (d odd), high nibble C / T.  The query offset is that position
+// minus m, so a row only depends on m - 2 h: w[m - 2 h + 2].  Entries mark the channels that differ from the query's base; the accumulators start at the
+// 2^23 pack bias (kmer_scan_seg_mfma_kernel's pack).
+inline void scan_packed_table(uint64_t query, size_t k, PackedScanTable *t) {
+    for (int delta = -2; delta < 32; ++delta)
+        for (int j = 0; j < 4; ++j)
+            for (int d = 0; d < 4; ++d) {
+                uint32_t w = 0;
+                for (int q = 0; q < 4; ++q) {
+                    const int i = 16 * j + 4 * q + (d >> 1) - delta;
+                    if (i < 0 || i >= (int)k) continue;
+                    const unsigned qb = (unsigned)((query >> (2 * i)) & 3);
+                    const unsigned lo = (d & 1) ? 2u : 0u, hi = lo + 1u; // (A, C) or (G, T)
+                    w |= ((qb != lo ? 0x02u : 0u) | (qb != hi ? 0x20u : 0u)) << (8 * q);
+                }
+                t->w[delta + 2][4 * j + d] = w;
+            }
+    for (int j = 0; j < 4; ++j) t->c[j] = 8388608.f;
+}
+
+// The count (three channels per base: A, C, G one-hot, T = 0), as count3_mfma_table but in the packed K order.  K-steps 0 / 1: dword t, byte q holds
+// the (A, C) nibbles of position 16 (2 s + h) + 4 q + t; K-step 2: dword d, nibble p (byte p >> 1, high nibble when p is odd) holds the G nibble of
+// position 32 h + 16 (d >> 1) + 2 p + (d & 1).  Rows, signs, row scales and start values are count3_mfma_table's.
+inline void count3_packed_table(uint64_t query, size_t k, unsigned tau, Count3MfmaTable *t) {
+    const bool all = tau >= k;
+    unsigned non_t = 0;
+    for (size_t i = 0; i < k; ++i) non_t += ((query >> (2 * i)) & 3) != 3;
+    auto nibble = [&](int m, int p, unsigned ch) -> uint32_t {
+        const int i = p - m;
+        if (all || i < 0 || i >= (int)k) return 0u;
+        const unsigned q = (unsigned)((query >> (2 * i)) & 3);
+        const int v = q == 3 ? 1 : (ch == q ? -1 : 0);
+        const int e = (m & 3) == 3 ? v : -v;
+        return e == 0 ? 0u : e > 0 ? 0x2u : 0xAu;
+    };
+    for (int lane = 0; lane < 64; ++lane) {
+        const int m = lane & 31, h = lane >> 5;
+        for (int s = 0; s < 3; ++s)
+            for (int d = 0; d < 4; ++d) {
+                uint32_t w = 0;
+                for (int b = 0; b < 4; ++b) {
+                    uint32_t lo, hi;
+                    if (s < 2) {
+                        const int p = 16 * (2 * s + h) + 4 * b + d;
+                        lo = nibble(m, p, 0), hi = nibble(m, p, 1);
+                    } else {
+                        const int p = 32 * h + 16 * (d >> 1) + 4 * b + (d & 1); // nibble 2 b; nibble 2 b + 1 is two positions later
+                        lo = nibble(m, p, 2), hi = nibble(m, p + 2, 2);
+                    }
+                    w |= (lo | hi << 4) << (8 * b);
+                }
+                t->w[lane][4 * s + d] = w;
+            }
     }
     for (int j = 0; j < 3; ++j) t->c[j] = 8388608.f + (float)((all ? 32u : 32u + tau - non_t) << (6 * j));
     t->c[3] = all ? -1.f : (float)(2 * (int)non_t - 2 * (int)tau - 1);

@@ -66,3 +66,10 @@ class PackedSequence:
 
     def base_counts(self):
         return self._ctx.base_counts(self.data, self.length)
+
+    # the sliding Hamming scan and its fused count over the packed words themselves (never decoded)
+    def kmer_hdist_scan(self, k, query):
+        return self._ctx.kmer_hdist_scan_packed(self.data, self.length, k, query)
+
+    def kmer_hdist_count(self, k, query, tau):
+        return self._ctx.kmer_hdist_count_packed(self.data, self.length, k, query, tau)

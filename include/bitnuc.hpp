@@ -237,6 +237,19 @@ class Context {
         if (bitnuc_kmer_hdist_scan(ctx_, ref.ptr, ref.len, k, query, out.data(), &e) != BITNUC_OK) return NucleotideError::from_c(e);
         return out;
     }
+    // the same scan and its fused count on a packed sequence of n bases (as encode writes it), without decoding it
+    Result<std::vector<uint8_t>> kmer_hdist_scan_packed(Words words, size_t n, size_t k, uint64_t query) const {
+        std::vector<uint8_t> out((k && n >= k) ? n - k + 1 : 0);
+        bitnuc_err e;
+        if (bitnuc_kmer_hdist_scan_packed(ctx_, words.ptr, words.len, n, k, query, out.data(), &e) != BITNUC_OK) return NucleotideError::from_c(e);
+        return out;
+    }
+    Result<uint64_t> kmer_hdist_count_packed(Words words, size_t n, size_t k, uint64_t query, unsigned tau) const {
+        uint64_t count = 0;
+        bitnuc_err e;
+        if (bitnuc_kmer_hdist_count_packed(ctx_, words.ptr, words.len, n, k, query, tau, &count, &e) != BITNUC_OK) return NucleotideError::from_c(e);
+        return count;
+    }
 
     // Ragged batch: `for s in seqs { encode(s, &mut ebuf)? }` in one launch.  Sequence i =
     // seq[offsets[i] .. offsets[i+1]); returns the concatenated words and fills word_offsets

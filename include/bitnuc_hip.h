@@ -164,6 +164,17 @@ int bitnuc_kmer_hdist_scan_dev(bitnuc_ctx *ctx, const uint8_t *d_ref, size_t n, 
 /* The same scan with the fused threshold of SURVEY 8(d) cfg 5: *d_count (one uint64 in device memory) = number of windows i with
  * hdist_scalar(as_2bit(ref[i..i+k]), query, k) <= tau.  No distance bytes are written: 1 byte read per window. */
 int bitnuc_kmer_hdist_count_dev(bitnuc_ctx *ctx, const uint8_t *d_ref, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *d_count, bitnuc_err *err);
+/* The scan and its fused count on a PACKED sequence: words[0 .. n_words) hold n bases (base i at bits 2 (i mod 32) of words[i / 32]), window j is
+ * as_2bit(decode(words, n)[j .. j+k]); the results are byte-identical to the ASCII forms on decode(words, n).  Bits above 2n in the last word and the
+ * query's bits above 2k are ignored.  Checks, in this order: k > 32 -> SEQUENCE_TOO_LONG(k); n_words < ceil(n/32) -> INVALID_LENGTH(n); k == 0 or
+ * n < k -> OK with no windows (the count writes 0); a NULL pointer, words not 8-byte aligned or a count not 8-byte aligned -> UNSUPPORTED.  Packed
+ * input holds no invalid base.  d_words 16-byte aligned or at 8 mod 16 run the same kernels at the same speed; d_dist may have any byte offset.
+ * The _dev forms are asynchronous on the context's stream and can be captured into a hipGraph. */
+int bitnuc_kmer_hdist_scan_packed_dev(bitnuc_ctx *ctx, const uint64_t *d_words, size_t n_words, size_t n, size_t k, uint64_t query, uint8_t *d_dist, bitnuc_err *err);
+int bitnuc_kmer_hdist_count_packed_dev(bitnuc_ctx *ctx, const uint64_t *d_words, size_t n_words, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *d_count, bitnuc_err *err);
+/* Host-pointer forms, sized like bitnuc_hdist: below the host cutoff they run on the host (ctx may be NULL), above it through the context. */
+int bitnuc_kmer_hdist_scan_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t n_words, size_t n, size_t k, uint64_t query, uint8_t *dist, bitnuc_err *err);
+int bitnuc_kmer_hdist_count_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t n_words, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *count, bitnuc_err *err);
 /* d_result: one uint32 in device memory, overwritten with the distance. */
 int bitnuc_hdist_dev(bitnuc_ctx *ctx, const uint64_t *d_a, size_t na, const uint64_t *d_b, size_t nb, size_t n_bases, uint32_t *d_result, bitnuc_err *err);
 

@@ -114,6 +114,11 @@ extern "C" {
     pub fn bitnuc_decode_batch_plan_dev(ctx: *mut bitnuc_ctx, plan: *const bitnuc_batch_plan, d_words: *const u64, d_out: *mut u8, err: *mut bitnuc_err) -> c_int;
     // fused scan threshold (SURVEY 8d cfg 5): number of windows with distance <= tau
     pub fn bitnuc_kmer_hdist_count_dev(ctx: *mut bitnuc_ctx, d_ref: *const u8, n: usize, k: usize, query: u64, tau: c_uint, d_count: *mut u64, err: *mut bitnuc_err) -> c_int;
+    // the scan and its fused count on packed words (base i at bits 2 (i mod 32) of word i / 32)
+    pub fn bitnuc_kmer_hdist_scan_packed_dev(ctx: *mut bitnuc_ctx, d_words: *const u64, n_words: usize, n: usize, k: usize, query: u64, d_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_hdist_count_packed_dev(ctx: *mut bitnuc_ctx, d_words: *const u64, n_words: usize, n: usize, k: usize, query: u64, tau: c_uint, d_count: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_hdist_scan_packed(ctx: *mut bitnuc_ctx, words: *const u64, n_words: usize, n: usize, k: usize, query: u64, dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_hdist_count_packed(ctx: *mut bitnuc_ctx, words: *const u64, n_words: usize, n: usize, k: usize, query: u64, tau: c_uint, count: *mut u64, err: *mut bitnuc_err) -> c_int;
     // diagnostics
     pub fn bitnuc_selftime_small(op: c_int, n: usize, iters: usize) -> f64;
     pub fn bitnuc_selftime_host_copy(bytes: usize, threads: c_int, mode: c_int) -> f64;

@@ -219,6 +219,27 @@ pub fn kmer_hdist_scan(reference: &[u8], k: usize, query: u64) -> Result<Vec<u8>
     if st == ffi::BITNUC_OK { Ok(out) } else { Err(to_err(&e)) }
 }
 
+/// `kmer_hdist_scan` of the packed sequence `words` holding `n` bases (as `encode` writes them), without decoding it.
+pub fn kmer_hdist_scan_packed(words: &[u64], n: usize, k: usize, query: u64) -> Result<Vec<u8>, NucleotideError> {
+    let nwin = if k > 0 && n >= k { n - k + 1 } else { 0 };
+    let mut out = vec![0u8; nwin];
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_hdist_scan_packed(c, words.as_ptr(), words.len(), n, k, query, out.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(out) } else { Err(to_err(&e)) }
+}
+
+/// The number of windows of the packed sequence `words` (`n` bases) whose Hamming distance to `query` is at most `tau`.
+pub fn kmer_hdist_count_packed(words: &[u64], n: usize, k: usize, query: u64, tau: u32) -> Result<u64, NucleotideError> {
+    let mut count = 0u64;
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_hdist_count_packed(c, words.as_ptr(), words.len(), n, k, query, tau, &mut count, &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(count) } else { Err(to_err(&e)) }
+}
+
 /// `for s in seqs { encode(s, &mut ebuf)? }` in one launch: sequence i =
 /// `seq[offsets[i]..offsets[i+1]]`; returns (concatenated words, word_offsets).
 pub fn encode_batch(seq: &[u8], offsets: &[u64]) -> Result<(Vec<u64>, Vec<u64>), NucleotideError> {
