@@ -13,7 +13,7 @@ kmer_scan3_kernel(const uint8_t *__restrict__ ref, unsigned long long n, unsigne
                   uint8_t *__restrict__ dist, unsigned long long *__restrict__ slot) {
     static_assert(C % U == 0, "a chunk is whole trips");
     const unsigned long long nwin = n - k + 1;                        // host guarantees 1 <= k <= 32, n >= k
-    const unsigned long long rounds = n >= 1056 ? (n - 32) >> 10 : 0; // round r reads bytes [1024 r, 1024 r + 1056)
+    const unsigned long long rounds = scan_rounds(n);
     const unsigned lane = threadIdx.x & 63;
     const unsigned long long wave = (unsigned long long)blockIdx.x * (blockDim.x >> 6) + wave_in_block();
     const uint32_t km = k == 32 ? ~0u : ((1u << k) - 1u);

@@ -63,7 +63,7 @@ void scan_mfma_table(uint64_t query, size_t k, ScanMfmaTable *t, bool match = fa
             hi[16 + i] = (uint8_t)((q != 2 ? 0x02 : 0) | (q != 3 ? 0x20 : 0));
         }
     }
-    for (int j = 0; j < 4; ++j) t->c[j] = 8388608.f + (match ? (float)((unsigned)k << (j == 3 ? 0 : 8 * j)) : 0.f);
+    for (int j = 0; j < 4; ++j) t->c[j] = kPackBias + (match ? (float)((unsigned)k << (j == 3 ? 0 : 8 * j)) : 0.f);
     memset(t->w[16], 0, sizeof t->w[16]);
     for (int rho = 0; rho < 16; ++rho)
         for (int s = 0; s < 6; ++s)
@@ -95,7 +95,7 @@ hipError_t launch_scan(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, ui
     uint32_t ql, qh;
     query_planes(query, k, &ql, &qh);
     const bool al = aligned16(ref) && aligned16(dist);
-    const unsigned long long lines = n >= 1056 ? (n - 32) >> 10 : 0; // line-aligned rounds of 1024 windows
+    const unsigned long long lines = scan_rounds(n); // line-aligned rounds of 1024 windows
     if (s.scan_impl == 8 && al) { // the shipped tiling with three channels per base, workgroups of two or four waves, or other trip lengths
         const int U = s.scan_mfma_unroll;
         if (s.scan_mfma_ch3) { // three channels per base: three MFMAs per 1024 windows
@@ -189,7 +189,7 @@ bool wants_count(const bitnuc_ctx *c, bool al) {
 hipError_t launch_count(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, uint64_t query, unsigned tau, unsigned long long *res,
                         unsigned long long *slot) {
     const SweepKnobs &s = knobs(c);
-    const unsigned long long rounds = n >= 1056 ? (n - 32) >> 10 : 0;
+    const unsigned long long rounds = scan_rounds(n);
     if (s.scan_impl < 7) return count_scan2_t<true, true, 4, 1>(c, ref, n, k, query, tau, res, slot); // round 4's fused count on the bit-plane scan (0.33 ms per 10^9 windows against the matrix-core form's 0.20)
     const int CU_ = s.scan_mfma_count_rounds;
     if (s.scan_mfma_count_form == 2) { // three channels per base at other trip lengths or grids

@@ -47,21 +47,19 @@ __device__ __forceinline__ void scan_mfma_emit(const f32x16 &acc, float tauf, ui
 #pragma unroll
         for (int r = 0; r < 16; ++r) hits += (uint32_t)__builtin_popcountll(__ballot(acc[r] <= tauf));
     } else {
-        u32x4 o;
+        uint32_t o[4];
+        if constexpr (PACK == 0) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if constexpr (PACK == 0) {
+            for (int q = 0; q < 4; ++q) {
                 uint32_t w = 0;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) w = __builtin_amdgcn_cvt_pk_u8_f32(acc[4 * q + j], j, w);
                 o[q] = w;
-            } else {
-                // (__float_as_uint on a copy: __builtin_bit_cast applied to a vector ELEMENT reads element 0 whatever the index -- hipcc 7.2)
-                const float d0 = acc[4 * q], d1 = acc[4 * q + 1], d2 = acc[4 * q + 2], d3 = acc[4 * q + 3];
-                o[q] = __builtin_amdgcn_perm(__float_as_uint(d3), __float_as_uint(d0) | __float_as_uint(d1) | __float_as_uint(d2), 0x04020100u);
             }
+        } else {
+            pack_distances(acc, o);
         }
-        store_group<NTST, true>(dst, o);
+        store_group<NTST, true>(dst, u32x4{o[0], o[1], o[2], o[3]});
     }
 }
 
@@ -80,7 +78,7 @@ kmer_scan_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, uns
     constexpr bool LDS = SHIFT == 1 || ONEHOT;
     __shared__ __attribute__((aligned(16))) uint8_t strips[LDS ? kBlock / 64 : 1][LDS ? kStrip : 16];
     const unsigned long long nwin = n - k + 1;                              // host guarantees 1 <= k <= 32, n >= k
-    const unsigned long long rounds = n >= 1056 ? (n - 32) >> 10 : 0;       // round r reads bytes [1024 r, 1024 r + 1056)
+    const unsigned long long rounds = scan_rounds(n);
     const unsigned lane = threadIdx.x & 63;
     const unsigned long long wave = (unsigned long long)blockIdx.x * (blockDim.x >> 6) + wave_in_block();
     const unsigned long long nwaves = ((unsigned long long)gridDim.x * blockDim.x) >> 6;
@@ -176,10 +174,10 @@ kmer_scan_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, uns
                 uint32_t any = 0;
 #pragma unroll
                 for (int u = 0; u < U; ++u) any |= badr[u];
-                if (__builtin_expect((any & 0xDFDFDFDFu) != 0u, 0)) {
+                if (__builtin_expect(trip_invalid(any), 0)) {
 #pragma unroll
                     for (int u = 0; u < U; ++u)
-                        if ((badr[u] & 0xDFDFDFDFu) != 0u) rescan_bytes(ref, ((r0 + u) << 10) + 16 * lane, 16, slot);
+                        if (trip_invalid(badr[u])) rescan_bytes(ref, ((r0 + u) << 10) + 16 * lane, 16, slot);
                 }
                 if constexpr (!PERSIST) break;
                 if (rn < rounds) cur = nxt;
@@ -193,13 +191,11 @@ kmer_scan_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, uns
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const u32x4 x = cur.v[u][0];
-                // validity of the lane's own 16 bytes, while they are in registers: a second LUT on the same index holds the upper-case byte
-                // that index stands for (0xFF for the four indices no base has: their low bits never match), so x ^ t is 0 or the case bit
                 uint32_t bad = 0;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) bad |= x[i] ^ __builtin_amdgcn_perm(0x47FFFF54u, 0x43FF41FFu, x[i] & 0x07070707u);
-                if constexpr (LEAN) trip_bad |= bad; // (a clamped copy repeats a round of this trip: nothing it could add)
-                else if (__builtin_expect((bad & 0xDFDFDFDFu) != 0u && (unsigned)u < m, 0)) rescan_bytes(ref, ((r0 + u) << 10) + 16 * lane, 16, slot);
+                if constexpr (LEAN) trip_bad |= bad;
+                else if (__builtin_expect(trip_invalid(bad) && (unsigned)u < m, 0)) rescan_bytes(ref, ((r0 + u) << 10) + 16 * lane, 16, slot);
                 const i32x8 e0 = onehot8(x.x, x.y), e1 = onehot8(x.z, x.w);
                 if constexpr (KEEP) { own[u][0] = e0; own[u][1] = e1; }
                 *reinterpret_cast<u32x4 *>(strip + 1024 * u + 16 * lane) = u32x4{(uint32_t)e0[0], (uint32_t)e0[1], (uint32_t)e0[2], (uint32_t)e0[3]};
@@ -211,7 +207,7 @@ kmer_scan_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, uns
                 *reinterpret_cast<u32x4 *>(strip + kPlane + 1024 * m + 16 * lane) = u32x4{(uint32_t)e1[0], (uint32_t)e1[1], (uint32_t)e1[2], (uint32_t)e1[3]};
             }
             if constexpr (LEAN) {
-                if (__builtin_expect((trip_bad & 0xDFDFDFDFu) != 0u, 0)) { // some lane of the trip holds an invalid byte: find the round
+                if (__builtin_expect(trip_invalid(trip_bad), 0)) { // some lane of the trip holds an invalid byte: find the round
 #pragma unroll 1
                     for (unsigned u = 0; u < m; ++u) rescan_bytes(ref, ((r0 + u) << 10) + 16 * lane, 16, slot);
                 }
@@ -316,12 +312,8 @@ kmer_scan_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, uns
 // EMIT: how 1024 f32 distances become a count.
 //   0 = sixteen v_cmp_le_f32 into wave masks + s_bcnt1 + s_add each (round 5's first form: 16 vector and 32 scalar instructions per round; the
 //       scalar unit is shared by the CU's four SIMDs, and its ~50 instructions per round cost as many issue slots as the ~55 vector ones)
-//   1 = the threshold inside the product: A's entries are -1.0 and its rows carry the E8M0 scale 2^(6 j), j = row & 3 < 3, the accumulator starts at
-//       2^23 + (32 + tau) 2^(6 j): a result's mantissa holds the 6-bit field 32 + tau - d of its row, whose top bit says d <= tau, and three rows OR
-//       into one register.  Row j = 3 (entries +1.0, scale 2, start -(2 tau + 1)) holds 2 d - 2 tau - 1: an odd number below 64 -- six significant
-//       bits, so mantissa bits 17 and below are zero and its SIGN says d <= tau.  (x | b3) & 0x80020820 then has one bit per hit of four windows:
-//       v_or3 + v_bitop3 + v_bcnt (which accumulates) per four windows = 12 vector instructions per round and none on the scalar unit; every
-//       partial sum is an integer below 2^24: exact.  The invalid-byte residue is OR-ed over the trip and tested once.
+//   1 = the threshold inside the product (count_row_scale, hit_bits; the table: count_mfma_table's thresholded forms).  The invalid-byte residue is
+//       OR-ed over the trip and tested once.
 //   2 = as 1, and the NEXT trip's loads are issued after this trip's bytes have been expanded into the strip, into the same registers (no second
 //       set of registers, no copy at the end of a trip; the matrix phase of the trip hides the loads)
 template <int U, bool NTLD, int EMIT>
@@ -336,7 +328,7 @@ kmer_count_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, un
     static_assert(kRegion % 128 == 64, "the two parities of one store must land 16 banks apart");
     __shared__ __attribute__((aligned(16))) uint8_t strips[kBlock / 64][4 * kRegion];
     const unsigned long long nwin = n - k + 1;
-    const unsigned long long rounds = n >= 1056 ? (n - 32) >> 10 : 0;
+    const unsigned long long rounds = scan_rounds(n);
     const unsigned lane = threadIdx.x & 63;
     const unsigned long long wave = (unsigned long long)blockIdx.x * (blockDim.x >> 6) + wave_in_block();
     const unsigned long long nwaves = ((unsigned long long)gridDim.x * blockDim.x) >> 6;
@@ -347,28 +339,19 @@ kmer_count_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, un
     if (r0 < rounds) scan_trip_load<U, 3, NTLD>(ref, r0, rounds, lane, cur);
     const unsigned m32 = lane & 31u, hh = lane >> 5;
     i32x8 A[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        A[j] = i32x8{0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) A[j][i] = (int)tab.w[m32 + 8u - 8u * hh][4 * j + i];
-    }
-    if constexpr (EMIT != 0) {
-        // a use of the table's registers BEFORE the loop.  The table arrives by global loads (a lane-varying index into the kernel arguments);
-        // left pending into the loop, they make the compiler wait for vmcnt(0) at the first MFMA of EVERY trip -- i.e. for the next trip's
-        // loads, issued a few instructions earlier, whose whole point is to fly during the matrix phase (round 5's first form did that)
+    query_operand<4>(tab.w[m32 + 8u - 8u * hh], A);
+    if constexpr (EMIT != 0) { // the pin (query_operand's note; round 5's first form had none)
         asm volatile("" : "+v"(A[0][0]), "+v"(A[0][1]), "+v"(A[0][2]), "+v"(A[0][3]), "+v"(A[1][0]), "+v"(A[1][1]), "+v"(A[1][2]), "+v"(A[1][3]),
                           "+v"(A[2][0]), "+v"(A[2][1]), "+v"(A[2][2]), "+v"(A[2][3]), "+v"(A[3][0]), "+v"(A[3][1]), "+v"(A[3][2]), "+v"(A[3][3]));
     }
     const float tauf = (float)tau;
     uint32_t hits = 0;      // EMIT 0: wave-uniform
     uint32_t lane_hits = 0; // EMIT 1, 2: per lane
-    const unsigned jrow = m32 & 3u;
-    const int scale_a = EMIT == 0 ? 127 : 127 + (jrow == 3u ? 1 : 6 * (int)jrow);
+    const int scale_a = EMIT == 0 ? 127 : count_row_scale(m32);
     f32x16 c0;
 #pragma unroll
     for (int i = 0; i < 16; ++i) c0[i] = EMIT == 0 ? 0.f : tab.c[i & 3]; // scan_mfma_host.h: count_mfma_table
-    if constexpr (EMIT != 0) asm volatile("" : "+v"(c0)); // sixteen registers used as an untied C operand (scan_mfma_emit's note)
+    if constexpr (EMIT != 0) asm volatile("" : "+v"(c0)); // (acc_start's note)
     // where group g of the trip lives: region (half e, parity g & 1), entry g >> 1
     const unsigned wr0 = (lane & 1u) * kRegion + 16u * (lane >> 1);                 // the lane's own group l of round u: + 2 kRegion e + 512 u
     const unsigned rd = hh * 2u * kRegion + 16u * m32;                              // lane (n, h), K-step j of round u: + (j & 1) kRegion + 16 (32 u + (j >> 1))
@@ -387,7 +370,7 @@ kmer_count_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, un
 #pragma unroll
             for (int i = 0; i < 4; ++i) bad |= x[i] ^ __builtin_amdgcn_perm(0x47FFFF54u, 0x43FF41FFu, x[i] & 0x07070707u);
             if constexpr (EMIT == 0) {
-                if (__builtin_expect((bad & 0xDFDFDFDFu) != 0u && (unsigned)u < m, 0)) rescan_bytes(ref, ((r0 + u) << 10) + 16 * lane, 16, slot);
+                if (__builtin_expect(trip_invalid(bad) && (unsigned)u < m, 0)) rescan_bytes(ref, ((r0 + u) << 10) + 16 * lane, 16, slot);
             } else {
                 trip_bad |= bad; // (a clamped copy repeats a round of this trip: nothing it could add)
             }
@@ -401,7 +384,7 @@ kmer_count_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, un
             *reinterpret_cast<u32x4 *>(strip + lane * kRegion + 512 * m + 2 * kRegion) = u32x4{(uint32_t)e1[0], (uint32_t)e1[1], (uint32_t)e1[2], (uint32_t)e1[3]};
         }
         if constexpr (EMIT != 0) {
-            if (__builtin_expect((trip_bad & 0xDFDFDFDFu) != 0u, 0)) { // some lane of the trip holds an invalid byte: find the round
+            if (__builtin_expect(trip_invalid(trip_bad), 0)) { // some lane of the trip holds an invalid byte: find the round
 #pragma unroll 1
                 for (unsigned u = 0; u < m; ++u) rescan_bytes(ref, ((r0 + u) << 10) + 16 * lane, 16, slot);
             }
@@ -425,12 +408,7 @@ kmer_count_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, un
                 for (int r = 0; r < 16; ++r) hits += (uint32_t)__builtin_popcountll(__ballot(acc[r] <= tauf));
             } else {
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    // (__float_as_uint on a copy: __builtin_bit_cast applied to a vector ELEMENT reads element 0 whatever the index -- hipcc 7.2)
-                    const float d0 = acc[4 * q], d1 = acc[4 * q + 1], d2 = acc[4 * q + 2], d3 = acc[4 * q + 3];
-                    const uint32_t x = __float_as_uint(d0) | __float_as_uint(d1) | __float_as_uint(d2);
-                    lane_hits += (uint32_t)__builtin_popcount((x | __float_as_uint(d3)) & 0x80020820u);
-                }
+                for (int q = 0; q < 4; ++q) lane_hits += (uint32_t)__builtin_popcount(hit_bits(acc, q));
             }
         }
         if constexpr (EMIT != 2) { if (rn < rounds) cur = nxt; } // (otherwise the loop ends: nothing was loaded into nxt)
@@ -481,7 +459,7 @@ kmer_scan_seg3_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n
     constexpr int kG = (32 * U + 1) * 16;
     __shared__ __attribute__((aligned(16))) uint8_t strips[kBlock / 64][2 * kAc + kG];
     const unsigned long long nwin = n - k + 1;
-    const unsigned long long rounds = n >= 1056 ? (n - 32) >> 10 : 0;
+    const unsigned long long rounds = scan_rounds(n);
     const unsigned lane = threadIdx.x & 63;
     const unsigned long long wave = (unsigned long long)blockIdx.x * (blockDim.x >> 6) + wave_in_block();
     uint8_t *strip = strips[wave_in_block()];
@@ -492,17 +470,9 @@ kmer_scan_seg3_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n
         const unsigned m = rounds - r0 < (unsigned long long)U ? (unsigned)(rounds - r0) : (unsigned)U;
         const unsigned m32 = lane & 31u, hh = lane >> 5;
         i32x8 A[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            A[j] = i32x8{0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) A[j][i] = (int)tab.w[lane][4 * j + i];
-        }
-        const int scale_a = 127 + 8 * (int)((m32 & 3u) == 3u ? 0u : (m32 & 3u));
-        f32x16 c0;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) c0[i] = tab.c[i & 3];
-        asm volatile("" : "+v"(c0));
+        query_operand<3>(tab.w[lane], A);
+        const int scale_a = dist_row_scale(m32);
+        const f32x16 c0 = acc_start(tab.c);
         const unsigned wr_ac = (lane & 1u) * kAc + 16u * (lane >> 1), wr_g = 2u * kAc + 8u * lane;
         const unsigned rd_ac = hh * kAc + 16u * m32, rd_g = 2u * kAc + 16u * (m32 + hh);
         uint32_t trip_bad = 0;
@@ -524,7 +494,7 @@ kmer_scan_seg3_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n
             *reinterpret_cast<u32x4 *>(strip + lane * kAc + 512 * m) = ac;
             *reinterpret_cast<u32x2 *>(strip + 2 * kAc + 512 * m + 8 * lane) = u32x2{g0, g1};
         }
-        if (__builtin_expect((trip_bad & 0xDFDFDFDFu) != 0u, 0)) {
+        if (__builtin_expect(trip_invalid(trip_bad), 0)) {
 #pragma unroll 1
             for (unsigned u = 0; u < m; ++u) rescan_bytes(ref, ((r0 + u) << 10) + 16 * lane, 16, slot);
         }
@@ -538,18 +508,9 @@ kmer_scan_seg3_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n
                 const u32x4 t = *reinterpret_cast<const u32x4 *>(strip + (j < 2 ? rd_ac + 16 * j : rd_g) + 512 * u);
                 B[j] = i32x8{(int)t.x, (int)t.y, (int)t.z, (int)t.w, 0, 0, 0, 0};
             }
-            f32x16 acc = c0;
-#pragma unroll
-            for (int j = 0; j < 3; ++j) acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A[j], B[j], acc, 4, 4, 0, scale_a, 0, 127);
             uint32_t o[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float d0 = acc[4 * q], d1 = acc[4 * q + 1], d2 = acc[4 * q + 2], d3 = acc[4 * q + 3];
-                o[q] = __builtin_amdgcn_perm(__float_as_uint(d3), __float_as_uint(d0) | __float_as_uint(d1) | __float_as_uint(d2), 0x04020100u);
-            }
-            const auto s02 = __builtin_amdgcn_permlane32_swap(o[0], o[2], false, false);
-            const auto s13 = __builtin_amdgcn_permlane32_swap(o[1], o[3], false, false);
-            store_group<NTST, true>(dist + ((r0 + u) << 10) + 16u * (2u * m32 + hh), u32x4{s02[0], s02[1], s13[0], s13[1]});
+            pack_distances(mfma_chain(A, B, c0, scale_a), o);
+            store_distances<NTST, true>(dist + ((r0 + u) << 10) + 16u * (2u * m32 + hh), o);
         }
     }
     scan_tail_windows<false>(ref, rounds << 10, nwin, k, query, 0u, dist, slot);

@@ -117,9 +117,8 @@ template <int U, int BLOCK>
 hipError_t scan_seg_t(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, uint64_t query, uint8_t *dist, unsigned long long *slot) {
     CountMfmaTable ct;
     count_mfma_table(query, k, &ct);
-    for (int j = 0; j < 4; ++j) ct.c[j] = 8388608.f;
-    const unsigned long long rounds = n >= 1056 ? (n - 32) >> 10 : 0;
-    kmer_scan_seg_mfma_kernel<3, U, BLOCK><<<(unsigned)(rounds / ((BLOCK / 64) * U) + 1), BLOCK, 0, c->stream>>>(ref, n, (unsigned)k, query, dist, slot, ct);
+    for (int j = 0; j < 4; ++j) ct.c[j] = kPackBias;
+    kmer_scan_seg_mfma_kernel<3, U, BLOCK><<<(unsigned)(scan_rounds(n) / ((BLOCK / 64) * U) + 1), BLOCK, 0, c->stream>>>(ref, n, (unsigned)k, query, dist, slot, ct);
     return hipGetLastError();
 }
 
@@ -133,14 +132,18 @@ hipError_t scan992_t(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, uint
     return hipGetLastError();
 }
 
-// the fused count with three channels per base: a bounded grid of per_cu workgroups per CU (each arrives once at the accumulator and the ticket)
+// a ticketed count's grid: one workgroup per `per_wg` rounds, at most per_cu workgroups per CU (each arrives once at the accumulator and the ticket)
+unsigned bounded_grid(const bitnuc_ctx *c, unsigned long long rounds, unsigned long long per_wg, int per_cu) {
+    const unsigned long long want = rounds / per_wg + 1, cap = (unsigned long long)c->num_cu * (unsigned)per_cu;
+    return (unsigned)(want < cap ? want : cap);
+}
+
+// the fused count with three channels per base: a bounded grid of per_cu workgroups per CU
 template <int U>
 hipError_t count3_t(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, uint64_t query, unsigned tau, unsigned long long *res, unsigned long long *slot, int per_cu) {
     Count3MfmaTable c3;
     count3_mfma_table(query, k, tau, &c3);
-    const unsigned long long rounds = n >= 1056 ? (n - 32) >> 10 : 0;
-    const unsigned long long want = rounds / ((kBlock / 64) * (unsigned long long)U) + 1, cap = (unsigned long long)c->num_cu * (unsigned)per_cu;
-    kmer_count3_mfma_kernel<U, true><<<(unsigned)(want < cap ? want : cap), kBlock, 0, c->stream>>>(ref, n, (unsigned)k, query, tau, res, c->d_acc + 5, c->d_tickets + 2, slot, c3);
+    kmer_count3_mfma_kernel<U, true><<<bounded_grid(c, scan_rounds(n), (kBlock / 64) * U, per_cu), kBlock, 0, c->stream>>>(ref, n, (unsigned)k, query, tau, res, c->d_acc + 5, c->d_tickets + 2, slot, c3);
     return hipGetLastError();
 }
 
@@ -149,9 +152,7 @@ template <bool AL, bool NL, int U, int GEN>
 hipError_t count_scan2_t(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, uint64_t query, unsigned tau, unsigned long long *res, unsigned long long *slot) {
     uint32_t ql, qh;
     query_planes(query, k, &ql, &qh);
-    const unsigned long long rounds = n >= 1056 ? (n - 32) >> 10 : 0;
-    const unsigned long long want = rounds / ((kBlock / 64) * 4) + 1, cap = (unsigned long long)c->num_cu * 8;
-    kmer_scan2_kernel<AL, NL, false, U, true, GEN><<<(unsigned)(want < cap ? want : cap), kBlock, 0, c->stream>>>(ref, n, (unsigned)k, query, ql, qh, tau, nullptr, res, c->d_acc + 5, c->d_tickets + 2, slot);
+    kmer_scan2_kernel<AL, NL, false, U, true, GEN><<<bounded_grid(c, scan_rounds(n), (kBlock / 64) * 4, 8), kBlock, 0, c->stream>>>(ref, n, (unsigned)k, query, ql, qh, tau, nullptr, res, c->d_acc + 5, c->d_tickets + 2, slot);
     return hipGetLastError();
 }
 
@@ -201,9 +202,7 @@ hipError_t launch_scan_packed(bitnuc_ctx *c, const uint64_t *words, size_t n, si
     PackedScanTable t;
     scan_packed_table(query, k, &t);
     const unsigned skip = aligned16(words) ? 0u : 32u;
-    const unsigned long long nr = n > skip ? n - skip : 0;
-    const unsigned long long rounds = nr >= 1056 ? (nr - 32) >> 10 : 0;
-    packed_scan_mfma_kernel<<<(unsigned)(rounds / 4 + 1), kPackedBlockScan, 0, c->stream>>>(words, n, skip, (unsigned)k, query, dist, t);
+    packed_scan_mfma_kernel<<<(unsigned)(scan_rounds(n, skip) / 4 + 1), kPackedBlockScan, 0, c->stream>>>(words, n, skip, (unsigned)k, query, dist, t);
     return hipGetLastError();
 }
 
@@ -212,10 +211,7 @@ hipError_t launch_count_packed(bitnuc_ctx *c, const uint64_t *words, size_t n, s
     Count3MfmaTable t;
     count3_packed_table(query, k, tau, &t);
     const unsigned skip = aligned16(words) ? 0u : 32u;
-    const unsigned long long nr = n > skip ? n - skip : 0;
-    const unsigned long long rounds = nr >= 1056 ? (nr - 32) >> 10 : 0;
-    const unsigned long long want = rounds / ((kBlock / 64) * 4ull) + 1, cap = (unsigned long long)c->num_cu * (unsigned)kCountGrid;
-    packed_count3_mfma_kernel<<<(unsigned)(want < cap ? want : cap), kBlock, 0, c->stream>>>(words, n, skip, (unsigned)k, query, tau, res, c->d_acc + 6, c->d_tickets + 3, t);
+    packed_count3_mfma_kernel<<<bounded_grid(c, scan_rounds(n, skip), (kBlock / 64) * 4, kCountGrid), kBlock, 0, c->stream>>>(words, n, skip, (unsigned)k, query, tau, res, c->d_acc + 6, c->d_tickets + 3, t);
     return hipGetLastError();
 }
 

@@ -18,6 +18,7 @@
 // trip, the other dense unrolls / policies -- profiles/NARRATIVE_r01_r03.md 3.3-3.4, profiles/README.md.
 #pragma once
 #include "device_prims.h"
+#include "scan_mfma_host.h" // scan_rounds
 
 namespace bitnuc_dev {
 
@@ -330,7 +331,7 @@ kmer_scan2_kernel(const uint8_t *__restrict__ ref, unsigned long long n, unsigne
                   unsigned long long *__restrict__ total /* zero between launches */, unsigned *__restrict__ ticket,
                   unsigned long long *__restrict__ slot) {
     const unsigned long long nwin = n - k + 1;                              // host guarantees 1 <= k <= 32, n >= k
-    const unsigned long long rounds = n >= 1056 ? (n - 32) >> 10 : 0;       // round r reads bytes [1024 r, 1024 r + 1056)
+    const unsigned long long rounds = scan_rounds(n);
     const unsigned lane = threadIdx.x & 63;
     const unsigned long long wave = (unsigned long long)blockIdx.x * (blockDim.x >> 6) + wave_in_block();
     const unsigned long long nwaves = ((unsigned long long)gridDim.x * blockDim.x) >> 6;

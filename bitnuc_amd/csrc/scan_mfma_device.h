@@ -25,11 +25,10 @@
 // groups live in regions 16 banks apart).  A trip is U consecutive rounds + the 32-byte halo after them.  The query's side of the product is built on the host
 // (scan_mfma_host.h) and passed BY VALUE in the kernel arguments (a hipGraph node keeps its own copy), together with the values the accumulators start at.
 //
-// Packing 16 f32 results into 16 bytes costs 2 instructions per 4 windows instead of 4: the accumulator starts at 2^23 (the integer d then sits in the low mantissa
-// bits) and A's rows carry the E8M0 block scale 2^(8 (m & 3)) for m & 3 < 3, so three results OR together into bytes 0-2 and a v_perm drops the fourth into byte 3.
-// Everything is an integer below 2^24: exact.  The count's threshold uses the same idea with 6-bit fields (kmer_count3_mfma_kernel).
-// Invalid bytes: the lane's own 16 bytes against a second v_perm LUT on the same index (the upper-case byte the index stands for: x ^ t is 0 or the case bit for a
-// valid byte), OR-ed over the trip and tested once; their one-hot is all zero, the call fails with INVALID_BASE anyway.
+// The back end -- query operand, accumulator start, row scales, MFMA chain, pack and store, hit bits -- is shared with the packed kernels
+// (scan_packed_device.h) and written once, below; each rule (the 2^23 pack bias, the threshold fields, the hit mask, the pins, the toolchain workarounds) is
+// explained at its helper.  Invalid bytes: trip_invalid, OR-ed over the trip and tested once; their one-hot is all zero, the call fails with
+// INVALID_BASE anyway.
 // Why four (three) matrix instructions and not the six of the tiling that shipped first: the matrix pipe's POWER is what makes a queue that starts on an idle chip
 // dip (profiles/r05_ablate_count_parts.txt); with four the scan runs at the HBM plateau from its first launch (profiles/r05_ab_scan_seg.txt).
 #pragma once
@@ -84,6 +83,92 @@ __device__ __forceinline__ void scan_trip_load(const uint8_t *__restrict__ ref, 
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The back end of the segment tiling: every matrix-core kernel of the scan and count (ASCII here, packed words in scan_packed_device.h) builds its operands its
+// own way and hands them to these.  Whole rounds: scan_rounds (scan_mfma_host.h).
+
+// The query's operand: K-step j of a row is dwords 4 j .. 4 j + 3 of the row's entry in the host table (the upper half of an fp4 operand is unused).
+// The kernels whose waves walk trips PIN it: one asm statement that uses all of A's registers BEFORE the trip loop.  The table arrives by global loads (a
+// lane-varying index into the kernel arguments); left pending into the loop, they make the compiler wait for vmcnt(0) at the first MFMA of EVERY trip -- i.e.
+// for the next trip's loads, issued a few instructions earlier, whose whole point is to fly during the matrix phase.  (The pin stays at the call site: split
+// into one statement per K-step here, it changes the kernels' waits.)  The kernels with one trip per wave do not pin: their table loads overlap the trip's.
+template <int NSTEPS>
+__device__ __forceinline__ void query_operand(const uint32_t *row, i32x8 (&A)[NSTEPS]) {
+#pragma unroll
+    for (int j = 0; j < NSTEPS; ++j) {
+        A[j] = i32x8{0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) A[j][i] = (int)row[4 * j + i];
+    }
+}
+
+// Where the accumulators start: result register r at c[r & 3] (the host tables' start values).  Sixteen registers used as an untied C operand: a splat
+// constant is re-materialised by 16 v_mov per round.
+__device__ __forceinline__ f32x16 acc_start(const float (&c)[4]) {
+    f32x16 c0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) c0[i] = c[i & 3];
+    asm volatile("" : "+v"(c0));
+    return c0;
+}
+
+// The distance pack: 16 f32 results into 16 bytes at 2 instructions per 4 windows instead of 4.  The accumulators start at 2^23 (kPackBias: the integer d
+// then sits in the low mantissa bits) and A's row m carries the E8M0 block scale 2^(8 (m & 3)) for m & 3 < 3, so three results OR together into bytes 0-2
+// and a v_perm drops the fourth into byte 3 (pack_distances).  Everything is an integer below 2^24: exact.
+__device__ __forceinline__ int dist_row_scale(unsigned m32) { return 127 + 8 * (int)((m32 & 3u) == 3u ? 0u : (m32 & 3u)); }
+
+// The count's threshold inside the product.  The entries are signed and A's row m carries the E8M0 scale 2^(6 j), j = m & 3 < 3; the accumulator starts at
+// 2^23 + (32 + tau - d0) 2^(6 j) (d0: what the table adds to every window, scan_mfma_host.h): a result's mantissa holds the 6-bit field 32 + tau - d of its
+// row, whose top bit says d <= tau, and three rows OR into one register.  Row j = 3 (scale 2, start 2 d0 - 2 tau - 1) holds 2 d - 2 tau - 1: an odd number
+// below 64 -- six significant bits, so mantissa bits 17 and below are zero and its SIGN says d <= tau (count_hits).  Every partial sum is an integer below
+// 2^24: exact.
+__device__ __forceinline__ int count_row_scale(unsigned m32) { return 127 + ((m32 & 3u) == 3u ? 1 : 6 * (int)(m32 & 3u)); }
+
+// v_mfma_scale_f32_32x32x64_f8f6f4 with fp4 (E2M1) operands on both sides, A's rows at E8M0 `scale`, B at 2^0: N K-steps of 64 nibbles into acc
+template <int N>
+__device__ __forceinline__ f32x16 mfma_chain(const i32x8 (&A)[N], const i32x8 (&B)[N], f32x16 acc, int scale) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A[j], B[j], acc, 4, 4, 0, scale, 0, 127);
+    return acc;
+}
+
+// o[q]: the distance bytes of result registers 4 q .. 4 q + 3 (dist_row_scale's pack)
+__device__ __forceinline__ void pack_distances(const f32x16 &acc, uint32_t (&o)[4]) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        // (__float_as_uint on a copy: __builtin_bit_cast applied to a vector ELEMENT reads element 0 whatever the index -- hipcc 7.2)
+        const float d0 = acc[4 * q], d1 = acc[4 * q + 1], d2 = acc[4 * q + 2], d3 = acc[4 * q + 3];
+        o[q] = __builtin_amdgcn_perm(__float_as_uint(d3), __float_as_uint(d0) | __float_as_uint(d1) | __float_as_uint(d2), 0x04020100u);
+    }
+}
+
+// Lane (n, h) holds windows 32 n + 8 q + 4 h + i (q = r >> 2, i = r & 3), i.e. after the pack one dword per q with four consecutive distance bytes.  Two
+// v_permlane32_swap (lanes l and l + 32 exchange a register: a's lanes 32-63 <-> b's lanes 0-31) give lane (n, 0) the dwords (q0, partner's q0, q1, partner's
+// q1) = bytes 32 n .. 32 n + 15 and lane (n, 1) (partner's q2, q2, partner's q3, q3) = bytes 32 n + 16 .. 32 n + 31: one dwordx4 store per lane at
+// p = the round's first byte + 16 (2 n + h).  ALIGNED: store_group<NT, true>; otherwise a nontemporal store to any byte address.
+template <bool NT, bool ALIGNED>
+__device__ __forceinline__ void store_distances(uint8_t *p, const uint32_t (&o)[4]) {
+    const auto s02 = __builtin_amdgcn_permlane32_swap(o[0], o[2], false, false);
+    const auto s13 = __builtin_amdgcn_permlane32_swap(o[1], o[3], false, false);
+    const u32x4 v = {s02[0], s02[1], s13[0], s13[1]};
+    if constexpr (ALIGNED) store_group<NT, true>(p, v);
+    else {
+        static_assert(NT, "unaligned distance stores are nontemporal");
+        __builtin_nontemporal_store(v, reinterpret_cast<u32x4_u *>(p));
+    }
+}
+
+// The count's hits (count_row_scale's fields) of result registers 4 q .. 4 q + 3: (x | d3) & 0x80020820 has one bit per hit of four windows.  The caller
+// adds their popcounts -- v_or3 + v_bitop3 + v_bcnt (which accumulates) per four windows = 12 vector instructions per round and none on the scalar unit
+// (sixteen v_cmp + s_bcnt1 + s_add cost 16 + 32, and the scalar unit is shared by the CU's four SIMDs).  (One call per q: a helper that sums the four
+// itself changes the kernels' code.)
+__device__ __forceinline__ uint32_t hit_bits(const f32x16 &acc, int q) {
+    // (__float_as_uint on a copy: pack_distances' note)
+    const float d0 = acc[4 * q], d1 = acc[4 * q + 1], d2 = acc[4 * q + 2], d3 = acc[4 * q + 3];
+    const uint32_t x = __float_as_uint(d0) | __float_as_uint(d1) | __float_as_uint(d2);
+    return (x | __float_as_uint(d3)) & 0x80020820u;
+}
+
 // The windows after the last whole round: one window per thread, byte loads (as the reference: naive.rs:3-20 then scalar.rs:33-47 per window)
 template <bool COUNT>
 __device__ __forceinline__ uint32_t scan_tail_windows(const uint8_t *__restrict__ ref, unsigned long long first, unsigned long long nwin, unsigned k, unsigned long long query, unsigned tau,
@@ -108,6 +193,12 @@ __device__ __forceinline__ uint32_t scan_tail_windows(const uint8_t *__restrict_
     return hits;
 }
 
+// The validity of 16 ASCII bytes while they are in registers (the kernels OR, per dword x, x ^ perm(0x47FFFF54, 0x43FF41FF, x & 0x07070707) into `bad`):
+// a second v_perm LUT on the one-hot's index holds the upper-case byte that index stands for (0xFF for the four indices no base has: their low bits never
+// match), so x ^ t is 0 or the case bit for a valid byte.  OR-ed over a trip (a clamped copy repeats a round of the trip: nothing it could add) and tested
+// once here; the call site finds the byte (rescan_bytes).
+__device__ __forceinline__ bool trip_invalid(uint32_t bad) { return (bad & 0xDFDFDFDFu) != 0u; }
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 // The segment tiling with four channels per base (the scan; evidence: kmer_count_mfma_kernel).  D[m][n] = dist(window 32 n + m); the 63 positions a segment's
 // windows cover are 4 K-steps of 16, nothing multiplies zeros: 4 MFMAs per 1024 windows.  Lane (n, h) of K-step j needs the one-hot operand of bases
@@ -116,10 +207,7 @@ __device__ __forceinline__ uint32_t scan_tail_windows(const uint8_t *__restrict_
 // w[delta + 8][4 j + i]: dword i of K-step j for the row with delta = m - 8 h (i = position - m only depends on it): CountMfmaTable, scan_mfma_host.h.
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// The distance bytes.  Lane (n, h) ends up holding windows 32 n + 8 q + 4 h + i (q = r >> 2, i = r & 3), i.e. after the 2^23-bias pack one dword per q with four
-// consecutive distance bytes, and two v_permlane32_swap (lanes l and l + 32 exchange a register) give lane (n, 0) the dwords (q0, partner's q0, q1, partner's q1) =
-// bytes 32 n .. 32 n + 15 and lane (n, 1) (partner's q2, q2, partner's q3, q3) = bytes 32 n + 16 .. 32 n + 31: one natural dwordx4 store per lane at 16 (2 n + h).
-// One trip of U rounds per wave; the hardware dispatcher walks the trips (how every streaming kernel of this library runs fastest).  BLOCK: threads per workgroup --
+// The distance bytes: pack_distances, then store_distances' natural dwordx4 store per lane.  One trip of U rounds per wave; the hardware dispatcher walks the trips (how every streaming kernel of this library runs fastest).  BLOCK: threads per workgroup --
 // nothing is shared inside one (the strips are wave-private), and with one wave per workgroup 19 waves fit a CU's LDS instead of 16 (profiles/r05_ab_scan_block.txt).
 template <int POLICY, int U, int BLOCK = kBlock>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, 8)))
@@ -132,7 +220,7 @@ kmer_scan_seg_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n,
     static_assert(kRegion % 128 == 64, "the two parities of one store must land 16 banks apart");
     __shared__ __attribute__((aligned(16))) uint8_t strips[BLOCK / 64][4 * kRegion];
     const unsigned long long nwin = n - k + 1;
-    const unsigned long long rounds = n >= 1056 ? (n - 32) >> 10 : 0;
+    const unsigned long long rounds = scan_rounds(n);
     const unsigned lane = threadIdx.x & 63;
     const unsigned long long wave = (unsigned long long)blockIdx.x * (blockDim.x >> 6) + wave_in_block();
     uint8_t *strip = strips[wave_in_block()];
@@ -143,17 +231,9 @@ kmer_scan_seg_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n,
         const unsigned m = rounds - r0 < (unsigned long long)U ? (unsigned)(rounds - r0) : (unsigned)U;
         const unsigned m32 = lane & 31u, hh = lane >> 5;
         i32x8 A[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            A[j] = i32x8{0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) A[j][i] = (int)tab.w[m32 + 8u - 8u * hh][4 * j + i];
-        }
-        const int scale_a = 127 + 8 * (int)((m32 & 3u) == 3u ? 0u : (m32 & 3u)); // E8M0: 2^(8 (row & 3)) for row & 3 < 3 (scan_mfma_emit's pack)
-        f32x16 c0;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) c0[i] = tab.c[i & 3]; // 2^23
-        asm volatile("" : "+v"(c0)); // sixteen registers used as an untied C operand (a splat constant is re-materialised by 16 v_mov per round)
+        query_operand<4>(tab.w[m32 + 8u - 8u * hh], A);
+        const int scale_a = dist_row_scale(m32);
+        const f32x16 c0 = acc_start(tab.c); // 2^23
         const unsigned wr0 = (lane & 1u) * kRegion + 16u * (lane >> 1);
         const unsigned rd = hh * 2u * kRegion + 16u * m32;
         uint32_t trip_bad = 0;
@@ -161,7 +241,7 @@ kmer_scan_seg_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n,
         for (int u = 0; u < U; ++u) {
             const u32x4 x = cur.v[u][0];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) trip_bad |= x[i] ^ __builtin_amdgcn_perm(0x47FFFF54u, 0x43FF41FFu, x[i] & 0x07070707u);
+            for (int i = 0; i < 4; ++i) trip_bad |= x[i] ^ __builtin_amdgcn_perm(0x47FFFF54u, 0x43FF41FFu, x[i] & 0x07070707u); // (trip_invalid's LUT)
             const i32x8 e0 = onehot8(x.x, x.y), e1 = onehot8(x.z, x.w);
             *reinterpret_cast<u32x4 *>(strip + wr0 + 512 * u) = u32x4{(uint32_t)e0[0], (uint32_t)e0[1], (uint32_t)e0[2], (uint32_t)e0[3]};
             *reinterpret_cast<u32x4 *>(strip + wr0 + 512 * u + 2 * kRegion) = u32x4{(uint32_t)e1[0], (uint32_t)e1[1], (uint32_t)e1[2], (uint32_t)e1[3]};
@@ -171,7 +251,7 @@ kmer_scan_seg_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n,
             *reinterpret_cast<u32x4 *>(strip + lane * kRegion + 512 * m) = u32x4{(uint32_t)e0[0], (uint32_t)e0[1], (uint32_t)e0[2], (uint32_t)e0[3]};
             *reinterpret_cast<u32x4 *>(strip + lane * kRegion + 512 * m + 2 * kRegion) = u32x4{(uint32_t)e1[0], (uint32_t)e1[1], (uint32_t)e1[2], (uint32_t)e1[3]};
         }
-        if (__builtin_expect((trip_bad & 0xDFDFDFDFu) != 0u, 0)) { // some lane of the trip holds an invalid byte: find the round
+        if (__builtin_expect(trip_invalid(trip_bad), 0)) { // some lane of the trip holds an invalid byte: find the round
 #pragma unroll 1
             for (unsigned u = 0; u < m; ++u) rescan_bytes(ref, ((r0 + u) << 10) + 16 * lane, 16, slot);
         }
@@ -185,20 +265,9 @@ kmer_scan_seg_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n,
                 const u32x4 t = *reinterpret_cast<const u32x4 *>(strip + rd + (j & 1) * kRegion + 16 * (32 * u + (j >> 1)));
                 B[j] = i32x8{(int)t.x, (int)t.y, (int)t.z, (int)t.w, 0, 0, 0, 0};
             }
-            f32x16 acc = c0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A[j], B[j], acc, 4, 4, 0, scale_a, 0, 127);
             uint32_t o[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                // (__float_as_uint on a copy: __builtin_bit_cast applied to a vector ELEMENT reads element 0 whatever the index -- hipcc 7.2)
-                const float d0 = acc[4 * q], d1 = acc[4 * q + 1], d2 = acc[4 * q + 2], d3 = acc[4 * q + 3];
-                o[q] = __builtin_amdgcn_perm(__float_as_uint(d3), __float_as_uint(d0) | __float_as_uint(d1) | __float_as_uint(d2), 0x04020100u);
-            }
-            // v_permlane32_swap a, b: a's lanes 32-63 <-> b's lanes 0-31
-            const auto s02 = __builtin_amdgcn_permlane32_swap(o[0], o[2], false, false);
-            const auto s13 = __builtin_amdgcn_permlane32_swap(o[1], o[3], false, false);
-            store_group<NTST, true>(dist + ((r0 + u) << 10) + 16u * (2u * m32 + hh), u32x4{s02[0], s02[1], s13[0], s13[1]});
+            pack_distances(mfma_chain(A, B, c0, scale_a), o);
+            store_distances<NTST, true>(dist + ((r0 + u) << 10) + 16u * (2u * m32 + hh), o);
         }
     }
 
@@ -214,16 +283,10 @@ kmer_scan_seg_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n,
 // and odd groups in separate regions, 16 banks apart, as above); K-step 2: the G nibbles of positions 32 h .. 32 h + 31 of its segment.  Per round: three
 // ds_read_b128 instead of four, ds_write_b128 + ds_write_b64 instead of two ds_write_b128, two more vector instructions for the nibble packing, a quarter fewer
 // matrix instructions -- whose power is what lowers the clock (profiles/r05_ablate_count_parts.txt).  An invalid byte reads as T; the call fails anyway.
-// w[lane][4 s + i]: the lane's 16-byte operand of K-step s (built on the host: kmer.hip count3_mfma_table); c as CountMfmaTable's.
-// The threshold is inside the product: the entries are signed and A's rows carry the E8M0 scale 2^(6 j), j = row & 3 < 3, the accumulator starts at
-// 2^23 + (32 + tau - #(q_i != T)) 2^(6 j): a result's mantissa holds the 6-bit field 32 + tau - d of its row, whose top bit says d <= tau, and three rows OR into
-// one register.  Row j = 3 (scale 2, start 2 #(q_i != T) - 2 tau - 1) holds 2 d - 2 tau - 1: an odd number below 64 -- six significant bits, so mantissa bits 17 and
-// below are zero and its SIGN says d <= tau.  (x | b3) & 0x80020820 then has one bit per hit of four windows: v_or3 + v_bitop3 + v_bcnt (which accumulates) per
-// four windows = 12 vector instructions per round and none on the scalar unit (sixteen v_cmp + s_bcnt1 + s_add cost 16 + 32, and the scalar unit is shared by the
-// CU's four SIMDs); every partial sum is an integer below 2^24: exact.  tau >= k (no window can miss) gets an all-zero table.
+// w[lane][4 s + i]: the lane's 16-byte operand of K-step s (built on the host: Count3MfmaTable, scan_mfma_host.h).  The threshold is inside the product
+// (count_row_scale, count_hits); tau >= k (no window can miss) gets an all-zero table.
 // A bounded grid (one arrival per workgroup at the accumulator's ticket) whose waves walk trips; the NEXT trip's loads are issued as soon as this trip's bytes
 // are in the strip, into the same registers, and fly during the matrix phase.
-// The query's operand: Count3MfmaTable, scan_mfma_host.h.
 
 // 16 bases (four ASCII dwords) -> their 16 (A, C) bytes and their 16 G nibbles (the three-channel operands)
 __device__ __forceinline__ void expand3(const u32x4 &x, u32x4 &ac, uint32_t &g0, uint32_t &g1) {
@@ -249,7 +312,7 @@ kmer_count3_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, u
     constexpr int kG = (32 * U + 1) * 16;       // G nibbles: 16 bytes per 32 positions
     __shared__ __attribute__((aligned(16))) uint8_t strips[kBlock / 64][2 * kAc + kG];
     const unsigned long long nwin = n - k + 1;
-    const unsigned long long rounds = n >= 1056 ? (n - 32) >> 10 : 0;
+    const unsigned long long rounds = scan_rounds(n);
     const unsigned lane = threadIdx.x & 63;
     const unsigned long long wave = (unsigned long long)blockIdx.x * (blockDim.x >> 6) + wave_in_block();
     const unsigned long long nwaves = ((unsigned long long)gridDim.x * blockDim.x) >> 6;
@@ -260,24 +323,12 @@ kmer_count3_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, u
     if (r0 < rounds) scan_trip_load<U, 3, NTLD>(ref, r0, rounds, lane, cur);
     const unsigned m32 = lane & 31u, hh = lane >> 5;
     i32x8 A[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        A[j] = i32x8{0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) A[j][i] = (int)tab.w[lane][4 * j + i];
-    }
-    // A use of the table's registers BEFORE the loop.  The table arrives by global loads (a lane-varying index into the kernel arguments); left pending into the
-    // loop, they make the compiler wait for vmcnt(0) at the first MFMA of EVERY trip -- i.e. for the next trip's loads, issued a few instructions earlier, whose
-    // whole point is to fly during the matrix phase.
+    query_operand<3>(tab.w[lane], A);
     asm volatile("" : "+v"(A[0][0]), "+v"(A[0][1]), "+v"(A[0][2]), "+v"(A[0][3]), "+v"(A[1][0]), "+v"(A[1][1]), "+v"(A[1][2]), "+v"(A[1][3]),
                       "+v"(A[2][0]), "+v"(A[2][1]), "+v"(A[2][2]), "+v"(A[2][3]));
     uint32_t lane_hits = 0;
-    const unsigned jrow = m32 & 3u;
-    const int scale_a = 127 + (jrow == 3u ? 1 : 6 * (int)jrow);
-    f32x16 c0;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) c0[i] = tab.c[i & 3];
-    asm volatile("" : "+v"(c0)); // sixteen registers used as an untied C operand
+    const int scale_a = count_row_scale(m32);
+    const f32x16 c0 = acc_start(tab.c);
     const unsigned wr_ac = (lane & 1u) * kAc + 16u * (lane >> 1); // the lane's own group l of round u: + 512 u
     const unsigned wr_g = 2u * kAc + 8u * lane;                   // ... its 16 G nibbles: + 512 u
     const unsigned rd_ac = hh * kAc + 16u * m32;                  // K-step s < 2 of round u: + 16 s + 512 u
@@ -292,7 +343,7 @@ kmer_count3_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, u
         for (int u = 0; u < U; ++u) {
             const u32x4 x = cur.v[u][0];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) trip_bad |= x[i] ^ __builtin_amdgcn_perm(0x47FFFF54u, 0x43FF41FFu, x[i] & 0x07070707u);
+            for (int i = 0; i < 4; ++i) trip_bad |= x[i] ^ __builtin_amdgcn_perm(0x47FFFF54u, 0x43FF41FFu, x[i] & 0x07070707u); // (trip_invalid's LUT)
             u32x4 ac;
             uint32_t g0, g1;
             expand3(x, ac, g0, g1);
@@ -306,7 +357,7 @@ kmer_count3_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, u
             *reinterpret_cast<u32x4 *>(strip + lane * kAc + 512 * m) = ac;
             *reinterpret_cast<u32x2 *>(strip + 2 * kAc + 512 * m + 8 * lane) = u32x2{g0, g1};
         }
-        if (__builtin_expect((trip_bad & 0xDFDFDFDFu) != 0u, 0)) { // some lane of the trip holds an invalid byte: find the round
+        if (__builtin_expect(trip_invalid(trip_bad), 0)) { // some lane of the trip holds an invalid byte: find the round
 #pragma unroll 1
             for (unsigned u = 0; u < m; ++u) rescan_bytes(ref, ((r0 + u) << 10) + 16 * lane, 16, slot);
         }
@@ -321,16 +372,9 @@ kmer_count3_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, u
                 const u32x4 t = *reinterpret_cast<const u32x4 *>(strip + (j < 2 ? rd_ac + 16 * j : rd_g) + 512 * u);
                 B[j] = i32x8{(int)t.x, (int)t.y, (int)t.z, (int)t.w, 0, 0, 0, 0};
             }
-            f32x16 acc = c0;
+            const f32x16 acc = mfma_chain(A, B, c0, scale_a);
 #pragma unroll
-            for (int j = 0; j < 3; ++j) acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A[j], B[j], acc, 4, 4, 0, scale_a, 0, 127);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                // (__float_as_uint on a copy: __builtin_bit_cast applied to a vector ELEMENT reads element 0 whatever the index -- hipcc 7.2)
-                const float d0 = acc[4 * q], d1 = acc[4 * q + 1], d2 = acc[4 * q + 2], d3 = acc[4 * q + 3];
-                const uint32_t x = __float_as_uint(d0) | __float_as_uint(d1) | __float_as_uint(d2);
-                lane_hits += (uint32_t)__builtin_popcount((x | __float_as_uint(d3)) & 0x80020820u);
-            }
+            for (int q = 0; q < 4; ++q) lane_hits += (uint32_t)__builtin_popcount(hit_bits(acc, q));
         }
         r0 = rn;
     }

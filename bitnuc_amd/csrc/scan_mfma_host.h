@@ -12,10 +12,23 @@ struct Count3MfmaTable { uint32_t w[64][12]; float c[4]; };
 struct PackedScanTable { uint32_t w[34][16]; float c[4]; }; // w[m - 2 h + 2]: the packed scan's rows only depend on m - 2 h (scan_packed_table)
 } // namespace bitnuc_dev
 
+namespace bitnuc_dev {
+// Whole rounds of 1024 windows in n bases whose first `skip` are left to the tail threads: round r reads bases [skip + 1024 r, skip + 1024 r + 1056).
+// constexpr: the launchers and the kernels both call it.
+constexpr unsigned long long scan_rounds(unsigned long long n, unsigned skip = 0) {
+    const unsigned long long nr = n > skip ? n - skip : 0; // the bases the rounds see
+    return nr >= 1056 ? (nr - 32) >> 10 : 0;
+}
+} // namespace bitnuc_dev
+
 namespace bitnuc_host {
 using bitnuc_dev::CountMfmaTable;
 using bitnuc_dev::Count3MfmaTable;
 using bitnuc_dev::PackedScanTable;
+
+// The accumulators of the distance pack and of the thresholded count start at 2^23 (plus their fields): the integer results then sit in the low mantissa
+// bits (scan_mfma_device.h: dist_row_scale, count_row_scale).
+constexpr float kPackBias = 8388608.f;
 
 // de-interleave a packed query into its two bit-planes (bit i = low / high code bit of base i)
 inline void query_planes(uint64_t query, size_t k, uint32_t *ql, uint32_t *qh) {
@@ -51,10 +64,10 @@ inline void count_mfma_table(uint64_t query, size_t k, CountMfmaTable *t, bool t
     const unsigned te = all ? (unsigned)k : tau; // tau < k <= 32 otherwise
     for (int j = 0; j < 4; ++j) {
         if (!thresholded) t->c[j] = 0.f;
-        else if (j < 3) t->c[j] = 8388608.f + (float)((match ? 32u + te - (unsigned)k : 32u + te) << (6 * j));
+        else if (j < 3) t->c[j] = kPackBias + (float)((match ? 32u + te - (unsigned)k : 32u + te) << (6 * j));
         else t->c[j] = match ? (float)(2 * (int)k - 2 * (int)te - 1) : -(float)(2 * te + 1);
     }
-    if (all) for (int j = 0; j < 3; ++j) t->c[j] = 8388608.f + (float)(32u << (6 * j)), t->c[3] = -1.f;
+    if (all) for (int j = 0; j < 3; ++j) t->c[j] = kPackBias + (float)(32u << (6 * j)), t->c[3] = -1.f;
     for (int d = -8; d < 32; ++d)
         for (int j = 0; j < 4; ++j)
             for (int i = 0; i < 4; ++i) {
@@ -68,23 +81,44 @@ inline void count_mfma_table(uint64_t query, size_t k, CountMfmaTable *t, bool t
             }
 }
 
-// ... and of the three-channel count (Count3MfmaTable below): per lane (row m = lane & 31, K-block h = lane >> 5) and K-step, the 32 nibbles that meet
-// the lane's operand -- K-steps 0 / 1: the (A, C) bytes of positions 32 s + 16 h + b; K-step 2: the G nibbles of positions 32 h .. + 31, byte b holding positions 8 (b >> 2) + (b & 3) and that + 4.
-// d = #(q_i != T) + sum over the window of v(q_i, channel) x[channel], v = -1 on channel q for q in {A, C, G}, +1 on all three for q = T; rows with m & 3 < 3 carry
-// -v and start at 2^23 + (32 + tau - #(q_i != T)) 2^(6 j) (they end at 32 + tau - d), rows with m & 3 = 3 carry v at scale 2 and start at 2 #(q_i != T) - 2 tau - 1.
-// distance = true (evidence build's three-channel scan): every row carries v and starts at 2^23 + #(q_i != T) 2^(8 j) (j = 3: 2^23 + #): the product is d itself.
-inline void count3_mfma_table(uint64_t query, size_t k, unsigned tau, Count3MfmaTable *t, bool distance = false) {
-    const bool all = !distance && tau >= k;
-    unsigned non_t = 0;
-    for (size_t i = 0; i < k; ++i) non_t += ((query >> (2 * i)) & 3) != 3;
-    auto nibble = [&](int m, int p, unsigned ch) -> uint32_t {
+// The three-channel code (A, C, G one-hot, T = 0) of both count tables (count3_mfma_table, count3_packed_table): d = #(q_i != T) + sum over the window
+// of v(q_i, channel) x[channel], v = -1 on channel q for q in {A, C, G}, +1 on all three for q = T.  Rows with m & 3 < 3 carry -v and start at
+// 2^23 + (32 + tau - #(q_i != T)) 2^(6 j) (they end at 32 + tau - d), rows with m & 3 = 3 carry v at scale 2 and start at 2 #(q_i != T) - 2 tau - 1.
+// distance = true (evidence build's three-channel scan): every row carries v and starts at 2^23 + #(q_i != T) 2^(8 j) (j = 3: 2^23 + #): the product is d
+// itself.  A threshold no window can miss (tau >= k) gets all-zero entries and the start values of an empty query (every field 32, every j = 3 result -1).
+struct Count3Rule {
+    uint64_t query;
+    size_t k;
+    unsigned tau;
+    bool distance, all;
+    unsigned non_t;
+    Count3Rule(uint64_t query, size_t k, unsigned tau, bool distance) : query(query), k(k), tau(tau), distance(distance), all(!distance && tau >= k), non_t(0) {
+        for (size_t i = 0; i < k; ++i) non_t += ((query >> (2 * i)) & 3) != 3;
+    }
+    // the nibble row m meets at segment position p on channel ch (0 = A, 1 = C, 2 = G): 0, +1.0 (0x2) or -1.0 (0xA)
+    uint32_t nibble(int m, int p, unsigned ch) const {
         const int i = p - m;
         if (all || i < 0 || i >= (int)k) return 0u;
         const unsigned q = (unsigned)((query >> (2 * i)) & 3);
         const int v = q == 3 ? 1 : (ch == q ? -1 : 0);
         const int e = distance || (m & 3) == 3 ? v : -v;
         return e == 0 ? 0u : e > 0 ? 0x2u : 0xAu;
-    };
+    }
+    void start(float *c) const {
+        if (distance) {
+            for (int j = 0; j < 4; ++j) c[j] = kPackBias + (float)(non_t << (j == 3 ? 0 : 8 * j));
+            return;
+        }
+        for (int j = 0; j < 3; ++j) c[j] = kPackBias + (float)((all ? 32u : 32u + tau - non_t) << (6 * j));
+        c[3] = all ? -1.f : (float)(2 * (int)non_t - 2 * (int)tau - 1);
+    }
+};
+
+// ... its table in the ASCII K order: per lane (row m = lane & 31, K-block h = lane >> 5) and K-step, the 32 nibbles that meet the lane's operand --
+// K-steps 0 / 1: the (A, C) bytes of positions 32 s + 16 h + b; K-step 2: the G nibbles of positions 32 h .. + 31, byte b holding positions 8 (b >> 2) + (b & 3)
+// and that + 4.
+inline void count3_mfma_table(uint64_t query, size_t k, unsigned tau, Count3MfmaTable *t, bool distance = false) {
+    const Count3Rule r(query, k, tau, distance);
     for (int lane = 0; lane < 64; ++lane) {
         const int m = lane & 31, h = lane >> 5;
         for (int s = 0; s < 3; ++s)
@@ -93,19 +127,14 @@ inline void count3_mfma_table(uint64_t query, size_t k, unsigned tau, Count3Mfma
                 for (int bb = 0; bb < 4; ++bb) {
                     const int b = 4 * i + bb;
                     const int gp = 32 * h + 8 * (b >> 2) + (b & 3); // K-step 2, byte b of the lane's 16: bases gp (low nibble) and gp + 4 (high nibble) of positions 32 h .. + 31
-                    const uint32_t lo = s < 2 ? nibble(m, 32 * s + 16 * h + b, 0) : nibble(m, gp, 2);
-                    const uint32_t hi = s < 2 ? nibble(m, 32 * s + 16 * h + b, 1) : nibble(m, gp + 4, 2);
+                    const uint32_t lo = s < 2 ? r.nibble(m, 32 * s + 16 * h + b, 0) : r.nibble(m, gp, 2);
+                    const uint32_t hi = s < 2 ? r.nibble(m, 32 * s + 16 * h + b, 1) : r.nibble(m, gp + 4, 2);
                     w |= (lo | hi << 4) << (8 * bb);
                 }
                 t->w[lane][4 * s + i] = w;
             }
     }
-    if (distance) {
-        for (int j = 0; j < 4; ++j) t->c[j] = 8388608.f + (float)(non_t << (j == 3 ? 0 : 8 * j));
-        return;
-    }
-    for (int j = 0; j < 3; ++j) t->c[j] = 8388608.f + (float)((all ? 32u : 32u + tau - non_t) << (6 * j));
-    t->c[3] = all ? -1.f : (float)(2 * (int)non_t - 2 * (int)tau - 1);
+    r.start(t->c);
 }
 
 // ---- the packed scan and count (scan_packed_device.h): the same products, with the one-hot operand built from 2-bit codes ----------------------------
@@ -130,24 +159,14 @@ inline void scan_packed_table(uint64_t query, size_t k, PackedScanTable *t) {
                 }
                 t->w[delta + 2][4 * j + d] = w;
             }
-    for (int j = 0; j < 4; ++j) t->c[j] = 8388608.f;
+    for (int j = 0; j < 4; ++j) t->c[j] = kPackBias;
 }
 
 // The count (three channels per base: A, C, G one-hot, T = 0), as count3_mfma_table but in the packed K order.  K-steps 0 / 1: dword t, byte q holds
 // the (A, C) nibbles of position 16 (2 s + h) + 4 q + t; K-step 2: dword d, nibble p (byte p >> 1, high nibble when p is odd) holds the G nibble of
-// position 32 h + 16 (d >> 1) + 2 p + (d & 1).  Rows, signs, row scales and start values are count3_mfma_table's.
+// position 32 h + 16 (d >> 1) + 2 p + (d & 1).  Rows, signs, row scales and start values: Count3Rule.
 inline void count3_packed_table(uint64_t query, size_t k, unsigned tau, Count3MfmaTable *t) {
-    const bool all = tau >= k;
-    unsigned non_t = 0;
-    for (size_t i = 0; i < k; ++i) non_t += ((query >> (2 * i)) & 3) != 3;
-    auto nibble = [&](int m, int p, unsigned ch) -> uint32_t {
-        const int i = p - m;
-        if (all || i < 0 || i >= (int)k) return 0u;
-        const unsigned q = (unsigned)((query >> (2 * i)) & 3);
-        const int v = q == 3 ? 1 : (ch == q ? -1 : 0);
-        const int e = (m & 3) == 3 ? v : -v;
-        return e == 0 ? 0u : e > 0 ? 0x2u : 0xAu;
-    };
+    const Count3Rule r(query, k, tau, false);
     for (int lane = 0; lane < 64; ++lane) {
         const int m = lane & 31, h = lane >> 5;
         for (int s = 0; s < 3; ++s)
@@ -157,18 +176,17 @@ inline void count3_packed_table(uint64_t query, size_t k, unsigned tau, Count3Mf
                     uint32_t lo, hi;
                     if (s < 2) {
                         const int p = 16 * (2 * s + h) + 4 * b + d;
-                        lo = nibble(m, p, 0), hi = nibble(m, p, 1);
+                        lo = r.nibble(m, p, 0), hi = r.nibble(m, p, 1);
                     } else {
                         const int p = 32 * h + 16 * (d >> 1) + 4 * b + (d & 1); // nibble 2 b; nibble 2 b + 1 is two positions later
-                        lo = nibble(m, p, 2), hi = nibble(m, p + 2, 2);
+                        lo = r.nibble(m, p, 2), hi = r.nibble(m, p + 2, 2);
                     }
                     w |= (lo | hi << 4) << (8 * b);
                 }
                 t->w[lane][4 * s + d] = w;
             }
     }
-    for (int j = 0; j < 3; ++j) t->c[j] = 8388608.f + (float)((all ? 32u : 32u + tau - non_t) << (6 * j));
-    t->c[3] = all ? -1.f : (float)(2 * (int)non_t - 2 * (int)tau - 1);
+    r.start(t->c);
 }
 
 } // namespace bitnuc_host

@@ -24,7 +24,7 @@
 // byte offset (gfx950 unaligned-access mode).  The windows that whole rounds do not cover, and all windows of n < 1056 (+ skip), are the tail threads'.
 #pragma once
 #include "device_prims.h"
-#include "scan_mfma_device.h" // i32x8, f32x16
+#include "scan_mfma_device.h" // i32x8, f32x16 and the back end: query_operand ... hit_bits
 #include "scan_mfma_host.h"
 
 namespace bitnuc_dev {
@@ -76,9 +76,8 @@ packed_scan_mfma_kernel(const uint64_t *__restrict__ words, unsigned long long n
                         const PackedScanTable tab) {
     __shared__ __attribute__((aligned(16))) uint8_t strip[8 * kPackedRegion];
     const unsigned long long nwin = n - k + 1;
-    const unsigned long long nr = n > skip ? n - skip : 0; // bases the rounds see (skip = 0 or 32)
     const unsigned long long pre = skip < nwin ? skip : nwin; // windows before the rounds: the tail threads'
-    const unsigned long long rounds = nr >= 1056 ? (nr - 32) >> 10 : 0;
+    const unsigned long long rounds = scan_rounds(n, skip);    // skip = 0 or 32
     const uint8_t *base = reinterpret_cast<const uint8_t *>(words + (skip >> 5)); // 16-byte aligned
     uint8_t *dst = dist + skip;
     const unsigned lane = threadIdx.x & 63;
@@ -91,17 +90,9 @@ packed_scan_mfma_kernel(const uint64_t *__restrict__ words, unsigned long long n
         if (lane < 2) hx = *reinterpret_cast<const uint32_t *>(base + ((r0 + m) << 8) + 4u * lane); // the halo: groups 0 and 1 of round m
         const unsigned m32 = lane & 31u, hh = lane >> 5;
         i32x8 A[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            A[j] = i32x8{0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) A[j][i] = (int)tab.w[m32 + 2u - 2u * hh][4 * j + i];
-        }
-        const int scale_a = 127 + 8 * (int)((m32 & 3u) == 3u ? 0u : (m32 & 3u)); // E8M0: 2^(8 (row & 3)) for row & 3 < 3
-        f32x16 c0;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) c0[i] = tab.c[i & 3]; // 2^23
-        asm volatile("" : "+v"(c0));
+        query_operand<4>(tab.w[m32 + 2u - 2u * hh], A);
+        const int scale_a = dist_row_scale(m32);
+        const f32x16 c0 = acc_start(tab.c); // 2^23
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             u32x4 e0, e1;
@@ -131,18 +122,9 @@ packed_scan_mfma_kernel(const uint64_t *__restrict__ words, unsigned long long n
                 const u32x4 t = *reinterpret_cast<const u32x4 *>(strip + rd[j] + 256u * u);
                 B[j] = i32x8{(int)t.x, (int)t.y, (int)t.z, (int)t.w, 0, 0, 0, 0};
             }
-            f32x16 acc = c0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A[j], B[j], acc, 4, 4, 0, scale_a, 0, 127);
             uint32_t o[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float d0 = acc[4 * q], d1 = acc[4 * q + 1], d2 = acc[4 * q + 2], d3 = acc[4 * q + 3];
-                o[q] = __builtin_amdgcn_perm(__float_as_uint(d3), __float_as_uint(d0) | __float_as_uint(d1) | __float_as_uint(d2), 0x04020100u);
-            }
-            const auto s02 = __builtin_amdgcn_permlane32_swap(o[0], o[2], false, false);
-            const auto s13 = __builtin_amdgcn_permlane32_swap(o[1], o[3], false, false);
-            __builtin_nontemporal_store(u32x4{s02[0], s02[1], s13[0], s13[1]}, reinterpret_cast<u32x4_u *>(dst + ((r0 + u) << 10) + 16u * (2u * m32 + hh)));
+            pack_distances(mfma_chain(A, B, c0, scale_a), o);
+            store_distances<true, false>(dst + ((r0 + u) << 10) + 16u * (2u * m32 + hh), o);
         }
     }
     packed_tail_windows<false>(words, pre, skip + (rounds << 10), nwin, k, query, 0u, dist);
@@ -167,9 +149,8 @@ packed_count3_mfma_kernel(const uint64_t *__restrict__ words, unsigned long long
     constexpr int kG0 = 4 * kPackedRegion;
     __shared__ __attribute__((aligned(16))) uint8_t strips[kBlock / 64][4 * kPackedRegion + 2 * kPackedGRegion];
     const unsigned long long nwin = n - k + 1;
-    const unsigned long long nr = n > skip ? n - skip : 0; // bases the rounds see (skip = 0 or 32)
     const unsigned long long pre = skip < nwin ? skip : nwin; // windows before the rounds: the tail threads'
-    const unsigned long long rounds = nr >= 1056 ? (nr - 32) >> 10 : 0;
+    const unsigned long long rounds = scan_rounds(n, skip);    // skip = 0 or 32
     const uint8_t *base = reinterpret_cast<const uint8_t *>(words + (skip >> 5));
     const unsigned lane = threadIdx.x & 63;
     const unsigned long long wave = (unsigned long long)blockIdx.x * (blockDim.x >> 6) + wave_in_block();
@@ -189,22 +170,12 @@ packed_count3_mfma_kernel(const uint64_t *__restrict__ words, unsigned long long
     if (r0 < rounds) load_trip(r0);
     const unsigned m32 = lane & 31u, hh = lane >> 5;
     i32x8 A[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        A[j] = i32x8{0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) A[j][i] = (int)tab.w[lane][4 * j + i];
-    }
-    // the table's registers used before the loop (kmer_count3_mfma_kernel: otherwise the first MFMA of every trip waits for the next trip's loads)
+    query_operand<3>(tab.w[lane], A);
     asm volatile("" : "+v"(A[0][0]), "+v"(A[0][1]), "+v"(A[0][2]), "+v"(A[0][3]), "+v"(A[1][0]), "+v"(A[1][1]), "+v"(A[1][2]), "+v"(A[1][3]),
                       "+v"(A[2][0]), "+v"(A[2][1]), "+v"(A[2][2]), "+v"(A[2][3]));
     uint32_t lane_hits = 0;
-    const unsigned jrow = m32 & 3u;
-    const int scale_a = 127 + (jrow == 3u ? 1 : 6 * (int)jrow);
-    f32x16 c0;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) c0[i] = tab.c[i & 3];
-    asm volatile("" : "+v"(c0));
+    const int scale_a = count_row_scale(m32);
+    const f32x16 c0 = acc_start(tab.c);
     unsigned rd[3];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -245,15 +216,9 @@ packed_count3_mfma_kernel(const uint64_t *__restrict__ words, unsigned long long
                 const u32x4 t = *reinterpret_cast<const u32x4 *>(strip + rd[j] + 256u * u);
                 B[j] = i32x8{(int)t.x, (int)t.y, (int)t.z, (int)t.w, 0, 0, 0, 0};
             }
-            f32x16 acc = c0;
+            const f32x16 acc = mfma_chain(A, B, c0, scale_a);
 #pragma unroll
-            for (int j = 0; j < 3; ++j) acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A[j], B[j], acc, 4, 4, 0, scale_a, 0, 127);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float d0 = acc[4 * q], d1 = acc[4 * q + 1], d2 = acc[4 * q + 2], d3 = acc[4 * q + 3];
-                const uint32_t y = __float_as_uint(d0) | __float_as_uint(d1) | __float_as_uint(d2);
-                lane_hits += (uint32_t)__builtin_popcount((y | __float_as_uint(d3)) & 0x80020820u);
-            }
+            for (int q = 0; q < 4; ++q) lane_hits += (uint32_t)__builtin_popcount(hit_bits(acc, q));
         }
         r0 = rn;
     }
