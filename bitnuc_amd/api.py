@@ -522,9 +522,8 @@ class Context:
         self._call_dev(self._lib.bitnuc_nucgen_dev, _dev_ptr(d_out), int(length), C.c_uint64(seed), C.c_uint64(first), int(flags))
 
     def host_pipe_info(self):
-        """Configuration and creation-time measurements of the pipelined host-pointer path (creates it if needed)."""
-        names = ["cores_visible", "cores_quota", "cores_usable", "chunk_bases", "depth", "encode_stage_in_threads", "encode_hand_back_threads",
-                 "decode_stage_in_threads", "decode_hand_back_threads", "heavy_side_thread_cap", "gpu_numa_node", "workers_bound_to_cpus", "direct_engine"]
+        """Configuration of the pipelined host-pointer path (creates it if needed): bases per chunk and chunks in flight."""
+        names = ["chunk_bases", "depth"]
         out = (C.c_double * len(names))()
         err = L.BitnucErr()
         if self._lib.bitnuc_host_pipe_info(self._h, out, len(names), C.byref(err)) != L.OK:

@@ -391,51 +391,35 @@ int bitnuc_decode_fixed_dev(bitnuc_ctx *c, const uint64_t *d_words, size_t read_
     return BITNUC_OK;
 }
 
-// Host-pointer fixed-length reads through the pipelined staging engine (host_pipe.h): a chunk is as many whole reads as fit both
-// pinned buffers (their bytes in an A buffer, their words in a B buffer; decode the other way round).
-constexpr int kNotPipelined = -1; // not a bitnuc_status: "this shape does not fit the engine, use the staged loop"
-static int fixed_pipelined(bitnuc_ctx *c, bool encode, const uint8_t *seq, const uint64_t *words, size_t read_len, size_t stride, size_t count,
-                           uint64_t *out_words, uint8_t *out_seq, bitnuc_err *err) {
-    HostPipe *p;
-    if (int st = pipe_get(c, &p, err)) return st;
-    const size_t wpr = words_for(read_len);
-    size_t per = (p->chunk / 4) / (8 * wpr);
-    const size_t by_bytes = p->chunk > read_len ? (p->chunk - read_len) / stride + 1 : 0;
-    if (by_bytes < per) per = by_bytes;
-    // a read larger than a chunk (today unreachable: the callers admit read_len, stride < 1 Mi and a chunk is at least 1 MiB): nothing
-    // has been started, the pipe is intact, the caller goes on to its staged-scratch loop
-    if (per == 0) return kNotPipelined;
-    PipeAbort guard{c, p};
-    struct Job {
-        bitnuc_ctx *c; bool encode; const uint8_t *seq; const uint64_t *words; size_t read_len, stride, count, per, wpr; uint64_t *out_words; uint8_t *out_seq;
-        size_t nchunks; int in_kind, out_kind, in_threads, out_threads;
-        size_t items(size_t ci) const { return count - ci * per < per ? count - ci * per : per; }
-        size_t seq_bytes(size_t ci) const { return (items(ci) - 1) * stride + read_len; }
-        const void *in_src(size_t ci) const { return encode ? static_cast<const void *>(seq + ci * per * stride) : static_cast<const void *>(words + ci * per * wpr); }
-        size_t in_bytes(size_t ci) const { return encode ? seq_bytes(ci) : items(ci) * wpr * 8; }
-        void *out_dst(size_t ci) const { return encode ? static_cast<void *>(out_words + ci * per * wpr) : static_cast<void *>(out_seq + ci * per * stride); }
-        size_t out_bytes(size_t ci) const { return encode ? items(ci) * wpr * 8 : seq_bytes(ci); }
-        int launch(size_t ci, const uint8_t *d_in, uint8_t *d_out, bitnuc_err *err) const {
-            if (encode) {
-                if (int st = bitnuc_encode_fixed_dev(c, d_in, read_len, stride, items(ci), reinterpret_cast<uint64_t *>(d_out), err)) return st;
-                set_last_slot_base(c, (unsigned long long)(ci * per) * stride); // report the index in the caller's buffer
-                return BITNUC_OK;
-            }
-            return bitnuc_decode_fixed_dev(c, reinterpret_cast<const uint64_t *>(d_in), read_len, stride, items(ci), d_out, err);
-        }
-    } job{c, encode, seq, words, read_len, stride, count, per, wpr, out_words, out_seq, (count + per - 1) / per};
-    job.in_kind = encode ? kBufA : kBufB;
-    job.out_kind = encode ? kBufB : kBufA;
-    job.in_threads = encode ? p->enc_in : p->dec_in;
-    job.out_threads = encode ? p->enc_out : p->dec_out;
-    if (int st = pipe_run(c, p, job, err)) return st;
-    bitnuc_err e;
-    const int st = drain(c, &e);
-    if (st == BITNUC_BACKEND_ERROR) { if (err) *err = e; return st; }
-    guard.dismissed = true;
-    if (st != BITNUC_OK) { if (err) *err = e; return st; }
-    return BITNUC_OK;
-}
+// Host-pointer fixed-length reads: a job of host_pipe.h whose items are reads.  A pipe chunk is as many whole reads as fit both
+// buffers (their bytes in an A buffer, their words in a B buffer; decode the other way round).
+namespace {
+struct FixedJob {
+    bitnuc_ctx *c; bool encode; const uint8_t *seq; const uint64_t *words; size_t read_len, stride, count; uint64_t *out_words; uint8_t *out_seq;
+    int in_kind, out_kind;
+    bool drains, inout; // encode latches errors; decode with separators copies the caller's bytes between reads in so they go back unchanged
+    size_t wpr;
+    FixedJob(bitnuc_ctx *c, bool encode, const uint8_t *seq, const uint64_t *words, size_t read_len, size_t stride, size_t count, uint64_t *out_words, uint8_t *out_seq)
+        : c(c), encode(encode), seq(seq), words(words), read_len(read_len), stride(stride), count(count), out_words(out_words), out_seq(out_seq),
+          in_kind(encode ? kBufA : kBufB), out_kind(encode ? kBufB : kBufA), drains(encode), inout(!encode && stride != read_len), wpr(words_for(read_len)) {}
+    size_t pipe_per(size_t chunk) const { // 0 for a read larger than a chunk (today unreachable: the callers admit read_len, stride < 1 Mi)
+        const size_t per = (chunk / 4) / (8 * wpr), by_bytes = chunk > read_len ? (chunk - read_len) / stride + 1 : 0;
+        return by_bytes < per ? by_bytes : per;
+    }
+    size_t scratch_per() const { return kHostChunk / stride; }
+    size_t seq_bytes(size_t m) const { return (m - 1) * stride + read_len; }
+    const void *in_src(size_t i0) const { return encode ? static_cast<const void *>(seq + i0 * stride) : static_cast<const void *>(words + i0 * wpr); }
+    size_t in_bytes(size_t m) const { return encode ? seq_bytes(m) : m * wpr * 8; }
+    void *out_dst(size_t i0) const { return encode ? static_cast<void *>(out_words + i0 * wpr) : static_cast<void *>(out_seq + i0 * stride); }
+    size_t out_bytes(size_t m) const { return encode ? m * wpr * 8 : seq_bytes(m); }
+    int launch(size_t i0, size_t m, const uint8_t *d_in, uint8_t *d_out, bitnuc_err *err) const {
+        if (!encode) return bitnuc_decode_fixed_dev(c, reinterpret_cast<const uint64_t *>(d_in), read_len, stride, m, d_out, err);
+        if (int st = bitnuc_encode_fixed_dev(c, d_in, read_len, stride, m, reinterpret_cast<uint64_t *>(d_out), err)) return st;
+        set_last_slot_base(c, (unsigned long long)i0 * stride); // report the index in the caller's buffer
+        return BITNUC_OK;
+    }
+};
+} // namespace
 
 int bitnuc_encode_fixed(bitnuc_ctx *c, const uint8_t *seq, size_t read_len, size_t stride, size_t count, uint64_t *out, bitnuc_err *err) {
     clear_err(err);
@@ -444,28 +428,8 @@ int bitnuc_encode_fixed(bitnuc_ctx *c, const uint8_t *seq, size_t read_len, size
     if (stride < read_len || !seq || !out) return fail(err, BITNUC_UNSUPPORTED);
     DeviceGuard g(c->device);
     if (int st = flush_pending(c, err)) return st;
-    if (c->host_pipeline && (count - 1) * stride + read_len >= kPipeMin && stride < ((size_t)1 << 20)) {
-        const int st = fixed_pipelined(c, true, seq, nullptr, read_len, stride, count, out, nullptr, err);
-        if (st != kNotPipelined) return st;
-    }
-    const size_t wpr = words_for(read_len);
-    size_t per = kHostChunk / stride; // reads per staged chunk
-    if (per == 0) per = 1;
-    if (per > count) per = count;
-    if (int st = ensure_scratch(c, 0, (per - 1) * stride + read_len + 16, err)) return st;
-    if (int st = ensure_scratch(c, 1, per * wpr * 8 + 16, err)) return st;
-    for (size_t r0 = 0; r0 < count; r0 += per) {
-        const size_t m = count - r0 < per ? count - r0 : per;
-        const size_t bytes = (m - 1) * stride + read_len;
-        HIPCHK(hipMemcpyAsync(c->scratch[0], seq + r0 * stride, bytes, hipMemcpyHostToDevice, c->stream));
-        bitnuc_err e;
-        if (int st = bitnuc_encode_fixed_dev(c, c->scratch[0], read_len, stride, m, reinterpret_cast<uint64_t *>(c->scratch[1]), &e)) { if (err) *err = e; return st; }
-        set_last_slot_base(c, (unsigned long long)r0 * stride); // report the index in the caller's buffer
-        HIPCHK(hipMemcpyAsync(out + r0 * wpr, c->scratch[1], m * wpr * 8, hipMemcpyDeviceToHost, c->stream));
-        int st = drain(c, &e);
-        if (st != BITNUC_OK) { if (err) *err = e; return st; }
-    }
-    return BITNUC_OK;
+    const FixedJob job(c, true, seq, nullptr, read_len, stride, count, out, nullptr);
+    return c->host_pipeline && (count - 1) * stride + read_len >= kPipeMin && stride < ((size_t)1 << 20) ? pipe_run(c, job, err) : scratch_run(c, job, err);
 }
 
 int bitnuc_decode_fixed(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t stride, size_t count, uint8_t *out, bitnuc_err *err) {
@@ -474,29 +438,13 @@ int bitnuc_decode_fixed(bitnuc_ctx *c, const uint64_t *words, size_t read_len, s
     if (count == 0 || read_len == 0) return BITNUC_OK;
     if (stride < read_len || !words || !out) return fail(err, BITNUC_UNSUPPORTED);
     DeviceGuard g(c->device);
+    const FixedJob job(c, false, nullptr, words, read_len, stride, count, nullptr, out);
     // back-to-back reads only: with separators the bytes between reads are the caller's and would have to travel both ways
     if (c->host_pipeline && stride == read_len && count * read_len >= kPipeMin && read_len < ((size_t)1 << 20)) {
         if (int st = flush_pending(c, err)) return st;
-        const int st = fixed_pipelined(c, false, nullptr, words, read_len, stride, count, nullptr, out, err);
-        if (st != kNotPipelined) return st;
+        return pipe_run(c, job, err);
     }
-    const size_t wpr = words_for(read_len);
-    size_t per = kHostChunk / stride;
-    if (per == 0) per = 1;
-    if (per > count) per = count;
-    if (int st = ensure_scratch(c, 0, (per - 1) * stride + read_len + 16, err)) return st;
-    if (int st = ensure_scratch(c, 1, per * wpr * 8 + 16, err)) return st;
-    for (size_t r0 = 0; r0 < count; r0 += per) {
-        const size_t m = count - r0 < per ? count - r0 : per;
-        const size_t bytes = (m - 1) * stride + read_len;
-        HIPCHK(hipMemcpyAsync(c->scratch[1], words + r0 * wpr, m * wpr * 8, hipMemcpyHostToDevice, c->stream));
-        if (stride != read_len) // separator bytes are the caller's: bring them in so they go back unchanged
-            HIPCHK(hipMemcpyAsync(c->scratch[0], out + r0 * stride, bytes, hipMemcpyHostToDevice, c->stream));
-        if (int st = bitnuc_decode_fixed_dev(c, reinterpret_cast<const uint64_t *>(c->scratch[1]), read_len, stride, m, c->scratch[0], err)) return st;
-        HIPCHK(hipMemcpyAsync(out + r0 * stride, c->scratch[0], bytes, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    return BITNUC_OK;
+    return scratch_run(c, job, err);
 }
 
 } // extern "C"

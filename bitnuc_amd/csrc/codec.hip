@@ -8,12 +8,10 @@
 #include "host_pipe.h"
 #include "host_word.h"
 
-#include <stdlib.h>
 #include <time.h>
 
 using namespace bitnuc_dev;
 using namespace bitnuc_rt;
-using bitnuc_host::CopyPool;
 
 namespace {
 
@@ -115,71 +113,43 @@ int codec_num_variants() { return kNumVariants; }
 int codec_ballot_variant() { return kEvidenceBuild ? kBallotVariant : -1; }
 } // namespace bitnuc_rt
 
-// ---- pipelined host-pointer path: host_pipe.h -------------------------------------------------------
+// ---- host-pointer jobs: host_pipe.h ---------------------------------------------------------------
 namespace {
 
-// encode / decode of a large pageable buffer through the engine of host_pipe.h.
-// On INVALID_BASE the pipeline has still run every chunk and handed every chunk's words back: out[*n_words ..] is
-// unspecified (include/bitnuc_hip.h), the words before the failing 32-base group are the reference's Vec contents.
-int encode_pipelined(bitnuc_ctx *c, const uint8_t *seq, size_t len, uint64_t *out, size_t *n_words, bitnuc_err *err) {
-    HostPipe *p;
-    if (int st = pipe_get(c, &p, err)) return st;
-    PipeAbort guard{c, p};
-    struct Job {
-        bitnuc_ctx *c; const uint8_t *seq; size_t len, chunk; uint64_t *out;
-        size_t nchunks; int in_kind = kBufA, out_kind = kBufB, in_threads, out_threads;
-        size_t bases(size_t ci) const { return len - ci * chunk < chunk ? len - ci * chunk : chunk; }
-        const void *in_src(size_t ci) const { return seq + ci * chunk; }
-        size_t in_bytes(size_t ci) const { return bases(ci); }
-        void *out_dst(size_t ci) const { return out + ci * (chunk / 32); }
-        size_t out_bytes(size_t ci) const { return words_for(bases(ci)) * 8; }
-        int launch(size_t ci, const uint8_t *d_in, uint8_t *d_out, bitnuc_err *err) const {
-            unsigned long long *slot;
-            if (int st = take_slot(c, ci * chunk, &slot, err)) return st;
-            HIPCHK(launch_encode(c, d_in, reinterpret_cast<uint64_t *>(d_out), bases(ci), slot));
-            return BITNUC_OK;
-        }
-    } job{c, seq, len, p->chunk, out, (len + p->chunk - 1) / p->chunk};
-    job.in_threads = p->enc_in;
-    job.out_threads = p->enc_out;
-    if (int st = pipe_run(c, p, job, err)) return st;
-    bitnuc_err e;
-    const int st = drain(c, &e); // one drain at the end: slots are examined in launch order = sequence order
-    if (st == BITNUC_BACKEND_ERROR) { if (err) *err = e; return st; }
-    guard.dismissed = true; // every stream has been waited for (the D2H events by the host, the kernels by the drain)
-    if (st != BITNUC_OK) {
-        if (err) *err = e;
-        if (st == BITNUC_INVALID_BASE && n_words) *n_words = (size_t)(e.index / 32);
-        return st;
+// items are bases; the pipe's chunks are a multiple of 32 bases, the scratch loop's too (or the whole input)
+struct EncodeJob {
+    bitnuc_ctx *c; const uint8_t *seq; uint64_t *out; size_t count;
+    static constexpr int in_kind = kBufA, out_kind = kBufB;
+    static constexpr bool drains = true, inout = false;
+    size_t pipe_per(size_t chunk) const { return chunk; }
+    size_t scratch_per() const { return kHostChunk; }
+    const void *in_src(size_t i0) const { return seq + i0; }
+    size_t in_bytes(size_t m) const { return m; }
+    void *out_dst(size_t i0) const { return out + i0 / 32; }
+    size_t out_bytes(size_t m) const { return words_for(m) * 8; }
+    int launch(size_t i0, size_t m, const uint8_t *d_in, uint8_t *d_out, bitnuc_err *err) const {
+        unsigned long long *slot;
+        if (int st = take_slot(c, i0, &slot, err)) return st;
+        HIPCHK(launch_encode(c, d_in, reinterpret_cast<uint64_t *>(d_out), m, slot));
+        return BITNUC_OK;
     }
-    if (n_words) *n_words = words_for(len);
-    return BITNUC_OK;
-}
+};
 
-int decode_pipelined(bitnuc_ctx *c, const uint64_t *ebuf, size_t n_bases, uint8_t *out, bitnuc_err *err) {
-    HostPipe *p;
-    if (int st = pipe_get(c, &p, err)) return st;
-    PipeAbort guard{c, p};
-    struct Job {
-        bitnuc_ctx *c; const uint64_t *ebuf; size_t n_bases, chunk; uint8_t *out;
-        size_t nchunks; int in_kind = kBufB, out_kind = kBufA, in_threads, out_threads;
-        size_t bases(size_t ci) const { return n_bases - ci * chunk < chunk ? n_bases - ci * chunk : chunk; }
-        const void *in_src(size_t ci) const { return ebuf + ci * (chunk / 32); }
-        size_t in_bytes(size_t ci) const { return words_for(bases(ci)) * 8; }
-        void *out_dst(size_t ci) const { return out + ci * chunk; }
-        size_t out_bytes(size_t ci) const { return bases(ci); }
-        int launch(size_t ci, const uint8_t *d_in, uint8_t *d_out, bitnuc_err *err) const {
-            HIPCHK(launch_decode(c, reinterpret_cast<const uint64_t *>(d_in), d_out, bases(ci)));
-            return BITNUC_OK;
-        }
-    } job{c, ebuf, n_bases, p->chunk, out, (n_bases + p->chunk - 1) / p->chunk};
-    job.in_threads = p->dec_in;
-    job.out_threads = p->dec_out;
-    if (int st = pipe_run(c, p, job, err)) return st;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    guard.dismissed = true;
-    return BITNUC_OK;
-}
+struct DecodeJob {
+    bitnuc_ctx *c; const uint64_t *ebuf; uint8_t *out; size_t count;
+    static constexpr int in_kind = kBufB, out_kind = kBufA;
+    static constexpr bool drains = false, inout = false;
+    size_t pipe_per(size_t chunk) const { return chunk; }
+    size_t scratch_per() const { return kHostChunk; }
+    const void *in_src(size_t i0) const { return ebuf + i0 / 32; }
+    size_t in_bytes(size_t m) const { return words_for(m) * 8; }
+    void *out_dst(size_t i0) const { return out + i0; }
+    size_t out_bytes(size_t m) const { return m; }
+    int launch(size_t, size_t m, const uint8_t *d_in, uint8_t *d_out, bitnuc_err *err) const {
+        HIPCHK(launch_decode(c, reinterpret_cast<const uint64_t *>(d_in), d_out, m));
+        return BITNUC_OK;
+    }
+};
 
 } // namespace
 
@@ -207,8 +177,7 @@ int encode_dev_at(bitnuc_ctx *c, const uint8_t *d_seq, size_t len, uint64_t *d_o
 extern "C" {
 
 // Diagnostic (bench.py's host_path block): how the pipelined host-pointer path of this context is configured.  Creates the pipe if
-// this context has none yet.  out[0..n): cores_visible, cores_quota (0 = none), cores_usable, chunk_bases, depth, enc_in, enc_out,
-// dec_in, dec_out (copy threads), heavy_cap, the GPU's NUMA node (-1 = unknown), CPUs of that node the workers are bound to (0 = free).
+// this context has none yet.  out[0..n): chunk_bases, depth; 0 past them.
 int bitnuc_host_pipe_info(bitnuc_ctx *c, double *out, int n, bitnuc_err *err) {
     clear_err(err);
     if (int st = check_ctx(c, err)) return st;
@@ -216,10 +185,8 @@ int bitnuc_host_pipe_info(bitnuc_ctx *c, double *out, int n, bitnuc_err *err) {
     DeviceGuard g(c->device);
     HostPipe *p;
     if (int st = pipe_get(c, &p, err)) return st;
-    const double v[13] = {(double)p->cores_visible, (double)p->cores_quota, (double)p->cores_usable, (double)p->chunk, (double)kPipeDepth,
-                          (double)p->enc_in, (double)p->enc_out, (double)p->dec_in, (double)p->dec_out, (double)p->heavy_cap,
-                          (double)p->numa_node, (double)p->bound_cpus, (double)c->pipe_impl};
-    for (int i = 0; i < n; ++i) out[i] = i < 13 ? v[i] : 0.0;
+    const double v[2] = {(double)p->chunk, (double)kPipeDepth};
+    for (int i = 0; i < n; ++i) out[i] = i < 2 ? v[i] : 0.0;
     return BITNUC_OK;
 }
 
@@ -318,29 +285,15 @@ int bitnuc_encode(bitnuc_ctx *c, const uint8_t *seq, size_t len, uint64_t *out, 
     if (int st = check_ctx(c, err)) return st;
     DeviceGuard g(c->device);
     if (int st = flush_pending(c, err)) return st;
-    if (c->host_pipeline && len >= kPipeMin) return encode_pipelined(c, seq, len, out, n_words, err);
-    const size_t chunk = len < kHostChunk ? len : kHostChunk;
-    if (int st = ensure_scratch(c, 0, chunk + 16, err)) return st;
-    if (int st = ensure_scratch(c, 1, words_for(chunk) * 8 + 16, err)) return st;
-    for (size_t off = 0; off < len; off += chunk) {
-        const size_t n = len - off < chunk ? len - off : chunk;
-        const size_t nw = words_for(n);
-        HIPCHK(hipMemcpyAsync(c->scratch[0], seq + off, n, hipMemcpyHostToDevice, c->stream));
-        unsigned long long *slot;
-        if (int st = take_slot(c, off, &slot, err)) return st;
-        HIPCHK(launch_encode(c, c->scratch[0], reinterpret_cast<uint64_t *>(c->scratch[1]), n, slot));
-        HIPCHK(hipMemcpyAsync(out + off / 32, c->scratch[1], nw * 8, hipMemcpyDeviceToHost, c->stream));
-        // the call is synchronous and stops at the first failing chunk (the words before it are the caller's)
-        bitnuc_err e;
-        int st = drain(c, &e);
-        if (st != BITNUC_OK) {
-            if (err) *err = e;
-            if (st == BITNUC_INVALID_BASE && n_words) *n_words = (size_t)(e.index / 32);
-            return st;
-        }
-    }
-    if (n_words) *n_words = words_for(len);
-    return BITNUC_OK;
+    // on INVALID_BASE the pipelined driver has still run every chunk and handed every chunk's words back, the scratch loop stopped at
+    // the failing chunk: out[*n_words ..] is unspecified (include/bitnuc_hip.h), the words before the failing 32-base group are the
+    // reference's Vec contents
+    const EncodeJob job{c, seq, out, len};
+    bitnuc_err e{};
+    const int st = c->host_pipeline && len >= kPipeMin ? pipe_run(c, job, &e) : scratch_run(c, job, &e);
+    if (err) *err = e;
+    if (n_words) *n_words = st == BITNUC_OK ? words_for(len) : st == BITNUC_INVALID_BASE ? (size_t)(e.index / 32) : 0;
+    return st;
 }
 
 int bitnuc_decode(bitnuc_ctx *c, const uint64_t *ebuf, size_t n_words, size_t n_bases, uint8_t *out, bitnuc_err *err) {
@@ -357,19 +310,8 @@ int bitnuc_decode(bitnuc_ctx *c, const uint64_t *ebuf, size_t n_words, size_t n_
     // like every host-pointer call: an InvalidBase latched by earlier asynchronous launches stays for the next bitnuc_ctx_sync
     // (decode itself latches nothing, but the pipeline's abort path drains the ring and would drop it)
     if (int st = flush_pending(c, err)) return st;
-    if (c->host_pipeline && n_bases >= kPipeMin) return decode_pipelined(c, ebuf, n_bases, out, err);
-    const size_t chunk = n_bases < kHostChunk ? n_bases : kHostChunk;
-    if (int st = ensure_scratch(c, 0, chunk + 16, err)) return st;
-    if (int st = ensure_scratch(c, 1, words_for(chunk) * 8 + 16, err)) return st;
-    for (size_t off = 0; off < n_bases; off += chunk) {
-        const size_t n = n_bases - off < chunk ? n_bases - off : chunk;
-        const size_t nw = words_for(n);
-        HIPCHK(hipMemcpyAsync(c->scratch[1], ebuf + off / 32, nw * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(launch_decode(c, reinterpret_cast<const uint64_t *>(c->scratch[1]), c->scratch[0], n));
-        HIPCHK(hipMemcpyAsync(out + off, c->scratch[0], n, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    return BITNUC_OK;
+    const DecodeJob job{c, ebuf, out, n_bases};
+    return c->host_pipeline && n_bases >= kPipeMin ? pipe_run(c, job, err) : scratch_run(c, job, err);
 }
 // ---- single-word API: host code; batches of one on the device when forced ----------------
 int bitnuc_as_2bit(bitnuc_ctx *c, const uint8_t *seq, size_t len, uint64_t *out, bitnuc_err *err) {
@@ -404,34 +346,6 @@ int bitnuc_hdist_scalar(bitnuc_ctx *c, uint64_t u, uint64_t v, size_t len, uint3
     if (c && c->force_gpu) return bitnuc_hdist(c, &u, 1, &v, 1, len, out, err);
     *out = bitnuc_host::hdist_word(u, v, len);
     return BITNUC_OK;
-}
-
-// Diagnostic (tools/host_path.py): GB/s of the staging pool's parallel memcpy of `bytes` with `threads` threads;
-// mode 0: pageable -> pageable, 1: pageable -> pinned (hipHostMalloc), 2: pinned -> pageable.  < 0 on failure.
-double bitnuc_selftime_host_copy(size_t bytes, int threads, int mode) {
-    if (bytes < 4096 || threads < 1 || threads > 64 || mode < 0 || mode > 2) return -1.0;
-    uint8_t *page = static_cast<uint8_t *>(malloc(bytes)), *other = nullptr;
-    if (!page) return -1.0;
-    memset(page, 65, bytes);
-    if (mode == 0) { other = static_cast<uint8_t *>(malloc(bytes)); if (other) memset(other, 1, bytes); }
-    else if (hipHostMalloc(reinterpret_cast<void **>(&other), bytes, hipHostMallocDefault) != hipSuccess) other = nullptr;
-    if (!other) { free(page); return -1.0; }
-    if (mode != 0) memset(other, 1, bytes);
-    double best = 0.0;
-    {
-        CopyPool pool(threads);
-        for (int rep = 0; rep < 4; ++rep) {
-            struct timespec t0, t1;
-            clock_gettime(CLOCK_MONOTONIC, &t0);
-            if (mode == 2) pool.copy(page, other, bytes); else pool.copy(other, page, bytes);
-            clock_gettime(CLOCK_MONOTONIC, &t1);
-            const double sec = (double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec);
-            if (rep > 0 && (double)bytes / sec / 1e9 > best) best = (double)bytes / sec / 1e9;
-        }
-    }
-    if (mode == 0) free(other); else (void)hipHostFree(other);
-    free(page);
-    return best;
 }
 
 // Diagnostic (bench.py's small_call_latency block): mean ns per call of the HOST path over `iters` calls on the

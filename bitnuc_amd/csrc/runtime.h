@@ -26,7 +26,7 @@ namespace bitnuc_rt {
 constexpr int kSlotBlock0 = 4096;        // error slots of a fresh context (launches between two syncs before the ring grows)
 constexpr int kSlotBlockMax = 1 << 20;   // the largest block the ring grows to (see take_slot)
 constexpr int kCapturedSlots = 1024;     // persistent slots of launches recorded into a hipGraph (a context's lifetime total)
-constexpr size_t kHostChunk = (size_t)128 << 20; // bases per staged chunk on the simple host-pointer path
+constexpr size_t kHostChunk = (size_t)128 << 20; // bases (bytes) per chunk of the host-pointer scratch loop (host_pipe.h scratch_run)
 // Size dispatch of the host-pointer bulk calls: the measured crossover between the library's host SWAR code (one
 // thread, 9-10 Gbases/s) and the GPU path (stage in, launch, stage out, one wait: 33-40 us + PCIe) on the GPU box, tools/host_cutoff.py,
 // profiles/r02_host_cutoff.txt: encode 1 Mi bases (101 vs 104 us), decode 512 Ki bases (62 vs 63 us).
@@ -143,9 +143,7 @@ struct bitnuc_ctx {
     int force_gpu = 0;                     // 1: single-word and below-cutoff calls launch kernels too (GPU parity tests, BITNUC_FORCE_GPU=1)
     size_t host_cutoff = bitnuc_rt::kDefaultHostCutoff; // bulk host-pointer encode / hdist below this many bases run on the host (host_word.h)
     size_t host_cutoff_decode = bitnuc_rt::kDefaultHostCutoffDecode; // ... decode
-    int host_pipeline = 1;                 // large host-pointer encode / decode: pinned buffers + overlapped H2D / kernel / D2H
-    int pipe_impl = 1;                     // host-pointer pipeline: 1 = direct engine (pageable copies from the calling thread + one mover thread: ships -- faster on four of four
-                                           // boxes, profiles/r03_ab_pipe_impl.txt), 0 = staged engine (own pinned buffers + copy threads); BITNUC_PIPE_IMPL=direct|staged (csrc/host_pipe.h)
+    int host_pipeline = 1;                 // large host-pointer bulk calls: overlapped H2D / kernel / D2H (host_pipe.h pipe_run; 0: the scratch loop, scratch_run)
     HostPipe *pipe = nullptr;              // created on the first large host-pointer call (codec.hip)
 };
 

@@ -51,10 +51,7 @@
  *     calls (>= 8 Mi bases) are pipelined in 32 Mi-base chunks: the calling thread copies chunk c from the
  *     caller's memory to the device and launches on it while ONE helper thread of the context copies chunk
  *     c-1's output into the caller's memory (the runtime pins pageable buffers in place: both copies run at
- *     the DMA rate, each blocks only the thread that issued it).  BITNUC_PIPE_IMPL=staged selects the earlier
- *     engine instead (the library's own pinned buffers, filled and emptied by 8 + 4 copy threads, capped by the
- *     CPUs this process may use -- affinity AND cgroup quota; BITNUC_HOST_THREADS / BITNUC_HOST_THREADS_LIGHT
- *     override); bitnuc_host_pipe_info reports the engine and that budget;
+ *     the DMA rate, each blocks only the thread that issued it); bitnuc_host_pipe_info reports the chunk size;
  *     bitnuc_as_2bit_batch, bitnuc_kmer_hdist_scan, bitnuc_encode_fixed and (back-to-back reads) bitnuc_decode_fixed
  *     ride the same engine from 8 MiB of input; the other host entry points (and smaller inputs) stage through
  *     device scratch in 128 Mbase chunks;
@@ -386,15 +383,8 @@ int bitnuc_stream_probe_dev(bitnuc_ctx *ctx, int mode, const void *d_src, void *
 /* Mean ns per call of the HOST path (op 0 as_2bit, 1 from_2bit, 2 encode, 3 decode, 4 hdist_scalar) on n bases of the
  * reference's bench input (benches/simd_comparison.rs:4-7), timed inside the library over `iters` calls; < 0 = bad argument. */
 double bitnuc_selftime_small(int op, size_t n, size_t iters);
-/* GB/s of the host-path staging pool's parallel memcpy (tools/host_path.py): mode 0 pageable -> pageable, 1 pageable -> pinned,
- * 2 pinned -> pageable; < 0 on failure. */
-double bitnuc_selftime_host_copy(size_t bytes, int threads, int mode);
-
-/* Configuration of this context's pipelined host-pointer path (creates it if needed): out[0..n) = cores_visible, cores_quota
- * (0 = none), cores_usable, chunk_bases, depth, encode stage-in / hand-back threads, decode stage-in / hand-back threads,
- * heavy_cap (the most threads the heavy side may use here), the GPU's NUMA node (-1 = unknown), the number of that node's CPUs
- * the staged engine's copy workers are bound to (0 = not bound; BITNUC_PIPE_NUMA=0 disables the binding), the engine in use
- * (1 = direct, 0 = staged). */
+/* Configuration of this context's pipelined host-pointer path (creates it if needed): out[0..n) = chunk_bases (bases per
+ * chunk), depth (chunks in flight); 0.0 past them. */
 int bitnuc_host_pipe_info(bitnuc_ctx *ctx, double *out, int n, bitnuc_err *err);
 
 #ifdef __cplusplus

@@ -121,5 +121,4 @@ extern "C" {
     pub fn bitnuc_kmer_hdist_count_packed(ctx: *mut bitnuc_ctx, words: *const u64, n_words: usize, n: usize, k: usize, query: u64, tau: c_uint, count: *mut u64, err: *mut bitnuc_err) -> c_int;
     // diagnostics
     pub fn bitnuc_selftime_small(op: c_int, n: usize, iters: usize) -> f64;
-    pub fn bitnuc_selftime_host_copy(bytes: usize, threads: c_int, mode: c_int) -> f64;
 }

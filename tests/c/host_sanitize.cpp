@@ -2,13 +2,12 @@
 //   * csrc/host_word.h   -- the SWAR single-word / below-cutoff codec (what bitnuc_as_2bit, bitnuc_from_2bit, bitnuc_hdist_scalar
 //                           and small host-pointer bitnuc_encode / bitnuc_decode / bitnuc_hdist run), on exact-size heap buffers
 //                           so that any over-read / over-write is caught, checked against the oracle;
-//   * csrc/host_pool.h   -- the staging pool of the pipelined host-pointer path (mutex + two condition variables, a blocking
-//                           and an asynchronous job form), hammered in the call pattern of encode_pipelined / decode_pipelined:
-//                           sizes around the 1 MiB serial threshold and the 4096-byte slice edges, 1..9 threads;
+//   * csrc/host_pool.h   -- the mover thread of the pipelined host-pointer path (TaskThread: a task queue, a mutex and two
+//                           condition variables), in the call pattern of pipe_run: tickets, early drains, destruction with tasks queued;
 //   * csrc/scan_mfma_host.h -- the query operand tables of the matrix-core scan and count (count_mfma_table, count3_mfma_table),
 //                           built into exact-size heap objects for every k, the threshold edges and random queries.
 // Built twice by tests/test_sanitizers.py: -fsanitize=address,undefined and -fsanitize=thread.  No header needs HIP.
-// The reference's single-thread contract is src/utils/unpacking/avx.rs:37 (its only static); these threads only move bytes.
+// The reference's single-thread contract is src/utils/unpacking/avx.rs:37 (its only static); the mover thread only moves bytes.
 #include "../../bitnuc_amd/csrc/host_pool.h"
 #include "../../bitnuc_amd/csrc/host_word.h"
 #include "../../bitnuc_amd/csrc/scan_mfma_host.h"
@@ -78,54 +77,7 @@ static void host_word_checks() {
     }
 }
 
-// the call pattern of encode_pipelined / decode_pipelined (codec.hip): per chunk a blocking stage-in copy by `pool`, then -- before
-// the chunk's "D2H" may overwrite a pinned output -- a wait for the previous hand-back, then the asynchronous hand-back of an
-// older chunk by `pool_out`, which overlaps the next chunk's stage-in.  Buffers are exact-size heap blocks.
-static void pool_checks(int threads_in, int threads_out) {
-    using bitnuc_host::CopyPool;
-    CopyPool pool(threads_in), pool_out(threads_out + 1);
-    const size_t sizes[] = {0, 1, 4095, 4096, 4097, (1u << 20) - 1, 1u << 20, (1u << 20) + 1, 3 * 4096 * 7 + 5, (5u << 20) + 4097};
-    for (size_t n : sizes) {
-        const int depth = 3, nchunks = 7;
-        uint8_t *src = static_cast<uint8_t *>(malloc(n * nchunks + 1)), *dst = static_cast<uint8_t *>(malloc(n * nchunks + 1));
-        for (size_t i = 0; i < n * nchunks; ++i) src[i] = (uint8_t)(i * 131 + (i >> 9));
-        memset(dst, 0, n * nchunks + 1);
-        uint8_t *stage[3];
-        for (int b = 0; b < depth; ++b) stage[b] = static_cast<uint8_t *>(malloc(n + 1));
-        for (int use_in = 1; use_in <= threads_in; use_in += (threads_in > 4 ? 3 : 1))
-            for (int ci = 0; ci < nchunks + depth - 1; ++ci) {
-                const int b = ci % depth;
-                if (ci < nchunks) {
-                    pool_out.wait(); // the staging buffer b may still be read by the hand-back of chunk ci - depth
-                    pool.copy(stage[b], src + (size_t)ci * n, n, use_in);
-                }
-                if (ci >= depth - 1) {
-                    const int j = ci - (depth - 1);
-                    pool_out.start(dst + (size_t)j * n, stage[j % depth], n, 1 + (ci % threads_out));
-                }
-            }
-        pool_out.wait();
-        CHECK(memcmp(src, dst, n * nchunks) == 0);
-        for (int b = 0; b < depth; ++b) free(stage[b]);
-        free(src); free(dst);
-    }
-    // back-to-back jobs of both forms on one pool, and destruction with an asynchronous job outstanding
-    uint8_t *a = static_cast<uint8_t *>(malloc(3u << 20)), *b2 = static_cast<uint8_t *>(malloc(3u << 20));
-    memset(a, 7, 3u << 20);
-    for (int rep = 0; rep < 20; ++rep) {
-        pool_out.start(b2, a, (3u << 20) - rep * 4099, 1 + rep % (threads_out));
-        if (rep & 1) pool_out.copy(b2, a, 2u << 20, 2 + rep % 3); // copy() waits for the outstanding job first
-    }
-    pool_out.wait();
-    CHECK(b2[12345] == 7);
-    {
-        CopyPool tmp(4);
-        tmp.start(b2, a, 3u << 20, 3);
-    } // ~CopyPool waits for the job before joining
-    free(a); free(b2);
-}
-
-// the call pattern of pipe_run_direct (csrc/host_pipe.h): the poster fills device-buffer stand-in b = ci % depth itself ("H2D"), posts the
+// the call pattern of pipe_run (csrc/host_pipe.h): the poster fills device-buffer stand-in b = ci % depth itself ("H2D"), posts the
 // chunk's hand-back to the mover, and before it refills b waits for the ticket of the chunk that used b; an error code travels
 // back through an atomic the tasks write; leaving early drains; destruction runs what is still queued.
 static void task_thread_checks() {
@@ -204,10 +156,6 @@ int main() {
     host_word_checks();
     table_checks();
     task_thread_checks();
-    for (int t = 1; t <= 9; t += 2) pool_checks(t, t);
-    pool_checks(8, 3);
-    pool_checks(2, 9);
-    CHECK(bitnuc_host::cores_visible() >= 1 && bitnuc_host::cores_usable() >= 1 && bitnuc_host::cores_usable() <= bitnuc_host::cores_visible());
     printf("host sanitizer harness ok\n");
     return 0;
 }

@@ -695,22 +695,20 @@ sys.exit(1 if fails else 0)
 """
 
 
-@pytest.mark.parametrize("engine", ["staged", "direct"])
-def test_fuzz_host_pointer_calls(engine):
+def test_fuzz_host_pointer_calls():
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, BITNUC_PIPE_CHUNK_MB="1", BITNUC_PIPE_IMPL=engine)  # both engines of csrc/host_pipe.h
+    env = dict(os.environ, BITNUC_PIPE_CHUNK_MB="1")  # 1 Mi-base chunks: the pipelined driver of csrc/host_pipe.h runs many per call
     env.pop("BITNUC_FORCE_GPU", None)
     env.pop("BITNUC_HOST_CUTOFF", None)
     r = subprocess.run([sys.executable, "-c", _HOST_FUZZ_CHILD, root], capture_output=True, text=True, timeout=1200, env=env)
     assert r.returncode == 0 and "host fuzz: 0 failing cases" in r.stdout, (r.stdout[-6000:], r.stderr[-3000:])
 
 
-def test_plan_accessors_and_host_copy_diagnostic(ctx, oracle):
-    """The small entry points nothing else calls: a plan's count / total words / device word-offset table, and the staged engine's
-    copy-rate diagnostic (argument rule + a positive rate for each of its three modes)."""
+def test_plan_accessors(ctx, oracle):
+    """The small entry points nothing else calls: a plan's count / total words / device word-offset table."""
     torch = _torch()
     lens = np.array([0, 1, 31, 32, 33, 150, 0, 64, 1000], dtype=np.uint64)
     off = np.zeros(lens.size + 1, dtype=np.uint64)
@@ -735,16 +733,13 @@ def test_plan_accessors_and_host_copy_diagnostic(ctx, oracle):
     got = out.cpu().numpy()
     assert np.array_equal(got[:-1].view(np.uint64), want) and got[-1] == -1
     plan.close()
-    assert lib.bitnuc_selftime_host_copy(100, 2, 0) < 0 and lib.bitnuc_selftime_host_copy(1 << 22, 0, 0) < 0 and lib.bitnuc_selftime_host_copy(1 << 22, 2, 3) < 0
-    for mode in (0, 1, 2):
-        assert lib.bitnuc_selftime_host_copy(8 << 20, 3, mode) > 0.1
 
 
 def test_host_pipeline_with_pinned_caller_memory(oracle):
     """A caller that hands PINNED buffers to the host-pointer calls gets truly asynchronous copies from the runtime (a pageable copy
-    blocks its issuer, a pinned one does not): the direct engine's ordering must then rest on its events and tickets alone.
-    150 M bases = 5 chunks of 32 Mi (every device buffer reused), encode and decode, both engines, checked against the oracle on
-    slices and as a round trip."""
+    blocks its issuer, a pinned one does not): the pipeline's ordering must then rest on its events and tickets alone.
+    150 M bases = 5 chunks of 32 Mi (every device buffer reused), encode and decode, checked against the oracle on slices and as a
+    round trip."""
     import torch
     import bitnuc_amd
     n = 150_000_001
@@ -756,22 +751,18 @@ def test_host_pipeline_with_pinned_caller_memory(oracle):
     rng = _rng(77)
     seq[:] = np.frombuffer(b"ACGTacgt", dtype=np.uint8)[rng.integers(0, 8, n)]
     c = bitnuc_amd.Context(0)
-    for engine in (1, 0):
-        c.set_variant("pipe_impl", engine)
-        words[:] = 0
-        back[:] = 0
-        assert c.encode_into(seq, words) == nw
-        for lo in (0, 32 * 1_048_576 - 64, 32 * 3_000_000, n - 1000 - (n - 1000) % 32):
-            assert np.array_equal(words[lo // 32:(lo + 992) // 32], oracle.encode(seq[lo:lo + 992])), (engine, lo)
-        assert np.array_equal(words[-1:], oracle.encode(seq[32 * (nw - 1):]))
-        c.decode_into(words, n, back)
-        assert np.array_equal(back, seq & 0xDF), engine
-        # an invalid byte in the fourth chunk, a later one that must not win
-        seq[3 * 33_554_432 + 17] = ord("N")
-        seq[4 * 33_554_432 + 5] = ord("X")
-        with pytest.raises(bitnuc_amd.NucleotideError) as ei:
-            c.encode_into(seq, words)
-        assert (ei.value.kind, ei.value.byte, ei.value.index) == ("InvalidBase", ord("N"), 3 * 33_554_432 + 17)
-        seq[3 * 33_554_432 + 17] = ord("A")
-        seq[4 * 33_554_432 + 5] = ord("C")
+    words[:] = 0
+    back[:] = 0
+    assert c.encode_into(seq, words) == nw
+    for lo in (0, 32 * 1_048_576 - 64, 32 * 3_000_000, n - 1000 - (n - 1000) % 32):
+        assert np.array_equal(words[lo // 32:(lo + 992) // 32], oracle.encode(seq[lo:lo + 992])), lo
+    assert np.array_equal(words[-1:], oracle.encode(seq[32 * (nw - 1):]))
+    c.decode_into(words, n, back)
+    assert np.array_equal(back, seq & 0xDF)
+    # an invalid byte in the fourth chunk, a later one that must not win
+    seq[3 * 33_554_432 + 17] = ord("N")
+    seq[4 * 33_554_432 + 5] = ord("X")
+    with pytest.raises(bitnuc_amd.NucleotideError) as ei:
+        c.encode_into(seq, words)
+    assert (ei.value.kind, ei.value.byte, ei.value.index) == ("InvalidBase", ord("N"), 3 * 33_554_432 + 17)
     c.close()

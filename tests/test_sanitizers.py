@@ -44,16 +44,16 @@ def _build_and_run_host_harness(tmp_path, tag, san_flags, env_extra, no_aslr=Fal
 
 
 def test_product_host_code_under_asan_ubsan(tmp_path):
-    """The product's own CPU code -- csrc/host_word.h (single words, below-cutoff bulk calls) and csrc/host_pool.h (the staging
-    pool of the pipelined host-pointer path) -- under AddressSanitizer + UBSan: exact-size heap buffers, every length, the
-    pool in encode_pipelined's call pattern.  Both headers compile without HIP."""
+    """The product's own CPU code -- csrc/host_word.h (single words, below-cutoff bulk calls) and csrc/host_pool.h (the mover
+    thread of the pipelined host-pointer path) -- under AddressSanitizer + UBSan: exact-size heap buffers, every length, the
+    mover in pipe_run's call pattern.  Both headers compile without HIP."""
     _build_and_run_host_harness(tmp_path, "asan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"],
                                 {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0"})
 
 
 def test_product_host_pool_under_tsan(tmp_path):
-    """The same harness under ThreadSanitizer: the pool's mutex / condition-variable protocol (blocking and asynchronous jobs,
-    1..9 threads, destruction with a job outstanding) has no data race.  The harness runs with address randomisation off: this
+    """The same harness under ThreadSanitizer: the mover thread's mutex / condition-variable protocol (tickets, waits for a
+    ticket, drains, destruction with tasks queued) has no data race.  The harness runs with address randomisation off: this
     compiler's TSan runtime knows a fixed memory layout, and on kernels with 32 bits of mmap randomisation the executable can
     land outside it ("FATAL: ThreadSanitizer: unexpected memory mapping") before a line of the harness runs."""
     _build_and_run_host_harness(tmp_path, "tsan", ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=1:second_deadlock_stack=1"}, no_aslr=True)

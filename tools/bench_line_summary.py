@@ -13,5 +13,5 @@ for path in sys.argv[1:]:
           f"counts {d['base_counts']['roofline']['frac']:.3f} query {d['hdist_query']['roofline']['frac']:.3f} split {d['split_packed']['roofline']['frac']:.3f} | "
           f"plan {d['reads_batch']['encode_frac']:.3f}/{d['reads_batch']['decode_frac']:.3f} tables {d['reads_batch_tables']['encode_frac']:.3f}/{d['reads_batch_tables']['decode_frac']:.3f} "
           f"fixed {d['reads_fixed']['encode_frac']:.3f}/{d['reads_fixed']['decode_frac']:.3f} | host enc {hp.get('encode_frac_of_pinned_h2d')} dec {hp.get('decode_frac_of_pinned_d2h')} "
-          f"kmer {hp.get('kmer_batch_host', {}).get('frac_of_pinned_h2d')} scan {hp.get('kmer_scan_host', {}).get('gwindows_s')} Gw/s numa {hp.get('pipe', {}).get('gpu_numa_node')} | "
+          f"kmer {hp.get('kmer_batch_host', {}).get('frac_of_pinned_h2d')} scan {hp.get('kmer_scan_host', {}).get('gwindows_s')} Gw/s | "
           f"sustained read {sp.get('read')} fill {sp.get('fill_nt')} copy {sp.get('copy')} | cpu {d.get('cpu_baseline', {}).get('value')}")
