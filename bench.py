@@ -16,7 +16,11 @@ value = bases pushed through the codec per second, whole job:
 The two kernels of a step are timed live by HIP events on the launch stream, on every 10th timed step (--event-every; on every step
 the three markers cost 2.5 % of the step itself, profiles/r03_ab_event_every.txt); `config.hip_events` in the line says what was done.
 
-What the line carries beside the contract's keys: `roofline` (the step's dominant kernel; `traffic` = HBM bytes per launch from live
+A plain run does only what the headline needs: it sets up, warms up, times the steps, checks that the last step's round trip is the
+identity, writes --dump-outputs if given and prints the line (`config.full`: false).  Everything else below runs with --full only (the
+--no-* options leave parts of it out); without it `roofline.traffic` is null and so is every `configs` entry but config 2's.
+
+What a --full line carries beside the contract's keys: `roofline` (the step's dominant kernel; `traffic` = HBM bytes per launch from live
 rocprofv3 PMC passes), `cpu_baseline` (oracle/bitnuc_avx2.c on one core: `value` from the tracked portable build, `native_value` from a
 -march=native build made on this host), `parity_vs_oracle` (EVERY word and base the timed step left on rank 0's GPU against the
 oracle's output for the same seeded stream; a mismatch makes the run exit 3), `config.library_csrc_sha16` (the hash the timed
@@ -70,18 +74,20 @@ def parse_args(argv=None):
     ap.add_argument("--enc-variant", type=int, default=-1)
     ap.add_argument("--dec-variant", type=int, default=-1)
     ap.add_argument("--grid-mult", type=int, default=-1)
-    ap.add_argument("--cpu-sample", type=int, default=10**9, help="bases timed on the CPU (default: the whole configs[1] workload)")
-    ap.add_argument("--cpu-reps", type=int, default=15, help="repetitions of the 10^9-base CPU round trip (median reported): about 12 s of single-core work")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the config-3 (k-mer batch) and config-5 (scan) side measurements")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the live rocprofv3 --pmc pass that measures roofline.traffic (N=1 only)")
+    ap.add_argument("--full", action="store_true", help="also run everything beside the headline: the live rocprofv3 --pmc pass (N=1), the CPU baseline with "
+                    "parity_vs_oracle, the side measurements and probes (N=1) and config 4's gathers (N>1); the --no-* options below leave parts of it out")
+    ap.add_argument("--cpu-sample", type=int, default=10**9, help="--full: bases timed on the CPU (default: the whole configs[1] workload)")
+    ap.add_argument("--cpu-reps", type=int, default=15, help="--full: repetitions of the 10^9-base CPU round trip (median reported): about 12 s of single-core work")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and parity_vs_oracle")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the side measurements and probes (configs 3 and 5, analysis kernels, read batches, host path)")
+    ap.add_argument("--no-traffic", action="store_true", help="--full: skip the live rocprofv3 --pmc pass that measures roofline.traffic (N=1 only)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL); gloo only to rehearse the N>1 control flow")
     ap.add_argument("--force-dist", action="store_true", help="rehearsal only: initialise torch.distributed and run the collectives even at world size 1")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal only: every rank uses cuda:0 (1-GPU box)")
     ap.add_argument("--rehearse-cpu", action="store_true", help="rehearsal only (CPU, no GPU touched): exercise launcher, process groups, watchdog and the JSON relay; value is null")
     ap.add_argument("--dist-timeout", type=float, default=600.0, help="seconds a rank may spend in process-group setup / a collective before it reports a stall")
     ap.add_argument("--warm-decode", action="store_true", help="decode the words the same step just encoded (a literal round trip: 20 %% of decode's input then comes from the Infinity Cache)")
-    ap.add_argument("--probe", action="store_true", help="also time pure streaming kernels (the box's own HBM rates) when --no-extras is given")
+    ap.add_argument("--probe", action="store_true", help="also time pure streaming kernels (the box's own HBM rates) when the side measurements are not run")
     ap.add_argument("--traffic-child", choices=["codec"], default=None, help=argparse.SUPPRESS)  # the workload run under rocprofv3 --pmc
     ap.add_argument("--inject-stall", type=int, default=-1, help=argparse.SUPPRESS)  # test hook: this rank never joins the side collectives
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (the packed words its encode wrote, "
@@ -655,7 +661,7 @@ def run_rank(args, real_stdout, traffic):
             state["line_extra"]["dump_outputs"] = dump_outputs(torch, args.dump_outputs, words[(args.steps - 1) % R], backs[r_last], n, nw, rank, world)
         # what the timed launches left for buffer set r_last (stream seed SEED + r_last), copied out now -- after the timed region,
         # before the side measurements reuse the buffers -- for the word-for-word comparison with the CPU oracle (cpu_baseline)
-        if rank == 0 and not args.no_cpu_baseline and args.steps + args.warmup >= R:
+        if rank == 0 and args.full and not args.no_cpu_baseline and args.steps + args.warmup >= R:
             state["gpu_result"] = {"words": words[r_last].cpu().numpy().view("uint64"), "back": backs[r_last].cpu().numpy(), "seed": SEED + r_last}
 
     elapsed = torch.tensor([t1 - t0], dtype=torch.float64, device=dev if on_gpu_collectives else "cpu")
@@ -700,6 +706,7 @@ def run_rank(args, real_stdout, traffic):
                                       "inserts three markers per step and costs 2.5 % of it") if ev_every > 1 else "per-kernel HIP events recorded on every timed step",
                        "decode_input": "words encoded in the same step (Infinity-Cache warm)" if args.warm_decode else f"words encoded {R - 1} steps earlier (HBM resident, cache cold)",
                        "parallelism": f"shard{world}" if world > 1 else "single",
+                       "full": args.full,  # False: the step alone (no PMC pass, CPU baseline, oracle parity or side blocks)
                        "control_backend": control_backend, "devices": identities,
                        "commit": git_head(), "csrc_sha16": csrc_sha16()},
         }
@@ -730,7 +737,7 @@ def run_rank(args, real_stdout, traffic):
                                 traffic_source=tr.get("source") or tr.get("error"))
         line["roofline_encode"], line["roofline_decode"], line["roofline_step"] = r_enc, r_dec, r_step
         line.update(extra)
-        if with_cpu and rank == 0 and not args.no_cpu_baseline:
+        if with_cpu and rank == 0 and args.full and not args.no_cpu_baseline:
             try:  # north_star: the CPU SIMD path "in the same run" at every GPU count (N > 1: 3 repetitions on rank 0's host cores, the other ranks idle)
                 g = state.get("gpu_result")
                 cb = cpu_baseline(args.cpu_sample, args.cpu_reps if world == 1 else min(args.cpu_reps, 3), all_cores=True,
@@ -767,7 +774,7 @@ def run_rank(args, real_stdout, traffic):
     state["headline"] = make_line
     extra = state["line_extra"]
 
-    if use_dist and (on_gpu_collectives or rehearse or args.backend == "gloo"):
+    if use_dist and args.full and (on_gpu_collectives or rehearse or args.backend == "gloo"):
         # config 4's concatenation, reported beside the step, never inside it.  These are collectives: a rank that
         # fails alone leaves the others waiting, and the watchdog then prints the headline with "stalled": true and
         # exits non-zero.
@@ -861,7 +868,7 @@ def run_rank(args, real_stdout, traffic):
             state["rc"] = 4
         wd.disarm()
 
-    if use_dist and not rehearse:
+    if use_dist and args.full and not rehearse:
         # The same concatenation through the C ABI (what a C / Rust host calls): one-shot ncclAllGather and the chunked,
         # in-place overlap (bitnuc_encode_sharded_allgather_overlapped_dev).  It is an EXTRA block with its own RCCL
         # communicator: it runs in a thread with a bounded wait so that it can never cost the headline line.
@@ -870,19 +877,20 @@ def run_rank(args, real_stdout, traffic):
         else:
             extra["c_abi_allgather"] = {"skipped": "needs RCCL and one GPU per rank"}
 
-    if not rehearse and (args.probe or (world == 1 and not args.no_extras)):
+    extras = args.full and not args.no_extras
+    if not rehearse and (args.probe or (world == 1 and extras)):
         # the step's two access shapes WITHOUT arithmetic, in the same sustained rotation as the timed loop: the
         # box's rate for exactly this traffic pattern (run before the side measurements free the rotating sets)
         try:
             extra["shape_probe_pair"] = sustained_shape_probes(args, ctx, torch, stream, seqs, words, backs, n, R)
         except Exception as e:  # noqa: BLE001
             extra["shape_probe_pair"] = {"error": repr(e)[:300]}
-    if not rehearse and world == 1 and not args.no_extras:
+    if not rehearse and world == 1 and extras:
         try:
             side_measurements(args, ctx, torch, dev, stream, seqs, words, backs, n, nw, extra)
         except Exception as e:  # noqa: BLE001 -- side measurements must never cost the headline line
             extra["extras_error"] = repr(e)[:300]
-    if not rehearse and (args.probe or (world == 1 and not args.no_extras)):
+    if not rehearse and (args.probe or (world == 1 and extras)):
         try:
             extra["stream_probe_gb_s"] = stream_probes(ctx, torch, stream, seqs, backs, n)
         except Exception as e:  # noqa: BLE001
@@ -1538,7 +1546,9 @@ def main():
     real_stdout = os.dup(1)
     os.dup2(2, 1)
     traffic = None
-    if not args.rehearse_cpu:
+    if not args.full:
+        traffic = {"error": "not measured in this run (bench.py --full measures it)"}
+    elif not args.rehearse_cpu:
         if args.gpus == 1 and not in_rank and not args.no_traffic:
             from bitnuc_amd import build as bn_build
             bn_build.ensure_built()  # before any child runs under rocprofv3: a profiled process must not start the compiler

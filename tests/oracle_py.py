@@ -32,9 +32,18 @@ _lib = None
 
 
 def build():
+    """Compile the oracle when it is missing or older than its sources.  Processes that start together (spawned ranks) decide and build
+    under one lock on the oracle directory: the linker rewrites the library in place, so a process that found it fresh while another was
+    still writing it would load a truncated file."""
+    import fcntl
     srcs = [os.path.join(ORACLE_DIR, f) for f in ("bitnuc_oracle.c", "bitnuc_avx2.c", "bitnuc_oracle.h", "Makefile")]
-    if not os.path.exists(LIB_PATH) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs):
-        subprocess.run(["make", "-C", ORACLE_DIR, "libbitnuc_oracle.so"], check=True, capture_output=True)
+    fd = os.open(ORACLE_DIR, os.O_RDONLY)
+    try:
+        fcntl.flock(fd, fcntl.LOCK_EX)
+        if not os.path.exists(LIB_PATH) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs):
+            subprocess.run(["make", "-C", ORACLE_DIR, "libbitnuc_oracle.so"], check=True, capture_output=True)
+    finally:
+        os.close(fd)  # releases the lock
     return LIB_PATH
 
 

@@ -25,7 +25,7 @@ def run(*flags, timeout=240, **env_extra):
 
 
 def test_self_launch_two_ranks_prints_one_line():
-    rc, lines, err = run("--gpus", "2", "--rehearse-cpu", "--backend", "gloo", "--steps", "5", "--warmup", "1")
+    rc, lines, err = run("--gpus", "2", "--rehearse-cpu", "--backend", "gloo", "--steps", "5", "--warmup", "1", "--full")
     assert rc == 0, err[-2000:]
     assert len(lines) == 1, lines
     line = json.loads(lines[0])
@@ -45,7 +45,7 @@ def test_self_launch_two_ranks_prints_one_line():
 def test_a_wrong_word_in_a_peer_slot_fails_the_run():
     """Config 4's check is literal: the gathered buffer is compared slot by slot with what every rank's shard must pack to (here, without a
     GPU, arange + rank), so a gather that delivered garbage into a PEER's slot is caught -- the line says so and the run exits 3."""
-    rc, lines, err = run("--gpus", "2", "--rehearse-cpu", "--backend", "gloo", "--steps", "3", "--warmup", "1", BITNUC_BENCH_PLANT_BAD_SLOT="1")
+    rc, lines, err = run("--gpus", "2", "--rehearse-cpu", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--full", BITNUC_BENCH_PLANT_BAD_SLOT="1")
     # the rank exits 3 (as for parity_vs_oracle); the launcher folds a failed rank into its own non-zero code and names the FIRST failure it saw as the root
     # cause -- usually rank 0's "exitcode: 3", now and then its peer's, torn down while rank 0 was exiting (seen once in round 5): the line below is the evidence
     assert rc != 0, (rc, err[-2000:])
@@ -56,11 +56,21 @@ def test_a_wrong_word_in_a_peer_slot_fails_the_run():
 
 def test_stalled_collective_is_reported_and_fails():
     rc, lines, err = run("--gpus", "2", "--rehearse-cpu", "--backend", "gloo", "--steps", "3", "--warmup", "1",
-                         "--inject-stall", "1", "--dist-timeout", "30")
+                         "--inject-stall", "1", "--dist-timeout", "30", "--full")
     assert rc != 0, "a stalled collective must not exit 0"
     assert len(lines) == 1, lines
     line = json.loads(lines[0])
     assert line["stalled"] is True and "allgather" in line["stalled_stage"]
+
+
+def test_plain_run_leaves_the_side_blocks_to_full():
+    """Without --full a run times the step alone: no config-4 gathers (nor a stall in them), no CPU baseline; the line says so."""
+    rc, lines, err = run("--gpus", "2", "--rehearse-cpu", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--inject-stall", "1", "--dist-timeout", "30")
+    assert rc == 0, err[-2000:]
+    assert len(lines) == 1, lines
+    line = json.loads(lines[0])
+    assert line["config"]["full"] is False and line["steps"] == 3
+    assert not {"allgather_packed", "encode_allgather_end_to_end", "ragged_batch_sharded", "c_abi_allgather", "cpu_baseline", "stalled"} & line.keys()
 
 
 def test_world_size_mismatch_is_refused():
@@ -103,3 +113,17 @@ def test_dump_outputs_are_the_last_steps_results(tmp_path, oracle):
     bi = a["decode_bases_index"].astype(np.int64)
     assert bi.size == 1 << 21 and bi[0] == 0 and bi[-1] == n - 1 and bool((np.diff(bi) > 0).all())
     assert np.array_equal(a["decode_bases"], oracle.nucgen(n, seed)[bi].astype(np.float32))
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_step_alone():
+    """A plain one-GPU run carries the headline and the step's own per-kernel figures, and nothing that takes a run of its own: no live PMC
+    pass, CPU baseline, oracle parity or side measurement; --full runs them (tests/test_gpu_comm.py)."""
+    rc, lines, err = run("--gpus", "1", "--steps", "4", "--warmup", "1", "--bases", str(10**8), timeout=600)
+    assert rc == 0, err[-3000:]
+    assert len(lines) == 1, lines
+    line = json.loads(lines[0])
+    assert line["config"]["full"] is False and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["roofline"]["traffic"] is None and "--full" in line["roofline"]["traffic_source"]
+    assert line["configs"]["cfg2_encode"] > 0 and line["configs"]["cfg2_decode"] > 0 and line["configs"]["cfg3_kmer_batch"] is None
+    assert not {"cpu_baseline", "parity_vs_oracle", "shape_probe_pair", "kmer_batch", "kmer_hdist_scan", "host_path", "stream_probe_gb_s"} & line.keys()

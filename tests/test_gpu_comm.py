@@ -74,7 +74,7 @@ def test_bench_self_launch_two_ranks_on_one_gpu():
     config 4's side measurements (here over gloo, both ranks sharing the one GPU: a rehearsal of the control flow)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--backend", "gloo",
-                        "--steps", "5", "--warmup", "2", "--bases", str(10**8)], capture_output=True, text=True, timeout=900, env=env)
+                        "--steps", "5", "--warmup", "2", "--bases", str(10**8), "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
@@ -88,7 +88,7 @@ def test_bench_self_launch_two_ranks_on_one_gpu():
     # ... and every slot of the gathered buffer against the closed form of the seeded stream (2^20 words of each rank's shard here)
     assert line["allgather_packed"]["all_slots_ok"] is True and line["allgather_packed"]["first_bad_slot"] is None
     bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--backend", "gloo", "--steps", "2", "--warmup", "1",
-                          "--bases", str(10**7), "--no-extras", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=dict(env, BITNUC_BENCH_PLANT_BAD_SLOT="1"))
+                          "--bases", str(10**7), "--full", "--no-extras", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=dict(env, BITNUC_BENCH_PLANT_BAD_SLOT="1"))
     assert bad.returncode != 0, (bad.returncode, bad.stderr[-2000:])  # (which rank the launcher names as the root cause depends on who is torn down first: the line is the evidence)
     bl = json.loads([l for l in bad.stdout.splitlines() if l.strip()][0])
     assert bl["allgather_packed"]["all_slots_ok"] is False and bl["allgather_packed"]["first_bad_slot"] == 1  # a wrong word in the PEER's slot is caught
@@ -298,7 +298,7 @@ def test_bench_force_dist_prints_the_multi_gpu_blocks():
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--steps", "5", "--warmup", "2", "--bases", str(10**8),
-                        "--no-extras", "--no-traffic", "--cpu-sample", str(10**7), "--cpu-reps", "3"], capture_output=True, text=True, timeout=900, env=env)
+                        "--full", "--no-extras", "--no-traffic", "--cpu-sample", str(10**7), "--cpu-reps", "3"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1

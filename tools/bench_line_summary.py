@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""One compact row per bench.py JSON line (for box-to-box tables in profiles/)."""
+"""One compact row per `bench.py --full` JSON line (for box-to-box tables in profiles/)."""
 import json
 import sys
 

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Vector-ALU utilisation of every kernel of the default bench run (one --pmc pass, counters only).
+# Vector-ALU utilisation of every kernel of a `bench.py --full` run (one --pmc pass, counters only).
 # usage on the GPU box: bash tools/pmc_valu_all.sh OUTDIR
 set -u
 # both libraries are built BEFORE the first rocprofv3 line: a profiled process has the GPU initialised by the profiler's preload
@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 ROOT=$PWD
 cd /tmp
-rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS GRBM_GUI_ACTIVE --output-format csv -d "$OUT/pmc" -o pmc -- python3 "$ROOT/bench.py" --no-traffic --no-cpu-baseline --steps 20 > "$OUT/run.log" 2>&1
+rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS GRBM_GUI_ACTIVE --output-format csv -d "$OUT/pmc" -o pmc -- python3 "$ROOT/bench.py" --full --no-traffic --no-cpu-baseline --steps 20 > "$OUT/run.log" 2>&1
 echo "rc=$?"
 cd "$ROOT"
 python3 - "$OUT" <<'PY'

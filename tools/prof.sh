@@ -1,6 +1,6 @@
 #!/bin/bash
 # rocprofv3 recipe for one round: kernel-trace stats of the timed step, HBM counters in separate --pmc passes (counters only,
-# never combined with a trace domain), then kernel-trace stats of the full default run (side measurements included).
+# never combined with a trace domain), then kernel-trace stats of a `bench.py --full` run (side measurements included).
 # usage (on the GPU box, from the repo root): bash tools/prof.sh r02
 set -u
 # both libraries are built BEFORE the first rocprofv3 line: a profiled process has the GPU initialised by the profiler's preload
@@ -13,7 +13,7 @@ export TMPDIR=/tmp
 # --no-traffic: bench.py would otherwise start its own rocprofv3 children; --no-extras: only the step's two kernels run at full
 # size, so the per-kernel averages of --stats are the step's (the side measurements launch the same kernels on small chunks)
 STEP="python3 $PWD/bench.py --no-cpu-baseline --no-traffic --no-extras"
-FULL="python3 $PWD/bench.py --no-cpu-baseline --no-traffic"
+FULL="python3 $PWD/bench.py --full --no-cpu-baseline --no-traffic"
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o trace -- $STEP > "$OUT/trace.log" 2>&1
 echo "trace rc=$?"
