@@ -55,6 +55,10 @@ SIGNATURES = {
     "bitnuc_kmer_hdist_count_packed_dev": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _U64, C.c_uint, _P, _ERR]),
     "bitnuc_kmer_hdist_scan_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _U64, _P, _ERR]),
     "bitnuc_kmer_hdist_count_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _U64, C.c_uint, C.POINTER(_U64), _ERR]),
+    "bitnuc_kmer_hdist_hits_dev": (C.c_int, [_P, _P, _SZ, _SZ, _U64, C.c_uint, _P, _P, _SZ, _P, _ERR]),
+    "bitnuc_kmer_hdist_hits_packed_dev": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _U64, C.c_uint, _P, _P, _SZ, _P, _ERR]),
+    "bitnuc_kmer_hdist_hits": (C.c_int, [_P, _P, _SZ, _SZ, _U64, C.c_uint, _P, _P, _SZ, C.POINTER(_U64), _ERR]),
+    "bitnuc_kmer_hdist_hits_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _U64, C.c_uint, _P, _P, _SZ, C.POINTER(_U64), _ERR]),
     "bitnuc_hdist_dev": (C.c_int, [_P, _P, _SZ, _P, _SZ, _SZ, _P, _ERR]),
     "bitnuc_batch_word_offsets_dev": (C.c_int, [_P, _P, _SZ, _P, C.POINTER(_SZ), _ERR]),
     "bitnuc_encode_batch_dev": (C.c_int, [_P, _P, _P, _P, _SZ, _SZ, _P, _ERR]),

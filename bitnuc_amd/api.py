@@ -306,6 +306,28 @@ class Context:
             _raise(err)
         return out.value
 
+    def _hits(self, fn, args, with_dist):
+        """A hit-list call sized by a first call with cap 0 (its *n_hits), then filled."""
+        err = L.BitnucErr()
+        total = C.c_uint64(0)
+        if fn(self._h, *args, None, None, 0, C.byref(total), C.byref(err)) != L.OK:
+            _raise(err)
+        pos = np.empty(total.value, dtype=np.uint64)
+        dist = np.empty(total.value if with_dist else 0, dtype=np.uint8)
+        if total.value and fn(self._h, *args, _ptr(pos), _ptr(dist) if with_dist else None, pos.size, C.byref(total), C.byref(err)) != L.OK:
+            _raise(err)
+        return (pos, dist) if with_dist else pos
+
+    def kmer_hdist_hits(self, ref, k, query, tau, with_dist=False):
+        """Positions (np.uint64, ascending) of the windows of `ref` with Hamming distance <= tau to the query; with_dist: (positions, np.uint8 distances)."""
+        s = _as_u8(ref)
+        return self._hits(self._lib.bitnuc_kmer_hdist_hits, (_ptr(s), s.size, int(k), C.c_uint64(query), int(tau)), with_dist)
+
+    def kmer_hdist_hits_packed(self, words, n_bases, k, query, tau, with_dist=False):
+        """kmer_hdist_hits of the packed sequence `words` holding `n_bases` bases, without decoding it."""
+        w = _as_u64(words)
+        return self._hits(self._lib.bitnuc_kmer_hdist_hits_packed, (_ptr(w), w.size, int(n_bases), int(k), C.c_uint64(query), int(tau)), with_dist)
+
     # -- analysis on packed words (src/utils/analysis.rs, hamming/scalar.rs) ------------------
     def base_counts(self, words, n_bases):
         """[A, C, G, T] counts of a packed sequence (BaseCount::base_counts, analysis.rs:23-39)."""
@@ -514,6 +536,17 @@ class Context:
     def kmer_hdist_count_packed_dev(self, d_words, n_words, n, k, query, tau, d_count):
         """The fused count on packed words in device memory -> *d_count (u64)."""
         self._call_dev(self._lib.bitnuc_kmer_hdist_count_packed_dev, _dev_ptr(d_words), int(n_words), int(n), int(k), C.c_uint64(query), int(tau), _dev_ptr(d_count))
+
+    def kmer_hdist_hits_dev(self, d_ref, n, k, query, tau, d_pos, d_hit_dist, cap, d_n_hits):
+        """The positions of the windows with distance <= tau -> d_pos[0 .. min(cap, total)) (u64, ascending), their distances at d_hit_dist (None: not
+        written), total -> *d_n_hits (u64)."""
+        self._call_dev(self._lib.bitnuc_kmer_hdist_hits_dev, _dev_ptr(d_ref), int(n), int(k), C.c_uint64(query), int(tau), _dev_ptr(d_pos),
+                       _dev_ptr(d_hit_dist), int(cap), _dev_ptr(d_n_hits))
+
+    def kmer_hdist_hits_packed_dev(self, d_words, n_words, n, k, query, tau, d_pos, d_hit_dist, cap, d_n_hits):
+        """The hit list on packed words in device memory (8-byte aligned)."""
+        self._call_dev(self._lib.bitnuc_kmer_hdist_hits_packed_dev, _dev_ptr(d_words), int(n_words), int(n), int(k), C.c_uint64(query), int(tau),
+                       _dev_ptr(d_pos), _dev_ptr(d_hit_dist), int(cap), _dev_ptr(d_n_hits))
 
     def hdist_dev(self, d_a, na, d_b, nb, n_bases, d_result):
         self._call_dev(self._lib.bitnuc_hdist_dev, _dev_ptr(d_a), int(na), _dev_ptr(d_b), int(nb), int(n_bases), _dev_ptr(d_result))

@@ -1,12 +1,15 @@
 // kmer.hip -- k-mer compositions of the hot path behind the C ABI (include/bitnuc_hip.h): batched as_2bit over many
 // <= 32-mers (BASELINE config 3, README.md:52-56), every window of a sequence (src/lib.rs:170-173), the sliding pack +
 // Hamming scan (config 5: packing/mod.rs:80-110 o hamming/scalar.rs:11-48) and bulk hdist (hamming/multi.rs:121-160).
-// Kernels: kmer_device.h; config 5 on the matrix cores: scan_mfma_device.h; the same scan and count on packed words: scan_packed_device.h.
+// Kernels: kmer_device.h; config 5 on the matrix cores: scan_mfma_device.h; the same scan and count on packed words: scan_packed_device.h; the hit
+// lists of both: scan_hits_device.h.
 #include "runtime.h"
 #include "kmer_device.h"
 #include "scan_mfma_device.h"
 #include "scan_packed_device.h"
+#include "scan_hits_device.h"
 #include "scan_mfma_host.h"
+#include "scan_hits_host.h"
 #include "host_word.h"
 #include "host_pipe.h"
 
@@ -222,6 +225,101 @@ int check_packed(const void *words, size_t n_words, size_t n, size_t k, bool *no
     *no_windows = k == 0 || n < k;
     if (*no_windows) return BITNUC_OK;
     if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    return BITNUC_OK;
+}
+
+// ---- the hit lists (scan_hits_device.h): count pass, scan of the per-trip counts, emit pass.  Context scratch 7 holds the counts (one u32 per trip, the
+// head's and the tail's) and the tiles' offsets; a launch recorded into a hipGraph keeps it (ensure_scratch).  cap == 0 skips the emit pass.  pos_base is added to every
+// position (the host forms' chunk offset).
+struct HitsArgs { uint64_t query; unsigned tau; unsigned long long *pos; uint8_t *hd; unsigned long long cap, *n_hits, pos_base; };
+
+int hits_scratch(bitnuc_ctx *c, unsigned long long ntr, unsigned **counts, unsigned long long **tiles, bitnuc_err *err) {
+    const unsigned long long ntiles = (ntr + kHitsTile - 1) / kHitsTile, cbytes = (4 * ntr + 255) & ~255ull;
+    if (int st = ensure_scratch(c, 7, cbytes + 8 * ntiles, err)) return st;
+    *counts = reinterpret_cast<unsigned *>(c->scratch[7]);
+    *tiles = reinterpret_cast<unsigned long long *>(c->scratch[7] + cbytes);
+    return BITNUC_OK;
+}
+
+hipError_t hits_scan(bitnuc_ctx *c, unsigned *counts, unsigned long long ntr, unsigned long long *tiles, unsigned long long *n_hits) {
+    const unsigned long long ntiles = (ntr + kHitsTile - 1) / kHitsTile;
+    hits_scan_tiles_kernel<<<(unsigned)ntiles, kHitsTileBlock, 0, c->stream>>>(counts, ntr, tiles);
+    hits_scan_top_kernel<<<1, kHitsTopBlock, 0, c->stream>>>(tiles, ntiles, n_hits);
+    return hipGetLastError();
+}
+
+// d_ref at any alignment: the rounds start at the first 16-byte aligned base, the windows before it are the tail workgroup's
+int launch_hits(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const HitsArgs &a, unsigned long long *slot, bitnuc_err *err) {
+    const unsigned skip = (unsigned)((16 - (reinterpret_cast<uintptr_t>(ref) & 15)) & 15);
+    const unsigned long long ntr = hits_trips(n, skip) + 2;
+    unsigned *counts;
+    unsigned long long *tiles;
+    if (int st = hits_scratch(c, ntr, &counts, &tiles, err)) return st;
+    CountMfmaTable ct;
+    count_mfma_table(a.query, k, &ct);
+    for (int j = 0; j < 4; ++j) ct.c[j] = kPackBias;
+    kmer_hits_mfma_kernel<false><<<(unsigned)ntr, 64, 0, c->stream>>>(ref, n, skip, (unsigned)k, a.query, a.tau, counts, nullptr, nullptr, nullptr, 0, 0, slot, ct);
+    HIPCHK(hits_scan(c, counts, ntr, tiles, a.n_hits));
+    if (a.cap) kmer_hits_mfma_kernel<true><<<(unsigned)ntr, 64, 0, c->stream>>>(ref, n, skip, (unsigned)k, a.query, a.tau, counts, tiles, a.pos, a.hd, a.cap, a.pos_base, slot, ct);
+    HIPCHK(hipGetLastError());
+    return BITNUC_OK;
+}
+
+// d_words 8-byte aligned (checked by the callers): at 8 mod 16 the rounds start one word later, as the packed scan's
+int launch_hits_packed(bitnuc_ctx *c, const uint64_t *words, size_t n, size_t k, const HitsArgs &a, bitnuc_err *err) {
+    const unsigned skip = aligned16(words) ? 0u : 32u;
+    const unsigned long long ntr = hits_trips(n, skip) + 2;
+    unsigned *counts;
+    unsigned long long *tiles;
+    if (int st = hits_scratch(c, ntr, &counts, &tiles, err)) return st;
+    PackedScanTable t;
+    scan_packed_table(a.query, k, &t);
+    packed_hits_mfma_kernel<false><<<(unsigned)ntr, 64, 0, c->stream>>>(words, n, skip, (unsigned)k, a.query, a.tau, counts, nullptr, nullptr, nullptr, 0, 0, t);
+    HIPCHK(hits_scan(c, counts, ntr, tiles, a.n_hits));
+    if (a.cap) packed_hits_mfma_kernel<true><<<(unsigned)ntr, 64, 0, c->stream>>>(words, n, skip, (unsigned)k, a.query, a.tau, counts, tiles, a.pos, a.hd, a.cap, a.pos_base, t);
+    HIPCHK(hipGetLastError());
+    return BITNUC_OK;
+}
+
+// the hit calls' output checks (after the count's / packed count's checks of k, lengths and words): n_hits and pos 8-byte aligned, pos NULL only for cap 0
+int check_hits_out(const void *pos, size_t cap, const void *n_hits, bitnuc_err *err) {
+    if (!n_hits || (reinterpret_cast<uintptr_t>(n_hits) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    if ((!pos && cap) || (reinterpret_cast<uintptr_t>(pos) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    return BITNUC_OK;
+}
+
+// The host forms' chunk loop: the input chunk in scratch 0, the chunk's positions / distances in scratch 1 / 2 (at most the cap still open), its
+// count in scratch 3.  `launch(i0, m, a)` runs the windows [i0, i0 + m) with a's outputs; positions come back shifted by i0.  Stops at the first
+// failing chunk (drain: its first invalid byte, relative to the whole sequence through the slot's base).
+template <class Launch>
+int hits_host_loop(bitnuc_ctx *c, size_t nwin, size_t per, unsigned tau, uint64_t query, uint64_t *pos, uint8_t *hit_dist, size_t cap, uint64_t *n_hits,
+                   bitnuc_err *err, Launch launch) {
+    const size_t pcap = cap < per ? cap : per;
+    if (pcap) {
+        if (int st = ensure_scratch(c, 1, pcap * 8, err)) return st;
+        if (hit_dist) if (int st = ensure_scratch(c, 2, pcap, err)) return st;
+    }
+    if (int st = ensure_scratch(c, 3, 64, err)) return st;
+    uint64_t total = 0;
+    for (size_t i0 = 0; i0 < nwin; i0 += per) {
+        const size_t m = nwin - i0 < per ? nwin - i0 : per;
+        const size_t open = total < cap ? cap - total : 0, ccap = open < m ? open : m;
+        const HitsArgs a{query, tau, reinterpret_cast<unsigned long long *>(c->scratch[1]), hit_dist ? c->scratch[2] : nullptr, ccap,
+                         reinterpret_cast<unsigned long long *>(c->scratch[3]), i0};
+        if (int st = launch(i0, m, a)) return st;
+        uint64_t part = 0;
+        HIPCHK(hipMemcpyAsync(&part, c->scratch[3], 8, hipMemcpyDeviceToHost, c->stream));
+        bitnuc_err e;
+        if (int st = drain(c, &e)) { if (err) *err = e; return st; }
+        const size_t got = part < ccap ? (size_t)part : ccap;
+        if (got) {
+            HIPCHK(hipMemcpyAsync(pos + total, c->scratch[1], got * 8, hipMemcpyDeviceToHost, c->stream));
+            if (hit_dist) HIPCHK(hipMemcpyAsync(hit_dist + total, c->scratch[2], got, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+        }
+        total += part;
+    }
+    *n_hits = total;
     return BITNUC_OK;
 }
 
@@ -495,6 +593,89 @@ int bitnuc_kmer_hdist_count_packed(bitnuc_ctx *c, const uint64_t *words, size_t 
     }
     *count = total;
     return BITNUC_OK;
+}
+
+// ---- the hit lists -------------------------------------------------------------------------------------------------------
+int bitnuc_kmer_hdist_hits_dev(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *d_pos, uint8_t *d_hit_dist,
+                               size_t cap, uint64_t *d_n_hits, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    if (int st = check_hits_out(d_pos, cap, d_n_hits, err)) return st;
+    DeviceGuard g(c->device);
+    if (k == 0 || n < k) { // no windows
+        HIPCHK(hipMemsetAsync(d_n_hits, 0, sizeof(uint64_t), c->stream));
+        return BITNUC_OK;
+    }
+    if (!d_ref) return fail(err, BITNUC_UNSUPPORTED);
+    unsigned long long *slot;
+    if (int st = take_slot(c, 0, &slot, err)) return st;
+    const HitsArgs a{query, tau, reinterpret_cast<unsigned long long *>(d_pos), d_hit_dist, cap, reinterpret_cast<unsigned long long *>(d_n_hits), 0};
+    return launch_hits(c, d_ref, n, k, a, slot, err);
+}
+
+int bitnuc_kmer_hdist_hits_packed_dev(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *d_pos,
+                                      uint8_t *d_hit_dist, size_t cap, uint64_t *d_n_hits, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    bool none;
+    if (int st = check_packed(d_words, n_words, n, k, &none, err)) return st;
+    if (int st = check_hits_out(d_pos, cap, d_n_hits, err)) return st;
+    DeviceGuard g(c->device);
+    if (none) {
+        HIPCHK(hipMemsetAsync(d_n_hits, 0, sizeof(uint64_t), c->stream));
+        return BITNUC_OK;
+    }
+    const HitsArgs a{query, tau, reinterpret_cast<unsigned long long *>(d_pos), d_hit_dist, cap, reinterpret_cast<unsigned long long *>(d_n_hits), 0};
+    return launch_hits_packed(c, d_words, n, k, a, err);
+}
+
+int bitnuc_kmer_hdist_hits(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *pos, uint8_t *hit_dist, size_t cap,
+                           uint64_t *n_hits, bitnuc_err *err) {
+    clear_err(err);
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    if (!n_hits || (!pos && cap)) return fail(err, BITNUC_UNSUPPORTED);
+    if (k == 0 || n < k) { *n_hits = 0; return BITNUC_OK; }
+    if (!ref) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, n)) {
+        const long long bad = bitnuc_host::kmer_hdist_hits_small(ref, n, k, query, tau, pos, hit_dist, cap, n_hits);
+        if (bad >= 0) {
+            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = ref[bad]; err->index = (uint64_t)bad; }
+            return BITNUC_INVALID_BASE;
+        }
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    // chunks of kHostChunk windows + their k - 1 halo bases
+    if (int st = ensure_scratch(c, 0, kHostChunk + 64, err)) return st;
+    return hits_host_loop(c, n - k + 1, kHostChunk, tau, query, pos, hit_dist, cap, n_hits, err, [&](size_t i0, size_t m, const HitsArgs &a) {
+        HIPCHK(hipMemcpyAsync(c->scratch[0], ref + i0, m + k - 1, hipMemcpyHostToDevice, c->stream));
+        unsigned long long *slot;
+        if (int st = take_slot(c, i0, &slot, err)) return st;
+        return launch_hits(c, c->scratch[0], m + k - 1, k, a, slot, err);
+    });
+}
+
+int bitnuc_kmer_hdist_hits_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *pos,
+                                  uint8_t *hit_dist, size_t cap, uint64_t *n_hits, bitnuc_err *err) {
+    clear_err(err);
+    bool none;
+    if (int st = check_packed(words, n_words, n, k, &none, err)) return st;
+    if (!n_hits || (!pos && cap)) return fail(err, BITNUC_UNSUPPORTED);
+    if (none) { *n_hits = 0; return BITNUC_OK; }
+    if (on_host(c, n)) { *n_hits = bitnuc_host::kmer_hdist_hits_packed_small(words, n, k, query, tau, pos, hit_dist, cap); return BITNUC_OK; }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    if (int st = ensure_scratch(c, 0, (kPackedChunkWords + 1) * 8, err)) return st;
+    // chunk w0 / 32 of whole words (packed_chunk): its windows start at base i0 = 32 w0
+    return hits_host_loop(c, n - k + 1, 32 * kPackedChunkWords, tau, query, pos, hit_dist, cap, n_hits, err, [&](size_t i0, size_t, const HitsArgs &a) {
+        const PackedChunk ch = packed_chunk(i0 / 32, n, k);
+        HIPCHK(hipMemcpyAsync(c->scratch[0], words + ch.w0, ch.words * 8, hipMemcpyHostToDevice, c->stream));
+        return launch_hits_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), ch.bases, k, a, err);
+    });
 }
 
 } // extern "C"

@@ -145,12 +145,21 @@ __device__ __forceinline__ void pack_distances(const f32x16 &acc, uint32_t (&o)[
 // Lane (n, h) holds windows 32 n + 8 q + 4 h + i (q = r >> 2, i = r & 3), i.e. after the pack one dword per q with four consecutive distance bytes.  Two
 // v_permlane32_swap (lanes l and l + 32 exchange a register: a's lanes 32-63 <-> b's lanes 0-31) give lane (n, 0) the dwords (q0, partner's q0, q1, partner's
 // q1) = bytes 32 n .. 32 n + 15 and lane (n, 1) (partner's q2, q2, partner's q3, q3) = bytes 32 n + 16 .. 32 n + 31: one dwordx4 store per lane at
-// p = the round's first byte + 16 (2 n + h).  ALIGNED: store_group<NT, true>; otherwise a nontemporal store to any byte address.
-template <bool NT, bool ALIGNED>
-__device__ __forceinline__ void store_distances(uint8_t *p, const uint32_t (&o)[4]) {
+// p = the round's first byte + 16 (2 n + h) (store_distances).  ALIGNED: store_group<NT, true>; otherwise a nontemporal store to any byte address.
+__device__ __forceinline__ u32x4 distances_in_order(const uint32_t (&o)[4]) {
     const auto s02 = __builtin_amdgcn_permlane32_swap(o[0], o[2], false, false);
     const auto s13 = __builtin_amdgcn_permlane32_swap(o[1], o[3], false, false);
-    const u32x4 v = {s02[0], s02[1], s13[0], s13[1]};
+    return u32x4{s02[0], s02[1], s13[0], s13[1]};
+}
+// ... the packed distances of a round's results in that order (the hit list: scan_hits_device.h)
+__device__ __forceinline__ u32x4 distances_in_order(const f32x16 &acc) {
+    uint32_t o[4];
+    pack_distances(acc, o);
+    return distances_in_order(o);
+}
+template <bool NT, bool ALIGNED>
+__device__ __forceinline__ void store_distances(uint8_t *p, const uint32_t (&o)[4]) {
+    const u32x4 v = distances_in_order(o);
     if constexpr (ALIGNED) store_group<NT, true>(p, v);
     else {
         static_assert(NT, "unaligned distance stores are nontemporal");

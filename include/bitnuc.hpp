@@ -250,6 +250,27 @@ class Context {
         if (bitnuc_kmer_hdist_count_packed(ctx_, words.ptr, words.len, n, k, query, tau, &count, &e) != BITNUC_OK) return NucleotideError::from_c(e);
         return count;
     }
+    // the positions (ascending) of the windows with distance <= tau, sized by a first call with cap 0; hit_dist, when given, gets their distances
+    Result<std::vector<uint64_t>> kmer_hdist_hits(Bytes ref, size_t k, uint64_t query, unsigned tau, std::vector<uint8_t> *hit_dist = nullptr) const {
+        uint64_t total = 0;
+        bitnuc_err e;
+        if (bitnuc_kmer_hdist_hits(ctx_, ref.ptr, ref.len, k, query, tau, nullptr, nullptr, 0, &total, &e) != BITNUC_OK) return NucleotideError::from_c(e);
+        std::vector<uint64_t> pos((size_t)total);
+        if (hit_dist) hit_dist->assign((size_t)total, 0);
+        if (total && bitnuc_kmer_hdist_hits(ctx_, ref.ptr, ref.len, k, query, tau, pos.data(), hit_dist ? hit_dist->data() : nullptr, pos.size(), &total, &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return pos;
+    }
+    Result<std::vector<uint64_t>> kmer_hdist_hits_packed(Words words, size_t n, size_t k, uint64_t query, unsigned tau, std::vector<uint8_t> *hit_dist = nullptr) const {
+        uint64_t total = 0;
+        bitnuc_err e;
+        if (bitnuc_kmer_hdist_hits_packed(ctx_, words.ptr, words.len, n, k, query, tau, nullptr, nullptr, 0, &total, &e) != BITNUC_OK) return NucleotideError::from_c(e);
+        std::vector<uint64_t> pos((size_t)total);
+        if (hit_dist) hit_dist->assign((size_t)total, 0);
+        if (total && bitnuc_kmer_hdist_hits_packed(ctx_, words.ptr, words.len, n, k, query, tau, pos.data(), hit_dist ? hit_dist->data() : nullptr, pos.size(), &total, &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return pos;
+    }
 
     // Ragged batch: `for s in seqs { encode(s, &mut ebuf)? }` in one launch.  Sequence i =
     // seq[offsets[i] .. offsets[i+1]); returns the concatenated words and fills word_offsets

@@ -172,6 +172,25 @@ int bitnuc_kmer_hdist_count_packed_dev(bitnuc_ctx *ctx, const uint64_t *d_words,
 /* Host-pointer forms, sized like bitnuc_hdist: below the host cutoff they run on the host (ctx may be NULL), above it through the context. */
 int bitnuc_kmer_hdist_scan_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t n_words, size_t n, size_t k, uint64_t query, uint8_t *dist, bitnuc_err *err);
 int bitnuc_kmer_hdist_count_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t n_words, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *count, bitnuc_err *err);
+/* The POSITIONS of the windows the count counts (a hit list).  *n_hits = the number of windows i with hdist_scalar(as_2bit(ref[i..i+k]), query, k) <= tau
+ * -- exactly the count's value for the same arguments, and it may exceed cap.  pos[0 .. min(cap, *n_hits)) = the first such windows in ASCENDING
+ * order; hit_dist[j] = the distance of window pos[j] (hit_dist may be NULL: not written).  Nothing at or beyond index cap is written in either array.
+ * The result is deterministic.  tau >= k makes every window a hit (any unsigned tau is valid); k == 0 or n < k -> OK with *n_hits = 0.
+ * Checks, in this order: the count's (ASCII: k > 32 -> SEQUENCE_TOO_LONG(k); packed: as the packed scan above), then n_hits NULL or not 8-byte aligned,
+ * pos not 8-byte aligned or NULL with cap > 0 -> UNSUPPORTED (host forms: NULL only), then no windows -> OK, then a NULL ref -> UNSUPPORTED.
+ * An invalid base -> INVALID_BASE with the first invalid byte in sequence order, as the count (the _dev forms latch it for bitnuc_ctx_sync(); pos
+ * and hit_dist are then unspecified).  d_ref may have any alignment at the same speed (the up to 15 windows before its first 16-byte aligned base take
+ * the tail's path); d_words 16-byte aligned or at 8 mod 16.  The _dev forms are asynchronous on the context's stream (no host synchronisation: three
+ * launches, the per-trip counts in context scratch) and can be captured into a hipGraph; d_n_hits is one uint64 in device memory.  The host forms
+ * are synchronous: below the host cutoff on the host (ctx may be NULL), above it through the context in chunks of 128 M windows. */
+int bitnuc_kmer_hdist_hits_dev(bitnuc_ctx *ctx, const uint8_t *d_ref, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *d_pos, uint8_t *d_hit_dist,
+                               size_t cap, uint64_t *d_n_hits, bitnuc_err *err);
+int bitnuc_kmer_hdist_hits_packed_dev(bitnuc_ctx *ctx, const uint64_t *d_words, size_t n_words, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *d_pos,
+                                      uint8_t *d_hit_dist, size_t cap, uint64_t *d_n_hits, bitnuc_err *err);
+int bitnuc_kmer_hdist_hits(bitnuc_ctx *ctx, const uint8_t *ref, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *pos, uint8_t *hit_dist, size_t cap,
+                           uint64_t *n_hits, bitnuc_err *err);
+int bitnuc_kmer_hdist_hits_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t n_words, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *pos,
+                                  uint8_t *hit_dist, size_t cap, uint64_t *n_hits, bitnuc_err *err);
 /* d_result: one uint32 in device memory, overwritten with the distance. */
 int bitnuc_hdist_dev(bitnuc_ctx *ctx, const uint64_t *d_a, size_t na, const uint64_t *d_b, size_t nb, size_t n_bases, uint32_t *d_result, bitnuc_err *err);
 

@@ -119,6 +119,10 @@ extern "C" {
     pub fn bitnuc_kmer_hdist_count_packed_dev(ctx: *mut bitnuc_ctx, d_words: *const u64, n_words: usize, n: usize, k: usize, query: u64, tau: c_uint, d_count: *mut u64, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_kmer_hdist_scan_packed(ctx: *mut bitnuc_ctx, words: *const u64, n_words: usize, n: usize, k: usize, query: u64, dist: *mut u8, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_kmer_hdist_count_packed(ctx: *mut bitnuc_ctx, words: *const u64, n_words: usize, n: usize, k: usize, query: u64, tau: c_uint, count: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_hdist_hits_dev(ctx: *mut bitnuc_ctx, d_ref: *const u8, n: usize, k: usize, query: u64, tau: c_uint, d_pos: *mut u64, d_hit_dist: *mut u8, cap: usize, d_n_hits: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_hdist_hits_packed_dev(ctx: *mut bitnuc_ctx, d_words: *const u64, n_words: usize, n: usize, k: usize, query: u64, tau: c_uint, d_pos: *mut u64, d_hit_dist: *mut u8, cap: usize, d_n_hits: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_hdist_hits(ctx: *mut bitnuc_ctx, reference: *const u8, n: usize, k: usize, query: u64, tau: c_uint, pos: *mut u64, hit_dist: *mut u8, cap: usize, n_hits: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_hdist_hits_packed(ctx: *mut bitnuc_ctx, words: *const u64, n_words: usize, n: usize, k: usize, query: u64, tau: c_uint, pos: *mut u64, hit_dist: *mut u8, cap: usize, n_hits: *mut u64, err: *mut bitnuc_err) -> c_int;
     // diagnostics
     pub fn bitnuc_selftime_small(op: c_int, n: usize, iters: usize) -> f64;
 }

@@ -240,6 +240,39 @@ pub fn kmer_hdist_count_packed(words: &[u64], n: usize, k: usize, query: u64, ta
     if st == ffi::BITNUC_OK { Ok(count) } else { Err(to_err(&e)) }
 }
 
+/// The positions (ascending) and distances of the windows of `reference` whose Hamming distance to `query` is at most `tau`: a first call
+/// with cap 0 returns their number, a second fills the lists.
+pub fn kmer_hdist_hits(reference: &[u8], k: usize, query: u64, tau: u32) -> Result<(Vec<u64>, Vec<u8>), NucleotideError> {
+    let mut total = 0u64;
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_hdist_hits(c, reference.as_ptr(), reference.len(), k, query, tau, std::ptr::null_mut(), std::ptr::null_mut(), 0, &mut total, &mut e)
+    });
+    if st != ffi::BITNUC_OK { return Err(to_err(&e)); }
+    let mut pos = vec![0u64; total as usize];
+    let mut dist = vec![0u8; total as usize];
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_hdist_hits(c, reference.as_ptr(), reference.len(), k, query, tau, pos.as_mut_ptr(), dist.as_mut_ptr(), pos.len(), &mut total, &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok((pos, dist)) } else { Err(to_err(&e)) }
+}
+
+/// `kmer_hdist_hits` of the packed sequence `words` holding `n` bases, without decoding it.
+pub fn kmer_hdist_hits_packed(words: &[u64], n: usize, k: usize, query: u64, tau: u32) -> Result<(Vec<u64>, Vec<u8>), NucleotideError> {
+    let mut total = 0u64;
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_hdist_hits_packed(c, words.as_ptr(), words.len(), n, k, query, tau, std::ptr::null_mut(), std::ptr::null_mut(), 0, &mut total, &mut e)
+    });
+    if st != ffi::BITNUC_OK { return Err(to_err(&e)); }
+    let mut pos = vec![0u64; total as usize];
+    let mut dist = vec![0u8; total as usize];
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_hdist_hits_packed(c, words.as_ptr(), words.len(), n, k, query, tau, pos.as_mut_ptr(), dist.as_mut_ptr(), pos.len(), &mut total, &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok((pos, dist)) } else { Err(to_err(&e)) }
+}
+
 /// `for s in seqs { encode(s, &mut ebuf)? }` in one launch: sequence i =
 /// `seq[offsets[i]..offsets[i+1]]`; returns (concatenated words, word_offsets).
 pub fn encode_batch(seq: &[u8], offsets: &[u64]) -> Result<(Vec<u64>, Vec<u64>), NucleotideError> {
