@@ -59,6 +59,10 @@ SIGNATURES = {
     "bitnuc_kmer_hdist_hits_packed_dev": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _U64, C.c_uint, _P, _P, _SZ, _P, _ERR]),
     "bitnuc_kmer_hdist_hits": (C.c_int, [_P, _P, _SZ, _SZ, _U64, C.c_uint, _P, _P, _SZ, C.POINTER(_U64), _ERR]),
     "bitnuc_kmer_hdist_hits_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _U64, C.c_uint, _P, _P, _SZ, C.POINTER(_U64), _ERR]),
+    "bitnuc_kmer_hdist_count_multi_dev": (C.c_int, [_P, _P, _SZ, _SZ, _P, _P, _SZ, _P, _ERR]),
+    "bitnuc_kmer_hdist_count_multi_packed_dev": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _P, _SZ, _P, _ERR]),
+    "bitnuc_kmer_hdist_count_multi": (C.c_int, [_P, _P, _SZ, _SZ, _P, _P, _SZ, _P, _ERR]),
+    "bitnuc_kmer_hdist_count_multi_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _P, _SZ, _P, _ERR]),
     "bitnuc_hdist_dev": (C.c_int, [_P, _P, _SZ, _P, _SZ, _SZ, _P, _ERR]),
     "bitnuc_batch_word_offsets_dev": (C.c_int, [_P, _P, _SZ, _P, C.POINTER(_SZ), _ERR]),
     "bitnuc_encode_batch_dev": (C.c_int, [_P, _P, _P, _P, _SZ, _SZ, _P, _ERR]),

@@ -328,6 +328,41 @@ class Context:
         w = _as_u64(words)
         return self._hits(self._lib.bitnuc_kmer_hdist_hits_packed, (_ptr(w), w.size, int(n_bases), int(k), C.c_uint64(query), int(tau)), with_dist)
 
+    @staticmethod
+    def _multi_args(queries, taus):
+        """(queries as np.uint64, taus as np.uint32): taus may be a scalar, broadcast to every query"""
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.uint64).reshape(-1))
+        t = np.asarray(taus, dtype=np.int64)
+        if t.ndim == 0:
+            t = np.full(q.size, int(t), dtype=np.int64)
+        t = t.reshape(-1)
+        if t.size != q.size:
+            raise ValueError("taus must be a scalar or hold one threshold per query")
+        if t.size and (t.min() < 0 or t.max() > 2**32 - 1):
+            raise ValueError("thresholds are uint32")
+        return q, np.ascontiguousarray(t.astype(np.uint32))
+
+    def kmer_hdist_count_multi(self, ref, k, queries, taus):
+        """counts[q] = the number of windows of `ref` with Hamming distance <= taus[q] to queries[q], one pass for all queries -> np.uint64"""
+        s = _as_u8(ref)
+        q, t = self._multi_args(queries, taus)
+        out = np.empty(q.size, dtype=np.uint64)
+        err = L.BitnucErr()
+        if self._lib.bitnuc_kmer_hdist_count_multi(self._h, _ptr(s), s.size, int(k), _ptr(q), _ptr(t), q.size, _ptr(out), C.byref(err)) != L.OK:
+            _raise(err)
+        return out
+
+    def kmer_hdist_count_multi_packed(self, words, n_bases, k, queries, taus):
+        """kmer_hdist_count_multi of the packed sequence `words` holding `n_bases` bases, without decoding it."""
+        w = _as_u64(words)
+        q, t = self._multi_args(queries, taus)
+        out = np.empty(q.size, dtype=np.uint64)
+        err = L.BitnucErr()
+        if self._lib.bitnuc_kmer_hdist_count_multi_packed(self._h, _ptr(w), w.size, int(n_bases), int(k), _ptr(q), _ptr(t), q.size, _ptr(out),
+                                                          C.byref(err)) != L.OK:
+            _raise(err)
+        return out
+
     # -- analysis on packed words (src/utils/analysis.rs, hamming/scalar.rs) ------------------
     def base_counts(self, words, n_bases):
         """[A, C, G, T] counts of a packed sequence (BaseCount::base_counts, analysis.rs:23-39)."""
@@ -547,6 +582,16 @@ class Context:
         """The hit list on packed words in device memory (8-byte aligned)."""
         self._call_dev(self._lib.bitnuc_kmer_hdist_hits_packed_dev, _dev_ptr(d_words), int(n_words), int(n), int(k), C.c_uint64(query), int(tau),
                        _dev_ptr(d_pos), _dev_ptr(d_hit_dist), int(cap), _dev_ptr(d_n_hits))
+
+    def kmer_hdist_count_multi_dev(self, d_ref, n, k, d_queries, d_taus, n_queries, d_counts):
+        """The fused count for n_queries queries at once: d_counts[q] (u64) = windows with distance <= d_taus[q] (u32) to d_queries[q] (u64)."""
+        self._call_dev(self._lib.bitnuc_kmer_hdist_count_multi_dev, _dev_ptr(d_ref), int(n), int(k), _dev_ptr(d_queries), _dev_ptr(d_taus), int(n_queries),
+                       _dev_ptr(d_counts))
+
+    def kmer_hdist_count_multi_packed_dev(self, d_words, n_words, n, k, d_queries, d_taus, n_queries, d_counts):
+        """The multi-query count on packed words in device memory (8-byte aligned)."""
+        self._call_dev(self._lib.bitnuc_kmer_hdist_count_multi_packed_dev, _dev_ptr(d_words), int(n_words), int(n), int(k), _dev_ptr(d_queries),
+                       _dev_ptr(d_taus), int(n_queries), _dev_ptr(d_counts))
 
     def hdist_dev(self, d_a, na, d_b, nb, n_bases, d_result):
         self._call_dev(self._lib.bitnuc_hdist_dev, _dev_ptr(d_a), int(na), _dev_ptr(d_b), int(nb), int(n_bases), _dev_ptr(d_result))

@@ -2,14 +2,16 @@
 // <= 32-mers (BASELINE config 3, README.md:52-56), every window of a sequence (src/lib.rs:170-173), the sliding pack +
 // Hamming scan (config 5: packing/mod.rs:80-110 o hamming/scalar.rs:11-48) and bulk hdist (hamming/multi.rs:121-160).
 // Kernels: kmer_device.h; config 5 on the matrix cores: scan_mfma_device.h; the same scan and count on packed words: scan_packed_device.h; the hit
-// lists of both: scan_hits_device.h.
+// lists of both: scan_hits_device.h; the count for many queries at once: scan_multi_device.h.
 #include "runtime.h"
 #include "kmer_device.h"
 #include "scan_mfma_device.h"
 #include "scan_packed_device.h"
 #include "scan_hits_device.h"
+#include "scan_multi_device.h"
 #include "scan_mfma_host.h"
 #include "scan_hits_host.h"
+#include "scan_multi_host.h"
 #include "host_word.h"
 #include "host_pipe.h"
 
@@ -320,6 +322,86 @@ int hits_host_loop(bitnuc_ctx *c, size_t nwin, size_t per, unsigned tau, uint64_
         total += part;
     }
     *n_hits = total;
+    return BITNUC_OK;
+}
+
+// ---- the count for many queries (scan_multi_device.h).  Context scratch 8 holds the tables (one Count3MfmaTable per query, built in-stream from d_queries /
+// d_taus); a launch recorded into a hipGraph keeps it (ensure_scratch: warm up with the same n_queries before capturing).  counts[] is zeroed first in the
+// same stream, then every workgroup adds its per-query sums.  The grid: kMultiGrid workgroups per CU at most (one fits a CU's LDS) x the query blocks.
+constexpr int kMultiGrid = 1;
+
+struct MultiArgs { const uint64_t *queries; const uint32_t *taus; size_t nq; unsigned long long *counts; };
+
+template <bool PACKED>
+int multi_setup(bitnuc_ctx *c, size_t k, const MultiArgs &a, unsigned long long rounds, const Count3MfmaTable **tabs, dim3 *grid, bitnuc_err *err) {
+    if (int st = ensure_scratch(c, 8, a.nq * sizeof(Count3MfmaTable), err)) return st;
+    Count3MfmaTable *t = reinterpret_cast<Count3MfmaTable *>(c->scratch[8]);
+    HIPCHK(hipMemsetAsync(a.counts, 0, a.nq * sizeof(uint64_t), c->stream));
+    count3_tables_kernel<PACKED><<<(unsigned)a.nq, 64, 0, c->stream>>>(reinterpret_cast<const unsigned long long *>(a.queries), a.taus, (unsigned)k, t);
+    HIPCHK(hipGetLastError());
+    *tabs = t;
+    *grid = dim3(bounded_grid(c, rounds, (kMultiBlock / 64) * kMultiRounds, kMultiGrid), (unsigned)((a.nq + kMultiQB - 1) / kMultiQB), 1);
+    return BITNUC_OK;
+}
+
+// d_ref at any alignment: the rounds start at its first 16-byte aligned base (the hit lists' rule)
+int launch_count_multi(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const MultiArgs &a, unsigned long long *slot, bitnuc_err *err) {
+    const unsigned skip = (unsigned)((16 - (reinterpret_cast<uintptr_t>(ref) & 15)) & 15);
+    const Count3MfmaTable *tabs;
+    dim3 grid;
+    if (int st = multi_setup<false>(c, k, a, scan_rounds(n, skip), &tabs, &grid, err)) return st;
+    kmer_count3_multi_kernel<kMultiRounds><<<grid, kMultiBlock, 0, c->stream>>>(ref, n, skip, (unsigned)k, reinterpret_cast<const unsigned long long *>(a.queries),
+                                                                               a.taus, (unsigned)a.nq, tabs, a.counts, slot);
+    HIPCHK(hipGetLastError());
+    return BITNUC_OK;
+}
+
+// d_words 8-byte aligned (checked by the callers): at 8 mod 16 the rounds start one word later, as the packed count's
+int launch_count_multi_packed(bitnuc_ctx *c, const uint64_t *words, size_t n, size_t k, const MultiArgs &a, bitnuc_err *err) {
+    const unsigned skip = aligned16(words) ? 0u : 32u;
+    const Count3MfmaTable *tabs;
+    dim3 grid;
+    if (int st = multi_setup<true>(c, k, a, scan_rounds(n, skip), &tabs, &grid, err)) return st;
+    packed_count3_multi_kernel<<<grid, kMultiBlock, 0, c->stream>>>(words, n, skip, (unsigned)k, reinterpret_cast<const unsigned long long *>(a.queries), a.taus,
+                                                                    (unsigned)a.nq, tabs, a.counts);
+    HIPCHK(hipGetLastError());
+    return BITNUC_OK;
+}
+
+// the multi-query calls' checks 4 - 6 (after ctx, k and the packed word count): n_queries == 0 -> OK (*none), too many queries, the three arrays
+int check_multi(const void *queries, const void *taus, size_t nq, const void *counts, bool *none, bitnuc_err *err) {
+    *none = nq == 0;
+    if (*none) return BITNUC_OK;
+    if (nq > BITNUC_MAX_QUERIES) return fail(err, BITNUC_UNSUPPORTED, nq);
+    if (!counts || (reinterpret_cast<uintptr_t>(counts) & 7) || !queries || (reinterpret_cast<uintptr_t>(queries) & 7) || !taus ||
+        (reinterpret_cast<uintptr_t>(taus) & 3))
+        return fail(err, BITNUC_UNSUPPORTED);
+    return BITNUC_OK;
+}
+
+// windows x queries, saturated: what the host forms' cutoff is judged on
+inline size_t multi_work(size_t nwin, size_t nq) { return nwin > (size_t)-1 / nq ? (size_t)-1 : nwin * nq; }
+
+// The host forms' chunk loop: queries and thresholds copied once into scratch 2, the chunk's counts in scratch 1; `launch(i0, a)` runs the chunk of
+// windows starting at i0 with a's device arrays.  Sums per query; stops at the first failing chunk (drain: its first invalid byte).
+template <class Launch>
+int multi_host_loop(bitnuc_ctx *c, size_t nwin, size_t per, const uint64_t *queries, const uint32_t *taus, size_t nq, uint64_t *counts, bitnuc_err *err,
+                    Launch launch) {
+    if (int st = ensure_scratch(c, 1, nq * 8, err)) return st;
+    if (int st = ensure_scratch(c, 2, nq * 12, err)) return st;
+    HIPCHK(hipMemcpyAsync(c->scratch[2], queries, nq * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->scratch[2] + nq * 8, taus, nq * 4, hipMemcpyHostToDevice, c->stream));
+    const MultiArgs a{reinterpret_cast<const uint64_t *>(c->scratch[2]), reinterpret_cast<const uint32_t *>(c->scratch[2] + nq * 8), nq,
+                      reinterpret_cast<unsigned long long *>(c->scratch[1])};
+    std::vector<uint64_t> part(nq), total(nq, 0);
+    for (size_t i0 = 0; i0 < nwin; i0 += per) {
+        if (int st = launch(i0, a)) return st;
+        HIPCHK(hipMemcpyAsync(part.data(), c->scratch[1], nq * 8, hipMemcpyDeviceToHost, c->stream));
+        bitnuc_err e;
+        if (int st = drain(c, &e)) { if (err) *err = e; return st; }
+        for (size_t q = 0; q < nq; ++q) total[q] += part[q];
+    }
+    memcpy(counts, total.data(), nq * 8);
     return BITNUC_OK;
 }
 
@@ -675,6 +757,102 @@ int bitnuc_kmer_hdist_hits_packed(bitnuc_ctx *c, const uint64_t *words, size_t n
         const PackedChunk ch = packed_chunk(i0 / 32, n, k);
         HIPCHK(hipMemcpyAsync(c->scratch[0], words + ch.w0, ch.words * 8, hipMemcpyHostToDevice, c->stream));
         return launch_hits_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), ch.bases, k, a, err);
+    });
+}
+
+// ---- the count for many queries -----------------------------------------------------------------------------------------
+int bitnuc_kmer_hdist_count_multi_dev(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const uint64_t *d_queries, const uint32_t *d_taus, size_t n_queries,
+                                      uint64_t *d_counts, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    bool none;
+    if (int st = check_multi(d_queries, d_taus, n_queries, d_counts, &none, err)) return st;
+    if (none) return BITNUC_OK;
+    DeviceGuard g(c->device);
+    if (k == 0 || n < k) { // no windows
+        HIPCHK(hipMemsetAsync(d_counts, 0, n_queries * sizeof(uint64_t), c->stream));
+        return BITNUC_OK;
+    }
+    if (!d_ref) return fail(err, BITNUC_UNSUPPORTED);
+    unsigned long long *slot;
+    if (int st = take_slot(c, 0, &slot, err)) return st;
+    return launch_count_multi(c, d_ref, n, k, MultiArgs{d_queries, d_taus, n_queries, reinterpret_cast<unsigned long long *>(d_counts)}, slot, err);
+}
+
+int bitnuc_kmer_hdist_count_multi_packed_dev(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const uint64_t *d_queries,
+                                             const uint32_t *d_taus, size_t n_queries, uint64_t *d_counts, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
+    bool none;
+    if (int st = check_multi(d_queries, d_taus, n_queries, d_counts, &none, err)) return st;
+    if (none) return BITNUC_OK;
+    DeviceGuard g(c->device);
+    if (k == 0 || n < k) {
+        HIPCHK(hipMemsetAsync(d_counts, 0, n_queries * sizeof(uint64_t), c->stream));
+        return BITNUC_OK;
+    }
+    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    return launch_count_multi_packed(c, d_words, n, k, MultiArgs{d_queries, d_taus, n_queries, reinterpret_cast<unsigned long long *>(d_counts)}, err);
+}
+
+int bitnuc_kmer_hdist_count_multi(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const uint64_t *queries, const uint32_t *taus, size_t n_queries,
+                                  uint64_t *counts, bitnuc_err *err) {
+    clear_err(err);
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    bool none;
+    if (int st = check_multi(queries, taus, n_queries, counts, &none, err)) return st;
+    if (none) return BITNUC_OK;
+    if (k == 0 || n < k) { memset(counts, 0, n_queries * sizeof(uint64_t)); return BITNUC_OK; }
+    if (!ref) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, multi_work(n - k + 1, n_queries))) {
+        const long long bad = bitnuc_host::kmer_hdist_count_multi_small(ref, n, k, queries, taus, n_queries, counts);
+        if (bad >= 0) {
+            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = ref[bad]; err->index = (uint64_t)bad; }
+            return BITNUC_INVALID_BASE;
+        }
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    // chunks of kHostChunk windows + their k - 1 halo bases
+    if (int st = ensure_scratch(c, 0, kHostChunk + 64, err)) return st;
+    const size_t nwin = n - k + 1;
+    return multi_host_loop(c, nwin, kHostChunk, queries, taus, n_queries, counts, err, [&](size_t i0, const MultiArgs &a) {
+        const size_t m = nwin - i0 < kHostChunk ? nwin - i0 : kHostChunk;
+        HIPCHK(hipMemcpyAsync(c->scratch[0], ref + i0, m + k - 1, hipMemcpyHostToDevice, c->stream));
+        unsigned long long *slot;
+        if (int st = take_slot(c, i0, &slot, err)) return st;
+        return launch_count_multi(c, c->scratch[0], m + k - 1, k, a, slot, err);
+    });
+}
+
+int bitnuc_kmer_hdist_count_multi_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const uint64_t *queries, const uint32_t *taus,
+                                         size_t n_queries, uint64_t *counts, bitnuc_err *err) {
+    clear_err(err);
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
+    bool none;
+    if (int st = check_multi(queries, taus, n_queries, counts, &none, err)) return st;
+    if (none) return BITNUC_OK;
+    if (k == 0 || n < k) { memset(counts, 0, n_queries * sizeof(uint64_t)); return BITNUC_OK; }
+    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, multi_work(n - k + 1, n_queries))) {
+        bitnuc_host::kmer_hdist_count_multi_packed_small(words, n, k, queries, taus, n_queries, counts);
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    if (int st = ensure_scratch(c, 0, (kPackedChunkWords + 1) * 8, err)) return st;
+    // chunk w0 / 32 of whole words (packed_chunk): its windows start at base i0 = 32 w0
+    return multi_host_loop(c, n - k + 1, 32 * kPackedChunkWords, queries, taus, n_queries, counts, err, [&](size_t i0, const MultiArgs &a) {
+        const PackedChunk ch = packed_chunk(i0 / 32, n, k);
+        HIPCHK(hipMemcpyAsync(c->scratch[0], words + ch.w0, ch.words * 8, hipMemcpyHostToDevice, c->stream));
+        return launch_count_multi_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), ch.bases, k, a, err);
     });
 }
 

@@ -124,9 +124,10 @@ struct bitnuc_ctx {
     int n_cap = 0;
     std::vector<bitnuc_err> deferred; // data errors found by implicit drains (host-pointer calls start from an empty ring), oldest first: one per bitnuc_ctx_sync
     // ---- scratch ----
-    uint8_t *scratch[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t scratch_cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    bool scratch_in_graph[8] = {false, false, false, false, false, false, false, false}; // handed to a launch recorded into a hipGraph: never freed before the context
+    // [8]: the multi-query count's per-query tables (kmer.hip launch_count_multi)
+    uint8_t *scratch[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t scratch_cap[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    bool scratch_in_graph[9] = {false, false, false, false, false, false, false, false, false}; // handed to a launch recorded into a hipGraph: never freed before the context
     std::vector<uint8_t *> retired_scratch; // ... outgrown since: alive until bitnuc_ctx_destroy (a replay still writes through them)
     uint32_t *d_sink = nullptr;
     unsigned long long *d_acc = nullptr; // accumulators of the single-launch reductions, zero between launches: [0..2] base_counts C,G,T; [4] hdist (u32); [5] scan count; [6] packed scan count

@@ -265,7 +265,7 @@ void bitnuc_ctx_destroy(bitnuc_ctx *c) {
     if (!c) return;
     DeviceGuard g(c->device);
     (void)hipStreamSynchronize(c->stream);
-    for (int i = 0; i < 8; ++i)
+    for (int i = 0; i < (int)(sizeof c->scratch / sizeof c->scratch[0]); ++i)
         if (c->scratch[i]) (void)hipFree(c->scratch[i]);
     for (uint8_t *p : c->retired_scratch) (void)hipFree(p);
     for (SlotBlock &b : c->slots) slot_block_free(&b);

@@ -6,6 +6,14 @@
 #include <stdint.h>
 #include <string.h>
 
+// The three-channel count's table builders (Count3Rule, count3_mfma_table, count3_packed_table) run on the host for the single-query counts and on the
+// device for the multi-query counts (scan_multi_device.h builds one table per query in-stream): one source for both.  Plain g++ sees nothing.
+#if defined(__HIP__)
+#define BITNUC_HD __host__ __device__
+#else
+#define BITNUC_HD
+#endif
+
 namespace bitnuc_dev {
 struct CountMfmaTable { uint32_t w[40][16]; float c[4]; }; // c[r & 3]: where result register r's accumulator starts
 struct Count3MfmaTable { uint32_t w[64][12]; float c[4]; };
@@ -92,11 +100,11 @@ struct Count3Rule {
     unsigned tau;
     bool distance, all;
     unsigned non_t;
-    Count3Rule(uint64_t query, size_t k, unsigned tau, bool distance) : query(query), k(k), tau(tau), distance(distance), all(!distance && tau >= k), non_t(0) {
+    BITNUC_HD Count3Rule(uint64_t query, size_t k, unsigned tau, bool distance) : query(query), k(k), tau(tau), distance(distance), all(!distance && tau >= k), non_t(0) {
         for (size_t i = 0; i < k; ++i) non_t += ((query >> (2 * i)) & 3) != 3;
     }
     // the nibble row m meets at segment position p on channel ch (0 = A, 1 = C, 2 = G): 0, +1.0 (0x2) or -1.0 (0xA)
-    uint32_t nibble(int m, int p, unsigned ch) const {
+    BITNUC_HD uint32_t nibble(int m, int p, unsigned ch) const {
         const int i = p - m;
         if (all || i < 0 || i >= (int)k) return 0u;
         const unsigned q = (unsigned)((query >> (2 * i)) & 3);
@@ -104,7 +112,7 @@ struct Count3Rule {
         const int e = distance || (m & 3) == 3 ? v : -v;
         return e == 0 ? 0u : e > 0 ? 0x2u : 0xAu;
     }
-    void start(float *c) const {
+    BITNUC_HD void start(float *c) const {
         if (distance) {
             for (int j = 0; j < 4; ++j) c[j] = kPackBias + (float)(non_t << (j == 3 ? 0 : 8 * j));
             return;
@@ -117,23 +125,25 @@ struct Count3Rule {
 // ... its table in the ASCII K order: per lane (row m = lane & 31, K-block h = lane >> 5) and K-step, the 32 nibbles that meet the lane's operand --
 // K-steps 0 / 1: the (A, C) bytes of positions 32 s + 16 h + b; K-step 2: the G nibbles of positions 32 h .. + 31, byte b holding positions 8 (b >> 2) + (b & 3)
 // and that + 4.
-inline void count3_mfma_table(uint64_t query, size_t k, unsigned tau, Count3MfmaTable *t, bool distance = false) {
-    const Count3Rule r(query, k, tau, distance);
-    for (int lane = 0; lane < 64; ++lane) {
-        const int m = lane & 31, h = lane >> 5;
-        for (int s = 0; s < 3; ++s)
-            for (int i = 0; i < 4; ++i) {
-                uint32_t w = 0;
-                for (int bb = 0; bb < 4; ++bb) {
-                    const int b = 4 * i + bb;
-                    const int gp = 32 * h + 8 * (b >> 2) + (b & 3); // K-step 2, byte b of the lane's 16: bases gp (low nibble) and gp + 4 (high nibble) of positions 32 h .. + 31
-                    const uint32_t lo = s < 2 ? r.nibble(m, 32 * s + 16 * h + b, 0) : r.nibble(m, gp, 2);
-                    const uint32_t hi = s < 2 ? r.nibble(m, 32 * s + 16 * h + b, 1) : r.nibble(m, gp + 4, 2);
-                    w |= (lo | hi << 4) << (8 * bb);
-                }
-                t->w[lane][4 * s + i] = w;
+// (one lane's 12 dwords: count3_mfma_lane; the device builder runs one thread per lane)
+BITNUC_HD inline void count3_mfma_lane(const Count3Rule &r, int lane, uint32_t *row) {
+    const int m = lane & 31, h = lane >> 5;
+    for (int s = 0; s < 3; ++s)
+        for (int i = 0; i < 4; ++i) {
+            uint32_t w = 0;
+            for (int bb = 0; bb < 4; ++bb) {
+                const int b = 4 * i + bb;
+                const int gp = 32 * h + 8 * (b >> 2) + (b & 3); // K-step 2, byte b of the lane's 16: bases gp (low nibble) and gp + 4 (high nibble) of positions 32 h .. + 31
+                const uint32_t lo = s < 2 ? r.nibble(m, 32 * s + 16 * h + b, 0) : r.nibble(m, gp, 2);
+                const uint32_t hi = s < 2 ? r.nibble(m, 32 * s + 16 * h + b, 1) : r.nibble(m, gp + 4, 2);
+                w |= (lo | hi << 4) << (8 * bb);
             }
-    }
+            row[4 * s + i] = w;
+        }
+}
+BITNUC_HD inline void count3_mfma_table(uint64_t query, size_t k, unsigned tau, Count3MfmaTable *t, bool distance = false) {
+    const Count3Rule r(query, k, tau, distance);
+    for (int lane = 0; lane < 64; ++lane) count3_mfma_lane(r, lane, t->w[lane]);
     r.start(t->c);
 }
 
@@ -165,27 +175,28 @@ inline void scan_packed_table(uint64_t query, size_t k, PackedScanTable *t) {
 // The count (three channels per base: A, C, G one-hot, T = 0), as count3_mfma_table but in the packed K order.  K-steps 0 / 1: dword t, byte q holds
 // the (A, C) nibbles of position 16 (2 s + h) + 4 q + t; K-step 2: dword d, nibble p (byte p >> 1, high nibble when p is odd) holds the G nibble of
 // position 32 h + 16 (d >> 1) + 2 p + (d & 1).  Rows, signs, row scales and start values: Count3Rule.
-inline void count3_packed_table(uint64_t query, size_t k, unsigned tau, Count3MfmaTable *t) {
-    const Count3Rule r(query, k, tau, false);
-    for (int lane = 0; lane < 64; ++lane) {
-        const int m = lane & 31, h = lane >> 5;
-        for (int s = 0; s < 3; ++s)
-            for (int d = 0; d < 4; ++d) {
-                uint32_t w = 0;
-                for (int b = 0; b < 4; ++b) {
-                    uint32_t lo, hi;
-                    if (s < 2) {
-                        const int p = 16 * (2 * s + h) + 4 * b + d;
-                        lo = r.nibble(m, p, 0), hi = r.nibble(m, p, 1);
-                    } else {
-                        const int p = 32 * h + 16 * (d >> 1) + 4 * b + (d & 1); // nibble 2 b; nibble 2 b + 1 is two positions later
-                        lo = r.nibble(m, p, 2), hi = r.nibble(m, p + 2, 2);
-                    }
-                    w |= (lo | hi << 4) << (8 * b);
+BITNUC_HD inline void count3_packed_lane(const Count3Rule &r, int lane, uint32_t *row) {
+    const int m = lane & 31, h = lane >> 5;
+    for (int s = 0; s < 3; ++s)
+        for (int d = 0; d < 4; ++d) {
+            uint32_t w = 0;
+            for (int b = 0; b < 4; ++b) {
+                uint32_t lo, hi;
+                if (s < 2) {
+                    const int p = 16 * (2 * s + h) + 4 * b + d;
+                    lo = r.nibble(m, p, 0), hi = r.nibble(m, p, 1);
+                } else {
+                    const int p = 32 * h + 16 * (d >> 1) + 4 * b + (d & 1); // nibble 2 b; nibble 2 b + 1 is two positions later
+                    lo = r.nibble(m, p, 2), hi = r.nibble(m, p + 2, 2);
                 }
-                t->w[lane][4 * s + d] = w;
+                w |= (lo | hi << 4) << (8 * b);
             }
-    }
+            row[4 * s + d] = w;
+        }
+}
+BITNUC_HD inline void count3_packed_table(uint64_t query, size_t k, unsigned tau, Count3MfmaTable *t) {
+    const Count3Rule r(query, k, tau, false);
+    for (int lane = 0; lane < 64; ++lane) count3_packed_lane(r, lane, t->w[lane]);
     r.start(t->c);
 }
 

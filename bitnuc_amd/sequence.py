@@ -73,3 +73,6 @@ class PackedSequence:
 
     def kmer_hdist_count(self, k, query, tau):
         return self._ctx.kmer_hdist_count_packed(self.data, self.length, k, query, tau)
+
+    def kmer_hdist_count_multi(self, k, queries, taus):
+        return self._ctx.kmer_hdist_count_multi_packed(self.data, self.length, k, queries, taus)

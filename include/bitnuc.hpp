@@ -261,6 +261,23 @@ class Context {
             return NucleotideError::from_c(e);
         return pos;
     }
+    // counts[q] = windows with distance <= taus[q] to queries[q], every query in one pass (taus.size() == queries.size())
+    Result<std::vector<uint64_t>> kmer_hdist_count_multi(Bytes ref, size_t k, const std::vector<uint64_t> &queries, const std::vector<uint32_t> &taus) const {
+        if (taus.size() != queries.size()) return NucleotideError::unsupported();
+        std::vector<uint64_t> counts(queries.size());
+        bitnuc_err e;
+        if (bitnuc_kmer_hdist_count_multi(ctx_, ref.ptr, ref.len, k, queries.data(), taus.data(), queries.size(), counts.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return counts;
+    }
+    Result<std::vector<uint64_t>> kmer_hdist_count_multi_packed(Words words, size_t n, size_t k, const std::vector<uint64_t> &queries, const std::vector<uint32_t> &taus) const {
+        if (taus.size() != queries.size()) return NucleotideError::unsupported();
+        std::vector<uint64_t> counts(queries.size());
+        bitnuc_err e;
+        if (bitnuc_kmer_hdist_count_multi_packed(ctx_, words.ptr, words.len, n, k, queries.data(), taus.data(), queries.size(), counts.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return counts;
+    }
     Result<std::vector<uint64_t>> kmer_hdist_hits_packed(Words words, size_t n, size_t k, uint64_t query, unsigned tau, std::vector<uint8_t> *hit_dist = nullptr) const {
         uint64_t total = 0;
         bitnuc_err e;

@@ -191,6 +191,31 @@ int bitnuc_kmer_hdist_hits(bitnuc_ctx *ctx, const uint8_t *ref, size_t n, size_t
                            uint64_t *n_hits, bitnuc_err *err);
 int bitnuc_kmer_hdist_hits_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t n_words, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *pos,
                                   uint8_t *hit_dist, size_t cap, uint64_t *n_hits, bitnuc_err *err);
+/* The fused count for MANY queries in one pass over the reference: counts[q] = the number of windows i with
+ * hdist_scalar(as_2bit(ref[i..i+k]), queries[q], k) <= taus[q] -- exactly what bitnuc_kmer_hdist_count[_packed]_dev returns for (ref, n, k, queries[q],
+ * taus[q]).  Query bits above 2k are ignored; any uint32_t tau is valid (tau >= k counts every window), and a per-query tau costs nothing (a query repeated
+ * with tau = 0, 1, 2, 3 gives its mismatch profile in one call).  counts[0 .. n_queries) is written and nothing after it.
+ * Checks, in this order: (1) ctx NULL -> UNSUPPORTED (_dev forms; the host forms below the cutoff accept NULL); (2) k > 32 -> SEQUENCE_TOO_LONG(k);
+ * (3) packed: n_words < ceil(n/32) -> INVALID_LENGTH(n); (4) n_queries == 0 -> OK, nothing written; (5) n_queries > BITNUC_MAX_QUERIES -> UNSUPPORTED
+ * (err.value = n_queries); (6) counts, queries or taus NULL or not 8-, 8-, 4-byte aligned -> UNSUPPORTED; (7) k == 0 or n < k -> OK, every count 0;
+ * (8) a NULL reference, or packed words not 8-byte aligned -> UNSUPPORTED.
+ * ASCII: an invalid base -> INVALID_BASE with the first invalid byte in sequence order, as the single count (the _dev forms latch it once per call for
+ * bitnuc_ctx_sync(); the counts are then unspecified).  d_ref may have any alignment (the up to 15 windows before its first 16-byte aligned base take the
+ * tail's path); packed words 16-byte aligned or at 8 mod 16.
+ * The _dev forms are asynchronous on the context's stream; queries, taus and counts are in device memory.  They build one table per query in context
+ * scratch (3 KiB each) and can be captured into a hipGraph, but scratch cannot grow during a capture (BITNUC_UNSUPPORTED, err.value = the bytes needed):
+ * warm up with the same (or a larger) n_queries first.
+ * The host forms are synchronous.  When windows x n_queries is below the host cutoff (as the single-query host forms judge their bases) they run on the
+ * host and ctx may be NULL; above it they run through the context in chunks of 128 M windows that overlap by k - 1 bases, summing per query. */
+#define BITNUC_MAX_QUERIES 65536
+int bitnuc_kmer_hdist_count_multi_dev(bitnuc_ctx *ctx, const uint8_t *d_ref, size_t n, size_t k, const uint64_t *d_queries, const uint32_t *d_taus,
+                                      size_t n_queries, uint64_t *d_counts, bitnuc_err *err);
+int bitnuc_kmer_hdist_count_multi_packed_dev(bitnuc_ctx *ctx, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const uint64_t *d_queries,
+                                             const uint32_t *d_taus, size_t n_queries, uint64_t *d_counts, bitnuc_err *err);
+int bitnuc_kmer_hdist_count_multi(bitnuc_ctx *ctx, const uint8_t *ref, size_t n, size_t k, const uint64_t *queries, const uint32_t *taus, size_t n_queries,
+                                  uint64_t *counts, bitnuc_err *err);
+int bitnuc_kmer_hdist_count_multi_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t n_words, size_t n, size_t k, const uint64_t *queries,
+                                         const uint32_t *taus, size_t n_queries, uint64_t *counts, bitnuc_err *err);
 /* d_result: one uint32 in device memory, overwritten with the distance. */
 int bitnuc_hdist_dev(bitnuc_ctx *ctx, const uint64_t *d_a, size_t na, const uint64_t *d_b, size_t nb, size_t n_bases, uint32_t *d_result, bitnuc_err *err);
 

@@ -123,6 +123,11 @@ extern "C" {
     pub fn bitnuc_kmer_hdist_hits_packed_dev(ctx: *mut bitnuc_ctx, d_words: *const u64, n_words: usize, n: usize, k: usize, query: u64, tau: c_uint, d_pos: *mut u64, d_hit_dist: *mut u8, cap: usize, d_n_hits: *mut u64, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_kmer_hdist_hits(ctx: *mut bitnuc_ctx, reference: *const u8, n: usize, k: usize, query: u64, tau: c_uint, pos: *mut u64, hit_dist: *mut u8, cap: usize, n_hits: *mut u64, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_kmer_hdist_hits_packed(ctx: *mut bitnuc_ctx, words: *const u64, n_words: usize, n: usize, k: usize, query: u64, tau: c_uint, pos: *mut u64, hit_dist: *mut u8, cap: usize, n_hits: *mut u64, err: *mut bitnuc_err) -> c_int;
+    // the fused count for many queries in one pass: counts[q] = windows with distance <= taus[q] to queries[q]
+    pub fn bitnuc_kmer_hdist_count_multi_dev(ctx: *mut bitnuc_ctx, d_ref: *const u8, n: usize, k: usize, d_queries: *const u64, d_taus: *const u32, n_queries: usize, d_counts: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_hdist_count_multi_packed_dev(ctx: *mut bitnuc_ctx, d_words: *const u64, n_words: usize, n: usize, k: usize, d_queries: *const u64, d_taus: *const u32, n_queries: usize, d_counts: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_hdist_count_multi(ctx: *mut bitnuc_ctx, reference: *const u8, n: usize, k: usize, queries: *const u64, taus: *const u32, n_queries: usize, counts: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_hdist_count_multi_packed(ctx: *mut bitnuc_ctx, words: *const u64, n_words: usize, n: usize, k: usize, queries: *const u64, taus: *const u32, n_queries: usize, counts: *mut u64, err: *mut bitnuc_err) -> c_int;
     // diagnostics
     pub fn bitnuc_selftime_small(op: c_int, n: usize, iters: usize) -> f64;
 }

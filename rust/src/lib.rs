@@ -273,6 +273,29 @@ pub fn kmer_hdist_hits_packed(words: &[u64], n: usize, k: usize, query: u64, tau
     if st == ffi::BITNUC_OK { Ok((pos, dist)) } else { Err(to_err(&e)) }
 }
 
+/// `counts[q]` = the number of windows of `reference` whose Hamming distance to `queries[q]` is at most `taus[q]`, every query in one pass
+/// (`taus.len()` must equal `queries.len()`).
+pub fn kmer_hdist_count_multi(reference: &[u8], k: usize, queries: &[u64], taus: &[u32]) -> Result<Vec<u64>, NucleotideError> {
+    if taus.len() != queries.len() { return Err(NucleotideError::Unsupported); }
+    let mut counts = vec![0u64; queries.len()];
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_hdist_count_multi(c, reference.as_ptr(), reference.len(), k, queries.as_ptr(), taus.as_ptr(), queries.len(), counts.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(counts) } else { Err(to_err(&e)) }
+}
+
+/// `kmer_hdist_count_multi` of the packed sequence `words` holding `n` bases, without decoding it.
+pub fn kmer_hdist_count_multi_packed(words: &[u64], n: usize, k: usize, queries: &[u64], taus: &[u32]) -> Result<Vec<u64>, NucleotideError> {
+    if taus.len() != queries.len() { return Err(NucleotideError::Unsupported); }
+    let mut counts = vec![0u64; queries.len()];
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_hdist_count_multi_packed(c, words.as_ptr(), words.len(), n, k, queries.as_ptr(), taus.as_ptr(), queries.len(), counts.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(counts) } else { Err(to_err(&e)) }
+}
+
 /// `for s in seqs { encode(s, &mut ebuf)? }` in one launch: sequence i =
 /// `seq[offsets[i]..offsets[i+1]]`; returns (concatenated words, word_offsets).
 pub fn encode_batch(seq: &[u8], offsets: &[u64]) -> Result<(Vec<u64>, Vec<u64>), NucleotideError> {
