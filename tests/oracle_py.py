@@ -172,6 +172,38 @@ def kmer_hdist_scan(ref, k, query):
     return out
 
 
+def kmer_hdist_scan_threaded(ref, k, query, threads=None):
+    """kmer_hdist_scan over a long sequence on the host cores: 32-window-aligned slices from bitnuc_amd.dist.scan_shard_range, one oracle call
+    each (the library releases the GIL during a foreign call), at most 16 threads.  Raises OracleError for the first failing slice in
+    sequence order, its index relative to ref."""
+    from concurrent.futures import ThreadPoolExecutor
+    from bitnuc_amd.dist import scan_shard_range
+    s = _u8(ref)
+    n = s.size
+    nwin = n - k + 1 if (n >= k and k > 0) else 0
+    out = np.zeros(nwin, dtype=np.uint8)
+    if nwin == 0:
+        return out
+    threads = threads or max(1, min(16, len(os.sched_getaffinity(0))))
+    parts = max(1, min(8 * threads, nwin // (1 << 16) + 1))
+    L = lib()
+
+    def run(r):
+        first, cnt, nread = scan_shard_range(n, k, r, parts)
+        err = OrcErr()
+        if cnt and L.orc_kmer_hdist_scan(C.c_void_p(s.ctypes.data + first), nread, k, C.c_uint64(query), C.c_void_p(out.ctypes.data + first), C.byref(err)):
+            err.index += first
+            return cnt, err
+        return cnt, None
+    with ThreadPoolExecutor(threads) as ex:
+        res = list(ex.map(run, range(parts)))
+    for _, err in res:
+        if err is not None:
+            raise OracleError(err)
+    assert sum(c for c, _ in res) == nwin
+    return out
+
+
 def base_counts(words, n_bases):
     w = np.ascontiguousarray(words, dtype=np.uint64)
     out, err = np.zeros(4, dtype=np.uint64), OrcErr()

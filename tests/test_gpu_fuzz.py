@@ -265,6 +265,146 @@ def test_fuzz_scan_dev(ctx, oracle):
     assert not fails, "\n".join(fails[:20]) + f"\n({len(fails)} failing cases)"
 
 
+def _near_copies(rng, n, k, query, rate):
+    """n bases, mixed case: the query's k bases repeated end to end, each replaced by a random base with probability `rate` (small thresholds hit)"""
+    qc = np.array([(query >> (2 * b)) & 3 for b in range(k)], dtype=np.int64)
+    codes = np.resize(qc, n)
+    flip = rng.random(n) < rate
+    codes[flip] = rng.integers(0, 4, int(flip.sum()))
+    s = np.frombuffer(b"ACGT", dtype=np.uint8)[codes]
+    return np.where(rng.random(n) < 0.25, s | 0x20, s).astype(np.uint8)
+
+
+def _draw_tau(rng, k):
+    """the whole range: below k, at and just above it, and far above (the kernels clamp at 32)"""
+    r = rng.random()
+    if r < 0.6:
+        return int(rng.integers(0, k + 1))
+    if r < 0.8:
+        return k + int(rng.integers(0, 3))
+    return (2**32 - 1, 2**31, 33, 255, 256, 65536)[rng.integers(6)]
+
+
+def _draw_query(rng):
+    return int(rng.integers(0, 1 << 62)) | (int(rng.integers(0, 4)) << 62)  # bits above 2k are ignored (scalar.rs:26-31)
+
+
+def _packed_words(rng, oracle, s):
+    """the oracle's packed words of a valid sequence, junk above 2 n in the last word, up to two words more than needed"""
+    w = oracle.encode(s).copy()
+    if s.size % 32:
+        w[-1] |= np.uint64(int(rng.integers(1, 1 << 62)) << 2) & ~np.uint64((1 << (2 * (s.size % 32))) - 1)
+    return np.concatenate([w, rng.integers(0, 1 << 63, int(rng.integers(0, 3)), dtype=np.uint64)])
+
+
+def test_fuzz_hits_dev(ctx, oracle):
+    """kmer_hdist_hits_dev / _hits_packed_dev: positions, distances and *n_hits against the oracle's scan; the first invalid byte as the oracle
+    reports it; pos / hit_dist / n_hits each between canaries, at arbitrary offsets; any cap, with and without hit_dist."""
+    rng = _rng(0x4175)
+    fails = []
+    for case in range(300):
+        k = int(rng.integers(1, 33)) if case % 3 else (31, 32, 21, 16)[(case // 3) % 4]
+        n = draw_len(rng, 2_000_000, k)
+        query = _draw_query(rng)
+        s = _near_copies(rng, n, k, query, float(rng.choice([0.01, 0.05, 0.2]))) if rng.random() < 0.6 else draw_seq(rng, n)
+        bad = plant(rng, s) if rng.random() < 0.3 else []
+        tau = _draw_tau(rng, k)
+        nwin = n - k + 1
+        want_err, want = expect_error(ctx, lambda: oracle.kmer_hdist_scan(s, k, query))
+        hits = np.flatnonzero(want <= tau).astype(np.uint64) if want is not None else None
+        total = int(hits.size) if hits is not None else int(rng.integers(0, nwin + 1))
+        for packed in (False, True):
+            if packed and bad:
+                continue
+            cap = (total + int(rng.integers(0, 6)), total, max(total - 1, 0), int(rng.integers(0, total + 1)), 0, 1)[rng.integers(6)]
+            with_dist = rng.random() < 0.7
+            pos = Arena(8 * cap, 8 * int(rng.integers(0, 8)))
+            hd = Arena(cap, int(rng.integers(0, 64))) if with_dist else None
+            nh = Arena(8, 8 * int(rng.integers(0, 8)))
+            pos_ptr = pos.ptr if (cap or rng.random() < 0.5) else None  # pos may be NULL for cap 0
+            if packed:
+                words = _packed_words(rng, oracle, s)
+                src = Arena(8 * words.size, 8 * int(rng.integers(0, 8)), words)
+                ctx.kmer_hdist_hits_packed_dev(src.ptr, words.size, n, k, query, tau, pos_ptr, hd.ptr if hd else None, cap, nh.ptr)
+            else:
+                src = Arena(n, int(rng.integers(0, 64)) if case % 4 else 0, s)
+                ctx.kmer_hdist_hits_dev(src.ptr, n, k, query, tau, pos_ptr, hd.ptr if hd else None, cap, nh.ptr)
+            got_err = sync_error(ctx)
+            tag = f"hits{'_packed' if packed else ''} case {case}: n={n} k={k} tau={tau} cap={cap} hit_dist={with_dist} src+{src.off} pos+{pos.off} bad={bad[:3]}"
+            (p, p_ok), (h, h_ok) = pos.back(), nh.back()
+            d, d_ok = hd.back() if hd else (None, True)
+            if not (p_ok and h_ok and d_ok and src.back()[1]):
+                fails.append(tag + ": canary overwritten")
+            if want_err is not None:
+                if got_err != (want_err[0], want_err[1], bad[0]):
+                    fails.append(tag + f": error {got_err}, oracle {want_err}")
+                continue
+            if got_err is not None:
+                fails.append(tag + f": unexpected error {got_err}")
+                continue
+            g = min(cap, total)
+            if int(h.view(np.uint64)[0]) != total:
+                fails.append(tag + f": n_hits {int(h.view(np.uint64)[0])}, oracle {total}")
+            elif not np.array_equal(p.view(np.uint64)[:g], hits[:g]):
+                fails.append(tag + f": first differing hit {int(np.flatnonzero(p.view(np.uint64)[:g] != hits[:g])[0])}")
+            elif d is not None and not np.array_equal(d[:g], want[hits[:g].astype(np.int64)]):
+                fails.append(tag + ": a hit's distance differs from the oracle's")
+    assert not fails, "\n".join(fails[:20]) + f"\n({len(fails)} failing cases)"
+
+
+def test_fuzz_multi_dev(ctx, oracle):
+    """kmer_hdist_count_multi_dev / _multi_packed_dev with 1..48 queries (up to three query blocks, the last one partial): every count against
+    the oracle's scan for that query; the first invalid byte in sequence order, reported once; queries, thresholds and counts between canaries."""
+    rng = _rng(0x3171)
+    fails = []
+    for case in range(200):
+        k = int(rng.integers(1, 33)) if case % 3 else (31, 32, 21, 16)[(case // 3) % 4]
+        n = draw_len(rng, 2_000_000, k)
+        nq = int(rng.integers(1, 49)) if case % 5 else (1, 16, 17, 32, 33, 48)[(case // 5) % 6]
+        distinct = [_draw_query(rng) for _ in range(min(nq, int(rng.integers(1, 5))))]  # the slots repeat a few queries under other thresholds
+        s = _near_copies(rng, n, k, distinct[0], float(rng.choice([0.01, 0.05, 0.2]))) if rng.random() < 0.6 else draw_seq(rng, n)
+        bad = plant(rng, s) if rng.random() < 0.3 else []
+        which = rng.integers(0, len(distinct), nq)
+        which[0] = 0
+        junk = [int(rng.integers(0, 1 << 62)) << (2 * k) & (2**64 - 1) if k < 32 else 0 for _ in range(nq)]  # the same query under other high bits
+        queries = np.array([(distinct[j] & ((1 << (2 * k)) - 1)) | x for j, x in zip(which, junk)], dtype=np.uint64)
+        taus = np.array([_draw_tau(rng, k) for _ in range(nq)], dtype=np.uint32)
+        want_err, dists = expect_error(ctx, lambda: [oracle.kmer_hdist_scan(s, k, q) for q in distinct])
+        want = np.array([int((dists[j] <= int(t)).sum()) for j, t in zip(which, taus)], dtype=np.uint64) if dists is not None else None
+        for packed in (False, True):
+            if packed and bad:
+                continue
+            dq = Arena(8 * nq, 8 * int(rng.integers(0, 8)), queries)
+            dt = Arena(4 * nq, 4 * int(rng.integers(0, 16)), taus)
+            cnt = Arena(8 * nq, 8 * int(rng.integers(0, 8)))
+            if packed:
+                words = _packed_words(rng, oracle, s)
+                src = Arena(8 * words.size, 8 * int(rng.integers(0, 8)), words)
+                ctx.kmer_hdist_count_multi_packed_dev(src.ptr, words.size, n, k, dq.ptr, dt.ptr, nq, cnt.ptr)
+            else:
+                src = Arena(n, int(rng.integers(0, 64)) if case % 4 else 0, s)
+                ctx.kmer_hdist_count_multi_dev(src.ptr, n, k, dq.ptr, dt.ptr, nq, cnt.ptr)
+            got_err = sync_error(ctx)
+            tag = f"multi{'_packed' if packed else ''} case {case}: n={n} k={k} nq={nq} src+{src.off} bad={bad[:3]}"
+            c, c_ok = cnt.back()
+            if not (c_ok and dq.back()[1] and dt.back()[1] and src.back()[1]):
+                fails.append(tag + ": canary overwritten")
+            if not (np.array_equal(dq.back()[0].view(np.uint64), queries) and np.array_equal(dt.back()[0].view(np.uint32), taus)):
+                fails.append(tag + ": queries or thresholds changed")
+            if want_err is not None:
+                if got_err != (want_err[0], want_err[1], bad[0]):
+                    fails.append(tag + f": error {got_err}, oracle {want_err}")
+                if sync_error(ctx) is not None:
+                    fails.append(tag + ": the invalid byte was reported twice")
+                continue
+            if got_err is not None:
+                fails.append(tag + f": unexpected error {got_err}")
+            elif not np.array_equal(c.view(np.uint64), want):
+                i = int(np.flatnonzero(c.view(np.uint64) != want)[0])
+                fails.append(tag + f": query {i} (tau {int(taus[i])}): count {int(c.view(np.uint64)[i])}, oracle {int(want[i])}")
+    assert not fails, "\n".join(fails[:20]) + f"\n({len(fails)} failing cases)"
+
+
 def test_fuzz_packed_word_kernels(ctx, oracle):
     """hdist (bulk), base_counts, hdist_pairs / hdist_query, split_packed on random packed buffers."""
     torch = _torch()
