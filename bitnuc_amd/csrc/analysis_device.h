@@ -168,8 +168,7 @@ hdist_words_kernel(const unsigned long long *__restrict__ a, const unsigned long
     }
     for (unsigned long long i = done + (unsigned long long)blockIdx.x * kBlock + threadIdx.x; i < count;
          i += (unsigned long long)gridDim.x * kBlock) {
-        const unsigned long long x = (a[i] ^ (QUERY ? query : b[i])) & mask;
-        dist[i] = (uint8_t)__builtin_popcountll((x | (x >> 1)) & 0x5555555555555555ull);
+        dist[i] = (uint8_t)word_distance(a[i], QUERY ? query : b[i], mask);
     }
 }
 

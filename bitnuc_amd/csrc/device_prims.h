@@ -68,6 +68,30 @@ __device__ __forceinline__ void rescan_bytes(const uint8_t *seq, unsigned long l
     }
 }
 
+// ---------------------------------------------------------------------------------
+// one k-mer window as a 2-bit word: the windows no wave round covers, one per thread
+// ---------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned long long kmer_mask(unsigned k) { return k == 32 ? ~0ull : ((1ull << (2 * k)) - 1); }
+
+// the Hamming distance of two 2-bit words under kmask (hamming/scalar.rs:33-47): a base differs where either bit of its field does
+__device__ __forceinline__ uint32_t word_distance(unsigned long long w, unsigned long long query, unsigned long long kmask) {
+    const unsigned long long x = (w ^ query) & kmask;
+    return (uint32_t)__builtin_popcountll((x | (x >> 1)) & 0x5555555555555555ull);
+}
+
+// as_2bit(ref[j .. j+k]) by byte loads (packing/naive.rs:3-20); `latch`: report the window's first invalid byte
+__device__ __forceinline__ unsigned long long ascii_window_word(const uint8_t *__restrict__ ref, unsigned long long j, unsigned k, bool latch,
+                                                                unsigned long long *__restrict__ slot) {
+    unsigned long long w = 0;
+    bool flagged = false;
+    for (unsigned b = 0; b < k; ++b) {
+        const uint32_t byte = ref[j + b];
+        if (latch && !valid_base(byte) && !flagged) { latch_bad(slot, j + b, byte); flagged = true; }
+        w |= (unsigned long long)code_of(byte) << (2 * b);
+    }
+    return w;
+}
+
 // threadIdx.x >> 6 is the same in all lanes of a wave; reading it through readfirstlane tells the
 // compiler, so everything derived from it (tile index, tile base address, record loads) is
 // computed once on the scalar unit instead of per lane in 64-bit VALU arithmetic.

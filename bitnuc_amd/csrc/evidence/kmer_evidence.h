@@ -82,7 +82,7 @@ kmer_scan3_kernel(const uint8_t *__restrict__ ref, unsigned long long n, unsigne
     }
 
     // tail: one window per thread, byte loads
-    const unsigned long long kmask = k == 32 ? ~0ull : ((1ull << (2 * k)) - 1);
+    const unsigned long long kmask = kmer_mask(k);
     const unsigned long long gt = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
     const unsigned long long nthreads = (unsigned long long)gridDim.x * blockDim.x;
     for (unsigned long long i = (rounds << 10) + gt; i < nwin; i += nthreads) {
@@ -93,8 +93,7 @@ kmer_scan3_kernel(const uint8_t *__restrict__ ref, unsigned long long n, unsigne
             if (!valid_base(byte) && !flagged) { latch_bad(slot, i + b, byte); flagged = true; }
             w |= (unsigned long long)code_of(byte) << (2 * b);
         }
-        const unsigned long long x = (w ^ query) & kmask;
-        dist[i] = (uint8_t)__builtin_popcountll((x | (x >> 1)) & 0x5555555555555555ull);
+        dist[i] = (uint8_t)word_distance(w, query, kmask);
     }
 }
 

@@ -134,7 +134,7 @@ kmer_scan_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, uns
                     const u32x4 x = cur.v[u][0];
                     uint32_t bad = 0;
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) bad |= x[i] ^ __builtin_amdgcn_perm(0x47FFFF54u, 0x43FF41FFu, x[i] & 0x07070707u);
+                    for (int i = 0; i < 4; ++i) bad |= dword_residue(x[i]);
                     badr[u] = bad;
                     const i32x8 e0 = onehot8(x.x, x.y), e1 = onehot8(x.z, x.w);
                     *reinterpret_cast<u32x4 *>(strip + 1024 * u + 16 * lane) = u32x4{(uint32_t)e0[0], (uint32_t)e0[1], (uint32_t)e0[2], (uint32_t)e0[3]};
@@ -193,7 +193,7 @@ kmer_scan_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, uns
                 const u32x4 x = cur.v[u][0];
                 uint32_t bad = 0;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) bad |= x[i] ^ __builtin_amdgcn_perm(0x47FFFF54u, 0x43FF41FFu, x[i] & 0x07070707u);
+                for (int i = 0; i < 4; ++i) bad |= dword_residue(x[i]);
                 if constexpr (LEAN) trip_bad |= bad;
                 else if (__builtin_expect(trip_invalid(bad) && (unsigned)u < m, 0)) rescan_bytes(ref, ((r0 + u) << 10) + 16 * lane, 16, slot);
                 const i32x8 e0 = onehot8(x.x, x.y), e1 = onehot8(x.z, x.w);
@@ -267,20 +267,19 @@ kmer_scan_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, uns
     }
 
     // tail: one window per thread, byte loads
-    const unsigned long long kmask = k == 32 ? ~0ull : ((1ull << (2 * k)) - 1);
+    const unsigned long long kmask = kmer_mask(k);
     const unsigned long long gt = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
     const unsigned long long nthreads = (unsigned long long)gridDim.x * blockDim.x;
     uint32_t tail_hits = 0;
     for (unsigned long long i = (rounds << 10) + gt; i < nwin; i += nthreads) {
-        unsigned long long w = 0;
+        unsigned long long w = 0; // (scan_tail_windows' note: the byte loop stays written out)
         bool flagged = false;
         for (unsigned b = 0; b < k; ++b) {
             const uint32_t byte = ref[i + b];
             if (!valid_base(byte) && !flagged) { latch_bad(slot, i + b, byte); flagged = true; }
             w |= (unsigned long long)code_of(byte) << (2 * b);
         }
-        const unsigned long long x = (w ^ query) & kmask;
-        const uint32_t d = (uint32_t)__builtin_popcountll((x | (x >> 1)) & 0x5555555555555555ull);
+        const uint32_t d = word_distance(w, query, kmask);
         if constexpr (COUNT) tail_hits += d <= tau ? 1u : 0u;
         else dist[i] = (uint8_t)d;
     }
@@ -321,25 +320,19 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 
 kmer_count_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, unsigned k, unsigned long long query, unsigned tau,
                        unsigned long long *__restrict__ result, unsigned long long *__restrict__ total /* zero between launches */,
                        unsigned *__restrict__ ticket, unsigned long long *__restrict__ slot, const CountMfmaTable tab) {
-    // one (half, parity) region: 32 U entries + the halo's, padded so that the odd-parity region starts 16 banks (64 B mod 128) after the even one: a
-    // ds_write_b128 serves 8 consecutive lanes at a time = 4 even groups (64 B of region 0) + 4 odd ones (64 B of region 1), which must not share a bank
-    // (round 5's first padding, + 64 B, put them 20 banks apart: SQ_LDS_BANK_CONFLICT = 30 % of the LDS cycles, profiles/r05_pmc_scan_mfma_shipped_forms.txt)
-    constexpr int kRegion = (32 * U + 1) * 16 + 48;
-    static_assert(kRegion % 128 == 64, "the two parities of one store must land 16 banks apart");
-    __shared__ __attribute__((aligned(16))) uint8_t strips[kBlock / 64][4 * kRegion];
+    __shared__ __attribute__((aligned(16))) uint8_t strips[kBlock / 64][AsciiStrip4<U>::kBytes];
     const unsigned long long nwin = n - k + 1;
     const unsigned long long rounds = scan_rounds(n);
     const unsigned lane = threadIdx.x & 63;
     const unsigned long long wave = (unsigned long long)blockIdx.x * (blockDim.x >> 6) + wave_in_block();
     const unsigned long long nwaves = ((unsigned long long)gridDim.x * blockDim.x) >> 6;
-    uint8_t *strip = strips[wave_in_block()];
+    const AsciiStrip4<U> fe(strips[wave_in_block()], lane);
 
     ScanTrip<U> cur;
     unsigned long long r0 = wave * U;
     if (r0 < rounds) scan_trip_load<U, 3, NTLD>(ref, r0, rounds, lane, cur);
-    const unsigned m32 = lane & 31u, hh = lane >> 5;
     i32x8 A[4];
-    query_operand<4>(tab.w[m32 + 8u - 8u * hh], A);
+    query_operand<4>(tab.w[fe.row], A);
     if constexpr (EMIT != 0) { // the pin (query_operand's note; round 5's first form had none)
         asm volatile("" : "+v"(A[0][0]), "+v"(A[0][1]), "+v"(A[0][2]), "+v"(A[0][3]), "+v"(A[1][0]), "+v"(A[1][1]), "+v"(A[1][2]), "+v"(A[1][3]),
                           "+v"(A[2][0]), "+v"(A[2][1]), "+v"(A[2][2]), "+v"(A[2][3]), "+v"(A[3][0]), "+v"(A[3][1]), "+v"(A[3][2]), "+v"(A[3][3]));
@@ -347,14 +340,11 @@ kmer_count_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, un
     const float tauf = (float)tau;
     uint32_t hits = 0;      // EMIT 0: wave-uniform
     uint32_t lane_hits = 0; // EMIT 1, 2: per lane
-    const int scale_a = EMIT == 0 ? 127 : count_row_scale(m32);
+    const int scale_a = EMIT == 0 ? 127 : count_row_scale(fe.m32);
     f32x16 c0;
 #pragma unroll
     for (int i = 0; i < 16; ++i) c0[i] = EMIT == 0 ? 0.f : tab.c[i & 3]; // scan_mfma_host.h: count_mfma_table
     if constexpr (EMIT != 0) asm volatile("" : "+v"(c0)); // (acc_start's note)
-    // where group g of the trip lives: region (half e, parity g & 1), entry g >> 1
-    const unsigned wr0 = (lane & 1u) * kRegion + 16u * (lane >> 1);                 // the lane's own group l of round u: + 2 kRegion e + 512 u
-    const unsigned rd = hh * 2u * kRegion + 16u * m32;                              // lane (n, h), K-step j of round u: + (j & 1) kRegion + 16 (32 u + (j >> 1))
 
     while (r0 < rounds) {
         const unsigned m = rounds - r0 < (unsigned long long)U ? (unsigned)(rounds - r0) : (unsigned)U;
@@ -362,27 +352,21 @@ kmer_count_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, un
         const unsigned long long rn = r0 + nwaves * U;
         if constexpr (EMIT != 2) { if (rn < rounds) scan_trip_load<U, 3, NTLD>(ref, rn, rounds, lane, nxt); }
         wave_lds_fence(); // the previous trip's readers are done
-        uint32_t trip_bad = 0;
+        uint32_t trip_bad = 0; // AsciiStrip4's fill in its parts: EMIT 0 tests the residue round by round
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const u32x4 x = cur.v[u][0];
             uint32_t bad = 0;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) bad |= x[i] ^ __builtin_amdgcn_perm(0x47FFFF54u, 0x43FF41FFu, x[i] & 0x07070707u);
+            for (int i = 0; i < 4; ++i) bad |= dword_residue(x[i]);
             if constexpr (EMIT == 0) {
                 if (__builtin_expect(trip_invalid(bad) && (unsigned)u < m, 0)) rescan_bytes(ref, ((r0 + u) << 10) + 16 * lane, 16, slot);
             } else {
                 trip_bad |= bad; // (a clamped copy repeats a round of this trip: nothing it could add)
             }
-            const i32x8 e0 = onehot8(x.x, x.y), e1 = onehot8(x.z, x.w);
-            *reinterpret_cast<u32x4 *>(strip + wr0 + 512 * u) = u32x4{(uint32_t)e0[0], (uint32_t)e0[1], (uint32_t)e0[2], (uint32_t)e0[3]};
-            *reinterpret_cast<u32x4 *>(strip + wr0 + 512 * u + 2 * kRegion) = u32x4{(uint32_t)e1[0], (uint32_t)e1[1], (uint32_t)e1[2], (uint32_t)e1[3]};
+            fe.put_round(u, x);
         }
-        if (lane < 2) { // the halo: groups 64 m and 64 m + 1 (after the last VALID round; in-order LDS: the later write wins over a clamped copy)
-            const i32x8 e0 = onehot8(cur.hv.x, cur.hv.y), e1 = onehot8(cur.hv.z, cur.hv.w);
-            *reinterpret_cast<u32x4 *>(strip + lane * kRegion + 512 * m) = u32x4{(uint32_t)e0[0], (uint32_t)e0[1], (uint32_t)e0[2], (uint32_t)e0[3]};
-            *reinterpret_cast<u32x4 *>(strip + lane * kRegion + 512 * m + 2 * kRegion) = u32x4{(uint32_t)e1[0], (uint32_t)e1[1], (uint32_t)e1[2], (uint32_t)e1[3]};
-        }
+        fe.put_halo(lane, m, cur.hv);
         if constexpr (EMIT != 0) {
             if (__builtin_expect(trip_invalid(trip_bad), 0)) { // some lane of the trip holds an invalid byte: find the round
 #pragma unroll 1
@@ -395,11 +379,7 @@ kmer_count_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, un
         for (int u = 0; u < U; ++u) {
             if ((unsigned)u >= m) break; // wave-uniform
             i32x8 B[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const u32x4 t = *reinterpret_cast<const u32x4 *>(strip + rd + (j & 1) * kRegion + 16 * (32 * u + (j >> 1)));
-                B[j] = i32x8{(int)t.x, (int)t.y, (int)t.z, (int)t.w, 0, 0, 0, 0};
-            }
+            fe.read_b(u, B);
             f32x16 acc = c0;
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A[j], B[j], acc, 4, 4, 0, scale_a, 0, 127);
@@ -416,20 +396,19 @@ kmer_count_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, un
     }
 
     // tail: one window per thread, byte loads
-    const unsigned long long kmask = k == 32 ? ~0ull : ((1ull << (2 * k)) - 1);
+    const unsigned long long kmask = kmer_mask(k);
     const unsigned long long gt = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
     const unsigned long long nthreads = (unsigned long long)gridDim.x * blockDim.x;
     uint32_t tail_hits = 0;
     for (unsigned long long i = (rounds << 10) + gt; i < nwin; i += nthreads) {
-        unsigned long long w = 0;
+        unsigned long long w = 0; // (scan_tail_windows' note: the byte loop stays written out)
         bool flagged = false;
         for (unsigned b = 0; b < k; ++b) {
             const uint32_t byte = ref[i + b];
             if (!valid_base(byte) && !flagged) { latch_bad(slot, i + b, byte); flagged = true; }
             w |= (unsigned long long)code_of(byte) << (2 * b);
         }
-        const unsigned long long x = (w ^ query) & kmask;
-        tail_hits += (uint32_t)__builtin_popcountll((x | (x >> 1)) & 0x5555555555555555ull) <= tau ? 1u : 0u;
+        tail_hits += word_distance(w, query, kmask) <= tau ? 1u : 0u;
     }
     tail_hits += lane_hits;
 #pragma unroll
@@ -454,47 +433,22 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 
 kmer_scan_seg3_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, unsigned k, unsigned long long query, uint8_t *__restrict__ dist,
                            unsigned long long *__restrict__ slot, const Count3MfmaTable tab) {
     constexpr bool NTLD = (POLICY & 1) != 0, NTST = (POLICY & 2) != 0;
-    constexpr int kAc = (32 * U + 1) * 16 + 48;
-    static_assert(kAc % 128 == 64, "the two parities of one store must land 16 banks apart");
-    constexpr int kG = (32 * U + 1) * 16;
-    __shared__ __attribute__((aligned(16))) uint8_t strips[kBlock / 64][2 * kAc + kG];
+    __shared__ __attribute__((aligned(16))) uint8_t strips[kBlock / 64][AsciiStrip3<U>::kBytes];
     const unsigned long long nwin = n - k + 1;
     const unsigned long long rounds = scan_rounds(n);
     const unsigned lane = threadIdx.x & 63;
     const unsigned long long wave = (unsigned long long)blockIdx.x * (blockDim.x >> 6) + wave_in_block();
-    uint8_t *strip = strips[wave_in_block()];
+    const AsciiStrip3<U> fe(strips[wave_in_block()], lane);
     const unsigned long long r0 = wave * U;
     if (r0 < rounds) {
         ScanTrip<U> cur;
         scan_trip_load<U, 3, NTLD>(ref, r0, rounds, lane, cur);
-        const unsigned m = rounds - r0 < (unsigned long long)U ? (unsigned)(rounds - r0) : (unsigned)U;
-        const unsigned m32 = lane & 31u, hh = lane >> 5;
+        const unsigned m = trip_rounds(r0, rounds, U);
         i32x8 A[3];
         query_operand<3>(tab.w[lane], A);
-        const int scale_a = dist_row_scale(m32);
+        const int scale_a = dist_row_scale(fe.m32);
         const f32x16 c0 = acc_start(tab.c);
-        const unsigned wr_ac = (lane & 1u) * kAc + 16u * (lane >> 1), wr_g = 2u * kAc + 8u * lane;
-        const unsigned rd_ac = hh * kAc + 16u * m32, rd_g = 2u * kAc + 16u * (m32 + hh);
-        uint32_t trip_bad = 0;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const u32x4 x = cur.v[u][0];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) trip_bad |= x[i] ^ __builtin_amdgcn_perm(0x47FFFF54u, 0x43FF41FFu, x[i] & 0x07070707u);
-            u32x4 ac;
-            uint32_t g0, g1;
-            expand3(x, ac, g0, g1);
-            *reinterpret_cast<u32x4 *>(strip + wr_ac + 512 * u) = ac;
-            *reinterpret_cast<u32x2 *>(strip + wr_g + 512 * u) = u32x2{g0, g1};
-        }
-        if (lane < 2) {
-            u32x4 ac;
-            uint32_t g0, g1;
-            expand3(cur.hv, ac, g0, g1);
-            *reinterpret_cast<u32x4 *>(strip + lane * kAc + 512 * m) = ac;
-            *reinterpret_cast<u32x2 *>(strip + 2 * kAc + 512 * m + 8 * lane) = u32x2{g0, g1};
-        }
-        if (__builtin_expect(trip_invalid(trip_bad), 0)) {
+        if (__builtin_expect(trip_invalid(fe.fill(lane, m, cur)), 0)) {
 #pragma unroll 1
             for (unsigned u = 0; u < m; ++u) rescan_bytes(ref, ((r0 + u) << 10) + 16 * lane, 16, slot);
         }
@@ -503,14 +457,10 @@ kmer_scan_seg3_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n
         for (int u = 0; u < U; ++u) {
             if ((unsigned)u >= m) break; // wave-uniform
             i32x8 B[3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const u32x4 t = *reinterpret_cast<const u32x4 *>(strip + (j < 2 ? rd_ac + 16 * j : rd_g) + 512 * u);
-                B[j] = i32x8{(int)t.x, (int)t.y, (int)t.z, (int)t.w, 0, 0, 0, 0};
-            }
+            fe.read_b(u, B);
             uint32_t o[4];
             pack_distances(mfma_chain(A, B, c0, scale_a), o);
-            store_distances<NTST, true>(dist + ((r0 + u) << 10) + 16u * (2u * m32 + hh), o);
+            store_distances<NTST, true>(dist + ((r0 + u) << 10) + 16u * (2u * fe.m32 + fe.hh), o);
         }
     }
     scan_tail_windows<false>(ref, rounds << 10, nwin, k, query, 0u, dist, slot);

@@ -116,13 +116,25 @@ hipError_t batch_legs(bitnuc_ctx *c, const uint8_t *kmers, size_t k, size_t stri
     return hipGetLastError();
 }
 
-// ---- the scan and its fused count: the shipped tilings, at the trip length / workgroup size / grid the caller picks
-// the segment tiling (four channels per base); the accumulators start at the 2^23 pack bias
-template <int U, int BLOCK>
-hipError_t scan_seg_t(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, uint64_t query, uint8_t *dist, unsigned long long *slot) {
+// ---- the windows the matrix-core rounds leave to single threads in front of them (`skip`; the kernels' tails take those behind the last whole round)
+// ASCII input at any alignment: the rounds start at the first 16-byte aligned base
+inline unsigned ascii_skip(const uint8_t *ref) { return (unsigned)((16 - (reinterpret_cast<uintptr_t>(ref) & 15)) & 15); }
+// packed words, 8-byte aligned (checked by the callers): words at 8 mod 16 start the rounds one word later
+inline unsigned packed_skip(const uint64_t *words) { return aligned16(words) ? 0u : 32u; }
+
+// the four-channel table of the distance bytes (the scan, the hit lists): no threshold, the accumulators start at the 2^23 pack bias
+inline CountMfmaTable scan_seg_table(uint64_t query, size_t k) {
     CountMfmaTable ct;
     count_mfma_table(query, k, &ct);
     for (int j = 0; j < 4; ++j) ct.c[j] = kPackBias;
+    return ct;
+}
+
+// ---- the scan and its fused count: the shipped tilings, at the trip length / workgroup size / grid the caller picks
+// the segment tiling (four channels per base)
+template <int U, int BLOCK>
+hipError_t scan_seg_t(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, uint64_t query, uint8_t *dist, unsigned long long *slot) {
+    const CountMfmaTable ct = scan_seg_table(query, k);
     kmer_scan_seg_mfma_kernel<3, U, BLOCK><<<(unsigned)(scan_rounds(n) / ((BLOCK / 64) * U) + 1), BLOCK, 0, c->stream>>>(ref, n, (unsigned)k, query, dist, slot, ct);
     return hipGetLastError();
 }
@@ -201,12 +213,12 @@ hipError_t launch_count(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, u
     return count_scan2_t<false, false, 1, 0>(c, ref, n, k, query, tau, res, slot);
 }
 
-// ---- the scan and its fused count on packed words (scan_packed_device.h).  d_words is 8-byte aligned (checked by the callers); at 8 mod 16 the rounds
-// start one word later and the tail threads take the first 32 windows (skip = 32), so both alignments run the same kernel.
+// ---- the scan and its fused count on packed words (scan_packed_device.h).  The tail threads take the first packed_skip windows, so both alignments
+// run the same kernel.
 hipError_t launch_scan_packed(bitnuc_ctx *c, const uint64_t *words, size_t n, size_t k, uint64_t query, uint8_t *dist) {
     PackedScanTable t;
     scan_packed_table(query, k, &t);
-    const unsigned skip = aligned16(words) ? 0u : 32u;
+    const unsigned skip = packed_skip(words);
     packed_scan_mfma_kernel<<<(unsigned)(scan_rounds(n, skip) / 4 + 1), kPackedBlockScan, 0, c->stream>>>(words, n, skip, (unsigned)k, query, dist, t);
     return hipGetLastError();
 }
@@ -215,7 +227,7 @@ hipError_t launch_scan_packed(bitnuc_ctx *c, const uint64_t *words, size_t n, si
 hipError_t launch_count_packed(bitnuc_ctx *c, const uint64_t *words, size_t n, size_t k, uint64_t query, unsigned tau, unsigned long long *res) {
     Count3MfmaTable t;
     count3_packed_table(query, k, tau, &t);
-    const unsigned skip = aligned16(words) ? 0u : 32u;
+    const unsigned skip = packed_skip(words);
     packed_count3_mfma_kernel<<<bounded_grid(c, scan_rounds(n, skip), (kBlock / 64) * 4, kCountGrid), kBlock, 0, c->stream>>>(words, n, skip, (unsigned)k, query, tau, res, c->d_acc + 6, c->d_tickets + 3, t);
     return hipGetLastError();
 }
@@ -250,16 +262,14 @@ hipError_t hits_scan(bitnuc_ctx *c, unsigned *counts, unsigned long long ntr, un
     return hipGetLastError();
 }
 
-// d_ref at any alignment: the rounds start at the first 16-byte aligned base, the windows before it are the tail workgroup's
+// d_ref at any alignment (ascii_skip): the windows before the rounds are the first workgroup's
 int launch_hits(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const HitsArgs &a, unsigned long long *slot, bitnuc_err *err) {
-    const unsigned skip = (unsigned)((16 - (reinterpret_cast<uintptr_t>(ref) & 15)) & 15);
+    const unsigned skip = ascii_skip(ref);
     const unsigned long long ntr = hits_trips(n, skip) + 2;
     unsigned *counts;
     unsigned long long *tiles;
     if (int st = hits_scratch(c, ntr, &counts, &tiles, err)) return st;
-    CountMfmaTable ct;
-    count_mfma_table(a.query, k, &ct);
-    for (int j = 0; j < 4; ++j) ct.c[j] = kPackBias;
+    const CountMfmaTable ct = scan_seg_table(a.query, k);
     kmer_hits_mfma_kernel<false><<<(unsigned)ntr, 64, 0, c->stream>>>(ref, n, skip, (unsigned)k, a.query, a.tau, counts, nullptr, nullptr, nullptr, 0, 0, slot, ct);
     HIPCHK(hits_scan(c, counts, ntr, tiles, a.n_hits));
     if (a.cap) kmer_hits_mfma_kernel<true><<<(unsigned)ntr, 64, 0, c->stream>>>(ref, n, skip, (unsigned)k, a.query, a.tau, counts, tiles, a.pos, a.hd, a.cap, a.pos_base, slot, ct);
@@ -267,9 +277,9 @@ int launch_hits(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const Hit
     return BITNUC_OK;
 }
 
-// d_words 8-byte aligned (checked by the callers): at 8 mod 16 the rounds start one word later, as the packed scan's
+// d_words 8-byte aligned (packed_skip)
 int launch_hits_packed(bitnuc_ctx *c, const uint64_t *words, size_t n, size_t k, const HitsArgs &a, bitnuc_err *err) {
-    const unsigned skip = aligned16(words) ? 0u : 32u;
+    const unsigned skip = packed_skip(words);
     const unsigned long long ntr = hits_trips(n, skip) + 2;
     unsigned *counts;
     unsigned long long *tiles;
@@ -344,9 +354,9 @@ int multi_setup(bitnuc_ctx *c, size_t k, const MultiArgs &a, unsigned long long 
     return BITNUC_OK;
 }
 
-// d_ref at any alignment: the rounds start at its first 16-byte aligned base (the hit lists' rule)
+// d_ref at any alignment (ascii_skip)
 int launch_count_multi(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const MultiArgs &a, unsigned long long *slot, bitnuc_err *err) {
-    const unsigned skip = (unsigned)((16 - (reinterpret_cast<uintptr_t>(ref) & 15)) & 15);
+    const unsigned skip = ascii_skip(ref);
     const Count3MfmaTable *tabs;
     dim3 grid;
     if (int st = multi_setup<false>(c, k, a, scan_rounds(n, skip), &tabs, &grid, err)) return st;
@@ -356,9 +366,9 @@ int launch_count_multi(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, co
     return BITNUC_OK;
 }
 
-// d_words 8-byte aligned (checked by the callers): at 8 mod 16 the rounds start one word later, as the packed count's
+// d_words 8-byte aligned (packed_skip)
 int launch_count_multi_packed(bitnuc_ctx *c, const uint64_t *words, size_t n, size_t k, const MultiArgs &a, bitnuc_err *err) {
-    const unsigned skip = aligned16(words) ? 0u : 32u;
+    const unsigned skip = packed_skip(words);
     const Count3MfmaTable *tabs;
     dim3 grid;
     if (int st = multi_setup<true>(c, k, a, scan_rounds(n, skip), &tabs, &grid, err)) return st;

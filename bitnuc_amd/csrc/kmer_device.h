@@ -126,7 +126,7 @@ kmer_dense_kernel(const uint8_t *__restrict__ kmers, unsigned k, unsigned long l
     const unsigned long long nwaves = ((unsigned long long)gridDim.x * blockDim.x) >> 6;
     const unsigned ngroups = 4 * k; // 16-byte groups per 64 k-mers
     const unsigned bit = 2 * k * lane, d = bit >> 5, sh = bit & 31;
-    const unsigned long long kmask = k == 32 ? ~0ull : ((1ull << (2 * k)) - 1);
+    const unsigned long long kmask = kmer_mask(k);
     const u32x4 pad = {0x41414141u, 0x41414141u, 0x41414141u, 0x41414141u};
     const bool a0 = lane < ngroups, a1 = lane + 64 < ngroups;
 
@@ -291,7 +291,7 @@ kmer_scan_kernel(const uint8_t *__restrict__ ref, unsigned long long n, unsigned
     }
 
     // tail: one window per thread, byte loads
-    const unsigned long long kmask = k == 32 ? ~0ull : ((1ull << (2 * k)) - 1);
+    const unsigned long long kmask = kmer_mask(k);
     const unsigned long long gt = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
     const unsigned long long nthreads = (unsigned long long)gridDim.x * blockDim.x;
     for (unsigned long long i = rounds * kScanWaveWindows + gt; i < nwin; i += nthreads) {
@@ -302,8 +302,7 @@ kmer_scan_kernel(const uint8_t *__restrict__ ref, unsigned long long n, unsigned
             if (!valid_base(byte) && !flagged) { latch_bad(slot, i + b, byte); flagged = true; }
             w |= (unsigned long long)code_of(byte) << (2 * b);
         }
-        const unsigned long long x = (w ^ query) & kmask;
-        dist[i] = (uint8_t)__builtin_popcountll((x | (x >> 1)) & 0x5555555555555555ull);
+        dist[i] = (uint8_t)word_distance(w, query, kmask);
     }
 }
 
@@ -415,7 +414,7 @@ kmer_scan2_kernel(const uint8_t *__restrict__ ref, unsigned long long n, unsigne
     }
 
     // tail: one window per thread, byte loads
-    const unsigned long long kmask = k == 32 ? ~0ull : ((1ull << (2 * k)) - 1);
+    const unsigned long long kmask = kmer_mask(k);
     const unsigned long long gt = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
     const unsigned long long nthreads = (unsigned long long)gridDim.x * blockDim.x;
     for (unsigned long long i = (rounds << 10) + gt; i < nwin; i += nthreads) {
@@ -426,8 +425,7 @@ kmer_scan2_kernel(const uint8_t *__restrict__ ref, unsigned long long n, unsigne
             if (!valid_base(byte) && !flagged) { latch_bad(slot, i + b, byte); flagged = true; }
             w |= (unsigned long long)code_of(byte) << (2 * b);
         }
-        const unsigned long long x = (w ^ query) & kmask;
-        const uint32_t d = (uint32_t)__builtin_popcountll((x | (x >> 1)) & 0x5555555555555555ull);
+        const uint32_t d = word_distance(w, query, kmask);
         if constexpr (COUNT) hits += d <= tau ? 1u : 0u;
         else dist[i] = (uint8_t)d;
     }
@@ -709,13 +707,11 @@ hdist_kernel(const unsigned long long *__restrict__ a, const unsigned long long 
         done = pairs << 1;
     }
     for (unsigned long long w = done + gt; w < full; w += nthreads) {
-        const unsigned long long x = a[w] ^ b[w];
-        acc += (uint32_t)__builtin_popcountll((x | (x >> 1)) & 0x5555555555555555ull);
+        acc += word_distance(a[w], b[w], ~0ull);
     }
     if (rem && blockIdx.x == 0 && threadIdx.x == 0) { // scalar.rs:26-33: bits above 2*rem are ignored
         const unsigned long long mask = (1ull << (2 * rem)) - 1;
-        const unsigned long long x = (a[full] ^ b[full]) & mask;
-        acc += (uint32_t)__builtin_popcountll((x | (x >> 1)) & 0x5555555555555555ull);
+        acc += word_distance(a[full], b[full], mask);
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);

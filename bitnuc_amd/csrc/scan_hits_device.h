@@ -16,8 +16,8 @@
 // The passes compute the same distances from the same bytes with the same instructions: the emit pass writes exactly the hits the count pass counted.
 #pragma once
 #include "device_prims.h"
-#include "scan_mfma_device.h"   // the back end: query_operand, acc_start, mfma_chain, pack_distances, distances_in_order; onehot8, ScanTrip
-#include "scan_packed_device.h" // the packed front end: expand4_packed, kPackedRegion
+#include "scan_mfma_device.h"   // the back end: query_operand, acc_start, mfma_chain, pack_distances, distances_in_order; the front end: AsciiStrip4
+#include "scan_packed_device.h" // the packed front end: PackedStrip4
 #include "scan_mfma_host.h"
 
 namespace bitnuc_dev {
@@ -133,7 +133,7 @@ __device__ __forceinline__ void write_hit_count(uint32_t hits, unsigned lane, un
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // ASCII input.  The rounds start at ref + skip, 16-byte aligned (skip = (-ref) mod 16; the first skip windows are the first workgroup's), so any ref runs these
-// kernels.  Front end and strip layout: kmer_scan_seg_mfma_kernel's (U = 4).  Invalid bytes are latched by the count pass only: trip_invalid over the
+// kernels.  Front end: AsciiStrip4 (U = 4), as the scan.  Invalid bytes are latched by the count pass only: trip_invalid over the
 // trip's rounds, byte loads in the tail (scan_tail_windows' rule), so the slot holds the first invalid byte of the whole sequence, as the count's.
 // EMIT: counts[] holds the exclusive offsets within a tile, tile_off[] the tiles' (hits_scan_*).
 template <bool EMIT>
@@ -143,13 +143,12 @@ kmer_hits_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, uns
                       uint8_t *__restrict__ hd, unsigned long long cap, unsigned long long pos_base, unsigned long long *__restrict__ slot,
                       const CountMfmaTable tab) {
     constexpr int U = kHitsRounds;
-    constexpr int kRegion = (32 * U + 1) * 16 + 48;
-    static_assert(kRegion % 128 == 64, "the two parities of one store must land 16 banks apart");
-    __shared__ __attribute__((aligned(16))) uint8_t strip[4 * kRegion];
+    __shared__ __attribute__((aligned(16))) uint8_t strip[AsciiStrip4<U>::kBytes];
     const unsigned long long nwin = n - k + 1;
     const unsigned long long rounds = scan_rounds(n, skip);
     const unsigned long long blk = blockIdx.x, trip = blk - 1;
     const unsigned lane = threadIdx.x & 63;
+    const AsciiStrip4<U> fe(strip, lane);
     const uint32_t bias = hits_bias(tau);
     unsigned long long rank = 0;
     if constexpr (EMIT) rank = tile_off[blk / kHitsTile] + counts[blk];
@@ -159,29 +158,12 @@ kmer_hits_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, uns
         const unsigned long long r0 = trip * U;
         ScanTrip<U> cur;
         scan_trip_load<U, 3, true>(base, r0, rounds, lane, cur);
-        const unsigned m = rounds - r0 < (unsigned long long)U ? (unsigned)(rounds - r0) : (unsigned)U;
-        const unsigned m32 = lane & 31u, hh = lane >> 5;
+        const unsigned m = trip_rounds(r0, rounds, U);
         i32x8 A[4];
-        query_operand<4>(tab.w[m32 + 8u - 8u * hh], A);
-        const int scale_a = dist_row_scale(m32);
+        query_operand<4>(tab.w[fe.row], A);
+        const int scale_a = dist_row_scale(lane & 31u);
         const f32x16 c0 = acc_start(tab.c); // 2^23
-        const unsigned wr0 = (lane & 1u) * kRegion + 16u * (lane >> 1);
-        const unsigned rd = hh * 2u * kRegion + 16u * m32;
-        uint32_t trip_bad = 0;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const u32x4 x = cur.v[u][0];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) trip_bad |= x[i] ^ __builtin_amdgcn_perm(0x47FFFF54u, 0x43FF41FFu, x[i] & 0x07070707u); // (trip_invalid's LUT)
-            const i32x8 e0 = onehot8(x.x, x.y), e1 = onehot8(x.z, x.w);
-            *reinterpret_cast<u32x4 *>(strip + wr0 + 512 * u) = u32x4{(uint32_t)e0[0], (uint32_t)e0[1], (uint32_t)e0[2], (uint32_t)e0[3]};
-            *reinterpret_cast<u32x4 *>(strip + wr0 + 512 * u + 2 * kRegion) = u32x4{(uint32_t)e1[0], (uint32_t)e1[1], (uint32_t)e1[2], (uint32_t)e1[3]};
-        }
-        if (lane < 2) { // the halo (kmer_scan_seg_mfma_kernel's)
-            const i32x8 e0 = onehot8(cur.hv.x, cur.hv.y), e1 = onehot8(cur.hv.z, cur.hv.w);
-            *reinterpret_cast<u32x4 *>(strip + lane * kRegion + 512 * m) = u32x4{(uint32_t)e0[0], (uint32_t)e0[1], (uint32_t)e0[2], (uint32_t)e0[3]};
-            *reinterpret_cast<u32x4 *>(strip + lane * kRegion + 512 * m + 2 * kRegion) = u32x4{(uint32_t)e1[0], (uint32_t)e1[1], (uint32_t)e1[2], (uint32_t)e1[3]};
-        }
+        const uint32_t trip_bad = fe.fill(lane, m, cur);
         if (!EMIT && __builtin_expect(trip_invalid(trip_bad), 0)) {
 #pragma unroll 1
             for (unsigned u = 0; u < m; ++u) rescan_bytes(ref, skip + ((r0 + u) << 10) + 16 * lane, 16, slot);
@@ -191,46 +173,34 @@ kmer_hits_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, uns
         for (int u = 0; u < U; ++u) {
             if ((unsigned)u >= m) break; // wave-uniform
             i32x8 B[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const u32x4 t = *reinterpret_cast<const u32x4 *>(strip + rd + (j & 1) * kRegion + 16 * (32 * u + (j >> 1)));
-                B[j] = i32x8{(int)t.x, (int)t.y, (int)t.z, (int)t.w, 0, 0, 0, 0};
-            }
+            fe.read_b(u, B);
             const f32x16 acc = mfma_chain(A, B, c0, scale_a);
             if constexpr (EMIT) emit_round(acc, bias, lane, pos_base + skip + ((r0 + u) << 10), rank, cap, pos, hd);
             else hits += round_hits(acc, bias);
         }
     } else { // the first workgroup: the head windows [0, skip); the last: the tail
-        const unsigned long long kmask = k == 32 ? ~0ull : ((1ull << (2 * k)) - 1);
+        const unsigned long long kmask = kmer_mask(k);
         const unsigned long long pre = blk == 0 ? (skip < nwin ? skip : nwin) : 0, first = blk == 0 ? nwin : skip + (rounds << 10);
-        hits = hits_tail<EMIT>(pre, first, nwin, tau, lane, rank, cap, pos_base, pos, hd, [&](unsigned long long j) {
-            unsigned long long w = 0;
-            bool flagged = false;
-            for (unsigned b = 0; b < k; ++b) {
-                const uint32_t byte = ref[j + b];
-                if (!EMIT && !valid_base(byte) && !flagged) { latch_bad(slot, j + b, byte); flagged = true; }
-                w |= (unsigned long long)code_of(byte) << (2 * b);
-            }
-            const unsigned long long x = (w ^ query) & kmask;
-            return (uint32_t)__builtin_popcountll((x | (x >> 1)) & 0x5555555555555555ull);
-        });
+        hits = hits_tail<EMIT>(pre, first, nwin, tau, lane, rank, cap, pos_base, pos, hd,
+                               [&](unsigned long long j) { return word_distance(ascii_window_word(ref, j, k, !EMIT, slot), query, kmask); });
     }
     if constexpr (!EMIT) write_hit_count(hits, lane, counts);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// Packed input: packed_scan_mfma_kernel's front end (one wave load of 1 KiB = one trip, strip cut by group residue); words at 8 mod 16 start the rounds
-// one word later (skip = 32).  No byte can be invalid.
+// Packed input: packed_trip_load and PackedStrip4, as the packed scan (one wave load of 1 KiB = one trip, strip cut by group residue); words at 8 mod 16
+// start the rounds one word later (skip = 32).  No byte can be invalid.
 template <bool EMIT>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8)))
 packed_hits_mfma_kernel(const uint64_t *__restrict__ words, unsigned long long n, unsigned skip, unsigned k, unsigned long long query, unsigned tau,
                         unsigned *__restrict__ counts, const unsigned long long *__restrict__ tile_off, unsigned long long *__restrict__ pos,
                         uint8_t *__restrict__ hd, unsigned long long cap, unsigned long long pos_base, const PackedScanTable tab) {
-    __shared__ __attribute__((aligned(16))) uint8_t strip[8 * kPackedRegion];
+    __shared__ __attribute__((aligned(16))) uint8_t strip[PackedStrip4::kBytes];
     const unsigned long long nwin = n - k + 1;
     const unsigned long long rounds = scan_rounds(n, skip);
     const unsigned long long blk = blockIdx.x, trip = blk - 1;
     const unsigned lane = threadIdx.x & 63;
+    const PackedStrip4 fe(strip, lane);
     const uint32_t bias = hits_bias(tau);
     unsigned long long rank = 0;
     if constexpr (EMIT) rank = tile_off[blk / kHitsTile] + counts[blk];
@@ -238,59 +208,32 @@ packed_hits_mfma_kernel(const uint64_t *__restrict__ words, unsigned long long n
     if (blk != 0 && trip < (rounds + 3) / 4) {
         const uint8_t *base = reinterpret_cast<const uint8_t *>(words + (skip >> 5)); // 16-byte aligned
         const unsigned long long r0 = trip * 4;
-        const unsigned m = rounds - r0 < 4ull ? (unsigned)(rounds - r0) : 4u;
-        const unsigned ul = lane >> 4, uc = ul < m ? ul : m - 1; // clamp: redundant but in bounds
-        const u32x4 x = load_group<true, true>(base + ((r0 + uc) << 8) + 16u * (lane & 15u));
-        uint32_t hx = 0;
-        if (lane < 2) hx = *reinterpret_cast<const uint32_t *>(base + ((r0 + m) << 8) + 4u * lane); // the halo: groups 0 and 1 of round m
-        const unsigned m32 = lane & 31u, hh = lane >> 5;
+        const unsigned m = trip_rounds(r0, rounds, 4u);
+        PackedTrip cur;
+        packed_trip_load(base, r0, rounds, lane, cur);
         i32x8 A[4];
-        query_operand<4>(tab.w[m32 + 2u - 2u * hh], A);
-        const int scale_a = dist_row_scale(m32);
+        query_operand<4>(tab.w[fe.row], A);
+        const int scale_a = dist_row_scale(lane & 31u);
         const f32x16 c0 = acc_start(tab.c); // 2^23
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            u32x4 e0, e1;
-            expand4_packed(x[i], e0, e1);
-            *reinterpret_cast<u32x4 *>(strip + i * kPackedRegion + 16u * lane) = e0;
-            *reinterpret_cast<u32x4 *>(strip + (4 + i) * kPackedRegion + 16u * lane) = e1;
-        }
-        if (lane < 2) {
-            u32x4 e0, e1;
-            expand4_packed(hx, e0, e1);
-            *reinterpret_cast<u32x4 *>(strip + lane * kPackedRegion + 256u * m) = e0;
-            *reinterpret_cast<u32x4 *>(strip + (4 + lane) * kPackedRegion + 256u * m) = e1;
-        }
-        unsigned rd[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const unsigned g = 2u * m32 + (unsigned)j;
-            rd[j] = (4u * hh + (g & 3u)) * kPackedRegion + 16u * (g >> 2);
-        }
+        fe.fill(lane, m, cur);
+        unsigned rd[4]; // (here and not in fe: read_offsets' note)
+        fe.read_offsets(rd);
         wave_lds_fence();
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             if ((unsigned)u >= m) break; // wave-uniform
             i32x8 B[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const u32x4 t = *reinterpret_cast<const u32x4 *>(strip + rd[j] + 256u * u);
-                B[j] = i32x8{(int)t.x, (int)t.y, (int)t.z, (int)t.w, 0, 0, 0, 0};
-            }
+            for (int j = 0; j < 4; ++j) B[j] = PackedStrip4::operand(strip, rd[j], u);
             const f32x16 acc = mfma_chain(A, B, c0, scale_a);
             if constexpr (EMIT) emit_round(acc, bias, lane, pos_base + skip + ((r0 + u) << 10), rank, cap, pos, hd);
             else hits += round_hits(acc, bias);
         }
     } else { // the head windows [0, skip), the tail
-        const unsigned long long kmask = k == 32 ? ~0ull : ((1ull << (2 * k)) - 1);
+        const unsigned long long kmask = kmer_mask(k);
         const unsigned long long pre = blk == 0 ? (skip < nwin ? skip : nwin) : 0, first = blk == 0 ? nwin : skip + (rounds << 10);
-        hits = hits_tail<EMIT>(pre, first, nwin, tau, lane, rank, cap, pos_base, pos, hd, [&](unsigned long long j) {
-            const unsigned sh = 2u * (unsigned)(j & 31);
-            unsigned long long x = words[j >> 5] >> sh;
-            if ((j & 31) + k > 32) x |= words[(j >> 5) + 1] << (64 - sh); // (packed_tail_windows' funnel: in bounds since j + k - 1 < n)
-            x = (x ^ query) & kmask;
-            return (uint32_t)__builtin_popcountll((x | (x >> 1)) & 0x5555555555555555ull);
-        });
+        hits = hits_tail<EMIT>(pre, first, nwin, tau, lane, rank, cap, pos_base, pos, hd,
+                               [&](unsigned long long j) { return word_distance(packed_window_word(words, j, k), query, kmask); });
     }
     if constexpr (!EMIT) write_hit_count(hits, lane, counts);
 }

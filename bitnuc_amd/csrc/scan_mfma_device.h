@@ -27,8 +27,11 @@
 //
 // The back end -- query operand, accumulator start, row scales, MFMA chain, pack and store, hit bits -- is shared with the packed kernels
 // (scan_packed_device.h) and written once, below; each rule (the 2^23 pack bias, the threshold fields, the hit mask, the pins, the toolchain workarounds) is
-// explained at its helper.  Invalid bytes: trip_invalid, OR-ed over the trip and tested once; their one-hot is all zero, the call fails with
-// INVALID_BASE anyway.
+// explained at its helper.  The front end -- strip geometry, the fill of the strip from a loaded trip, the lane's read offsets and the read of a round's B
+// operand -- is written once per layout as well: AsciiStrip4 and AsciiStrip3 below (the trip load of both: scan_trip_load), PackedStrip4 and PackedStrip3 in
+// scan_packed_device.h; the hit lists (scan_hits_device.h), the multi-query count (scan_multi_device.h) and the evidence kernels call the same four.  A
+// kernel keeps its grid walk, when it prefetches the next trip, the pin of A and what it does with the results.  Invalid bytes: ascii_residue, OR-ed over
+// the trip and tested once (trip_invalid); their one-hot is all zero, the call fails with INVALID_BASE anyway.
 // Why four (three) matrix instructions and not the six of the tiling that shipped first: the matrix pipe's POWER is what makes a queue that starts on an idle chip
 // dip (profiles/r05_ablate_count_parts.txt); with four the scan runs at the HBM plateau from its first launch (profiles/r05_ab_scan_seg.txt).
 #pragma once
@@ -182,31 +185,50 @@ __device__ __forceinline__ uint32_t hit_bits(const f32x16 &acc, int q) {
 template <bool COUNT>
 __device__ __forceinline__ uint32_t scan_tail_windows(const uint8_t *__restrict__ ref, unsigned long long first, unsigned long long nwin, unsigned k, unsigned long long query, unsigned tau,
                                                      uint8_t *__restrict__ dist, unsigned long long *__restrict__ slot) {
-    const unsigned long long kmask = k == 32 ? ~0ull : ((1ull << (2 * k)) - 1);
+    const unsigned long long kmask = kmer_mask(k);
     const unsigned long long gt = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
     const unsigned long long nthreads = (unsigned long long)gridDim.x * blockDim.x;
     uint32_t hits = 0;
     for (unsigned long long i = first + gt; i < nwin; i += nthreads) {
-        unsigned long long w = 0;
+        unsigned long long w = 0; // (ascii_window_word's loop, written out: called here, it costs kmer_count3_mfma_kernel an instruction)
         bool flagged = false;
         for (unsigned b = 0; b < k; ++b) {
             const uint32_t byte = ref[i + b];
             if (!valid_base(byte) && !flagged) { latch_bad(slot, i + b, byte); flagged = true; }
             w |= (unsigned long long)code_of(byte) << (2 * b);
         }
-        const unsigned long long x = (w ^ query) & kmask;
-        const uint32_t d = (uint32_t)__builtin_popcountll((x | (x >> 1)) & 0x5555555555555555ull);
+        const uint32_t d = word_distance(w, query, kmask);
         if constexpr (COUNT) hits += d <= tau ? 1u : 0u;
         else dist[i] = (uint8_t)d;
     }
     return hits;
 }
 
-// The validity of 16 ASCII bytes while they are in registers (the kernels OR, per dword x, x ^ perm(0x47FFFF54, 0x43FF41FF, x & 0x07070707) into `bad`):
-// a second v_perm LUT on the one-hot's index holds the upper-case byte that index stands for (0xFF for the four indices no base has: their low bits never
-// match), so x ^ t is 0 or the case bit for a valid byte.  OR-ed over a trip (a clamped copy repeats a round of the trip: nothing it could add) and tested
-// once here; the call site finds the byte (rescan_bytes).
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The front end of the ASCII kernels.  A trip is U rounds of 1 KiB + the 32-byte halo after them: lane l of round u holds the 16-byte group 64 u + l
+// (scan_trip_load, SHIFT 3), lanes 0 and 1 the halo's two groups.  Each group is expanded once and written to the wave-private strip; the valid rounds of a
+// trip (trip_rounds: fewer than U at the end of the input) are read back as B operands.  A round past the last valid one is a clamped copy of that one
+// (redundant but in bounds); the halo is written after the rounds, and LDS operations of one wave complete in order, so where the halo lands on a clamped
+// copy's entry the later write wins.
+__device__ __forceinline__ unsigned trip_rounds(unsigned long long r0, unsigned long long rounds, unsigned U) {
+    return rounds - r0 < (unsigned long long)U ? (unsigned)(rounds - r0) : U; // wave-uniform
+}
+
+// The validity of 16 ASCII bytes while they are in registers: a second v_perm LUT on the one-hot's index holds the upper-case byte that index stands for
+// (0xFF for the four indices no base has: their low bits never match), so x ^ t is 0 or the case bit for a valid byte.  OR-ed over a trip (a clamped copy
+// repeats a round of the trip: nothing it could add) and tested once (trip_invalid); the call site then finds the byte (rescan_bytes).
+__device__ __forceinline__ uint32_t dword_residue(uint32_t x) { return x ^ __builtin_amdgcn_perm(0x47FFFF54u, 0x43FF41FFu, x & 0x07070707u); }
+__device__ __forceinline__ void ascii_residue(const u32x4 &x, uint32_t &bad) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) bad |= dword_residue(x[i]);
+}
 __device__ __forceinline__ bool trip_invalid(uint32_t bad) { return (bad & 0xDFDFDFDFu) != 0u; }
+
+// one 16-byte strip entry as an fp4 operand (the upper half of the operand's registers is unused)
+__device__ __forceinline__ i32x8 strip_operand(const uint8_t *p) {
+    const u32x4 t = *reinterpret_cast<const u32x4 *>(p);
+    return i32x8{(int)t.x, (int)t.y, (int)t.z, (int)t.w, 0, 0, 0, 0};
+}
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // The segment tiling with four channels per base (the scan; evidence: kmer_count_mfma_kernel).  D[m][n] = dist(window 32 n + m); the 63 positions a segment's
@@ -214,6 +236,53 @@ __device__ __forceinline__ bool trip_invalid(uint32_t bad) { return (bad & 0xDFD
 // 32 n + 16 j + 8 h .. + 8: half h of the 16-byte group 2 n + j -- not the lane's own group, so all four operands come from the strip, which keeps the halves
 // and the even / odd groups in separate regions (a K-step's 32 reads are then 32 consecutive 16-byte entries: conflict-free).
 // w[delta + 8][4 j + i]: dword i of K-step j for the row with delta = m - 8 h (i = position - m only depends on it): CountMfmaTable, scan_mfma_host.h.
+
+// The strip: four regions, (half e of a group, parity of the group); group g of the trip is entry g >> 1 of its two regions.  One region holds 32 U entries
+// + the halo's, padded so that the odd-parity region starts 16 banks (64 B mod 128) after the even one: a ds_write_b128 serves 8 consecutive lanes at a time
+// = 4 even groups (64 B of region 0) + 4 odd ones (64 B of region 1), which must not share a bank.  (The first padding, + 64 B, put them 20 banks apart:
+// SQ_LDS_BANK_CONFLICT = 30 % of the LDS cycles, profiles/r05_pmc_scan_mfma_shipped_forms.txt.)
+template <int U>
+struct AsciiStrip4 {
+    static constexpr int kRegion = (32 * U + 1) * 16 + 48;
+    static_assert(kRegion % 128 == 64, "the two parities of one store must land 16 banks apart");
+    static constexpr int kBytes = 4 * kRegion; // per wave
+    uint8_t *strip;
+    unsigned wr;  // the lane's own group l of round u: + 2 kRegion e + 512 u
+    unsigned rd;  // lane (n, h), K-step j of round u: + (j & 1) kRegion + 16 (32 u + (j >> 1))
+    unsigned m32, hh; // lane (n, h): column n, K-block h
+    unsigned row;     // the lane's row of CountMfmaTable: delta + 8
+    __device__ __forceinline__ AsciiStrip4(uint8_t *strip, unsigned lane) : strip(strip), m32(lane & 31u), hh(lane >> 5) {
+        wr = (lane & 1u) * kRegion + 16u * (lane >> 1);
+        rd = hh * 2u * kRegion + 16u * m32;
+        row = m32 + 8u - 8u * hh;
+    }
+    // one group: its two halves' one-hot nibbles
+    static __device__ __forceinline__ void put(uint8_t *p, const u32x4 &x) {
+        const i32x8 e0 = onehot8(x.x, x.y), e1 = onehot8(x.z, x.w);
+        *reinterpret_cast<u32x4 *>(p) = u32x4{(uint32_t)e0[0], (uint32_t)e0[1], (uint32_t)e0[2], (uint32_t)e0[3]};
+        *reinterpret_cast<u32x4 *>(p + 2 * kRegion) = u32x4{(uint32_t)e1[0], (uint32_t)e1[1], (uint32_t)e1[2], (uint32_t)e1[3]};
+    }
+    __device__ __forceinline__ void put_round(int u, const u32x4 &x) const { put(strip + wr + 512 * u, x); }
+    // groups 64 m and 64 m + 1, after the last VALID round
+    __device__ __forceinline__ void put_halo(unsigned lane, unsigned m, const u32x4 &hv) const {
+        if (lane < 2) put(strip + lane * kRegion + 512 * m, hv);
+    }
+    // the rounds, then the halo; returns the trip's validity residue
+    __device__ __forceinline__ uint32_t fill(unsigned lane, unsigned m, const ScanTrip<U> &t) const {
+        uint32_t bad = 0;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            ascii_residue(t.v[u][0], bad);
+            put_round(u, t.v[u][0]);
+        }
+        put_halo(lane, m, t.hv);
+        return bad;
+    }
+    __device__ __forceinline__ void read_b(int u, i32x8 (&B)[4]) const {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) B[j] = strip_operand(strip + rd + (j & 1) * kRegion + 16 * (32 * u + (j >> 1)));
+    }
+};
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // The distance bytes: pack_distances, then store_distances' natural dwordx4 store per lane.  One trip of U rounds per wave; the hardware dispatcher walks the trips (how every streaming kernel of this library runs fastest).  BLOCK: threads per workgroup --
@@ -223,44 +292,22 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, 8
 kmer_scan_seg_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, unsigned k, unsigned long long query, uint8_t *__restrict__ dist,
                           unsigned long long *__restrict__ slot, const CountMfmaTable tab) {
     constexpr bool NTLD = (POLICY & 1) != 0, NTST = (POLICY & 2) != 0;
-    // one (half, parity) region: 32 U entries + the halo's, padded so that the odd-parity region starts 16 banks (64 B mod 128) after the even one: a ds_write_b128
-    // serves 8 consecutive lanes at a time = 4 even groups (64 B of region 0) + 4 odd ones (64 B of region 1), which must not share a bank
-    constexpr int kRegion = (32 * U + 1) * 16 + 48;
-    static_assert(kRegion % 128 == 64, "the two parities of one store must land 16 banks apart");
-    __shared__ __attribute__((aligned(16))) uint8_t strips[BLOCK / 64][4 * kRegion];
+    __shared__ __attribute__((aligned(16))) uint8_t strips[BLOCK / 64][AsciiStrip4<U>::kBytes];
     const unsigned long long nwin = n - k + 1;
     const unsigned long long rounds = scan_rounds(n);
     const unsigned lane = threadIdx.x & 63;
     const unsigned long long wave = (unsigned long long)blockIdx.x * (blockDim.x >> 6) + wave_in_block();
-    uint8_t *strip = strips[wave_in_block()];
+    const AsciiStrip4<U> fe(strips[wave_in_block()], lane);
     const unsigned long long r0 = wave * U;
     if (r0 < rounds) {
         ScanTrip<U> cur;
         scan_trip_load<U, 3, NTLD>(ref, r0, rounds, lane, cur); // before the table: its loads overlap these
-        const unsigned m = rounds - r0 < (unsigned long long)U ? (unsigned)(rounds - r0) : (unsigned)U;
-        const unsigned m32 = lane & 31u, hh = lane >> 5;
+        const unsigned m = trip_rounds(r0, rounds, U);
         i32x8 A[4];
-        query_operand<4>(tab.w[m32 + 8u - 8u * hh], A);
-        const int scale_a = dist_row_scale(m32);
+        query_operand<4>(tab.w[fe.row], A);
+        const int scale_a = dist_row_scale(fe.m32);
         const f32x16 c0 = acc_start(tab.c); // 2^23
-        const unsigned wr0 = (lane & 1u) * kRegion + 16u * (lane >> 1);
-        const unsigned rd = hh * 2u * kRegion + 16u * m32;
-        uint32_t trip_bad = 0;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const u32x4 x = cur.v[u][0];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) trip_bad |= x[i] ^ __builtin_amdgcn_perm(0x47FFFF54u, 0x43FF41FFu, x[i] & 0x07070707u); // (trip_invalid's LUT)
-            const i32x8 e0 = onehot8(x.x, x.y), e1 = onehot8(x.z, x.w);
-            *reinterpret_cast<u32x4 *>(strip + wr0 + 512 * u) = u32x4{(uint32_t)e0[0], (uint32_t)e0[1], (uint32_t)e0[2], (uint32_t)e0[3]};
-            *reinterpret_cast<u32x4 *>(strip + wr0 + 512 * u + 2 * kRegion) = u32x4{(uint32_t)e1[0], (uint32_t)e1[1], (uint32_t)e1[2], (uint32_t)e1[3]};
-        }
-        if (lane < 2) { // the halo: groups 64 m and 64 m + 1 (after the last VALID round; in-order LDS: the later write wins over a clamped copy)
-            const i32x8 e0 = onehot8(cur.hv.x, cur.hv.y), e1 = onehot8(cur.hv.z, cur.hv.w);
-            *reinterpret_cast<u32x4 *>(strip + lane * kRegion + 512 * m) = u32x4{(uint32_t)e0[0], (uint32_t)e0[1], (uint32_t)e0[2], (uint32_t)e0[3]};
-            *reinterpret_cast<u32x4 *>(strip + lane * kRegion + 512 * m + 2 * kRegion) = u32x4{(uint32_t)e1[0], (uint32_t)e1[1], (uint32_t)e1[2], (uint32_t)e1[3]};
-        }
-        if (__builtin_expect(trip_invalid(trip_bad), 0)) { // some lane of the trip holds an invalid byte: find the round
+        if (__builtin_expect(trip_invalid(fe.fill(lane, m, cur)), 0)) { // some lane of the trip holds an invalid byte: find the round
 #pragma unroll 1
             for (unsigned u = 0; u < m; ++u) rescan_bytes(ref, ((r0 + u) << 10) + 16 * lane, 16, slot);
         }
@@ -269,14 +316,10 @@ kmer_scan_seg_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n,
         for (int u = 0; u < U; ++u) {
             if ((unsigned)u >= m) break; // wave-uniform
             i32x8 B[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const u32x4 t = *reinterpret_cast<const u32x4 *>(strip + rd + (j & 1) * kRegion + 16 * (32 * u + (j >> 1)));
-                B[j] = i32x8{(int)t.x, (int)t.y, (int)t.z, (int)t.w, 0, 0, 0, 0};
-            }
+            fe.read_b(u, B);
             uint32_t o[4];
             pack_distances(mfma_chain(A, B, c0, scale_a), o);
-            store_distances<NTST, true>(dist + ((r0 + u) << 10) + 16u * (2u * m32 + hh), o);
+            store_distances<NTST, true>(dist + ((r0 + u) << 10) + 16u * (2u * fe.m32 + fe.hh), o);
         }
     }
 
@@ -294,8 +337,6 @@ kmer_scan_seg_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n,
 // matrix instructions -- whose power is what lowers the clock (profiles/r05_ablate_count_parts.txt).  An invalid byte reads as T; the call fails anyway.
 // w[lane][4 s + i]: the lane's 16-byte operand of K-step s (built on the host: Count3MfmaTable, scan_mfma_host.h).  The threshold is inside the product
 // (count_row_scale, count_hits); tau >= k (no window can miss) gets an all-zero table.
-// A bounded grid (one arrival per workgroup at the accumulator's ticket) whose waves walk trips; the NEXT trip's loads are issued as soon as this trip's bytes
-// are in the strip, into the same registers, and fly during the matrix phase.
 
 // 16 bases (four ASCII dwords) -> their 16 (A, C) bytes and their 16 G nibbles (the three-channel operands)
 __device__ __forceinline__ void expand3(const u32x4 &x, u32x4 &ac, uint32_t &g0, uint32_t &g1) {
@@ -310,63 +351,78 @@ __device__ __forceinline__ void expand3(const u32x4 &x, u32x4 &ac, uint32_t &g0,
     g1 = (g[3] << 4) | g[2]; // ... bases 8 + t and 12 + t
 }
 
+// The strip: the (A, C) entries by the group's parity (two regions, the odd one 16 banks after the even one: AsciiStrip4's argument), then the G nibbles,
+// 16 bytes per 32 positions = 8 per group, in group order.
+template <int U>
+struct AsciiStrip3 {
+    static constexpr int kAc = (32 * U + 1) * 16 + 48; // one parity's (A, C) entries of a trip + the halo's
+    static_assert(kAc % 128 == 64, "the two parities of one store must land 16 banks apart");
+    static constexpr int kG = (32 * U + 1) * 16;
+    static constexpr int kBytes = 2 * kAc + kG; // per wave
+    uint8_t *strip;
+    unsigned wr_ac, wr_g; // the lane's own group l of round u, its 16 G nibbles: + 512 u
+    unsigned rd_ac, rd_g; // K-step s < 2 of round u: + 16 s + 512 u; K-step 2: + 512 u
+    unsigned m32, hh;     // lane (n, h): column n, K-block h
+    __device__ __forceinline__ AsciiStrip3(uint8_t *strip, unsigned lane)
+        : strip(strip), wr_ac((lane & 1u) * kAc + 16u * (lane >> 1)), wr_g(2u * kAc + 8u * lane), m32(lane & 31u), hh(lane >> 5) {
+        rd_ac = hh * kAc + 16u * m32;
+        rd_g = 2u * kAc + 16u * (m32 + hh);
+    }
+    static __device__ __forceinline__ void put(uint8_t *p_ac, uint8_t *p_g, const u32x4 &x) {
+        u32x4 ac;
+        uint32_t g0, g1;
+        expand3(x, ac, g0, g1);
+        *reinterpret_cast<u32x4 *>(p_ac) = ac;
+        *reinterpret_cast<u32x2 *>(p_g) = u32x2{g0, g1};
+    }
+    // the rounds, then the halo (groups 64 m and 64 m + 1, after the last VALID round); returns the trip's validity residue
+    __device__ __forceinline__ uint32_t fill(unsigned lane, unsigned m, const ScanTrip<U> &t) const {
+        uint32_t bad = 0;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            ascii_residue(t.v[u][0], bad);
+            put(strip + wr_ac + 512 * u, strip + wr_g + 512 * u, t.v[u][0]);
+        }
+        if (lane < 2) put(strip + lane * kAc + 512 * m, strip + 2 * kAc + 512 * m + 8 * lane, t.hv);
+        return bad;
+    }
+    __device__ __forceinline__ void read_b(int u, i32x8 (&B)[3]) const {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) B[j] = strip_operand(strip + (j < 2 ? rd_ac + 16 * j : rd_g) + 512 * u);
+    }
+};
 
+// A bounded grid (one arrival per workgroup at the accumulator's ticket) whose waves walk trips; the NEXT trip's loads are issued as soon as this trip's bytes
+// are in the strip, into the same registers, and fly during the matrix phase.
 template <int U, bool NTLD>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 8)))
 kmer_count3_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, unsigned k, unsigned long long query, unsigned tau,
                         unsigned long long *__restrict__ result, unsigned long long *__restrict__ total /* zero between launches */,
                         unsigned *__restrict__ ticket, unsigned long long *__restrict__ slot, const Count3MfmaTable tab) {
-    constexpr int kAc = (32 * U + 1) * 16 + 48; // one parity's (A, C) entries of a trip + the halo's; the odd region starts 16 banks after the even one
-    static_assert(kAc % 128 == 64, "the two parities of one store must land 16 banks apart");
-    constexpr int kG = (32 * U + 1) * 16;       // G nibbles: 16 bytes per 32 positions
-    __shared__ __attribute__((aligned(16))) uint8_t strips[kBlock / 64][2 * kAc + kG];
+    __shared__ __attribute__((aligned(16))) uint8_t strips[kBlock / 64][AsciiStrip3<U>::kBytes];
     const unsigned long long nwin = n - k + 1;
     const unsigned long long rounds = scan_rounds(n);
     const unsigned lane = threadIdx.x & 63;
     const unsigned long long wave = (unsigned long long)blockIdx.x * (blockDim.x >> 6) + wave_in_block();
     const unsigned long long nwaves = ((unsigned long long)gridDim.x * blockDim.x) >> 6;
-    uint8_t *strip = strips[wave_in_block()];
+    const AsciiStrip3<U> fe(strips[wave_in_block()], lane);
 
     ScanTrip<U> cur;
     unsigned long long r0 = wave * U;
     if (r0 < rounds) scan_trip_load<U, 3, NTLD>(ref, r0, rounds, lane, cur);
-    const unsigned m32 = lane & 31u, hh = lane >> 5;
     i32x8 A[3];
     query_operand<3>(tab.w[lane], A);
     asm volatile("" : "+v"(A[0][0]), "+v"(A[0][1]), "+v"(A[0][2]), "+v"(A[0][3]), "+v"(A[1][0]), "+v"(A[1][1]), "+v"(A[1][2]), "+v"(A[1][3]),
                       "+v"(A[2][0]), "+v"(A[2][1]), "+v"(A[2][2]), "+v"(A[2][3]));
     uint32_t lane_hits = 0;
-    const int scale_a = count_row_scale(m32);
+    const int scale_a = count_row_scale(lane & 31u);
     const f32x16 c0 = acc_start(tab.c);
-    const unsigned wr_ac = (lane & 1u) * kAc + 16u * (lane >> 1); // the lane's own group l of round u: + 512 u
-    const unsigned wr_g = 2u * kAc + 8u * lane;                   // ... its 16 G nibbles: + 512 u
-    const unsigned rd_ac = hh * kAc + 16u * m32;                  // K-step s < 2 of round u: + 16 s + 512 u
-    const unsigned rd_g = 2u * kAc + 16u * (m32 + hh);            // K-step 2: + 512 u
 
     while (r0 < rounds) {
-        const unsigned m = rounds - r0 < (unsigned long long)U ? (unsigned)(rounds - r0) : (unsigned)U;
+        const unsigned m = trip_rounds(r0, rounds, U);
         const unsigned long long rn = r0 + nwaves * U;
         wave_lds_fence(); // the previous trip's readers are done
-        uint32_t trip_bad = 0;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const u32x4 x = cur.v[u][0];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) trip_bad |= x[i] ^ __builtin_amdgcn_perm(0x47FFFF54u, 0x43FF41FFu, x[i] & 0x07070707u); // (trip_invalid's LUT)
-            u32x4 ac;
-            uint32_t g0, g1;
-            expand3(x, ac, g0, g1);
-            *reinterpret_cast<u32x4 *>(strip + wr_ac + 512 * u) = ac;
-            *reinterpret_cast<u32x2 *>(strip + wr_g + 512 * u) = u32x2{g0, g1};
-        }
-        if (lane < 2) { // the halo: groups 64 m and 64 m + 1 (after the last VALID round; in-order LDS: the later write wins over a clamped copy)
-            u32x4 ac;
-            uint32_t g0, g1;
-            expand3(cur.hv, ac, g0, g1);
-            *reinterpret_cast<u32x4 *>(strip + lane * kAc + 512 * m) = ac;
-            *reinterpret_cast<u32x2 *>(strip + 2 * kAc + 512 * m + 8 * lane) = u32x2{g0, g1};
-        }
-        if (__builtin_expect(trip_invalid(trip_bad), 0)) { // some lane of the trip holds an invalid byte: find the round
+        if (__builtin_expect(trip_invalid(fe.fill(lane, m, cur)), 0)) { // some lane of the trip holds an invalid byte: find the round
 #pragma unroll 1
             for (unsigned u = 0; u < m; ++u) rescan_bytes(ref, ((r0 + u) << 10) + 16 * lane, 16, slot);
         }
@@ -376,11 +432,7 @@ kmer_count3_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, u
         for (int u = 0; u < U; ++u) {
             if ((unsigned)u >= m) break; // wave-uniform
             i32x8 B[3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const u32x4 t = *reinterpret_cast<const u32x4 *>(strip + (j < 2 ? rd_ac + 16 * j : rd_g) + 512 * u);
-                B[j] = i32x8{(int)t.x, (int)t.y, (int)t.z, (int)t.w, 0, 0, 0, 0};
-            }
+            fe.read_b(u, B);
             const f32x16 acc = mfma_chain(A, B, c0, scale_a);
 #pragma unroll
             for (int q = 0; q < 4; ++q) lane_hits += (uint32_t)__builtin_popcount(hit_bits(acc, q));
