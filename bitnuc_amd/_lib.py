@@ -63,6 +63,10 @@ SIGNATURES = {
     "bitnuc_kmer_hdist_count_multi_packed_dev": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _P, _SZ, _P, _ERR]),
     "bitnuc_kmer_hdist_count_multi": (C.c_int, [_P, _P, _SZ, _SZ, _P, _P, _SZ, _P, _ERR]),
     "bitnuc_kmer_hdist_count_multi_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _P, _SZ, _P, _ERR]),
+    "bitnuc_kmer_hdist_best_async": (C.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _ERR]),
+    "bitnuc_kmer_hdist_best_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _ERR]),
+    "bitnuc_kmer_hdist_best": (C.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _ERR]),
+    "bitnuc_kmer_hdist_best_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _ERR]),
     "bitnuc_hdist_dev": (C.c_int, [_P, _P, _SZ, _P, _SZ, _SZ, _P, _ERR]),
     "bitnuc_batch_word_offsets_dev": (C.c_int, [_P, _P, _SZ, _P, C.POINTER(_SZ), _ERR]),
     "bitnuc_encode_batch_dev": (C.c_int, [_P, _P, _P, _P, _SZ, _SZ, _P, _ERR]),

@@ -363,6 +363,26 @@ class Context:
             _raise(err)
         return out
 
+    def _best(self, fn, head, queries):
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.uint64).reshape(-1))  # a scalar query: Q = 1
+        pos = np.empty(q.size, dtype=np.uint64)
+        dist = np.empty(q.size, dtype=np.uint8)
+        err = L.BitnucErr()
+        if fn(self._h, *head, _ptr(q), q.size, _ptr(pos), _ptr(dist), C.byref(err)) != L.OK:
+            _raise(err)
+        return pos, dist
+
+    def kmer_hdist_best(self, ref, k, queries):
+        """The best match per query in one pass: (pos, dist) with dist[q] = the smallest Hamming distance of a window of `ref` to queries[q] (np.uint8)
+        and pos[q] = the leftmost window that attains it (np.uint64); without windows every pos is 2^64 - 1 and every dist 255."""
+        s = _as_u8(ref)
+        return self._best(self._lib.bitnuc_kmer_hdist_best, (_ptr(s), s.size, int(k)), queries)
+
+    def kmer_hdist_best_packed(self, words, n_bases, k, queries):
+        """kmer_hdist_best of the packed sequence `words` holding `n_bases` bases, without decoding it."""
+        w = _as_u64(words)
+        return self._best(self._lib.bitnuc_kmer_hdist_best_packed, (_ptr(w), w.size, int(n_bases), int(k)), queries)
+
     # -- analysis on packed words (src/utils/analysis.rs, hamming/scalar.rs) ------------------
     def base_counts(self, words, n_bases):
         """[A, C, G, T] counts of a packed sequence (BaseCount::base_counts, analysis.rs:23-39)."""
@@ -592,6 +612,17 @@ class Context:
         """The multi-query count on packed words in device memory (8-byte aligned)."""
         self._call_dev(self._lib.bitnuc_kmer_hdist_count_multi_packed_dev, _dev_ptr(d_words), int(n_words), int(n), int(k), _dev_ptr(d_queries),
                        _dev_ptr(d_taus), int(n_queries), _dev_ptr(d_counts))
+
+    def kmer_hdist_best_async(self, d_ref, n, k, d_queries, n_queries, d_pos, d_dist):
+        """The best match of n_queries queries at once: d_dist[q] (u8) = the smallest distance of a window to d_queries[q] (u64), d_pos[q] (u64) = the
+        leftmost window that attains it.  Asynchronous on the context's stream, as the _dev calls."""
+        self._call_dev(self._lib.bitnuc_kmer_hdist_best_async, _dev_ptr(d_ref), int(n), int(k), _dev_ptr(d_queries), int(n_queries), _dev_ptr(d_pos),
+                       _dev_ptr(d_dist))
+
+    def kmer_hdist_best_packed_async(self, d_words, n_words, n, k, d_queries, n_queries, d_pos, d_dist):
+        """The best match per query on packed words in device memory (8-byte aligned)."""
+        self._call_dev(self._lib.bitnuc_kmer_hdist_best_packed_async, _dev_ptr(d_words), int(n_words), int(n), int(k), _dev_ptr(d_queries), int(n_queries),
+                       _dev_ptr(d_pos), _dev_ptr(d_dist))
 
     def hdist_dev(self, d_a, na, d_b, nb, n_bases, d_result):
         self._call_dev(self._lib.bitnuc_hdist_dev, _dev_ptr(d_a), int(na), _dev_ptr(d_b), int(nb), int(n_bases), _dev_ptr(d_result))

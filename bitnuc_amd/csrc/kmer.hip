@@ -2,16 +2,18 @@
 // <= 32-mers (BASELINE config 3, README.md:52-56), every window of a sequence (src/lib.rs:170-173), the sliding pack +
 // Hamming scan (config 5: packing/mod.rs:80-110 o hamming/scalar.rs:11-48) and bulk hdist (hamming/multi.rs:121-160).
 // Kernels: kmer_device.h; config 5 on the matrix cores: scan_mfma_device.h; the same scan and count on packed words: scan_packed_device.h; the hit
-// lists of both: scan_hits_device.h; the count for many queries at once: scan_multi_device.h.
+// lists of both: scan_hits_device.h; the count for many queries at once: scan_multi_device.h; the best match per query: scan_best_device.h.
 #include "runtime.h"
 #include "kmer_device.h"
 #include "scan_mfma_device.h"
 #include "scan_packed_device.h"
 #include "scan_hits_device.h"
 #include "scan_multi_device.h"
+#include "scan_best_device.h"
 #include "scan_mfma_host.h"
 #include "scan_hits_host.h"
 #include "scan_multi_host.h"
+#include "scan_best_host.h"
 #include "host_word.h"
 #include "host_pipe.h"
 
@@ -412,6 +414,99 @@ int multi_host_loop(bitnuc_ctx *c, size_t nwin, size_t per, const uint64_t *quer
         for (size_t q = 0; q < nq; ++q) total[q] += part[q];
     }
     memcpy(counts, total.data(), nq * 8);
+    return BITNUC_OK;
+}
+
+// ---- the best match per query (scan_best_device.h).  Context scratch 9 holds the keys (one u64 per query, all-ones = no window yet) and behind them the
+// tables (one BestTable per query, built in-stream from d_queries); a launch recorded into a hipGraph keeps it (ensure_scratch: warm up with the same
+// n_queries before capturing).  The keys are set to all-ones first in the same stream, every workgroup then takes its per-query minima into them and
+// best_finish_kernel writes pos[] / dist[].  The grid: the multi-query count's (one workgroup per CU at most x the query blocks).
+struct BestArgs { const uint64_t *queries; size_t nq; unsigned long long *pos; uint8_t *dist; };
+
+template <bool PACKED>
+int best_setup(bitnuc_ctx *c, size_t k, const BestArgs &a, unsigned long long rounds, unsigned long long **keys, const BestTable **tabs, dim3 *grid, bitnuc_err *err) {
+    const size_t kbytes = (a.nq * 8 + 255) & ~(size_t)255;
+    if (int st = ensure_scratch(c, 9, kbytes + a.nq * sizeof(BestTable), err)) return st;
+    *keys = reinterpret_cast<unsigned long long *>(c->scratch[9]);
+    BestTable *t = reinterpret_cast<BestTable *>(c->scratch[9] + kbytes);
+    HIPCHK(hipMemsetAsync(*keys, 0xFF, a.nq * sizeof(uint64_t), c->stream));
+    best_tables_kernel<PACKED><<<(unsigned)a.nq, 64, 0, c->stream>>>(reinterpret_cast<const unsigned long long *>(a.queries), (unsigned)k, t);
+    HIPCHK(hipGetLastError());
+    *tabs = t;
+    *grid = dim3(bounded_grid(c, rounds, (kMultiBlock / 64) * kMultiRounds, kMultiGrid), (unsigned)((a.nq + kMultiQB - 1) / kMultiQB), 1);
+    return BITNUC_OK;
+}
+
+int best_finish(bitnuc_ctx *c, const unsigned long long *keys, const BestArgs &a, bitnuc_err *err) {
+    HIPCHK(hipGetLastError());
+    best_finish_kernel<<<(unsigned)((a.nq + 255) / 256), 256, 0, c->stream>>>(keys, (unsigned)a.nq, a.pos, a.dist);
+    HIPCHK(hipGetLastError());
+    return BITNUC_OK;
+}
+
+// d_ref at any alignment (ascii_skip)
+int launch_best(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const BestArgs &a, unsigned long long *slot, bitnuc_err *err) {
+    const unsigned skip = ascii_skip(ref);
+    unsigned long long *keys;
+    const BestTable *tabs;
+    dim3 grid;
+    if (int st = best_setup<false>(c, k, a, scan_rounds(n, skip), &keys, &tabs, &grid, err)) return st;
+    kmer_best_kernel<kMultiRounds><<<grid, kMultiBlock, 0, c->stream>>>(ref, n, skip, (unsigned)k, reinterpret_cast<const unsigned long long *>(a.queries),
+                                                                       (unsigned)a.nq, tabs, keys, slot);
+    return best_finish(c, keys, a, err);
+}
+
+// d_words 8-byte aligned (packed_skip)
+int launch_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t n, size_t k, const BestArgs &a, bitnuc_err *err) {
+    const unsigned skip = packed_skip(words);
+    unsigned long long *keys;
+    const BestTable *tabs;
+    dim3 grid;
+    if (int st = best_setup<true>(c, k, a, scan_rounds(n, skip), &keys, &tabs, &grid, err)) return st;
+    packed_best_kernel<<<grid, kMultiBlock, 0, c->stream>>>(words, n, skip, (unsigned)k, reinterpret_cast<const unsigned long long *>(a.queries), (unsigned)a.nq, tabs,
+                                                            keys);
+    return best_finish(c, keys, a, err);
+}
+
+// the best-match calls' checks 4 - 6 (after ctx, k and the packed word count): n_queries == 0 -> OK (*none), too many queries, the three arrays
+int check_best(const void *queries, size_t nq, const void *pos, const void *dist, bool *none, bitnuc_err *err) {
+    *none = nq == 0;
+    if (*none) return BITNUC_OK;
+    if (nq > BITNUC_MAX_QUERIES) return fail(err, BITNUC_UNSUPPORTED, nq);
+    if (!pos || (reinterpret_cast<uintptr_t>(pos) & 7) || !queries || (reinterpret_cast<uintptr_t>(queries) & 7) || !dist) return fail(err, BITNUC_UNSUPPORTED);
+    return BITNUC_OK;
+}
+
+// no windows: every pos UINT64_MAX, every dist 0xFF
+int best_fill_dev(bitnuc_ctx *c, uint64_t *d_pos, uint8_t *d_dist, size_t nq, bitnuc_err *err) {
+    HIPCHK(hipMemsetAsync(d_pos, 0xFF, nq * sizeof(uint64_t), c->stream));
+    HIPCHK(hipMemsetAsync(d_dist, 0xFF, nq, c->stream));
+    return BITNUC_OK;
+}
+
+// The host forms' chunk loop: the queries copied once into scratch 2, the chunk's positions / distances in scratch 1 / 3; `launch(i0, a)` runs the chunk
+// of windows starting at i0 with a's device arrays.  The chunks' results merge by the lexicographic (dist, absolute pos) minimum; stops at the first
+// failing chunk (drain: its first invalid byte).
+template <class Launch>
+int best_host_loop(bitnuc_ctx *c, size_t nwin, size_t per, const uint64_t *queries, size_t nq, uint64_t *pos, uint8_t *dist, bitnuc_err *err, Launch launch) {
+    if (int st = ensure_scratch(c, 1, nq * 8, err)) return st;
+    if (int st = ensure_scratch(c, 2, nq * 8, err)) return st;
+    if (int st = ensure_scratch(c, 3, nq < 64 ? 64 : nq, err)) return st;
+    HIPCHK(hipMemcpyAsync(c->scratch[2], queries, nq * 8, hipMemcpyHostToDevice, c->stream));
+    const BestArgs a{reinterpret_cast<const uint64_t *>(c->scratch[2]), nq, reinterpret_cast<unsigned long long *>(c->scratch[1]), c->scratch[3]};
+    std::vector<uint64_t> ppos(nq), bpos(nq, ~0ull);
+    std::vector<uint8_t> pdist(nq), bdist(nq, 0xFF);
+    for (size_t i0 = 0; i0 < nwin; i0 += per) {
+        if (int st = launch(i0, a)) return st;
+        HIPCHK(hipMemcpyAsync(ppos.data(), c->scratch[1], nq * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(pdist.data(), c->scratch[3], nq, hipMemcpyDeviceToHost, c->stream));
+        bitnuc_err e;
+        if (int st = drain(c, &e)) { if (err) *err = e; return st; }
+        for (size_t q = 0; q < nq; ++q) // chunks come in ascending order: a later chunk wins on a smaller distance only
+            if (pdist[q] < bdist[q]) bdist[q] = pdist[q], bpos[q] = i0 + ppos[q];
+    }
+    memcpy(pos, bpos.data(), nq * 8);
+    memcpy(dist, bdist.data(), nq);
     return BITNUC_OK;
 }
 
@@ -863,6 +958,96 @@ int bitnuc_kmer_hdist_count_multi_packed(bitnuc_ctx *c, const uint64_t *words, s
         const PackedChunk ch = packed_chunk(i0 / 32, n, k);
         HIPCHK(hipMemcpyAsync(c->scratch[0], words + ch.w0, ch.words * 8, hipMemcpyHostToDevice, c->stream));
         return launch_count_multi_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), ch.bases, k, a, err);
+    });
+}
+
+// ---- the best match per query -------------------------------------------------------------------------------------------
+int bitnuc_kmer_hdist_best_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const uint64_t *d_queries, size_t n_queries, uint64_t *d_pos,
+                                 uint8_t *d_dist, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    bool none;
+    if (int st = check_best(d_queries, n_queries, d_pos, d_dist, &none, err)) return st;
+    if (none) return BITNUC_OK;
+    DeviceGuard g(c->device);
+    if (k == 0 || n < k) return best_fill_dev(c, d_pos, d_dist, n_queries, err); // no windows
+    if (!d_ref) return fail(err, BITNUC_UNSUPPORTED);
+    unsigned long long *slot;
+    if (int st = take_slot(c, 0, &slot, err)) return st;
+    return launch_best(c, d_ref, n, k, BestArgs{d_queries, n_queries, reinterpret_cast<unsigned long long *>(d_pos), d_dist}, slot, err);
+}
+
+int bitnuc_kmer_hdist_best_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const uint64_t *d_queries, size_t n_queries,
+                                        uint64_t *d_pos, uint8_t *d_dist, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
+    bool none;
+    if (int st = check_best(d_queries, n_queries, d_pos, d_dist, &none, err)) return st;
+    if (none) return BITNUC_OK;
+    DeviceGuard g(c->device);
+    if (k == 0 || n < k) return best_fill_dev(c, d_pos, d_dist, n_queries, err);
+    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    return launch_best_packed(c, d_words, n, k, BestArgs{d_queries, n_queries, reinterpret_cast<unsigned long long *>(d_pos), d_dist}, err);
+}
+
+int bitnuc_kmer_hdist_best(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const uint64_t *queries, size_t n_queries, uint64_t *pos, uint8_t *dist,
+                           bitnuc_err *err) {
+    clear_err(err);
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    bool none;
+    if (int st = check_best(queries, n_queries, pos, dist, &none, err)) return st;
+    if (none) return BITNUC_OK;
+    if (k == 0 || n < k) { memset(pos, 0xFF, n_queries * sizeof(uint64_t)); memset(dist, 0xFF, n_queries); return BITNUC_OK; }
+    if (!ref) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, multi_work(n - k + 1, n_queries))) {
+        const long long bad = bitnuc_host::kmer_hdist_best_small(ref, n, k, queries, n_queries, pos, dist);
+        if (bad >= 0) {
+            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = ref[bad]; err->index = (uint64_t)bad; }
+            return BITNUC_INVALID_BASE;
+        }
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    // chunks of kHostChunk windows + their k - 1 halo bases
+    if (int st = ensure_scratch(c, 0, kHostChunk + 64, err)) return st;
+    const size_t nwin = n - k + 1;
+    return best_host_loop(c, nwin, kHostChunk, queries, n_queries, pos, dist, err, [&](size_t i0, const BestArgs &a) {
+        const size_t m = nwin - i0 < kHostChunk ? nwin - i0 : kHostChunk;
+        HIPCHK(hipMemcpyAsync(c->scratch[0], ref + i0, m + k - 1, hipMemcpyHostToDevice, c->stream));
+        unsigned long long *slot;
+        if (int st = take_slot(c, i0, &slot, err)) return st;
+        return launch_best(c, c->scratch[0], m + k - 1, k, a, slot, err);
+    });
+}
+
+int bitnuc_kmer_hdist_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const uint64_t *queries, size_t n_queries, uint64_t *pos,
+                                  uint8_t *dist, bitnuc_err *err) {
+    clear_err(err);
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
+    bool none;
+    if (int st = check_best(queries, n_queries, pos, dist, &none, err)) return st;
+    if (none) return BITNUC_OK;
+    if (k == 0 || n < k) { memset(pos, 0xFF, n_queries * sizeof(uint64_t)); memset(dist, 0xFF, n_queries); return BITNUC_OK; }
+    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, multi_work(n - k + 1, n_queries))) {
+        bitnuc_host::kmer_hdist_best_packed_small(words, n, k, queries, n_queries, pos, dist);
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    if (int st = ensure_scratch(c, 0, (kPackedChunkWords + 1) * 8, err)) return st;
+    // chunk w0 / 32 of whole words (packed_chunk): its windows start at base i0 = 32 w0
+    return best_host_loop(c, n - k + 1, 32 * kPackedChunkWords, queries, n_queries, pos, dist, err, [&](size_t i0, const BestArgs &a) {
+        const PackedChunk ch = packed_chunk(i0 / 32, n, k);
+        HIPCHK(hipMemcpyAsync(c->scratch[0], words + ch.w0, ch.words * 8, hipMemcpyHostToDevice, c->stream));
+        return launch_best_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), ch.bases, k, a, err);
     });
 }
 

@@ -18,6 +18,8 @@ namespace bitnuc_dev {
 struct CountMfmaTable { uint32_t w[40][16]; float c[4]; }; // c[r & 3]: where result register r's accumulator starts
 struct Count3MfmaTable { uint32_t w[64][12]; float c[4]; };
 struct PackedScanTable { uint32_t w[34][16]; float c[4]; }; // w[m - 2 h + 2]: the packed scan's rows only depend on m - 2 h (scan_packed_table)
+constexpr int kBestRows = 40;                             // rows of a best-match table: CountMfmaTable's 40 (ASCII), PackedScanTable's 34 (packed)
+struct BestTable { uint32_t w[kBestRows][16]; };           // one query's operand rows of the best-match kernels (scan_best_device.h); no start values
 } // namespace bitnuc_dev
 
 namespace bitnuc_dev {
@@ -89,6 +91,24 @@ inline void count_mfma_table(uint64_t query, size_t k, CountMfmaTable *t, bool t
             }
 }
 
+// Row delta of count_mfma_table's plain (not thresholded) form, straight from the query: dword 4 j + i, byte b meets query base
+// 16 j + 4 (i >> 1) + b - delta on channels (A, C) (i even) or (G, T) (i odd), 1.0 where the channel differs from the query's base.  The best-match
+// kernels build their tables with it on the device, one thread per row (scan_best_device.h).
+BITNUC_HD inline void scan_seg_row(uint64_t query, size_t k, int delta, uint32_t *row) {
+    for (int j = 0; j < 4; ++j)
+        for (int i = 0; i < 4; ++i) {
+            uint32_t w = 0;
+            for (int b = 0; b < 4; ++b) {
+                const int p = 16 * j + 4 * (i >> 1) + b - delta;
+                if (p < 0 || p >= (int)k) continue;
+                const unsigned qb = (unsigned)((query >> (2 * p)) & 3);
+                const unsigned lo = (i & 1) ? 2u : 0u, hi = lo + 1u; // (A, C) or (G, T)
+                w |= ((qb != lo ? 0x02u : 0u) | (qb != hi ? 0x20u : 0u)) << (8 * b);
+            }
+            row[4 * j + i] = w;
+        }
+}
+
 // The three-channel code (A, C, G one-hot, T = 0) of both count tables (count3_mfma_table, count3_packed_table): d = #(q_i != T) + sum over the window
 // of v(q_i, channel) x[channel], v = -1 on channel q for q in {A, C, G}, +1 on all three for q = T.  Rows with m & 3 < 3 carry -v and start at
 // 2^23 + (32 + tau - #(q_i != T)) 2^(6 j) (they end at 32 + tau - d), rows with m & 3 = 3 carry v at scale 2 and start at 2 #(q_i != T) - 2 tau - 1.
@@ -155,20 +175,23 @@ BITNUC_HD inline void count3_mfma_table(uint64_t query, size_t k, unsigned tau, 
 // 16-base group is its bases with (b & 3) >> 1 == h), low nibble channel A (d even) / G (d odd), high nibble C / T.  The query offset is that position
 // minus m, so a row only depends on m - 2 h: w[m - 2 h + 2].  Entries mark the channels that differ from the query's base; the accumulators start at the
 // 2^23 pack bias (kmer_scan_seg_mfma_kernel's pack).
-inline void scan_packed_table(uint64_t query, size_t k, PackedScanTable *t) {
-    for (int delta = -2; delta < 32; ++delta)
-        for (int j = 0; j < 4; ++j)
-            for (int d = 0; d < 4; ++d) {
-                uint32_t w = 0;
-                for (int q = 0; q < 4; ++q) {
-                    const int i = 16 * j + 4 * q + (d >> 1) - delta;
-                    if (i < 0 || i >= (int)k) continue;
-                    const unsigned qb = (unsigned)((query >> (2 * i)) & 3);
-                    const unsigned lo = (d & 1) ? 2u : 0u, hi = lo + 1u; // (A, C) or (G, T)
-                    w |= ((qb != lo ? 0x02u : 0u) | (qb != hi ? 0x20u : 0u)) << (8 * q);
-                }
-                t->w[delta + 2][4 * j + d] = w;
+// (one row: scan_packed_row; the best-match kernels build theirs on the device, one thread per row: scan_best_device.h)
+BITNUC_HD inline void scan_packed_row(uint64_t query, size_t k, int delta, uint32_t *row) {
+    for (int j = 0; j < 4; ++j)
+        for (int d = 0; d < 4; ++d) {
+            uint32_t w = 0;
+            for (int q = 0; q < 4; ++q) {
+                const int i = 16 * j + 4 * q + (d >> 1) - delta;
+                if (i < 0 || i >= (int)k) continue;
+                const unsigned qb = (unsigned)((query >> (2 * i)) & 3);
+                const unsigned lo = (d & 1) ? 2u : 0u, hi = lo + 1u; // (A, C) or (G, T)
+                w |= ((qb != lo ? 0x02u : 0u) | (qb != hi ? 0x20u : 0u)) << (8 * q);
             }
+            row[4 * j + d] = w;
+        }
+}
+inline void scan_packed_table(uint64_t query, size_t k, PackedScanTable *t) {
+    for (int delta = -2; delta < 32; ++delta) scan_packed_row(query, k, delta, t->w[delta + 2]);
     for (int j = 0; j < 4; ++j) t->c[j] = kPackBias;
 }
 

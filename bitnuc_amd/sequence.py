@@ -76,3 +76,6 @@ class PackedSequence:
 
     def kmer_hdist_count_multi(self, k, queries, taus):
         return self._ctx.kmer_hdist_count_multi_packed(self.data, self.length, k, queries, taus)
+
+    def kmer_hdist_best(self, k, queries):
+        return self._ctx.kmer_hdist_best_packed(self.data, self.length, k, queries)

@@ -278,6 +278,24 @@ class Context {
             return NucleotideError::from_c(e);
         return counts;
     }
+    // the best match per query in one pass: (pos[q], dist[q]) = the leftmost window with the smallest distance to queries[q] and that distance
+    // (no windows: UINT64_MAX / 0xFF)
+    Result<std::pair<std::vector<uint64_t>, std::vector<uint8_t>>> kmer_hdist_best(Bytes ref, size_t k, const std::vector<uint64_t> &queries) const {
+        std::vector<uint64_t> pos(queries.size());
+        std::vector<uint8_t> dist(queries.size());
+        bitnuc_err e;
+        if (bitnuc_kmer_hdist_best(ctx_, ref.ptr, ref.len, k, queries.data(), queries.size(), pos.data(), dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return std::make_pair(std::move(pos), std::move(dist));
+    }
+    Result<std::pair<std::vector<uint64_t>, std::vector<uint8_t>>> kmer_hdist_best_packed(Words words, size_t n, size_t k, const std::vector<uint64_t> &queries) const {
+        std::vector<uint64_t> pos(queries.size());
+        std::vector<uint8_t> dist(queries.size());
+        bitnuc_err e;
+        if (bitnuc_kmer_hdist_best_packed(ctx_, words.ptr, words.len, n, k, queries.data(), queries.size(), pos.data(), dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return std::make_pair(std::move(pos), std::move(dist));
+    }
     Result<std::vector<uint64_t>> kmer_hdist_hits_packed(Words words, size_t n, size_t k, uint64_t query, unsigned tau, std::vector<uint8_t> *hit_dist = nullptr) const {
         uint64_t total = 0;
         bitnuc_err e;

@@ -57,7 +57,8 @@
  *     device scratch in 128 Mbase chunks;
  *     "_dev" entry points take device pointers, are enqueued
  *     on the context's stream and return immediately -- data-dependent errors
- *     (InvalidBase) are latched on the device and reported by bitnuc_ctx_sync();
+ *     (InvalidBase) are latched on the device and reported by bitnuc_ctx_sync(); the "_async" entry points
+ *     (bitnuc_kmer_hdist_best[_packed]_async) have exactly the "_dev" contract under another suffix;
  *   - a bitnuc_ctx owns one device + stream + scratch and must not be used from
  *     two threads at once; separate contexts are independent.
  */
@@ -216,6 +217,33 @@ int bitnuc_kmer_hdist_count_multi(bitnuc_ctx *ctx, const uint8_t *ref, size_t n,
                                   uint64_t *counts, bitnuc_err *err);
 int bitnuc_kmer_hdist_count_multi_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t n_words, size_t n, size_t k, const uint64_t *queries,
                                          const uint32_t *taus, size_t n_queries, uint64_t *counts, bitnuc_err *err);
+/* The BEST MATCH per query in one pass over the reference: dist[q] = the minimum over the windows i in 0..n-k+1 of
+ * hdist_scalar(as_2bit(ref[i..i+k]), queries[q], k) and pos[q] = the smallest i that attains it -- what an arg-min over bitnuc_kmer_hdist_scan's distance
+ * bytes gives per query (composition of packing/mod.rs:80-110 and hamming/scalar.rs:11-48), without writing or reading those bytes: one byte read per
+ * window whatever the number of queries.  The result is deterministic.  Query bits above 2k are ignored.  With no windows (k == 0 or n < k) every
+ * pos[q] = UINT64_MAX and every dist[q] = 0xFF.  pos[0 .. n_queries) and dist[0 .. n_queries) are written and nothing after them.
+ * Checks, in this order: (1) ctx NULL -> UNSUPPORTED (_async forms; the host forms below the cutoff accept NULL); (2) k > 32 -> SEQUENCE_TOO_LONG(k);
+ * (3) packed: n_words < ceil(n/32) -> INVALID_LENGTH(n); (4) n_queries == 0 -> OK, nothing written; (5) n_queries > BITNUC_MAX_QUERIES -> UNSUPPORTED
+ * (err.value = n_queries); (6) pos or queries NULL or not 8-byte aligned, or dist NULL -> UNSUPPORTED (dist may have any byte offset); (7) k == 0 or
+ * n < k -> OK with the values above; (8) a NULL reference, or packed words not 8-byte aligned -> UNSUPPORTED.
+ * ASCII: an invalid base -> INVALID_BASE with the first invalid byte in sequence order (the _async forms latch it once per call for bitnuc_ctx_sync();
+ * pos and dist are then unspecified).  d_ref may have any alignment (the up to 15 windows before its first 16-byte aligned base take the tail's path);
+ * packed words 16-byte aligned or at 8 mod 16.
+ * The _async forms have the _dev contract: device pointers (queries, pos and dist included), enqueued on the context's stream, no host synchronisation
+ * (with the one exception below), InvalidBase latched for bitnuc_ctx_sync().  They keep one key per query and one table per query (2.5 KiB) in context scratch and can be captured into
+ * a hipGraph, but scratch cannot grow during a capture (BITNUC_UNSUPPORTED, err.value = the bytes needed): warm up with the same (or a larger)
+ * n_queries first.  Outside a capture a call that needs more scratch than the context holds (a larger n_queries than any call before it) waits for the
+ * stream before it replaces the allocation, as the multi-query count does: a queue that must never wait starts with its largest n_queries.
+ * The host forms are synchronous.  When windows x n_queries is below the host cutoff (as the multi-query count judges it) they run on the host and ctx
+ * may be NULL; above it they run through the context in chunks of 128 M windows that overlap by k - 1 bases, merged by the smallest (dist, pos). */
+int bitnuc_kmer_hdist_best_async(bitnuc_ctx *ctx, const uint8_t *d_ref, size_t n, size_t k, const uint64_t *d_queries, size_t n_queries, uint64_t *d_pos,
+                                 uint8_t *d_dist, bitnuc_err *err);
+int bitnuc_kmer_hdist_best_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const uint64_t *d_queries,
+                                        size_t n_queries, uint64_t *d_pos, uint8_t *d_dist, bitnuc_err *err);
+int bitnuc_kmer_hdist_best(bitnuc_ctx *ctx, const uint8_t *ref, size_t n, size_t k, const uint64_t *queries, size_t n_queries, uint64_t *pos, uint8_t *dist,
+                           bitnuc_err *err);
+int bitnuc_kmer_hdist_best_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t n_words, size_t n, size_t k, const uint64_t *queries, size_t n_queries,
+                                  uint64_t *pos, uint8_t *dist, bitnuc_err *err);
 /* d_result: one uint32 in device memory, overwritten with the distance. */
 int bitnuc_hdist_dev(bitnuc_ctx *ctx, const uint64_t *d_a, size_t na, const uint64_t *d_b, size_t nb, size_t n_bases, uint32_t *d_result, bitnuc_err *err);
 

@@ -128,6 +128,10 @@ extern "C" {
     pub fn bitnuc_kmer_hdist_count_multi_packed_dev(ctx: *mut bitnuc_ctx, d_words: *const u64, n_words: usize, n: usize, k: usize, d_queries: *const u64, d_taus: *const u32, n_queries: usize, d_counts: *mut u64, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_kmer_hdist_count_multi(ctx: *mut bitnuc_ctx, reference: *const u8, n: usize, k: usize, queries: *const u64, taus: *const u32, n_queries: usize, counts: *mut u64, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_kmer_hdist_count_multi_packed(ctx: *mut bitnuc_ctx, words: *const u64, n_words: usize, n: usize, k: usize, queries: *const u64, taus: *const u32, n_queries: usize, counts: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_hdist_best_async(ctx: *mut bitnuc_ctx, d_ref: *const u8, n: usize, k: usize, d_queries: *const u64, n_queries: usize, d_pos: *mut u64, d_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_hdist_best_packed_async(ctx: *mut bitnuc_ctx, d_words: *const u64, n_words: usize, n: usize, k: usize, d_queries: *const u64, n_queries: usize, d_pos: *mut u64, d_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_hdist_best(ctx: *mut bitnuc_ctx, reference: *const u8, n: usize, k: usize, queries: *const u64, n_queries: usize, pos: *mut u64, dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_hdist_best_packed(ctx: *mut bitnuc_ctx, words: *const u64, n_words: usize, n: usize, k: usize, queries: *const u64, n_queries: usize, pos: *mut u64, dist: *mut u8, err: *mut bitnuc_err) -> c_int;
     // diagnostics
     pub fn bitnuc_selftime_small(op: c_int, n: usize, iters: usize) -> f64;
 }

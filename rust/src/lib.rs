@@ -296,6 +296,29 @@ pub fn kmer_hdist_count_multi_packed(words: &[u64], n: usize, k: usize, queries:
     if st == ffi::BITNUC_OK { Ok(counts) } else { Err(to_err(&e)) }
 }
 
+/// The best match per query in one pass: `(pos, dist)` with `dist[q]` = the smallest Hamming distance of a window of `reference` to `queries[q]` and
+/// `pos[q]` = the leftmost window that attains it (no windows: `u64::MAX` / `0xFF`).
+pub fn kmer_hdist_best(reference: &[u8], k: usize, queries: &[u64]) -> Result<(Vec<u64>, Vec<u8>), NucleotideError> {
+    let mut pos = vec![0u64; queries.len()];
+    let mut dist = vec![0u8; queries.len()];
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_hdist_best(c, reference.as_ptr(), reference.len(), k, queries.as_ptr(), queries.len(), pos.as_mut_ptr(), dist.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok((pos, dist)) } else { Err(to_err(&e)) }
+}
+
+/// `kmer_hdist_best` of the packed sequence `words` holding `n` bases, without decoding it.
+pub fn kmer_hdist_best_packed(words: &[u64], n: usize, k: usize, queries: &[u64]) -> Result<(Vec<u64>, Vec<u8>), NucleotideError> {
+    let mut pos = vec![0u64; queries.len()];
+    let mut dist = vec![0u8; queries.len()];
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_hdist_best_packed(c, words.as_ptr(), words.len(), n, k, queries.as_ptr(), queries.len(), pos.as_mut_ptr(), dist.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok((pos, dist)) } else { Err(to_err(&e)) }
+}
+
 /// `for s in seqs { encode(s, &mut ebuf)? }` in one launch: sequence i =
 /// `seq[offsets[i]..offsets[i+1]]`; returns (concatenated words, word_offsets).
 pub fn encode_batch(seq: &[u8], offsets: &[u64]) -> Result<(Vec<u64>, Vec<u64>), NucleotideError> {
