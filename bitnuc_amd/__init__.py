@@ -9,10 +9,10 @@ Layout
 """
 from .api import (BackendError, BatchPlan, Comm, CommGroup, Context, NucleotideError, as_2bit, as_2bit_batch, batch_shard_ranges, decode,
                   default_context, encode, encode_alloc, from_2bit, from_2bit_alloc, hdist,
-                  hdist_scalar, kmer_hdist_scan, kmer_hdist_scan_packed, split_packed)
+                  hdist_scalar, kmer_hdist_scan, kmer_hdist_scan_packed, pattern_from_2bit, pattern_from_iupac, split_packed)
 
 from .sequence import PackedSequence
 
 __all__ = ["PackedSequence", "BatchPlan", "Comm", "CommGroup", "BackendError", "Context", "NucleotideError", "as_2bit", "as_2bit_batch", "batch_shard_ranges", "decode",
            "default_context", "encode", "encode_alloc", "from_2bit", "from_2bit_alloc", "hdist",
-           "hdist_scalar", "kmer_hdist_scan", "kmer_hdist_scan_packed", "split_packed"]
+           "hdist_scalar", "kmer_hdist_scan", "kmer_hdist_scan_packed", "pattern_from_2bit", "pattern_from_iupac", "split_packed"]

@@ -67,6 +67,20 @@ SIGNATURES = {
     "bitnuc_kmer_hdist_best_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _ERR]),
     "bitnuc_kmer_hdist_best": (C.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _ERR]),
     "bitnuc_kmer_hdist_best_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _ERR]),
+    "bitnuc_pattern_from_iupac": (C.c_int, [_P, _SZ, _P, _ERR]),
+    "bitnuc_pattern_from_2bit": (C.c_int, [_U64, _SZ, _P, _ERR]),
+    "bitnuc_kmer_pattern_count_multi_async": (C.c_int, [_P, _P, _SZ, _SZ, _P, _P, _SZ, _P, _ERR]),
+    "bitnuc_kmer_pattern_count_multi_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _P, _SZ, _P, _ERR]),
+    "bitnuc_kmer_pattern_count_multi": (C.c_int, [_P, _P, _SZ, _SZ, _P, _P, _SZ, _P, _ERR]),
+    "bitnuc_kmer_pattern_count_multi_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _P, _SZ, _P, _ERR]),
+    "bitnuc_kmer_pattern_best_async": (C.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _ERR]),
+    "bitnuc_kmer_pattern_best_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _ERR]),
+    "bitnuc_kmer_pattern_best": (C.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _ERR]),
+    "bitnuc_kmer_pattern_best_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _ERR]),
+    "bitnuc_kmer_pattern_hits_async": (C.c_int, [_P, _P, _SZ, _SZ, _P, C.c_uint, _P, _P, _SZ, _P, _ERR]),
+    "bitnuc_kmer_pattern_hits_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, C.c_uint, _P, _P, _SZ, _P, _ERR]),
+    "bitnuc_kmer_pattern_hits": (C.c_int, [_P, _P, _SZ, _SZ, _P, C.c_uint, _P, _P, _SZ, C.POINTER(_U64), _ERR]),
+    "bitnuc_kmer_pattern_hits_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, C.c_uint, _P, _P, _SZ, C.POINTER(_U64), _ERR]),
     "bitnuc_hdist_dev": (C.c_int, [_P, _P, _SZ, _P, _SZ, _SZ, _P, _ERR]),
     "bitnuc_batch_word_offsets_dev": (C.c_int, [_P, _P, _SZ, _P, C.POINTER(_SZ), _ERR]),
     "bitnuc_encode_batch_dev": (C.c_int, [_P, _P, _P, _P, _SZ, _SZ, _P, _ERR]),

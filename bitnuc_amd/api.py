@@ -383,6 +383,77 @@ class Context:
         w = _as_u64(words)
         return self._best(self._lib.bitnuc_kmer_hdist_best_packed, (_ptr(w), w.size, int(n_bases), int(k)), queries)
 
+    # -- pattern queries: a set of bases per position (bitnuc_pattern) -------------------------
+    @staticmethod
+    def _patterns(patterns, k):
+        """(Q, 4) np.uint32 from a (Q, 4) / (4,) uint32 array, one IUPAC string or a list of IUPAC strings of length k"""
+        if isinstance(patterns, (str, bytes)):
+            patterns = [patterns]
+        if isinstance(patterns, (list, tuple)) and patterns and all(isinstance(x, (str, bytes)) for x in patterns):
+            for x in patterns:
+                if len(x) != int(k):
+                    raise ValueError(f"an IUPAC pattern of {len(x)} letters for k = {k}")
+            return np.ascontiguousarray(np.stack([pattern_from_iupac(x) for x in patterns]))
+        p = np.ascontiguousarray(np.asarray(patterns, dtype=np.uint32).reshape(-1, 4))
+        return p
+
+    def kmer_pattern_count_multi(self, ref, k, patterns, taus):
+        """counts[q] = the number of windows j of `ref` with pdist(j) = #{i < k : ref[j+i] not in S_i of patterns[q]} <= taus[q] -> np.uint64.
+        patterns: a (Q, 4) np.uint32 array (pattern_from_iupac / pattern_from_2bit) or a list of IUPAC strings of length k."""
+        s = _as_u8(ref)
+        p = self._patterns(patterns, k)
+        _, t = self._multi_args(np.zeros(p.shape[0], dtype=np.uint64), taus)
+        out = np.empty(p.shape[0], dtype=np.uint64)
+        err = L.BitnucErr()
+        if self._lib.bitnuc_kmer_pattern_count_multi(self._h, _ptr(s), s.size, int(k), _ptr(p), _ptr(t), p.shape[0], _ptr(out), C.byref(err)) != L.OK:
+            _raise(err)
+        return out
+
+    def kmer_pattern_count_multi_packed(self, words, n_bases, k, patterns, taus):
+        """kmer_pattern_count_multi of the packed sequence `words` holding `n_bases` bases, without decoding it."""
+        w = _as_u64(words)
+        p = self._patterns(patterns, k)
+        _, t = self._multi_args(np.zeros(p.shape[0], dtype=np.uint64), taus)
+        out = np.empty(p.shape[0], dtype=np.uint64)
+        err = L.BitnucErr()
+        if self._lib.bitnuc_kmer_pattern_count_multi_packed(self._h, _ptr(w), w.size, int(n_bases), int(k), _ptr(p), _ptr(t), p.shape[0], _ptr(out),
+                                                            C.byref(err)) != L.OK:
+            _raise(err)
+        return out
+
+    def _pattern_best(self, fn, head, patterns, k):
+        p = self._patterns(patterns, k)
+        pos = np.empty(p.shape[0], dtype=np.uint64)
+        dist = np.empty(p.shape[0], dtype=np.uint8)
+        err = L.BitnucErr()
+        if fn(self._h, *head, _ptr(p), p.shape[0], _ptr(pos), _ptr(dist), C.byref(err)) != L.OK:
+            _raise(err)
+        return pos, dist
+
+    def kmer_pattern_best(self, ref, k, patterns):
+        """The best match per pattern in one pass: (pos, dist) with dist[q] = the smallest pdist of a window of `ref` under patterns[q] (np.uint8) and
+        pos[q] = the leftmost window that attains it (np.uint64); without windows every pos is 2^64 - 1 and every dist 255."""
+        s = _as_u8(ref)
+        return self._pattern_best(self._lib.bitnuc_kmer_pattern_best, (_ptr(s), s.size, int(k)), patterns, k)
+
+    def kmer_pattern_best_packed(self, words, n_bases, k, patterns):
+        """kmer_pattern_best of the packed sequence `words` holding `n_bases` bases, without decoding it."""
+        w = _as_u64(words)
+        return self._pattern_best(self._lib.bitnuc_kmer_pattern_best_packed, (_ptr(w), w.size, int(n_bases), int(k)), patterns, k)
+
+    def kmer_pattern_hits(self, ref, k, pattern, tau, with_dist=False):
+        """Positions (np.uint64, ascending) of the windows of `ref` with pdist <= tau under the pattern (a (4,) np.uint32 array or an IUPAC string);
+        with_dist: (positions, np.uint8 distances)."""
+        s = _as_u8(ref)
+        p = self._patterns(pattern, k)[:1]
+        return self._hits(self._lib.bitnuc_kmer_pattern_hits, (_ptr(s), s.size, int(k), _ptr(p), int(tau)), with_dist)
+
+    def kmer_pattern_hits_packed(self, words, n_bases, k, pattern, tau, with_dist=False):
+        """kmer_pattern_hits of the packed sequence `words` holding `n_bases` bases, without decoding it."""
+        w = _as_u64(words)
+        p = self._patterns(pattern, k)[:1]
+        return self._hits(self._lib.bitnuc_kmer_pattern_hits_packed, (_ptr(w), w.size, int(n_bases), int(k), _ptr(p), int(tau)), with_dist)
+
     # -- analysis on packed words (src/utils/analysis.rs, hamming/scalar.rs) ------------------
     def base_counts(self, words, n_bases):
         """[A, C, G, T] counts of a packed sequence (BaseCount::base_counts, analysis.rs:23-39)."""
@@ -624,6 +695,41 @@ class Context:
         self._call_dev(self._lib.bitnuc_kmer_hdist_best_packed_async, _dev_ptr(d_words), int(n_words), int(n), int(k), _dev_ptr(d_queries), int(n_queries),
                        _dev_ptr(d_pos), _dev_ptr(d_dist))
 
+    # the pattern twins: d_patterns holds n_queries bitnuc_pattern (16 bytes each, 4-byte aligned) in device memory; the hit lists take their one
+    # pattern from the host (a (4,) np.uint32 array)
+    def kmer_pattern_count_multi_async(self, d_ref, n, k, d_patterns, d_taus, n_queries, d_counts):
+        """d_counts[q] (u64) = windows with pdist <= d_taus[q] (u32) under d_patterns[q].  Asynchronous on the context's stream, as the _dev calls."""
+        self._call_dev(self._lib.bitnuc_kmer_pattern_count_multi_async, _dev_ptr(d_ref), int(n), int(k), _dev_ptr(d_patterns), _dev_ptr(d_taus), int(n_queries),
+                       _dev_ptr(d_counts))
+
+    def kmer_pattern_count_multi_packed_async(self, d_words, n_words, n, k, d_patterns, d_taus, n_queries, d_counts):
+        """The multi-pattern count on packed words in device memory (8-byte aligned)."""
+        self._call_dev(self._lib.bitnuc_kmer_pattern_count_multi_packed_async, _dev_ptr(d_words), int(n_words), int(n), int(k), _dev_ptr(d_patterns),
+                       _dev_ptr(d_taus), int(n_queries), _dev_ptr(d_counts))
+
+    def kmer_pattern_best_async(self, d_ref, n, k, d_patterns, n_queries, d_pos, d_dist):
+        """d_dist[q] (u8) = the smallest pdist of a window under d_patterns[q], d_pos[q] (u64) = the leftmost window that attains it."""
+        self._call_dev(self._lib.bitnuc_kmer_pattern_best_async, _dev_ptr(d_ref), int(n), int(k), _dev_ptr(d_patterns), int(n_queries), _dev_ptr(d_pos),
+                       _dev_ptr(d_dist))
+
+    def kmer_pattern_best_packed_async(self, d_words, n_words, n, k, d_patterns, n_queries, d_pos, d_dist):
+        """The best match per pattern on packed words in device memory (8-byte aligned)."""
+        self._call_dev(self._lib.bitnuc_kmer_pattern_best_packed_async, _dev_ptr(d_words), int(n_words), int(n), int(k), _dev_ptr(d_patterns), int(n_queries),
+                       _dev_ptr(d_pos), _dev_ptr(d_dist))
+
+    def kmer_pattern_hits_async(self, d_ref, n, k, pattern, tau, d_pos, d_hit_dist, cap, d_n_hits):
+        """The positions of the windows with pdist <= tau -> d_pos[0 .. min(cap, total)) (u64, ascending), their distances at d_hit_dist (None: not
+        written), total -> *d_n_hits (u64).  pattern: host memory ((4,) np.uint32) or None (the library refuses it)."""
+        p = None if pattern is None else np.ascontiguousarray(np.asarray(pattern, dtype=np.uint32).reshape(4))
+        self._call_dev(self._lib.bitnuc_kmer_pattern_hits_async, _dev_ptr(d_ref), int(n), int(k), None if p is None else _ptr(p), int(tau), _dev_ptr(d_pos),
+                       _dev_ptr(d_hit_dist), int(cap), _dev_ptr(d_n_hits))
+
+    def kmer_pattern_hits_packed_async(self, d_words, n_words, n, k, pattern, tau, d_pos, d_hit_dist, cap, d_n_hits):
+        """The pattern hit list on packed words in device memory (8-byte aligned)."""
+        p = None if pattern is None else np.ascontiguousarray(np.asarray(pattern, dtype=np.uint32).reshape(4))
+        self._call_dev(self._lib.bitnuc_kmer_pattern_hits_packed_async, _dev_ptr(d_words), int(n_words), int(n), int(k), None if p is None else _ptr(p), int(tau),
+                       _dev_ptr(d_pos), _dev_ptr(d_hit_dist), int(cap), _dev_ptr(d_n_hits))
+
     def hdist_dev(self, d_a, na, d_b, nb, n_bases, d_result):
         self._call_dev(self._lib.bitnuc_hdist_dev, _dev_ptr(d_a), int(na), _dev_ptr(d_b), int(nb), int(n_bases), _dev_ptr(d_result))
 
@@ -850,6 +956,27 @@ def peer_link_probe(src_device, dst_devices, nbytes=256 << 20, reps=3, lib_path=
 
 # ---- module-level functions with the reference's names (default context, device 0) ----------
 _default = None
+
+
+def pattern_from_iupac(letters, lib_path=None):
+    """A pattern query from IUPAC letters (ACGTU RYSWKM BDHV N, either case; at most 32) -> (4,) np.uint32: allow[c] bit i set <=> base code c
+    (A 0, C 1, G 2, T 3) matches at position i.  Host code, no context."""
+    b = np.frombuffer(letters.encode() if isinstance(letters, str) else bytes(letters), dtype=np.uint8)
+    out = np.zeros(4, dtype=np.uint32)
+    err = L.BitnucErr()
+    if L.load(lib_path).bitnuc_pattern_from_iupac(_ptr(b) if b.size else None, b.size, _ptr(out), C.byref(err)) != L.OK:
+        _raise(err)
+    return out
+
+
+def pattern_from_2bit(query, k, lib_path=None):
+    """The pattern of singletons of a packed exact query of k bases -> (4,) np.uint32: it makes every pattern entry point compute what its exact twin
+    computes for `query`.  Host code, no context."""
+    out = np.zeros(4, dtype=np.uint32)
+    err = L.BitnucErr()
+    if L.load(lib_path).bitnuc_pattern_from_2bit(C.c_uint64(int(query)), int(k), _ptr(out), C.byref(err)) != L.OK:
+        _raise(err)
+    return out
 
 
 def default_context():

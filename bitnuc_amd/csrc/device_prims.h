@@ -79,6 +79,25 @@ __device__ __forceinline__ uint32_t word_distance(unsigned long long w, unsigned
     return (uint32_t)__builtin_popcountll((x | (x >> 1)) & 0x5555555555555555ull);
 }
 
+// A window against a PATTERN (position i accepts a set of bases: allow[c] bit i set <=> code c matches there, bitnuc_pattern): de-interleave the
+// window's 2-bit word into its two bit-planes ONCE per window (bit i of lo / hi = the low / high code bit of base i), then per pattern the positions
+// whose base is in the set are four ANDs of the planes with the pattern's masks, and pdist = popcount(ones(k) & ~match).
+struct WindowPlanes { uint32_t lo, hi; };
+__device__ __forceinline__ uint32_t even_bits(unsigned long long x) { // bits 0, 2, 4, ... of x -> bits 0, 1, 2, ...
+    x &= 0x5555555555555555ull;
+    x = (x | (x >> 1)) & 0x3333333333333333ull;
+    x = (x | (x >> 2)) & 0x0F0F0F0F0F0F0F0Full;
+    x = (x | (x >> 4)) & 0x00FF00FF00FF00FFull;
+    x = (x | (x >> 8)) & 0x0000FFFF0000FFFFull;
+    return (uint32_t)(x | (x >> 16));
+}
+__device__ __forceinline__ WindowPlanes window_planes(unsigned long long w) { return WindowPlanes{even_bits(w), even_bits(w >> 1)}; }
+__device__ __forceinline__ uint32_t kmer_ones(unsigned k) { return k >= 32 ? ~0u : ((1u << k) - 1u); }
+__device__ __forceinline__ uint32_t pattern_distance(WindowPlanes p, uint32_t a, uint32_t c, uint32_t g, uint32_t t, uint32_t ones) {
+    const uint32_t match = (~p.hi & ~p.lo & a) | (~p.hi & p.lo & c) | (p.hi & ~p.lo & g) | (p.hi & p.lo & t);
+    return (uint32_t)__builtin_popcount(ones & ~match);
+}
+
 // as_2bit(ref[j .. j+k]) by byte loads (packing/naive.rs:3-20); `latch`: report the window's first invalid byte
 __device__ __forceinline__ unsigned long long ascii_window_word(const uint8_t *__restrict__ ref, unsigned long long j, unsigned k, bool latch,
                                                                 unsigned long long *__restrict__ slot) {

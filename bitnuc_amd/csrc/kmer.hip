@@ -14,6 +14,7 @@
 #include "scan_hits_host.h"
 #include "scan_multi_host.h"
 #include "scan_best_host.h"
+#include "pattern_host.h"
 #include "host_word.h"
 #include "host_pipe.h"
 
@@ -124,8 +125,19 @@ inline unsigned ascii_skip(const uint8_t *ref) { return (unsigned)((16 - (reinte
 // packed words, 8-byte aligned (checked by the callers): words at 8 mod 16 start the rounds one word later
 inline unsigned packed_skip(const uint64_t *words) { return aligned16(words) ? 0u : 32u; }
 
+// ---- the two kinds of query of the hit lists, the multi-query count and the best match: an exact query (uint64_t) or a pattern (bitnuc_pattern).  The
+// launchers and host loops below are templates over the ABI's type HQ; the kernels take its device twin (QueryKind, scan_mfma_device.h).
+static_assert(sizeof(bitnuc_pattern) == sizeof(PatternSets) && alignof(bitnuc_pattern) == alignof(PatternSets), "bitnuc_pattern is PatternSets");
+template <class HQ> struct DevQuery;
+template <> struct DevQuery<uint64_t> { using type = unsigned long long; };
+template <> struct DevQuery<bitnuc_pattern> { using type = PatternSets; };
+template <class HQ> const typename DevQuery<HQ>::type *dev_queries(const HQ *q) { return reinterpret_cast<const typename DevQuery<HQ>::type *>(q); }
+inline unsigned long long dev_query(uint64_t q) { return q; }
+inline PatternSets dev_query(const bitnuc_pattern &p) { return *dev_queries(&p); }
+
 // the four-channel table of the distance bytes (the scan, the hit lists): no threshold, the accumulators start at the 2^23 pack bias
-inline CountMfmaTable scan_seg_table(uint64_t query, size_t k) {
+template <class DQ>
+inline CountMfmaTable scan_seg_table(const DQ &query, size_t k) {
     CountMfmaTable ct;
     count_mfma_table(query, k, &ct);
     for (int j = 0; j < 4; ++j) ct.c[j] = kPackBias;
@@ -247,7 +259,8 @@ int check_packed(const void *words, size_t n_words, size_t n, size_t k, bool *no
 // ---- the hit lists (scan_hits_device.h): count pass, scan of the per-trip counts, emit pass.  Context scratch 7 holds the counts (one u32 per trip, the
 // head's and the tail's) and the tiles' offsets; a launch recorded into a hipGraph keeps it (ensure_scratch).  cap == 0 skips the emit pass.  pos_base is added to every
 // position (the host forms' chunk offset).
-struct HitsArgs { uint64_t query; unsigned tau; unsigned long long *pos; uint8_t *hd; unsigned long long cap, *n_hits, pos_base; };
+template <class HQ> struct HitsArgsT { HQ query; unsigned tau; unsigned long long *pos; uint8_t *hd; unsigned long long cap, *n_hits, pos_base; };
+using HitsArgs = HitsArgsT<uint64_t>;
 
 int hits_scratch(bitnuc_ctx *c, unsigned long long ntr, unsigned **counts, unsigned long long **tiles, bitnuc_err *err) {
     const unsigned long long ntiles = (ntr + kHitsTile - 1) / kHitsTile, cbytes = (4 * ntr + 255) & ~255ull;
@@ -265,32 +278,38 @@ hipError_t hits_scan(bitnuc_ctx *c, unsigned *counts, unsigned long long ntr, un
 }
 
 // d_ref at any alignment (ascii_skip): the windows before the rounds are the first workgroup's
-int launch_hits(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const HitsArgs &a, unsigned long long *slot, bitnuc_err *err) {
+template <class HQ>
+int launch_hits(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const HitsArgsT<HQ> &a, unsigned long long *slot, bitnuc_err *err) {
+    using DQ = typename DevQuery<HQ>::type;
+    const DQ query = dev_query(a.query);
     const unsigned skip = ascii_skip(ref);
     const unsigned long long ntr = hits_trips(n, skip) + 2;
     unsigned *counts;
     unsigned long long *tiles;
     if (int st = hits_scratch(c, ntr, &counts, &tiles, err)) return st;
-    const CountMfmaTable ct = scan_seg_table(a.query, k);
-    kmer_hits_mfma_kernel<false><<<(unsigned)ntr, 64, 0, c->stream>>>(ref, n, skip, (unsigned)k, a.query, a.tau, counts, nullptr, nullptr, nullptr, 0, 0, slot, ct);
+    const CountMfmaTable ct = scan_seg_table(query, k);
+    kmer_hits_mfma_kernel<false, DQ><<<(unsigned)ntr, 64, 0, c->stream>>>(ref, n, skip, (unsigned)k, query, a.tau, counts, nullptr, nullptr, nullptr, 0, 0, slot, ct);
     HIPCHK(hits_scan(c, counts, ntr, tiles, a.n_hits));
-    if (a.cap) kmer_hits_mfma_kernel<true><<<(unsigned)ntr, 64, 0, c->stream>>>(ref, n, skip, (unsigned)k, a.query, a.tau, counts, tiles, a.pos, a.hd, a.cap, a.pos_base, slot, ct);
+    if (a.cap) kmer_hits_mfma_kernel<true, DQ><<<(unsigned)ntr, 64, 0, c->stream>>>(ref, n, skip, (unsigned)k, query, a.tau, counts, tiles, a.pos, a.hd, a.cap, a.pos_base, slot, ct);
     HIPCHK(hipGetLastError());
     return BITNUC_OK;
 }
 
 // d_words 8-byte aligned (packed_skip)
-int launch_hits_packed(bitnuc_ctx *c, const uint64_t *words, size_t n, size_t k, const HitsArgs &a, bitnuc_err *err) {
+template <class HQ>
+int launch_hits_packed(bitnuc_ctx *c, const uint64_t *words, size_t n, size_t k, const HitsArgsT<HQ> &a, bitnuc_err *err) {
+    using DQ = typename DevQuery<HQ>::type;
+    const DQ query = dev_query(a.query);
     const unsigned skip = packed_skip(words);
     const unsigned long long ntr = hits_trips(n, skip) + 2;
     unsigned *counts;
     unsigned long long *tiles;
     if (int st = hits_scratch(c, ntr, &counts, &tiles, err)) return st;
     PackedScanTable t;
-    scan_packed_table(a.query, k, &t);
-    packed_hits_mfma_kernel<false><<<(unsigned)ntr, 64, 0, c->stream>>>(words, n, skip, (unsigned)k, a.query, a.tau, counts, nullptr, nullptr, nullptr, 0, 0, t);
+    scan_packed_table(query, k, &t);
+    packed_hits_mfma_kernel<false, DQ><<<(unsigned)ntr, 64, 0, c->stream>>>(words, n, skip, (unsigned)k, query, a.tau, counts, nullptr, nullptr, nullptr, 0, 0, t);
     HIPCHK(hits_scan(c, counts, ntr, tiles, a.n_hits));
-    if (a.cap) packed_hits_mfma_kernel<true><<<(unsigned)ntr, 64, 0, c->stream>>>(words, n, skip, (unsigned)k, a.query, a.tau, counts, tiles, a.pos, a.hd, a.cap, a.pos_base, t);
+    if (a.cap) packed_hits_mfma_kernel<true, DQ><<<(unsigned)ntr, 64, 0, c->stream>>>(words, n, skip, (unsigned)k, query, a.tau, counts, tiles, a.pos, a.hd, a.cap, a.pos_base, t);
     HIPCHK(hipGetLastError());
     return BITNUC_OK;
 }
@@ -305,8 +324,8 @@ int check_hits_out(const void *pos, size_t cap, const void *n_hits, bitnuc_err *
 // The host forms' chunk loop: the input chunk in scratch 0, the chunk's positions / distances in scratch 1 / 2 (at most the cap still open), its
 // count in scratch 3.  `launch(i0, m, a)` runs the windows [i0, i0 + m) with a's outputs; positions come back shifted by i0.  Stops at the first
 // failing chunk (drain: its first invalid byte, relative to the whole sequence through the slot's base).
-template <class Launch>
-int hits_host_loop(bitnuc_ctx *c, size_t nwin, size_t per, unsigned tau, uint64_t query, uint64_t *pos, uint8_t *hit_dist, size_t cap, uint64_t *n_hits,
+template <class HQ, class Launch>
+int hits_host_loop(bitnuc_ctx *c, size_t nwin, size_t per, unsigned tau, const HQ &query, uint64_t *pos, uint8_t *hit_dist, size_t cap, uint64_t *n_hits,
                    bitnuc_err *err, Launch launch) {
     const size_t pcap = cap < per ? cap : per;
     if (pcap) {
@@ -318,7 +337,7 @@ int hits_host_loop(bitnuc_ctx *c, size_t nwin, size_t per, unsigned tau, uint64_
     for (size_t i0 = 0; i0 < nwin; i0 += per) {
         const size_t m = nwin - i0 < per ? nwin - i0 : per;
         const size_t open = total < cap ? cap - total : 0, ccap = open < m ? open : m;
-        const HitsArgs a{query, tau, reinterpret_cast<unsigned long long *>(c->scratch[1]), hit_dist ? c->scratch[2] : nullptr, ccap,
+        const HitsArgsT<HQ> a{query, tau, reinterpret_cast<unsigned long long *>(c->scratch[1]), hit_dist ? c->scratch[2] : nullptr, ccap,
                          reinterpret_cast<unsigned long long *>(c->scratch[3]), i0};
         if (int st = launch(i0, m, a)) return st;
         uint64_t part = 0;
@@ -342,14 +361,15 @@ int hits_host_loop(bitnuc_ctx *c, size_t nwin, size_t per, unsigned tau, uint64_
 // same stream, then every workgroup adds its per-query sums.  The grid: kMultiGrid workgroups per CU at most (one fits a CU's LDS) x the query blocks.
 constexpr int kMultiGrid = 1;
 
-struct MultiArgs { const uint64_t *queries; const uint32_t *taus; size_t nq; unsigned long long *counts; };
+template <class HQ> struct MultiArgsT { const HQ *queries; const uint32_t *taus; size_t nq; unsigned long long *counts; };
+using MultiArgs = MultiArgsT<uint64_t>;
 
-template <bool PACKED>
-int multi_setup(bitnuc_ctx *c, size_t k, const MultiArgs &a, unsigned long long rounds, const Count3MfmaTable **tabs, dim3 *grid, bitnuc_err *err) {
+template <bool PACKED, class HQ>
+int multi_setup(bitnuc_ctx *c, size_t k, const MultiArgsT<HQ> &a, unsigned long long rounds, const Count3MfmaTable **tabs, dim3 *grid, bitnuc_err *err) {
     if (int st = ensure_scratch(c, 8, a.nq * sizeof(Count3MfmaTable), err)) return st;
     Count3MfmaTable *t = reinterpret_cast<Count3MfmaTable *>(c->scratch[8]);
     HIPCHK(hipMemsetAsync(a.counts, 0, a.nq * sizeof(uint64_t), c->stream));
-    count3_tables_kernel<PACKED><<<(unsigned)a.nq, 64, 0, c->stream>>>(reinterpret_cast<const unsigned long long *>(a.queries), a.taus, (unsigned)k, t);
+    count3_tables_kernel<PACKED><<<(unsigned)a.nq, 64, 0, c->stream>>>(dev_queries(a.queries), a.taus, (unsigned)k, t);
     HIPCHK(hipGetLastError());
     *tabs = t;
     *grid = dim3(bounded_grid(c, rounds, (kMultiBlock / 64) * kMultiRounds, kMultiGrid), (unsigned)((a.nq + kMultiQB - 1) / kMultiQB), 1);
@@ -357,35 +377,37 @@ int multi_setup(bitnuc_ctx *c, size_t k, const MultiArgs &a, unsigned long long 
 }
 
 // d_ref at any alignment (ascii_skip)
-int launch_count_multi(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const MultiArgs &a, unsigned long long *slot, bitnuc_err *err) {
+template <class HQ>
+int launch_count_multi(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const MultiArgsT<HQ> &a, unsigned long long *slot, bitnuc_err *err) {
     const unsigned skip = ascii_skip(ref);
     const Count3MfmaTable *tabs;
     dim3 grid;
     if (int st = multi_setup<false>(c, k, a, scan_rounds(n, skip), &tabs, &grid, err)) return st;
-    kmer_count3_multi_kernel<kMultiRounds><<<grid, kMultiBlock, 0, c->stream>>>(ref, n, skip, (unsigned)k, reinterpret_cast<const unsigned long long *>(a.queries),
-                                                                               a.taus, (unsigned)a.nq, tabs, a.counts, slot);
+    kmer_count3_multi_kernel<kMultiRounds><<<grid, kMultiBlock, 0, c->stream>>>(ref, n, skip, (unsigned)k, dev_queries(a.queries), a.taus, (unsigned)a.nq, tabs,
+                                                                               a.counts, slot);
     HIPCHK(hipGetLastError());
     return BITNUC_OK;
 }
 
 // d_words 8-byte aligned (packed_skip)
-int launch_count_multi_packed(bitnuc_ctx *c, const uint64_t *words, size_t n, size_t k, const MultiArgs &a, bitnuc_err *err) {
+template <class HQ>
+int launch_count_multi_packed(bitnuc_ctx *c, const uint64_t *words, size_t n, size_t k, const MultiArgsT<HQ> &a, bitnuc_err *err) {
     const unsigned skip = packed_skip(words);
     const Count3MfmaTable *tabs;
     dim3 grid;
     if (int st = multi_setup<true>(c, k, a, scan_rounds(n, skip), &tabs, &grid, err)) return st;
-    packed_count3_multi_kernel<<<grid, kMultiBlock, 0, c->stream>>>(words, n, skip, (unsigned)k, reinterpret_cast<const unsigned long long *>(a.queries), a.taus,
-                                                                    (unsigned)a.nq, tabs, a.counts);
+    packed_count3_multi_kernel<<<grid, kMultiBlock, 0, c->stream>>>(words, n, skip, (unsigned)k, dev_queries(a.queries), a.taus, (unsigned)a.nq, tabs, a.counts);
     HIPCHK(hipGetLastError());
     return BITNUC_OK;
 }
 
 // the multi-query calls' checks 4 - 6 (after ctx, k and the packed word count): n_queries == 0 -> OK (*none), too many queries, the three arrays
-int check_multi(const void *queries, const void *taus, size_t nq, const void *counts, bool *none, bitnuc_err *err) {
+// (qmask: 7 for exact queries, 3 for patterns)
+int check_multi(const void *queries, const void *taus, size_t nq, const void *counts, bool *none, bitnuc_err *err, uintptr_t qmask = 7) {
     *none = nq == 0;
     if (*none) return BITNUC_OK;
     if (nq > BITNUC_MAX_QUERIES) return fail(err, BITNUC_UNSUPPORTED, nq);
-    if (!counts || (reinterpret_cast<uintptr_t>(counts) & 7) || !queries || (reinterpret_cast<uintptr_t>(queries) & 7) || !taus ||
+    if (!counts || (reinterpret_cast<uintptr_t>(counts) & 7) || !queries || (reinterpret_cast<uintptr_t>(queries) & qmask) || !taus ||
         (reinterpret_cast<uintptr_t>(taus) & 3))
         return fail(err, BITNUC_UNSUPPORTED);
     return BITNUC_OK;
@@ -396,15 +418,20 @@ inline size_t multi_work(size_t nwin, size_t nq) { return nwin > (size_t)-1 / nq
 
 // The host forms' chunk loop: queries and thresholds copied once into scratch 2, the chunk's counts in scratch 1; `launch(i0, a)` runs the chunk of
 // windows starting at i0 with a's device arrays.  Sums per query; stops at the first failing chunk (drain: its first invalid byte).
-template <class Launch>
-int multi_host_loop(bitnuc_ctx *c, size_t nwin, size_t per, const uint64_t *queries, const uint32_t *taus, size_t nq, uint64_t *counts, bitnuc_err *err,
+template <class HQ, class Launch>
+int multi_host_loop(bitnuc_ctx *c, size_t nwin, size_t per, const HQ *queries, const uint32_t *taus, size_t nq, uint64_t *counts, bitnuc_err *err,
                     Launch launch) {
+    constexpr size_t qb = sizeof(HQ); // 8: exact queries, 16: patterns
     if (int st = ensure_scratch(c, 1, nq * 8, err)) return st;
-    if (int st = ensure_scratch(c, 2, nq * 12, err)) return st;
-    HIPCHK(hipMemcpyAsync(c->scratch[2], queries, nq * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->scratch[2] + nq * 8, taus, nq * 4, hipMemcpyHostToDevice, c->stream));
-    const MultiArgs a{reinterpret_cast<const uint64_t *>(c->scratch[2]), reinterpret_cast<const uint32_t *>(c->scratch[2] + nq * 8), nq,
-                      reinterpret_cast<unsigned long long *>(c->scratch[1])};
+    if constexpr (qb == 8) {
+        if (int st = ensure_scratch(c, 2, nq * 12, err)) return st;
+    } else {
+        if (int st = ensure_scratch(c, 2, nq * (qb + 4), err)) return st;
+    }
+    HIPCHK(hipMemcpyAsync(c->scratch[2], queries, nq * qb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->scratch[2] + nq * qb, taus, nq * 4, hipMemcpyHostToDevice, c->stream));
+    const MultiArgsT<HQ> a{reinterpret_cast<const HQ *>(c->scratch[2]), reinterpret_cast<const uint32_t *>(c->scratch[2] + nq * qb), nq,
+                           reinterpret_cast<unsigned long long *>(c->scratch[1])};
     std::vector<uint64_t> part(nq), total(nq, 0);
     for (size_t i0 = 0; i0 < nwin; i0 += per) {
         if (int st = launch(i0, a)) return st;
@@ -421,23 +448,25 @@ int multi_host_loop(bitnuc_ctx *c, size_t nwin, size_t per, const uint64_t *quer
 // tables (one BestTable per query, built in-stream from d_queries); a launch recorded into a hipGraph keeps it (ensure_scratch: warm up with the same
 // n_queries before capturing).  The keys are set to all-ones first in the same stream, every workgroup then takes its per-query minima into them and
 // best_finish_kernel writes pos[] / dist[].  The grid: the multi-query count's (one workgroup per CU at most x the query blocks).
-struct BestArgs { const uint64_t *queries; size_t nq; unsigned long long *pos; uint8_t *dist; };
+template <class HQ> struct BestArgsT { const HQ *queries; size_t nq; unsigned long long *pos; uint8_t *dist; };
+using BestArgs = BestArgsT<uint64_t>;
 
-template <bool PACKED>
-int best_setup(bitnuc_ctx *c, size_t k, const BestArgs &a, unsigned long long rounds, unsigned long long **keys, const BestTable **tabs, dim3 *grid, bitnuc_err *err) {
+template <bool PACKED, class HQ>
+int best_setup(bitnuc_ctx *c, size_t k, const BestArgsT<HQ> &a, unsigned long long rounds, unsigned long long **keys, const BestTable **tabs, dim3 *grid, bitnuc_err *err) {
     const size_t kbytes = (a.nq * 8 + 255) & ~(size_t)255;
     if (int st = ensure_scratch(c, 9, kbytes + a.nq * sizeof(BestTable), err)) return st;
     *keys = reinterpret_cast<unsigned long long *>(c->scratch[9]);
     BestTable *t = reinterpret_cast<BestTable *>(c->scratch[9] + kbytes);
     HIPCHK(hipMemsetAsync(*keys, 0xFF, a.nq * sizeof(uint64_t), c->stream));
-    best_tables_kernel<PACKED><<<(unsigned)a.nq, 64, 0, c->stream>>>(reinterpret_cast<const unsigned long long *>(a.queries), (unsigned)k, t);
+    best_tables_kernel<PACKED><<<(unsigned)a.nq, 64, 0, c->stream>>>(dev_queries(a.queries), (unsigned)k, t);
     HIPCHK(hipGetLastError());
     *tabs = t;
     *grid = dim3(bounded_grid(c, rounds, (kMultiBlock / 64) * kMultiRounds, kMultiGrid), (unsigned)((a.nq + kMultiQB - 1) / kMultiQB), 1);
     return BITNUC_OK;
 }
 
-int best_finish(bitnuc_ctx *c, const unsigned long long *keys, const BestArgs &a, bitnuc_err *err) {
+template <class HQ>
+int best_finish(bitnuc_ctx *c, const unsigned long long *keys, const BestArgsT<HQ> &a, bitnuc_err *err) {
     HIPCHK(hipGetLastError());
     best_finish_kernel<<<(unsigned)((a.nq + 255) / 256), 256, 0, c->stream>>>(keys, (unsigned)a.nq, a.pos, a.dist);
     HIPCHK(hipGetLastError());
@@ -445,35 +474,36 @@ int best_finish(bitnuc_ctx *c, const unsigned long long *keys, const BestArgs &a
 }
 
 // d_ref at any alignment (ascii_skip)
-int launch_best(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const BestArgs &a, unsigned long long *slot, bitnuc_err *err) {
+template <class HQ>
+int launch_best(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const BestArgsT<HQ> &a, unsigned long long *slot, bitnuc_err *err) {
     const unsigned skip = ascii_skip(ref);
     unsigned long long *keys;
     const BestTable *tabs;
     dim3 grid;
     if (int st = best_setup<false>(c, k, a, scan_rounds(n, skip), &keys, &tabs, &grid, err)) return st;
-    kmer_best_kernel<kMultiRounds><<<grid, kMultiBlock, 0, c->stream>>>(ref, n, skip, (unsigned)k, reinterpret_cast<const unsigned long long *>(a.queries),
-                                                                       (unsigned)a.nq, tabs, keys, slot);
+    kmer_best_kernel<kMultiRounds><<<grid, kMultiBlock, 0, c->stream>>>(ref, n, skip, (unsigned)k, dev_queries(a.queries), (unsigned)a.nq, tabs, keys, slot);
     return best_finish(c, keys, a, err);
 }
 
 // d_words 8-byte aligned (packed_skip)
-int launch_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t n, size_t k, const BestArgs &a, bitnuc_err *err) {
+template <class HQ>
+int launch_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t n, size_t k, const BestArgsT<HQ> &a, bitnuc_err *err) {
     const unsigned skip = packed_skip(words);
     unsigned long long *keys;
     const BestTable *tabs;
     dim3 grid;
     if (int st = best_setup<true>(c, k, a, scan_rounds(n, skip), &keys, &tabs, &grid, err)) return st;
-    packed_best_kernel<<<grid, kMultiBlock, 0, c->stream>>>(words, n, skip, (unsigned)k, reinterpret_cast<const unsigned long long *>(a.queries), (unsigned)a.nq, tabs,
-                                                            keys);
+    packed_best_kernel<<<grid, kMultiBlock, 0, c->stream>>>(words, n, skip, (unsigned)k, dev_queries(a.queries), (unsigned)a.nq, tabs, keys);
     return best_finish(c, keys, a, err);
 }
 
 // the best-match calls' checks 4 - 6 (after ctx, k and the packed word count): n_queries == 0 -> OK (*none), too many queries, the three arrays
-int check_best(const void *queries, size_t nq, const void *pos, const void *dist, bool *none, bitnuc_err *err) {
+// (qmask: 7 for exact queries, 3 for patterns)
+int check_best(const void *queries, size_t nq, const void *pos, const void *dist, bool *none, bitnuc_err *err, uintptr_t qmask = 7) {
     *none = nq == 0;
     if (*none) return BITNUC_OK;
     if (nq > BITNUC_MAX_QUERIES) return fail(err, BITNUC_UNSUPPORTED, nq);
-    if (!pos || (reinterpret_cast<uintptr_t>(pos) & 7) || !queries || (reinterpret_cast<uintptr_t>(queries) & 7) || !dist) return fail(err, BITNUC_UNSUPPORTED);
+    if (!pos || (reinterpret_cast<uintptr_t>(pos) & 7) || !queries || (reinterpret_cast<uintptr_t>(queries) & qmask) || !dist) return fail(err, BITNUC_UNSUPPORTED);
     return BITNUC_OK;
 }
 
@@ -487,13 +517,13 @@ int best_fill_dev(bitnuc_ctx *c, uint64_t *d_pos, uint8_t *d_dist, size_t nq, bi
 // The host forms' chunk loop: the queries copied once into scratch 2, the chunk's positions / distances in scratch 1 / 3; `launch(i0, a)` runs the chunk
 // of windows starting at i0 with a's device arrays.  The chunks' results merge by the lexicographic (dist, absolute pos) minimum; stops at the first
 // failing chunk (drain: its first invalid byte).
-template <class Launch>
-int best_host_loop(bitnuc_ctx *c, size_t nwin, size_t per, const uint64_t *queries, size_t nq, uint64_t *pos, uint8_t *dist, bitnuc_err *err, Launch launch) {
+template <class HQ, class Launch>
+int best_host_loop(bitnuc_ctx *c, size_t nwin, size_t per, const HQ *queries, size_t nq, uint64_t *pos, uint8_t *dist, bitnuc_err *err, Launch launch) {
     if (int st = ensure_scratch(c, 1, nq * 8, err)) return st;
-    if (int st = ensure_scratch(c, 2, nq * 8, err)) return st;
+    if (int st = ensure_scratch(c, 2, nq * sizeof(HQ), err)) return st;
     if (int st = ensure_scratch(c, 3, nq < 64 ? 64 : nq, err)) return st;
-    HIPCHK(hipMemcpyAsync(c->scratch[2], queries, nq * 8, hipMemcpyHostToDevice, c->stream));
-    const BestArgs a{reinterpret_cast<const uint64_t *>(c->scratch[2]), nq, reinterpret_cast<unsigned long long *>(c->scratch[1]), c->scratch[3]};
+    HIPCHK(hipMemcpyAsync(c->scratch[2], queries, nq * sizeof(HQ), hipMemcpyHostToDevice, c->stream));
+    const BestArgsT<HQ> a{reinterpret_cast<const HQ *>(c->scratch[2]), nq, reinterpret_cast<unsigned long long *>(c->scratch[1]), c->scratch[3]};
     std::vector<uint64_t> ppos(nq), bpos(nq, ~0ull);
     std::vector<uint8_t> pdist(nq), bdist(nq, 0xFF);
     for (size_t i0 = 0; i0 < nwin; i0 += per) {
@@ -1048,6 +1078,299 @@ int bitnuc_kmer_hdist_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t n
         const PackedChunk ch = packed_chunk(i0 / 32, n, k);
         HIPCHK(hipMemcpyAsync(c->scratch[0], words + ch.w0, ch.words * 8, hipMemcpyHostToDevice, c->stream));
         return launch_best_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), ch.bases, k, a, err);
+    });
+}
+
+// ---- pattern queries: a set of bases per position (bitnuc_pattern).  The twelve entry points below are the twins of the exact ones above: the same checks
+// in the same order, the same launchers, loops and kernels under the other query kind.
+int bitnuc_pattern_from_iupac(const uint8_t *letters, size_t k, bitnuc_pattern *out, bitnuc_err *err) {
+    clear_err(err);
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k); // before any letter is read
+    if (!out || (!letters && k)) return fail(err, BITNUC_UNSUPPORTED);
+    PatternSets p;
+    const long long bad = bitnuc_host::pattern_from_iupac(letters, k, &p);
+    if (bad >= 0) {
+        if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = letters[bad]; err->index = (uint64_t)bad; }
+        return BITNUC_INVALID_BASE;
+    }
+    memcpy(out, &p, sizeof p);
+    return BITNUC_OK;
+}
+
+int bitnuc_pattern_from_2bit(uint64_t query, size_t k, bitnuc_pattern *out, bitnuc_err *err) {
+    clear_err(err);
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    if (!out) return fail(err, BITNUC_UNSUPPORTED);
+    const PatternSets p = pattern_of_2bit(query, k);
+    memcpy(out, &p, sizeof p);
+    return BITNUC_OK;
+}
+
+int bitnuc_kmer_pattern_count_multi_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const bitnuc_pattern *d_patterns, const uint32_t *d_taus, size_t n_queries,
+                                          uint64_t *d_counts, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    bool none;
+    if (int st = check_multi(d_patterns, d_taus, n_queries, d_counts, &none, err, 3)) return st;
+    if (none) return BITNUC_OK;
+    DeviceGuard g(c->device);
+    if (k == 0 || n < k) { // no windows
+        HIPCHK(hipMemsetAsync(d_counts, 0, n_queries * sizeof(uint64_t), c->stream));
+        return BITNUC_OK;
+    }
+    if (!d_ref) return fail(err, BITNUC_UNSUPPORTED);
+    unsigned long long *slot;
+    if (int st = take_slot(c, 0, &slot, err)) return st;
+    return launch_count_multi(c, d_ref, n, k, MultiArgsT<bitnuc_pattern>{d_patterns, d_taus, n_queries, reinterpret_cast<unsigned long long *>(d_counts)}, slot, err);
+}
+
+int bitnuc_kmer_pattern_count_multi_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *d_patterns,
+                                                 const uint32_t *d_taus, size_t n_queries, uint64_t *d_counts, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
+    bool none;
+    if (int st = check_multi(d_patterns, d_taus, n_queries, d_counts, &none, err, 3)) return st;
+    if (none) return BITNUC_OK;
+    DeviceGuard g(c->device);
+    if (k == 0 || n < k) {
+        HIPCHK(hipMemsetAsync(d_counts, 0, n_queries * sizeof(uint64_t), c->stream));
+        return BITNUC_OK;
+    }
+    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    return launch_count_multi_packed(c, d_words, n, k, MultiArgsT<bitnuc_pattern>{d_patterns, d_taus, n_queries, reinterpret_cast<unsigned long long *>(d_counts)}, err);
+}
+
+int bitnuc_kmer_pattern_count_multi(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const bitnuc_pattern *patterns, const uint32_t *taus, size_t n_queries,
+                                    uint64_t *counts, bitnuc_err *err) {
+    clear_err(err);
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    bool none;
+    if (int st = check_multi(patterns, taus, n_queries, counts, &none, err, 3)) return st;
+    if (none) return BITNUC_OK;
+    if (k == 0 || n < k) { memset(counts, 0, n_queries * sizeof(uint64_t)); return BITNUC_OK; }
+    if (!ref) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, multi_work(n - k + 1, n_queries))) {
+        const long long bad = bitnuc_host::kmer_hdist_count_multi_small(ref, n, k, dev_queries(patterns), taus, n_queries, counts);
+        if (bad >= 0) {
+            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = ref[bad]; err->index = (uint64_t)bad; }
+            return BITNUC_INVALID_BASE;
+        }
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    // chunks of kHostChunk windows + their k - 1 halo bases
+    if (int st = ensure_scratch(c, 0, kHostChunk + 64, err)) return st;
+    const size_t nwin = n - k + 1;
+    return multi_host_loop(c, nwin, kHostChunk, patterns, taus, n_queries, counts, err, [&](size_t i0, const MultiArgsT<bitnuc_pattern> &a) {
+        const size_t m = nwin - i0 < kHostChunk ? nwin - i0 : kHostChunk;
+        HIPCHK(hipMemcpyAsync(c->scratch[0], ref + i0, m + k - 1, hipMemcpyHostToDevice, c->stream));
+        unsigned long long *slot;
+        if (int st = take_slot(c, i0, &slot, err)) return st;
+        return launch_count_multi(c, c->scratch[0], m + k - 1, k, a, slot, err);
+    });
+}
+
+int bitnuc_kmer_pattern_count_multi_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *patterns, const uint32_t *taus,
+                                           size_t n_queries, uint64_t *counts, bitnuc_err *err) {
+    clear_err(err);
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
+    bool none;
+    if (int st = check_multi(patterns, taus, n_queries, counts, &none, err, 3)) return st;
+    if (none) return BITNUC_OK;
+    if (k == 0 || n < k) { memset(counts, 0, n_queries * sizeof(uint64_t)); return BITNUC_OK; }
+    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, multi_work(n - k + 1, n_queries))) {
+        bitnuc_host::kmer_hdist_count_multi_packed_small(words, n, k, dev_queries(patterns), taus, n_queries, counts);
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    if (int st = ensure_scratch(c, 0, (kPackedChunkWords + 1) * 8, err)) return st;
+    // chunk w0 / 32 of whole words (packed_chunk): its windows start at base i0 = 32 w0
+    return multi_host_loop(c, n - k + 1, 32 * kPackedChunkWords, patterns, taus, n_queries, counts, err, [&](size_t i0, const MultiArgsT<bitnuc_pattern> &a) {
+        const PackedChunk ch = packed_chunk(i0 / 32, n, k);
+        HIPCHK(hipMemcpyAsync(c->scratch[0], words + ch.w0, ch.words * 8, hipMemcpyHostToDevice, c->stream));
+        return launch_count_multi_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), ch.bases, k, a, err);
+    });
+}
+
+int bitnuc_kmer_pattern_best_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries, uint64_t *d_pos,
+                                   uint8_t *d_dist, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    bool none;
+    if (int st = check_best(d_patterns, n_queries, d_pos, d_dist, &none, err, 3)) return st;
+    if (none) return BITNUC_OK;
+    DeviceGuard g(c->device);
+    if (k == 0 || n < k) return best_fill_dev(c, d_pos, d_dist, n_queries, err); // no windows
+    if (!d_ref) return fail(err, BITNUC_UNSUPPORTED);
+    unsigned long long *slot;
+    if (int st = take_slot(c, 0, &slot, err)) return st;
+    return launch_best(c, d_ref, n, k, BestArgsT<bitnuc_pattern>{d_patterns, n_queries, reinterpret_cast<unsigned long long *>(d_pos), d_dist}, slot, err);
+}
+
+int bitnuc_kmer_pattern_best_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries,
+                                          uint64_t *d_pos, uint8_t *d_dist, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
+    bool none;
+    if (int st = check_best(d_patterns, n_queries, d_pos, d_dist, &none, err, 3)) return st;
+    if (none) return BITNUC_OK;
+    DeviceGuard g(c->device);
+    if (k == 0 || n < k) return best_fill_dev(c, d_pos, d_dist, n_queries, err);
+    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    return launch_best_packed(c, d_words, n, k, BestArgsT<bitnuc_pattern>{d_patterns, n_queries, reinterpret_cast<unsigned long long *>(d_pos), d_dist}, err);
+}
+
+int bitnuc_kmer_pattern_best(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const bitnuc_pattern *patterns, size_t n_queries, uint64_t *pos, uint8_t *dist,
+                             bitnuc_err *err) {
+    clear_err(err);
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    bool none;
+    if (int st = check_best(patterns, n_queries, pos, dist, &none, err, 3)) return st;
+    if (none) return BITNUC_OK;
+    if (k == 0 || n < k) { memset(pos, 0xFF, n_queries * sizeof(uint64_t)); memset(dist, 0xFF, n_queries); return BITNUC_OK; }
+    if (!ref) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, multi_work(n - k + 1, n_queries))) {
+        const long long bad = bitnuc_host::kmer_hdist_best_small(ref, n, k, dev_queries(patterns), n_queries, pos, dist);
+        if (bad >= 0) {
+            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = ref[bad]; err->index = (uint64_t)bad; }
+            return BITNUC_INVALID_BASE;
+        }
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    // chunks of kHostChunk windows + their k - 1 halo bases
+    if (int st = ensure_scratch(c, 0, kHostChunk + 64, err)) return st;
+    const size_t nwin = n - k + 1;
+    return best_host_loop(c, nwin, kHostChunk, patterns, n_queries, pos, dist, err, [&](size_t i0, const BestArgsT<bitnuc_pattern> &a) {
+        const size_t m = nwin - i0 < kHostChunk ? nwin - i0 : kHostChunk;
+        HIPCHK(hipMemcpyAsync(c->scratch[0], ref + i0, m + k - 1, hipMemcpyHostToDevice, c->stream));
+        unsigned long long *slot;
+        if (int st = take_slot(c, i0, &slot, err)) return st;
+        return launch_best(c, c->scratch[0], m + k - 1, k, a, slot, err);
+    });
+}
+
+int bitnuc_kmer_pattern_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *patterns, size_t n_queries, uint64_t *pos,
+                                    uint8_t *dist, bitnuc_err *err) {
+    clear_err(err);
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
+    bool none;
+    if (int st = check_best(patterns, n_queries, pos, dist, &none, err, 3)) return st;
+    if (none) return BITNUC_OK;
+    if (k == 0 || n < k) { memset(pos, 0xFF, n_queries * sizeof(uint64_t)); memset(dist, 0xFF, n_queries); return BITNUC_OK; }
+    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, multi_work(n - k + 1, n_queries))) {
+        bitnuc_host::kmer_hdist_best_packed_small(words, n, k, dev_queries(patterns), n_queries, pos, dist);
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    if (int st = ensure_scratch(c, 0, (kPackedChunkWords + 1) * 8, err)) return st;
+    // chunk w0 / 32 of whole words (packed_chunk): its windows start at base i0 = 32 w0
+    return best_host_loop(c, n - k + 1, 32 * kPackedChunkWords, patterns, n_queries, pos, dist, err, [&](size_t i0, const BestArgsT<bitnuc_pattern> &a) {
+        const PackedChunk ch = packed_chunk(i0 / 32, n, k);
+        HIPCHK(hipMemcpyAsync(c->scratch[0], words + ch.w0, ch.words * 8, hipMemcpyHostToDevice, c->stream));
+        return launch_best_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), ch.bases, k, a, err);
+    });
+}
+
+int bitnuc_kmer_pattern_hits_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const bitnuc_pattern *pattern, unsigned tau, uint64_t *d_pos, uint8_t *d_hit_dist,
+                                   size_t cap, uint64_t *d_n_hits, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    if (int st = check_hits_out(d_pos, cap, d_n_hits, err)) return st;
+    if (!pattern) return fail(err, BITNUC_UNSUPPORTED);
+    DeviceGuard g(c->device);
+    if (k == 0 || n < k) { // no windows
+        HIPCHK(hipMemsetAsync(d_n_hits, 0, sizeof(uint64_t), c->stream));
+        return BITNUC_OK;
+    }
+    if (!d_ref) return fail(err, BITNUC_UNSUPPORTED);
+    unsigned long long *slot;
+    if (int st = take_slot(c, 0, &slot, err)) return st;
+    const HitsArgsT<bitnuc_pattern> a{*pattern, tau, reinterpret_cast<unsigned long long *>(d_pos), d_hit_dist, cap, reinterpret_cast<unsigned long long *>(d_n_hits), 0};
+    return launch_hits(c, d_ref, n, k, a, slot, err);
+}
+
+int bitnuc_kmer_pattern_hits_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *pattern, unsigned tau, uint64_t *d_pos,
+                                          uint8_t *d_hit_dist, size_t cap, uint64_t *d_n_hits, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    bool none;
+    if (int st = check_packed(d_words, n_words, n, k, &none, err)) return st;
+    if (int st = check_hits_out(d_pos, cap, d_n_hits, err)) return st;
+    if (!pattern) return fail(err, BITNUC_UNSUPPORTED);
+    DeviceGuard g(c->device);
+    if (none) {
+        HIPCHK(hipMemsetAsync(d_n_hits, 0, sizeof(uint64_t), c->stream));
+        return BITNUC_OK;
+    }
+    const HitsArgsT<bitnuc_pattern> a{*pattern, tau, reinterpret_cast<unsigned long long *>(d_pos), d_hit_dist, cap, reinterpret_cast<unsigned long long *>(d_n_hits), 0};
+    return launch_hits_packed(c, d_words, n, k, a, err);
+}
+
+int bitnuc_kmer_pattern_hits(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const bitnuc_pattern *pattern, unsigned tau, uint64_t *pos, uint8_t *hit_dist, size_t cap,
+                             uint64_t *n_hits, bitnuc_err *err) {
+    clear_err(err);
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    if (!n_hits || (!pos && cap) || !pattern) return fail(err, BITNUC_UNSUPPORTED);
+    if (k == 0 || n < k) { *n_hits = 0; return BITNUC_OK; }
+    if (!ref) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, n)) {
+        const long long bad = bitnuc_host::kmer_hdist_hits_small(ref, n, k, dev_query(*pattern), tau, pos, hit_dist, cap, n_hits);
+        if (bad >= 0) {
+            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = ref[bad]; err->index = (uint64_t)bad; }
+            return BITNUC_INVALID_BASE;
+        }
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    // chunks of kHostChunk windows + their k - 1 halo bases
+    if (int st = ensure_scratch(c, 0, kHostChunk + 64, err)) return st;
+    return hits_host_loop(c, n - k + 1, kHostChunk, tau, *pattern, pos, hit_dist, cap, n_hits, err, [&](size_t i0, size_t m, const HitsArgsT<bitnuc_pattern> &a) {
+        HIPCHK(hipMemcpyAsync(c->scratch[0], ref + i0, m + k - 1, hipMemcpyHostToDevice, c->stream));
+        unsigned long long *slot;
+        if (int st = take_slot(c, i0, &slot, err)) return st;
+        return launch_hits(c, c->scratch[0], m + k - 1, k, a, slot, err);
+    });
+}
+
+int bitnuc_kmer_pattern_hits_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *pattern, unsigned tau, uint64_t *pos,
+                                    uint8_t *hit_dist, size_t cap, uint64_t *n_hits, bitnuc_err *err) {
+    clear_err(err);
+    bool none;
+    if (int st = check_packed(words, n_words, n, k, &none, err)) return st;
+    if (!n_hits || (!pos && cap) || !pattern) return fail(err, BITNUC_UNSUPPORTED);
+    if (none) { *n_hits = 0; return BITNUC_OK; }
+    if (on_host(c, n)) { *n_hits = bitnuc_host::kmer_hdist_hits_packed_small(words, n, k, dev_query(*pattern), tau, pos, hit_dist, cap); return BITNUC_OK; }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    if (int st = ensure_scratch(c, 0, (kPackedChunkWords + 1) * 8, err)) return st;
+    // chunk w0 / 32 of whole words (packed_chunk): its windows start at base i0 = 32 w0
+    return hits_host_loop(c, n - k + 1, 32 * kPackedChunkWords, tau, *pattern, pos, hit_dist, cap, n_hits, err, [&](size_t i0, size_t, const HitsArgsT<bitnuc_pattern> &a) {
+        const PackedChunk ch = packed_chunk(i0 / 32, n, k);
+        HIPCHK(hipMemcpyAsync(c->scratch[0], words + ch.w0, ch.words * 8, hipMemcpyHostToDevice, c->stream));
+        return launch_hits_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), ch.bases, k, a, err);
     });
 }
 

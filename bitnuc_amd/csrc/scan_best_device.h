@@ -36,8 +36,9 @@ constexpr int kBestPosBits = 58;                     // key = d << 58 | j
 static_assert(sizeof(BestTable) % 16 == 0, "tables are copied and read as 16-byte pieces");
 
 // One thread per (query, row): row's 16 dwords of query q's table (ASCII: delta = row - 8, 40 rows; packed: delta = row - 2, 34 rows)
-template <bool PACKED>
-__global__ void __launch_bounds__(64) best_tables_kernel(const unsigned long long *__restrict__ queries, unsigned k, BestTable *__restrict__ tabs) {
+// Q: the query kind (QueryKind, scan_mfma_device.h) -- the row builders take either
+template <bool PACKED, class Q>
+__global__ void __launch_bounds__(64) best_tables_kernel(const Q *__restrict__ queries, unsigned k, BestTable *__restrict__ tabs) {
     const unsigned q = blockIdx.x, row = threadIdx.x;
     if constexpr (PACKED) {
         if (row < 34u) bitnuc_host::scan_packed_row(queries[q], k, (int)row - 2, tabs[q].w[row]);
@@ -119,21 +120,21 @@ __device__ __forceinline__ void best_lane_keys(const uint32_t (&best)[kMultiQB],
 }
 
 // The windows [0, pre) and [first, nwin), one per thread of the grid's x extent, every query of the block: word_of(j) is window j's 2-bit word
-template <class WordOf>
+template <class Q, class WordOf>
 __device__ __forceinline__ void best_tail_windows(unsigned long long pre, unsigned long long first, unsigned long long nwin, unsigned k,
-                                                  const unsigned long long *__restrict__ queries, unsigned nq, unsigned long long (&key)[kMultiQB],
+                                                  const Q *__restrict__ queries, unsigned nq, unsigned long long (&key)[kMultiQB],
                                                   WordOf word_of) {
-    const unsigned long long kmask = kmer_mask(k);
+    const QueryKind<Q> kind(k);
     const unsigned long long gt = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
     const unsigned long long nthreads = (unsigned long long)gridDim.x * blockDim.x;
     const unsigned long long total = pre + (nwin > first ? nwin - first : 0);
     for (unsigned long long t = gt; t < total; t += nthreads) {
         const unsigned long long j = t < pre ? t : first + (t - pre);
-        const unsigned long long w = word_of(j);
+        const auto w = kind.window(word_of(j));
 #pragma unroll
         for (int qi = 0; qi < kMultiQB; ++qi) {
             if ((unsigned)qi < nq) {
-                const unsigned long long c = best_key(word_distance(w, queries[qi], kmask), j);
+                const unsigned long long c = best_key(kind.dist(w, queries[qi]), j);
                 key[qi] = c < key[qi] ? c : key[qi];
             }
         }
@@ -176,9 +177,9 @@ __global__ void __launch_bounds__(256) best_finish_kernel(const unsigned long lo
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // ASCII bytes at any alignment: the rounds start at ref + skip (16-byte aligned).
-template <int U>
+template <int U, class Q>
 __global__ void __launch_bounds__(kMultiBlock)
-kmer_best_kernel(const uint8_t *__restrict__ ref, unsigned long long n, unsigned skip, unsigned k, const unsigned long long *__restrict__ queries,
+kmer_best_kernel(const uint8_t *__restrict__ ref, unsigned long long n, unsigned skip, unsigned k, const Q *__restrict__ queries,
                  unsigned n_queries, const BestTable *__restrict__ tabs, unsigned long long *__restrict__ keys, unsigned long long *__restrict__ slot) {
     __shared__ __attribute__((aligned(16))) BestTable qtab[kMultiQB];
     __shared__ __attribute__((aligned(16))) uint8_t strips[kMultiBlock / 64][AsciiStrip4<U>::kBytes];
@@ -229,8 +230,9 @@ kmer_best_kernel(const uint8_t *__restrict__ ref, unsigned long long n, unsigned
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Packed words (8-byte aligned; at 8 mod 16 the rounds start one word later).
+template <class Q>
 __global__ void __launch_bounds__(kMultiBlock)
-packed_best_kernel(const uint64_t *__restrict__ words, unsigned long long n, unsigned skip, unsigned k, const unsigned long long *__restrict__ queries,
+packed_best_kernel(const uint64_t *__restrict__ words, unsigned long long n, unsigned skip, unsigned k, const Q *__restrict__ queries,
                    unsigned n_queries, const BestTable *__restrict__ tabs, unsigned long long *__restrict__ keys) {
     __shared__ __attribute__((aligned(16))) BestTable qtab[kMultiQB];
     __shared__ __attribute__((aligned(16))) uint8_t strips[kMultiBlock / 64][PackedStrip4::kBytes];

@@ -6,20 +6,23 @@
 #include <stdint.h>
 #include <string.h>
 
-#include "host_word.h" // hdist_word, packed_window
+#include "host_word.h"    // packed_window
+#include "pattern_host.h" // window_dist: exact queries (uint64_t) and patterns (PatternSets)
 
 namespace bitnuc_host {
 
 // window j's word w against every query: a strictly smaller distance takes the place (windows come in ascending order: the leftmost stays)
-static inline void best_window(uint64_t w, size_t j, size_t k, const uint64_t *queries, size_t nq, uint64_t *pos, uint8_t *dist) {
+template <class Q>
+static inline void best_window(uint64_t w, size_t j, size_t k, const Q *queries, size_t nq, uint64_t *pos, uint8_t *dist) {
     for (size_t q = 0; q < nq; ++q) {
-        const uint32_t d = hdist_word(w, queries[q], k);
+        const uint32_t d = window_dist(w, queries[q], k);
         if (d < dist[q]) dist[q] = (uint8_t)d, pos[q] = j;
     }
 }
 
 // packed sequence of n bases (1 <= k <= min(n, 32)): pos[0 .. nq) and dist[0 .. nq) overwritten
-static inline void kmer_hdist_best_packed_small(const uint64_t *words, size_t n, size_t k, const uint64_t *queries, size_t nq, uint64_t *pos, uint8_t *dist) {
+template <class Q>
+static inline void kmer_hdist_best_packed_small(const uint64_t *words, size_t n, size_t k, const Q *queries, size_t nq, uint64_t *pos, uint8_t *dist) {
     memset(pos, 0xFF, nq * sizeof(uint64_t));
     memset(dist, 0xFF, nq);
     for (size_t j = 0; j + k <= n; ++j) best_window(packed_window(words, j, k), j, k, queries, nq, pos, dist);
@@ -27,7 +30,8 @@ static inline void kmer_hdist_best_packed_small(const uint64_t *words, size_t n,
 
 // ASCII sequence of n bytes (1 <= k <= min(n, 32)): -1 with pos[0 .. nq) and dist[0 .. nq) overwritten, or the index of the first invalid byte (outputs
 // untouched)
-static inline long long kmer_hdist_best_small(const uint8_t *ref, size_t n, size_t k, const uint64_t *queries, size_t nq, uint64_t *pos, uint8_t *dist) {
+template <class Q>
+static inline long long kmer_hdist_best_small(const uint8_t *ref, size_t n, size_t k, const Q *queries, size_t nq, uint64_t *pos, uint8_t *dist) {
     for (size_t i = 0; i < n; ++i) {
         const unsigned u = ref[i] & 0xDFu;
         if (u != 'A' && u != 'C' && u != 'G' && u != 'T') return (long long)i;

@@ -136,9 +136,10 @@ __device__ __forceinline__ void write_hit_count(uint32_t hits, unsigned lane, un
 // kernels.  Front end: AsciiStrip4 (U = 4), as the scan.  Invalid bytes are latched by the count pass only: trip_invalid over the
 // trip's rounds, byte loads in the tail (scan_tail_windows' rule), so the slot holds the first invalid byte of the whole sequence, as the count's.
 // EMIT: counts[] holds the exclusive offsets within a tile, tile_off[] the tiles' (hits_scan_*).
-template <bool EMIT>
+// Q: the query kind (QueryKind, scan_mfma_device.h); the table is the caller's (scan_seg_table of either kind)
+template <bool EMIT, class Q>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8)))
-kmer_hits_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, unsigned skip, unsigned k, unsigned long long query, unsigned tau,
+kmer_hits_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, unsigned skip, unsigned k, const Q query, unsigned tau,
                       unsigned *__restrict__ counts, const unsigned long long *__restrict__ tile_off, unsigned long long *__restrict__ pos,
                       uint8_t *__restrict__ hd, unsigned long long cap, unsigned long long pos_base, unsigned long long *__restrict__ slot,
                       const CountMfmaTable tab) {
@@ -179,10 +180,10 @@ kmer_hits_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, uns
             else hits += round_hits(acc, bias);
         }
     } else { // the first workgroup: the head windows [0, skip); the last: the tail
-        const unsigned long long kmask = kmer_mask(k);
+        const QueryKind<Q> kind(k);
         const unsigned long long pre = blk == 0 ? (skip < nwin ? skip : nwin) : 0, first = blk == 0 ? nwin : skip + (rounds << 10);
         hits = hits_tail<EMIT>(pre, first, nwin, tau, lane, rank, cap, pos_base, pos, hd,
-                               [&](unsigned long long j) { return word_distance(ascii_window_word(ref, j, k, !EMIT, slot), query, kmask); });
+                               [&](unsigned long long j) { return kind.dist(kind.window(ascii_window_word(ref, j, k, !EMIT, slot)), query); });
     }
     if constexpr (!EMIT) write_hit_count(hits, lane, counts);
 }
@@ -190,9 +191,9 @@ kmer_hits_mfma_kernel(const uint8_t *__restrict__ ref, unsigned long long n, uns
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Packed input: packed_trip_load and PackedStrip4, as the packed scan (one wave load of 1 KiB = one trip, strip cut by group residue); words at 8 mod 16
 // start the rounds one word later (skip = 32).  No byte can be invalid.
-template <bool EMIT>
+template <bool EMIT, class Q>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8)))
-packed_hits_mfma_kernel(const uint64_t *__restrict__ words, unsigned long long n, unsigned skip, unsigned k, unsigned long long query, unsigned tau,
+packed_hits_mfma_kernel(const uint64_t *__restrict__ words, unsigned long long n, unsigned skip, unsigned k, const Q query, unsigned tau,
                         unsigned *__restrict__ counts, const unsigned long long *__restrict__ tile_off, unsigned long long *__restrict__ pos,
                         uint8_t *__restrict__ hd, unsigned long long cap, unsigned long long pos_base, const PackedScanTable tab) {
     __shared__ __attribute__((aligned(16))) uint8_t strip[PackedStrip4::kBytes];
@@ -230,10 +231,10 @@ packed_hits_mfma_kernel(const uint64_t *__restrict__ words, unsigned long long n
             else hits += round_hits(acc, bias);
         }
     } else { // the head windows [0, skip), the tail
-        const unsigned long long kmask = kmer_mask(k);
+        const QueryKind<Q> kind(k);
         const unsigned long long pre = blk == 0 ? (skip < nwin ? skip : nwin) : 0, first = blk == 0 ? nwin : skip + (rounds << 10);
         hits = hits_tail<EMIT>(pre, first, nwin, tau, lane, rank, cap, pos_base, pos, hd,
-                               [&](unsigned long long j) { return word_distance(packed_window_word(words, j, k), query, kmask); });
+                               [&](unsigned long long j) { return kind.dist(kind.window(packed_window_word(words, j, k)), query); });
     }
     if constexpr (!EMIT) write_hit_count(hits, lane, counts);
 }

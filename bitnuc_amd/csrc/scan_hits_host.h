@@ -5,7 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "host_word.h" // hdist_word, packed_window
+#include "host_word.h"    // packed_window
+#include "pattern_host.h" // window_dist: exact queries (uint64_t) and patterns (PatternSets)
 
 namespace bitnuc_host {
 
@@ -16,19 +17,21 @@ static inline void hits_keep(uint64_t hits, size_t cap, uint64_t j, uint32_t d, 
     if (dist) dist[hits] = (uint8_t)d;
 }
 
-// packed sequence of n bases (1 <= k <= min(n, 32))
-static inline uint64_t kmer_hdist_hits_packed_small(const uint64_t *words, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *pos, uint8_t *dist,
+// packed sequence of n bases (1 <= k <= min(n, 32)); Q: uint64_t (an exact query) or PatternSets
+template <class Q>
+static inline uint64_t kmer_hdist_hits_packed_small(const uint64_t *words, size_t n, size_t k, const Q &query, unsigned tau, uint64_t *pos, uint8_t *dist,
                                                     size_t cap) {
     uint64_t hits = 0;
     for (size_t j = 0; j + k <= n; ++j) {
-        const uint32_t d = hdist_word(packed_window(words, j, k), query, k);
+        const uint32_t d = window_dist(packed_window(words, j, k), query, k);
         if (d <= tau) hits_keep(hits++, cap, j, d, pos, dist);
     }
     return hits;
 }
 
 // ASCII sequence of n bytes (1 <= k <= min(n, 32)): -1 with *n_hits set, or the index of the first invalid byte (nothing written)
-static inline long long kmer_hdist_hits_small(const uint8_t *ref, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *pos, uint8_t *dist,
+template <class Q>
+static inline long long kmer_hdist_hits_small(const uint8_t *ref, size_t n, size_t k, const Q &query, unsigned tau, uint64_t *pos, uint8_t *dist,
                                               size_t cap, uint64_t *n_hits) {
     for (size_t i = 0; i < n; ++i) {
         const unsigned u = ref[i] & 0xDFu;
@@ -39,7 +42,7 @@ static inline long long kmer_hdist_hits_small(const uint8_t *ref, size_t n, size
         const uint64_t code = ((ref[i] >> 1) ^ (ref[i] >> 2)) & 3u; // A 0, C 1, G 2, T 3, either case
         w = (w >> 2) | (code << (2 * (k - 1)));                      // window i + 1 - k, base b at bits 2 b
         if (i + 1 < k) continue;
-        const uint32_t d = hdist_word(w, query, k);
+        const uint32_t d = window_dist(w, query, k);
         if (d <= tau) hits_keep(hits++, cap, i + 1 - k, d, pos, dist);
     }
     *n_hits = hits;

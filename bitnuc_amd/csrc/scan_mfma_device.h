@@ -41,6 +41,25 @@
 
 namespace bitnuc_dev {
 
+// The two kinds of query the multi-query count, the best match and the hit lists take (their template parameter Q): an exact query, one base per position
+// packed into a 64-bit word, or a pattern, a set of bases per position (PatternSets, scan_mfma_host.h).  The matrix-core rounds never see the
+// difference -- it is all in the tables --; the windows the rounds do not cover go through QueryKind<Q>: built once per kernel from k, window(w) is what
+// is common to every query of a window (computed once per window), dist(window, q) the window's distance to one query.
+template <class Q> struct QueryKind;
+template <> struct QueryKind<unsigned long long> {
+    unsigned long long kmask;
+    __device__ __forceinline__ explicit QueryKind(unsigned k) : kmask(kmer_mask(k)) {}
+    __device__ __forceinline__ unsigned long long window(unsigned long long w) const { return w; }
+    __device__ __forceinline__ uint32_t dist(unsigned long long w, unsigned long long query) const { return word_distance(w, query, kmask); }
+};
+template <> struct QueryKind<PatternSets> {
+    uint32_t ones;
+    __device__ __forceinline__ explicit QueryKind(unsigned k) : ones(kmer_ones(k)) {}
+    __device__ __forceinline__ WindowPlanes window(unsigned long long w) const { return window_planes(w); }
+    __device__ __forceinline__ uint32_t dist(WindowPlanes p, const PatternSets &q) const { return pattern_distance(p, q.allow[0], q.allow[1], q.allow[2], q.allow[3], ones); }
+};
+
+
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 

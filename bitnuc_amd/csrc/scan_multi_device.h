@@ -34,9 +34,10 @@ constexpr int kMultiRounds = 4;  // rounds per trip (ASCII; a packed trip is one
 static_assert(sizeof(Count3MfmaTable) % 16 == 0, "tables are copied and read as 16-byte pieces");
 using bitnuc_host::Count3Rule;
 
-// One thread per (query, lane): lane's 12 dwords of query q's table, lane 0 also its start values
-template <bool PACKED>
-__global__ void __launch_bounds__(64) count3_tables_kernel(const unsigned long long *__restrict__ queries, const unsigned *__restrict__ taus, unsigned k,
+// One thread per (query, lane): lane's 12 dwords of query q's table, lane 0 also its start values.  Q: the query kind (QueryKind, scan_mfma_device.h) --
+// Count3Rule takes either
+template <bool PACKED, class Q>
+__global__ void __launch_bounds__(64) count3_tables_kernel(const Q *__restrict__ queries, const unsigned *__restrict__ taus, unsigned k,
                                                            Count3MfmaTable *__restrict__ tabs) {
     const unsigned q = blockIdx.x, lane = threadIdx.x;
     const Count3Rule r(queries[q], k, taus[q], false);
@@ -79,20 +80,20 @@ __device__ __forceinline__ void multi_trip_queries(const Count3MfmaTable *qtab, 
 }
 
 // The windows [0, pre) and [first, nwin), one per thread of the grid's x extent, every query of the block: word_of(j) is window j's 2-bit word
-template <class WordOf>
+template <class Q, class WordOf>
 __device__ __forceinline__ void multi_tail_windows(unsigned long long pre, unsigned long long first, unsigned long long nwin, unsigned k,
-                                                   const unsigned long long *__restrict__ queries, const unsigned *__restrict__ taus, unsigned nq,
+                                                   const Q *__restrict__ queries, const unsigned *__restrict__ taus, unsigned nq,
                                                    uint32_t (&hits)[kMultiQB], WordOf word_of) {
-    const unsigned long long kmask = kmer_mask(k);
+    const QueryKind<Q> kind(k);
     const unsigned long long gt = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
     const unsigned long long nthreads = (unsigned long long)gridDim.x * blockDim.x;
     const unsigned long long total = pre + (nwin > first ? nwin - first : 0);
     for (unsigned long long t = gt; t < total; t += nthreads) {
         const unsigned long long j = t < pre ? t : first + (t - pre);
-        const unsigned long long w = word_of(j);
+        const auto w = kind.window(word_of(j));
 #pragma unroll
         for (int qi = 0; qi < kMultiQB; ++qi) {
-            if ((unsigned)qi < nq) hits[qi] += word_distance(w, queries[qi], kmask) <= taus[qi] ? 1u : 0u;
+            if ((unsigned)qi < nq) hits[qi] += kind.dist(w, queries[qi]) <= taus[qi] ? 1u : 0u;
         }
     }
 }
@@ -119,9 +120,9 @@ __device__ __forceinline__ void multi_reduce(uint32_t (&hits)[kMultiQB], unsigne
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // ASCII bytes at any alignment: the rounds start at ref + skip (16-byte aligned).
-template <int U>
+template <int U, class Q>
 __global__ void __launch_bounds__(kMultiBlock)
-kmer_count3_multi_kernel(const uint8_t *__restrict__ ref, unsigned long long n, unsigned skip, unsigned k, const unsigned long long *__restrict__ queries,
+kmer_count3_multi_kernel(const uint8_t *__restrict__ ref, unsigned long long n, unsigned skip, unsigned k, const Q *__restrict__ queries,
                          const unsigned *__restrict__ taus, unsigned n_queries, const Count3MfmaTable *__restrict__ tabs,
                          unsigned long long *__restrict__ counts, unsigned long long *__restrict__ slot) {
     __shared__ __attribute__((aligned(16))) Count3MfmaTable qtab[kMultiQB];
@@ -169,8 +170,9 @@ kmer_count3_multi_kernel(const uint8_t *__restrict__ ref, unsigned long long n, 
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Packed words (8-byte aligned; at 8 mod 16 the rounds start one word later).
+template <class Q>
 __global__ void __launch_bounds__(kMultiBlock)
-packed_count3_multi_kernel(const uint64_t *__restrict__ words, unsigned long long n, unsigned skip, unsigned k, const unsigned long long *__restrict__ queries,
+packed_count3_multi_kernel(const uint64_t *__restrict__ words, unsigned long long n, unsigned skip, unsigned k, const Q *__restrict__ queries,
                            const unsigned *__restrict__ taus, unsigned n_queries, const Count3MfmaTable *__restrict__ tabs,
                            unsigned long long *__restrict__ counts) {
     __shared__ __attribute__((aligned(16))) Count3MfmaTable qtab[kMultiQB];

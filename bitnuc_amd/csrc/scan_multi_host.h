@@ -5,24 +5,28 @@
 #include <stdint.h>
 #include <string.h>
 
-#include "host_word.h" // hdist_word, packed_window
+#include "host_word.h"    // packed_window
+#include "pattern_host.h" // window_dist: exact queries (uint64_t) and patterns (PatternSets)
 
 namespace bitnuc_host {
 
-// window word w against every query
-static inline void multi_count_window(uint64_t w, size_t k, const uint64_t *queries, const uint32_t *taus, size_t nq, uint64_t *counts) {
-    for (size_t q = 0; q < nq; ++q) counts[q] += hdist_word(w, queries[q], k) <= taus[q];
+// window word w against every query (Q: uint64_t, an exact query, or PatternSets)
+template <class Q>
+static inline void multi_count_window(uint64_t w, size_t k, const Q *queries, const uint32_t *taus, size_t nq, uint64_t *counts) {
+    for (size_t q = 0; q < nq; ++q) counts[q] += window_dist(w, queries[q], k) <= taus[q];
 }
 
 // packed sequence of n bases (1 <= k <= min(n, 32)): counts[0 .. nq) overwritten
-static inline void kmer_hdist_count_multi_packed_small(const uint64_t *words, size_t n, size_t k, const uint64_t *queries, const uint32_t *taus, size_t nq,
+template <class Q>
+static inline void kmer_hdist_count_multi_packed_small(const uint64_t *words, size_t n, size_t k, const Q *queries, const uint32_t *taus, size_t nq,
                                                        uint64_t *counts) {
     memset(counts, 0, nq * sizeof(uint64_t));
     for (size_t j = 0; j + k <= n; ++j) multi_count_window(packed_window(words, j, k), k, queries, taus, nq, counts);
 }
 
 // ASCII sequence of n bytes (1 <= k <= min(n, 32)): -1 with counts[0 .. nq) overwritten, or the index of the first invalid byte (counts untouched)
-static inline long long kmer_hdist_count_multi_small(const uint8_t *ref, size_t n, size_t k, const uint64_t *queries, const uint32_t *taus, size_t nq,
+template <class Q>
+static inline long long kmer_hdist_count_multi_small(const uint8_t *ref, size_t n, size_t k, const Q *queries, const uint32_t *taus, size_t nq,
                                                      uint64_t *counts) {
     for (size_t i = 0; i < n; ++i) {
         const unsigned u = ref[i] & 0xDFu;

@@ -307,6 +307,79 @@ class Context {
         return pos;
     }
 
+    // ---- pattern queries: a set of bases per position (bitnuc_pattern), pdist(j) = #{ i < k : ref[j+i] not in S_i }.  The converters need no context.
+    static Result<bitnuc_pattern> pattern_from_iupac(Bytes letters) { // ACGTU RYSWKM BDHV N, either case; at most 32
+        bitnuc_pattern p;
+        bitnuc_err e;
+        if (bitnuc_pattern_from_iupac(letters.ptr, letters.len, &p, &e) != BITNUC_OK) return NucleotideError::from_c(e);
+        return p;
+    }
+    static Result<bitnuc_pattern> pattern_from_2bit(uint64_t query, size_t k) { // the singletons of an exact query: the exact entry points' results
+        bitnuc_pattern p;
+        bitnuc_err e;
+        if (bitnuc_pattern_from_2bit(query, k, &p, &e) != BITNUC_OK) return NucleotideError::from_c(e);
+        return p;
+    }
+    // counts[q] = windows with pdist <= taus[q] under patterns[q], every pattern in one pass (taus.size() == patterns.size())
+    Result<std::vector<uint64_t>> kmer_pattern_count_multi(Bytes ref, size_t k, const std::vector<bitnuc_pattern> &patterns, const std::vector<uint32_t> &taus) const {
+        if (taus.size() != patterns.size()) return NucleotideError::unsupported();
+        std::vector<uint64_t> counts(patterns.size());
+        bitnuc_err e;
+        if (bitnuc_kmer_pattern_count_multi(ctx_, ref.ptr, ref.len, k, patterns.data(), taus.data(), patterns.size(), counts.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return counts;
+    }
+    Result<std::vector<uint64_t>> kmer_pattern_count_multi_packed(Words words, size_t n, size_t k, const std::vector<bitnuc_pattern> &patterns,
+                                                                  const std::vector<uint32_t> &taus) const {
+        if (taus.size() != patterns.size()) return NucleotideError::unsupported();
+        std::vector<uint64_t> counts(patterns.size());
+        bitnuc_err e;
+        if (bitnuc_kmer_pattern_count_multi_packed(ctx_, words.ptr, words.len, n, k, patterns.data(), taus.data(), patterns.size(), counts.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return counts;
+    }
+    // (pos[q], dist[q]) = the leftmost window with the smallest pdist under patterns[q] and that pdist (no windows: UINT64_MAX / 0xFF)
+    Result<std::pair<std::vector<uint64_t>, std::vector<uint8_t>>> kmer_pattern_best(Bytes ref, size_t k, const std::vector<bitnuc_pattern> &patterns) const {
+        std::vector<uint64_t> pos(patterns.size());
+        std::vector<uint8_t> dist(patterns.size());
+        bitnuc_err e;
+        if (bitnuc_kmer_pattern_best(ctx_, ref.ptr, ref.len, k, patterns.data(), patterns.size(), pos.data(), dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return std::make_pair(std::move(pos), std::move(dist));
+    }
+    Result<std::pair<std::vector<uint64_t>, std::vector<uint8_t>>> kmer_pattern_best_packed(Words words, size_t n, size_t k,
+                                                                                            const std::vector<bitnuc_pattern> &patterns) const {
+        std::vector<uint64_t> pos(patterns.size());
+        std::vector<uint8_t> dist(patterns.size());
+        bitnuc_err e;
+        if (bitnuc_kmer_pattern_best_packed(ctx_, words.ptr, words.len, n, k, patterns.data(), patterns.size(), pos.data(), dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return std::make_pair(std::move(pos), std::move(dist));
+    }
+    // the positions (ascending) of the windows with pdist <= tau, sized by a first call with cap 0; hit_dist, when given, gets their distances
+    Result<std::vector<uint64_t>> kmer_pattern_hits(Bytes ref, size_t k, const bitnuc_pattern &pattern, unsigned tau, std::vector<uint8_t> *hit_dist = nullptr) const {
+        uint64_t total = 0;
+        bitnuc_err e;
+        if (bitnuc_kmer_pattern_hits(ctx_, ref.ptr, ref.len, k, &pattern, tau, nullptr, nullptr, 0, &total, &e) != BITNUC_OK) return NucleotideError::from_c(e);
+        std::vector<uint64_t> pos((size_t)total);
+        if (hit_dist) hit_dist->assign((size_t)total, 0);
+        if (total && bitnuc_kmer_pattern_hits(ctx_, ref.ptr, ref.len, k, &pattern, tau, pos.data(), hit_dist ? hit_dist->data() : nullptr, pos.size(), &total, &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return pos;
+    }
+    Result<std::vector<uint64_t>> kmer_pattern_hits_packed(Words words, size_t n, size_t k, const bitnuc_pattern &pattern, unsigned tau,
+                                                           std::vector<uint8_t> *hit_dist = nullptr) const {
+        uint64_t total = 0;
+        bitnuc_err e;
+        if (bitnuc_kmer_pattern_hits_packed(ctx_, words.ptr, words.len, n, k, &pattern, tau, nullptr, nullptr, 0, &total, &e) != BITNUC_OK) return NucleotideError::from_c(e);
+        std::vector<uint64_t> pos((size_t)total);
+        if (hit_dist) hit_dist->assign((size_t)total, 0);
+        if (total && bitnuc_kmer_pattern_hits_packed(ctx_, words.ptr, words.len, n, k, &pattern, tau, pos.data(), hit_dist ? hit_dist->data() : nullptr, pos.size(), &total,
+                                                     &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return pos;
+    }
+
     // Ragged batch: `for s in seqs { encode(s, &mut ebuf)? }` in one launch.  Sequence i =
     // seq[offsets[i] .. offsets[i+1]); returns the concatenated words and fills word_offsets
     // (count+1 entries, word_offsets[i] = first word of sequence i).

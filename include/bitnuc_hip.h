@@ -58,7 +58,7 @@
  *     "_dev" entry points take device pointers, are enqueued
  *     on the context's stream and return immediately -- data-dependent errors
  *     (InvalidBase) are latched on the device and reported by bitnuc_ctx_sync(); the "_async" entry points
- *     (bitnuc_kmer_hdist_best[_packed]_async) have exactly the "_dev" contract under another suffix;
+ *     (bitnuc_kmer_hdist_best[_packed]_async, bitnuc_kmer_pattern_*_async) have exactly the "_dev" contract under another suffix;
  *   - a bitnuc_ctx owns one device + stream + scratch and must not be used from
  *     two threads at once; separate contexts are independent.
  */
@@ -244,6 +244,56 @@ int bitnuc_kmer_hdist_best(bitnuc_ctx *ctx, const uint8_t *ref, size_t n, size_t
                            bitnuc_err *err);
 int bitnuc_kmer_hdist_best_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t n_words, size_t n, size_t k, const uint64_t *queries, size_t n_queries,
                                   uint64_t *pos, uint8_t *dist, bitnuc_err *err);
+/* PATTERN queries for the multi-query count, the best match and the hit lists: position i < k of a pattern accepts a SET S_i of bases instead of one base,
+ * and the distance of window j is pdist(j) = #{ i < k : ref[j+i] not in S_i }.  A guide search NNNNNNNNNNNNNNNNNNNNNGG is twenty positions whose
+ * mismatches are counted (their exact bases), one that never counts (N) and two that must match; primers and adapters use R, Y, N.  A pattern of
+ * singletons S_i = {q_i} makes pdist equal to hdist_scalar(as_2bit(ref[j..j+k]), q, k), what the exact entry points compute; an empty set mismatches every
+ * base and is legal.  Only the query's side of the matrix-core product changes (its table and the accumulators' start values): a pattern costs what an
+ * exact query costs. */
+typedef struct bitnuc_pattern { uint32_t allow[4]; } bitnuc_pattern;
+/* allow[c] bit i set <=> base code c (A=0, C=1, G=2, T=3) matches at position i; bits at positions >= k are ignored */
+/* The converters are host code and take no context.  _from_iupac: k letters of ACGTU RYSWKM BDHV N in either case (U = T); k > 32 ->
+ * SEQUENCE_TOO_LONG(k) before any letter is read; any other byte -> INVALID_BASE(byte, index); out NULL (or letters NULL with k > 0) -> UNSUPPORTED.
+ * _from_2bit: the singletons of a packed exact query (query bits above 2k are ignored); k > 32 -> SEQUENCE_TOO_LONG(k). */
+int bitnuc_pattern_from_iupac(const uint8_t *letters, size_t k, bitnuc_pattern *out, bitnuc_err *err);
+int bitnuc_pattern_from_2bit(uint64_t query, size_t k, bitnuc_pattern *out, bitnuc_err *err);
+/* The pattern twins of bitnuc_kmer_hdist_count_multi*, _best* and _hits*: `const bitnuc_pattern *patterns` (n_queries of them) stands where
+ * `const uint64_t *queries` stood, `const bitnuc_pattern *pattern` (one, by HOST pointer in every form) where `uint64_t query` stood, pdist where
+ * hdist_scalar stood.  Everything else is the twin's contract word for word: the same checks in the same order with "queries NULL or not 8-byte aligned"
+ * read as "patterns NULL or not 4-byte aligned", the same BITNUC_MAX_QUERIES, the same results with no windows, the same chunking of the host forms above
+ * the cutoff, the same freedom of alignment for d_ref / d_words, the same context scratch.  tau >= k counts (or hits) every window.  A non-ACGT byte in
+ * the REFERENCE is still INVALID_BASE: the sets are on the query's side only.  A single-pattern count is count_multi with one pattern.  The distance-byte
+ * scan has no pattern form.
+ * The _async forms have exactly the _dev contract (as bitnuc_kmer_hdist_best_async): device pointers (patterns, taus and outputs included), enqueued on the
+ * context's stream, no host synchronisation except the documented growth of context scratch, InvalidBase latched for bitnuc_ctx_sync(), capturable into a
+ * hipGraph after a warm-up with the same (or a larger) n_queries.
+ * Hit lists: *n_hits = the number of windows j with pdist(j) <= tau (it may exceed cap); pos[0 .. min(cap, *n_hits)) = the first such windows in ascending
+ * order, hit_dist[r] = pdist(pos[r]) (hit_dist may be NULL); nothing at or beyond index cap is written.  A NULL pattern -> UNSUPPORTED, checked where pos
+ * is checked. */
+int bitnuc_kmer_pattern_count_multi_async(bitnuc_ctx *ctx, const uint8_t *d_ref, size_t n, size_t k, const bitnuc_pattern *d_patterns, const uint32_t *d_taus,
+                                          size_t n_queries, uint64_t *d_counts, bitnuc_err *err);
+int bitnuc_kmer_pattern_count_multi_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *d_patterns,
+                                                 const uint32_t *d_taus, size_t n_queries, uint64_t *d_counts, bitnuc_err *err);
+int bitnuc_kmer_pattern_count_multi(bitnuc_ctx *ctx, const uint8_t *ref, size_t n, size_t k, const bitnuc_pattern *patterns, const uint32_t *taus, size_t n_queries,
+                                    uint64_t *counts, bitnuc_err *err);
+int bitnuc_kmer_pattern_count_multi_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *patterns,
+                                           const uint32_t *taus, size_t n_queries, uint64_t *counts, bitnuc_err *err);
+int bitnuc_kmer_pattern_best_async(bitnuc_ctx *ctx, const uint8_t *d_ref, size_t n, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries, uint64_t *d_pos,
+                                   uint8_t *d_dist, bitnuc_err *err);
+int bitnuc_kmer_pattern_best_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *d_patterns,
+                                          size_t n_queries, uint64_t *d_pos, uint8_t *d_dist, bitnuc_err *err);
+int bitnuc_kmer_pattern_best(bitnuc_ctx *ctx, const uint8_t *ref, size_t n, size_t k, const bitnuc_pattern *patterns, size_t n_queries, uint64_t *pos, uint8_t *dist,
+                             bitnuc_err *err);
+int bitnuc_kmer_pattern_best_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *patterns, size_t n_queries,
+                                    uint64_t *pos, uint8_t *dist, bitnuc_err *err);
+int bitnuc_kmer_pattern_hits_async(bitnuc_ctx *ctx, const uint8_t *d_ref, size_t n, size_t k, const bitnuc_pattern *pattern, unsigned tau, uint64_t *d_pos,
+                                   uint8_t *d_hit_dist, size_t cap, uint64_t *d_n_hits, bitnuc_err *err);
+int bitnuc_kmer_pattern_hits_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *pattern, unsigned tau,
+                                          uint64_t *d_pos, uint8_t *d_hit_dist, size_t cap, uint64_t *d_n_hits, bitnuc_err *err);
+int bitnuc_kmer_pattern_hits(bitnuc_ctx *ctx, const uint8_t *ref, size_t n, size_t k, const bitnuc_pattern *pattern, unsigned tau, uint64_t *pos, uint8_t *hit_dist,
+                             size_t cap, uint64_t *n_hits, bitnuc_err *err);
+int bitnuc_kmer_pattern_hits_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *pattern, unsigned tau,
+                                    uint64_t *pos, uint8_t *hit_dist, size_t cap, uint64_t *n_hits, bitnuc_err *err);
 /* d_result: one uint32 in device memory, overwritten with the distance. */
 int bitnuc_hdist_dev(bitnuc_ctx *ctx, const uint64_t *d_a, size_t na, const uint64_t *d_b, size_t nb, size_t n_bases, uint32_t *d_result, bitnuc_err *err);
 

@@ -24,6 +24,13 @@ pub struct bitnuc_err {
     pub _pad: [u8; 7],
 }
 
+/// A pattern query: `allow[c]` bit `i` set <=> base code `c` (A=0, C=1, G=2, T=3) matches at position `i`.
+#[repr(C)]
+#[derive(Clone, Copy, Default, PartialEq, Eq, Debug)]
+pub struct bitnuc_pattern {
+    pub allow: [u32; 4],
+}
+
 #[repr(C)]
 pub struct bitnuc_ctx {
     _private: [u8; 0],
@@ -132,6 +139,21 @@ extern "C" {
     pub fn bitnuc_kmer_hdist_best_packed_async(ctx: *mut bitnuc_ctx, d_words: *const u64, n_words: usize, n: usize, k: usize, d_queries: *const u64, n_queries: usize, d_pos: *mut u64, d_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_kmer_hdist_best(ctx: *mut bitnuc_ctx, reference: *const u8, n: usize, k: usize, queries: *const u64, n_queries: usize, pos: *mut u64, dist: *mut u8, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_kmer_hdist_best_packed(ctx: *mut bitnuc_ctx, words: *const u64, n_words: usize, n: usize, k: usize, queries: *const u64, n_queries: usize, pos: *mut u64, dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    // pattern queries (a set of bases per position): the converters and the twins of count_multi / best / hits
+    pub fn bitnuc_pattern_from_iupac(letters: *const u8, k: usize, out: *mut bitnuc_pattern, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_pattern_from_2bit(query: u64, k: usize, out: *mut bitnuc_pattern, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_count_multi_async(ctx: *mut bitnuc_ctx, d_ref: *const u8, n: usize, k: usize, d_patterns: *const bitnuc_pattern, d_taus: *const u32, n_queries: usize, d_counts: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_count_multi_packed_async(ctx: *mut bitnuc_ctx, d_words: *const u64, n_words: usize, n: usize, k: usize, d_patterns: *const bitnuc_pattern, d_taus: *const u32, n_queries: usize, d_counts: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_count_multi(ctx: *mut bitnuc_ctx, reference: *const u8, n: usize, k: usize, patterns: *const bitnuc_pattern, taus: *const u32, n_queries: usize, counts: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_count_multi_packed(ctx: *mut bitnuc_ctx, words: *const u64, n_words: usize, n: usize, k: usize, patterns: *const bitnuc_pattern, taus: *const u32, n_queries: usize, counts: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_best_async(ctx: *mut bitnuc_ctx, d_ref: *const u8, n: usize, k: usize, d_patterns: *const bitnuc_pattern, n_queries: usize, d_pos: *mut u64, d_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_best_packed_async(ctx: *mut bitnuc_ctx, d_words: *const u64, n_words: usize, n: usize, k: usize, d_patterns: *const bitnuc_pattern, n_queries: usize, d_pos: *mut u64, d_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_best(ctx: *mut bitnuc_ctx, reference: *const u8, n: usize, k: usize, patterns: *const bitnuc_pattern, n_queries: usize, pos: *mut u64, dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_best_packed(ctx: *mut bitnuc_ctx, words: *const u64, n_words: usize, n: usize, k: usize, patterns: *const bitnuc_pattern, n_queries: usize, pos: *mut u64, dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_hits_async(ctx: *mut bitnuc_ctx, d_ref: *const u8, n: usize, k: usize, pattern: *const bitnuc_pattern, tau: c_uint, d_pos: *mut u64, d_hit_dist: *mut u8, cap: usize, d_n_hits: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_hits_packed_async(ctx: *mut bitnuc_ctx, d_words: *const u64, n_words: usize, n: usize, k: usize, pattern: *const bitnuc_pattern, tau: c_uint, d_pos: *mut u64, d_hit_dist: *mut u8, cap: usize, d_n_hits: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_hits(ctx: *mut bitnuc_ctx, reference: *const u8, n: usize, k: usize, pattern: *const bitnuc_pattern, tau: c_uint, pos: *mut u64, hit_dist: *mut u8, cap: usize, n_hits: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_hits_packed(ctx: *mut bitnuc_ctx, words: *const u64, n_words: usize, n: usize, k: usize, pattern: *const bitnuc_pattern, tau: c_uint, pos: *mut u64, hit_dist: *mut u8, cap: usize, n_hits: *mut u64, err: *mut bitnuc_err) -> c_int;
     // diagnostics
     pub fn bitnuc_selftime_small(op: c_int, n: usize, iters: usize) -> f64;
 }

@@ -319,6 +319,104 @@ pub fn kmer_hdist_best_packed(words: &[u64], n: usize, k: usize, queries: &[u64]
     if st == ffi::BITNUC_OK { Ok((pos, dist)) } else { Err(to_err(&e)) }
 }
 
+/// A pattern query: a set of bases per position (`allow[c]` bit `i` set <=> base code `c` matches at position `i`).
+pub use ffi::bitnuc_pattern as Pattern;
+
+/// The pattern of `letters` (IUPAC: `ACGTU RYSWKM BDHV N`, either case; at most 32).  Host code, no context.
+pub fn pattern_from_iupac(letters: &[u8]) -> Result<Pattern, NucleotideError> {
+    let mut p = Pattern::default();
+    let mut e = ffi::bitnuc_err::default();
+    let st = unsafe { ffi::bitnuc_pattern_from_iupac(letters.as_ptr(), letters.len(), &mut p, &mut e) };
+    if st == ffi::BITNUC_OK { Ok(p) } else { Err(to_err(&e)) }
+}
+
+/// The pattern of singletons of the packed exact query `query` of `k` bases: under it the pattern functions return what their exact twins return.
+pub fn pattern_from_2bit(query: u64, k: usize) -> Result<Pattern, NucleotideError> {
+    let mut p = Pattern::default();
+    let mut e = ffi::bitnuc_err::default();
+    let st = unsafe { ffi::bitnuc_pattern_from_2bit(query, k, &mut p, &mut e) };
+    if st == ffi::BITNUC_OK { Ok(p) } else { Err(to_err(&e)) }
+}
+
+/// `counts[q]` = the number of windows `j` of `reference` with `pdist(j) = #{ i < k : reference[j+i] not in S_i of patterns[q] } <= taus[q]`, every
+/// pattern in one pass (`taus.len()` must equal `patterns.len()`).
+pub fn kmer_pattern_count_multi(reference: &[u8], k: usize, patterns: &[Pattern], taus: &[u32]) -> Result<Vec<u64>, NucleotideError> {
+    if taus.len() != patterns.len() { return Err(NucleotideError::Unsupported); }
+    let mut counts = vec![0u64; patterns.len()];
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_pattern_count_multi(c, reference.as_ptr(), reference.len(), k, patterns.as_ptr(), taus.as_ptr(), patterns.len(), counts.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(counts) } else { Err(to_err(&e)) }
+}
+
+/// `kmer_pattern_count_multi` of the packed sequence `words` holding `n` bases, without decoding it.
+pub fn kmer_pattern_count_multi_packed(words: &[u64], n: usize, k: usize, patterns: &[Pattern], taus: &[u32]) -> Result<Vec<u64>, NucleotideError> {
+    if taus.len() != patterns.len() { return Err(NucleotideError::Unsupported); }
+    let mut counts = vec![0u64; patterns.len()];
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_pattern_count_multi_packed(c, words.as_ptr(), words.len(), n, k, patterns.as_ptr(), taus.as_ptr(), patterns.len(), counts.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(counts) } else { Err(to_err(&e)) }
+}
+
+/// The best match per pattern in one pass: `(pos, dist)` with `dist[q]` = the smallest pdist of a window under `patterns[q]` and `pos[q]` = the leftmost
+/// window that attains it (no windows: `u64::MAX` / `0xFF`).
+pub fn kmer_pattern_best(reference: &[u8], k: usize, patterns: &[Pattern]) -> Result<(Vec<u64>, Vec<u8>), NucleotideError> {
+    let mut pos = vec![0u64; patterns.len()];
+    let mut dist = vec![0u8; patterns.len()];
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_pattern_best(c, reference.as_ptr(), reference.len(), k, patterns.as_ptr(), patterns.len(), pos.as_mut_ptr(), dist.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok((pos, dist)) } else { Err(to_err(&e)) }
+}
+
+/// `kmer_pattern_best` of the packed sequence `words` holding `n` bases, without decoding it.
+pub fn kmer_pattern_best_packed(words: &[u64], n: usize, k: usize, patterns: &[Pattern]) -> Result<(Vec<u64>, Vec<u8>), NucleotideError> {
+    let mut pos = vec![0u64; patterns.len()];
+    let mut dist = vec![0u8; patterns.len()];
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_pattern_best_packed(c, words.as_ptr(), words.len(), n, k, patterns.as_ptr(), patterns.len(), pos.as_mut_ptr(), dist.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok((pos, dist)) } else { Err(to_err(&e)) }
+}
+
+/// The positions (ascending) and distances of the windows of `reference` with pdist at most `tau` under `pattern`: a first call with cap 0 returns
+/// their number, a second fills the lists.
+pub fn kmer_pattern_hits(reference: &[u8], k: usize, pattern: &Pattern, tau: u32) -> Result<(Vec<u64>, Vec<u8>), NucleotideError> {
+    let mut total = 0u64;
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_pattern_hits(c, reference.as_ptr(), reference.len(), k, pattern, tau, std::ptr::null_mut(), std::ptr::null_mut(), 0, &mut total, &mut e)
+    });
+    if st != ffi::BITNUC_OK { return Err(to_err(&e)); }
+    let mut pos = vec![0u64; total as usize];
+    let mut dist = vec![0u8; total as usize];
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_pattern_hits(c, reference.as_ptr(), reference.len(), k, pattern, tau, pos.as_mut_ptr(), dist.as_mut_ptr(), pos.len(), &mut total, &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok((pos, dist)) } else { Err(to_err(&e)) }
+}
+
+/// `kmer_pattern_hits` of the packed sequence `words` holding `n` bases, without decoding it.
+pub fn kmer_pattern_hits_packed(words: &[u64], n: usize, k: usize, pattern: &Pattern, tau: u32) -> Result<(Vec<u64>, Vec<u8>), NucleotideError> {
+    let mut total = 0u64;
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_pattern_hits_packed(c, words.as_ptr(), words.len(), n, k, pattern, tau, std::ptr::null_mut(), std::ptr::null_mut(), 0, &mut total, &mut e)
+    });
+    if st != ffi::BITNUC_OK { return Err(to_err(&e)); }
+    let mut pos = vec![0u64; total as usize];
+    let mut dist = vec![0u8; total as usize];
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_pattern_hits_packed(c, words.as_ptr(), words.len(), n, k, pattern, tau, pos.as_mut_ptr(), dist.as_mut_ptr(), pos.len(), &mut total, &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok((pos, dist)) } else { Err(to_err(&e)) }
+}
+
 /// `for s in seqs { encode(s, &mut ebuf)? }` in one launch: sequence i =
 /// `seq[offsets[i]..offsets[i+1]]`; returns (concatenated words, word_offsets).
 pub fn encode_batch(seq: &[u8], offsets: &[u64]) -> Result<(Vec<u64>, Vec<u64>), NucleotideError> {
