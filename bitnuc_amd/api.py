@@ -383,6 +383,38 @@ class Context:
         w = _as_u64(words)
         return self._best(self._lib.bitnuc_kmer_hdist_best_packed, (_ptr(w), w.size, int(n_bases), int(k)), queries)
 
+    def _reads_best(self, fn, head, count, queries):
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.uint64).reshape(-1))  # a scalar query: Q = 1
+        query = np.empty(count, dtype=np.uint32)
+        pos = np.empty(count, dtype=np.uint32)
+        dist = np.empty(count, dtype=np.uint8)
+        err = L.BitnucErr()
+        if fn(self._h, *head, _ptr(q), q.size, _ptr(query), _ptr(pos), _ptr(dist), C.byref(err)) != L.OK:
+            _raise(err)
+        return query, pos, dist
+
+    def reads_hdist_best(self, reads, read_len, k, queries, count=None):
+        """The best match per read of back-to-back reads of `read_len` bases (`reads` holds a whole number of them): (query, pos, dist) with, per
+        read, the smallest (distance, query index, offset) over all queries and the windows that lie wholly inside the read (np.uint32, np.uint32,
+        np.uint8); a read without a window, or no queries: 2^32 - 1, 2^32 - 1, 255.  `count` defaults to len(reads) / read_len."""
+        s = _as_u8(reads)
+        read_len = int(read_len)
+        if count is None:
+            if read_len <= 0 or s.size % read_len:
+                raise ValueError("reads must hold a whole number of reads of read_len bases")
+            count = s.size // read_len
+        count = int(count)
+        if s.size < count * read_len:
+            raise ValueError("reads must hold count reads of read_len bases")
+        return self._reads_best(self._lib.bitnuc_reads_hdist_best, (_ptr(s), read_len, count, int(k)), count, queries)
+
+    def reads_hdist_best_packed(self, words, read_len, count, k, queries):
+        """reads_hdist_best of the packed words encode_fixed writes (ceil(read_len / 32) words per read), without decoding them."""
+        w = _as_u64(words)
+        if w.size < int(count) * ((int(read_len) + 31) // 32):
+            raise ValueError("words must hold count reads of ceil(read_len / 32) words each")
+        return self._reads_best(self._lib.bitnuc_reads_hdist_best_packed, (_ptr(w), int(read_len), int(count), int(k)), int(count), queries)
+
     # -- pattern queries: a set of bases per position (bitnuc_pattern) -------------------------
     @staticmethod
     def _patterns(patterns, k):
@@ -694,6 +726,17 @@ class Context:
         """The best match per query on packed words in device memory (8-byte aligned)."""
         self._call_dev(self._lib.bitnuc_kmer_hdist_best_packed_async, _dev_ptr(d_words), int(n_words), int(n), int(k), _dev_ptr(d_queries), int(n_queries),
                        _dev_ptr(d_pos), _dev_ptr(d_dist))
+
+    def reads_hdist_best_async(self, d_reads, read_len, count, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist):
+        """The best match per read of `count` back-to-back ASCII reads in device memory: d_best_query[r], d_best_pos[r] (u32), d_best_dist[r] (u8) =
+        the smallest (distance, query, offset) over the windows inside read r.  Asynchronous on the context's stream, as the _dev calls."""
+        self._call_dev(self._lib.bitnuc_reads_hdist_best_async, _dev_ptr(d_reads), int(read_len), int(count), int(k), _dev_ptr(d_queries), int(n_queries),
+                       _dev_ptr(d_best_query), _dev_ptr(d_best_pos), _dev_ptr(d_best_dist))
+
+    def reads_hdist_best_packed_async(self, d_words, read_len, count, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist):
+        """The best match per read on the packed words encode_fixed_dev writes (8-byte aligned, ceil(read_len / 32) words per read)."""
+        self._call_dev(self._lib.bitnuc_reads_hdist_best_packed_async, _dev_ptr(d_words), int(read_len), int(count), int(k), _dev_ptr(d_queries),
+                       int(n_queries), _dev_ptr(d_best_query), _dev_ptr(d_best_pos), _dev_ptr(d_best_dist))
 
     # the pattern twins: d_patterns holds n_queries bitnuc_pattern (16 bytes each, 4-byte aligned) in device memory; the hit lists take their one
     # pattern from the host (a (4,) np.uint32 array)

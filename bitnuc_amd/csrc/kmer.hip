@@ -2,7 +2,8 @@
 // <= 32-mers (BASELINE config 3, README.md:52-56), every window of a sequence (src/lib.rs:170-173), the sliding pack +
 // Hamming scan (config 5: packing/mod.rs:80-110 o hamming/scalar.rs:11-48) and bulk hdist (hamming/multi.rs:121-160).
 // Kernels: kmer_device.h; config 5 on the matrix cores: scan_mfma_device.h; the same scan and count on packed words: scan_packed_device.h; the hit
-// lists of both: scan_hits_device.h; the count for many queries at once: scan_multi_device.h; the best match per query: scan_best_device.h.
+// lists of both: scan_hits_device.h; the count for many queries at once: scan_multi_device.h; the best match per query: scan_best_device.h; the best match per read of a
+// fixed-length batch: scan_reads_device.h.
 #include "runtime.h"
 #include "kmer_device.h"
 #include "scan_mfma_device.h"
@@ -10,10 +11,12 @@
 #include "scan_hits_device.h"
 #include "scan_multi_device.h"
 #include "scan_best_device.h"
+#include "scan_reads_device.h"
 #include "scan_mfma_host.h"
 #include "scan_hits_host.h"
 #include "scan_multi_host.h"
 #include "scan_best_host.h"
+#include "reads_best_host.h"
 #include "pattern_host.h"
 #include "host_word.h"
 #include "host_pipe.h"
@@ -602,6 +605,131 @@ struct ScanJob {
     }
 };
 
+// ---- the best match per read of a fixed-length batch (scan_reads_device.h).  Context scratch 10 holds the per-read keys (one u64 per read, all-ones = no
+// admissible window yet) and behind them the tables (one BestTable per query, built in-stream from d_queries); a launch recorded into a hipGraph keeps
+// it (ensure_scratch: warm up with the same or larger (count, n_queries) before capturing).  The keys are set to all-ones first in the same stream,
+// the waves take their per-read minima into them and reads_finish_kernel writes query[] / pos[] / dist[].  The grid: the best match's (one workgroup
+// per CU at most x the query blocks); a batch whose period is below a segment, or too small for a round, spreads its windows over more workgroups.
+template <class HQ> struct ReadsArgsT { const HQ *queries; size_t nq; uint32_t *query, *pos; uint8_t *dist; };
+using ReadsArgs = ReadsArgsT<uint64_t>;
+
+inline ReadsGeom reads_geom(size_t period, size_t read_len, size_t k) { return ReadsGeom{period, (unsigned)(read_len - k), 1.0f / (float)period}; }
+
+template <bool PACKED, class HQ>
+int reads_setup(bitnuc_ctx *c, size_t k, size_t count, unsigned long long n, unsigned long long rounds, const ReadsArgsT<HQ> &a, unsigned long long **keys,
+                const BestTable **tabs, dim3 *grid, bitnuc_err *err) {
+    const size_t kbytes = (count * 8 + 255) & ~(size_t)255;
+    if (int st = ensure_scratch(c, 10, kbytes + a.nq * sizeof(BestTable), err)) return st;
+    *keys = reinterpret_cast<unsigned long long *>(c->scratch[10]);
+    BestTable *t = reinterpret_cast<BestTable *>(c->scratch[10] + kbytes);
+    HIPCHK(hipMemsetAsync(*keys, 0xFF, count * sizeof(uint64_t), c->stream));
+    best_tables_kernel<PACKED><<<(unsigned)a.nq, 64, 0, c->stream>>>(dev_queries(a.queries), (unsigned)k, t);
+    HIPCHK(hipGetLastError());
+    *tabs = t;
+    unsigned gx = bounded_grid(c, rounds, (kMultiBlock / 64) * kMultiRounds, kMultiGrid);
+    const unsigned long long single = (n - (rounds << 10)) / (4ull * kMultiBlock) + 1; // one-window-per-thread windows: four per thread
+    const unsigned want = (unsigned)(single < (unsigned long long)c->num_cu ? single : (unsigned long long)c->num_cu);
+    if (want > gx) gx = want;
+    *grid = dim3(gx, (unsigned)((a.nq + kMultiQB - 1) / kMultiQB), 1);
+    return BITNUC_OK;
+}
+
+template <class HQ>
+int reads_finish(bitnuc_ctx *c, const unsigned long long *keys, size_t count, const ReadsArgsT<HQ> &a, bitnuc_err *err) {
+    HIPCHK(hipGetLastError());
+    const size_t want = (count + 255) / 256, cap = (size_t)c->num_cu * 8;
+    reads_finish_kernel<<<(unsigned)(want < cap ? want : cap), 256, 0, c->stream>>>(keys, count, a.query, a.pos, a.dist);
+    HIPCHK(hipGetLastError());
+    return BITNUC_OK;
+}
+
+// d_reads at any alignment (ascii_skip); 1 <= k <= read_len, count >= 1, nq >= 1
+template <class HQ>
+int launch_reads_best(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, const ReadsArgsT<HQ> &a, unsigned long long *slot, bitnuc_err *err) {
+    const unsigned skip = ascii_skip(reads);
+    const unsigned long long n = (unsigned long long)count * read_len;
+    const unsigned long long rounds = read_len >= kReadsMinPeriod ? scan_rounds(n, skip) : 0;
+    unsigned long long *keys;
+    const BestTable *tabs;
+    dim3 grid;
+    if (int st = reads_setup<false>(c, k, count, n, rounds, a, &keys, &tabs, &grid, err)) return st;
+    reads_best_kernel<kMultiRounds><<<grid, kMultiBlock, 0, c->stream>>>(reads, n, skip, rounds, (unsigned)k, reads_geom(read_len, read_len, k), dev_queries(a.queries),
+                                                                        (unsigned)a.nq, tabs, keys, slot);
+    return reads_finish(c, keys, count, a, err);
+}
+
+// d_words 8-byte aligned (packed_skip): the period is a whole number of words
+template <class HQ>
+int launch_reads_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, const ReadsArgsT<HQ> &a, bitnuc_err *err) {
+    const unsigned skip = packed_skip(words);
+    const size_t period = 32 * words_for(read_len);
+    const unsigned long long n = (unsigned long long)count * period;
+    const unsigned long long rounds = scan_rounds(n, skip);
+    unsigned long long *keys;
+    const BestTable *tabs;
+    dim3 grid;
+    if (int st = reads_setup<true>(c, k, count, n, rounds, a, &keys, &tabs, &grid, err)) return st;
+    reads_best_packed_kernel<<<grid, kMultiBlock, 0, c->stream>>>(words, n, skip, rounds, (unsigned)k, reads_geom(period, read_len, k), dev_queries(a.queries),
+                                                                  (unsigned)a.nq, tabs, keys);
+    return reads_finish(c, keys, count, a, err);
+}
+
+// the reads calls' checks 2 - 6 (after ctx): *done = nothing to do (count == 0)
+int check_reads(size_t read_len, size_t count, size_t k, const void *queries, size_t nq, const void *query, const void *pos, const void *dist, bool *done,
+                bitnuc_err *err) {
+    *done = false;
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    constexpr size_t kLimit = (size_t)1 << 58;
+    if (read_len >= 0xFFFFFFFFull) return fail(err, BITNUC_UNSUPPORTED, read_len);
+    const size_t period = 32 * words_for(read_len); // >= read_len, < 2^33
+    if (period && count > (kLimit - 1) / period) return fail(err, BITNUC_UNSUPPORTED, read_len);
+    if (nq > BITNUC_MAX_QUERIES) return fail(err, BITNUC_UNSUPPORTED, nq);
+    *done = count == 0;
+    if (*done) return BITNUC_OK;
+    if (!query || !pos || !dist || (reinterpret_cast<uintptr_t>(query) & 3) || (reinterpret_cast<uintptr_t>(pos) & 3) || (!queries && nq) ||
+        (reinterpret_cast<uintptr_t>(queries) & 7))
+        return fail(err, BITNUC_UNSUPPORTED);
+    return BITNUC_OK;
+}
+
+inline bool reads_no_windows(size_t read_len, size_t k, size_t nq) { return k == 0 || read_len < k || nq == 0; }
+
+// no windows: every read UINT32_MAX, UINT32_MAX, 0xFF
+int reads_fill_dev(bitnuc_ctx *c, size_t count, uint32_t *d_query, uint32_t *d_pos, uint8_t *d_dist, bitnuc_err *err) {
+    HIPCHK(hipMemsetAsync(d_query, 0xFF, count * sizeof(uint32_t), c->stream));
+    HIPCHK(hipMemsetAsync(d_pos, 0xFF, count * sizeof(uint32_t), c->stream));
+    HIPCHK(hipMemsetAsync(d_dist, 0xFF, count, c->stream));
+    return BITNUC_OK;
+}
+
+// windows x queries of a batch, saturated: what the host forms' cutoff is judged on
+inline size_t reads_work(size_t read_len, size_t count, size_t k, size_t nq) { return multi_work(multi_work(read_len - k + 1, count), nq); }
+
+// The host forms' chunk loop: whole reads, `per` of them per chunk (no overlap: no window crosses a read); the queries copied once into scratch 2, a
+// chunk's query / pos arrays in scratch 1, its distances in scratch 3, copied straight to their place in the outputs.  `launch(r0, m, a)` runs the
+// reads [r0, r0 + m) with a's device arrays.  Stops at the first failing chunk (drain: its first invalid byte, absolute through the slot's base).
+template <class Launch>
+int reads_host_loop(bitnuc_ctx *c, size_t count, size_t per, const uint64_t *queries, size_t nq, uint32_t *query, uint32_t *pos, uint8_t *dist, bitnuc_err *err,
+                    Launch launch) {
+    const size_t pm = count < per ? count : per;
+    if (int st = ensure_scratch(c, 1, pm * 8, err)) return st;
+    if (int st = ensure_scratch(c, 2, nq * 8, err)) return st;
+    if (int st = ensure_scratch(c, 3, pm < 64 ? 64 : pm, err)) return st;
+    HIPCHK(hipMemcpyAsync(c->scratch[2], queries, nq * 8, hipMemcpyHostToDevice, c->stream));
+    uint32_t *d_query = reinterpret_cast<uint32_t *>(c->scratch[1]), *d_pos = d_query + pm;
+    const ReadsArgs a{reinterpret_cast<const uint64_t *>(c->scratch[2]), nq, d_query, d_pos, c->scratch[3]};
+    for (size_t r0 = 0; r0 < count; r0 += per) {
+        const size_t m = count - r0 < per ? count - r0 : per;
+        if (int st = launch(r0, m, a)) return st;
+        HIPCHK(hipMemcpyAsync(query + r0, d_query, m * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(pos + r0, d_pos, m * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(dist + r0, c->scratch[3], m, hipMemcpyDeviceToHost, c->stream));
+        bitnuc_err e;
+        if (int st = drain(c, &e)) { if (err) *err = e; return st; }
+    }
+    return BITNUC_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -1078,6 +1206,88 @@ int bitnuc_kmer_hdist_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t n
         const PackedChunk ch = packed_chunk(i0 / 32, n, k);
         HIPCHK(hipMemcpyAsync(c->scratch[0], words + ch.w0, ch.words * 8, hipMemcpyHostToDevice, c->stream));
         return launch_best_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), ch.bases, k, a, err);
+    });
+}
+
+// ---- the best match per read of a fixed-length batch ---------------------------------------------------------------------------
+int bitnuc_reads_hdist_best_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const uint64_t *d_queries, size_t n_queries,
+                                  uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    bool done;
+    if (int st = check_reads(read_len, count, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist, &done, err)) return st;
+    if (done) return BITNUC_OK;
+    DeviceGuard g(c->device);
+    if (reads_no_windows(read_len, k, n_queries)) return reads_fill_dev(c, count, d_best_query, d_best_pos, d_best_dist, err);
+    if (!d_reads) return fail(err, BITNUC_UNSUPPORTED);
+    unsigned long long *slot;
+    if (int st = take_slot(c, 0, &slot, err)) return st;
+    return launch_reads_best(c, d_reads, read_len, count, k, ReadsArgs{d_queries, n_queries, d_best_query, d_best_pos, d_best_dist}, slot, err);
+}
+
+int bitnuc_reads_hdist_best_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, const uint64_t *d_queries,
+                                         size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    bool done;
+    if (int st = check_reads(read_len, count, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist, &done, err)) return st;
+    if (done) return BITNUC_OK;
+    DeviceGuard g(c->device);
+    if (reads_no_windows(read_len, k, n_queries)) return reads_fill_dev(c, count, d_best_query, d_best_pos, d_best_dist, err);
+    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    return launch_reads_best_packed(c, d_words, read_len, count, k, ReadsArgs{d_queries, n_queries, d_best_query, d_best_pos, d_best_dist}, err);
+}
+
+int bitnuc_reads_hdist_best(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
+                            uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err) {
+    clear_err(err);
+    bool done;
+    if (int st = check_reads(read_len, count, k, queries, n_queries, best_query, best_pos, best_dist, &done, err)) return st;
+    if (done) return BITNUC_OK;
+    if (reads_no_windows(read_len, k, n_queries)) { bitnuc_host::reads_best_fill(count, best_query, best_pos, best_dist); return BITNUC_OK; }
+    if (!reads) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, reads_work(read_len, count, k, n_queries))) {
+        const long long bad = bitnuc_host::reads_hdist_best_small(reads, read_len, count, k, queries, n_queries, best_query, best_pos, best_dist);
+        if (bad >= 0) {
+            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = reads[bad]; err->index = (uint64_t)bad; }
+            return BITNUC_INVALID_BASE;
+        }
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    const size_t per = read_len < kHostChunk ? kHostChunk / read_len : 1, pm = count < per ? count : per; // whole reads per chunk
+    if (int st = ensure_scratch(c, 0, pm * read_len + 64, err)) return st;
+    return reads_host_loop(c, count, per, queries, n_queries, best_query, best_pos, best_dist, err, [&](size_t r0, size_t m, const ReadsArgs &a) {
+        HIPCHK(hipMemcpyAsync(c->scratch[0], reads + r0 * read_len, m * read_len, hipMemcpyHostToDevice, c->stream));
+        unsigned long long *slot;
+        if (int st = take_slot(c, r0 * read_len, &slot, err)) return st;
+        return launch_reads_best(c, c->scratch[0], read_len, m, k, a, slot, err);
+    });
+}
+
+int bitnuc_reads_hdist_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
+                                   uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err) {
+    clear_err(err);
+    bool done;
+    if (int st = check_reads(read_len, count, k, queries, n_queries, best_query, best_pos, best_dist, &done, err)) return st;
+    if (done) return BITNUC_OK;
+    if (reads_no_windows(read_len, k, n_queries)) { bitnuc_host::reads_best_fill(count, best_query, best_pos, best_dist); return BITNUC_OK; }
+    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, reads_work(read_len, count, k, n_queries))) {
+        bitnuc_host::reads_hdist_best_packed_small(words, read_len, count, k, queries, n_queries, best_query, best_pos, best_dist);
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    const size_t wpr = words_for(read_len);
+    const size_t per = wpr < kPackedChunkWords ? kPackedChunkWords / wpr : 1, pm = count < per ? count : per; // whole reads per chunk
+    if (int st = ensure_scratch(c, 0, pm * wpr * 8, err)) return st;
+    return reads_host_loop(c, count, per, queries, n_queries, best_query, best_pos, best_dist, err, [&](size_t r0, size_t m, const ReadsArgs &a) {
+        HIPCHK(hipMemcpyAsync(c->scratch[0], words + r0 * wpr, m * wpr * 8, hipMemcpyHostToDevice, c->stream));
+        return launch_reads_best_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), read_len, m, k, a, err);
     });
 }
 

@@ -2,7 +2,8 @@
 //   runtime.hip   the context: device + stream, error slots and their lifetime, scratch, knobs       (this header's functions)
 //   codec.hip     bulk encode / decode, the single-word API, the pipelined host-pointer path, probes  (codec_device.h)
 //   kmer.hip      k-mer batches, sliding scan (matrix cores, ASCII and packed input), bulk hdist     (kmer_device.h, scan_mfma_device.h, scan_packed_device.h,
-//                                                                                                      scan_hits_device.h, scan_multi_device.h, scan_best_device.h)
+//                                                                                                      scan_hits_device.h, scan_multi_device.h, scan_best_device.h,
+//                                                                                                      scan_reads_device.h)
 //   batch.hip     ragged / planned / fixed-length batches of reads                                   (batch_device.h)
 //   analysis.hip  base counts, many-pair hdist, split_packed                                         (analysis_device.h)
 //   comm.hip      RCCL all-gather of the packed words, xGMI link probe
@@ -125,10 +126,11 @@ struct bitnuc_ctx {
     int n_cap = 0;
     std::vector<bitnuc_err> deferred; // data errors found by implicit drains (host-pointer calls start from an empty ring), oldest first: one per bitnuc_ctx_sync
     // ---- scratch ----
-    // [8]: the multi-query count's per-query tables (kmer.hip launch_count_multi); [9]: the best match's keys and per-query tables (kmer.hip best_setup)
-    uint8_t *scratch[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t scratch_cap[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    bool scratch_in_graph[10] = {false, false, false, false, false, false, false, false, false, false}; // handed to a launch recorded into a hipGraph: never freed before the context
+    // [8]: the multi-query count's per-query tables (kmer.hip launch_count_multi); [9]: the best match's keys and per-query tables (kmer.hip best_setup);
+    // [10]: the per-read best match's keys (one per read) and per-query tables (kmer.hip reads_setup)
+    uint8_t *scratch[11] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t scratch_cap[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    bool scratch_in_graph[11] = {false, false, false, false, false, false, false, false, false, false, false}; // handed to a launch recorded into a hipGraph: never freed before the context
     std::vector<uint8_t *> retired_scratch; // ... outgrown since: alive until bitnuc_ctx_destroy (a replay still writes through them)
     uint32_t *d_sink = nullptr;
     unsigned long long *d_acc = nullptr; // accumulators of the single-launch reductions, zero between launches: [0..2] base_counts C,G,T; [4] hdist (u32); [5] scan count; [6] packed scan count

@@ -296,6 +296,24 @@ class Context {
             return NucleotideError::from_c(e);
         return std::make_pair(std::move(pos), std::move(dist));
     }
+    // the best match per read of a fixed-length batch: (query, pos, dist) per read, the smallest (distance, query, offset) over the windows inside it
+    struct ReadsBest { std::vector<uint32_t> query, pos; std::vector<uint8_t> dist; };
+    Result<ReadsBest> reads_hdist_best(Bytes reads, size_t read_len, size_t k, const std::vector<uint64_t> &queries) const {
+        const size_t count = read_len ? reads.len / read_len : 0;
+        ReadsBest b{std::vector<uint32_t>(count), std::vector<uint32_t>(count), std::vector<uint8_t>(count)};
+        bitnuc_err e;
+        if (bitnuc_reads_hdist_best(ctx_, reads.ptr, read_len, count, k, queries.data(), queries.size(), b.query.data(), b.pos.data(), b.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
+    // ... of the packed words encode_fixed writes: words.len >= count * ceil(read_len / 32)
+    Result<ReadsBest> reads_hdist_best_packed(Words words, size_t read_len, size_t count, size_t k, const std::vector<uint64_t> &queries) const {
+        ReadsBest b{std::vector<uint32_t>(count), std::vector<uint32_t>(count), std::vector<uint8_t>(count)};
+        bitnuc_err e;
+        if (bitnuc_reads_hdist_best_packed(ctx_, words.ptr, read_len, count, k, queries.data(), queries.size(), b.query.data(), b.pos.data(), b.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
     Result<std::vector<uint64_t>> kmer_hdist_hits_packed(Words words, size_t n, size_t k, uint64_t query, unsigned tau, std::vector<uint8_t> *hit_dist = nullptr) const {
         uint64_t total = 0;
         bitnuc_err e;

@@ -354,6 +354,36 @@ int bitnuc_decode_fixed_dev(bitnuc_ctx *ctx, const uint64_t *d_words, size_t rea
 int bitnuc_encode_fixed(bitnuc_ctx *ctx, const uint8_t *seq, size_t read_len, size_t stride, size_t count, uint64_t *out, bitnuc_err *err);
 int bitnuc_decode_fixed(bitnuc_ctx *ctx, const uint64_t *words, size_t read_len, size_t stride, size_t count, uint8_t *out, bitnuc_err *err);
 
+/* ---- best match per read of a fixed-length batch (demultiplexing: which of Q barcodes / adapters / primers a read carries, where, and
+ * with how many mismatches) ----
+ * For every read r: best_dist[r] = the minimum over q < n_queries and 0 <= i <= read_len - k of hdist_scalar(as_2bit(read_r[i .. i+k]),
+ * queries[q], k) -- only windows that lie wholly inside the read; a window never crosses into the next read --, ties by the smallest q, then the
+ * smallest i; best_query[r] and best_pos[r] are that q and i.  Query bits above 2k are ignored.  Deterministic.  Exactly [0, count) of each output is
+ * written; best_dist may have any byte offset.  A read without a window, or no queries (k == 0, read_len < k, n_queries == 0): UINT32_MAX,
+ * UINT32_MAX, 0xFF.
+ * Input.  ASCII: read r is reads[r*read_len .. (r+1)*read_len), back to back, at any byte alignment, either case.  Reads with separators between them
+ * (newline-separated, ...) go through bitnuc_encode_fixed_dev, which skips the separators, and then the packed form.  Packed: what encode_fixed
+ * writes -- read r's wpr = ceil(read_len/32) words at words[r*wpr ..], 8-byte aligned; the bits above 2*read_len in a read's last word are ignored.
+ * As decode_fixed, the call trusts that count*wpr words are present.
+ * Checks, in this order: (1) ctx NULL -> UNSUPPORTED (the host forms accept NULL below the host cutoff); (2) k > 32 -> SEQUENCE_TOO_LONG(k);
+ * (3) read_len >= 2^32 - 1, or count*read_len or count*wpr*32 not below 2^58 -> UNSUPPORTED (value = read_len); (4) n_queries > BITNUC_MAX_QUERIES
+ * -> UNSUPPORTED (value = n_queries); (5) count == 0 -> OK, nothing written; (6) an output NULL, best_query / best_pos not 4-byte aligned, queries
+ * NULL with n_queries > 0 or not 8-byte aligned -> UNSUPPORTED; (7) no windows -> OK with the fill above in every read, nothing read or validated;
+ * (8) reads NULL, or words NULL or not 8-byte aligned -> UNSUPPORTED.
+ * ASCII: a non-ACGT byte -> INVALID_BASE with the first invalid byte in buffer order (index = its byte offset in reads); the _async form latches
+ * it once per call for bitnuc_ctx_sync(), the outputs are then unspecified.
+ * The _async forms have the _dev contract (device pointers for everything, the context's stream, no host synchronisation but the growth of context
+ * scratch) and can be captured into a hipGraph after a warm-up with the same or larger (count, n_queries).  The host forms judge
+ * windows x n_queries against the host cutoff; above it they run through the context in chunks of whole reads. */
+int bitnuc_reads_hdist_best_async(bitnuc_ctx *ctx, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const uint64_t *d_queries, size_t n_queries,
+                                  uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err);
+int bitnuc_reads_hdist_best_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t read_len, size_t count, size_t k, const uint64_t *d_queries,
+                                         size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err);
+int bitnuc_reads_hdist_best(bitnuc_ctx *ctx, const uint8_t *reads, size_t read_len, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
+                            uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err);
+int bitnuc_reads_hdist_best_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t read_len, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
+                                   uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err);
+
 /* ---- analysis on packed words (the callers just above the codec) ------ */
 /* BaseCount::base_counts / GCContent::gc_content of a packed sequence
  * (src/utils/analysis.rs:7-39: the reference decodes to ASCII, then counts bytes): counts[] =

@@ -139,6 +139,11 @@ extern "C" {
     pub fn bitnuc_kmer_hdist_best_packed_async(ctx: *mut bitnuc_ctx, d_words: *const u64, n_words: usize, n: usize, k: usize, d_queries: *const u64, n_queries: usize, d_pos: *mut u64, d_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_kmer_hdist_best(ctx: *mut bitnuc_ctx, reference: *const u8, n: usize, k: usize, queries: *const u64, n_queries: usize, pos: *mut u64, dist: *mut u8, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_kmer_hdist_best_packed(ctx: *mut bitnuc_ctx, words: *const u64, n_words: usize, n: usize, k: usize, queries: *const u64, n_queries: usize, pos: *mut u64, dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    // the best match per read of a fixed-length batch
+    pub fn bitnuc_reads_hdist_best_async(ctx: *mut bitnuc_ctx, d_reads: *const u8, read_len: usize, count: usize, k: usize, d_queries: *const u64, n_queries: usize, d_best_query: *mut u32, d_best_pos: *mut u32, d_best_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_reads_hdist_best_packed_async(ctx: *mut bitnuc_ctx, d_words: *const u64, read_len: usize, count: usize, k: usize, d_queries: *const u64, n_queries: usize, d_best_query: *mut u32, d_best_pos: *mut u32, d_best_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_reads_hdist_best(ctx: *mut bitnuc_ctx, reads: *const u8, read_len: usize, count: usize, k: usize, queries: *const u64, n_queries: usize, best_query: *mut u32, best_pos: *mut u32, best_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_reads_hdist_best_packed(ctx: *mut bitnuc_ctx, words: *const u64, read_len: usize, count: usize, k: usize, queries: *const u64, n_queries: usize, best_query: *mut u32, best_pos: *mut u32, best_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
     // pattern queries (a set of bases per position): the converters and the twins of count_multi / best / hits
     pub fn bitnuc_pattern_from_iupac(letters: *const u8, k: usize, out: *mut bitnuc_pattern, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_pattern_from_2bit(query: u64, k: usize, out: *mut bitnuc_pattern, err: *mut bitnuc_err) -> c_int;

@@ -319,6 +319,29 @@ pub fn kmer_hdist_best_packed(words: &[u64], n: usize, k: usize, queries: &[u64]
     if st == ffi::BITNUC_OK { Ok((pos, dist)) } else { Err(to_err(&e)) }
 }
 
+/// The best match per read of `count` back-to-back reads of `read_len` bases: `(query, pos, dist)` with the smallest (distance, query, offset)
+/// over all queries and the windows that lie wholly inside each read; a read without a window gets `u32::MAX`, `u32::MAX`, `255`.
+pub fn reads_hdist_best(reads: &[u8], read_len: usize, k: usize, queries: &[u64]) -> Result<(Vec<u32>, Vec<u32>, Vec<u8>), NucleotideError> {
+    let count = if read_len == 0 { 0 } else { reads.len() / read_len };
+    let (mut query, mut pos, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_hdist_best(c, reads.as_ptr(), read_len, count, k, queries.as_ptr(), queries.len(), query.as_mut_ptr(), pos.as_mut_ptr(), dist.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok((query, pos, dist)) } else { Err(to_err(&e)) }
+}
+
+/// `reads_hdist_best` of the packed words `encode_fixed` writes (`ceil(read_len / 32)` words per read), without decoding them.
+pub fn reads_hdist_best_packed(words: &[u64], read_len: usize, count: usize, k: usize, queries: &[u64]) -> Result<(Vec<u32>, Vec<u32>, Vec<u8>), NucleotideError> {
+    assert!(words.len() >= count * ((read_len + 31) / 32), "count reads of ceil(read_len / 32) words each");
+    let (mut query, mut pos, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_hdist_best_packed(c, words.as_ptr(), read_len, count, k, queries.as_ptr(), queries.len(), query.as_mut_ptr(), pos.as_mut_ptr(), dist.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok((query, pos, dist)) } else { Err(to_err(&e)) }
+}
+
 /// A pattern query: a set of bases per position (`allow[c]` bit `i` set <=> base code `c` matches at position `i`).
 pub use ffi::bitnuc_pattern as Pattern;
 
