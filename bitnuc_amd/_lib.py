@@ -81,6 +81,14 @@ SIGNATURES = {
     "bitnuc_kmer_pattern_best_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _ERR]),
     "bitnuc_kmer_pattern_best": (C.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _ERR]),
     "bitnuc_kmer_pattern_best_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _ERR]),
+    "bitnuc_kmer_hdist_hist_async": (C.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _P, _ERR]),
+    "bitnuc_kmer_hdist_hist_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _SZ, _P, _ERR]),
+    "bitnuc_kmer_hdist_hist": (C.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _P, _ERR]),
+    "bitnuc_kmer_hdist_hist_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _SZ, _P, _ERR]),
+    "bitnuc_kmer_pattern_hist_async": (C.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _P, _ERR]),
+    "bitnuc_kmer_pattern_hist_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _SZ, _P, _ERR]),
+    "bitnuc_kmer_pattern_hist": (C.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _P, _ERR]),
+    "bitnuc_kmer_pattern_hist_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _SZ, _P, _ERR]),
     "bitnuc_kmer_pattern_hits_async": (C.c_int, [_P, _P, _SZ, _SZ, _P, C.c_uint, _P, _P, _SZ, _P, _ERR]),
     "bitnuc_kmer_pattern_hits_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, C.c_uint, _P, _P, _SZ, _P, _ERR]),
     "bitnuc_kmer_pattern_hits": (C.c_int, [_P, _P, _SZ, _SZ, _P, C.c_uint, _P, _P, _SZ, C.POINTER(_U64), _ERR]),

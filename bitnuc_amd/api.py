@@ -473,6 +473,41 @@ class Context:
         w = _as_u64(words)
         return self._pattern_best(self._lib.bitnuc_kmer_pattern_best_packed, (_ptr(w), w.size, int(n_bases), int(k)), patterns, k)
 
+    # -- the mismatch histogram per query: windows at each distance 0 .. n_bins - 1 in one pass --
+    def _hist(self, fn, head, q, nq, n_bins):
+        n_bins = int(n_bins)
+        out = np.empty((nq, min(max(n_bins, 0), 16)), dtype=np.uint64)  # (a refused n_bins writes nothing)
+        err = L.BitnucErr()
+        if fn(self._h, *head, _ptr(q), nq, n_bins, _ptr(out), C.byref(err)) != L.OK:
+            _raise(err)
+        return out
+
+    def kmer_hdist_hist(self, ref, k, queries, n_bins):
+        """hist[q, d] = the number of windows of `ref` at Hamming distance exactly d from queries[q], d < n_bins <= 16, one pass for all queries
+        -> (n_queries, n_bins) np.uint64; a window at n_bins or more mismatches is counted nowhere."""
+        s = _as_u8(ref)
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.uint64).reshape(-1))  # a scalar query: Q = 1
+        return self._hist(self._lib.bitnuc_kmer_hdist_hist, (_ptr(s), s.size, int(k)), q, q.size, n_bins)
+
+    def kmer_hdist_hist_packed(self, words, n_bases, k, queries, n_bins):
+        """kmer_hdist_hist of the packed sequence `words` holding `n_bases` bases, without decoding it."""
+        w = _as_u64(words)
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.uint64).reshape(-1))
+        return self._hist(self._lib.bitnuc_kmer_hdist_hist_packed, (_ptr(w), w.size, int(n_bases), int(k)), q, q.size, n_bins)
+
+    def kmer_pattern_hist(self, ref, k, patterns, n_bins):
+        """hist[q, d] = the number of windows j of `ref` with pdist(j) == d under patterns[q], d < n_bins <= 16 -> (n_queries, n_bins) np.uint64.
+        patterns: a (Q, 4) np.uint32 array (pattern_from_iupac / pattern_from_2bit) or a list of IUPAC strings of length k."""
+        s = _as_u8(ref)
+        p = self._patterns(patterns, k)
+        return self._hist(self._lib.bitnuc_kmer_pattern_hist, (_ptr(s), s.size, int(k)), p, p.shape[0], n_bins)
+
+    def kmer_pattern_hist_packed(self, words, n_bases, k, patterns, n_bins):
+        """kmer_pattern_hist of the packed sequence `words` holding `n_bases` bases, without decoding it."""
+        w = _as_u64(words)
+        p = self._patterns(patterns, k)
+        return self._hist(self._lib.bitnuc_kmer_pattern_hist_packed, (_ptr(w), w.size, int(n_bases), int(k)), p, p.shape[0], n_bins)
+
     def kmer_pattern_hits(self, ref, k, pattern, tau, with_dist=False):
         """Positions (np.uint64, ascending) of the windows of `ref` with pdist <= tau under the pattern (a (4,) np.uint32 array or an IUPAC string);
         with_dist: (positions, np.uint8 distances)."""
@@ -759,6 +794,27 @@ class Context:
         """The best match per pattern on packed words in device memory (8-byte aligned)."""
         self._call_dev(self._lib.bitnuc_kmer_pattern_best_packed_async, _dev_ptr(d_words), int(n_words), int(n), int(k), _dev_ptr(d_patterns), int(n_queries),
                        _dev_ptr(d_pos), _dev_ptr(d_dist))
+
+    def kmer_hdist_hist_async(self, d_ref, n, k, d_queries, n_queries, n_bins, d_hist):
+        """The mismatch histogram of n_queries queries at once: d_hist[q * n_bins + d] (u64) = windows at distance exactly d < n_bins from d_queries[q]
+        (u64).  Asynchronous on the context's stream, as the _dev calls."""
+        self._call_dev(self._lib.bitnuc_kmer_hdist_hist_async, _dev_ptr(d_ref), int(n), int(k), _dev_ptr(d_queries), int(n_queries), int(n_bins),
+                       _dev_ptr(d_hist))
+
+    def kmer_hdist_hist_packed_async(self, d_words, n_words, n, k, d_queries, n_queries, n_bins, d_hist):
+        """The mismatch histogram per query on packed words in device memory (8-byte aligned)."""
+        self._call_dev(self._lib.bitnuc_kmer_hdist_hist_packed_async, _dev_ptr(d_words), int(n_words), int(n), int(k), _dev_ptr(d_queries), int(n_queries),
+                       int(n_bins), _dev_ptr(d_hist))
+
+    def kmer_pattern_hist_async(self, d_ref, n, k, d_patterns, n_queries, n_bins, d_hist):
+        """d_hist[q * n_bins + d] (u64) = windows with pdist exactly d < n_bins under d_patterns[q]."""
+        self._call_dev(self._lib.bitnuc_kmer_pattern_hist_async, _dev_ptr(d_ref), int(n), int(k), _dev_ptr(d_patterns), int(n_queries), int(n_bins),
+                       _dev_ptr(d_hist))
+
+    def kmer_pattern_hist_packed_async(self, d_words, n_words, n, k, d_patterns, n_queries, n_bins, d_hist):
+        """The mismatch histogram per pattern on packed words in device memory (8-byte aligned)."""
+        self._call_dev(self._lib.bitnuc_kmer_pattern_hist_packed_async, _dev_ptr(d_words), int(n_words), int(n), int(k), _dev_ptr(d_patterns), int(n_queries),
+                       int(n_bins), _dev_ptr(d_hist))
 
     def kmer_pattern_hits_async(self, d_ref, n, k, pattern, tau, d_pos, d_hit_dist, cap, d_n_hits):
         """The positions of the windows with pdist <= tau -> d_pos[0 .. min(cap, total)) (u64, ascending), their distances at d_hit_dist (None: not

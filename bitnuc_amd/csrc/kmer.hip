@@ -2,7 +2,7 @@
 // <= 32-mers (BASELINE config 3, README.md:52-56), every window of a sequence (src/lib.rs:170-173), the sliding pack +
 // Hamming scan (config 5: packing/mod.rs:80-110 o hamming/scalar.rs:11-48) and bulk hdist (hamming/multi.rs:121-160).
 // Kernels: kmer_device.h; config 5 on the matrix cores: scan_mfma_device.h; the same scan and count on packed words: scan_packed_device.h; the hit
-// lists of both: scan_hits_device.h; the count for many queries at once: scan_multi_device.h; the best match per query: scan_best_device.h; the best match per read of a
+// lists of both: scan_hits_device.h; the count for many queries at once: scan_multi_device.h; the best match per query: scan_best_device.h; the mismatch histogram per query: scan_hist_device.h; the best match per read of a
 // fixed-length batch: scan_reads_device.h.
 #include "runtime.h"
 #include "kmer_device.h"
@@ -12,11 +12,13 @@
 #include "scan_multi_device.h"
 #include "scan_best_device.h"
 #include "scan_reads_device.h"
+#include "scan_hist_device.h"
 #include "scan_mfma_host.h"
 #include "scan_hits_host.h"
 #include "scan_multi_host.h"
 #include "scan_best_host.h"
 #include "reads_best_host.h"
+#include "scan_hist_host.h"
 #include "pattern_host.h"
 #include "host_word.h"
 #include "host_pipe.h"
@@ -543,6 +545,95 @@ int best_host_loop(bitnuc_ctx *c, size_t nwin, size_t per, const HQ *queries, si
     return BITNUC_OK;
 }
 
+// ---- the mismatch histogram per query (scan_hist_device.h).  The tables are the best match's and live where its tables live, in context scratch 9 (behind
+// the space of its keys: the two calls run in stream order, as the two users of scratch 7 do); a launch recorded into a hipGraph keeps it (ensure_scratch:
+// warm up with the same n_queries before capturing).  hist[] is zeroed first in the same stream, then every workgroup adds its per-(query, bin) sums.  The
+// grid: the best match's.  n_bins <= 8 runs the one-tier kernels, 9 - 16 the two-tier ones.
+template <class HQ> struct HistArgsT { const HQ *queries; size_t nq, n_bins; unsigned long long *hist; };
+static_assert(BITNUC_HIST_MAX_BINS == kHistMaxBins, "the kernels' two tiers of eight bins");
+
+template <bool PACKED, class HQ>
+int hist_setup(bitnuc_ctx *c, size_t k, const HistArgsT<HQ> &a, unsigned long long rounds, const BestTable **tabs, dim3 *grid, bitnuc_err *err) {
+    const size_t kbytes = (a.nq * 8 + 255) & ~(size_t)255;
+    if (int st = ensure_scratch(c, 9, kbytes + a.nq * sizeof(BestTable), err)) return st;
+    BestTable *t = reinterpret_cast<BestTable *>(c->scratch[9] + kbytes);
+    HIPCHK(hipMemsetAsync(a.hist, 0, a.nq * a.n_bins * sizeof(uint64_t), c->stream));
+    best_tables_kernel<PACKED><<<(unsigned)a.nq, 64, 0, c->stream>>>(dev_queries(a.queries), (unsigned)k, t);
+    HIPCHK(hipGetLastError());
+    *tabs = t;
+    *grid = dim3(bounded_grid(c, rounds, (kMultiBlock / 64) * kMultiRounds, kMultiGrid), (unsigned)((a.nq + kMultiQB - 1) / kMultiQB), 1);
+    return BITNUC_OK;
+}
+
+// d_ref at any alignment (ascii_skip)
+template <class HQ>
+int launch_hist(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const HistArgsT<HQ> &a, unsigned long long *slot, bitnuc_err *err) {
+    const unsigned skip = ascii_skip(ref);
+    const BestTable *tabs;
+    dim3 grid;
+    if (int st = hist_setup<false>(c, k, a, scan_rounds(n, skip), &tabs, &grid, err)) return st;
+    if (a.n_bins <= 8)
+        kmer_hist_kernel<kMultiRounds, 1><<<grid, kMultiBlock, 0, c->stream>>>(ref, n, skip, (unsigned)k, dev_queries(a.queries), (unsigned)a.nq, (unsigned)a.n_bins, tabs,
+                                                                            a.hist, slot);
+    else
+        kmer_hist_kernel<kMultiRounds, 2><<<grid, kMultiBlock, 0, c->stream>>>(ref, n, skip, (unsigned)k, dev_queries(a.queries), (unsigned)a.nq, (unsigned)a.n_bins, tabs,
+                                                                            a.hist, slot);
+    HIPCHK(hipGetLastError());
+    return BITNUC_OK;
+}
+
+// d_words 8-byte aligned (packed_skip)
+template <class HQ>
+int launch_hist_packed(bitnuc_ctx *c, const uint64_t *words, size_t n, size_t k, const HistArgsT<HQ> &a, bitnuc_err *err) {
+    const unsigned skip = packed_skip(words);
+    const BestTable *tabs;
+    dim3 grid;
+    if (int st = hist_setup<true>(c, k, a, scan_rounds(n, skip), &tabs, &grid, err)) return st;
+    if (a.n_bins <= 8)
+        packed_hist_kernel<1><<<grid, kMultiBlock, 0, c->stream>>>(words, n, skip, (unsigned)k, dev_queries(a.queries), (unsigned)a.nq, (unsigned)a.n_bins, tabs, a.hist);
+    else
+        packed_hist_kernel<2><<<grid, kMultiBlock, 0, c->stream>>>(words, n, skip, (unsigned)k, dev_queries(a.queries), (unsigned)a.nq, (unsigned)a.n_bins, tabs, a.hist);
+    HIPCHK(hipGetLastError());
+    return BITNUC_OK;
+}
+
+// the histogram calls' checks 4 - 7 (after ctx, k and the packed word count): the number of bins, n_queries == 0 -> OK (*none), too many queries, the two
+// arrays (qmask: 7 for exact queries, 3 for patterns)
+int check_hist(const void *queries, size_t nq, size_t n_bins, const void *hist, bool *none, bitnuc_err *err, uintptr_t qmask) {
+    *none = false;
+    if (n_bins == 0 || n_bins > BITNUC_HIST_MAX_BINS) return fail(err, BITNUC_UNSUPPORTED, n_bins);
+    *none = nq == 0;
+    if (*none) return BITNUC_OK;
+    if (nq > BITNUC_MAX_QUERIES) return fail(err, BITNUC_UNSUPPORTED, nq);
+    if (!hist || (reinterpret_cast<uintptr_t>(hist) & 7) || !queries || (reinterpret_cast<uintptr_t>(queries) & qmask)) return fail(err, BITNUC_UNSUPPORTED);
+    return BITNUC_OK;
+}
+template <class HQ> constexpr uintptr_t hist_qmask() { return sizeof(HQ) == 8 ? 7 : 3; }
+// the queries as the host code takes them (scan_hist_host.h: window_dist's two kinds)
+inline const uint64_t *host_queries(const uint64_t *q) { return q; }
+inline const PatternSets *host_queries(const bitnuc_pattern *q) { return reinterpret_cast<const PatternSets *>(q); }
+
+// The host forms' chunk loop: the queries copied once into scratch 2, the chunk's histogram in scratch 1; `launch(i0, a)` runs the chunk of windows starting
+// at i0 with a's device arrays.  Sums per bin; stops at the first failing chunk (drain: its first invalid byte).
+template <class HQ, class Launch>
+int hist_host_loop(bitnuc_ctx *c, size_t nwin, size_t per, const HQ *queries, size_t nq, size_t n_bins, uint64_t *hist, bitnuc_err *err, Launch launch) {
+    const size_t cells = nq * n_bins;
+    if (int st = ensure_scratch(c, 1, cells * 8, err)) return st;
+    if (int st = ensure_scratch(c, 2, nq * sizeof(HQ), err)) return st;
+    HIPCHK(hipMemcpyAsync(c->scratch[2], queries, nq * sizeof(HQ), hipMemcpyHostToDevice, c->stream));
+    const HistArgsT<HQ> a{reinterpret_cast<const HQ *>(c->scratch[2]), nq, n_bins, reinterpret_cast<unsigned long long *>(c->scratch[1])};
+    std::vector<uint64_t> part(cells), total(cells, 0);
+    for (size_t i0 = 0; i0 < nwin; i0 += per) {
+        if (int st = launch(i0, a)) return st;
+        HIPCHK(hipMemcpyAsync(part.data(), c->scratch[1], cells * 8, hipMemcpyDeviceToHost, c->stream));
+        bitnuc_err e;
+        if (int st = drain(c, &e)) { if (err) *err = e; return st; }
+        for (size_t i = 0; i < cells; ++i) total[i] += part[i];
+    }
+    memcpy(hist, total.data(), cells * 8);
+    return BITNUC_OK;
+}
+
 // host-pointer packed calls: chunks of whole words; chunk w0 holds the windows [32 w0, 32 (w0 + cw)) and the k - 1 bases after them (one more word)
 constexpr size_t kPackedChunkWords = kHostChunk / 32;
 struct PackedChunk { size_t w0, words, bases, nwin; };
@@ -728,6 +819,104 @@ int reads_host_loop(bitnuc_ctx *c, size_t count, size_t per, const uint64_t *que
         if (int st = drain(c, &e)) { if (err) *err = e; return st; }
     }
     return BITNUC_OK;
+}
+
+// ---- the mismatch histogram per query: the four forms, once for exact queries (uint64_t) and patterns (bitnuc_pattern) -----------------------------
+template <class HQ>
+int hist_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const HQ *d_queries, size_t n_queries, size_t n_bins, uint64_t *d_hist, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    bool none;
+    if (int st = check_hist(d_queries, n_queries, n_bins, d_hist, &none, err, hist_qmask<HQ>())) return st;
+    if (none) return BITNUC_OK;
+    DeviceGuard g(c->device);
+    if (k == 0 || n < k) { // no windows
+        HIPCHK(hipMemsetAsync(d_hist, 0, n_queries * n_bins * sizeof(uint64_t), c->stream));
+        return BITNUC_OK;
+    }
+    if (!d_ref) return fail(err, BITNUC_UNSUPPORTED);
+    unsigned long long *slot;
+    if (int st = take_slot(c, 0, &slot, err)) return st;
+    return launch_hist(c, d_ref, n, k, HistArgsT<HQ>{d_queries, n_queries, n_bins, reinterpret_cast<unsigned long long *>(d_hist)}, slot, err);
+}
+
+template <class HQ>
+int hist_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const HQ *d_queries, size_t n_queries, size_t n_bins,
+                      uint64_t *d_hist, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
+    bool none;
+    if (int st = check_hist(d_queries, n_queries, n_bins, d_hist, &none, err, hist_qmask<HQ>())) return st;
+    if (none) return BITNUC_OK;
+    DeviceGuard g(c->device);
+    if (k == 0 || n < k) {
+        HIPCHK(hipMemsetAsync(d_hist, 0, n_queries * n_bins * sizeof(uint64_t), c->stream));
+        return BITNUC_OK;
+    }
+    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    return launch_hist_packed(c, d_words, n, k, HistArgsT<HQ>{d_queries, n_queries, n_bins, reinterpret_cast<unsigned long long *>(d_hist)}, err);
+}
+
+template <class HQ>
+int hist_host(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const HQ *queries, size_t n_queries, size_t n_bins, uint64_t *hist, bitnuc_err *err) {
+    clear_err(err);
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    bool none;
+    if (int st = check_hist(queries, n_queries, n_bins, hist, &none, err, hist_qmask<HQ>())) return st;
+    if (none) return BITNUC_OK;
+    if (k == 0 || n < k) { memset(hist, 0, n_queries * n_bins * sizeof(uint64_t)); return BITNUC_OK; }
+    if (!ref) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, multi_work(n - k + 1, n_queries))) {
+        const long long bad = bitnuc_host::kmer_hdist_hist_small(ref, n, k, host_queries(queries), n_queries, n_bins, hist);
+        if (bad >= 0) {
+            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = ref[bad]; err->index = (uint64_t)bad; }
+            return BITNUC_INVALID_BASE;
+        }
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    // chunks of kHostChunk windows + their k - 1 halo bases
+    if (int st = ensure_scratch(c, 0, kHostChunk + 64, err)) return st;
+    const size_t nwin = n - k + 1;
+    return hist_host_loop(c, nwin, kHostChunk, queries, n_queries, n_bins, hist, err, [&](size_t i0, const HistArgsT<HQ> &a) {
+        const size_t m = nwin - i0 < kHostChunk ? nwin - i0 : kHostChunk;
+        HIPCHK(hipMemcpyAsync(c->scratch[0], ref + i0, m + k - 1, hipMemcpyHostToDevice, c->stream));
+        unsigned long long *slot;
+        if (int st = take_slot(c, i0, &slot, err)) return st;
+        return launch_hist(c, c->scratch[0], m + k - 1, k, a, slot, err);
+    });
+}
+
+template <class HQ>
+int hist_packed_host(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const HQ *queries, size_t n_queries, size_t n_bins, uint64_t *hist,
+                     bitnuc_err *err) {
+    clear_err(err);
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
+    bool none;
+    if (int st = check_hist(queries, n_queries, n_bins, hist, &none, err, hist_qmask<HQ>())) return st;
+    if (none) return BITNUC_OK;
+    if (k == 0 || n < k) { memset(hist, 0, n_queries * n_bins * sizeof(uint64_t)); return BITNUC_OK; }
+    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, multi_work(n - k + 1, n_queries))) {
+        bitnuc_host::kmer_hdist_hist_packed_small(words, n, k, host_queries(queries), n_queries, n_bins, hist);
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    if (int st = ensure_scratch(c, 0, (kPackedChunkWords + 1) * 8, err)) return st;
+    // chunk w0 / 32 of whole words (packed_chunk): its windows start at base i0 = 32 w0
+    return hist_host_loop(c, n - k + 1, 32 * kPackedChunkWords, queries, n_queries, n_bins, hist, err, [&](size_t i0, const HistArgsT<HQ> &a) {
+        const PackedChunk ch = packed_chunk(i0 / 32, n, k);
+        HIPCHK(hipMemcpyAsync(c->scratch[0], words + ch.w0, ch.words * 8, hipMemcpyHostToDevice, c->stream));
+        return launch_hist_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), ch.bases, k, a, err);
+    });
 }
 
 } // namespace
@@ -1498,6 +1687,40 @@ int bitnuc_kmer_pattern_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t
         HIPCHK(hipMemcpyAsync(c->scratch[0], words + ch.w0, ch.words * 8, hipMemcpyHostToDevice, c->stream));
         return launch_best_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), ch.bases, k, a, err);
     });
+}
+
+// ---- the mismatch histogram per query (hist_async ... hist_packed_host above) ------------------------------------------------------------------
+int bitnuc_kmer_hdist_hist_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const uint64_t *d_queries, size_t n_queries, size_t n_bins,
+                                 uint64_t *d_hist, bitnuc_err *err) {
+    return hist_async(c, d_ref, n, k, d_queries, n_queries, n_bins, d_hist, err);
+}
+int bitnuc_kmer_hdist_hist_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const uint64_t *d_queries, size_t n_queries,
+                                        size_t n_bins, uint64_t *d_hist, bitnuc_err *err) {
+    return hist_packed_async(c, d_words, n_words, n, k, d_queries, n_queries, n_bins, d_hist, err);
+}
+int bitnuc_kmer_hdist_hist(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const uint64_t *queries, size_t n_queries, size_t n_bins, uint64_t *hist,
+                           bitnuc_err *err) {
+    return hist_host(c, ref, n, k, queries, n_queries, n_bins, hist, err);
+}
+int bitnuc_kmer_hdist_hist_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const uint64_t *queries, size_t n_queries, size_t n_bins,
+                                  uint64_t *hist, bitnuc_err *err) {
+    return hist_packed_host(c, words, n_words, n, k, queries, n_queries, n_bins, hist, err);
+}
+int bitnuc_kmer_pattern_hist_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries, size_t n_bins,
+                                   uint64_t *d_hist, bitnuc_err *err) {
+    return hist_async(c, d_ref, n, k, d_patterns, n_queries, n_bins, d_hist, err);
+}
+int bitnuc_kmer_pattern_hist_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *d_patterns,
+                                          size_t n_queries, size_t n_bins, uint64_t *d_hist, bitnuc_err *err) {
+    return hist_packed_async(c, d_words, n_words, n, k, d_patterns, n_queries, n_bins, d_hist, err);
+}
+int bitnuc_kmer_pattern_hist(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const bitnuc_pattern *patterns, size_t n_queries, size_t n_bins, uint64_t *hist,
+                             bitnuc_err *err) {
+    return hist_host(c, ref, n, k, patterns, n_queries, n_bins, hist, err);
+}
+int bitnuc_kmer_pattern_hist_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *patterns, size_t n_queries,
+                                    size_t n_bins, uint64_t *hist, bitnuc_err *err) {
+    return hist_packed_host(c, words, n_words, n, k, patterns, n_queries, n_bins, hist, err);
 }
 
 int bitnuc_kmer_pattern_hits_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const bitnuc_pattern *pattern, unsigned tau, uint64_t *d_pos, uint8_t *d_hit_dist,

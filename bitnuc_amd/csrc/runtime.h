@@ -126,7 +126,8 @@ struct bitnuc_ctx {
     int n_cap = 0;
     std::vector<bitnuc_err> deferred; // data errors found by implicit drains (host-pointer calls start from an empty ring), oldest first: one per bitnuc_ctx_sync
     // ---- scratch ----
-    // [8]: the multi-query count's per-query tables (kmer.hip launch_count_multi); [9]: the best match's keys and per-query tables (kmer.hip best_setup);
+    // [8]: the multi-query count's per-query tables (kmer.hip launch_count_multi); [9]: the best match's keys and per-query tables (kmer.hip best_setup), shared in
+    // stream order with the mismatch histogram's per-query tables (kmer.hip hist_setup: the same tables at the same offset);
     // [10]: the per-read best match's keys (one per read) and per-query tables (kmer.hip reads_setup)
     uint8_t *scratch[11] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     size_t scratch_cap[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};

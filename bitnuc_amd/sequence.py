@@ -80,12 +80,18 @@ class PackedSequence:
     def kmer_hdist_best(self, k, queries):
         return self._ctx.kmer_hdist_best_packed(self.data, self.length, k, queries)
 
+    def kmer_hdist_hist(self, k, queries, n_bins):
+        return self._ctx.kmer_hdist_hist_packed(self.data, self.length, k, queries, n_bins)
+
     # pattern queries (a set of bases per position: IUPAC strings or (Q, 4) uint32 arrays) over the packed words
     def kmer_pattern_count_multi(self, k, patterns, taus):
         return self._ctx.kmer_pattern_count_multi_packed(self.data, self.length, k, patterns, taus)
 
     def kmer_pattern_best(self, k, patterns):
         return self._ctx.kmer_pattern_best_packed(self.data, self.length, k, patterns)
+
+    def kmer_pattern_hist(self, k, patterns, n_bins):
+        return self._ctx.kmer_pattern_hist_packed(self.data, self.length, k, patterns, n_bins)
 
     def kmer_pattern_hits(self, k, pattern, tau, with_dist=False):
         return self._ctx.kmer_pattern_hits_packed(self.data, self.length, k, pattern, tau, with_dist)

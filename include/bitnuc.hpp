@@ -296,6 +296,22 @@ class Context {
             return NucleotideError::from_c(e);
         return std::make_pair(std::move(pos), std::move(dist));
     }
+    // the mismatch histogram per query in one pass: hist[q * n_bins + d] = the windows at distance exactly d < n_bins (<= BITNUC_HIST_MAX_BINS) from
+    // queries[q]; a window at n_bins or more mismatches is counted nowhere
+    Result<std::vector<uint64_t>> kmer_hdist_hist(Bytes ref, size_t k, const std::vector<uint64_t> &queries, size_t n_bins) const {
+        std::vector<uint64_t> hist(queries.size() * (n_bins < BITNUC_HIST_MAX_BINS ? n_bins : BITNUC_HIST_MAX_BINS)); // (a refused n_bins writes nothing)
+        bitnuc_err e;
+        if (bitnuc_kmer_hdist_hist(ctx_, ref.ptr, ref.len, k, queries.data(), queries.size(), n_bins, hist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return hist;
+    }
+    Result<std::vector<uint64_t>> kmer_hdist_hist_packed(Words words, size_t n, size_t k, const std::vector<uint64_t> &queries, size_t n_bins) const {
+        std::vector<uint64_t> hist(queries.size() * (n_bins < BITNUC_HIST_MAX_BINS ? n_bins : BITNUC_HIST_MAX_BINS)); // (a refused n_bins writes nothing)
+        bitnuc_err e;
+        if (bitnuc_kmer_hdist_hist_packed(ctx_, words.ptr, words.len, n, k, queries.data(), queries.size(), n_bins, hist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return hist;
+    }
     // the best match per read of a fixed-length batch: (query, pos, dist) per read, the smallest (distance, query, offset) over the windows inside it
     struct ReadsBest { std::vector<uint32_t> query, pos; std::vector<uint8_t> dist; };
     Result<ReadsBest> reads_hdist_best(Bytes reads, size_t read_len, size_t k, const std::vector<uint64_t> &queries) const {
@@ -373,6 +389,21 @@ class Context {
         if (bitnuc_kmer_pattern_best_packed(ctx_, words.ptr, words.len, n, k, patterns.data(), patterns.size(), pos.data(), dist.data(), &e) != BITNUC_OK)
             return NucleotideError::from_c(e);
         return std::make_pair(std::move(pos), std::move(dist));
+    }
+    // hist[q * n_bins + d] = the windows with pdist exactly d < n_bins under patterns[q]
+    Result<std::vector<uint64_t>> kmer_pattern_hist(Bytes ref, size_t k, const std::vector<bitnuc_pattern> &patterns, size_t n_bins) const {
+        std::vector<uint64_t> hist(patterns.size() * (n_bins < BITNUC_HIST_MAX_BINS ? n_bins : BITNUC_HIST_MAX_BINS));
+        bitnuc_err e;
+        if (bitnuc_kmer_pattern_hist(ctx_, ref.ptr, ref.len, k, patterns.data(), patterns.size(), n_bins, hist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return hist;
+    }
+    Result<std::vector<uint64_t>> kmer_pattern_hist_packed(Words words, size_t n, size_t k, const std::vector<bitnuc_pattern> &patterns, size_t n_bins) const {
+        std::vector<uint64_t> hist(patterns.size() * (n_bins < BITNUC_HIST_MAX_BINS ? n_bins : BITNUC_HIST_MAX_BINS));
+        bitnuc_err e;
+        if (bitnuc_kmer_pattern_hist_packed(ctx_, words.ptr, words.len, n, k, patterns.data(), patterns.size(), n_bins, hist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return hist;
     }
     // the positions (ascending) of the windows with pdist <= tau, sized by a first call with cap 0; hit_dist, when given, gets their distances
     Result<std::vector<uint64_t>> kmer_pattern_hits(Bytes ref, size_t k, const bitnuc_pattern &pattern, unsigned tau, std::vector<uint8_t> *hit_dist = nullptr) const {

@@ -195,7 +195,8 @@ int bitnuc_kmer_hdist_hits_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t
 /* The fused count for MANY queries in one pass over the reference: counts[q] = the number of windows i with
  * hdist_scalar(as_2bit(ref[i..i+k]), queries[q], k) <= taus[q] -- exactly what bitnuc_kmer_hdist_count[_packed]_dev returns for (ref, n, k, queries[q],
  * taus[q]).  Query bits above 2k are ignored; any uint32_t tau is valid (tau >= k counts every window), and a per-query tau costs nothing (a query repeated
- * with tau = 0, 1, 2, 3 gives its mismatch profile in one call).  counts[0 .. n_queries) is written and nothing after it.
+ * with tau = 0, 1, 2, 3 gives its mismatch profile in one call; bitnuc_kmer_hdist_hist* below gives the whole profile, up to 16 bins, from ONE query per
+ * profile and without the subtraction).  counts[0 .. n_queries) is written and nothing after it.
  * Checks, in this order: (1) ctx NULL -> UNSUPPORTED (_dev forms; the host forms below the cutoff accept NULL); (2) k > 32 -> SEQUENCE_TOO_LONG(k);
  * (3) packed: n_words < ceil(n/32) -> INVALID_LENGTH(n); (4) n_queries == 0 -> OK, nothing written; (5) n_queries > BITNUC_MAX_QUERIES -> UNSUPPORTED
  * (err.value = n_queries); (6) counts, queries or taus NULL or not 8-, 8-, 4-byte aligned -> UNSUPPORTED; (7) k == 0 or n < k -> OK, every count 0;
@@ -294,6 +295,50 @@ int bitnuc_kmer_pattern_hits(bitnuc_ctx *ctx, const uint8_t *ref, size_t n, size
                              size_t cap, uint64_t *n_hits, bitnuc_err *err);
 int bitnuc_kmer_pattern_hits_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *pattern, unsigned tau,
                                     uint64_t *pos, uint8_t *hit_dist, size_t cap, uint64_t *n_hits, bitnuc_err *err);
+/* The MISMATCH HISTOGRAM per query in one pass over the reference: hist[q * n_bins + d] = the number of windows i in 0..n-k+1 with
+ * hdist_scalar(as_2bit(ref[i..i+k]), queries[q], k) == d, for d < n_bins (pattern forms: pdist(i) == d).  A window at distance n_bins or more is counted
+ * nowhere.  Exactly hist[0 .. n_queries * n_bins) is written and nothing after it.  Query bits above 2k are ignored.  The result is deterministic
+ * (integer sums).  With no windows (k == 0 or n < k) every entry is 0.  It is the profile an off-target report asks of a guide and a barcode or primer
+ * check asks of a probe: one query and one table per profile where bitnuc_kmer_hdist_count_multi* needs one per bin and a subtraction afterwards.
+ * Identities: the sum over d <= t of hist[q][d] equals bitnuc_kmer_hdist_count_multi*'s counts[q] with taus[q] = t (t < n_bins); the first non-zero bin is
+ * bitnuc_kmer_hdist_best*'s dist[q] when that distance is below n_bins; with n_bins > k the bins of a query sum to n - k + 1.
+ * Checks, in this order: (1) ctx NULL -> UNSUPPORTED (_async forms; the host forms below the cutoff accept NULL); (2) k > 32 -> SEQUENCE_TOO_LONG(k);
+ * (3) packed: n_words < ceil(n/32) -> INVALID_LENGTH(n); (4) n_bins == 0 or n_bins > BITNUC_HIST_MAX_BINS -> UNSUPPORTED (err.value = n_bins);
+ * (5) n_queries == 0 -> OK, nothing written; (6) n_queries > BITNUC_MAX_QUERIES -> UNSUPPORTED (err.value = n_queries); (7) hist or queries NULL or not
+ * 8-byte aligned (patterns: NULL or not 4-byte aligned) -> UNSUPPORTED; (8) k == 0 or n < k -> OK, every entry 0; (9) a NULL reference, or packed words
+ * not 8-byte aligned -> UNSUPPORTED.
+ * ASCII: an invalid base -> INVALID_BASE with the first invalid byte in sequence order (the _async forms latch it once per call for bitnuc_ctx_sync();
+ * hist is then unspecified; the host forms below the cutoff leave hist untouched).  d_ref may have any alignment (the up to 15 windows before its first
+ * 16-byte aligned base take the tail's path); packed words 16-byte aligned or at 8 mod 16.
+ * The _async forms have the _dev contract: device pointers (d_queries / d_patterns and d_hist included), enqueued on the context's stream, no host
+ * synchronisation (with the one exception below), InvalidBase latched for bitnuc_ctx_sync().  They keep one table per query (2.5 KiB) in the context
+ * scratch the best match uses and can be captured into a hipGraph, but scratch cannot grow during a capture (BITNUC_UNSUPPORTED, err.value = the bytes
+ * needed): warm up with the same (or a larger) n_queries first.  Outside a capture a call that needs more scratch than the context holds waits for the
+ * stream before it replaces the allocation, as the best match does.
+ * The host forms are synchronous.  When windows x n_queries is below the host cutoff (as the multi-query count judges it) they run on the host and ctx
+ * may be NULL; above it they run through the context in chunks of 128 M windows that overlap by k - 1 bases, summing per bin.
+ * Cost: the best match's four matrix instructions per 1024 windows and query, then three vector instructions per window for every eight bins: n_bins <= 8
+ * costs one such tier, 9 - 16 two.  Measured on 10^9 bases in one process (profiles/r12_kmer_hist.json; ASCII and packed, exact and pattern
+ * queries alike): against count_multi with every query repeated n_bins times it takes 0.48 - 0.53 x the time at n_bins = 4, 0.24 - 0.27 x at 8 and
+ * 0.20 - 0.22 x at 16 for 8 queries and more (one query: 0.69 - 0.72, 0.39 - 0.43, 0.30 - 0.40 x), so it pays from n_bins = 4, the smallest measured;
+ * against the best match at the same number of queries 1.6 - 1.7 x with one tier and 2.6 - 2.9 x with two (one query: 1.5 and 2.1 - 2.6 x). */
+#define BITNUC_HIST_MAX_BINS 16
+int bitnuc_kmer_hdist_hist_async(bitnuc_ctx *ctx, const uint8_t *d_ref, size_t n, size_t k, const uint64_t *d_queries, size_t n_queries, size_t n_bins,
+                                 uint64_t *d_hist, bitnuc_err *err);
+int bitnuc_kmer_hdist_hist_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const uint64_t *d_queries,
+                                        size_t n_queries, size_t n_bins, uint64_t *d_hist, bitnuc_err *err);
+int bitnuc_kmer_hdist_hist(bitnuc_ctx *ctx, const uint8_t *ref, size_t n, size_t k, const uint64_t *queries, size_t n_queries, size_t n_bins, uint64_t *hist,
+                           bitnuc_err *err);
+int bitnuc_kmer_hdist_hist_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t n_words, size_t n, size_t k, const uint64_t *queries, size_t n_queries,
+                                  size_t n_bins, uint64_t *hist, bitnuc_err *err);
+int bitnuc_kmer_pattern_hist_async(bitnuc_ctx *ctx, const uint8_t *d_ref, size_t n, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries, size_t n_bins,
+                                   uint64_t *d_hist, bitnuc_err *err);
+int bitnuc_kmer_pattern_hist_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *d_patterns,
+                                          size_t n_queries, size_t n_bins, uint64_t *d_hist, bitnuc_err *err);
+int bitnuc_kmer_pattern_hist(bitnuc_ctx *ctx, const uint8_t *ref, size_t n, size_t k, const bitnuc_pattern *patterns, size_t n_queries, size_t n_bins, uint64_t *hist,
+                             bitnuc_err *err);
+int bitnuc_kmer_pattern_hist_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *patterns, size_t n_queries,
+                                    size_t n_bins, uint64_t *hist, bitnuc_err *err);
 /* d_result: one uint32 in device memory, overwritten with the distance. */
 int bitnuc_hdist_dev(bitnuc_ctx *ctx, const uint64_t *d_a, size_t na, const uint64_t *d_b, size_t nb, size_t n_bases, uint32_t *d_result, bitnuc_err *err);
 

@@ -46,6 +46,7 @@ pub struct bitnuc_comm {
     _private: [u8; 0],
 }
 pub const BITNUC_UNIQUE_ID_BYTES: usize = 128;
+pub const BITNUC_HIST_MAX_BINS: usize = 16;
 
 extern "C" {
     pub fn bitnuc_version() -> *const c_char;
@@ -155,6 +156,14 @@ extern "C" {
     pub fn bitnuc_kmer_pattern_best_packed_async(ctx: *mut bitnuc_ctx, d_words: *const u64, n_words: usize, n: usize, k: usize, d_patterns: *const bitnuc_pattern, n_queries: usize, d_pos: *mut u64, d_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_kmer_pattern_best(ctx: *mut bitnuc_ctx, reference: *const u8, n: usize, k: usize, patterns: *const bitnuc_pattern, n_queries: usize, pos: *mut u64, dist: *mut u8, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_kmer_pattern_best_packed(ctx: *mut bitnuc_ctx, words: *const u64, n_words: usize, n: usize, k: usize, patterns: *const bitnuc_pattern, n_queries: usize, pos: *mut u64, dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_hdist_hist_async(ctx: *mut bitnuc_ctx, d_ref: *const u8, n: usize, k: usize, d_queries: *const u64, n_queries: usize, n_bins: usize, d_hist: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_hdist_hist_packed_async(ctx: *mut bitnuc_ctx, d_words: *const u64, n_words: usize, n: usize, k: usize, d_queries: *const u64, n_queries: usize, n_bins: usize, d_hist: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_hdist_hist(ctx: *mut bitnuc_ctx, reference: *const u8, n: usize, k: usize, queries: *const u64, n_queries: usize, n_bins: usize, hist: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_hdist_hist_packed(ctx: *mut bitnuc_ctx, words: *const u64, n_words: usize, n: usize, k: usize, queries: *const u64, n_queries: usize, n_bins: usize, hist: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_hist_async(ctx: *mut bitnuc_ctx, d_ref: *const u8, n: usize, k: usize, d_patterns: *const bitnuc_pattern, n_queries: usize, n_bins: usize, d_hist: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_hist_packed_async(ctx: *mut bitnuc_ctx, d_words: *const u64, n_words: usize, n: usize, k: usize, d_patterns: *const bitnuc_pattern, n_queries: usize, n_bins: usize, d_hist: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_hist(ctx: *mut bitnuc_ctx, reference: *const u8, n: usize, k: usize, patterns: *const bitnuc_pattern, n_queries: usize, n_bins: usize, hist: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_hist_packed(ctx: *mut bitnuc_ctx, words: *const u64, n_words: usize, n: usize, k: usize, patterns: *const bitnuc_pattern, n_queries: usize, n_bins: usize, hist: *mut u64, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_kmer_pattern_hits_async(ctx: *mut bitnuc_ctx, d_ref: *const u8, n: usize, k: usize, pattern: *const bitnuc_pattern, tau: c_uint, d_pos: *mut u64, d_hit_dist: *mut u8, cap: usize, d_n_hits: *mut u64, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_kmer_pattern_hits_packed_async(ctx: *mut bitnuc_ctx, d_words: *const u64, n_words: usize, n: usize, k: usize, pattern: *const bitnuc_pattern, tau: c_uint, d_pos: *mut u64, d_hit_dist: *mut u8, cap: usize, d_n_hits: *mut u64, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_kmer_pattern_hits(ctx: *mut bitnuc_ctx, reference: *const u8, n: usize, k: usize, pattern: *const bitnuc_pattern, tau: c_uint, pos: *mut u64, hit_dist: *mut u8, cap: usize, n_hits: *mut u64, err: *mut bitnuc_err) -> c_int;

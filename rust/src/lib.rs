@@ -319,6 +319,27 @@ pub fn kmer_hdist_best_packed(words: &[u64], n: usize, k: usize, queries: &[u64]
     if st == ffi::BITNUC_OK { Ok((pos, dist)) } else { Err(to_err(&e)) }
 }
 
+/// The mismatch histogram per query in one pass: `hist[q * n_bins + d]` = the number of windows of `reference` at Hamming distance exactly `d` from
+/// `queries[q]`, `d < n_bins <= 16`; a window at `n_bins` or more mismatches is counted nowhere.
+pub fn kmer_hdist_hist(reference: &[u8], k: usize, queries: &[u64], n_bins: usize) -> Result<Vec<u64>, NucleotideError> {
+    let mut hist = vec![0u64; queries.len() * n_bins.min(ffi::BITNUC_HIST_MAX_BINS)]; // (a refused n_bins writes nothing)
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_hdist_hist(c, reference.as_ptr(), reference.len(), k, queries.as_ptr(), queries.len(), n_bins, hist.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(hist) } else { Err(to_err(&e)) }
+}
+
+/// `kmer_hdist_hist` of the packed sequence `words` holding `n` bases, without decoding it.
+pub fn kmer_hdist_hist_packed(words: &[u64], n: usize, k: usize, queries: &[u64], n_bins: usize) -> Result<Vec<u64>, NucleotideError> {
+    let mut hist = vec![0u64; queries.len() * n_bins.min(ffi::BITNUC_HIST_MAX_BINS)]; // (a refused n_bins writes nothing)
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_hdist_hist_packed(c, words.as_ptr(), words.len(), n, k, queries.as_ptr(), queries.len(), n_bins, hist.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(hist) } else { Err(to_err(&e)) }
+}
+
 /// The best match per read of `count` back-to-back reads of `read_len` bases: `(query, pos, dist)` with the smallest (distance, query, offset)
 /// over all queries and the windows that lie wholly inside each read; a read without a window gets `u32::MAX`, `u32::MAX`, `255`.
 pub fn reads_hdist_best(reads: &[u8], read_len: usize, k: usize, queries: &[u64]) -> Result<(Vec<u32>, Vec<u32>, Vec<u8>), NucleotideError> {
@@ -405,6 +426,27 @@ pub fn kmer_pattern_best_packed(words: &[u64], n: usize, k: usize, patterns: &[P
         ffi::bitnuc_kmer_pattern_best_packed(c, words.as_ptr(), words.len(), n, k, patterns.as_ptr(), patterns.len(), pos.as_mut_ptr(), dist.as_mut_ptr(), &mut e)
     });
     if st == ffi::BITNUC_OK { Ok((pos, dist)) } else { Err(to_err(&e)) }
+}
+
+/// The mismatch histogram per pattern in one pass: `hist[q * n_bins + d]` = the number of windows with pdist exactly `d` under `patterns[q]`,
+/// `d < n_bins <= 16`.
+pub fn kmer_pattern_hist(reference: &[u8], k: usize, patterns: &[Pattern], n_bins: usize) -> Result<Vec<u64>, NucleotideError> {
+    let mut hist = vec![0u64; patterns.len() * n_bins.min(ffi::BITNUC_HIST_MAX_BINS)]; // (a refused n_bins writes nothing)
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_pattern_hist(c, reference.as_ptr(), reference.len(), k, patterns.as_ptr(), patterns.len(), n_bins, hist.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(hist) } else { Err(to_err(&e)) }
+}
+
+/// `kmer_pattern_hist` of the packed sequence `words` holding `n` bases, without decoding it.
+pub fn kmer_pattern_hist_packed(words: &[u64], n: usize, k: usize, patterns: &[Pattern], n_bins: usize) -> Result<Vec<u64>, NucleotideError> {
+    let mut hist = vec![0u64; patterns.len() * n_bins.min(ffi::BITNUC_HIST_MAX_BINS)]; // (a refused n_bins writes nothing)
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_pattern_hist_packed(c, words.as_ptr(), words.len(), n, k, patterns.as_ptr(), patterns.len(), n_bins, hist.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(hist) } else { Err(to_err(&e)) }
 }
 
 /// The positions (ascending) and distances of the windows of `reference` with pdist at most `tau` under `pattern`: a first call with cap 0 returns
