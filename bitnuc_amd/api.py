@@ -415,6 +415,31 @@ class Context:
             raise ValueError("words must hold count reads of ceil(read_len / 32) words each")
         return self._reads_best(self._lib.bitnuc_reads_hdist_best_packed, (_ptr(w), int(read_len), int(count), int(k)), int(count), queries)
 
+    def reads_hdist_best_batch(self, seq, offsets, k, queries):
+        """The best match per read of a ragged batch: read r is seq[offsets[r]:offsets[r + 1]] (`offsets`: count + 1 non-decreasing entries from 0).
+        (query, pos, dist) as reads_hdist_best; an empty read, or one shorter than k: 2^32 - 1, 2^32 - 1, 255."""
+        s = _as_u8(seq)
+        off = _as_u64(offsets)
+        if off.size == 0:
+            raise ValueError("offsets must hold count + 1 entries")
+        if s.size < int(off[-1]):
+            raise ValueError("seq must hold offsets[-1] bases")
+        count = off.size - 1
+        return self._reads_best(self._lib.bitnuc_reads_hdist_best_batch, (_ptr(s), _ptr(off), count, int(k)), count, queries)
+
+    def reads_hdist_best_batch_packed(self, words, word_offsets, offsets, k, queries):
+        """reads_hdist_best_batch of the packed words encode_batch writes (read r's ceil(len_r / 32) words start at words[word_offsets[r]]), without
+        decoding them."""
+        w = _as_u64(words)
+        woff = _as_u64(word_offsets)
+        off = _as_u64(offsets)
+        if off.size == 0 or woff.size != off.size:
+            raise ValueError("offsets and word_offsets must hold count + 1 entries each")
+        if w.size < int(woff[-1]):
+            raise ValueError("words must hold word_offsets[-1] words")
+        count = off.size - 1
+        return self._reads_best(self._lib.bitnuc_reads_hdist_best_batch_packed, (_ptr(w), _ptr(woff), _ptr(off), count, int(k)), count, queries)
+
     # -- pattern queries: a set of bases per position (bitnuc_pattern) -------------------------
     @staticmethod
     def _patterns(patterns, k):
@@ -772,6 +797,18 @@ class Context:
         """The best match per read on the packed words encode_fixed_dev writes (8-byte aligned, ceil(read_len / 32) words per read)."""
         self._call_dev(self._lib.bitnuc_reads_hdist_best_packed_async, _dev_ptr(d_words), int(read_len), int(count), int(k), _dev_ptr(d_queries),
                        int(n_queries), _dev_ptr(d_best_query), _dev_ptr(d_best_pos), _dev_ptr(d_best_dist))
+
+    def reads_hdist_best_batch_async(self, d_seq, d_offsets, count, total_bases, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist):
+        """The best match per read of a ragged batch of ASCII reads in device memory: read r is d_seq[d_offsets[r] .. d_offsets[r + 1]) (u64, count + 1
+        entries from 0, total_bases = the last).  The table is trusted and read on the device.  Asynchronous on the context's stream, as the _dev calls."""
+        self._call_dev(self._lib.bitnuc_reads_hdist_best_batch_async, _dev_ptr(d_seq), _dev_ptr(d_offsets), int(count), int(total_bases), int(k),
+                       _dev_ptr(d_queries), int(n_queries), _dev_ptr(d_best_query), _dev_ptr(d_best_pos), _dev_ptr(d_best_dist))
+
+    def reads_hdist_best_batch_packed_async(self, d_words, d_word_offsets, d_offsets, count, total_words, k, d_queries, n_queries, d_best_query, d_best_pos,
+                                            d_best_dist):
+        """The best match per read on the packed words encode_batch_dev writes (8-byte aligned; both tables u64 in device memory, trusted)."""
+        self._call_dev(self._lib.bitnuc_reads_hdist_best_batch_packed_async, _dev_ptr(d_words), _dev_ptr(d_word_offsets), _dev_ptr(d_offsets), int(count),
+                       int(total_words), int(k), _dev_ptr(d_queries), int(n_queries), _dev_ptr(d_best_query), _dev_ptr(d_best_pos), _dev_ptr(d_best_dist))
 
     # the pattern twins: d_patterns holds n_queries bitnuc_pattern (16 bytes each, 4-byte aligned) in device memory; the hit lists take their one
     # pattern from the host (a (4,) np.uint32 array)

@@ -3,7 +3,7 @@
 // Hamming scan (config 5: packing/mod.rs:80-110 o hamming/scalar.rs:11-48) and bulk hdist (hamming/multi.rs:121-160).
 // Kernels: kmer_device.h; config 5 on the matrix cores: scan_mfma_device.h; the same scan and count on packed words: scan_packed_device.h; the hit
 // lists of both: scan_hits_device.h; the count for many queries at once: scan_multi_device.h; the best match per query: scan_best_device.h; the mismatch histogram per query: scan_hist_device.h; the best match per read of a
-// fixed-length batch: scan_reads_device.h.
+// fixed-length batch: scan_reads_device.h; ... of a ragged batch: scan_reads_batch_device.h.
 #include "runtime.h"
 #include "kmer_device.h"
 #include "scan_mfma_device.h"
@@ -12,12 +12,14 @@
 #include "scan_multi_device.h"
 #include "scan_best_device.h"
 #include "scan_reads_device.h"
+#include "scan_reads_batch_device.h"
 #include "scan_hist_device.h"
 #include "scan_mfma_host.h"
 #include "scan_hits_host.h"
 #include "scan_multi_host.h"
 #include "scan_best_host.h"
 #include "reads_best_host.h"
+#include "reads_batch_host.h"
 #include "scan_hist_host.h"
 #include "pattern_host.h"
 #include "host_word.h"
@@ -821,6 +823,88 @@ int reads_host_loop(bitnuc_ctx *c, size_t count, size_t per, const uint64_t *que
     return BITNUC_OK;
 }
 
+// ---- the best match per read of a RAGGED batch (scan_reads_batch_device.h): the fixed-length form's scratch, keys, tables, grid and finish; the
+// kernels take the run's length and the layout's two tables instead of a period.
+inline BatchTables batch_tables(const uint64_t *starts, const uint64_t *offsets, size_t count, unsigned shift) {
+    return BatchTables{reinterpret_cast<const unsigned long long *>(starts), reinterpret_cast<const unsigned long long *>(offsets), count, shift};
+}
+
+// d_seq at any alignment (ascii_skip); 1 <= k <= total, count >= 1, nq >= 1
+template <class HQ>
+int launch_reads_batch(bitnuc_ctx *c, const uint8_t *seq, const uint64_t *d_offsets, size_t count, size_t total, size_t k, const ReadsArgsT<HQ> &a,
+                       unsigned long long *slot, bitnuc_err *err) {
+    const unsigned skip = ascii_skip(seq);
+    const unsigned long long n = total, rounds = scan_rounds(n, skip);
+    unsigned long long *keys;
+    const BestTable *tabs;
+    dim3 grid;
+    if (int st = reads_setup<false>(c, k, count, n, rounds, a, &keys, &tabs, &grid, err)) return st;
+    reads_batch_kernel<kMultiRounds><<<grid, kMultiBlock, 0, c->stream>>>(seq, batch_tables(d_offsets, d_offsets, count, 0), n, skip, rounds, (unsigned)k,
+                                                                         dev_queries(a.queries), (unsigned)a.nq, tabs, keys, slot);
+    return reads_finish(c, keys, count, a, err);
+}
+
+// d_words 8-byte aligned (packed_skip); total_words >= 1
+template <class HQ>
+int launch_reads_batch_packed(bitnuc_ctx *c, const uint64_t *words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count, size_t total_words,
+                              size_t k, const ReadsArgsT<HQ> &a, bitnuc_err *err) {
+    const unsigned skip = packed_skip(words);
+    const unsigned long long n = 32ull * total_words, rounds = scan_rounds(n, skip);
+    unsigned long long *keys;
+    const BestTable *tabs;
+    dim3 grid;
+    if (int st = reads_setup<true>(c, k, count, n, rounds, a, &keys, &tabs, &grid, err)) return st;
+    reads_batch_packed_kernel<<<grid, kMultiBlock, 0, c->stream>>>(words, batch_tables(d_word_offsets, d_offsets, count, 5), n, skip, rounds, (unsigned)k,
+                                                                   dev_queries(a.queries), (unsigned)a.nq, tabs, keys);
+    return reads_finish(c, keys, count, a, err);
+}
+
+// the ragged reads calls' checks 2 - 6 (after ctx): `total` is what check 3 bounds (bases, or 32 x words; the host forms pass 0 and bound their tables'
+// totals with the table validation); tab2: the second table of the packed forms.  *done = nothing to do (count == 0)
+int check_reads_batch(uint64_t total, uint64_t total_value, size_t count, size_t k, const void *queries, size_t nq, const void *query, const void *pos, const void *dist,
+                      const void *tab1, const void *tab2, bool two_tables, bool *done, bitnuc_err *err) {
+    *done = false;
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    if (total >= ((uint64_t)1 << 58)) return fail(err, BITNUC_UNSUPPORTED, total_value);
+    if (nq > BITNUC_MAX_QUERIES) return fail(err, BITNUC_UNSUPPORTED, nq);
+    *done = count == 0;
+    if (*done) return BITNUC_OK;
+    if (!query || !pos || !dist || (reinterpret_cast<uintptr_t>(query) & 3) || (reinterpret_cast<uintptr_t>(pos) & 3) || (!queries && nq) ||
+        (reinterpret_cast<uintptr_t>(queries) & 7) || !tab1 || (reinterpret_cast<uintptr_t>(tab1) & 7) ||
+        (two_tables && (!tab2 || (reinterpret_cast<uintptr_t>(tab2) & 7))))
+        return fail(err, BITNUC_UNSUPPORTED);
+    return BITNUC_OK;
+}
+
+// check 7 of the host forms: batch_check_tables' finding as the call's error
+int fail_batch_tables(const BatchFault &f, bitnuc_err *err) {
+    return fail(err, f.kind >= 4 ? BITNUC_UNSUPPORTED : BITNUC_INVALID_RANGE, f.value);
+}
+
+// The ragged host forms' chunk loop: reads_host_loop with chunks of whole reads of any number: chunk_end(r0) is the read after the chunk's last;
+// `launch(r0, m, a)` runs the reads [r0, r0 + m) with a's device arrays.
+template <class ChunkEnd, class Launch>
+int reads_batch_host_loop(bitnuc_ctx *c, size_t count, const uint64_t *queries, size_t nq, uint32_t *query, uint32_t *pos, uint8_t *dist, bitnuc_err *err,
+                          ChunkEnd chunk_end, Launch launch) {
+    if (int st = ensure_scratch(c, 2, nq * 8, err)) return st;
+    HIPCHK(hipMemcpyAsync(c->scratch[2], queries, nq * 8, hipMemcpyHostToDevice, c->stream));
+    for (size_t r0 = 0; r0 < count;) {
+        const size_t m = chunk_end(r0) - r0;
+        if (int st = ensure_scratch(c, 1, m * 8, err)) return st;
+        if (int st = ensure_scratch(c, 3, m < 64 ? 64 : m, err)) return st;
+        uint32_t *d_query = reinterpret_cast<uint32_t *>(c->scratch[1]), *d_pos = d_query + m;
+        const ReadsArgs a{reinterpret_cast<const uint64_t *>(c->scratch[2]), nq, d_query, d_pos, c->scratch[3]};
+        if (int st = launch(r0, m, a)) return st;
+        HIPCHK(hipMemcpyAsync(query + r0, d_query, m * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(pos + r0, d_pos, m * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(dist + r0, c->scratch[3], m, hipMemcpyDeviceToHost, c->stream));
+        bitnuc_err e;
+        if (int st = drain(c, &e)) { if (err) *err = e; return st; }
+        r0 += m;
+    }
+    return BITNUC_OK;
+}
+
 // ---- the mismatch histogram per query: the four forms, once for exact queries (uint64_t) and patterns (bitnuc_pattern) -----------------------------
 template <class HQ>
 int hist_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const HQ *d_queries, size_t n_queries, size_t n_bins, uint64_t *d_hist, bitnuc_err *err) {
@@ -1478,6 +1562,122 @@ int bitnuc_reads_hdist_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t 
         HIPCHK(hipMemcpyAsync(c->scratch[0], words + r0 * wpr, m * wpr * 8, hipMemcpyHostToDevice, c->stream));
         return launch_reads_best_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), read_len, m, k, a, err);
     });
+}
+
+// ---- the best match per read of a ragged batch ------------------------------------------------------------------------------------
+int bitnuc_reads_hdist_best_batch_async(bitnuc_ctx *c, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k,
+                                        const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    bool done;
+    if (int st = check_reads_batch(total_bases, total_bases, count, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist, d_offsets, nullptr, false, &done, err)) return st;
+    if (done) return BITNUC_OK;
+    DeviceGuard g(c->device);
+    if (k == 0 || n_queries == 0 || total_bases < k) return reads_fill_dev(c, count, d_best_query, d_best_pos, d_best_dist, err);
+    if (!d_seq) return fail(err, BITNUC_UNSUPPORTED);
+    unsigned long long *slot;
+    if (int st = take_slot(c, 0, &slot, err)) return st;
+    return launch_reads_batch(c, d_seq, d_offsets, count, total_bases, k, ReadsArgs{d_queries, n_queries, d_best_query, d_best_pos, d_best_dist}, slot, err);
+}
+
+int bitnuc_reads_hdist_best_batch_packed_async(bitnuc_ctx *c, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
+                                               size_t total_words, size_t k, const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query,
+                                               uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    bool done;
+    const uint64_t as_bases = total_words >= ((uint64_t)1 << 53) ? ~(uint64_t)0 : 32 * (uint64_t)total_words;
+    if (int st = check_reads_batch(as_bases, total_words, count, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist, d_word_offsets, d_offsets, true, &done, err)) return st;
+    if (done) return BITNUC_OK;
+    DeviceGuard g(c->device);
+    if (k == 0 || n_queries == 0 || total_words == 0) return reads_fill_dev(c, count, d_best_query, d_best_pos, d_best_dist, err);
+    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    return launch_reads_batch_packed(c, d_words, d_word_offsets, d_offsets, count, total_words, k, ReadsArgs{d_queries, n_queries, d_best_query, d_best_pos, d_best_dist}, err);
+}
+
+int bitnuc_reads_hdist_best_batch(bitnuc_ctx *c, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
+                                  uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err) {
+    clear_err(err);
+    bool done;
+    if (int st = check_reads_batch(0, 0, count, k, queries, n_queries, best_query, best_pos, best_dist, offsets, nullptr, false, &done, err)) return st;
+    if (done) return BITNUC_OK;
+    const BatchFault f = batch_check_tables(offsets, nullptr, count);
+    if (f.kind) return fail_batch_tables(f, err);
+    const size_t total = (size_t)offsets[count];
+    if (k == 0 || n_queries == 0 || total < k) { bitnuc_host::reads_best_fill(count, best_query, best_pos, best_dist); return BITNUC_OK; }
+    if (!seq) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, multi_work(batch_windows(offsets, count, k), n_queries))) {
+        const long long bad = bitnuc_host::reads_hdist_best_batch_small(seq, offsets, count, k, queries, n_queries, best_query, best_pos, best_dist);
+        if (bad >= 0) {
+            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = seq[bad]; err->index = (uint64_t)bad; }
+            return BITNUC_INVALID_BASE;
+        }
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    std::vector<uint64_t> tab; // the chunk's rebased table
+    return reads_batch_host_loop(
+        c, count, queries, n_queries, best_query, best_pos, best_dist, err,
+        [&](size_t r0) { return batch_chunk_end(r0, count, kHostChunk, [&](size_t a, size_t b) { return offsets[b] - offsets[a]; }); },
+        [&](size_t r0, size_t m, const ReadsArgs &a) {
+            const size_t b0 = (size_t)offsets[r0], bytes = (size_t)offsets[r0 + m] - b0;
+            if (bytes < k) { // no window in the chunk and nothing to launch: its bytes are still validated, here
+                for (size_t i = 0; i < bytes; ++i) {
+                    const unsigned u = seq[b0 + i] & 0xDFu;
+                    if (u != 'A' && u != 'C' && u != 'G' && u != 'T') {
+                        if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = seq[b0 + i]; err->index = (uint64_t)(b0 + i); }
+                        return (int)BITNUC_INVALID_BASE;
+                    }
+                }
+                return reads_fill_dev(c, m, a.query, a.pos, a.dist, err);
+            }
+            if (int st = ensure_scratch(c, 0, bytes + 64, err)) return st;
+            if (int st = ensure_scratch(c, 4, (m + 1) * 8, err)) return st;
+            tab.resize(m + 1);
+            for (size_t i = 0; i <= m; ++i) tab[i] = offsets[r0 + i] - b0;
+            HIPCHK(hipMemcpyAsync(c->scratch[0], seq + b0, bytes, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(c->scratch[4], tab.data(), (m + 1) * 8, hipMemcpyHostToDevice, c->stream));
+            unsigned long long *slot;
+            if (int st = take_slot(c, b0, &slot, err)) return st;
+            return launch_reads_batch(c, c->scratch[0], reinterpret_cast<const uint64_t *>(c->scratch[4]), m, bytes, k, a, slot, err);
+        });
+}
+
+int bitnuc_reads_hdist_best_batch_packed(bitnuc_ctx *c, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
+                                         const uint64_t *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err) {
+    clear_err(err);
+    bool done;
+    if (int st = check_reads_batch(0, 0, count, k, queries, n_queries, best_query, best_pos, best_dist, word_offsets, offsets, true, &done, err)) return st;
+    if (done) return BITNUC_OK;
+    const BatchFault f = batch_check_tables(offsets, word_offsets, count);
+    if (f.kind) return fail_batch_tables(f, err);
+    if (k == 0 || n_queries == 0 || offsets[count] < k) { bitnuc_host::reads_best_fill(count, best_query, best_pos, best_dist); return BITNUC_OK; }
+    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, multi_work(batch_windows(offsets, count, k), n_queries))) {
+        bitnuc_host::reads_hdist_best_batch_packed_small(words, word_offsets, offsets, count, k, queries, n_queries, best_query, best_pos, best_dist);
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    std::vector<uint64_t> tab; // the chunk's two rebased tables: word_offsets, then offsets
+    return reads_batch_host_loop(
+        c, count, queries, n_queries, best_query, best_pos, best_dist, err,
+        [&](size_t r0) { return batch_chunk_end(r0, count, kPackedChunkWords, [&](size_t a, size_t b) { return word_offsets[b] - word_offsets[a]; }); },
+        [&](size_t r0, size_t m, const ReadsArgs &a) {
+            const size_t w0 = (size_t)word_offsets[r0], nw = (size_t)word_offsets[r0 + m] - w0;
+            if (nw == 0) return reads_fill_dev(c, m, a.query, a.pos, a.dist, err);
+            if (int st = ensure_scratch(c, 0, nw * 8, err)) return st;
+            if (int st = ensure_scratch(c, 4, 2 * (m + 1) * 8, err)) return st;
+            tab.resize(2 * (m + 1));
+            for (size_t i = 0; i <= m; ++i) tab[i] = word_offsets[r0 + i] - w0, tab[m + 1 + i] = offsets[r0 + i] - offsets[r0];
+            HIPCHK(hipMemcpyAsync(c->scratch[0], words + w0, nw * 8, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(c->scratch[4], tab.data(), 2 * (m + 1) * 8, hipMemcpyHostToDevice, c->stream));
+            const uint64_t *d_tab = reinterpret_cast<const uint64_t *>(c->scratch[4]);
+            return launch_reads_batch_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), d_tab, d_tab + m + 1, m, nw, k, a, err);
+        });
 }
 
 // ---- pattern queries: a set of bases per position (bitnuc_pattern).  The twelve entry points below are the twins of the exact ones above: the same checks

@@ -330,6 +330,29 @@ class Context {
             return NucleotideError::from_c(e);
         return b;
     }
+    // ... of a ragged batch: read r is seq[offsets[r] .. offsets[r + 1]) (offsets: count + 1 non-decreasing entries from 0, seq.len >= offsets.back())
+    Result<ReadsBest> reads_hdist_best_batch(Bytes seq, const std::vector<uint64_t> &offsets, size_t k, const std::vector<uint64_t> &queries) const {
+        const size_t count = offsets.empty() ? 0 : offsets.size() - 1;
+        if (count && seq.len < offsets.back()) return NucleotideError::invalid_length(seq.len); // seq does not hold offsets.back() bases
+        ReadsBest b{std::vector<uint32_t>(count), std::vector<uint32_t>(count), std::vector<uint8_t>(count)};
+        bitnuc_err e;
+        if (bitnuc_reads_hdist_best_batch(ctx_, seq.ptr, offsets.data(), count, k, queries.data(), queries.size(), b.query.data(), b.pos.data(), b.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
+    // ... of the packed words encode_batch writes: read r's words start at words[word_offsets[r]] (word_offsets.size() == offsets.size())
+    Result<ReadsBest> reads_hdist_best_batch_packed(Words words, const std::vector<uint64_t> &word_offsets, const std::vector<uint64_t> &offsets, size_t k,
+                                                    const std::vector<uint64_t> &queries) const {
+        const size_t count = offsets.empty() ? 0 : offsets.size() - 1;
+        if (word_offsets.size() != offsets.size()) return NucleotideError::unsupported(); // one word offset per base offset: the call reads count + 1 of each
+        if (count && words.len < word_offsets.back()) return NucleotideError::invalid_length(words.len); // words does not hold word_offsets.back() words
+        ReadsBest b{std::vector<uint32_t>(count), std::vector<uint32_t>(count), std::vector<uint8_t>(count)};
+        bitnuc_err e;
+        if (bitnuc_reads_hdist_best_batch_packed(ctx_, words.ptr, word_offsets.data(), offsets.data(), count, k, queries.data(), queries.size(), b.query.data(), b.pos.data(),
+                                                 b.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
     Result<std::vector<uint64_t>> kmer_hdist_hits_packed(Words words, size_t n, size_t k, uint64_t query, unsigned tau, std::vector<uint8_t> *hit_dist = nullptr) const {
         uint64_t total = 0;
         bitnuc_err e;

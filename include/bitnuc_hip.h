@@ -429,6 +429,49 @@ int bitnuc_reads_hdist_best(bitnuc_ctx *ctx, const uint8_t *reads, size_t read_l
 int bitnuc_reads_hdist_best_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t read_len, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
                                    uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err);
 
+/* ---- best match per read of a RAGGED batch (reads after trimming, merged pairs, amplicons, long reads, contigs): the twins of the block above for
+ * the layout the ragged batch entry points read and write ----
+ * Layout.  Read r is seq[offsets[r] .. offsets[r+1]) -- `offsets` has count + 1 non-decreasing entries and offsets[0] == 0 (a batch cut out of a larger
+ * table passes a rebased table) --, and packed its ceil(len_r/32) words start at words[word_offsets[r]]: exactly what bitnuc_encode_batch* writes.  The
+ * bits above a read's last base are ignored; a zero-length read has no words.  total_bases == offsets[count] and total_words == word_offsets[count]:
+ * the caller knows both, as for bitnuc_encode_batch_dev.
+ * Result.  For every read r the minimum over q < n_queries and 0 <= i <= len_r - k of hdist_scalar(as_2bit(read_r[i .. i+k]), queries[q], k), ties by
+ * the smallest q, then the smallest i; a window never crosses into the next read; query bits above 2k are ignored; deterministic.  Exactly [0, count) of
+ * each output is written; best_dist may have any byte offset.  A read without a window (len_r < k, empty), and every read when k == 0 or
+ * n_queries == 0: UINT32_MAX, UINT32_MAX, 0xFF.  On a batch whose reads all have length L the results equal bitnuc_reads_hdist_best* with
+ * read_len = L, byte for byte.
+ * Checks, in this order: (1) ctx NULL -> UNSUPPORTED (the host forms accept NULL below the host cutoff); (2) k > 32 -> SEQUENCE_TOO_LONG(k);
+ * (3) total_bases, or 32*total_words, not below 2^58 -> UNSUPPORTED (value = that total; the host forms have no such argument and bound their tables'
+ * totals at the end of check 7); (4) n_queries > BITNUC_MAX_QUERIES -> UNSUPPORTED (value = n_queries); (5) count == 0 -> OK, nothing written; (6) an
+ * output NULL, best_query / best_pos not 4-byte aligned, queries NULL with n_queries > 0 or not 8-byte aligned, an offsets table NULL or not 8-byte
+ * aligned -> UNSUPPORTED; (7) host forms only, the tables: decreasing offsets -> INVALID_RANGE exactly as bitnuc_encode_batch reports it,
+ * offsets[0] != 0 -> INVALID_RANGE (value 0), a word_offsets table that is not the one encode_batch produces for these offsets -> INVALID_RANGE as
+ * bitnuc_decode_batch, a read of 2^32 - 1 bases or more -> UNSUPPORTED (value = its length); (8) no window is possible from the host-known arguments
+ * (k == 0, n_queries == 0, total_bases < k; packed _async: total_words == 0) -> OK with the fill above in every read, nothing read or validated;
+ * (9) seq NULL, or words NULL or not 8-byte aligned -> UNSUPPORTED.
+ * The _async forms TRUST their tables, as the _dev batch forms do: the caller promises tables as above (non-decreasing from 0, word_offsets the table
+ * encode_batch produces for offsets, the totals their last entries) and reads below 2^32 - 1 bases; anything else is undefined.
+ * ASCII: every byte of seq[0 .. total_bases) is validated, whether or not its read is long enough to hold a window; a non-ACGT byte (either case is
+ * valid) -> INVALID_BASE with the first invalid byte in buffer order (index = its offset in seq), latched once per call for bitnuc_ctx_sync(), the
+ * outputs are then unspecified; the host forms below the cutoff leave the outputs untouched.
+ * The _async forms have the _dev contract (device pointers for everything, the context's stream, no host synchronisation but the growth of context
+ * scratch) and can be captured into a hipGraph after a warm-up with the same or larger (count, n_queries); the tables are read on the device at every
+ * replay, so a replay after the lengths changed (same count and totals) gives the new answers.  d_seq may have any alignment; d_words must be 8-byte
+ * aligned (0 or 8 mod 16).  The host forms judge the sum over the reads of max(0, len_r - k + 1), times n_queries, saturated, against the host cutoff;
+ * above it they run through the context in chunks of whole reads (the longest run of whole reads within the chunk budget, at least one), each with
+ * its rebased tables; INVALID_BASE indices stay absolute.
+ * Speed: packed words run on the matrix cores throughout; ASCII wherever 1024 consecutive windows touch no read of 1 .. 31 bases (those windows take
+ * an exact one-window-per-thread path with the same result, as does a stretch of 4096 windows that touches more than 132 reads, empty ones included). */
+int bitnuc_reads_hdist_best_batch_async(bitnuc_ctx *ctx, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k,
+                                        const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err);
+int bitnuc_reads_hdist_best_batch_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
+                                               size_t total_words, size_t k, const uint64_t *d_queries, size_t n_queries,
+                                               uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err);
+int bitnuc_reads_hdist_best_batch(bitnuc_ctx *ctx, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
+                                  uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err);
+int bitnuc_reads_hdist_best_batch_packed(bitnuc_ctx *ctx, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
+                                         const uint64_t *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err);
+
 /* ---- analysis on packed words (the callers just above the codec) ------ */
 /* BaseCount::base_counts / GCContent::gc_content of a packed sequence
  * (src/utils/analysis.rs:7-39: the reference decodes to ASCII, then counts bytes): counts[] =

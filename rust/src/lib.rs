@@ -363,6 +363,32 @@ pub fn reads_hdist_best_packed(words: &[u64], read_len: usize, count: usize, k: 
     if st == ffi::BITNUC_OK { Ok((query, pos, dist)) } else { Err(to_err(&e)) }
 }
 
+/// The best match per read of a ragged batch: read `r` is `seq[offsets[r] .. offsets[r + 1])` (`offsets` has `count + 1` non-decreasing entries
+/// from 0).  `(query, pos, dist)` as `reads_hdist_best`; an empty read or one shorter than `k` gets `u32::MAX`, `u32::MAX`, `255`.
+pub fn reads_hdist_best_batch(seq: &[u8], offsets: &[u64], k: usize, queries: &[u64]) -> Result<(Vec<u32>, Vec<u32>, Vec<u8>), NucleotideError> {
+    let count = offsets.len().saturating_sub(1);
+    assert!(count == 0 || seq.len() as u64 >= offsets[count], "seq holds offsets[count] bases");
+    let (mut query, mut pos, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_hdist_best_batch(c, seq.as_ptr(), offsets.as_ptr(), count, k, queries.as_ptr(), queries.len(), query.as_mut_ptr(), pos.as_mut_ptr(), dist.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok((query, pos, dist)) } else { Err(to_err(&e)) }
+}
+
+/// `reads_hdist_best_batch` of the packed words `encode_batch` writes (read `r`'s words start at `words[word_offsets[r]]`), without decoding them.
+pub fn reads_hdist_best_batch_packed(words: &[u64], word_offsets: &[u64], offsets: &[u64], k: usize, queries: &[u64]) -> Result<(Vec<u32>, Vec<u32>, Vec<u8>), NucleotideError> {
+    let count = offsets.len().saturating_sub(1);
+    assert!(word_offsets.len() == offsets.len(), "one word offset per base offset");
+    assert!(count == 0 || words.len() as u64 >= word_offsets[count], "words holds word_offsets[count] words");
+    let (mut query, mut pos, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_hdist_best_batch_packed(c, words.as_ptr(), word_offsets.as_ptr(), offsets.as_ptr(), count, k, queries.as_ptr(), queries.len(), query.as_mut_ptr(), pos.as_mut_ptr(), dist.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok((query, pos, dist)) } else { Err(to_err(&e)) }
+}
+
 /// A pattern query: a set of bases per position (`allow[c]` bit `i` set <=> base code `c` matches at position `i`).
 pub use ffi::bitnuc_pattern as Pattern;
 
