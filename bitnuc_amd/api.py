@@ -415,6 +415,36 @@ class Context:
             raise ValueError("words must hold count reads of ceil(read_len / 32) words each")
         return self._reads_best(self._lib.bitnuc_reads_hdist_best_packed, (_ptr(w), int(read_len), int(count), int(k)), int(count), queries)
 
+    def _reads_best2(self, fn, head, count, queries):
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.uint64).reshape(-1))  # a scalar query: Q = 1
+        out = [np.empty(count, dtype=t) for t in (np.uint32, np.uint32, np.uint8, np.uint32, np.uint32, np.uint8)]
+        err = L.BitnucErr()
+        if fn(self._h, *head, _ptr(q), q.size, *(_ptr(a) for a in out), C.byref(err)) != L.OK:
+            _raise(err)
+        return tuple(out)
+
+    def reads_hdist_best2(self, reads, read_len, k, queries, count=None):
+        """The best match per read as reads_hdist_best, and the runner-up: (query, pos, dist, second_query, second_pos, second_dist), the second triple
+        the smallest (distance, query index, offset) over the queries other than the winner's -- another window of the winning query is never the
+        runner-up; with one query it is 2^32 - 1, 2^32 - 1, 255.  `count` defaults to len(reads) / read_len."""
+        s = _as_u8(reads)
+        read_len = int(read_len)
+        if count is None:
+            if read_len <= 0 or s.size % read_len:
+                raise ValueError("reads must hold a whole number of reads of read_len bases")
+            count = s.size // read_len
+        count = int(count)
+        if s.size < count * read_len:
+            raise ValueError("reads must hold count reads of read_len bases")
+        return self._reads_best2(self._lib.bitnuc_reads_hdist_best2, (_ptr(s), read_len, count, int(k)), count, queries)
+
+    def reads_hdist_best2_packed(self, words, read_len, count, k, queries):
+        """reads_hdist_best2 of the packed words encode_fixed writes (ceil(read_len / 32) words per read), without decoding them."""
+        w = _as_u64(words)
+        if w.size < int(count) * ((int(read_len) + 31) // 32):
+            raise ValueError("words must hold count reads of ceil(read_len / 32) words each")
+        return self._reads_best2(self._lib.bitnuc_reads_hdist_best2_packed, (_ptr(w), int(read_len), int(count), int(k)), int(count), queries)
+
     def reads_hdist_best_batch(self, seq, offsets, k, queries):
         """The best match per read of a ragged batch: read r is seq[offsets[r]:offsets[r + 1]] (`offsets`: count + 1 non-decreasing entries from 0).
         (query, pos, dist) as reads_hdist_best; an empty read, or one shorter than k: 2^32 - 1, 2^32 - 1, 255."""
@@ -797,6 +827,19 @@ class Context:
         """The best match per read on the packed words encode_fixed_dev writes (8-byte aligned, ceil(read_len / 32) words per read)."""
         self._call_dev(self._lib.bitnuc_reads_hdist_best_packed_async, _dev_ptr(d_words), int(read_len), int(count), int(k), _dev_ptr(d_queries),
                        int(n_queries), _dev_ptr(d_best_query), _dev_ptr(d_best_pos), _dev_ptr(d_best_dist))
+
+    def reads_hdist_best2_async(self, d_reads, read_len, count, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist, d_second_query, d_second_pos,
+                                d_second_dist):
+        """reads_hdist_best_async with the runner-up: d_second_query[r], d_second_pos[r] (u32), d_second_dist[r] (u8) = the smallest (distance, query,
+        offset) over the queries other than d_best_query[r].  Asynchronous on the context's stream, as the _dev calls."""
+        self._call_dev(self._lib.bitnuc_reads_hdist_best2_async, _dev_ptr(d_reads), int(read_len), int(count), int(k), _dev_ptr(d_queries), int(n_queries),
+                       _dev_ptr(d_best_query), _dev_ptr(d_best_pos), _dev_ptr(d_best_dist), _dev_ptr(d_second_query), _dev_ptr(d_second_pos), _dev_ptr(d_second_dist))
+
+    def reads_hdist_best2_packed_async(self, d_words, read_len, count, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist, d_second_query, d_second_pos,
+                                       d_second_dist):
+        """The best match and the runner-up per read on the packed words encode_fixed_dev writes (8-byte aligned, ceil(read_len / 32) words per read)."""
+        self._call_dev(self._lib.bitnuc_reads_hdist_best2_packed_async, _dev_ptr(d_words), int(read_len), int(count), int(k), _dev_ptr(d_queries), int(n_queries),
+                       _dev_ptr(d_best_query), _dev_ptr(d_best_pos), _dev_ptr(d_best_dist), _dev_ptr(d_second_query), _dev_ptr(d_second_pos), _dev_ptr(d_second_dist))
 
     def reads_hdist_best_batch_async(self, d_seq, d_offsets, count, total_bases, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist):
         """The best match per read of a ragged batch of ASCII reads in device memory: read r is d_seq[d_offsets[r] .. d_offsets[r + 1]) (u64, count + 1

@@ -19,6 +19,7 @@
 #include "scan_multi_host.h"
 #include "scan_best_host.h"
 #include "reads_best_host.h"
+#include "reads_best2_host.h"
 #include "reads_batch_host.h"
 #include "scan_hist_host.h"
 #include "pattern_host.h"
@@ -703,19 +704,24 @@ struct ScanJob {
 // it (ensure_scratch: warm up with the same or larger (count, n_queries) before capturing).  The keys are set to all-ones first in the same stream,
 // the waves take their per-read minima into them and reads_finish_kernel writes query[] / pos[] / dist[].  The grid: the best match's (one workgroup
 // per CU at most x the query blocks); a batch whose period is below a segment, or too small for a round, spreads its windows over more workgroups.
+// The runner-up (bitnuc_reads_hdist_best2*) keeps two key arrays there: keys1 with one spare entry (count + 1: the exclusion form's loads), then keys2,
+// both set to all-ones by one memset; the second pass reads keys1 and fills keys2, reads_finish2_kernel writes the six outputs.
 template <class HQ> struct ReadsArgsT { const HQ *queries; size_t nq; uint32_t *query, *pos; uint8_t *dist; };
 using ReadsArgs = ReadsArgsT<uint64_t>;
+struct ReadsSecond { uint32_t *query, *pos; uint8_t *dist; }; // the runner-up's outputs
 
 inline ReadsGeom reads_geom(size_t period, size_t read_len, size_t k) { return ReadsGeom{period, (unsigned)(read_len - k), 1.0f / (float)period}; }
 
 template <bool PACKED, class HQ>
 int reads_setup(bitnuc_ctx *c, size_t k, size_t count, unsigned long long n, unsigned long long rounds, const ReadsArgsT<HQ> &a, unsigned long long **keys,
-                const BestTable **tabs, dim3 *grid, bitnuc_err *err) {
-    const size_t kbytes = (count * 8 + 255) & ~(size_t)255;
+                const BestTable **tabs, dim3 *grid, bitnuc_err *err, unsigned long long **keys2 = nullptr) {
+    const size_t nkeys = keys2 ? 2 * count + 1 : count;
+    const size_t kbytes = (nkeys * 8 + 255) & ~(size_t)255;
     if (int st = ensure_scratch(c, 10, kbytes + a.nq * sizeof(BestTable), err)) return st;
     *keys = reinterpret_cast<unsigned long long *>(c->scratch[10]);
+    if (keys2) *keys2 = *keys + count + 1;
     BestTable *t = reinterpret_cast<BestTable *>(c->scratch[10] + kbytes);
-    HIPCHK(hipMemsetAsync(*keys, 0xFF, count * sizeof(uint64_t), c->stream));
+    HIPCHK(hipMemsetAsync(*keys, 0xFF, nkeys * sizeof(uint64_t), c->stream));
     best_tables_kernel<PACKED><<<(unsigned)a.nq, 64, 0, c->stream>>>(dev_queries(a.queries), (unsigned)k, t);
     HIPCHK(hipGetLastError());
     *tabs = t;
@@ -736,35 +742,60 @@ int reads_finish(bitnuc_ctx *c, const unsigned long long *keys, size_t count, co
     return BITNUC_OK;
 }
 
-// d_reads at any alignment (ascii_skip); 1 <= k <= read_len, count >= 1, nq >= 1
 template <class HQ>
-int launch_reads_best(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, const ReadsArgsT<HQ> &a, unsigned long long *slot, bitnuc_err *err) {
+int reads_finish2(bitnuc_ctx *c, const unsigned long long *keys, const unsigned long long *keys2, size_t count, const ReadsArgsT<HQ> &a, const ReadsSecond &b,
+                  bitnuc_err *err) {
+    HIPCHK(hipGetLastError());
+    const size_t want = (count + 255) / 256, cap = (size_t)c->num_cu * 8;
+    reads_finish2_kernel<<<(unsigned)(want < cap ? want : cap), 256, 0, c->stream>>>(keys, keys2, count, a.query, a.pos, a.dist, b.query, b.pos, b.dist);
+    HIPCHK(hipGetLastError());
+    return BITNUC_OK;
+}
+
+// d_reads at any alignment (ascii_skip); 1 <= k <= read_len, count >= 1, nq >= 1.  second: the runner-up's outputs as well -- the exclusion pass over
+// the same reads (none with one query: keys2 stays all-ones, the fill)
+template <class HQ>
+int launch_reads_best(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, const ReadsArgsT<HQ> &a, unsigned long long *slot, bitnuc_err *err,
+                      const ReadsSecond *second = nullptr) {
     const unsigned skip = ascii_skip(reads);
     const unsigned long long n = (unsigned long long)count * read_len;
     const unsigned long long rounds = read_len >= kReadsMinPeriod ? scan_rounds(n, skip) : 0;
-    unsigned long long *keys;
+    unsigned long long *keys, *keys2 = nullptr;
     const BestTable *tabs;
     dim3 grid;
-    if (int st = reads_setup<false>(c, k, count, n, rounds, a, &keys, &tabs, &grid, err)) return st;
-    reads_best_kernel<kMultiRounds><<<grid, kMultiBlock, 0, c->stream>>>(reads, n, skip, rounds, (unsigned)k, reads_geom(read_len, read_len, k), dev_queries(a.queries),
-                                                                        (unsigned)a.nq, tabs, keys, slot);
-    return reads_finish(c, keys, count, a, err);
+    if (int st = reads_setup<false>(c, k, count, n, rounds, a, &keys, &tabs, &grid, err, second ? &keys2 : nullptr)) return st;
+    const ReadsGeom g = reads_geom(read_len, read_len, k);
+    reads_best_kernel<kMultiRounds, false><<<grid, kMultiBlock, 0, c->stream>>>(reads, n, skip, rounds, (unsigned)k, g, dev_queries(a.queries), (unsigned)a.nq, tabs, keys,
+                                                                               slot);
+    if (!second) return reads_finish(c, keys, count, a, err);
+    if (a.nq > 1) {
+        HIPCHK(hipGetLastError());
+        reads_best_kernel<kMultiRounds, true><<<grid, kMultiBlock, 0, c->stream>>>(reads, n, skip, rounds, (unsigned)k, g, dev_queries(a.queries), (unsigned)a.nq, tabs,
+                                                                                  keys, nullptr); // (keys2 == keys + count + 1: the kernel's own sum)
+    }
+    return reads_finish2(c, keys, keys2, count, a, *second, err);
 }
 
 // d_words 8-byte aligned (packed_skip): the period is a whole number of words
 template <class HQ>
-int launch_reads_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, const ReadsArgsT<HQ> &a, bitnuc_err *err) {
+int launch_reads_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, const ReadsArgsT<HQ> &a, bitnuc_err *err,
+                             const ReadsSecond *second = nullptr) {
     const unsigned skip = packed_skip(words);
     const size_t period = 32 * words_for(read_len);
     const unsigned long long n = (unsigned long long)count * period;
     const unsigned long long rounds = scan_rounds(n, skip);
-    unsigned long long *keys;
+    unsigned long long *keys, *keys2 = nullptr;
     const BestTable *tabs;
     dim3 grid;
-    if (int st = reads_setup<true>(c, k, count, n, rounds, a, &keys, &tabs, &grid, err)) return st;
-    reads_best_packed_kernel<<<grid, kMultiBlock, 0, c->stream>>>(words, n, skip, rounds, (unsigned)k, reads_geom(period, read_len, k), dev_queries(a.queries),
-                                                                  (unsigned)a.nq, tabs, keys);
-    return reads_finish(c, keys, count, a, err);
+    if (int st = reads_setup<true>(c, k, count, n, rounds, a, &keys, &tabs, &grid, err, second ? &keys2 : nullptr)) return st;
+    const ReadsGeom g = reads_geom(period, read_len, k);
+    reads_best_packed_kernel<false><<<grid, kMultiBlock, 0, c->stream>>>(words, n, skip, rounds, (unsigned)k, g, dev_queries(a.queries), (unsigned)a.nq, tabs, keys);
+    if (!second) return reads_finish(c, keys, count, a, err);
+    if (a.nq > 1) {
+        HIPCHK(hipGetLastError());
+        reads_best_packed_kernel<true><<<grid, kMultiBlock, 0, c->stream>>>(words, n, skip, rounds, (unsigned)k, g, dev_queries(a.queries), (unsigned)a.nq, tabs, keys);
+    }
+    return reads_finish2(c, keys, keys2, count, a, *second, err);
 }
 
 // the reads calls' checks 2 - 6 (after ctx): *done = nothing to do (count == 0)
@@ -782,6 +813,12 @@ int check_reads(size_t read_len, size_t count, size_t k, const void *queries, si
     if (!query || !pos || !dist || (reinterpret_cast<uintptr_t>(query) & 3) || (reinterpret_cast<uintptr_t>(pos) & 3) || (!queries && nq) ||
         (reinterpret_cast<uintptr_t>(queries) & 7))
         return fail(err, BITNUC_UNSUPPORTED);
+    return BITNUC_OK;
+}
+
+// check 6 of the runner-up calls: its three outputs as well (after check_reads, count > 0)
+int check_reads_second(const void *query, const void *pos, const void *dist, bitnuc_err *err) {
+    if (!query || !pos || !dist || (reinterpret_cast<uintptr_t>(query) & 3) || (reinterpret_cast<uintptr_t>(pos) & 3)) return fail(err, BITNUC_UNSUPPORTED);
     return BITNUC_OK;
 }
 
@@ -817,6 +854,35 @@ int reads_host_loop(bitnuc_ctx *c, size_t count, size_t per, const uint64_t *que
         HIPCHK(hipMemcpyAsync(query + r0, d_query, m * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(pos + r0, d_pos, m * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(dist + r0, c->scratch[3], m, hipMemcpyDeviceToHost, c->stream));
+        bitnuc_err e;
+        if (int st = drain(c, &e)) { if (err) *err = e; return st; }
+    }
+    return BITNUC_OK;
+}
+
+// reads_host_loop with the runner-up's outputs: four query / pos arrays in scratch 1, two distance arrays in scratch 3.  A chunk holds whole reads, so
+// both triples are the chunk's own: nothing is merged across chunks.
+template <class Launch>
+int reads_host_loop2(bitnuc_ctx *c, size_t count, size_t per, const uint64_t *queries, size_t nq, uint32_t *query, uint32_t *pos, uint8_t *dist, uint32_t *query2,
+                     uint32_t *pos2, uint8_t *dist2, bitnuc_err *err, Launch launch) {
+    const size_t pm = count < per ? count : per;
+    if (int st = ensure_scratch(c, 1, pm * 16, err)) return st;
+    if (int st = ensure_scratch(c, 2, nq * 8, err)) return st;
+    if (int st = ensure_scratch(c, 3, 2 * pm < 64 ? 64 : 2 * pm, err)) return st;
+    HIPCHK(hipMemcpyAsync(c->scratch[2], queries, nq * 8, hipMemcpyHostToDevice, c->stream));
+    uint32_t *d_query = reinterpret_cast<uint32_t *>(c->scratch[1]), *d_pos = d_query + pm, *d_query2 = d_pos + pm, *d_pos2 = d_query2 + pm;
+    uint8_t *d_dist = c->scratch[3], *d_dist2 = d_dist + pm;
+    const ReadsArgs a{reinterpret_cast<const uint64_t *>(c->scratch[2]), nq, d_query, d_pos, d_dist};
+    const ReadsSecond b{d_query2, d_pos2, d_dist2};
+    for (size_t r0 = 0; r0 < count; r0 += per) {
+        const size_t m = count - r0 < per ? count - r0 : per;
+        if (int st = launch(r0, m, a, b)) return st;
+        HIPCHK(hipMemcpyAsync(query + r0, d_query, m * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(pos + r0, d_pos, m * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(dist + r0, d_dist, m, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(query2 + r0, d_query2, m * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(pos2 + r0, d_pos2, m * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(dist2 + r0, d_dist2, m, hipMemcpyDeviceToHost, c->stream));
         bitnuc_err e;
         if (int st = drain(c, &e)) { if (err) *err = e; return st; }
     }
@@ -1561,6 +1627,116 @@ int bitnuc_reads_hdist_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t 
     return reads_host_loop(c, count, per, queries, n_queries, best_query, best_pos, best_dist, err, [&](size_t r0, size_t m, const ReadsArgs &a) {
         HIPCHK(hipMemcpyAsync(c->scratch[0], words + r0 * wpr, m * wpr * 8, hipMemcpyHostToDevice, c->stream));
         return launch_reads_best_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), read_len, m, k, a, err);
+    });
+}
+
+// ---- the best match and the runner-up per read of a fixed-length batch ---------------------------------------------------------------
+int bitnuc_reads_hdist_best2_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const uint64_t *d_queries, size_t n_queries,
+                                   uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_pos,
+                                   uint8_t *d_second_dist, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    bool done;
+    if (int st = check_reads(read_len, count, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist, &done, err)) return st;
+    if (done) return BITNUC_OK;
+    if (int st = check_reads_second(d_second_query, d_second_pos, d_second_dist, err)) return st;
+    DeviceGuard g(c->device);
+    if (reads_no_windows(read_len, k, n_queries)) {
+        if (int st = reads_fill_dev(c, count, d_best_query, d_best_pos, d_best_dist, err)) return st;
+        return reads_fill_dev(c, count, d_second_query, d_second_pos, d_second_dist, err);
+    }
+    if (!d_reads) return fail(err, BITNUC_UNSUPPORTED);
+    unsigned long long *slot;
+    if (int st = take_slot(c, 0, &slot, err)) return st;
+    const ReadsSecond b{d_second_query, d_second_pos, d_second_dist};
+    return launch_reads_best(c, d_reads, read_len, count, k, ReadsArgs{d_queries, n_queries, d_best_query, d_best_pos, d_best_dist}, slot, err, &b);
+}
+
+int bitnuc_reads_hdist_best2_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, const uint64_t *d_queries,
+                                          size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, uint32_t *d_second_query,
+                                          uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    bool done;
+    if (int st = check_reads(read_len, count, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist, &done, err)) return st;
+    if (done) return BITNUC_OK;
+    if (int st = check_reads_second(d_second_query, d_second_pos, d_second_dist, err)) return st;
+    DeviceGuard g(c->device);
+    if (reads_no_windows(read_len, k, n_queries)) {
+        if (int st = reads_fill_dev(c, count, d_best_query, d_best_pos, d_best_dist, err)) return st;
+        return reads_fill_dev(c, count, d_second_query, d_second_pos, d_second_dist, err);
+    }
+    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    const ReadsSecond b{d_second_query, d_second_pos, d_second_dist};
+    return launch_reads_best_packed(c, d_words, read_len, count, k, ReadsArgs{d_queries, n_queries, d_best_query, d_best_pos, d_best_dist}, err, &b);
+}
+
+int bitnuc_reads_hdist_best2(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
+                             uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos, uint8_t *second_dist,
+                             bitnuc_err *err) {
+    clear_err(err);
+    bool done;
+    if (int st = check_reads(read_len, count, k, queries, n_queries, best_query, best_pos, best_dist, &done, err)) return st;
+    if (done) return BITNUC_OK;
+    if (int st = check_reads_second(second_query, second_pos, second_dist, err)) return st;
+    if (reads_no_windows(read_len, k, n_queries)) {
+        bitnuc_host::reads_best_fill(count, best_query, best_pos, best_dist);
+        bitnuc_host::reads_best_fill(count, second_query, second_pos, second_dist);
+        return BITNUC_OK;
+    }
+    if (!reads) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, reads_work(read_len, count, k, n_queries))) {
+        const long long bad = bitnuc_host::reads_hdist_best2_small(reads, read_len, count, k, queries, n_queries, best_query, best_pos, best_dist, second_query,
+                                                                   second_pos, second_dist);
+        if (bad >= 0) {
+            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = reads[bad]; err->index = (uint64_t)bad; }
+            return BITNUC_INVALID_BASE;
+        }
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    const size_t per = read_len < kHostChunk ? kHostChunk / read_len : 1, pm = count < per ? count : per; // whole reads per chunk
+    if (int st = ensure_scratch(c, 0, pm * read_len + 64, err)) return st;
+    return reads_host_loop2(c, count, per, queries, n_queries, best_query, best_pos, best_dist, second_query, second_pos, second_dist, err,
+                            [&](size_t r0, size_t m, const ReadsArgs &a, const ReadsSecond &b) {
+        HIPCHK(hipMemcpyAsync(c->scratch[0], reads + r0 * read_len, m * read_len, hipMemcpyHostToDevice, c->stream));
+        unsigned long long *slot;
+        if (int st = take_slot(c, r0 * read_len, &slot, err)) return st;
+        return launch_reads_best(c, c->scratch[0], read_len, m, k, a, slot, err, &b);
+    });
+}
+
+int bitnuc_reads_hdist_best2_packed(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
+                                    uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos,
+                                    uint8_t *second_dist, bitnuc_err *err) {
+    clear_err(err);
+    bool done;
+    if (int st = check_reads(read_len, count, k, queries, n_queries, best_query, best_pos, best_dist, &done, err)) return st;
+    if (done) return BITNUC_OK;
+    if (int st = check_reads_second(second_query, second_pos, second_dist, err)) return st;
+    if (reads_no_windows(read_len, k, n_queries)) {
+        bitnuc_host::reads_best_fill(count, best_query, best_pos, best_dist);
+        bitnuc_host::reads_best_fill(count, second_query, second_pos, second_dist);
+        return BITNUC_OK;
+    }
+    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, reads_work(read_len, count, k, n_queries))) {
+        bitnuc_host::reads_hdist_best2_packed_small(words, read_len, count, k, queries, n_queries, best_query, best_pos, best_dist, second_query, second_pos,
+                                                    second_dist);
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    const size_t wpr = words_for(read_len);
+    const size_t per = wpr < kPackedChunkWords ? kPackedChunkWords / wpr : 1, pm = count < per ? count : per; // whole reads per chunk
+    if (int st = ensure_scratch(c, 0, pm * wpr * 8, err)) return st;
+    return reads_host_loop2(c, count, per, queries, n_queries, best_query, best_pos, best_dist, second_query, second_pos, second_dist, err,
+                            [&](size_t r0, size_t m, const ReadsArgs &a, const ReadsSecond &b) {
+        HIPCHK(hipMemcpyAsync(c->scratch[0], words + r0 * wpr, m * wpr * 8, hipMemcpyHostToDevice, c->stream));
+        return launch_reads_best_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), read_len, m, k, a, err, &b);
     });
 }
 

@@ -31,6 +31,15 @@
 // P < 32 (reads shorter than a segment) runs no rounds: every window takes the one-window-per-thread path, which also serves the windows in front of the
 // rounds and behind the last whole one, with the same admissibility test and one global atomicMin per (window, query block).
 // Invalid bytes (ASCII) are latched by the first query block only, as the best match does.
+//
+// The RUNNER-UP (bitnuc_reads_hdist_best2*): the smallest (distance, query, offset) over the queries other than the winner's.  One pass with atomics
+// cannot give it: which query is excluded is known only when every wave has delivered, so a merge of per-wave (best, second) pairs is no minimum and
+// would depend on the order of arrival.  It is a SECOND PASS of the same kernels in their exclusion form (the template flag EX): keys1[] of the first
+// pass is an input, a lane takes the winners' queries of its two reads A and B from it once per round (two loads that hit L2: keys1 was just written)
+// and an improvement counts only when the query is not that one -- a compare and a select per (round, query) --; the one-window-per-thread path tests
+// the same per query.  keys1 has one spare all-ones entry (B of the run's last segment is read `count`) and keys2 lies right behind it.  An all-ones key's query field is above every
+// query: nothing is excluded.  The second pass validates nothing (the first did).  reads_finish2_kernel writes both triples.  EX = false is the code
+// above, instruction for instruction.
 #pragma once
 #include "device_prims.h"
 #include "scan_best_device.h" // best_tables_kernel, best_tables_to_lds, best_key, kBestScale; the front ends and mfma_chain through it
@@ -52,6 +61,10 @@ struct ReadsGeom {
 
 __device__ __forceinline__ unsigned long long reads_key(uint32_t d, unsigned q, unsigned i) {
     return best_key(d, ((unsigned long long)q << kReadsQueryBits) | i);
+}
+// a key's query; of the all-ones key 2^26 - 1, above every query
+__device__ __forceinline__ uint32_t reads_key_query(unsigned long long key) {
+    return (uint32_t)(key >> kReadsQueryBits) & ((1u << (kBestPosBits - kReadsQueryBits)) - 1u);
 }
 
 // t = a P + o for a quotient below 2^20: a float estimate is within one of it
@@ -113,10 +126,11 @@ __device__ __forceinline__ void reads_table_clear(unsigned long long *table, uns
 }
 
 // One trip: every round against every query of the block, the lane's results into the wave's table, the table into keys[read0 ..].  The trip's first
-// window is window off0 of read read0; read_b(u, B): round u's B operand.
-template <int U, class ReadB>
+// window is window off0 of read read0; read_b(u, B): round u's B operand.  EX: excl[] holds the first pass' keys, whose queries are left out per read.
+template <int U, bool EX, class ReadB>
 __device__ __forceinline__ void reads_trip(const BestTable *qtab, unsigned nq, unsigned q0, unsigned row, unsigned m, unsigned lane, unsigned long long read0,
-                                           unsigned off0, const ReadsGeom &g, unsigned long long *table, unsigned long long *__restrict__ keys, ReadB read_b) {
+                                           unsigned off0, const ReadsGeom &g, unsigned long long *table, unsigned long long *__restrict__ keys,
+                                           const unsigned long long *__restrict__ excl, ReadB read_b) {
     const unsigned m32 = lane & 31u, hh = lane >> 5;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -128,6 +142,11 @@ __device__ __forceinline__ void reads_trip(const BestTable *qtab, unsigned nq, u
         i32x8 B[4];
         read_b(u, B);
         uint32_t ka = kReadsNoA, kb = kReadsNoB, qa = 0, qb = 0;
+        uint32_t xa = 0, xb = 0; // EX: the block's query that A / B leaves out (none of the block's: at or above kMultiQB)
+        if constexpr (EX) {
+            xa = reads_key_query(excl[read0 + a]) - q0;
+            xb = reads_key_query(excl[read0 + a + 1]) - q0; // (at most read `count`: the spare entry)
+        }
 #pragma unroll
         for (int qi = 0; qi < kMultiQB; ++qi) {
             if ((unsigned)qi < nq) { // wave-uniform
@@ -135,8 +154,12 @@ __device__ __forceinline__ void reads_trip(const BestTable *qtab, unsigned nq, u
                 query_operand<4>(qtab[qi].w[row], A);
                 uint32_t mn, mx;
                 round_min_max(mfma_chain(A, B, c0, kBestScale), mn, mx);
-                const bool fa = (mn | 15u) < ka;  // d below A's best d
-                const bool fb = (mx & ~15u) > kb; // d below B's best d
+                bool fa = (mn | 15u) < ka;  // d below A's best d
+                bool fb = (mx & ~15u) > kb; // d below B's best d
+                if constexpr (EX) {
+                    fa = fa && xa != (uint32_t)qi;
+                    fb = fb && xb != (uint32_t)qi;
+                }
                 ka = fa ? mn : ka;
                 qa = fa ? (uint32_t)qi : qa;
                 kb = fb ? mx : kb;
@@ -179,11 +202,11 @@ struct ReadsCursor {
 
 // The windows [0, pre) and [first, n) of the run, one per thread of the grid's x extent, every query of the block: word_of(j) is window j's 2-bit word
 // (read only for an admissible window: it lies inside its read); check(j) validates base j of the run -- the bases behind the last round that only
-// windows of the rounds cover are seen by no window here
-template <class Q, class WordOf, class Check>
+// windows of the rounds cover are seen by no window here.  EX: the query of excl[read] is left out.
+template <bool EX, class Q, class WordOf, class Check>
 __device__ __forceinline__ void reads_tail_windows(unsigned long long pre, unsigned long long first, unsigned long long n, unsigned k, const ReadsGeom &g,
                                                    const Q *__restrict__ queries, unsigned nq, unsigned q0, unsigned long long *__restrict__ keys,
-                                                   WordOf word_of, Check check) {
+                                                   const unsigned long long *__restrict__ excl, WordOf word_of, Check check) {
     const QueryKind<Q> kind(k);
     const unsigned long long gt = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
     const unsigned long long nthreads = (unsigned long long)gridDim.x * blockDim.x;
@@ -195,13 +218,26 @@ __device__ __forceinline__ void reads_tail_windows(unsigned long long pre, unsig
         if (off > g.lim) continue;
         const auto w = kind.window(word_of(j));
         unsigned long long key = kBestNoKey;
+        uint32_t x = 0;
+        if constexpr (EX) x = reads_key_query(excl[read]) - q0;
         for (unsigned qi = 0; qi < nq; ++qi) { // ascending queries: the lowest of equal distances stays
             const unsigned long long c = reads_key(kind.dist(w, queries[qi]), q0 + qi, (unsigned)off);
-            key = c < key ? c : key;
+            if constexpr (EX) key = (c < key && qi != x) ? c : key;
+            else key = c < key ? c : key;
         }
-        atomicMin(keys + read, key);
+        if (!EX || key != kBestNoKey) atomicMin(keys + read, key);
     }
 }
+
+// a kernel's one keys argument: the keys it fills, and with EX the first pass' keys in front of them (count + 1 entries, the last a spare all-ones
+// one; count = n / P)
+template <bool EX> struct ReadsKeys {
+    unsigned long long *out;
+    const unsigned long long *excl;
+    __device__ __forceinline__ ReadsKeys(unsigned long long *keys, unsigned long long n, const ReadsGeom &g) : out(keys), excl(nullptr) {
+        if constexpr (EX) excl = keys, out = keys + n / g.period + 1;
+    }
+};
 
 // keys[r] -> query[r], pos[r], dist[r] (dist at any byte offset)
 __global__ void __launch_bounds__(256) reads_finish_kernel(const unsigned long long *__restrict__ keys, unsigned long long count, uint32_t *__restrict__ query,
@@ -216,10 +252,30 @@ __global__ void __launch_bounds__(256) reads_finish_kernel(const unsigned long l
     }
 }
 
+// the six outputs of the best and the runner-up: keys1[r] -> query[r], pos[r], dist[r]; keys2[r] -> query2[r], pos2[r], dist2[r]
+__global__ void __launch_bounds__(256) reads_finish2_kernel(const unsigned long long *__restrict__ keys1, const unsigned long long *__restrict__ keys2,
+                                                            unsigned long long count, uint32_t *__restrict__ query, uint32_t *__restrict__ pos,
+                                                            uint8_t *__restrict__ dist, uint32_t *__restrict__ query2, uint32_t *__restrict__ pos2,
+                                                            uint8_t *__restrict__ dist2) {
+    const unsigned long long nthreads = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long r = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; r < count; r += nthreads) {
+        const unsigned long long k1 = keys1[r], k2 = keys2[r];
+        const bool none1 = k1 == kBestNoKey, none2 = k2 == kBestNoKey;
+        query[r] = none1 ? 0xFFFFFFFFu : reads_key_query(k1);
+        pos[r] = none1 ? 0xFFFFFFFFu : (uint32_t)k1;
+        dist[r] = none1 ? (uint8_t)0xFF : (uint8_t)(k1 >> kBestPosBits);
+        query2[r] = none2 ? 0xFFFFFFFFu : reads_key_query(k2);
+        pos2[r] = none2 ? 0xFFFFFFFFu : (uint32_t)k2;
+        dist2[r] = none2 ? (uint8_t)0xFF : (uint8_t)(k2 >> kBestPosBits);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Back-to-back ASCII reads at any alignment: the rounds start at reads + skip (16-byte aligned); n = count * read_len, the period is read_len.
-// rounds: the launcher's (scan_rounds(n, skip), or 0 below kReadsMinPeriod).
-template <int U, class Q>
+// rounds: the launcher's (scan_rounds(n, skip), or 0 below kReadsMinPeriod).  EX: the second pass -- keys[0, count] are the first pass' keys (the
+// exclusion's input) and the keys it fills lie behind them, from keys + count + 1 (no further argument: the argument block of EX = false stays the
+// best match's); nothing is validated and slot is unused.
+template <int U, bool EX, class Q>
 __global__ void __launch_bounds__(kMultiBlock)
 reads_best_kernel(const uint8_t *__restrict__ ref, unsigned long long n, unsigned skip, unsigned long long rounds, unsigned k, const ReadsGeom g,
                   const Q *__restrict__ queries, unsigned n_queries, const BestTable *__restrict__ tabs, unsigned long long *__restrict__ keys,
@@ -229,8 +285,9 @@ reads_best_kernel(const uint8_t *__restrict__ ref, unsigned long long n, unsigne
     __shared__ unsigned long long tables[kMultiBlock / 64][kReadsTable];
     const unsigned q0 = blockIdx.y * kMultiQB;
     const unsigned nq = n_queries - q0 < (unsigned)kMultiQB ? n_queries - q0 : (unsigned)kMultiQB;
-    const bool latch = blockIdx.y == 0; // one query block reports invalid bytes
+    const bool latch = !EX && blockIdx.y == 0; // one query block reports invalid bytes
     best_tables_to_lds(tabs + q0, nq, qtab);
+    const ReadsKeys<EX> kk(keys, n, g);
 
     const uint8_t *base = ref + skip;
     const unsigned lane = threadIdx.x & 63;
@@ -256,21 +313,21 @@ reads_best_kernel(const uint8_t *__restrict__ ref, unsigned long long n, unsigne
             }
             if (rn < rounds) scan_trip_load<U, 3, true>(base, rn, rounds, lane, cur); // cur's bytes are in the strip: its registers take the next trip
             wave_lds_fence();
-            reads_trip<U>(qtab, nq, q0, fe.row, m, lane, at.read, (unsigned)at.off, g, table, keys, [&](int u, i32x8 (&B)[4]) { fe.read_b(u, B); });
+            reads_trip<U, EX>(qtab, nq, q0, fe.row, m, lane, at.read, (unsigned)at.off, g, table, kk.out, kk.excl, [&](int u, i32x8 (&B)[4]) { fe.read_b(u, B); });
             at.advance();
             r0 = rn;
         }
     }
 
     const unsigned long long pre = skip < n ? skip : n, first = skip + (rounds << 10);
-    reads_tail_windows(pre, first, n, k, g, queries + q0, nq, q0, keys, [&](unsigned long long j) { return ascii_window_word(ref, j, k, false, slot); },
-                       [&](unsigned long long j) { if (latch && !valid_base(ref[j])) latch_bad(slot, j, ref[j]); });
+    reads_tail_windows<EX>(pre, first, n, k, g, queries + q0, nq, q0, kk.out, kk.excl, [&](unsigned long long j) { return ascii_window_word(ref, j, k, false, slot); },
+                           [&](unsigned long long j) { if (latch && !valid_base(ref[j])) latch_bad(slot, j, ref[j]); });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // The packed words of encode_fixed (8-byte aligned; at 8 mod 16 the rounds start one word later): n = 32 * count * ceil(read_len / 32) bases, the period
 // is 32 * ceil(read_len / 32).  The pad bits above a read's last base only ever reach inadmissible windows.
-template <class Q>
+template <bool EX, class Q>
 __global__ void __launch_bounds__(kMultiBlock)
 reads_best_packed_kernel(const uint64_t *__restrict__ words, unsigned long long n, unsigned skip, unsigned long long rounds, unsigned k, const ReadsGeom g,
                          const Q *__restrict__ queries, unsigned n_queries, const BestTable *__restrict__ tabs, unsigned long long *__restrict__ keys) {
@@ -280,6 +337,7 @@ reads_best_packed_kernel(const uint64_t *__restrict__ words, unsigned long long 
     const unsigned q0 = blockIdx.y * kMultiQB;
     const unsigned nq = n_queries - q0 < (unsigned)kMultiQB ? n_queries - q0 : (unsigned)kMultiQB;
     best_tables_to_lds(tabs + q0, nq, qtab);
+    const ReadsKeys<EX> kk(keys, n, g);
 
     const uint8_t *base = reinterpret_cast<const uint8_t *>(words + (skip >> 5));
     const unsigned lane = threadIdx.x & 63;
@@ -304,7 +362,7 @@ reads_best_packed_kernel(const uint64_t *__restrict__ words, unsigned long long 
             fe.fill(lane, m, cur);
             if (rn < rounds) packed_trip_load(base, rn, rounds, lane, cur); // cur's bases are in the strip: its registers take the next trip
             wave_lds_fence();
-            reads_trip<4>(qtab, nq, q0, fe.row, m, lane, at.read, (unsigned)at.off, g, table, keys, [&](int u, i32x8 (&B)[4]) {
+            reads_trip<4, EX>(qtab, nq, q0, fe.row, m, lane, at.read, (unsigned)at.off, g, table, kk.out, kk.excl, [&](int u, i32x8 (&B)[4]) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) B[j] = PackedStrip4::operand(strip, rd[j], u);
             });
@@ -314,7 +372,8 @@ reads_best_packed_kernel(const uint64_t *__restrict__ words, unsigned long long 
     }
 
     const unsigned long long pre = skip < n ? skip : n, first = skip + (rounds << 10);
-    reads_tail_windows(pre, first, n, k, g, queries + q0, nq, q0, keys, [&](unsigned long long j) { return packed_window_word(words, j, k); }, [](unsigned long long) {});
+    reads_tail_windows<EX>(pre, first, n, k, g, queries + q0, nq, q0, kk.out, kk.excl, [&](unsigned long long j) { return packed_window_word(words, j, k); },
+                           [](unsigned long long) {});
 }
 
 } // namespace bitnuc_dev

@@ -330,6 +330,28 @@ class Context {
             return NucleotideError::from_c(e);
         return b;
     }
+    // the best match and the runner-up per read: `second` is the smallest (distance, query, offset) over the queries other than the winner's (with one
+    // query: UINT32_MAX, UINT32_MAX, 0xFF)
+    struct ReadsBest2 { ReadsBest best, second; };
+    Result<ReadsBest2> reads_hdist_best2(Bytes reads, size_t read_len, size_t k, const std::vector<uint64_t> &queries) const {
+        const size_t count = read_len ? reads.len / read_len : 0;
+        ReadsBest2 b{{std::vector<uint32_t>(count), std::vector<uint32_t>(count), std::vector<uint8_t>(count)},
+                     {std::vector<uint32_t>(count), std::vector<uint32_t>(count), std::vector<uint8_t>(count)}};
+        bitnuc_err e;
+        if (bitnuc_reads_hdist_best2(ctx_, reads.ptr, read_len, count, k, queries.data(), queries.size(), b.best.query.data(), b.best.pos.data(), b.best.dist.data(),
+                                     b.second.query.data(), b.second.pos.data(), b.second.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
+    Result<ReadsBest2> reads_hdist_best2_packed(Words words, size_t read_len, size_t count, size_t k, const std::vector<uint64_t> &queries) const {
+        ReadsBest2 b{{std::vector<uint32_t>(count), std::vector<uint32_t>(count), std::vector<uint8_t>(count)},
+                     {std::vector<uint32_t>(count), std::vector<uint32_t>(count), std::vector<uint8_t>(count)}};
+        bitnuc_err e;
+        if (bitnuc_reads_hdist_best2_packed(ctx_, words.ptr, read_len, count, k, queries.data(), queries.size(), b.best.query.data(), b.best.pos.data(),
+                                            b.best.dist.data(), b.second.query.data(), b.second.pos.data(), b.second.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
     // ... of a ragged batch: read r is seq[offsets[r] .. offsets[r + 1]) (offsets: count + 1 non-decreasing entries from 0, seq.len >= offsets.back())
     Result<ReadsBest> reads_hdist_best_batch(Bytes seq, const std::vector<uint64_t> &offsets, size_t k, const std::vector<uint64_t> &queries) const {
         const size_t count = offsets.empty() ? 0 : offsets.size() - 1;

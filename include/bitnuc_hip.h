@@ -429,6 +429,42 @@ int bitnuc_reads_hdist_best(bitnuc_ctx *ctx, const uint8_t *reads, size_t read_l
 int bitnuc_reads_hdist_best_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t read_len, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
                                    uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err);
 
+/* ---- best match AND runner-up per read of a fixed-length batch (ambiguous barcodes: a read is assigned only if its best barcode is close enough and
+ * no OTHER barcode is nearly as close) -- the twins of the block above with three more outputs ----
+ * Results.  best_query / best_pos / best_dist are exactly what bitnuc_reads_hdist_best* writes, byte for byte.  second_*[r] is the lexicographically
+ * smallest (distance, query, offset) over all queries q != best_query[r] and all windows wholly inside read r: ties by the smallest q, then the
+ * smallest i.  A second window of the winning query is never the runner-up.  Two equal entries of the query list are two queries: the first of them
+ * wins and the second is then the runner-up, at the same distance (and the same offset).  Deterministic.  Exactly [0, count) of each of the six
+ * outputs is written; the two dist arrays may have any byte offset.
+ * Fills (UINT32_MAX, UINT32_MAX, 0xFF).  No window in the read, or no queries (k == 0, read_len < k, n_queries == 0): all six outputs.
+ * n_queries == 1: the second_* triple only; the best triple is real.
+ * Input layouts, alignment, either-case ASCII, pad bits and the trust in count*wpr words: those of bitnuc_reads_hdist_best*, word for word.
+ * Checks, in the order of bitnuc_reads_hdist_best*; check (6) covers all six outputs: any of them NULL, or best_query / best_pos / second_query /
+ * second_pos not 4-byte aligned -> UNSUPPORTED.  Nothing is written on an argument error.
+ * ASCII: a non-ACGT byte -> INVALID_BASE with the first invalid byte in buffer order; the _async form latches it once per call for bitnuc_ctx_sync()
+ * (one call leaves nothing for a second sync), the outputs are then unspecified; the host form below the cutoff leaves all six outputs untouched.
+ * The _async forms have the _dev contract (device pointers for everything, the context's stream, no host synchronisation but the growth of context
+ * scratch) and can be captured into a hipGraph after a warm-up of THIS call with the same or larger (count, n_queries); the reads and the queries are
+ * read at every replay.  The host forms are synchronous and judge windows x n_queries against the host cutoff exactly as bitnuc_reads_hdist_best
+ * does: below it they run on the host (ctx may be NULL), above it through the context in chunks of whole reads, of the twins' sizes; INVALID_BASE
+ * indices stay absolute.
+ * Cost: two passes over the reads in one call (the best match's kernels, then their exclusion form that leaves out each read's winning query, then
+ * one kernel for the six outputs), none with one query.  Measured against bitnuc_reads_hdist_best*_async on the same data (6,666,667 x 150-base
+ * reads, k = 31, one MI355X; profiles/r14_reads_best2.json): 2.02 - 2.03 x its time at 8, 64 and 512 queries, 1.05 x at one.
+ * Out of scope: the ragged twins (*_best_batch*), pattern twins, a per-read exclusion list as an argument, more than two ranks. */
+int bitnuc_reads_hdist_best2_async(bitnuc_ctx *ctx, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const uint64_t *d_queries, size_t n_queries,
+                                   uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_pos,
+                                   uint8_t *d_second_dist, bitnuc_err *err);
+int bitnuc_reads_hdist_best2_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t read_len, size_t count, size_t k, const uint64_t *d_queries,
+                                          size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, uint32_t *d_second_query,
+                                          uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err);
+int bitnuc_reads_hdist_best2(bitnuc_ctx *ctx, const uint8_t *reads, size_t read_len, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
+                             uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos, uint8_t *second_dist,
+                             bitnuc_err *err);
+int bitnuc_reads_hdist_best2_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t read_len, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
+                                    uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos,
+                                    uint8_t *second_dist, bitnuc_err *err);
+
 /* ---- best match per read of a RAGGED batch (reads after trimming, merged pairs, amplicons, long reads, contigs): the twins of the block above for
  * the layout the ragged batch entry points read and write ----
  * Layout.  Read r is seq[offsets[r] .. offsets[r+1]) -- `offsets` has count + 1 non-decreasing entries and offsets[0] == 0 (a batch cut out of a larger

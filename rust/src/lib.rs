@@ -363,6 +363,36 @@ pub fn reads_hdist_best_packed(words: &[u64], read_len: usize, count: usize, k: 
     if st == ffi::BITNUC_OK { Ok((query, pos, dist)) } else { Err(to_err(&e)) }
 }
 
+/// `(query, pos, dist)` of the best match and of the runner-up per read.
+pub type ReadsBest2 = ((Vec<u32>, Vec<u32>, Vec<u8>), (Vec<u32>, Vec<u32>, Vec<u8>));
+
+/// The best match per read as `reads_hdist_best`, and the runner-up: the smallest (distance, query, offset) over the queries other than the
+/// winner's (a second window of the winning query is never the runner-up; with one query it is `u32::MAX`, `u32::MAX`, `255`).
+pub fn reads_hdist_best2(reads: &[u8], read_len: usize, k: usize, queries: &[u64]) -> Result<ReadsBest2, NucleotideError> {
+    let count = if read_len == 0 { 0 } else { reads.len() / read_len };
+    let (mut query, mut pos, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let (mut query2, mut pos2, mut dist2) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_hdist_best2(c, reads.as_ptr(), read_len, count, k, queries.as_ptr(), queries.len(), query.as_mut_ptr(), pos.as_mut_ptr(), dist.as_mut_ptr(),
+                                      query2.as_mut_ptr(), pos2.as_mut_ptr(), dist2.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(((query, pos, dist), (query2, pos2, dist2))) } else { Err(to_err(&e)) }
+}
+
+/// `reads_hdist_best2` of the packed words `encode_fixed` writes (`ceil(read_len / 32)` words per read), without decoding them.
+pub fn reads_hdist_best2_packed(words: &[u64], read_len: usize, count: usize, k: usize, queries: &[u64]) -> Result<ReadsBest2, NucleotideError> {
+    assert!(words.len() >= count * ((read_len + 31) / 32), "count reads of ceil(read_len / 32) words each");
+    let (mut query, mut pos, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let (mut query2, mut pos2, mut dist2) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_hdist_best2_packed(c, words.as_ptr(), read_len, count, k, queries.as_ptr(), queries.len(), query.as_mut_ptr(), pos.as_mut_ptr(), dist.as_mut_ptr(),
+                                             query2.as_mut_ptr(), pos2.as_mut_ptr(), dist2.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(((query, pos, dist), (query2, pos2, dist2))) } else { Err(to_err(&e)) }
+}
+
 /// The best match per read of a ragged batch: read `r` is `seq[offsets[r] .. offsets[r + 1])` (`offsets` has `count + 1` non-decreasing entries
 /// from 0).  `(query, pos, dist)` as `reads_hdist_best`; an empty read or one shorter than `k` gets `u32::MAX`, `u32::MAX`, `255`.
 pub fn reads_hdist_best_batch(seq: &[u8], offsets: &[u64], k: usize, queries: &[u64]) -> Result<(Vec<u32>, Vec<u32>, Vec<u8>), NucleotideError> {
