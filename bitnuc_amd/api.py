@@ -96,6 +96,9 @@ def _as_u64(buf):
     return np.asarray(list(buf), dtype=np.uint64)
 
 
+_SIZE_MAX = C.c_size_t(-1).value  # pos_hi of the anchored calls: to the end of the read
+
+
 def _ptr(a):
     return C.c_void_p(a.ctypes.data if a.size else 0)
 
@@ -444,6 +447,39 @@ class Context:
         if w.size < int(count) * ((int(read_len) + 31) // 32):
             raise ValueError("words must hold count reads of ceil(read_len / 32) words each")
         return self._reads_best2(self._lib.bitnuc_reads_hdist_best2_packed, (_ptr(w), int(read_len), int(count), int(k)), int(count), queries)
+
+    def _reads_anchored(self, fn, head, count, queries, pos_lo, pos_hi, second):
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.uint64).reshape(-1))  # a scalar query: Q = 1
+        types = (np.uint32, np.uint32, np.uint8) * (2 if second else 1)
+        out = [np.empty(count, dtype=t) for t in types]
+        ptrs = [_ptr(a) for a in out] + [None] * (6 - len(out))
+        err = L.BitnucErr()
+        if fn(self._h, *head, int(pos_lo), _SIZE_MAX if pos_hi is None else int(pos_hi), _ptr(q), q.size, *ptrs, C.byref(err)) != L.OK:
+            _raise(err)
+        return tuple(out)
+
+    def reads_hdist_anchored(self, reads, read_len, k, queries, pos_lo=0, pos_hi=None, count=None, second=True):
+        """The best match and the runner-up per read as reads_hdist_best2, over the offsets pos_lo <= i <= min(pos_hi, read_len - k) only (pos_hi None: to
+        the end of the read; the span hi - pos_lo + k may not exceed 64 bases).  (query, pos, dist, second_query, second_pos, second_dist), positions
+        counted in the read; second=False: the best triple only.  Only the span's bytes of each read are read and validated."""
+        s = _as_u8(reads)
+        read_len = int(read_len)
+        if count is None:
+            if read_len <= 0 or s.size % read_len:
+                raise ValueError("reads must hold a whole number of reads of read_len bases")
+            count = s.size // read_len
+        count = int(count)
+        if s.size < count * read_len:
+            raise ValueError("reads must hold count reads of read_len bases")
+        return self._reads_anchored(self._lib.bitnuc_reads_hdist_anchored, (_ptr(s), read_len, count, int(k)), count, queries, pos_lo, pos_hi, second)
+
+    def reads_hdist_anchored_packed(self, words, read_len, count, k, queries, pos_lo=0, pos_hi=None, second=True):
+        """reads_hdist_anchored of the packed words encode_fixed writes (ceil(read_len / 32) words per read), without decoding them."""
+        w = _as_u64(words)
+        if w.size < int(count) * ((int(read_len) + 31) // 32):
+            raise ValueError("words must hold count reads of ceil(read_len / 32) words each")
+        return self._reads_anchored(self._lib.bitnuc_reads_hdist_anchored_packed, (_ptr(w), int(read_len), int(count), int(k)), int(count), queries, pos_lo, pos_hi,
+                                    second)
 
     def reads_hdist_best_batch(self, seq, offsets, k, queries):
         """The best match per read of a ragged batch: read r is seq[offsets[r]:offsets[r + 1]] (`offsets`: count + 1 non-decreasing entries from 0).
@@ -840,6 +876,21 @@ class Context:
         """The best match and the runner-up per read on the packed words encode_fixed_dev writes (8-byte aligned, ceil(read_len / 32) words per read)."""
         self._call_dev(self._lib.bitnuc_reads_hdist_best2_packed_async, _dev_ptr(d_words), int(read_len), int(count), int(k), _dev_ptr(d_queries), int(n_queries),
                        _dev_ptr(d_best_query), _dev_ptr(d_best_pos), _dev_ptr(d_best_dist), _dev_ptr(d_second_query), _dev_ptr(d_second_pos), _dev_ptr(d_second_dist))
+
+    def reads_hdist_anchored_async(self, d_reads, read_len, count, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist, d_second_query=None,
+                                   d_second_pos=None, d_second_dist=None, pos_lo=0, pos_hi=None):
+        """reads_hdist_best2_async over the offsets pos_lo <= i <= min(pos_hi, read_len - k) of every read only (pos_hi None: to the end of the read; a span
+        of at most 64 bases); the three d_second_* all None: the best triple only.  Asynchronous on the context's stream, as the _dev calls."""
+        self._call_dev(self._lib.bitnuc_reads_hdist_anchored_async, _dev_ptr(d_reads), int(read_len), int(count), int(k), int(pos_lo),
+                       _SIZE_MAX if pos_hi is None else int(pos_hi), _dev_ptr(d_queries), int(n_queries), _dev_ptr(d_best_query), _dev_ptr(d_best_pos),
+                       _dev_ptr(d_best_dist), *(_dev_ptr(a) for a in (d_second_query, d_second_pos, d_second_dist)))
+
+    def reads_hdist_anchored_packed_async(self, d_words, read_len, count, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist, d_second_query=None,
+                                          d_second_pos=None, d_second_dist=None, pos_lo=0, pos_hi=None):
+        """reads_hdist_anchored_async on the packed words encode_fixed_dev writes (8-byte aligned, ceil(read_len / 32) words per read)."""
+        self._call_dev(self._lib.bitnuc_reads_hdist_anchored_packed_async, _dev_ptr(d_words), int(read_len), int(count), int(k), int(pos_lo),
+                       _SIZE_MAX if pos_hi is None else int(pos_hi), _dev_ptr(d_queries), int(n_queries), _dev_ptr(d_best_query), _dev_ptr(d_best_pos),
+                       _dev_ptr(d_best_dist), *(_dev_ptr(a) for a in (d_second_query, d_second_pos, d_second_dist)))
 
     def reads_hdist_best_batch_async(self, d_seq, d_offsets, count, total_bases, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist):
         """The best match per read of a ragged batch of ASCII reads in device memory: read r is d_seq[d_offsets[r] .. d_offsets[r + 1]) (u64, count + 1

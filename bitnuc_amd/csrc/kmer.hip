@@ -13,6 +13,7 @@
 #include "scan_best_device.h"
 #include "scan_reads_device.h"
 #include "scan_reads_batch_device.h"
+#include "scan_anchored_device.h"
 #include "scan_hist_device.h"
 #include "scan_mfma_host.h"
 #include "scan_hits_host.h"
@@ -20,6 +21,7 @@
 #include "scan_best_host.h"
 #include "reads_best_host.h"
 #include "reads_best2_host.h"
+#include "reads_anchored_host.h"
 #include "reads_batch_host.h"
 #include "scan_hist_host.h"
 #include "pattern_host.h"
@@ -889,6 +891,93 @@ int reads_host_loop2(bitnuc_ctx *c, size_t count, size_t per, const uint64_t *qu
     return BITNUC_OK;
 }
 
+// ---- the ANCHORED best match and runner-up per read (scan_anchored_device.h): one kernel writes the six outputs.  Context scratch: the per-query
+// tables only (256 bytes per query, after the per-read forms' in scratch 10, shared with them in stream order).
+struct AnchorOut { uint32_t *query, *pos; uint8_t *dist, *dist2; uint32_t *query2, *pos2; }; // query2 == nullptr: the best triple only
+
+// the calls' checks 2 - 7 (after ctx).  *done: nothing to do (count == 0); *offsets == 0: no window (fill), otherwise the offsets per read
+int check_anchored(size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi, const void *queries, size_t nq, const AnchorOut &o, bool *done,
+                   size_t *offsets, bitnuc_err *err) {
+    *done = false;
+    *offsets = 0;
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    constexpr size_t kLimit = (size_t)1 << 58;
+    if (read_len >= 0xFFFFFFFFull) return fail(err, BITNUC_UNSUPPORTED, read_len);
+    const size_t period = 32 * words_for(read_len); // >= read_len, < 2^33
+    if (period && count > (kLimit - 1) / period) return fail(err, BITNUC_UNSUPPORTED, read_len);
+    if (nq > BITNUC_MAX_QUERIES) return fail(err, BITNUC_UNSUPPORTED, nq);
+    size_t m = 0;
+    if (anchored_offsets(read_len, k, pos_lo, pos_hi, &m) && m + k - 1 > BITNUC_ANCHOR_MAX_SPAN) return fail(err, BITNUC_UNSUPPORTED, m + k - 1);
+    *done = count == 0;
+    if (*done) return BITNUC_OK;
+    if (!o.query || !o.pos || !o.dist || (reinterpret_cast<uintptr_t>(o.query) & 3) || (reinterpret_cast<uintptr_t>(o.pos) & 3) || (!queries && nq) ||
+        (reinterpret_cast<uintptr_t>(queries) & 7))
+        return fail(err, BITNUC_UNSUPPORTED);
+    const int n2 = (o.query2 != nullptr) + (o.pos2 != nullptr) + (o.dist2 != nullptr);
+    if ((n2 != 0 && n2 != 3) || (reinterpret_cast<uintptr_t>(o.query2) & 3) || (reinterpret_cast<uintptr_t>(o.pos2) & 3)) return fail(err, BITNUC_UNSUPPORTED);
+    if (nq) *offsets = m;
+    return BITNUC_OK;
+}
+
+void anchored_fill_host(size_t count, const AnchorOut &o) {
+    bitnuc_host::reads_best_fill(count, o.query, o.pos, o.dist);
+    if (o.query2) bitnuc_host::reads_best_fill(count, o.query2, o.pos2, o.dist2);
+}
+
+int anchored_fill_dev(bitnuc_ctx *c, size_t count, const AnchorOut &o, bitnuc_err *err) {
+    if (int st = reads_fill_dev(c, count, o.query, o.pos, o.dist, err)) return st;
+    return o.query2 ? reads_fill_dev(c, count, o.query2, o.pos2, o.dist2, err) : BITNUC_OK;
+}
+
+// data: ASCII reads at any alignment (stride = read_len bytes) or 8-byte aligned packed words (stride = words per read); count, nq, offsets >= 1
+template <bool PACKED>
+int launch_reads_anchored(bitnuc_ctx *c, const void *data, size_t stride, size_t count, size_t k, size_t pos_lo, size_t offsets, const uint64_t *d_queries, size_t nq,
+                          const AnchorOut &o, unsigned long long *slot, bitnuc_err *err) {
+    if (int st = ensure_scratch(c, 10, nq * kAnchorEntry, err)) return st;
+    anchored_tables_kernel<<<(unsigned)nq, 64, 0, c->stream>>>(dev_queries(d_queries), (unsigned)k, reinterpret_cast<uint32_t *>(c->scratch[10]));
+    HIPCHK(hipGetLastError());
+    unsigned lg = 0;
+    while (((size_t)1 << lg) < offsets) ++lg;
+    const AnchorGeom g{(unsigned long long)stride, (unsigned)pos_lo, (unsigned)(offsets + k - 1), (unsigned)offsets, lg, (unsigned)k, (unsigned)nq,
+                       (unsigned)(((nq << lg) + 31) >> 5)};
+    const size_t want = (count + 255) / 256, cap = (size_t)c->num_cu * 4; // 64 reads per wave and trip
+    reads_anchored_kernel<PACKED><<<(unsigned)(want < cap ? want : cap), kAnchorBlock, 0, c->stream>>>(
+        static_cast<const uint8_t *>(data), (unsigned long long)count, g, c->scratch[10], o.query, o.pos, o.dist, o.query2, o.pos2, o.dist2, slot);
+    HIPCHK(hipGetLastError());
+    return BITNUC_OK;
+}
+
+// offsets x queries of a batch, saturated: what the anchored host forms' cutoff is judged on
+inline size_t anchored_work(size_t offsets, size_t count, size_t nq) { return multi_work(multi_work(offsets, count), nq); }
+
+// The anchored host forms' chunk loop: reads_host_loop2's scratch and copies; without the second triple its three arrays are neither computed nor copied.
+template <class Launch>
+int anchored_host_loop(bitnuc_ctx *c, size_t count, size_t per, const uint64_t *queries, size_t nq, const AnchorOut &o, bitnuc_err *err, Launch launch) {
+    const size_t pm = count < per ? count : per;
+    if (int st = ensure_scratch(c, 1, pm * 16, err)) return st;
+    if (int st = ensure_scratch(c, 2, nq * 8, err)) return st;
+    if (int st = ensure_scratch(c, 3, 2 * pm < 64 ? 64 : 2 * pm, err)) return st;
+    HIPCHK(hipMemcpyAsync(c->scratch[2], queries, nq * 8, hipMemcpyHostToDevice, c->stream));
+    uint32_t *d_query = reinterpret_cast<uint32_t *>(c->scratch[1]), *d_pos = d_query + pm, *d_query2 = d_pos + pm, *d_pos2 = d_query2 + pm;
+    uint8_t *d_dist = c->scratch[3], *d_dist2 = d_dist + pm;
+    const AnchorOut d = o.query2 ? AnchorOut{d_query, d_pos, d_dist, d_dist2, d_query2, d_pos2} : AnchorOut{d_query, d_pos, d_dist, nullptr, nullptr, nullptr};
+    for (size_t r0 = 0; r0 < count; r0 += per) {
+        const size_t m = count - r0 < per ? count - r0 : per;
+        if (int st = launch(r0, m, reinterpret_cast<const uint64_t *>(c->scratch[2]), d)) return st;
+        HIPCHK(hipMemcpyAsync(o.query + r0, d_query, m * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(o.pos + r0, d_pos, m * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(o.dist + r0, d_dist, m, hipMemcpyDeviceToHost, c->stream));
+        if (o.query2) {
+            HIPCHK(hipMemcpyAsync(o.query2 + r0, d_query2, m * 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(o.pos2 + r0, d_pos2, m * 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(o.dist2 + r0, d_dist2, m, hipMemcpyDeviceToHost, c->stream));
+        }
+        bitnuc_err e;
+        if (int st = drain(c, &e)) { if (err) *err = e; return st; }
+    }
+    return BITNUC_OK;
+}
+
 // ---- the best match per read of a RAGGED batch (scan_reads_batch_device.h): the fixed-length form's scratch, keys, tables, grid and finish; the
 // kernels take the run's length and the layout's two tables instead of a period.
 inline BatchTables batch_tables(const uint64_t *starts, const uint64_t *offsets, size_t count, unsigned shift) {
@@ -1737,6 +1826,102 @@ int bitnuc_reads_hdist_best2_packed(bitnuc_ctx *c, const uint64_t *words, size_t
                             [&](size_t r0, size_t m, const ReadsArgs &a, const ReadsSecond &b) {
         HIPCHK(hipMemcpyAsync(c->scratch[0], words + r0 * wpr, m * wpr * 8, hipMemcpyHostToDevice, c->stream));
         return launch_reads_best_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), read_len, m, k, a, err, &b);
+    });
+}
+
+// ---- the anchored best match and runner-up per read of a fixed-length batch -------------------------------------------------------------
+int bitnuc_reads_hdist_anchored_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                      const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist,
+                                      uint32_t *d_second_query, uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    const AnchorOut o{d_best_query, d_best_pos, d_best_dist, d_second_dist, d_second_query, d_second_pos};
+    bool done;
+    size_t offsets;
+    if (int st = check_anchored(read_len, count, k, pos_lo, pos_hi, d_queries, n_queries, o, &done, &offsets, err)) return st;
+    if (done) return BITNUC_OK;
+    DeviceGuard g(c->device);
+    if (!offsets) return anchored_fill_dev(c, count, o, err);
+    if (!d_reads) return fail(err, BITNUC_UNSUPPORTED);
+    unsigned long long *slot;
+    if (int st = take_slot(c, 0, &slot, err)) return st;
+    return launch_reads_anchored<false>(c, d_reads, read_len, count, k, pos_lo, offsets, d_queries, n_queries, o, slot, err);
+}
+
+int bitnuc_reads_hdist_anchored_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                             const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist,
+                                             uint32_t *d_second_query, uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    const AnchorOut o{d_best_query, d_best_pos, d_best_dist, d_second_dist, d_second_query, d_second_pos};
+    bool done;
+    size_t offsets;
+    if (int st = check_anchored(read_len, count, k, pos_lo, pos_hi, d_queries, n_queries, o, &done, &offsets, err)) return st;
+    if (done) return BITNUC_OK;
+    DeviceGuard g(c->device);
+    if (!offsets) return anchored_fill_dev(c, count, o, err);
+    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    return launch_reads_anchored<true>(c, d_words, words_for(read_len), count, k, pos_lo, offsets, d_queries, n_queries, o, nullptr, err);
+}
+
+int bitnuc_reads_hdist_anchored(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi, const uint64_t *queries,
+                                size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos,
+                                uint8_t *second_dist, bitnuc_err *err) {
+    clear_err(err);
+    const AnchorOut o{best_query, best_pos, best_dist, second_dist, second_query, second_pos};
+    bool done;
+    size_t offsets;
+    if (int st = check_anchored(read_len, count, k, pos_lo, pos_hi, queries, n_queries, o, &done, &offsets, err)) return st;
+    if (done) return BITNUC_OK;
+    if (!offsets) { anchored_fill_host(count, o); return BITNUC_OK; }
+    if (!reads) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, anchored_work(offsets, count, n_queries))) {
+        const long long bad = bitnuc_host::reads_hdist_anchored_small(reads, read_len, count, k, pos_lo, offsets, queries, n_queries, best_query, best_pos, best_dist,
+                                                                      second_query, second_pos, second_dist);
+        if (bad >= 0) {
+            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = reads[bad]; err->index = (uint64_t)bad; }
+            return BITNUC_INVALID_BASE;
+        }
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    const size_t per = read_len < kHostChunk ? kHostChunk / read_len : 1, pm = count < per ? count : per; // whole reads per chunk
+    if (int st = ensure_scratch(c, 0, pm * read_len + 64, err)) return st;
+    return anchored_host_loop(c, count, per, queries, n_queries, o, err, [&](size_t r0, size_t m, const uint64_t *d_queries, const AnchorOut &d) {
+        HIPCHK(hipMemcpyAsync(c->scratch[0], reads + r0 * read_len, m * read_len, hipMemcpyHostToDevice, c->stream));
+        unsigned long long *slot;
+        if (int st = take_slot(c, r0 * read_len, &slot, err)) return st;
+        return launch_reads_anchored<false>(c, c->scratch[0], read_len, m, k, pos_lo, offsets, d_queries, n_queries, d, slot, err);
+    });
+}
+
+int bitnuc_reads_hdist_anchored_packed(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                       const uint64_t *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query,
+                                       uint32_t *second_pos, uint8_t *second_dist, bitnuc_err *err) {
+    clear_err(err);
+    const AnchorOut o{best_query, best_pos, best_dist, second_dist, second_query, second_pos};
+    bool done;
+    size_t offsets;
+    if (int st = check_anchored(read_len, count, k, pos_lo, pos_hi, queries, n_queries, o, &done, &offsets, err)) return st;
+    if (done) return BITNUC_OK;
+    if (!offsets) { anchored_fill_host(count, o); return BITNUC_OK; }
+    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, anchored_work(offsets, count, n_queries))) {
+        bitnuc_host::reads_hdist_anchored_packed_small(words, read_len, count, k, pos_lo, offsets, queries, n_queries, best_query, best_pos, best_dist, second_query,
+                                                       second_pos, second_dist);
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    const size_t wpr = words_for(read_len);
+    const size_t per = wpr < kPackedChunkWords ? kPackedChunkWords / wpr : 1, pm = count < per ? count : per; // whole reads per chunk
+    if (int st = ensure_scratch(c, 0, pm * wpr * 8, err)) return st;
+    return anchored_host_loop(c, count, per, queries, n_queries, o, err, [&](size_t r0, size_t m, const uint64_t *d_queries, const AnchorOut &d) {
+        HIPCHK(hipMemcpyAsync(c->scratch[0], words + r0 * wpr, m * wpr * 8, hipMemcpyHostToDevice, c->stream));
+        return launch_reads_anchored<true>(c, c->scratch[0], wpr, m, k, pos_lo, offsets, d_queries, n_queries, d, nullptr, err);
     });
 }
 

@@ -352,6 +352,29 @@ class Context {
             return NucleotideError::from_c(e);
         return b;
     }
+    // the anchored best match and runner-up per read: reads_hdist_best2 over the offsets pos_lo <= i <= min(pos_hi, read_len - k) only (pos_hi = SIZE_MAX:
+    // to the end of the read; the span hi - pos_lo + k may not exceed BITNUC_ANCHOR_MAX_SPAN); positions are offsets in the read
+    Result<ReadsBest2> reads_hdist_anchored(Bytes reads, size_t read_len, size_t k, const std::vector<uint64_t> &queries, size_t pos_lo = 0,
+                                            size_t pos_hi = SIZE_MAX) const {
+        const size_t count = read_len ? reads.len / read_len : 0;
+        ReadsBest2 b{{std::vector<uint32_t>(count), std::vector<uint32_t>(count), std::vector<uint8_t>(count)},
+                     {std::vector<uint32_t>(count), std::vector<uint32_t>(count), std::vector<uint8_t>(count)}};
+        bitnuc_err e;
+        if (bitnuc_reads_hdist_anchored(ctx_, reads.ptr, read_len, count, k, pos_lo, pos_hi, queries.data(), queries.size(), b.best.query.data(), b.best.pos.data(),
+                                        b.best.dist.data(), b.second.query.data(), b.second.pos.data(), b.second.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
+    Result<ReadsBest2> reads_hdist_anchored_packed(Words words, size_t read_len, size_t count, size_t k, const std::vector<uint64_t> &queries, size_t pos_lo = 0,
+                                                   size_t pos_hi = SIZE_MAX) const {
+        ReadsBest2 b{{std::vector<uint32_t>(count), std::vector<uint32_t>(count), std::vector<uint8_t>(count)},
+                     {std::vector<uint32_t>(count), std::vector<uint32_t>(count), std::vector<uint8_t>(count)}};
+        bitnuc_err e;
+        if (bitnuc_reads_hdist_anchored_packed(ctx_, words.ptr, read_len, count, k, pos_lo, pos_hi, queries.data(), queries.size(), b.best.query.data(),
+                                               b.best.pos.data(), b.best.dist.data(), b.second.query.data(), b.second.pos.data(), b.second.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
     // ... of a ragged batch: read r is seq[offsets[r] .. offsets[r + 1]) (offsets: count + 1 non-decreasing entries from 0, seq.len >= offsets.back())
     Result<ReadsBest> reads_hdist_best_batch(Bytes seq, const std::vector<uint64_t> &offsets, size_t k, const std::vector<uint64_t> &queries) const {
         const size_t count = offsets.empty() ? 0 : offsets.size() - 1;

@@ -465,6 +465,60 @@ int bitnuc_reads_hdist_best2_packed(bitnuc_ctx *ctx, const uint64_t *words, size
                                     uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos,
                                     uint8_t *second_dist, bitnuc_err *err);
 
+/* ---- ANCHORED best match and runner-up per read of a fixed-length batch (a barcode, index or adapter at a known place: offset 0, 0..3 behind staggered
+ * spacers, the last k bases) -- the best2 twins above restricted to an offset range ----
+ * Windows.  The admissible windows of read r are the offsets i with pos_lo <= i <= hi_eff, hi_eff = min(pos_hi, read_len - k).  pos_hi = SIZE_MAX: to the
+ * end of the read; a 3' anchor with slack w: pos_lo = read_len - k - w, pos_hi = SIZE_MAX.  An empty range (pos_lo > hi_eff, k == 0, read_len < k,
+ * n_queries == 0) has no window: all written outputs get the fill (UINT32_MAX, UINT32_MAX, 0xFF).
+ * Span.  span = hi_eff - pos_lo + k is the number of bases of each read the call looks at.  span > BITNUC_ANCHOR_MAX_SPAN -> UNSUPPORTED (err.value =
+ * span); wider searches are what bitnuc_reads_hdist_best2* is for.
+ * The span is judged on (read_len, k, pos_lo, pos_hi) alone: a range wider than that is UNSUPPORTED with n_queries == 0 as well, although such a call
+ * would write only fills.
+ * Results.  best_*[r] is the lexicographically smallest (distance, query, offset) over all queries and the admissible windows; second_*[r] the smallest
+ * over the queries other than best_query[r], with the semantics of bitnuc_reads_hdist_best2* word for word: another window of the winner is never the
+ * runner-up, an equal duplicate query at a higher index is (at the same distance and offset), one query gives the fill in the second triple.  best_pos /
+ * second_pos are offsets in the read, not relative to pos_lo.  Deterministic.  Exactly [0, count) of each output is written; the dist arrays may have
+ * any byte offset.
+ * Second triple.  second_query, second_pos and second_dist may ALL be NULL: only the best triple is computed and written.  One or two of them NULL ->
+ * UNSUPPORTED.
+ * Identity.  With pos_lo = 0, pos_hi = SIZE_MAX and read_len <= 64 all six outputs equal bitnuc_reads_hdist_best2*'s byte for byte.
+ * Input layouts, alignment freedom, either-case ASCII and ignored pad bits: those of bitnuc_reads_hdist_best*.  Checks, in order: (1) ctx (_async forms,
+ * and the host forms above the cutoff), (2) k > 32 -> SEQUENCE_TOO_LONG, (3) read_len / count limits as bitnuc_reads_hdist_best*, (4) n_queries >
+ * BITNUC_MAX_QUERIES -> UNSUPPORTED (value = n_queries), (5) span > BITNUC_ANCHOR_MAX_SPAN -> UNSUPPORTED (value = span), (6) count == 0 -> OK, nothing
+ * written, (7) best_* NULL or best_query / best_pos not 4-byte aligned, queries NULL with n_queries > 0 or not 8-byte aligned, the second triple partly
+ * NULL or second_query / second_pos not 4-byte aligned -> UNSUPPORTED, (8) with a window: reads / words NULL (words not 8-byte aligned) -> UNSUPPORTED.
+ * Nothing is written on an argument error.
+ * Validation -- the one deliberate difference.  Only the span bytes [pos_lo, hi_eff + k) of each read are read and validated; bytes outside are never
+ * examined (as separators are not by bitnuc_encode_fixed).  The first invalid byte in buffer order among the span bytes -> INVALID_BASE with its absolute
+ * index.  The _async forms latch it once per call for bitnuc_ctx_sync(), the outputs are then unspecified; the host forms below the cutoff leave the
+ * outputs untouched.  A call with no window reads and validates nothing.  (The ASCII kernel loads aligned 4-byte words: at most 3 bytes before and after
+ * a span are touched, never examined.)
+ * The _async forms have the _dev contract (device pointers for everything, the context's stream, no host synchronisation but the growth of context
+ * scratch) and can be captured into a hipGraph after a warm-up of THIS call with the same or larger (count, n_queries).  Context scratch: 256 bytes per
+ * query; no per-read or per-(query, offset) arrays -- one kernel writes the outputs itself.  The host forms are synchronous and judge count x offsets x
+ * n_queries against the host cutoff: below it they run on the host (ctx may be NULL), above it through the context in chunks of whole reads, of the best2
+ * forms' sizes; INVALID_BASE indices stay absolute.
+ * Cost: one pass, ceil(span / 16) matrix instructions per (32 reads, 32 (query, offset) rows, offsets rounded up to a power of two); the runner-up comes
+ * with it.   Measured on 6,666,667 x 150-base reads, one MI355X
+ * (profiles/r15_reads_anchored.json), ASCII / packed with the second triple: k = 16, four offsets: 0.28 / 0.20 ms at 1 query, 0.27 / 0.19 at 8, 0.56 /
+ * 0.46 at 64, 2.8 / 2.6 at 512; one offset: 0.25 / 0.17, 0.25 / 0.17, 0.27 / 0.20, 0.90 / 0.77 ms; 0.003 - 0.84 x the time of a copy of the spans plus
+ * bitnuc_reads_hdist_best2*_async on it.
+ * Out of scope: the ragged twins, pattern (IUPAC) queries, a per-read offset table, spans above 64 bases, reverse-complement queries (callers add the
+ * reverse complements to the query list themselves). */
+#define BITNUC_ANCHOR_MAX_SPAN 64
+int bitnuc_reads_hdist_anchored_async(bitnuc_ctx *ctx, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                      const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist,
+                                      uint32_t *d_second_query, uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err);
+int bitnuc_reads_hdist_anchored_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                             const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist,
+                                             uint32_t *d_second_query, uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err);
+int bitnuc_reads_hdist_anchored(bitnuc_ctx *ctx, const uint8_t *reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi, const uint64_t *queries,
+                                size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos,
+                                uint8_t *second_dist, bitnuc_err *err);
+int bitnuc_reads_hdist_anchored_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                       const uint64_t *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query,
+                                       uint32_t *second_pos, uint8_t *second_dist, bitnuc_err *err);
+
 /* ---- best match per read of a RAGGED batch (reads after trimming, merged pairs, amplicons, long reads, contigs): the twins of the block above for
  * the layout the ragged batch entry points read and write ----
  * Layout.  Read r is seq[offsets[r] .. offsets[r+1]) -- `offsets` has count + 1 non-decreasing entries and offsets[0] == 0 (a batch cut out of a larger

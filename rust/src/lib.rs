@@ -393,6 +393,34 @@ pub fn reads_hdist_best2_packed(words: &[u64], read_len: usize, count: usize, k:
     if st == ffi::BITNUC_OK { Ok(((query, pos, dist), (query2, pos2, dist2))) } else { Err(to_err(&e)) }
 }
 
+/// The best match and the runner-up per read as `reads_hdist_best2`, over the offsets `pos_lo <= i <= min(pos_hi, read_len - k)` only (`pos_hi = None`:
+/// to the end of the read; a 3' anchor with slack `w` is `pos_lo = read_len - k - w`, `pos_hi = None`).  The span `hi - pos_lo + k` may not exceed 64
+/// bases; only the span's bytes of each read are read and validated.  Positions are offsets in the read.
+pub fn reads_hdist_anchored(reads: &[u8], read_len: usize, k: usize, pos_lo: usize, pos_hi: Option<usize>, queries: &[u64]) -> Result<ReadsBest2, NucleotideError> {
+    let count = if read_len == 0 { 0 } else { reads.len() / read_len };
+    let (mut query, mut pos, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let (mut query2, mut pos2, mut dist2) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_hdist_anchored(c, reads.as_ptr(), read_len, count, k, pos_lo, pos_hi.unwrap_or(usize::MAX), queries.as_ptr(), queries.len(), query.as_mut_ptr(),
+                                         pos.as_mut_ptr(), dist.as_mut_ptr(), query2.as_mut_ptr(), pos2.as_mut_ptr(), dist2.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(((query, pos, dist), (query2, pos2, dist2))) } else { Err(to_err(&e)) }
+}
+
+/// `reads_hdist_anchored` of the packed words `encode_fixed` writes (`ceil(read_len / 32)` words per read), without decoding them.
+pub fn reads_hdist_anchored_packed(words: &[u64], read_len: usize, count: usize, k: usize, pos_lo: usize, pos_hi: Option<usize>, queries: &[u64]) -> Result<ReadsBest2, NucleotideError> {
+    assert!(words.len() >= count * ((read_len + 31) / 32), "count reads of ceil(read_len / 32) words each");
+    let (mut query, mut pos, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let (mut query2, mut pos2, mut dist2) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_hdist_anchored_packed(c, words.as_ptr(), read_len, count, k, pos_lo, pos_hi.unwrap_or(usize::MAX), queries.as_ptr(), queries.len(),
+                                                query.as_mut_ptr(), pos.as_mut_ptr(), dist.as_mut_ptr(), query2.as_mut_ptr(), pos2.as_mut_ptr(), dist2.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(((query, pos, dist), (query2, pos2, dist2))) } else { Err(to_err(&e)) }
+}
+
 /// The best match per read of a ragged batch: read `r` is `seq[offsets[r] .. offsets[r + 1])` (`offsets` has `count + 1` non-decreasing entries
 /// from 0).  `(query, pos, dist)` as `reads_hdist_best`; an empty read or one shorter than `k` gets `u32::MAX`, `u32::MAX`, `255`.
 pub fn reads_hdist_best_batch(seq: &[u8], offsets: &[u64], k: usize, queries: &[u64]) -> Result<(Vec<u32>, Vec<u32>, Vec<u8>), NucleotideError> {
