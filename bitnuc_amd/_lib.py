@@ -79,6 +79,10 @@ SIGNATURES = {
     "bitnuc_reads_hdist_anchored_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
     "bitnuc_reads_hdist_anchored": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
     "bitnuc_reads_hdist_anchored_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_hdist_anchored_batch_async": (C.c_int, [_P, _P, _P, _SZ, _SZ, _SZ, C.c_int, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_hdist_anchored_batch_packed_async": (C.c_int, [_P, _P, _P, _P, _SZ, _SZ, _SZ, C.c_int, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_hdist_anchored_batch": (C.c_int, [_P, _P, _P, _SZ, _SZ, C.c_int, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_hdist_anchored_batch_packed": (C.c_int, [_P, _P, _P, _P, _SZ, _SZ, C.c_int, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
     "bitnuc_reads_hdist_best_batch_async": (C.c_int, [_P, _P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _ERR]),
     "bitnuc_reads_hdist_best_batch_packed_async": (C.c_int, [_P, _P, _P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _ERR]),
     "bitnuc_reads_hdist_best_batch": (C.c_int, [_P, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _P, _ERR]),

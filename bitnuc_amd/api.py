@@ -481,6 +481,44 @@ class Context:
         return self._reads_anchored(self._lib.bitnuc_reads_hdist_anchored_packed, (_ptr(w), int(read_len), int(count), int(k)), int(count), queries, pos_lo, pos_hi,
                                     second)
 
+    @staticmethod
+    def _anchor(anchor):
+        """BITNUC_ANCHOR_START / _END of "start" / "end" (or of 0 / 1)"""
+        if anchor in ("start", "end"):
+            return 0 if anchor == "start" else 1
+        if isinstance(anchor, str):
+            raise ValueError('anchor must be "start" or "end"')
+        return int(anchor)
+
+    def reads_hdist_anchored_batch(self, seq, offsets, k, queries, pos_lo=0, pos_hi=0, anchor="start", second=True):
+        """reads_hdist_anchored of a ragged batch (read r is seq[offsets[r]:offsets[r + 1]]).  anchor="start": the offsets pos_lo <= i <= min(pos_hi,
+        len_r - k); anchor="end": those with pos_lo <= len_r - k - i <= pos_hi, measured from each read's own end ("end", 0, 3: the last k bases with
+        three bases of slack).  pos_hi - pos_lo + k may not exceed 64.  (query, pos, dist, second_query, second_pos, second_dist), positions counted
+        from the read's start; a read without an admissible window: the fill; second=False: the best triple only.  Only span bytes are validated."""
+        s = _as_u8(seq)
+        off = _as_u64(offsets)
+        if off.size == 0:
+            raise ValueError("offsets must hold count + 1 entries")
+        if s.size < int(off[-1]):
+            raise ValueError("seq must hold offsets[-1] bases")
+        count = off.size - 1
+        return self._reads_anchored(self._lib.bitnuc_reads_hdist_anchored_batch, (_ptr(s), _ptr(off), count, int(k), self._anchor(anchor)), count, queries, pos_lo,
+                                    int(pos_hi), second)
+
+    def reads_hdist_anchored_batch_packed(self, words, word_offsets, offsets, k, queries, pos_lo=0, pos_hi=0, anchor="start", second=True):
+        """reads_hdist_anchored_batch of the packed words encode_batch writes (read r's ceil(len_r / 32) words start at words[word_offsets[r]]), without
+        decoding them."""
+        w = _as_u64(words)
+        woff = _as_u64(word_offsets)
+        off = _as_u64(offsets)
+        if off.size == 0 or woff.size != off.size:
+            raise ValueError("offsets and word_offsets must hold count + 1 entries each")
+        if w.size < int(woff[-1]):
+            raise ValueError("words must hold word_offsets[-1] words")
+        count = off.size - 1
+        return self._reads_anchored(self._lib.bitnuc_reads_hdist_anchored_batch_packed, (_ptr(w), _ptr(woff), _ptr(off), count, int(k), self._anchor(anchor)), count,
+                                    queries, pos_lo, int(pos_hi), second)
+
     def reads_hdist_best_batch(self, seq, offsets, k, queries):
         """The best match per read of a ragged batch: read r is seq[offsets[r]:offsets[r + 1]] (`offsets`: count + 1 non-decreasing entries from 0).
         (query, pos, dist) as reads_hdist_best; an empty read, or one shorter than k: 2^32 - 1, 2^32 - 1, 255."""
@@ -891,6 +929,22 @@ class Context:
         self._call_dev(self._lib.bitnuc_reads_hdist_anchored_packed_async, _dev_ptr(d_words), int(read_len), int(count), int(k), int(pos_lo),
                        _SIZE_MAX if pos_hi is None else int(pos_hi), _dev_ptr(d_queries), int(n_queries), _dev_ptr(d_best_query), _dev_ptr(d_best_pos),
                        _dev_ptr(d_best_dist), *(_dev_ptr(a) for a in (d_second_query, d_second_pos, d_second_dist)))
+
+    def reads_hdist_anchored_batch_async(self, d_seq, d_offsets, count, total_bases, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist,
+                                         d_second_query=None, d_second_pos=None, d_second_dist=None, pos_lo=0, pos_hi=0, anchor="start"):
+        """reads_hdist_anchored_async of a ragged batch in device memory: read r is d_seq[d_offsets[r] .. d_offsets[r + 1]) (u64, count + 1 entries from 0,
+        total_bases = the last; trusted, read on the device).  anchor "start" / "end": the range pos_lo .. pos_hi counts offsets from the read's start, or
+        bases behind the window from its end; pos_hi - pos_lo + k <= 64.  The three d_second_* all None: the best triple only."""
+        self._call_dev(self._lib.bitnuc_reads_hdist_anchored_batch_async, _dev_ptr(d_seq), _dev_ptr(d_offsets), int(count), int(total_bases), int(k),
+                       self._anchor(anchor), int(pos_lo), int(pos_hi), _dev_ptr(d_queries), int(n_queries), _dev_ptr(d_best_query), _dev_ptr(d_best_pos),
+                       _dev_ptr(d_best_dist), *(_dev_ptr(a) for a in (d_second_query, d_second_pos, d_second_dist)))
+
+    def reads_hdist_anchored_batch_packed_async(self, d_words, d_word_offsets, d_offsets, count, total_words, k, d_queries, n_queries, d_best_query, d_best_pos,
+                                                d_best_dist, d_second_query=None, d_second_pos=None, d_second_dist=None, pos_lo=0, pos_hi=0, anchor="start"):
+        """reads_hdist_anchored_batch_async on the packed words encode_batch_dev writes (8-byte aligned; both tables u64 in device memory, trusted)."""
+        self._call_dev(self._lib.bitnuc_reads_hdist_anchored_batch_packed_async, _dev_ptr(d_words), _dev_ptr(d_word_offsets), _dev_ptr(d_offsets), int(count),
+                       int(total_words), int(k), self._anchor(anchor), int(pos_lo), int(pos_hi), _dev_ptr(d_queries), int(n_queries), _dev_ptr(d_best_query),
+                       _dev_ptr(d_best_pos), _dev_ptr(d_best_dist), *(_dev_ptr(a) for a in (d_second_query, d_second_pos, d_second_dist)))
 
     def reads_hdist_best_batch_async(self, d_seq, d_offsets, count, total_bases, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist):
         """The best match per read of a ragged batch of ASCII reads in device memory: read r is d_seq[d_offsets[r] .. d_offsets[r + 1]) (u64, count + 1

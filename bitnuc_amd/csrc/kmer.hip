@@ -22,6 +22,7 @@
 #include "reads_best_host.h"
 #include "reads_best2_host.h"
 #include "reads_anchored_host.h"
+#include "reads_anchored_batch_host.h"
 #include "reads_batch_host.h"
 #include "scan_hist_host.h"
 #include "pattern_host.h"
@@ -941,7 +942,7 @@ int launch_reads_anchored(bitnuc_ctx *c, const void *data, size_t stride, size_t
     const AnchorGeom g{(unsigned long long)stride, (unsigned)pos_lo, (unsigned)(offsets + k - 1), (unsigned)offsets, lg, (unsigned)k, (unsigned)nq,
                        (unsigned)(((nq << lg) + 31) >> 5)};
     const size_t want = (count + 255) / 256, cap = (size_t)c->num_cu * 4; // 64 reads per wave and trip
-    reads_anchored_kernel<PACKED><<<(unsigned)(want < cap ? want : cap), kAnchorBlock, 0, c->stream>>>(
+    reads_anchored_kernel<PACKED, AnchorGeom><<<(unsigned)(want < cap ? want : cap), kAnchorBlock, 0, c->stream>>>(
         static_cast<const uint8_t *>(data), (unsigned long long)count, g, c->scratch[10], o.query, o.pos, o.dist, o.query2, o.pos2, o.dist2, slot);
     HIPCHK(hipGetLastError());
     return BITNUC_OK;
@@ -1053,6 +1054,87 @@ int reads_batch_host_loop(bitnuc_ctx *c, size_t count, const uint64_t *queries, 
         HIPCHK(hipMemcpyAsync(query + r0, d_query, m * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(pos + r0, d_pos, m * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(dist + r0, c->scratch[3], m, hipMemcpyDeviceToHost, c->stream));
+        bitnuc_err e;
+        if (int st = drain(c, &e)) { if (err) *err = e; return st; }
+        r0 += m;
+    }
+    return BITNUC_OK;
+}
+
+// ---- the ANCHORED best match and runner-up per read of a RAGGED batch: reads_anchored_kernel under its other layout policy (AnchorBatchGeom), the
+// fixed form's tables and scratch (256 bytes per query), the ragged forms' tables and chunk cut.
+// the calls' checks 2 - 7 (after ctx): `total` is what check 3 bounds (the host forms pass 0: their tables' validation bounds the totals).  *done:
+// nothing to do (count == 0); *offsets: pos_hi - pos_lo + 1, 0 for an empty range
+int check_anchored_batch(uint64_t total, uint64_t total_value, size_t count, size_t k, int anchor, size_t pos_lo, size_t pos_hi, const void *queries, size_t nq,
+                         const AnchorOut &o, const void *tab1, const void *tab2, bool two_tables, bool *done, size_t *offsets, bitnuc_err *err) {
+    *done = false;
+    *offsets = 0;
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    if (total >= ((uint64_t)1 << 58)) return fail(err, BITNUC_UNSUPPORTED, total_value);
+    if (nq > BITNUC_MAX_QUERIES) return fail(err, BITNUC_UNSUPPORTED, nq);
+    if (anchor != BITNUC_ANCHOR_START && anchor != BITNUC_ANCHOR_END) return fail(err, BITNUC_UNSUPPORTED, (uint64_t)(unsigned)anchor);
+    size_t span;
+    anchored_batch_span(k, pos_lo, pos_hi, offsets, &span);
+    if (span > BITNUC_ANCHOR_MAX_SPAN) return fail(err, BITNUC_UNSUPPORTED, span);
+    *done = count == 0;
+    if (*done) return BITNUC_OK;
+    if (!o.query || !o.pos || !o.dist || (reinterpret_cast<uintptr_t>(o.query) & 3) || (reinterpret_cast<uintptr_t>(o.pos) & 3) || (!queries && nq) ||
+        (reinterpret_cast<uintptr_t>(queries) & 7))
+        return fail(err, BITNUC_UNSUPPORTED);
+    const int n2 = (o.query2 != nullptr) + (o.pos2 != nullptr) + (o.dist2 != nullptr);
+    if ((n2 != 0 && n2 != 3) || (reinterpret_cast<uintptr_t>(o.query2) & 3) || (reinterpret_cast<uintptr_t>(o.pos2) & 3)) return fail(err, BITNUC_UNSUPPORTED);
+    if (!tab1 || (reinterpret_cast<uintptr_t>(tab1) & 7) || (two_tables && (!tab2 || (reinterpret_cast<uintptr_t>(tab2) & 7)))) return fail(err, BITNUC_UNSUPPORTED);
+    return BITNUC_OK;
+}
+
+// check 9: no read of a batch of `total` bases can hold a window (a window at offset pos_lo, or pos_lo bases in front of the end, needs k + pos_lo bases;
+// reads are below 2^32 - 1 bases)
+inline bool anchored_batch_no_window(uint64_t total, size_t k, size_t nq, size_t offsets, size_t pos_lo) {
+    return k == 0 || nq == 0 || offsets == 0 || total < k || total - k < pos_lo || pos_lo >= 0xFFFFFFFFull;
+}
+
+// data: ASCII at any alignment, read r at bytes d_offsets[r] .. d_offsets[r + 1], or 8-byte aligned words, read r from word d_starts[r]; the tables in
+// device memory; count, nq >= 1, 1 <= offsets, offsets + k - 1 <= 64, pos_lo < 2^32 - 1
+template <bool PACKED>
+int launch_reads_anchored_batch(bitnuc_ctx *c, const void *data, const uint64_t *d_starts, const uint64_t *d_offsets, size_t count, size_t k, int anchor, size_t pos_lo,
+                                size_t offsets, const uint64_t *d_queries, size_t nq, const AnchorOut &o, unsigned long long *slot, bitnuc_err *err) {
+    if (int st = ensure_scratch(c, 10, nq * kAnchorEntry, err)) return st;
+    anchored_tables_kernel<<<(unsigned)nq, 64, 0, c->stream>>>(dev_queries(d_queries), (unsigned)k, reinterpret_cast<uint32_t *>(c->scratch[10]));
+    HIPCHK(hipGetLastError());
+    unsigned lg = 0;
+    while (((size_t)1 << lg) < offsets) ++lg;
+    const AnchorBatchGeom g{reinterpret_cast<const unsigned long long *>(d_offsets), reinterpret_cast<const unsigned long long *>(d_starts), (unsigned)pos_lo,
+                            (unsigned)(anchor == BITNUC_ANCHOR_END), (unsigned)(offsets + k - 1), (unsigned)offsets, lg, (unsigned)k, (unsigned)nq,
+                            (unsigned)(((nq << lg) + 31) >> 5)};
+    const size_t want = (count + 255) / 256, cap = (size_t)c->num_cu * 4; // 64 reads per wave and trip
+    reads_anchored_kernel<PACKED, AnchorBatchGeom><<<(unsigned)(want < cap ? want : cap), kAnchorBlock, 0, c->stream>>>(
+        static_cast<const uint8_t *>(data), (unsigned long long)count, g, c->scratch[10], o.query, o.pos, o.dist, o.query2, o.pos2, o.dist2, slot);
+    HIPCHK(hipGetLastError());
+    return BITNUC_OK;
+}
+
+// The ragged anchored host forms' chunk loop: reads_batch_host_loop's chunks (chunk_end(r0) is the read after the chunk's last) with anchored_host_loop's
+// outputs: six arrays, or three without the second triple.  `launch(r0, m, d_queries, d)` runs the reads [r0, r0 + m) into d's device arrays.
+template <class ChunkEnd, class Launch>
+int anchored_batch_host_loop(bitnuc_ctx *c, size_t count, const uint64_t *queries, size_t nq, const AnchorOut &o, bitnuc_err *err, ChunkEnd chunk_end, Launch launch) {
+    if (int st = ensure_scratch(c, 2, nq * 8, err)) return st;
+    HIPCHK(hipMemcpyAsync(c->scratch[2], queries, nq * 8, hipMemcpyHostToDevice, c->stream));
+    for (size_t r0 = 0; r0 < count;) {
+        const size_t m = chunk_end(r0) - r0;
+        if (int st = ensure_scratch(c, 1, m * 16, err)) return st;
+        if (int st = ensure_scratch(c, 3, 2 * m < 64 ? 64 : 2 * m, err)) return st;
+        uint32_t *d_query = reinterpret_cast<uint32_t *>(c->scratch[1]), *d_pos = d_query + m, *d_query2 = d_pos + m, *d_pos2 = d_query2 + m;
+        uint8_t *d_dist = c->scratch[3], *d_dist2 = d_dist + m;
+        const AnchorOut d = o.query2 ? AnchorOut{d_query, d_pos, d_dist, d_dist2, d_query2, d_pos2} : AnchorOut{d_query, d_pos, d_dist, nullptr, nullptr, nullptr};
+        if (int st = launch(r0, m, reinterpret_cast<const uint64_t *>(c->scratch[2]), d)) return st;
+        HIPCHK(hipMemcpyAsync(o.query + r0, d_query, m * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(o.pos + r0, d_pos, m * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(o.dist + r0, d_dist, m, hipMemcpyDeviceToHost, c->stream));
+        if (o.query2) {
+            HIPCHK(hipMemcpyAsync(o.query2 + r0, d_query2, m * 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(o.pos2 + r0, d_pos2, m * 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(o.dist2 + r0, d_dist2, m, hipMemcpyDeviceToHost, c->stream));
+        }
         bitnuc_err e;
         if (int st = drain(c, &e)) { if (err) *err = e; return st; }
         r0 += m;
@@ -1923,6 +2005,130 @@ int bitnuc_reads_hdist_anchored_packed(bitnuc_ctx *c, const uint64_t *words, siz
         HIPCHK(hipMemcpyAsync(c->scratch[0], words + r0 * wpr, m * wpr * 8, hipMemcpyHostToDevice, c->stream));
         return launch_reads_anchored<true>(c, c->scratch[0], wpr, m, k, pos_lo, offsets, d_queries, n_queries, d, nullptr, err);
     });
+}
+
+// ---- the anchored best match and runner-up per read of a ragged batch ----------------------------------------------------------------
+int bitnuc_reads_hdist_anchored_batch_async(bitnuc_ctx *c, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k, int anchor,
+                                            size_t pos_lo, size_t pos_hi, const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos,
+                                            uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    const AnchorOut o{d_best_query, d_best_pos, d_best_dist, d_second_dist, d_second_query, d_second_pos};
+    bool done;
+    size_t offsets;
+    if (int st = check_anchored_batch(total_bases, total_bases, count, k, anchor, pos_lo, pos_hi, d_queries, n_queries, o, d_offsets, nullptr, false, &done, &offsets, err))
+        return st;
+    if (done) return BITNUC_OK;
+    DeviceGuard g(c->device);
+    if (anchored_batch_no_window(total_bases, k, n_queries, offsets, pos_lo)) return anchored_fill_dev(c, count, o, err);
+    if (!d_seq) return fail(err, BITNUC_UNSUPPORTED);
+    unsigned long long *slot;
+    if (int st = take_slot(c, 0, &slot, err)) return st;
+    return launch_reads_anchored_batch<false>(c, d_seq, nullptr, d_offsets, count, k, anchor, pos_lo, offsets, d_queries, n_queries, o, slot, err);
+}
+
+int bitnuc_reads_hdist_anchored_batch_packed_async(bitnuc_ctx *c, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
+                                                   size_t total_words, size_t k, int anchor, size_t pos_lo, size_t pos_hi, const uint64_t *d_queries, size_t n_queries,
+                                                   uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, uint32_t *d_second_query,
+                                                   uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    const AnchorOut o{d_best_query, d_best_pos, d_best_dist, d_second_dist, d_second_query, d_second_pos};
+    bool done;
+    size_t offsets;
+    const uint64_t as_bases = total_words >= ((uint64_t)1 << 53) ? ~(uint64_t)0 : 32 * (uint64_t)total_words;
+    if (int st = check_anchored_batch(as_bases, total_words, count, k, anchor, pos_lo, pos_hi, d_queries, n_queries, o, d_word_offsets, d_offsets, true, &done, &offsets,
+                                      err))
+        return st;
+    if (done) return BITNUC_OK;
+    DeviceGuard g(c->device);
+    if (anchored_batch_no_window(as_bases, k, n_queries, offsets, pos_lo)) return anchored_fill_dev(c, count, o, err);
+    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    return launch_reads_anchored_batch<true>(c, d_words, d_word_offsets, d_offsets, count, k, anchor, pos_lo, offsets, d_queries, n_queries, o, nullptr, err);
+}
+
+int bitnuc_reads_hdist_anchored_batch(bitnuc_ctx *c, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, int anchor, size_t pos_lo, size_t pos_hi,
+                                      const uint64_t *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query,
+                                      uint32_t *second_pos, uint8_t *second_dist, bitnuc_err *err) {
+    clear_err(err);
+    const AnchorOut o{best_query, best_pos, best_dist, second_dist, second_query, second_pos};
+    bool done;
+    size_t width; // the range's offsets
+    if (int st = check_anchored_batch(0, 0, count, k, anchor, pos_lo, pos_hi, queries, n_queries, o, offsets, nullptr, false, &done, &width, err)) return st;
+    if (done) return BITNUC_OK;
+    const BatchFault f = batch_check_tables(offsets, nullptr, count);
+    if (f.kind) return fail_batch_tables(f, err);
+    if (anchored_batch_no_window(offsets[count], k, n_queries, width, pos_lo)) { anchored_fill_host(count, o); return BITNUC_OK; }
+    if (!seq) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, anchored_work(width, count, n_queries))) {
+        const long long bad = bitnuc_host::reads_hdist_anchored_batch_small(seq, offsets, count, k, anchor, pos_lo, pos_hi, queries, n_queries, best_query, best_pos,
+                                                                            best_dist, second_query, second_pos, second_dist);
+        if (bad >= 0) {
+            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = seq[bad]; err->index = (uint64_t)bad; }
+            return BITNUC_INVALID_BASE;
+        }
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    std::vector<uint64_t> tab; // the chunk's rebased table
+    return anchored_batch_host_loop(
+        c, count, queries, n_queries, o, err,
+        [&](size_t r0) { return batch_chunk_end(r0, count, kHostChunk, [&](size_t a, size_t b) { return offsets[b] - offsets[a]; }); },
+        [&](size_t r0, size_t m, const uint64_t *d_queries, const AnchorOut &d) {
+            const size_t b0 = (size_t)offsets[r0], bytes = (size_t)offsets[r0 + m] - b0;
+            if (anchored_batch_no_window(bytes, k, n_queries, width, pos_lo)) return anchored_fill_dev(c, m, d, err); // nothing to launch, nothing validated
+            if (int st = ensure_scratch(c, 0, bytes + 64, err)) return st;
+            if (int st = ensure_scratch(c, 4, (m + 1) * 8, err)) return st;
+            tab.resize(m + 1);
+            for (size_t i = 0; i <= m; ++i) tab[i] = offsets[r0 + i] - b0;
+            HIPCHK(hipMemcpyAsync(c->scratch[0], seq + b0, bytes, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(c->scratch[4], tab.data(), (m + 1) * 8, hipMemcpyHostToDevice, c->stream));
+            unsigned long long *slot;
+            if (int st = take_slot(c, b0, &slot, err)) return st;
+            return launch_reads_anchored_batch<false>(c, c->scratch[0], nullptr, reinterpret_cast<const uint64_t *>(c->scratch[4]), m, k, anchor, pos_lo, width, d_queries,
+                                                      n_queries, d, slot, err);
+        });
+}
+
+int bitnuc_reads_hdist_anchored_batch_packed(bitnuc_ctx *c, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
+                                             int anchor, size_t pos_lo, size_t pos_hi, const uint64_t *queries, size_t n_queries, uint32_t *best_query,
+                                             uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos, uint8_t *second_dist, bitnuc_err *err) {
+    clear_err(err);
+    const AnchorOut o{best_query, best_pos, best_dist, second_dist, second_query, second_pos};
+    bool done;
+    size_t width;
+    if (int st = check_anchored_batch(0, 0, count, k, anchor, pos_lo, pos_hi, queries, n_queries, o, word_offsets, offsets, true, &done, &width, err)) return st;
+    if (done) return BITNUC_OK;
+    const BatchFault f = batch_check_tables(offsets, word_offsets, count);
+    if (f.kind) return fail_batch_tables(f, err);
+    if (anchored_batch_no_window(offsets[count], k, n_queries, width, pos_lo)) { anchored_fill_host(count, o); return BITNUC_OK; }
+    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, anchored_work(width, count, n_queries))) {
+        bitnuc_host::reads_hdist_anchored_batch_packed_small(words, word_offsets, offsets, count, k, anchor, pos_lo, pos_hi, queries, n_queries, best_query, best_pos,
+                                                             best_dist, second_query, second_pos, second_dist);
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    std::vector<uint64_t> tab; // the chunk's two rebased tables: word_offsets, then offsets
+    return anchored_batch_host_loop(
+        c, count, queries, n_queries, o, err,
+        [&](size_t r0) { return batch_chunk_end(r0, count, kPackedChunkWords, [&](size_t a, size_t b) { return word_offsets[b] - word_offsets[a]; }); },
+        [&](size_t r0, size_t m, const uint64_t *d_queries, const AnchorOut &d) {
+            const size_t w0 = (size_t)word_offsets[r0], nw = (size_t)word_offsets[r0 + m] - w0;
+            if (nw == 0) return anchored_fill_dev(c, m, d, err);
+            if (int st = ensure_scratch(c, 0, nw * 8, err)) return st;
+            if (int st = ensure_scratch(c, 4, 2 * (m + 1) * 8, err)) return st;
+            tab.resize(2 * (m + 1));
+            for (size_t i = 0; i <= m; ++i) tab[i] = word_offsets[r0 + i] - w0, tab[m + 1 + i] = offsets[r0 + i] - offsets[r0];
+            HIPCHK(hipMemcpyAsync(c->scratch[0], words + w0, nw * 8, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(c->scratch[4], tab.data(), 2 * (m + 1) * 8, hipMemcpyHostToDevice, c->stream));
+            const uint64_t *d_tab = reinterpret_cast<const uint64_t *>(c->scratch[4]);
+            return launch_reads_anchored_batch<true>(c, c->scratch[0], d_tab, d_tab + m + 1, m, k, anchor, pos_lo, width, d_queries, n_queries, d, nullptr, err);
+        });
 }
 
 // ---- the best match per read of a ragged batch ------------------------------------------------------------------------------------

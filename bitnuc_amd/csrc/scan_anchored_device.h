@@ -27,6 +27,16 @@
 // MFMA of four at spans of 49 .. 63 and one of two at 17 .. 21, at the price of a second table and operand form; not shipped.
 // Invalid ASCII bytes: ascii_residue's LUT on every piece, restricted to the span's bytes; a lane that sees one latches its first (atomicMin: the first
 // in buffer order wins).
+//
+// Two layouts, one kernel (the template parameter G, everything that differs under `if constexpr`).  Fixed (AnchorGeom): reads at a stride, one range for
+// all of them -- the text above.  RAGGED (AnchorBatchGeom, bitnuc_reads_hdist_anchored_batch*): reads behind an offsets table, the range counted from each
+// read's start or from its end.  A lane already is one read, so the layout is per-lane data: the lane loads its read's two table entries (coalesced) and
+// derives a_r, the offset of row 0, and n_r <= offsets, its number of admissible offsets (anchored_lane); its pieces are cut at n_r + k - 1 bytes, so
+// nothing behind its own span is loaded or validated; row s is offset a_r + s.  The A operand is shared by the tile's 32 reads, so a row that one read
+// does not admit is live for its neighbours: admissibility is per (row, column) and sits in the accumulators' START VALUES (a lane holds one column),
+// computed once per block and group for the tiles whose queries all exist -- the tile loop is the fixed layout's, instruction for instruction apart from
+// constants.  A live inadmissible row collects matches, so its start value must stay out of reach of 32 of them: the ragged layout widens the distance
+// field to seven bits (AnchorField).  The fixed instantiations' instructions are those of the kernel before it had a second layout.
 #pragma once
 #include "device_prims.h"
 #include "scan_mfma_device.h"   // i32x8, f32x16, onehot8, dword_residue, trip_invalid
@@ -38,10 +48,30 @@ constexpr int kAnchorBlock = 256;          // four waves, nothing shared between
 constexpr int kAnchorGroups = 2;           // groups of 32 reads per wave and tile walk
 constexpr unsigned kAnchorEntry = 256;     // bytes of a query's table entry: 128 bases x 16 bits
 constexpr uint32_t kAnchorBias = 0x4B000000u; // 2^23
-constexpr int kAnchorScale = 127 + 17;     // A's E8M0 scale: a match subtracts 1 << 17
 
 // stride: bytes (ASCII) or words (packed) per read; lg: log2 of the rows per query; ntiles: ceil(nq << lg / 32)
-struct AnchorGeom { unsigned long long stride; unsigned pos_lo, span, offsets, lg, k, nq, ntiles; };
+struct AnchorGeom { unsigned long long stride; unsigned pos_lo, span, offsets, lg, k, nq, ntiles; static constexpr bool kRagged = false; };
+
+// The RAGGED layout (bitnuc_reads_hdist_anchored_batch*), the kernel's other layout policy: read r is tab[r] .. tab[r + 1] (bytes of ASCII, bases of packed
+// words that start at word wtab[r]); the range is pos_lo .. pos_lo + offsets - 1, counted from the read's start or (end != 0) in bases BEHIND the window.
+// span = offsets + k - 1 is the widest span; every read has its own first span base a_r and number of admissible offsets n_r <= offsets (AnchorLane).
+struct AnchorBatchGeom {
+    const unsigned long long *tab, *wtab;
+    unsigned pos_lo, end, span, offsets, lg, k, nq, ntiles;
+    static constexpr bool kRagged = true;
+};
+
+// The distance field of an accumulator's bit pattern.  Fixed layout: six bits at bit 17, an inadmissible row starts at 63 and has an all-zero A, so it
+// stays there.  Ragged: a row that is inadmissible for one read of the tile is admissible for its neighbours and has a LIVE A -- up to 32 matches would
+// take 63 down to 31, a real distance --, so the field is seven bits at bit 16 (bits 6 .. 16 were unused) and such a row starts at 127: it ends at 95 or
+// above, no real distance (<= 32) and behind every real row in the unsigned minimum.  Costs nothing in the tile loop: only constants differ.
+template <bool RAGGED> struct AnchorField {
+    static constexpr unsigned kShift = RAGGED ? 16u : 17u;        // a match subtracts 1 << kShift
+    static constexpr unsigned kNone = RAGGED ? 127u : 63u;        // where an inadmissible row starts
+    static constexpr unsigned kKeyShift = RAGGED ? 25u : 26u;     // the field's place in a global key
+    static constexpr uint32_t kKeyMask = ~0u << kKeyShift;
+    static constexpr int kScale = 127 + (int)kShift;              // A's E8M0 scale
+};
 
 // entry i of query q: base i - 64 of the query as -1.0 in its channel's nibble (A, C, G, T from bit 0), zero outside [0, k)
 __global__ void __launch_bounds__(64) anchored_tables_kernel(const unsigned long long *__restrict__ queries, unsigned k, uint32_t *__restrict__ tabs) {
@@ -99,8 +129,8 @@ __device__ __forceinline__ void anchored_piece_packed(const uint64_t *__restrict
 
 __device__ __forceinline__ uint32_t anchored_bits(float x) { return __float_as_uint(x); } // (on a copy: pack_distances' note)
 
-// a tile-local pattern -> dist << 26 | tilebase + local; all-ones (and every row that starts at 63) -> dist field 63 = none
-__device__ __forceinline__ uint32_t anchored_global(uint32_t u, uint32_t tilebase) { return ((u << 9) & 0xFC000000u) | (tilebase + (u & 63u)); }
+// a tile-local pattern -> dist << 26 (ragged: 25) | tilebase + local; all-ones (and every row that starts at 63 / 127) -> a dist field above 32 = none
+template <class F> __device__ __forceinline__ uint32_t anchored_global(uint32_t u, uint32_t tilebase) { return ((u << 9) & F::kKeyMask) | (tilebase + (u & 63u)); }
 
 // (b1, b2) <- the two smallest of (b1, b2, g1, g2); b1 <= b2 and g1 <= g2 are keys of distinct queries
 __device__ __forceinline__ void anchored_merge(uint32_t &b1, uint32_t &b2, uint32_t g1, uint32_t g2) {
@@ -117,7 +147,7 @@ __device__ __forceinline__ void anchored_halves(uint32_t x, uint32_t &low, uint3
 }
 
 // P <= 16 rows per query: 16 / P queries in the lane's registers
-template <int P>
+template <int P, class F>
 __device__ __forceinline__ void anchored_reduce(const f32x16 &acc, uint32_t tilebase, uint32_t &b1, uint32_t &b2) {
     uint32_t m1 = ~0u, m2 = ~0u;
 #pragma unroll
@@ -132,7 +162,7 @@ __device__ __forceinline__ void anchored_reduce(const f32x16 &acc, uint32_t tile
         m2 = min(m2, max(m1, m));
         m1 = min(m1, m);
     }
-    anchored_merge(b1, b2, anchored_global(m1, tilebase), anchored_global(m2, tilebase));
+    anchored_merge(b1, b2, anchored_global<F>(m1, tilebase), anchored_global<F>(m2, tilebase));
 }
 
 __device__ __forceinline__ uint32_t anchored_min16(const f32x16 &acc) {
@@ -146,34 +176,63 @@ __device__ __forceinline__ uint32_t anchored_min16(const f32x16 &acc) {
     return m;
 }
 
-// where the lane's accumulators of tile T start: register r is slot 16 h + r, global row 32 T + slot
-__device__ __forceinline__ f32x16 anchored_start(unsigned T, unsigned hh, const AnchorGeom &g, unsigned nq) {
+// where the lane's accumulators of tile T start: register r is slot 16 h + r, global row 32 T + slot; `offsets`: the admissible offsets of the lane's
+// column (the fixed layout's g.offsets, the ragged layout's n_r of the lane's read: admissibility is per (row, column), and a lane holds one column)
+template <class F, class G>
+__device__ __forceinline__ f32x16 anchored_start(unsigned T, unsigned hh, const G &g, unsigned nq, unsigned offsets) {
     f32x16 c;
     const unsigned pm = (1u << g.lg) - 1u;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const unsigned row = 32u * T + 16u * hh + (unsigned)r;
         const unsigned s = row & pm, local = row & (g.lg == 6 ? 63u : 31u);
-        const bool valid = (row >> g.lg) < nq && s < g.offsets;
-        c[r] = __uint_as_float(kAnchorBias | ((valid ? g.k : 63u) << 17) | local);
+        bool valid;
+        if constexpr (G::kRagged) valid = (row >> g.lg) < nq && s < offsets;
+        else valid = (row >> g.lg) < nq && s < g.offsets; // (offsets == g.offsets: spelled as before the ragged layout, the generated code is the same)
+        c[r] = __uint_as_float(kAnchorBias | ((valid ? g.k : F::kNone) << F::kShift) | local);
     }
     return c;
 }
 
-__device__ __forceinline__ void anchored_store(uint32_t key, const AnchorGeom &g, unsigned long long r, uint32_t *__restrict__ query, uint32_t *__restrict__ pos,
-                                               uint8_t *__restrict__ dist) {
-    const uint32_t d = key >> 26, row = key & 0x03FFFFFFu;
+// first: the offset of row 0 (the fixed layout's pos_lo, the ragged layout's a_r)
+template <class F>
+__device__ __forceinline__ void anchored_store(uint32_t key, unsigned lg, unsigned first, unsigned long long r, uint32_t *__restrict__ query,
+                                               uint32_t *__restrict__ pos, uint8_t *__restrict__ dist) {
+    const uint32_t d = key >> F::kKeyShift, row = key & ~F::kKeyMask;
     const bool none = d > 32u;
-    query[r] = none ? 0xFFFFFFFFu : row >> g.lg;
-    pos[r] = none ? 0xFFFFFFFFu : g.pos_lo + (row & ((1u << g.lg) - 1u));
+    query[r] = none ? 0xFFFFFFFFu : row >> lg;
+    pos[r] = none ? 0xFFFFFFFFu : first + (row & ((1u << lg) - 1u));
     dist[r] = none ? (uint8_t)0xFF : (uint8_t)d;
 }
 
-// data: the reads (ASCII bytes at any alignment, or 8-byte aligned packed words); count >= 1, 1 <= k <= 32, nq >= 1, 1 <= offsets, span = offsets + k - 1
-// <= 64.  sq == nullptr: the best triple only.  A bounded grid; a wave walks blocks of 64 reads.
+// a lane's read in the ragged layout: base = where the read starts in data (byte, or word when packed), a = its first span base, n = its admissible
+// offsets (0 .. g.offsets).  room = last_r - pos_lo: START admits i = pos_lo .. pos_lo + min(room, offsets - 1), END admits e = pos_lo .. the same, that
+// is i = room - min(room, offsets - 1) .. room.  Two coalesced 8-byte loads per lane (three when packed); reads are below 2^32 - 1 bases.  The entries are
+// loaded one block ahead (AnchorEntries: only the loads, no use), so that the dependent chain table -> span bytes does not start at the top of a block.
+struct AnchorLane { unsigned long long base; unsigned a, n; };
+struct AnchorEntries { unsigned long long o0, o1, w; };
 template <bool PACKED>
+__device__ __forceinline__ AnchorEntries anchored_entries(const AnchorBatchGeom &g, unsigned long long r) {
+    return AnchorEntries{g.tab[r], g.tab[r + 1], PACKED ? g.wtab[r] : 0ull};
+}
+template <bool PACKED>
+__device__ __forceinline__ AnchorLane anchored_lane(const AnchorBatchGeom &g, const AnchorEntries &e) {
+    const long long room = (long long)(e.o1 - e.o0) - (long long)g.k - (long long)g.pos_lo;
+    AnchorLane L{PACKED ? e.w : e.o0, g.pos_lo, 0u};
+    if (room >= 0) {
+        const unsigned more = room < (long long)(g.offsets - 1u) ? (unsigned)room : g.offsets - 1u;
+        L.n = more + 1u;
+        if (g.end) L.a = (unsigned)(room - (long long)more);
+    }
+    return L;
+}
+
+// data: the reads (ASCII bytes at any alignment, or 8-byte aligned packed words); count >= 1, 1 <= k <= 32, nq >= 1, 1 <= offsets, span = offsets + k - 1
+// <= 64.  sq == nullptr: the best triple only.  A bounded grid; a wave walks blocks of 64 reads.  G: the layout policy (AnchorGeom: a fixed stride, one
+// range for all reads; AnchorBatchGeom: tables, a range per read); everything that differs is under `if constexpr`, the tile loop has no branch on it.
+template <bool PACKED, class G>
 __global__ void __launch_bounds__(kAnchorBlock)
-reads_anchored_kernel(const uint8_t *__restrict__ data, unsigned long long count, const AnchorGeom g, const uint8_t *__restrict__ tabs, uint32_t *__restrict__ bq,
+reads_anchored_kernel(const uint8_t *__restrict__ data, unsigned long long count, const G g, const uint8_t *__restrict__ tabs, uint32_t *__restrict__ bq,
                       uint32_t *__restrict__ bp, uint8_t *__restrict__ bd, uint32_t *__restrict__ sq, uint32_t *__restrict__ sp, uint8_t *__restrict__ sd,
                       unsigned long long *__restrict__ slot) {
     const unsigned lane = threadIdx.x & 63, n = lane & 31u, hh = lane >> 5;
@@ -182,24 +241,55 @@ reads_anchored_kernel(const uint8_t *__restrict__ data, unsigned long long count
     const unsigned long long nblocks = (count + 63) >> 6;
     const unsigned nsteps = (g.span + 15u) >> 4; // wave-uniform
     const unsigned slot_row = 16u * ((n >> 2) & 1u) + (n & 3u) + 4u * (n >> 3); // the slot of A's row n
-    const f32x16 c_full = anchored_start(0u, hh, g, ~0u); // a tile whose queries all exist, P <= 32: the same for every tile
+    using F = AnchorField<G::kRagged>;
+    f32x16 c_full[G::kRagged ? kAnchorGroups : 1]; // a tile whose queries all exist, P <= 32: the same for every tile (ragged: per group, set per block)
+    if constexpr (!G::kRagged) c_full[0] = anchored_start<F>(0u, hh, g, ~0u, g.offsets);
+    // the lane's read of block blk and group gi, clamped at the batch's end: in bounds, never stored
+    const auto clamped = [&](unsigned long long blk, int gi) {
+        const unsigned long long r = (blk << 6) + 32u * gi + n;
+        return r < count ? r : count - 1;
+    };
+    AnchorEntries ahead[G::kRagged ? kAnchorGroups : 1]; // ragged: the table entries of the wave's next block
+    if constexpr (G::kRagged) {
+        if (wave < nblocks) {
+#pragma unroll
+            for (int gi = 0; gi < kAnchorGroups; ++gi) ahead[gi] = anchored_entries<PACKED>(g, clamped(wave, gi));
+        }
+    }
 
     for (unsigned long long blk = wave; blk < nblocks; blk += nwaves) {
         i32x8 B[kAnchorGroups][4];
+        unsigned first[kAnchorGroups], admit[kAnchorGroups]; // row 0's offset and the admissible offsets of the lane's read
 #pragma unroll
         for (int gi = 0; gi < kAnchorGroups; ++gi) {
-            const unsigned long long r = (blk << 6) + 32u * gi + n;
-            const unsigned long long rc = r < count ? r : count - 1; // a clamped copy: in bounds, never stored
+            const unsigned long long rc = clamped(blk, gi);
+            unsigned long long base; // of the read in data: bytes, or words when packed
+            unsigned span;           // the span bytes of THIS read: nothing behind them is loaded or validated
+            if constexpr (G::kRagged) {
+                const AnchorLane L = anchored_lane<PACKED>(g, ahead[gi]);
+                base = L.base, first[gi] = L.a, admit[gi] = L.n;
+                span = L.n ? L.n + g.k - 1u : 0u;
+                c_full[gi] = anchored_start<F>(0u, hh, g, ~0u, L.n);
+            } else {
+                base = rc * g.stride, first[gi] = g.pos_lo, admit[gi] = g.offsets;
+                span = g.span;
+            }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const unsigned o = 16u * j + 8u * hh;
-                const unsigned len = o < g.span ? (g.span - o < 8u ? g.span - o : 8u) : 0u;
+                const unsigned len = o < span ? (span - o < 8u ? span - o : 8u) : 0u;
                 if constexpr (PACKED) {
-                    anchored_piece_packed(reinterpret_cast<const uint64_t *>(data) + rc * g.stride, g.pos_lo + o, len, B[gi][j]);
+                    anchored_piece_packed(reinterpret_cast<const uint64_t *>(data) + base, first[gi] + o, len, B[gi][j]);
                 } else {
-                    const unsigned long long at = rc * g.stride + g.pos_lo + o;
+                    const unsigned long long at = base + first[gi] + o;
                     if (__builtin_expect(trip_invalid(anchored_piece_ascii(data + at, len, B[gi][j])), 0)) rescan_bytes(data, at, len, slot);
                 }
+            }
+        }
+        if constexpr (G::kRagged) {
+            if (blk + nwaves < nblocks) { // behind this block's loads: the next block's entries
+#pragma unroll
+                for (int gi = 0; gi < kAnchorGroups; ++gi) ahead[gi] = anchored_entries<PACKED>(g, clamped(blk + nwaves, gi));
             }
         }
         uint32_t b1[kAnchorGroups], b2[kAnchorGroups], carry[kAnchorGroups];
@@ -222,20 +312,30 @@ reads_anchored_kernel(const uint8_t *__restrict__ data, unsigned long long count
                 }
             }
             const bool full = g.lg <= 5u && ((32u * T + 31u) >> g.lg) < g.nq; // wave-uniform
-            const f32x16 c = full ? c_full : anchored_start(T, hh, g, g.nq);
+            f32x16 c, cg[G::kRagged ? kAnchorGroups : 1];
+            if constexpr (!G::kRagged) {
+                c = full ? c_full[0] : anchored_start<F>(T, hh, g, g.nq, g.offsets);
+            } else if (full) { // ONE wave-uniform region for both groups: the partial tile's arithmetic stays out of the full tiles' path
+#pragma unroll
+                for (int gi = 0; gi < kAnchorGroups; ++gi) cg[gi] = c_full[gi];
+            } else {
+#pragma unroll
+                for (int gi = 0; gi < kAnchorGroups; ++gi) cg[gi] = anchored_start<F>(T, hh, g, g.nq, admit[gi]);
+            }
             const uint32_t tilebase = g.lg == 6u ? 32u * (T & ~1u) : 32u * T;
 #pragma unroll
             for (int gi = 0; gi < kAnchorGroups; ++gi) {
+                if constexpr (G::kRagged) c = cg[gi];
                 f32x16 acc = c;
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    if ((unsigned)j < nsteps) acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A[j], B[gi][j], acc, 4, 4, 0, kAnchorScale, 0, 127);
+                    if ((unsigned)j < nsteps) acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A[j], B[gi][j], acc, 4, 4, 0, F::kScale, 0, 127);
                 switch (g.lg) { // wave-uniform
-                case 0: anchored_reduce<1>(acc, tilebase, b1[gi], b2[gi]); break;
-                case 1: anchored_reduce<2>(acc, tilebase, b1[gi], b2[gi]); break;
-                case 2: anchored_reduce<4>(acc, tilebase, b1[gi], b2[gi]); break;
-                case 3: anchored_reduce<8>(acc, tilebase, b1[gi], b2[gi]); break;
-                case 4: anchored_reduce<16>(acc, tilebase, b1[gi], b2[gi]); break;
+                case 0: anchored_reduce<1, F>(acc, tilebase, b1[gi], b2[gi]); break;
+                case 1: anchored_reduce<2, F>(acc, tilebase, b1[gi], b2[gi]); break;
+                case 2: anchored_reduce<4, F>(acc, tilebase, b1[gi], b2[gi]); break;
+                case 3: anchored_reduce<8, F>(acc, tilebase, b1[gi], b2[gi]); break;
+                case 4: anchored_reduce<16, F>(acc, tilebase, b1[gi], b2[gi]); break;
                 default: {
                     uint32_t m = anchored_min16(acc);
                     if (g.lg == 6u) {
@@ -245,7 +345,7 @@ reads_anchored_kernel(const uint8_t *__restrict__ data, unsigned long long count
                     }
                     uint32_t lo, hi;
                     anchored_halves(m, lo, hi);
-                    const uint32_t key = anchored_global(min(lo, hi), tilebase);
+                    const uint32_t key = anchored_global<F>(min(lo, hi), tilebase);
                     b2[gi] = min(b2[gi], max(b1[gi], key));
                     b1[gi] = min(b1[gi], key);
                 }
@@ -263,8 +363,8 @@ reads_anchored_kernel(const uint8_t *__restrict__ data, unsigned long long count
             }
             const unsigned long long r = (blk << 6) + 32u * gi + n;
             if (hh == 0u && r < count) {
-                anchored_store(b1[gi], g, r, bq, bp, bd);
-                if (sq) anchored_store(b2[gi], g, r, sq, sp, sd);
+                anchored_store<F>(b1[gi], g.lg, first[gi], r, bq, bp, bd);
+                if (sq) anchored_store<F>(b2[gi], g.lg, first[gi], r, sq, sp, sd);
             }
         }
     }

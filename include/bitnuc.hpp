@@ -398,6 +398,36 @@ class Context {
             return NucleotideError::from_c(e);
         return b;
     }
+    // the anchored best match and runner-up per read of a ragged batch: anchor = BITNUC_ANCHOR_START admits pos_lo <= i <= min(pos_hi, len_r - k),
+    // BITNUC_ANCHOR_END the i with pos_lo <= len_r - k - i <= pos_hi (END, 0, 3: the last k bases with three bases of slack); pos_hi - pos_lo + k may not
+    // exceed BITNUC_ANCHOR_MAX_SPAN; a read without an admissible window gets the fill; positions are offsets from the read's start
+    Result<ReadsBest2> reads_hdist_anchored_batch(Bytes seq, const std::vector<uint64_t> &offsets, size_t k, const std::vector<uint64_t> &queries, size_t pos_lo = 0,
+                                                  size_t pos_hi = 0, int anchor = BITNUC_ANCHOR_START) const {
+        const size_t count = offsets.empty() ? 0 : offsets.size() - 1;
+        if (count && seq.len < offsets.back()) return NucleotideError::invalid_length(seq.len); // seq does not hold offsets.back() bases
+        ReadsBest2 b{{std::vector<uint32_t>(count), std::vector<uint32_t>(count), std::vector<uint8_t>(count)},
+                     {std::vector<uint32_t>(count), std::vector<uint32_t>(count), std::vector<uint8_t>(count)}};
+        bitnuc_err e;
+        if (bitnuc_reads_hdist_anchored_batch(ctx_, seq.ptr, offsets.data(), count, k, anchor, pos_lo, pos_hi, queries.data(), queries.size(), b.best.query.data(),
+                                              b.best.pos.data(), b.best.dist.data(), b.second.query.data(), b.second.pos.data(), b.second.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
+    Result<ReadsBest2> reads_hdist_anchored_batch_packed(Words words, const std::vector<uint64_t> &word_offsets, const std::vector<uint64_t> &offsets, size_t k,
+                                                         const std::vector<uint64_t> &queries, size_t pos_lo = 0, size_t pos_hi = 0,
+                                                         int anchor = BITNUC_ANCHOR_START) const {
+        const size_t count = offsets.empty() ? 0 : offsets.size() - 1;
+        if (word_offsets.size() != offsets.size()) return NucleotideError::unsupported(); // one word offset per base offset: the call reads count + 1 of each
+        if (count && words.len < word_offsets.back()) return NucleotideError::invalid_length(words.len); // words does not hold word_offsets.back() words
+        ReadsBest2 b{{std::vector<uint32_t>(count), std::vector<uint32_t>(count), std::vector<uint8_t>(count)},
+                     {std::vector<uint32_t>(count), std::vector<uint32_t>(count), std::vector<uint8_t>(count)}};
+        bitnuc_err e;
+        if (bitnuc_reads_hdist_anchored_batch_packed(ctx_, words.ptr, word_offsets.data(), offsets.data(), count, k, anchor, pos_lo, pos_hi, queries.data(),
+                                                     queries.size(), b.best.query.data(), b.best.pos.data(), b.best.dist.data(), b.second.query.data(),
+                                                     b.second.pos.data(), b.second.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
     Result<std::vector<uint64_t>> kmer_hdist_hits_packed(Words words, size_t n, size_t k, uint64_t query, unsigned tau, std::vector<uint8_t> *hit_dist = nullptr) const {
         uint64_t total = 0;
         bitnuc_err e;

@@ -503,7 +503,7 @@ int bitnuc_reads_hdist_best2_packed(bitnuc_ctx *ctx, const uint64_t *words, size
  * (profiles/r15_reads_anchored.json), ASCII / packed with the second triple: k = 16, four offsets: 0.28 / 0.20 ms at 1 query, 0.27 / 0.19 at 8, 0.56 /
  * 0.46 at 64, 2.8 / 2.6 at 512; one offset: 0.25 / 0.17, 0.25 / 0.17, 0.27 / 0.20, 0.90 / 0.77 ms; 0.003 - 0.84 x the time of a copy of the spans plus
  * bitnuc_reads_hdist_best2*_async on it.
- * Out of scope: the ragged twins, pattern (IUPAC) queries, a per-read offset table, spans above 64 bases, reverse-complement queries (callers add the
+ * The ragged twins: bitnuc_reads_hdist_anchored_batch* below.  Out of scope: pattern (IUPAC) queries, a per-read offset table, spans above 64 bases, reverse-complement queries (callers add the
  * reverse complements to the query list themselves). */
 #define BITNUC_ANCHOR_MAX_SPAN 64
 int bitnuc_reads_hdist_anchored_async(bitnuc_ctx *ctx, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
@@ -518,6 +518,64 @@ int bitnuc_reads_hdist_anchored(bitnuc_ctx *ctx, const uint8_t *reads, size_t re
 int bitnuc_reads_hdist_anchored_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
                                        const uint64_t *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query,
                                        uint32_t *second_pos, uint8_t *second_dist, bitnuc_err *err);
+
+/* ---- ANCHORED best match and runner-up per read of a RAGGED batch (a barcode or adapter in the first or the last k (+ slack) bases of trimmed, merged or
+ * long reads): the twins of the block above for the layout of bitnuc_reads_hdist_best_batch*, with an anchor that follows each read's own end ----
+ * Layout: that of bitnuc_reads_hdist_best_batch* (below), word for word: read r is seq[offsets[r] .. offsets[r+1]), packed its words start at
+ * words[word_offsets[r]]; bits above a read's last base are ignored; a zero-length read has no words.
+ * Windows.  len_r is the read's length, last_r = len_r - k.  BITNUC_ANCHOR_START: the admissible offsets are the i with pos_lo <= i <= min(pos_hi,
+ * last_r).  BITNUC_ANCHOR_END: offsets are measured from the read's end: e = last_r - i is the number of bases behind the window, admissible are the i
+ * with pos_lo <= e <= pos_hi and i >= 0 -- END, 0, 0 is the last k bases, END, 0, 3 the last k bases with three bases of slack.  In both modes best_pos /
+ * second_pos are offsets from the read's start.  Ties: the smallest query, then the smallest i.
+ * Span.  offsets = pos_hi - pos_lo + 1 and span = offsets + k - 1, judged on the arguments alone (computed without overflow; a value that does not fit is
+ * reported as SIZE_MAX).  span > BITNUC_ANCHOR_MAX_SPAN -> UNSUPPORTED (err.value = span): pos_hi = SIZE_MAX does NOT mean "to the end of the read" here
+ * -- the END anchor serves that purpose.  pos_hi < pos_lo is an empty range: every read gets the fill.
+ * Results: the six outputs of bitnuc_reads_hdist_anchored*, word for word (another window of the winner is never the runner-up, an equal duplicate query
+ * at a higher index is, one query gives the fill in the second triple).  A read without an admissible window (len_r < k, too short for pos_lo, empty)
+ * gets the fill (UINT32_MAX, UINT32_MAX, 0xFF) in all six.  The second triple may be ALL NULL; one or two of its pointers NULL -> UNSUPPORTED.  Exactly
+ * [0, count) of each output is written; the dist arrays may have any byte offset.  On a batch of equal lengths L, START (lo, hi) equals
+ * bitnuc_reads_hdist_anchored*(read_len = L, lo, hi) byte for byte, and END (e_lo, e_hi) equals it with pos_lo = L - k - e_hi, pos_hi = L - k - e_lo
+ * (L - k >= e_hi).
+ * Validation follows the fixed anchored form, not best_batch: of a read with n_r admissible offsets only the n_r + k - 1 span bytes are read and
+ * validated, never a byte of another read or behind the batch; a read without a window is not validated at all.  The first invalid span byte in buffer
+ * order -> INVALID_BASE with its absolute index, latched once per call for bitnuc_ctx_sync() by the _async forms (outputs then unspecified); the host
+ * forms below the cutoff leave the outputs untouched.  (The ASCII kernel loads aligned 4-byte words that hold a span byte: at most 3 bytes before and
+ * after a span are touched, never examined.)
+ * Checks, in order: (1) ctx NULL (_async forms always, host forms above the cutoff) -> UNSUPPORTED; (2) k > 32 -> SEQUENCE_TOO_LONG; (3) _async forms:
+ * total_bases, or 32*total_words, not below 2^58 -> UNSUPPORTED (value = that total); (4) n_queries > BITNUC_MAX_QUERIES -> UNSUPPORTED (value =
+ * n_queries); (5) anchor not 0 or 1 -> UNSUPPORTED (value = anchor), then span > BITNUC_ANCHOR_MAX_SPAN -> UNSUPPORTED (value = span); (6) count == 0 ->
+ * OK, nothing written; (7) outputs and queries as bitnuc_reads_hdist_anchored*, the tables as bitnuc_reads_hdist_best_batch* (NULL or not 8-byte aligned
+ * -> UNSUPPORTED); (8) host forms only: the tables' faults exactly as bitnuc_reads_hdist_best_batch reports them; (9) no window possible from the
+ * host-known arguments (k == 0, n_queries == 0, an empty range, fewer than k + pos_lo bases in the whole batch) -> OK with the fill, nothing is read;
+ * (10) seq NULL, or words NULL or not 8-byte aligned -> UNSUPPORTED.  Nothing is written on an argument error.
+ * The _async forms TRUST their tables (as bitnuc_reads_hdist_best_batch*_async), have the _dev contract, use the context's stream, do no host
+ * synchronisation but the growth of context scratch (256 bytes per query, as the fixed form) and can be captured into a hipGraph after a warm-up; the
+ * tables are read on the device at every replay, so a replay after the lengths changed (same count and totals) gives the new answers.  The host forms
+ * judge count x offsets x n_queries (saturated) against the host cutoff: below it they run on the host (ctx may be NULL), above it through the context
+ * in chunks of whole reads with rebased tables; INVALID_BASE indices stay absolute.
+ * Cost: the fixed form's kernel under a ragged layout policy -- every lane loads its own read's two table entries, start values of the accumulators
+ * carry each read's own number of admissible offsets, the tile loop is the fixed form's.  Measured on 6,666,667 reads of 100 .. 200 bases (10^9 bases), one
+ * MI355X (profiles/r16_reads_anchored_batch.json), ASCII / packed, all six outputs, END anchor: k = 16, one offset: 0.30 / 0.26 ms at 1 and at 8 queries,
+ * 0.32 / 0.28 at 64, 0.95 / 0.91 at 512; four offsets: 0.33 / 0.29, 0.30 / 0.27, 0.62 / 0.58, 2.90 / 2.88 ms; 0.17 - 0.83 x the time of a device gather of the
+ * spans into a compact batch plus bitnuc_reads_hdist_anchored*_async on it, at every measured point.  On equal-length reads the fixed form above gives the
+ * same answers in less time (this form takes 1.02 - 1.45 x of it, 0.03 - 0.27 ms more): a fixed-length batch belongs there.
+ * Out of scope: pattern (IUPAC) queries, a per-read offset table as an argument, spans above 64 bases, reverse-complement queries, a whole-read ragged
+ * best2. */
+#define BITNUC_ANCHOR_START 0
+#define BITNUC_ANCHOR_END 1
+int bitnuc_reads_hdist_anchored_batch_async(bitnuc_ctx *ctx, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k, int anchor,
+                                            size_t pos_lo, size_t pos_hi, const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos,
+                                            uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err);
+int bitnuc_reads_hdist_anchored_batch_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
+                                                   size_t total_words, size_t k, int anchor, size_t pos_lo, size_t pos_hi, const uint64_t *d_queries, size_t n_queries,
+                                                   uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, uint32_t *d_second_query,
+                                                   uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err);
+int bitnuc_reads_hdist_anchored_batch(bitnuc_ctx *ctx, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, int anchor, size_t pos_lo, size_t pos_hi,
+                                      const uint64_t *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query,
+                                      uint32_t *second_pos, uint8_t *second_dist, bitnuc_err *err);
+int bitnuc_reads_hdist_anchored_batch_packed(bitnuc_ctx *ctx, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
+                                             int anchor, size_t pos_lo, size_t pos_hi, const uint64_t *queries, size_t n_queries, uint32_t *best_query,
+                                             uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos, uint8_t *second_dist, bitnuc_err *err);
 
 /* ---- best match per read of a RAGGED batch (reads after trimming, merged pairs, amplicons, long reads, contigs): the twins of the block above for
  * the layout the ragged batch entry points read and write ----

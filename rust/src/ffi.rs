@@ -11,6 +11,8 @@ pub const BITNUC_INVALID_RANGE: c_int = 5;
 pub const BITNUC_UNSUPPORTED: c_int = 6;
 pub const BITNUC_SPLIT_AS_WRITTEN: c_int = 0;
 pub const BITNUC_SPLIT_CANONICAL: c_int = 1;
+pub const BITNUC_ANCHOR_START: c_int = 0;
+pub const BITNUC_ANCHOR_END: c_int = 1;
 pub const BITNUC_BACKEND_ERROR: c_int = 100;
 
 #[repr(C)]
@@ -153,6 +155,10 @@ extern "C" {
     pub fn bitnuc_reads_hdist_anchored_packed_async(ctx: *mut bitnuc_ctx, d_words: *const u64, read_len: usize, count: usize, k: usize, pos_lo: usize, pos_hi: usize, d_queries: *const u64, n_queries: usize, d_best_query: *mut u32, d_best_pos: *mut u32, d_best_dist: *mut u8, d_second_query: *mut u32, d_second_pos: *mut u32, d_second_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_reads_hdist_anchored(ctx: *mut bitnuc_ctx, reads: *const u8, read_len: usize, count: usize, k: usize, pos_lo: usize, pos_hi: usize, queries: *const u64, n_queries: usize, best_query: *mut u32, best_pos: *mut u32, best_dist: *mut u8, second_query: *mut u32, second_pos: *mut u32, second_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_reads_hdist_anchored_packed(ctx: *mut bitnuc_ctx, words: *const u64, read_len: usize, count: usize, k: usize, pos_lo: usize, pos_hi: usize, queries: *const u64, n_queries: usize, best_query: *mut u32, best_pos: *mut u32, best_dist: *mut u8, second_query: *mut u32, second_pos: *mut u32, second_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_reads_hdist_anchored_batch_async(ctx: *mut bitnuc_ctx, d_seq: *const u8, d_offsets: *const u64, count: usize, total_bases: usize, k: usize, anchor: c_int, pos_lo: usize, pos_hi: usize, d_queries: *const u64, n_queries: usize, d_best_query: *mut u32, d_best_pos: *mut u32, d_best_dist: *mut u8, d_second_query: *mut u32, d_second_pos: *mut u32, d_second_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_reads_hdist_anchored_batch_packed_async(ctx: *mut bitnuc_ctx, d_words: *const u64, d_word_offsets: *const u64, d_offsets: *const u64, count: usize, total_words: usize, k: usize, anchor: c_int, pos_lo: usize, pos_hi: usize, d_queries: *const u64, n_queries: usize, d_best_query: *mut u32, d_best_pos: *mut u32, d_best_dist: *mut u8, d_second_query: *mut u32, d_second_pos: *mut u32, d_second_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_reads_hdist_anchored_batch(ctx: *mut bitnuc_ctx, seq: *const u8, offsets: *const u64, count: usize, k: usize, anchor: c_int, pos_lo: usize, pos_hi: usize, queries: *const u64, n_queries: usize, best_query: *mut u32, best_pos: *mut u32, best_dist: *mut u8, second_query: *mut u32, second_pos: *mut u32, second_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_reads_hdist_anchored_batch_packed(ctx: *mut bitnuc_ctx, words: *const u64, word_offsets: *const u64, offsets: *const u64, count: usize, k: usize, anchor: c_int, pos_lo: usize, pos_hi: usize, queries: *const u64, n_queries: usize, best_query: *mut u32, best_pos: *mut u32, best_dist: *mut u8, second_query: *mut u32, second_pos: *mut u32, second_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_reads_hdist_best_batch_async(ctx: *mut bitnuc_ctx, d_seq: *const u8, d_offsets: *const u64, count: usize, total_bases: usize, k: usize, d_queries: *const u64, n_queries: usize, d_best_query: *mut u32, d_best_pos: *mut u32, d_best_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_reads_hdist_best_batch_packed_async(ctx: *mut bitnuc_ctx, d_words: *const u64, d_word_offsets: *const u64, d_offsets: *const u64, count: usize, total_words: usize, k: usize, d_queries: *const u64, n_queries: usize, d_best_query: *mut u32, d_best_pos: *mut u32, d_best_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_reads_hdist_best_batch(ctx: *mut bitnuc_ctx, seq: *const u8, offsets: *const u64, count: usize, k: usize, queries: *const u64, n_queries: usize, best_query: *mut u32, best_pos: *mut u32, best_dist: *mut u8, err: *mut bitnuc_err) -> c_int;

@@ -421,6 +421,46 @@ pub fn reads_hdist_anchored_packed(words: &[u64], read_len: usize, count: usize,
     if st == ffi::BITNUC_OK { Ok(((query, pos, dist), (query2, pos2, dist2))) } else { Err(to_err(&e)) }
 }
 
+/// Where the offset range of the ragged anchored calls is counted from: the read's start, or (in bases behind the window) its end.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum Anchor { Start, End }
+
+impl Anchor {
+    fn raw(self) -> std::os::raw::c_int { match self { Anchor::Start => ffi::BITNUC_ANCHOR_START, Anchor::End => ffi::BITNUC_ANCHOR_END } }
+}
+
+/// `reads_hdist_anchored` of a ragged batch (read `r` is `seq[offsets[r] .. offsets[r + 1])`): `Anchor::Start` admits the offsets
+/// `pos_lo <= i <= min(pos_hi, len_r - k)`, `Anchor::End` those with `pos_lo <= len_r - k - i <= pos_hi` (`End, 0, 3`: the last `k` bases with three bases
+/// of slack).  `pos_hi - pos_lo + k` may not exceed 64; a read without an admissible window gets the fill.  Positions are offsets from the read's start.
+pub fn reads_hdist_anchored_batch(seq: &[u8], offsets: &[u64], k: usize, anchor: Anchor, pos_lo: usize, pos_hi: usize, queries: &[u64]) -> Result<ReadsBest2, NucleotideError> {
+    let count = offsets.len().saturating_sub(1);
+    assert!(count == 0 || seq.len() as u64 >= offsets[count], "seq holds offsets[count] bases");
+    let (mut query, mut pos, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let (mut query2, mut pos2, mut dist2) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_hdist_anchored_batch(c, seq.as_ptr(), offsets.as_ptr(), count, k, anchor.raw(), pos_lo, pos_hi, queries.as_ptr(), queries.len(), query.as_mut_ptr(),
+                                               pos.as_mut_ptr(), dist.as_mut_ptr(), query2.as_mut_ptr(), pos2.as_mut_ptr(), dist2.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(((query, pos, dist), (query2, pos2, dist2))) } else { Err(to_err(&e)) }
+}
+
+/// `reads_hdist_anchored_batch` of the packed words `encode_batch` writes (read `r`'s words start at `words[word_offsets[r]]`), without decoding them.
+pub fn reads_hdist_anchored_batch_packed(words: &[u64], word_offsets: &[u64], offsets: &[u64], k: usize, anchor: Anchor, pos_lo: usize, pos_hi: usize, queries: &[u64]) -> Result<ReadsBest2, NucleotideError> {
+    let count = offsets.len().saturating_sub(1);
+    assert!(word_offsets.len() == offsets.len(), "one word offset per base offset");
+    assert!(count == 0 || words.len() as u64 >= word_offsets[count], "words holds word_offsets[count] words");
+    let (mut query, mut pos, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let (mut query2, mut pos2, mut dist2) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_hdist_anchored_batch_packed(c, words.as_ptr(), word_offsets.as_ptr(), offsets.as_ptr(), count, k, anchor.raw(), pos_lo, pos_hi, queries.as_ptr(),
+                                                      queries.len(), query.as_mut_ptr(), pos.as_mut_ptr(), dist.as_mut_ptr(), query2.as_mut_ptr(), pos2.as_mut_ptr(),
+                                                      dist2.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(((query, pos, dist), (query2, pos2, dist2))) } else { Err(to_err(&e)) }
+}
+
 /// The best match per read of a ragged batch: read `r` is `seq[offsets[r] .. offsets[r + 1])` (`offsets` has `count + 1` non-decreasing entries
 /// from 0).  `(query, pos, dist)` as `reads_hdist_best`; an empty read or one shorter than `k` gets `u32::MAX`, `u32::MAX`, `255`.
 pub fn reads_hdist_best_batch(seq: &[u8], offsets: &[u64], k: usize, queries: &[u64]) -> Result<(Vec<u32>, Vec<u32>, Vec<u8>), NucleotideError> {
