@@ -386,13 +386,21 @@ class Context:
         w = _as_u64(words)
         return self._best(self._lib.bitnuc_kmer_hdist_best_packed, (_ptr(w), w.size, int(n_bases), int(k)), queries)
 
-    def _reads_best(self, fn, head, count, queries):
+    def _reads_queries(self, queries, pattern_k):
+        """(array, Q) of a per-read call's queries: exact 2-bit words, or (pattern_k not None) patterns as _patterns takes them"""
+        if pattern_k is not None:
+            p = self._patterns(queries, pattern_k)
+            return p, p.shape[0]
         q = np.ascontiguousarray(np.asarray(queries, dtype=np.uint64).reshape(-1))  # a scalar query: Q = 1
+        return q, q.size
+
+    def _reads_best(self, fn, head, count, queries, pattern_k=None):
+        q, nq = self._reads_queries(queries, pattern_k)
         query = np.empty(count, dtype=np.uint32)
         pos = np.empty(count, dtype=np.uint32)
         dist = np.empty(count, dtype=np.uint8)
         err = L.BitnucErr()
-        if fn(self._h, *head, _ptr(q), q.size, _ptr(query), _ptr(pos), _ptr(dist), C.byref(err)) != L.OK:
+        if fn(self._h, *head, _ptr(q), nq, _ptr(query), _ptr(pos), _ptr(dist), C.byref(err)) != L.OK:
             _raise(err)
         return query, pos, dist
 
@@ -418,11 +426,11 @@ class Context:
             raise ValueError("words must hold count reads of ceil(read_len / 32) words each")
         return self._reads_best(self._lib.bitnuc_reads_hdist_best_packed, (_ptr(w), int(read_len), int(count), int(k)), int(count), queries)
 
-    def _reads_best2(self, fn, head, count, queries):
-        q = np.ascontiguousarray(np.asarray(queries, dtype=np.uint64).reshape(-1))  # a scalar query: Q = 1
+    def _reads_best2(self, fn, head, count, queries, pattern_k=None):
+        q, nq = self._reads_queries(queries, pattern_k)
         out = [np.empty(count, dtype=t) for t in (np.uint32, np.uint32, np.uint8, np.uint32, np.uint32, np.uint8)]
         err = L.BitnucErr()
-        if fn(self._h, *head, _ptr(q), q.size, *(_ptr(a) for a in out), C.byref(err)) != L.OK:
+        if fn(self._h, *head, _ptr(q), nq, *(_ptr(a) for a in out), C.byref(err)) != L.OK:
             _raise(err)
         return tuple(out)
 
@@ -448,13 +456,13 @@ class Context:
             raise ValueError("words must hold count reads of ceil(read_len / 32) words each")
         return self._reads_best2(self._lib.bitnuc_reads_hdist_best2_packed, (_ptr(w), int(read_len), int(count), int(k)), int(count), queries)
 
-    def _reads_anchored(self, fn, head, count, queries, pos_lo, pos_hi, second):
-        q = np.ascontiguousarray(np.asarray(queries, dtype=np.uint64).reshape(-1))  # a scalar query: Q = 1
+    def _reads_anchored(self, fn, head, count, queries, pos_lo, pos_hi, second, pattern_k=None):
+        q, nq = self._reads_queries(queries, pattern_k)
         types = (np.uint32, np.uint32, np.uint8) * (2 if second else 1)
         out = [np.empty(count, dtype=t) for t in types]
         ptrs = [_ptr(a) for a in out] + [None] * (6 - len(out))
         err = L.BitnucErr()
-        if fn(self._h, *head, int(pos_lo), _SIZE_MAX if pos_hi is None else int(pos_hi), _ptr(q), q.size, *ptrs, C.byref(err)) != L.OK:
+        if fn(self._h, *head, int(pos_lo), _SIZE_MAX if pos_hi is None else int(pos_hi), _ptr(q), nq, *ptrs, C.byref(err)) != L.OK:
             _raise(err)
         return tuple(out)
 
@@ -601,6 +609,104 @@ class Context:
         """kmer_pattern_best of the packed sequence `words` holding `n_bases` bases, without decoding it."""
         w = _as_u64(words)
         return self._pattern_best(self._lib.bitnuc_kmer_pattern_best_packed, (_ptr(w), w.size, int(n_bases), int(k)), patterns, k)
+
+    # -- pattern queries for the per-read matchers: the reads_hdist_* methods with `patterns` ((Q, 4) np.uint32, or IUPAC strings of length k) where
+    # `queries` stood and pdist where the Hamming distance stood; everything else as their exact twins --
+    @staticmethod
+    def _fixed_reads(reads, read_len, count):
+        s = _as_u8(reads)
+        read_len = int(read_len)
+        if count is None:
+            if read_len <= 0 or s.size % read_len:
+                raise ValueError("reads must hold a whole number of reads of read_len bases")
+            count = s.size // read_len
+        count = int(count)
+        if s.size < count * read_len:
+            raise ValueError("reads must hold count reads of read_len bases")
+        return s, read_len, count
+
+    @staticmethod
+    def _fixed_words(words, read_len, count):
+        w = _as_u64(words)
+        if w.size < int(count) * ((int(read_len) + 31) // 32):
+            raise ValueError("words must hold count reads of ceil(read_len / 32) words each")
+        return w, int(read_len), int(count)
+
+    @staticmethod
+    def _ragged_reads(seq, offsets):
+        s = _as_u8(seq)
+        off = _as_u64(offsets)
+        if off.size == 0:
+            raise ValueError("offsets must hold count + 1 entries")
+        if s.size < int(off[-1]):
+            raise ValueError("seq must hold offsets[-1] bases")
+        return s, off, off.size - 1
+
+    @staticmethod
+    def _ragged_words(words, word_offsets, offsets):
+        w = _as_u64(words)
+        woff = _as_u64(word_offsets)
+        off = _as_u64(offsets)
+        if off.size == 0 or woff.size != off.size:
+            raise ValueError("offsets and word_offsets must hold count + 1 entries each")
+        if w.size < int(woff[-1]):
+            raise ValueError("words must hold word_offsets[-1] words")
+        return w, woff, off, off.size - 1
+
+    def reads_pattern_best(self, reads, read_len, k, patterns, count=None):
+        """reads_hdist_best under pattern queries: per read the smallest (pdist, pattern index, offset) -> (query, pos, dist).  An N in a READ is still
+        an invalid base: the sets are on the query's side only."""
+        s, read_len, count = self._fixed_reads(reads, read_len, count)
+        return self._reads_best(self._lib.bitnuc_reads_pattern_best, (_ptr(s), read_len, count, int(k)), count, patterns, int(k))
+
+    def reads_pattern_best_packed(self, words, read_len, count, k, patterns):
+        """reads_pattern_best of the packed words encode_fixed writes (ceil(read_len / 32) words per read), without decoding them."""
+        w, read_len, count = self._fixed_words(words, read_len, count)
+        return self._reads_best(self._lib.bitnuc_reads_pattern_best_packed, (_ptr(w), read_len, count, int(k)), count, patterns, int(k))
+
+    def reads_pattern_best2(self, reads, read_len, k, patterns, count=None):
+        """reads_hdist_best2 under pattern queries: two equal patterns are two queries (the one at the higher index is the runner-up), another window of
+        the winning pattern never is."""
+        s, read_len, count = self._fixed_reads(reads, read_len, count)
+        return self._reads_best2(self._lib.bitnuc_reads_pattern_best2, (_ptr(s), read_len, count, int(k)), count, patterns, int(k))
+
+    def reads_pattern_best2_packed(self, words, read_len, count, k, patterns):
+        """reads_pattern_best2 of the packed words encode_fixed writes, without decoding them."""
+        w, read_len, count = self._fixed_words(words, read_len, count)
+        return self._reads_best2(self._lib.bitnuc_reads_pattern_best2_packed, (_ptr(w), read_len, count, int(k)), count, patterns, int(k))
+
+    def reads_pattern_anchored(self, reads, read_len, k, patterns, pos_lo=0, pos_hi=None, count=None, second=True):
+        """reads_hdist_anchored under pattern queries (the offsets pos_lo <= i <= min(pos_hi, read_len - k); span at most 64 bases)."""
+        s, read_len, count = self._fixed_reads(reads, read_len, count)
+        return self._reads_anchored(self._lib.bitnuc_reads_pattern_anchored, (_ptr(s), read_len, count, int(k)), count, patterns, pos_lo, pos_hi, second, int(k))
+
+    def reads_pattern_anchored_packed(self, words, read_len, count, k, patterns, pos_lo=0, pos_hi=None, second=True):
+        """reads_pattern_anchored of the packed words encode_fixed writes, without decoding them."""
+        w, read_len, count = self._fixed_words(words, read_len, count)
+        return self._reads_anchored(self._lib.bitnuc_reads_pattern_anchored_packed, (_ptr(w), read_len, count, int(k)), count, patterns, pos_lo, pos_hi, second,
+                                    int(k))
+
+    def reads_pattern_anchored_batch(self, seq, offsets, k, patterns, pos_lo=0, pos_hi=0, anchor="start", second=True):
+        """reads_hdist_anchored_batch under pattern queries (a ragged batch; the range counted from each read's start or end)."""
+        s, off, count = self._ragged_reads(seq, offsets)
+        return self._reads_anchored(self._lib.bitnuc_reads_pattern_anchored_batch, (_ptr(s), _ptr(off), count, int(k), self._anchor(anchor)), count, patterns, pos_lo,
+                                    int(pos_hi), second, int(k))
+
+    def reads_pattern_anchored_batch_packed(self, words, word_offsets, offsets, k, patterns, pos_lo=0, pos_hi=0, anchor="start", second=True):
+        """reads_pattern_anchored_batch of the packed words encode_batch writes, without decoding them."""
+        w, woff, off, count = self._ragged_words(words, word_offsets, offsets)
+        return self._reads_anchored(self._lib.bitnuc_reads_pattern_anchored_batch_packed, (_ptr(w), _ptr(woff), _ptr(off), count, int(k), self._anchor(anchor)), count,
+                                    patterns, pos_lo, int(pos_hi), second, int(k))
+
+    def reads_pattern_best_batch(self, seq, offsets, k, patterns):
+        """reads_hdist_best_batch under pattern queries (a ragged batch, every window of every read)."""
+        s, off, count = self._ragged_reads(seq, offsets)
+        return self._reads_best(self._lib.bitnuc_reads_pattern_best_batch, (_ptr(s), _ptr(off), count, int(k)), count, patterns, int(k))
+
+    def reads_pattern_best_batch_packed(self, words, word_offsets, offsets, k, patterns):
+        """reads_pattern_best_batch of the packed words encode_batch writes, without decoding them."""
+        w, woff, off, count = self._ragged_words(words, word_offsets, offsets)
+        return self._reads_best(self._lib.bitnuc_reads_pattern_best_batch_packed, (_ptr(w), _ptr(woff), _ptr(off), count, int(k)), count, patterns, int(k))
 
     # -- the mismatch histogram per query: windows at each distance 0 .. n_bins - 1 in one pass --
     def _hist(self, fn, head, q, nq, n_bins):
@@ -957,6 +1063,69 @@ class Context:
         """The best match per read on the packed words encode_batch_dev writes (8-byte aligned; both tables u64 in device memory, trusted)."""
         self._call_dev(self._lib.bitnuc_reads_hdist_best_batch_packed_async, _dev_ptr(d_words), _dev_ptr(d_word_offsets), _dev_ptr(d_offsets), int(count),
                        int(total_words), int(k), _dev_ptr(d_queries), int(n_queries), _dev_ptr(d_best_query), _dev_ptr(d_best_pos), _dev_ptr(d_best_dist))
+
+    # the per-read matchers' pattern twins: the reads_hdist_*_async methods with d_patterns (n_queries bitnuc_pattern, 16 bytes each, 4-byte aligned,
+    # device memory) where d_queries stood
+    def reads_pattern_best_async(self, d_reads, read_len, count, k, d_patterns, n_queries, d_best_query, d_best_pos, d_best_dist):
+        """reads_hdist_best_async under pattern queries."""
+        self._call_dev(self._lib.bitnuc_reads_pattern_best_async, _dev_ptr(d_reads), int(read_len), int(count), int(k), _dev_ptr(d_patterns), int(n_queries),
+                       _dev_ptr(d_best_query), _dev_ptr(d_best_pos), _dev_ptr(d_best_dist))
+
+    def reads_pattern_best_packed_async(self, d_words, read_len, count, k, d_patterns, n_queries, d_best_query, d_best_pos, d_best_dist):
+        """reads_hdist_best_packed_async under pattern queries."""
+        self._call_dev(self._lib.bitnuc_reads_pattern_best_packed_async, _dev_ptr(d_words), int(read_len), int(count), int(k), _dev_ptr(d_patterns),
+                       int(n_queries), _dev_ptr(d_best_query), _dev_ptr(d_best_pos), _dev_ptr(d_best_dist))
+
+    def reads_pattern_best2_async(self, d_reads, read_len, count, k, d_patterns, n_queries, d_best_query, d_best_pos, d_best_dist, d_second_query, d_second_pos,
+                                  d_second_dist):
+        """reads_hdist_best2_async under pattern queries."""
+        self._call_dev(self._lib.bitnuc_reads_pattern_best2_async, _dev_ptr(d_reads), int(read_len), int(count), int(k), _dev_ptr(d_patterns), int(n_queries),
+                       _dev_ptr(d_best_query), _dev_ptr(d_best_pos), _dev_ptr(d_best_dist), _dev_ptr(d_second_query), _dev_ptr(d_second_pos), _dev_ptr(d_second_dist))
+
+    def reads_pattern_best2_packed_async(self, d_words, read_len, count, k, d_patterns, n_queries, d_best_query, d_best_pos, d_best_dist, d_second_query,
+                                         d_second_pos, d_second_dist):
+        """reads_hdist_best2_packed_async under pattern queries."""
+        self._call_dev(self._lib.bitnuc_reads_pattern_best2_packed_async, _dev_ptr(d_words), int(read_len), int(count), int(k), _dev_ptr(d_patterns), int(n_queries),
+                       _dev_ptr(d_best_query), _dev_ptr(d_best_pos), _dev_ptr(d_best_dist), _dev_ptr(d_second_query), _dev_ptr(d_second_pos), _dev_ptr(d_second_dist))
+
+    def reads_pattern_anchored_async(self, d_reads, read_len, count, k, d_patterns, n_queries, d_best_query, d_best_pos, d_best_dist, d_second_query=None,
+                                     d_second_pos=None, d_second_dist=None, pos_lo=0, pos_hi=None):
+        """reads_hdist_anchored_async under pattern queries."""
+        self._call_dev(self._lib.bitnuc_reads_pattern_anchored_async, _dev_ptr(d_reads), int(read_len), int(count), int(k), int(pos_lo),
+                       _SIZE_MAX if pos_hi is None else int(pos_hi), _dev_ptr(d_patterns), int(n_queries), _dev_ptr(d_best_query), _dev_ptr(d_best_pos),
+                       _dev_ptr(d_best_dist), *(_dev_ptr(a) for a in (d_second_query, d_second_pos, d_second_dist)))
+
+    def reads_pattern_anchored_packed_async(self, d_words, read_len, count, k, d_patterns, n_queries, d_best_query, d_best_pos, d_best_dist, d_second_query=None,
+                                            d_second_pos=None, d_second_dist=None, pos_lo=0, pos_hi=None):
+        """reads_hdist_anchored_packed_async under pattern queries."""
+        self._call_dev(self._lib.bitnuc_reads_pattern_anchored_packed_async, _dev_ptr(d_words), int(read_len), int(count), int(k), int(pos_lo),
+                       _SIZE_MAX if pos_hi is None else int(pos_hi), _dev_ptr(d_patterns), int(n_queries), _dev_ptr(d_best_query), _dev_ptr(d_best_pos),
+                       _dev_ptr(d_best_dist), *(_dev_ptr(a) for a in (d_second_query, d_second_pos, d_second_dist)))
+
+    def reads_pattern_anchored_batch_async(self, d_seq, d_offsets, count, total_bases, k, d_patterns, n_queries, d_best_query, d_best_pos, d_best_dist,
+                                           d_second_query=None, d_second_pos=None, d_second_dist=None, pos_lo=0, pos_hi=0, anchor="start"):
+        """reads_hdist_anchored_batch_async under pattern queries."""
+        self._call_dev(self._lib.bitnuc_reads_pattern_anchored_batch_async, _dev_ptr(d_seq), _dev_ptr(d_offsets), int(count), int(total_bases), int(k),
+                       self._anchor(anchor), int(pos_lo), int(pos_hi), _dev_ptr(d_patterns), int(n_queries), _dev_ptr(d_best_query), _dev_ptr(d_best_pos),
+                       _dev_ptr(d_best_dist), *(_dev_ptr(a) for a in (d_second_query, d_second_pos, d_second_dist)))
+
+    def reads_pattern_anchored_batch_packed_async(self, d_words, d_word_offsets, d_offsets, count, total_words, k, d_patterns, n_queries, d_best_query, d_best_pos,
+                                                  d_best_dist, d_second_query=None, d_second_pos=None, d_second_dist=None, pos_lo=0, pos_hi=0, anchor="start"):
+        """reads_hdist_anchored_batch_packed_async under pattern queries."""
+        self._call_dev(self._lib.bitnuc_reads_pattern_anchored_batch_packed_async, _dev_ptr(d_words), _dev_ptr(d_word_offsets), _dev_ptr(d_offsets), int(count),
+                       int(total_words), int(k), self._anchor(anchor), int(pos_lo), int(pos_hi), _dev_ptr(d_patterns), int(n_queries), _dev_ptr(d_best_query),
+                       _dev_ptr(d_best_pos), _dev_ptr(d_best_dist), *(_dev_ptr(a) for a in (d_second_query, d_second_pos, d_second_dist)))
+
+    def reads_pattern_best_batch_async(self, d_seq, d_offsets, count, total_bases, k, d_patterns, n_queries, d_best_query, d_best_pos, d_best_dist):
+        """reads_hdist_best_batch_async under pattern queries."""
+        self._call_dev(self._lib.bitnuc_reads_pattern_best_batch_async, _dev_ptr(d_seq), _dev_ptr(d_offsets), int(count), int(total_bases), int(k),
+                       _dev_ptr(d_patterns), int(n_queries), _dev_ptr(d_best_query), _dev_ptr(d_best_pos), _dev_ptr(d_best_dist))
+
+    def reads_pattern_best_batch_packed_async(self, d_words, d_word_offsets, d_offsets, count, total_words, k, d_patterns, n_queries, d_best_query, d_best_pos,
+                                              d_best_dist):
+        """reads_hdist_best_batch_packed_async under pattern queries."""
+        self._call_dev(self._lib.bitnuc_reads_pattern_best_batch_packed_async, _dev_ptr(d_words), _dev_ptr(d_word_offsets), _dev_ptr(d_offsets), int(count),
+                       int(total_words), int(k), _dev_ptr(d_patterns), int(n_queries), _dev_ptr(d_best_query), _dev_ptr(d_best_pos), _dev_ptr(d_best_dist))
 
     # the pattern twins: d_patterns holds n_queries bitnuc_pattern (16 bytes each, 4-byte aligned) in device memory; the hit lists take their one
     # pattern from the host (a (4,) np.uint32 array)

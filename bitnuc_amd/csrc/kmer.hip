@@ -710,7 +710,7 @@ struct ScanJob {
 // The runner-up (bitnuc_reads_hdist_best2*) keeps two key arrays there: keys1 with one spare entry (count + 1: the exclusion form's loads), then keys2,
 // both set to all-ones by one memset; the second pass reads keys1 and fills keys2, reads_finish2_kernel writes the six outputs.
 template <class HQ> struct ReadsArgsT { const HQ *queries; size_t nq; uint32_t *query, *pos; uint8_t *dist; };
-using ReadsArgs = ReadsArgsT<uint64_t>;
+template <class HQ> constexpr uintptr_t reads_qmask() { return sizeof(HQ) == 8 ? 7 : 3; } // the queries' alignment: 8 bytes exact, 4 bytes patterns
 struct ReadsSecond { uint32_t *query, *pos; uint8_t *dist; }; // the runner-up's outputs
 
 inline ReadsGeom reads_geom(size_t period, size_t read_len, size_t k) { return ReadsGeom{period, (unsigned)(read_len - k), 1.0f / (float)period}; }
@@ -802,8 +802,8 @@ int launch_reads_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t read_l
 }
 
 // the reads calls' checks 2 - 6 (after ctx): *done = nothing to do (count == 0)
-int check_reads(size_t read_len, size_t count, size_t k, const void *queries, size_t nq, const void *query, const void *pos, const void *dist, bool *done,
-                bitnuc_err *err) {
+int check_reads(size_t read_len, size_t count, size_t k, const void *queries, uintptr_t qmask, size_t nq, const void *query, const void *pos, const void *dist,
+                bool *done, bitnuc_err *err) {
     *done = false;
     if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
     constexpr size_t kLimit = (size_t)1 << 58;
@@ -814,7 +814,7 @@ int check_reads(size_t read_len, size_t count, size_t k, const void *queries, si
     *done = count == 0;
     if (*done) return BITNUC_OK;
     if (!query || !pos || !dist || (reinterpret_cast<uintptr_t>(query) & 3) || (reinterpret_cast<uintptr_t>(pos) & 3) || (!queries && nq) ||
-        (reinterpret_cast<uintptr_t>(queries) & 7))
+        (reinterpret_cast<uintptr_t>(queries) & qmask))
         return fail(err, BITNUC_UNSUPPORTED);
     return BITNUC_OK;
 }
@@ -841,16 +841,16 @@ inline size_t reads_work(size_t read_len, size_t count, size_t k, size_t nq) { r
 // The host forms' chunk loop: whole reads, `per` of them per chunk (no overlap: no window crosses a read); the queries copied once into scratch 2, a
 // chunk's query / pos arrays in scratch 1, its distances in scratch 3, copied straight to their place in the outputs.  `launch(r0, m, a)` runs the
 // reads [r0, r0 + m) with a's device arrays.  Stops at the first failing chunk (drain: its first invalid byte, absolute through the slot's base).
-template <class Launch>
-int reads_host_loop(bitnuc_ctx *c, size_t count, size_t per, const uint64_t *queries, size_t nq, uint32_t *query, uint32_t *pos, uint8_t *dist, bitnuc_err *err,
+template <class HQ, class Launch>
+int reads_host_loop(bitnuc_ctx *c, size_t count, size_t per, const HQ *queries, size_t nq, uint32_t *query, uint32_t *pos, uint8_t *dist, bitnuc_err *err,
                     Launch launch) {
     const size_t pm = count < per ? count : per;
     if (int st = ensure_scratch(c, 1, pm * 8, err)) return st;
-    if (int st = ensure_scratch(c, 2, nq * 8, err)) return st;
+    if (int st = ensure_scratch(c, 2, nq * sizeof(HQ), err)) return st; // 8: exact queries, 16: patterns
     if (int st = ensure_scratch(c, 3, pm < 64 ? 64 : pm, err)) return st;
-    HIPCHK(hipMemcpyAsync(c->scratch[2], queries, nq * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->scratch[2], queries, nq * sizeof(HQ), hipMemcpyHostToDevice, c->stream));
     uint32_t *d_query = reinterpret_cast<uint32_t *>(c->scratch[1]), *d_pos = d_query + pm;
-    const ReadsArgs a{reinterpret_cast<const uint64_t *>(c->scratch[2]), nq, d_query, d_pos, c->scratch[3]};
+    const ReadsArgsT<HQ> a{reinterpret_cast<const HQ *>(c->scratch[2]), nq, d_query, d_pos, c->scratch[3]};
     for (size_t r0 = 0; r0 < count; r0 += per) {
         const size_t m = count - r0 < per ? count - r0 : per;
         if (int st = launch(r0, m, a)) return st;
@@ -865,17 +865,17 @@ int reads_host_loop(bitnuc_ctx *c, size_t count, size_t per, const uint64_t *que
 
 // reads_host_loop with the runner-up's outputs: four query / pos arrays in scratch 1, two distance arrays in scratch 3.  A chunk holds whole reads, so
 // both triples are the chunk's own: nothing is merged across chunks.
-template <class Launch>
-int reads_host_loop2(bitnuc_ctx *c, size_t count, size_t per, const uint64_t *queries, size_t nq, uint32_t *query, uint32_t *pos, uint8_t *dist, uint32_t *query2,
+template <class HQ, class Launch>
+int reads_host_loop2(bitnuc_ctx *c, size_t count, size_t per, const HQ *queries, size_t nq, uint32_t *query, uint32_t *pos, uint8_t *dist, uint32_t *query2,
                      uint32_t *pos2, uint8_t *dist2, bitnuc_err *err, Launch launch) {
     const size_t pm = count < per ? count : per;
     if (int st = ensure_scratch(c, 1, pm * 16, err)) return st;
-    if (int st = ensure_scratch(c, 2, nq * 8, err)) return st;
+    if (int st = ensure_scratch(c, 2, nq * sizeof(HQ), err)) return st;
     if (int st = ensure_scratch(c, 3, 2 * pm < 64 ? 64 : 2 * pm, err)) return st;
-    HIPCHK(hipMemcpyAsync(c->scratch[2], queries, nq * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->scratch[2], queries, nq * sizeof(HQ), hipMemcpyHostToDevice, c->stream));
     uint32_t *d_query = reinterpret_cast<uint32_t *>(c->scratch[1]), *d_pos = d_query + pm, *d_query2 = d_pos + pm, *d_pos2 = d_query2 + pm;
     uint8_t *d_dist = c->scratch[3], *d_dist2 = d_dist + pm;
-    const ReadsArgs a{reinterpret_cast<const uint64_t *>(c->scratch[2]), nq, d_query, d_pos, d_dist};
+    const ReadsArgsT<HQ> a{reinterpret_cast<const HQ *>(c->scratch[2]), nq, d_query, d_pos, d_dist};
     const ReadsSecond b{d_query2, d_pos2, d_dist2};
     for (size_t r0 = 0; r0 < count; r0 += per) {
         const size_t m = count - r0 < per ? count - r0 : per;
@@ -897,8 +897,8 @@ int reads_host_loop2(bitnuc_ctx *c, size_t count, size_t per, const uint64_t *qu
 struct AnchorOut { uint32_t *query, *pos; uint8_t *dist, *dist2; uint32_t *query2, *pos2; }; // query2 == nullptr: the best triple only
 
 // the calls' checks 2 - 7 (after ctx).  *done: nothing to do (count == 0); *offsets == 0: no window (fill), otherwise the offsets per read
-int check_anchored(size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi, const void *queries, size_t nq, const AnchorOut &o, bool *done,
-                   size_t *offsets, bitnuc_err *err) {
+int check_anchored(size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi, const void *queries, uintptr_t qmask, size_t nq, const AnchorOut &o,
+                   bool *done, size_t *offsets, bitnuc_err *err) {
     *done = false;
     *offsets = 0;
     if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
@@ -912,7 +912,7 @@ int check_anchored(size_t read_len, size_t count, size_t k, size_t pos_lo, size_
     *done = count == 0;
     if (*done) return BITNUC_OK;
     if (!o.query || !o.pos || !o.dist || (reinterpret_cast<uintptr_t>(o.query) & 3) || (reinterpret_cast<uintptr_t>(o.pos) & 3) || (!queries && nq) ||
-        (reinterpret_cast<uintptr_t>(queries) & 7))
+        (reinterpret_cast<uintptr_t>(queries) & qmask))
         return fail(err, BITNUC_UNSUPPORTED);
     const int n2 = (o.query2 != nullptr) + (o.pos2 != nullptr) + (o.dist2 != nullptr);
     if ((n2 != 0 && n2 != 3) || (reinterpret_cast<uintptr_t>(o.query2) & 3) || (reinterpret_cast<uintptr_t>(o.pos2) & 3)) return fail(err, BITNUC_UNSUPPORTED);
@@ -931,8 +931,8 @@ int anchored_fill_dev(bitnuc_ctx *c, size_t count, const AnchorOut &o, bitnuc_er
 }
 
 // data: ASCII reads at any alignment (stride = read_len bytes) or 8-byte aligned packed words (stride = words per read); count, nq, offsets >= 1
-template <bool PACKED>
-int launch_reads_anchored(bitnuc_ctx *c, const void *data, size_t stride, size_t count, size_t k, size_t pos_lo, size_t offsets, const uint64_t *d_queries, size_t nq,
+template <bool PACKED, class HQ>
+int launch_reads_anchored(bitnuc_ctx *c, const void *data, size_t stride, size_t count, size_t k, size_t pos_lo, size_t offsets, const HQ *d_queries, size_t nq,
                           const AnchorOut &o, unsigned long long *slot, bitnuc_err *err) {
     if (int st = ensure_scratch(c, 10, nq * kAnchorEntry, err)) return st;
     anchored_tables_kernel<<<(unsigned)nq, 64, 0, c->stream>>>(dev_queries(d_queries), (unsigned)k, reinterpret_cast<uint32_t *>(c->scratch[10]));
@@ -952,19 +952,19 @@ int launch_reads_anchored(bitnuc_ctx *c, const void *data, size_t stride, size_t
 inline size_t anchored_work(size_t offsets, size_t count, size_t nq) { return multi_work(multi_work(offsets, count), nq); }
 
 // The anchored host forms' chunk loop: reads_host_loop2's scratch and copies; without the second triple its three arrays are neither computed nor copied.
-template <class Launch>
-int anchored_host_loop(bitnuc_ctx *c, size_t count, size_t per, const uint64_t *queries, size_t nq, const AnchorOut &o, bitnuc_err *err, Launch launch) {
+template <class HQ, class Launch>
+int anchored_host_loop(bitnuc_ctx *c, size_t count, size_t per, const HQ *queries, size_t nq, const AnchorOut &o, bitnuc_err *err, Launch launch) {
     const size_t pm = count < per ? count : per;
     if (int st = ensure_scratch(c, 1, pm * 16, err)) return st;
-    if (int st = ensure_scratch(c, 2, nq * 8, err)) return st;
+    if (int st = ensure_scratch(c, 2, nq * sizeof(HQ), err)) return st;
     if (int st = ensure_scratch(c, 3, 2 * pm < 64 ? 64 : 2 * pm, err)) return st;
-    HIPCHK(hipMemcpyAsync(c->scratch[2], queries, nq * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->scratch[2], queries, nq * sizeof(HQ), hipMemcpyHostToDevice, c->stream));
     uint32_t *d_query = reinterpret_cast<uint32_t *>(c->scratch[1]), *d_pos = d_query + pm, *d_query2 = d_pos + pm, *d_pos2 = d_query2 + pm;
     uint8_t *d_dist = c->scratch[3], *d_dist2 = d_dist + pm;
     const AnchorOut d = o.query2 ? AnchorOut{d_query, d_pos, d_dist, d_dist2, d_query2, d_pos2} : AnchorOut{d_query, d_pos, d_dist, nullptr, nullptr, nullptr};
     for (size_t r0 = 0; r0 < count; r0 += per) {
         const size_t m = count - r0 < per ? count - r0 : per;
-        if (int st = launch(r0, m, reinterpret_cast<const uint64_t *>(c->scratch[2]), d)) return st;
+        if (int st = launch(r0, m, reinterpret_cast<const HQ *>(c->scratch[2]), d)) return st;
         HIPCHK(hipMemcpyAsync(o.query + r0, d_query, m * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(o.pos + r0, d_pos, m * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(o.dist + r0, d_dist, m, hipMemcpyDeviceToHost, c->stream));
@@ -1017,8 +1017,8 @@ int launch_reads_batch_packed(bitnuc_ctx *c, const uint64_t *words, const uint64
 
 // the ragged reads calls' checks 2 - 6 (after ctx): `total` is what check 3 bounds (bases, or 32 x words; the host forms pass 0 and bound their tables'
 // totals with the table validation); tab2: the second table of the packed forms.  *done = nothing to do (count == 0)
-int check_reads_batch(uint64_t total, uint64_t total_value, size_t count, size_t k, const void *queries, size_t nq, const void *query, const void *pos, const void *dist,
-                      const void *tab1, const void *tab2, bool two_tables, bool *done, bitnuc_err *err) {
+int check_reads_batch(uint64_t total, uint64_t total_value, size_t count, size_t k, const void *queries, uintptr_t qmask, size_t nq, const void *query, const void *pos,
+                      const void *dist, const void *tab1, const void *tab2, bool two_tables, bool *done, bitnuc_err *err) {
     *done = false;
     if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
     if (total >= ((uint64_t)1 << 58)) return fail(err, BITNUC_UNSUPPORTED, total_value);
@@ -1026,7 +1026,7 @@ int check_reads_batch(uint64_t total, uint64_t total_value, size_t count, size_t
     *done = count == 0;
     if (*done) return BITNUC_OK;
     if (!query || !pos || !dist || (reinterpret_cast<uintptr_t>(query) & 3) || (reinterpret_cast<uintptr_t>(pos) & 3) || (!queries && nq) ||
-        (reinterpret_cast<uintptr_t>(queries) & 7) || !tab1 || (reinterpret_cast<uintptr_t>(tab1) & 7) ||
+        (reinterpret_cast<uintptr_t>(queries) & qmask) || !tab1 || (reinterpret_cast<uintptr_t>(tab1) & 7) ||
         (two_tables && (!tab2 || (reinterpret_cast<uintptr_t>(tab2) & 7))))
         return fail(err, BITNUC_UNSUPPORTED);
     return BITNUC_OK;
@@ -1039,17 +1039,17 @@ int fail_batch_tables(const BatchFault &f, bitnuc_err *err) {
 
 // The ragged host forms' chunk loop: reads_host_loop with chunks of whole reads of any number: chunk_end(r0) is the read after the chunk's last;
 // `launch(r0, m, a)` runs the reads [r0, r0 + m) with a's device arrays.
-template <class ChunkEnd, class Launch>
-int reads_batch_host_loop(bitnuc_ctx *c, size_t count, const uint64_t *queries, size_t nq, uint32_t *query, uint32_t *pos, uint8_t *dist, bitnuc_err *err,
+template <class HQ, class ChunkEnd, class Launch>
+int reads_batch_host_loop(bitnuc_ctx *c, size_t count, const HQ *queries, size_t nq, uint32_t *query, uint32_t *pos, uint8_t *dist, bitnuc_err *err,
                           ChunkEnd chunk_end, Launch launch) {
-    if (int st = ensure_scratch(c, 2, nq * 8, err)) return st;
-    HIPCHK(hipMemcpyAsync(c->scratch[2], queries, nq * 8, hipMemcpyHostToDevice, c->stream));
+    if (int st = ensure_scratch(c, 2, nq * sizeof(HQ), err)) return st;
+    HIPCHK(hipMemcpyAsync(c->scratch[2], queries, nq * sizeof(HQ), hipMemcpyHostToDevice, c->stream));
     for (size_t r0 = 0; r0 < count;) {
         const size_t m = chunk_end(r0) - r0;
         if (int st = ensure_scratch(c, 1, m * 8, err)) return st;
         if (int st = ensure_scratch(c, 3, m < 64 ? 64 : m, err)) return st;
         uint32_t *d_query = reinterpret_cast<uint32_t *>(c->scratch[1]), *d_pos = d_query + m;
-        const ReadsArgs a{reinterpret_cast<const uint64_t *>(c->scratch[2]), nq, d_query, d_pos, c->scratch[3]};
+        const ReadsArgsT<HQ> a{reinterpret_cast<const HQ *>(c->scratch[2]), nq, d_query, d_pos, c->scratch[3]};
         if (int st = launch(r0, m, a)) return st;
         HIPCHK(hipMemcpyAsync(query + r0, d_query, m * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(pos + r0, d_pos, m * 4, hipMemcpyDeviceToHost, c->stream));
@@ -1065,8 +1065,8 @@ int reads_batch_host_loop(bitnuc_ctx *c, size_t count, const uint64_t *queries, 
 // fixed form's tables and scratch (256 bytes per query), the ragged forms' tables and chunk cut.
 // the calls' checks 2 - 7 (after ctx): `total` is what check 3 bounds (the host forms pass 0: their tables' validation bounds the totals).  *done:
 // nothing to do (count == 0); *offsets: pos_hi - pos_lo + 1, 0 for an empty range
-int check_anchored_batch(uint64_t total, uint64_t total_value, size_t count, size_t k, int anchor, size_t pos_lo, size_t pos_hi, const void *queries, size_t nq,
-                         const AnchorOut &o, const void *tab1, const void *tab2, bool two_tables, bool *done, size_t *offsets, bitnuc_err *err) {
+int check_anchored_batch(uint64_t total, uint64_t total_value, size_t count, size_t k, int anchor, size_t pos_lo, size_t pos_hi, const void *queries, uintptr_t qmask,
+                         size_t nq, const AnchorOut &o, const void *tab1, const void *tab2, bool two_tables, bool *done, size_t *offsets, bitnuc_err *err) {
     *done = false;
     *offsets = 0;
     if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
@@ -1079,7 +1079,7 @@ int check_anchored_batch(uint64_t total, uint64_t total_value, size_t count, siz
     *done = count == 0;
     if (*done) return BITNUC_OK;
     if (!o.query || !o.pos || !o.dist || (reinterpret_cast<uintptr_t>(o.query) & 3) || (reinterpret_cast<uintptr_t>(o.pos) & 3) || (!queries && nq) ||
-        (reinterpret_cast<uintptr_t>(queries) & 7))
+        (reinterpret_cast<uintptr_t>(queries) & qmask))
         return fail(err, BITNUC_UNSUPPORTED);
     const int n2 = (o.query2 != nullptr) + (o.pos2 != nullptr) + (o.dist2 != nullptr);
     if ((n2 != 0 && n2 != 3) || (reinterpret_cast<uintptr_t>(o.query2) & 3) || (reinterpret_cast<uintptr_t>(o.pos2) & 3)) return fail(err, BITNUC_UNSUPPORTED);
@@ -1095,9 +1095,9 @@ inline bool anchored_batch_no_window(uint64_t total, size_t k, size_t nq, size_t
 
 // data: ASCII at any alignment, read r at bytes d_offsets[r] .. d_offsets[r + 1], or 8-byte aligned words, read r from word d_starts[r]; the tables in
 // device memory; count, nq >= 1, 1 <= offsets, offsets + k - 1 <= 64, pos_lo < 2^32 - 1
-template <bool PACKED>
+template <bool PACKED, class HQ>
 int launch_reads_anchored_batch(bitnuc_ctx *c, const void *data, const uint64_t *d_starts, const uint64_t *d_offsets, size_t count, size_t k, int anchor, size_t pos_lo,
-                                size_t offsets, const uint64_t *d_queries, size_t nq, const AnchorOut &o, unsigned long long *slot, bitnuc_err *err) {
+                                size_t offsets, const HQ *d_queries, size_t nq, const AnchorOut &o, unsigned long long *slot, bitnuc_err *err) {
     if (int st = ensure_scratch(c, 10, nq * kAnchorEntry, err)) return st;
     anchored_tables_kernel<<<(unsigned)nq, 64, 0, c->stream>>>(dev_queries(d_queries), (unsigned)k, reinterpret_cast<uint32_t *>(c->scratch[10]));
     HIPCHK(hipGetLastError());
@@ -1115,10 +1115,10 @@ int launch_reads_anchored_batch(bitnuc_ctx *c, const void *data, const uint64_t 
 
 // The ragged anchored host forms' chunk loop: reads_batch_host_loop's chunks (chunk_end(r0) is the read after the chunk's last) with anchored_host_loop's
 // outputs: six arrays, or three without the second triple.  `launch(r0, m, d_queries, d)` runs the reads [r0, r0 + m) into d's device arrays.
-template <class ChunkEnd, class Launch>
-int anchored_batch_host_loop(bitnuc_ctx *c, size_t count, const uint64_t *queries, size_t nq, const AnchorOut &o, bitnuc_err *err, ChunkEnd chunk_end, Launch launch) {
-    if (int st = ensure_scratch(c, 2, nq * 8, err)) return st;
-    HIPCHK(hipMemcpyAsync(c->scratch[2], queries, nq * 8, hipMemcpyHostToDevice, c->stream));
+template <class HQ, class ChunkEnd, class Launch>
+int anchored_batch_host_loop(bitnuc_ctx *c, size_t count, const HQ *queries, size_t nq, const AnchorOut &o, bitnuc_err *err, ChunkEnd chunk_end, Launch launch) {
+    if (int st = ensure_scratch(c, 2, nq * sizeof(HQ), err)) return st;
+    HIPCHK(hipMemcpyAsync(c->scratch[2], queries, nq * sizeof(HQ), hipMemcpyHostToDevice, c->stream));
     for (size_t r0 = 0; r0 < count;) {
         const size_t m = chunk_end(r0) - r0;
         if (int st = ensure_scratch(c, 1, m * 16, err)) return st;
@@ -1126,7 +1126,7 @@ int anchored_batch_host_loop(bitnuc_ctx *c, size_t count, const uint64_t *querie
         uint32_t *d_query = reinterpret_cast<uint32_t *>(c->scratch[1]), *d_pos = d_query + m, *d_query2 = d_pos + m, *d_pos2 = d_query2 + m;
         uint8_t *d_dist = c->scratch[3], *d_dist2 = d_dist + m;
         const AnchorOut d = o.query2 ? AnchorOut{d_query, d_pos, d_dist, d_dist2, d_query2, d_pos2} : AnchorOut{d_query, d_pos, d_dist, nullptr, nullptr, nullptr};
-        if (int st = launch(r0, m, reinterpret_cast<const uint64_t *>(c->scratch[2]), d)) return st;
+        if (int st = launch(r0, m, reinterpret_cast<const HQ *>(c->scratch[2]), d)) return st;
         HIPCHK(hipMemcpyAsync(o.query + r0, d_query, m * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(o.pos + r0, d_pos, m * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(o.dist + r0, d_dist, m, hipMemcpyDeviceToHost, c->stream));
@@ -1719,45 +1719,54 @@ int bitnuc_kmer_hdist_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t n
     });
 }
 
+} // extern "C"
+
+// ---- the per-read matchers, written once for both query kinds (HQ: uint64_t, bitnuc_reads_hdist_*; bitnuc_pattern, bitnuc_reads_pattern_*): the entry
+// points behind them only name the instantiation, so a twin's checks, fills, chunking and launches are its exact form's line for line.
+namespace {
+
 // ---- the best match per read of a fixed-length batch ---------------------------------------------------------------------------
-int bitnuc_reads_hdist_best_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const uint64_t *d_queries, size_t n_queries,
-                                  uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err) {
+template <class HQ>
+int reads_best_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const HQ *d_queries, size_t n_queries,
+                     uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err) {
     clear_err(err);
     if (int st = check_ctx(c, err)) return st;
     bool done;
-    if (int st = check_reads(read_len, count, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist, &done, err)) return st;
+    if (int st = check_reads(read_len, count, k, d_queries, reads_qmask<HQ>(), n_queries, d_best_query, d_best_pos, d_best_dist, &done, err)) return st;
     if (done) return BITNUC_OK;
     DeviceGuard g(c->device);
     if (reads_no_windows(read_len, k, n_queries)) return reads_fill_dev(c, count, d_best_query, d_best_pos, d_best_dist, err);
     if (!d_reads) return fail(err, BITNUC_UNSUPPORTED);
     unsigned long long *slot;
     if (int st = take_slot(c, 0, &slot, err)) return st;
-    return launch_reads_best(c, d_reads, read_len, count, k, ReadsArgs{d_queries, n_queries, d_best_query, d_best_pos, d_best_dist}, slot, err);
+    return launch_reads_best(c, d_reads, read_len, count, k, ReadsArgsT<HQ>{d_queries, n_queries, d_best_query, d_best_pos, d_best_dist}, slot, err);
 }
 
-int bitnuc_reads_hdist_best_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, const uint64_t *d_queries,
-                                         size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err) {
+template <class HQ>
+int reads_best_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, const HQ *d_queries,
+                            size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err) {
     clear_err(err);
     if (int st = check_ctx(c, err)) return st;
     bool done;
-    if (int st = check_reads(read_len, count, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist, &done, err)) return st;
+    if (int st = check_reads(read_len, count, k, d_queries, reads_qmask<HQ>(), n_queries, d_best_query, d_best_pos, d_best_dist, &done, err)) return st;
     if (done) return BITNUC_OK;
     DeviceGuard g(c->device);
     if (reads_no_windows(read_len, k, n_queries)) return reads_fill_dev(c, count, d_best_query, d_best_pos, d_best_dist, err);
     if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    return launch_reads_best_packed(c, d_words, read_len, count, k, ReadsArgs{d_queries, n_queries, d_best_query, d_best_pos, d_best_dist}, err);
+    return launch_reads_best_packed(c, d_words, read_len, count, k, ReadsArgsT<HQ>{d_queries, n_queries, d_best_query, d_best_pos, d_best_dist}, err);
 }
 
-int bitnuc_reads_hdist_best(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
-                            uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err) {
+template <class HQ>
+int reads_best_host(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, const HQ *queries, size_t n_queries,
+                    uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err) {
     clear_err(err);
     bool done;
-    if (int st = check_reads(read_len, count, k, queries, n_queries, best_query, best_pos, best_dist, &done, err)) return st;
+    if (int st = check_reads(read_len, count, k, queries, reads_qmask<HQ>(), n_queries, best_query, best_pos, best_dist, &done, err)) return st;
     if (done) return BITNUC_OK;
     if (reads_no_windows(read_len, k, n_queries)) { bitnuc_host::reads_best_fill(count, best_query, best_pos, best_dist); return BITNUC_OK; }
     if (!reads) return fail(err, BITNUC_UNSUPPORTED);
     if (on_host(c, reads_work(read_len, count, k, n_queries))) {
-        const long long bad = bitnuc_host::reads_hdist_best_small(reads, read_len, count, k, queries, n_queries, best_query, best_pos, best_dist);
+        const long long bad = bitnuc_host::reads_hdist_best_small(reads, read_len, count, k, host_queries(queries), n_queries, best_query, best_pos, best_dist);
         if (bad >= 0) {
             if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = reads[bad]; err->index = (uint64_t)bad; }
             return BITNUC_INVALID_BASE;
@@ -1769,7 +1778,7 @@ int bitnuc_reads_hdist_best(bitnuc_ctx *c, const uint8_t *reads, size_t read_len
     if (int st = flush_pending(c, err)) return st;
     const size_t per = read_len < kHostChunk ? kHostChunk / read_len : 1, pm = count < per ? count : per; // whole reads per chunk
     if (int st = ensure_scratch(c, 0, pm * read_len + 64, err)) return st;
-    return reads_host_loop(c, count, per, queries, n_queries, best_query, best_pos, best_dist, err, [&](size_t r0, size_t m, const ReadsArgs &a) {
+    return reads_host_loop(c, count, per, queries, n_queries, best_query, best_pos, best_dist, err, [&](size_t r0, size_t m, const ReadsArgsT<HQ> &a) {
         HIPCHK(hipMemcpyAsync(c->scratch[0], reads + r0 * read_len, m * read_len, hipMemcpyHostToDevice, c->stream));
         unsigned long long *slot;
         if (int st = take_slot(c, r0 * read_len, &slot, err)) return st;
@@ -1777,16 +1786,17 @@ int bitnuc_reads_hdist_best(bitnuc_ctx *c, const uint8_t *reads, size_t read_len
     });
 }
 
-int bitnuc_reads_hdist_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
-                                   uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err) {
+template <class HQ>
+int reads_best_packed_host(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, const HQ *queries, size_t n_queries,
+                           uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err) {
     clear_err(err);
     bool done;
-    if (int st = check_reads(read_len, count, k, queries, n_queries, best_query, best_pos, best_dist, &done, err)) return st;
+    if (int st = check_reads(read_len, count, k, queries, reads_qmask<HQ>(), n_queries, best_query, best_pos, best_dist, &done, err)) return st;
     if (done) return BITNUC_OK;
     if (reads_no_windows(read_len, k, n_queries)) { bitnuc_host::reads_best_fill(count, best_query, best_pos, best_dist); return BITNUC_OK; }
     if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
     if (on_host(c, reads_work(read_len, count, k, n_queries))) {
-        bitnuc_host::reads_hdist_best_packed_small(words, read_len, count, k, queries, n_queries, best_query, best_pos, best_dist);
+        bitnuc_host::reads_hdist_best_packed_small(words, read_len, count, k, host_queries(queries), n_queries, best_query, best_pos, best_dist);
         return BITNUC_OK;
     }
     if (int st = check_ctx(c, err)) return st;
@@ -1795,20 +1805,21 @@ int bitnuc_reads_hdist_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t 
     const size_t wpr = words_for(read_len);
     const size_t per = wpr < kPackedChunkWords ? kPackedChunkWords / wpr : 1, pm = count < per ? count : per; // whole reads per chunk
     if (int st = ensure_scratch(c, 0, pm * wpr * 8, err)) return st;
-    return reads_host_loop(c, count, per, queries, n_queries, best_query, best_pos, best_dist, err, [&](size_t r0, size_t m, const ReadsArgs &a) {
+    return reads_host_loop(c, count, per, queries, n_queries, best_query, best_pos, best_dist, err, [&](size_t r0, size_t m, const ReadsArgsT<HQ> &a) {
         HIPCHK(hipMemcpyAsync(c->scratch[0], words + r0 * wpr, m * wpr * 8, hipMemcpyHostToDevice, c->stream));
         return launch_reads_best_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), read_len, m, k, a, err);
     });
 }
 
 // ---- the best match and the runner-up per read of a fixed-length batch ---------------------------------------------------------------
-int bitnuc_reads_hdist_best2_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const uint64_t *d_queries, size_t n_queries,
-                                   uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_pos,
+template <class HQ>
+int reads_best2_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const HQ *d_queries, size_t n_queries,
+                      uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_pos,
                                    uint8_t *d_second_dist, bitnuc_err *err) {
     clear_err(err);
     if (int st = check_ctx(c, err)) return st;
     bool done;
-    if (int st = check_reads(read_len, count, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist, &done, err)) return st;
+    if (int st = check_reads(read_len, count, k, d_queries, reads_qmask<HQ>(), n_queries, d_best_query, d_best_pos, d_best_dist, &done, err)) return st;
     if (done) return BITNUC_OK;
     if (int st = check_reads_second(d_second_query, d_second_pos, d_second_dist, err)) return st;
     DeviceGuard g(c->device);
@@ -1820,16 +1831,17 @@ int bitnuc_reads_hdist_best2_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t
     unsigned long long *slot;
     if (int st = take_slot(c, 0, &slot, err)) return st;
     const ReadsSecond b{d_second_query, d_second_pos, d_second_dist};
-    return launch_reads_best(c, d_reads, read_len, count, k, ReadsArgs{d_queries, n_queries, d_best_query, d_best_pos, d_best_dist}, slot, err, &b);
+    return launch_reads_best(c, d_reads, read_len, count, k, ReadsArgsT<HQ>{d_queries, n_queries, d_best_query, d_best_pos, d_best_dist}, slot, err, &b);
 }
 
-int bitnuc_reads_hdist_best2_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, const uint64_t *d_queries,
-                                          size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, uint32_t *d_second_query,
+template <class HQ>
+int reads_best2_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, const HQ *d_queries,
+                             size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, uint32_t *d_second_query,
                                           uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err) {
     clear_err(err);
     if (int st = check_ctx(c, err)) return st;
     bool done;
-    if (int st = check_reads(read_len, count, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist, &done, err)) return st;
+    if (int st = check_reads(read_len, count, k, d_queries, reads_qmask<HQ>(), n_queries, d_best_query, d_best_pos, d_best_dist, &done, err)) return st;
     if (done) return BITNUC_OK;
     if (int st = check_reads_second(d_second_query, d_second_pos, d_second_dist, err)) return st;
     DeviceGuard g(c->device);
@@ -1839,15 +1851,16 @@ int bitnuc_reads_hdist_best2_packed_async(bitnuc_ctx *c, const uint64_t *d_words
     }
     if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
     const ReadsSecond b{d_second_query, d_second_pos, d_second_dist};
-    return launch_reads_best_packed(c, d_words, read_len, count, k, ReadsArgs{d_queries, n_queries, d_best_query, d_best_pos, d_best_dist}, err, &b);
+    return launch_reads_best_packed(c, d_words, read_len, count, k, ReadsArgsT<HQ>{d_queries, n_queries, d_best_query, d_best_pos, d_best_dist}, err, &b);
 }
 
-int bitnuc_reads_hdist_best2(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
-                             uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos, uint8_t *second_dist,
+template <class HQ>
+int reads_best2_host(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, const HQ *queries, size_t n_queries,
+                     uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos, uint8_t *second_dist,
                              bitnuc_err *err) {
     clear_err(err);
     bool done;
-    if (int st = check_reads(read_len, count, k, queries, n_queries, best_query, best_pos, best_dist, &done, err)) return st;
+    if (int st = check_reads(read_len, count, k, queries, reads_qmask<HQ>(), n_queries, best_query, best_pos, best_dist, &done, err)) return st;
     if (done) return BITNUC_OK;
     if (int st = check_reads_second(second_query, second_pos, second_dist, err)) return st;
     if (reads_no_windows(read_len, k, n_queries)) {
@@ -1857,7 +1870,7 @@ int bitnuc_reads_hdist_best2(bitnuc_ctx *c, const uint8_t *reads, size_t read_le
     }
     if (!reads) return fail(err, BITNUC_UNSUPPORTED);
     if (on_host(c, reads_work(read_len, count, k, n_queries))) {
-        const long long bad = bitnuc_host::reads_hdist_best2_small(reads, read_len, count, k, queries, n_queries, best_query, best_pos, best_dist, second_query,
+        const long long bad = bitnuc_host::reads_hdist_best2_small(reads, read_len, count, k, host_queries(queries), n_queries, best_query, best_pos, best_dist, second_query,
                                                                    second_pos, second_dist);
         if (bad >= 0) {
             if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = reads[bad]; err->index = (uint64_t)bad; }
@@ -1871,7 +1884,7 @@ int bitnuc_reads_hdist_best2(bitnuc_ctx *c, const uint8_t *reads, size_t read_le
     const size_t per = read_len < kHostChunk ? kHostChunk / read_len : 1, pm = count < per ? count : per; // whole reads per chunk
     if (int st = ensure_scratch(c, 0, pm * read_len + 64, err)) return st;
     return reads_host_loop2(c, count, per, queries, n_queries, best_query, best_pos, best_dist, second_query, second_pos, second_dist, err,
-                            [&](size_t r0, size_t m, const ReadsArgs &a, const ReadsSecond &b) {
+                            [&](size_t r0, size_t m, const ReadsArgsT<HQ> &a, const ReadsSecond &b) {
         HIPCHK(hipMemcpyAsync(c->scratch[0], reads + r0 * read_len, m * read_len, hipMemcpyHostToDevice, c->stream));
         unsigned long long *slot;
         if (int st = take_slot(c, r0 * read_len, &slot, err)) return st;
@@ -1879,12 +1892,13 @@ int bitnuc_reads_hdist_best2(bitnuc_ctx *c, const uint8_t *reads, size_t read_le
     });
 }
 
-int bitnuc_reads_hdist_best2_packed(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
-                                    uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos,
+template <class HQ>
+int reads_best2_packed_host(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, const HQ *queries, size_t n_queries,
+                            uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos,
                                     uint8_t *second_dist, bitnuc_err *err) {
     clear_err(err);
     bool done;
-    if (int st = check_reads(read_len, count, k, queries, n_queries, best_query, best_pos, best_dist, &done, err)) return st;
+    if (int st = check_reads(read_len, count, k, queries, reads_qmask<HQ>(), n_queries, best_query, best_pos, best_dist, &done, err)) return st;
     if (done) return BITNUC_OK;
     if (int st = check_reads_second(second_query, second_pos, second_dist, err)) return st;
     if (reads_no_windows(read_len, k, n_queries)) {
@@ -1894,7 +1908,7 @@ int bitnuc_reads_hdist_best2_packed(bitnuc_ctx *c, const uint64_t *words, size_t
     }
     if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
     if (on_host(c, reads_work(read_len, count, k, n_queries))) {
-        bitnuc_host::reads_hdist_best2_packed_small(words, read_len, count, k, queries, n_queries, best_query, best_pos, best_dist, second_query, second_pos,
+        bitnuc_host::reads_hdist_best2_packed_small(words, read_len, count, k, host_queries(queries), n_queries, best_query, best_pos, best_dist, second_query, second_pos,
                                                     second_dist);
         return BITNUC_OK;
     }
@@ -1905,22 +1919,23 @@ int bitnuc_reads_hdist_best2_packed(bitnuc_ctx *c, const uint64_t *words, size_t
     const size_t per = wpr < kPackedChunkWords ? kPackedChunkWords / wpr : 1, pm = count < per ? count : per; // whole reads per chunk
     if (int st = ensure_scratch(c, 0, pm * wpr * 8, err)) return st;
     return reads_host_loop2(c, count, per, queries, n_queries, best_query, best_pos, best_dist, second_query, second_pos, second_dist, err,
-                            [&](size_t r0, size_t m, const ReadsArgs &a, const ReadsSecond &b) {
+                            [&](size_t r0, size_t m, const ReadsArgsT<HQ> &a, const ReadsSecond &b) {
         HIPCHK(hipMemcpyAsync(c->scratch[0], words + r0 * wpr, m * wpr * 8, hipMemcpyHostToDevice, c->stream));
         return launch_reads_best_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), read_len, m, k, a, err, &b);
     });
 }
 
 // ---- the anchored best match and runner-up per read of a fixed-length batch -------------------------------------------------------------
-int bitnuc_reads_hdist_anchored_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
-                                      const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist,
+template <class HQ>
+int reads_anchored_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                         const HQ *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist,
                                       uint32_t *d_second_query, uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err) {
     clear_err(err);
     if (int st = check_ctx(c, err)) return st;
     const AnchorOut o{d_best_query, d_best_pos, d_best_dist, d_second_dist, d_second_query, d_second_pos};
     bool done;
     size_t offsets;
-    if (int st = check_anchored(read_len, count, k, pos_lo, pos_hi, d_queries, n_queries, o, &done, &offsets, err)) return st;
+    if (int st = check_anchored(read_len, count, k, pos_lo, pos_hi, d_queries, reads_qmask<HQ>(), n_queries, o, &done, &offsets, err)) return st;
     if (done) return BITNUC_OK;
     DeviceGuard g(c->device);
     if (!offsets) return anchored_fill_dev(c, count, o, err);
@@ -1930,15 +1945,16 @@ int bitnuc_reads_hdist_anchored_async(bitnuc_ctx *c, const uint8_t *d_reads, siz
     return launch_reads_anchored<false>(c, d_reads, read_len, count, k, pos_lo, offsets, d_queries, n_queries, o, slot, err);
 }
 
-int bitnuc_reads_hdist_anchored_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
-                                             const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist,
+template <class HQ>
+int reads_anchored_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                const HQ *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist,
                                              uint32_t *d_second_query, uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err) {
     clear_err(err);
     if (int st = check_ctx(c, err)) return st;
     const AnchorOut o{d_best_query, d_best_pos, d_best_dist, d_second_dist, d_second_query, d_second_pos};
     bool done;
     size_t offsets;
-    if (int st = check_anchored(read_len, count, k, pos_lo, pos_hi, d_queries, n_queries, o, &done, &offsets, err)) return st;
+    if (int st = check_anchored(read_len, count, k, pos_lo, pos_hi, d_queries, reads_qmask<HQ>(), n_queries, o, &done, &offsets, err)) return st;
     if (done) return BITNUC_OK;
     DeviceGuard g(c->device);
     if (!offsets) return anchored_fill_dev(c, count, o, err);
@@ -1946,19 +1962,20 @@ int bitnuc_reads_hdist_anchored_packed_async(bitnuc_ctx *c, const uint64_t *d_wo
     return launch_reads_anchored<true>(c, d_words, words_for(read_len), count, k, pos_lo, offsets, d_queries, n_queries, o, nullptr, err);
 }
 
-int bitnuc_reads_hdist_anchored(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi, const uint64_t *queries,
-                                size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos,
+template <class HQ>
+int reads_anchored_host(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi, const HQ *queries,
+                        size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos,
                                 uint8_t *second_dist, bitnuc_err *err) {
     clear_err(err);
     const AnchorOut o{best_query, best_pos, best_dist, second_dist, second_query, second_pos};
     bool done;
     size_t offsets;
-    if (int st = check_anchored(read_len, count, k, pos_lo, pos_hi, queries, n_queries, o, &done, &offsets, err)) return st;
+    if (int st = check_anchored(read_len, count, k, pos_lo, pos_hi, queries, reads_qmask<HQ>(), n_queries, o, &done, &offsets, err)) return st;
     if (done) return BITNUC_OK;
     if (!offsets) { anchored_fill_host(count, o); return BITNUC_OK; }
     if (!reads) return fail(err, BITNUC_UNSUPPORTED);
     if (on_host(c, anchored_work(offsets, count, n_queries))) {
-        const long long bad = bitnuc_host::reads_hdist_anchored_small(reads, read_len, count, k, pos_lo, offsets, queries, n_queries, best_query, best_pos, best_dist,
+        const long long bad = bitnuc_host::reads_hdist_anchored_small(reads, read_len, count, k, pos_lo, offsets, host_queries(queries), n_queries, best_query, best_pos, best_dist,
                                                                       second_query, second_pos, second_dist);
         if (bad >= 0) {
             if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = reads[bad]; err->index = (uint64_t)bad; }
@@ -1971,7 +1988,7 @@ int bitnuc_reads_hdist_anchored(bitnuc_ctx *c, const uint8_t *reads, size_t read
     if (int st = flush_pending(c, err)) return st;
     const size_t per = read_len < kHostChunk ? kHostChunk / read_len : 1, pm = count < per ? count : per; // whole reads per chunk
     if (int st = ensure_scratch(c, 0, pm * read_len + 64, err)) return st;
-    return anchored_host_loop(c, count, per, queries, n_queries, o, err, [&](size_t r0, size_t m, const uint64_t *d_queries, const AnchorOut &d) {
+    return anchored_host_loop(c, count, per, queries, n_queries, o, err, [&](size_t r0, size_t m, const HQ *d_queries, const AnchorOut &d) {
         HIPCHK(hipMemcpyAsync(c->scratch[0], reads + r0 * read_len, m * read_len, hipMemcpyHostToDevice, c->stream));
         unsigned long long *slot;
         if (int st = take_slot(c, r0 * read_len, &slot, err)) return st;
@@ -1979,19 +1996,20 @@ int bitnuc_reads_hdist_anchored(bitnuc_ctx *c, const uint8_t *reads, size_t read
     });
 }
 
-int bitnuc_reads_hdist_anchored_packed(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
-                                       const uint64_t *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query,
+template <class HQ>
+int reads_anchored_packed_host(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                               const HQ *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query,
                                        uint32_t *second_pos, uint8_t *second_dist, bitnuc_err *err) {
     clear_err(err);
     const AnchorOut o{best_query, best_pos, best_dist, second_dist, second_query, second_pos};
     bool done;
     size_t offsets;
-    if (int st = check_anchored(read_len, count, k, pos_lo, pos_hi, queries, n_queries, o, &done, &offsets, err)) return st;
+    if (int st = check_anchored(read_len, count, k, pos_lo, pos_hi, queries, reads_qmask<HQ>(), n_queries, o, &done, &offsets, err)) return st;
     if (done) return BITNUC_OK;
     if (!offsets) { anchored_fill_host(count, o); return BITNUC_OK; }
     if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
     if (on_host(c, anchored_work(offsets, count, n_queries))) {
-        bitnuc_host::reads_hdist_anchored_packed_small(words, read_len, count, k, pos_lo, offsets, queries, n_queries, best_query, best_pos, best_dist, second_query,
+        bitnuc_host::reads_hdist_anchored_packed_small(words, read_len, count, k, pos_lo, offsets, host_queries(queries), n_queries, best_query, best_pos, best_dist, second_query,
                                                        second_pos, second_dist);
         return BITNUC_OK;
     }
@@ -2001,22 +2019,23 @@ int bitnuc_reads_hdist_anchored_packed(bitnuc_ctx *c, const uint64_t *words, siz
     const size_t wpr = words_for(read_len);
     const size_t per = wpr < kPackedChunkWords ? kPackedChunkWords / wpr : 1, pm = count < per ? count : per; // whole reads per chunk
     if (int st = ensure_scratch(c, 0, pm * wpr * 8, err)) return st;
-    return anchored_host_loop(c, count, per, queries, n_queries, o, err, [&](size_t r0, size_t m, const uint64_t *d_queries, const AnchorOut &d) {
+    return anchored_host_loop(c, count, per, queries, n_queries, o, err, [&](size_t r0, size_t m, const HQ *d_queries, const AnchorOut &d) {
         HIPCHK(hipMemcpyAsync(c->scratch[0], words + r0 * wpr, m * wpr * 8, hipMemcpyHostToDevice, c->stream));
         return launch_reads_anchored<true>(c, c->scratch[0], wpr, m, k, pos_lo, offsets, d_queries, n_queries, d, nullptr, err);
     });
 }
 
 // ---- the anchored best match and runner-up per read of a ragged batch ----------------------------------------------------------------
-int bitnuc_reads_hdist_anchored_batch_async(bitnuc_ctx *c, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k, int anchor,
-                                            size_t pos_lo, size_t pos_hi, const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos,
+template <class HQ>
+int reads_anchored_batch_async(bitnuc_ctx *c, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k, int anchor,
+                               size_t pos_lo, size_t pos_hi, const HQ *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos,
                                             uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err) {
     clear_err(err);
     if (int st = check_ctx(c, err)) return st;
     const AnchorOut o{d_best_query, d_best_pos, d_best_dist, d_second_dist, d_second_query, d_second_pos};
     bool done;
     size_t offsets;
-    if (int st = check_anchored_batch(total_bases, total_bases, count, k, anchor, pos_lo, pos_hi, d_queries, n_queries, o, d_offsets, nullptr, false, &done, &offsets, err))
+    if (int st = check_anchored_batch(total_bases, total_bases, count, k, anchor, pos_lo, pos_hi, d_queries, reads_qmask<HQ>(), n_queries, o, d_offsets, nullptr, false, &done, &offsets, err))
         return st;
     if (done) return BITNUC_OK;
     DeviceGuard g(c->device);
@@ -2027,8 +2046,9 @@ int bitnuc_reads_hdist_anchored_batch_async(bitnuc_ctx *c, const uint8_t *d_seq,
     return launch_reads_anchored_batch<false>(c, d_seq, nullptr, d_offsets, count, k, anchor, pos_lo, offsets, d_queries, n_queries, o, slot, err);
 }
 
-int bitnuc_reads_hdist_anchored_batch_packed_async(bitnuc_ctx *c, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
-                                                   size_t total_words, size_t k, int anchor, size_t pos_lo, size_t pos_hi, const uint64_t *d_queries, size_t n_queries,
+template <class HQ>
+int reads_anchored_batch_packed_async(bitnuc_ctx *c, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
+                                      size_t total_words, size_t k, int anchor, size_t pos_lo, size_t pos_hi, const HQ *d_queries, size_t n_queries,
                                                    uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, uint32_t *d_second_query,
                                                    uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err) {
     clear_err(err);
@@ -2037,7 +2057,7 @@ int bitnuc_reads_hdist_anchored_batch_packed_async(bitnuc_ctx *c, const uint64_t
     bool done;
     size_t offsets;
     const uint64_t as_bases = total_words >= ((uint64_t)1 << 53) ? ~(uint64_t)0 : 32 * (uint64_t)total_words;
-    if (int st = check_anchored_batch(as_bases, total_words, count, k, anchor, pos_lo, pos_hi, d_queries, n_queries, o, d_word_offsets, d_offsets, true, &done, &offsets,
+    if (int st = check_anchored_batch(as_bases, total_words, count, k, anchor, pos_lo, pos_hi, d_queries, reads_qmask<HQ>(), n_queries, o, d_word_offsets, d_offsets, true, &done, &offsets,
                                       err))
         return st;
     if (done) return BITNUC_OK;
@@ -2047,21 +2067,22 @@ int bitnuc_reads_hdist_anchored_batch_packed_async(bitnuc_ctx *c, const uint64_t
     return launch_reads_anchored_batch<true>(c, d_words, d_word_offsets, d_offsets, count, k, anchor, pos_lo, offsets, d_queries, n_queries, o, nullptr, err);
 }
 
-int bitnuc_reads_hdist_anchored_batch(bitnuc_ctx *c, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, int anchor, size_t pos_lo, size_t pos_hi,
-                                      const uint64_t *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query,
+template <class HQ>
+int reads_anchored_batch_host(bitnuc_ctx *c, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, int anchor, size_t pos_lo, size_t pos_hi,
+                              const HQ *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query,
                                       uint32_t *second_pos, uint8_t *second_dist, bitnuc_err *err) {
     clear_err(err);
     const AnchorOut o{best_query, best_pos, best_dist, second_dist, second_query, second_pos};
     bool done;
     size_t width; // the range's offsets
-    if (int st = check_anchored_batch(0, 0, count, k, anchor, pos_lo, pos_hi, queries, n_queries, o, offsets, nullptr, false, &done, &width, err)) return st;
+    if (int st = check_anchored_batch(0, 0, count, k, anchor, pos_lo, pos_hi, queries, reads_qmask<HQ>(), n_queries, o, offsets, nullptr, false, &done, &width, err)) return st;
     if (done) return BITNUC_OK;
     const BatchFault f = batch_check_tables(offsets, nullptr, count);
     if (f.kind) return fail_batch_tables(f, err);
     if (anchored_batch_no_window(offsets[count], k, n_queries, width, pos_lo)) { anchored_fill_host(count, o); return BITNUC_OK; }
     if (!seq) return fail(err, BITNUC_UNSUPPORTED);
     if (on_host(c, anchored_work(width, count, n_queries))) {
-        const long long bad = bitnuc_host::reads_hdist_anchored_batch_small(seq, offsets, count, k, anchor, pos_lo, pos_hi, queries, n_queries, best_query, best_pos,
+        const long long bad = bitnuc_host::reads_hdist_anchored_batch_small(seq, offsets, count, k, anchor, pos_lo, pos_hi, host_queries(queries), n_queries, best_query, best_pos,
                                                                             best_dist, second_query, second_pos, second_dist);
         if (bad >= 0) {
             if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = seq[bad]; err->index = (uint64_t)bad; }
@@ -2076,7 +2097,7 @@ int bitnuc_reads_hdist_anchored_batch(bitnuc_ctx *c, const uint8_t *seq, const u
     return anchored_batch_host_loop(
         c, count, queries, n_queries, o, err,
         [&](size_t r0) { return batch_chunk_end(r0, count, kHostChunk, [&](size_t a, size_t b) { return offsets[b] - offsets[a]; }); },
-        [&](size_t r0, size_t m, const uint64_t *d_queries, const AnchorOut &d) {
+        [&](size_t r0, size_t m, const HQ *d_queries, const AnchorOut &d) {
             const size_t b0 = (size_t)offsets[r0], bytes = (size_t)offsets[r0 + m] - b0;
             if (anchored_batch_no_window(bytes, k, n_queries, width, pos_lo)) return anchored_fill_dev(c, m, d, err); // nothing to launch, nothing validated
             if (int st = ensure_scratch(c, 0, bytes + 64, err)) return st;
@@ -2092,21 +2113,22 @@ int bitnuc_reads_hdist_anchored_batch(bitnuc_ctx *c, const uint8_t *seq, const u
         });
 }
 
-int bitnuc_reads_hdist_anchored_batch_packed(bitnuc_ctx *c, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
-                                             int anchor, size_t pos_lo, size_t pos_hi, const uint64_t *queries, size_t n_queries, uint32_t *best_query,
+template <class HQ>
+int reads_anchored_batch_packed_host(bitnuc_ctx *c, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
+                                     int anchor, size_t pos_lo, size_t pos_hi, const HQ *queries, size_t n_queries, uint32_t *best_query,
                                              uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos, uint8_t *second_dist, bitnuc_err *err) {
     clear_err(err);
     const AnchorOut o{best_query, best_pos, best_dist, second_dist, second_query, second_pos};
     bool done;
     size_t width;
-    if (int st = check_anchored_batch(0, 0, count, k, anchor, pos_lo, pos_hi, queries, n_queries, o, word_offsets, offsets, true, &done, &width, err)) return st;
+    if (int st = check_anchored_batch(0, 0, count, k, anchor, pos_lo, pos_hi, queries, reads_qmask<HQ>(), n_queries, o, word_offsets, offsets, true, &done, &width, err)) return st;
     if (done) return BITNUC_OK;
     const BatchFault f = batch_check_tables(offsets, word_offsets, count);
     if (f.kind) return fail_batch_tables(f, err);
     if (anchored_batch_no_window(offsets[count], k, n_queries, width, pos_lo)) { anchored_fill_host(count, o); return BITNUC_OK; }
     if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
     if (on_host(c, anchored_work(width, count, n_queries))) {
-        bitnuc_host::reads_hdist_anchored_batch_packed_small(words, word_offsets, offsets, count, k, anchor, pos_lo, pos_hi, queries, n_queries, best_query, best_pos,
+        bitnuc_host::reads_hdist_anchored_batch_packed_small(words, word_offsets, offsets, count, k, anchor, pos_lo, pos_hi, host_queries(queries), n_queries, best_query, best_pos,
                                                              best_dist, second_query, second_pos, second_dist);
         return BITNUC_OK;
     }
@@ -2117,7 +2139,7 @@ int bitnuc_reads_hdist_anchored_batch_packed(bitnuc_ctx *c, const uint64_t *word
     return anchored_batch_host_loop(
         c, count, queries, n_queries, o, err,
         [&](size_t r0) { return batch_chunk_end(r0, count, kPackedChunkWords, [&](size_t a, size_t b) { return word_offsets[b] - word_offsets[a]; }); },
-        [&](size_t r0, size_t m, const uint64_t *d_queries, const AnchorOut &d) {
+        [&](size_t r0, size_t m, const HQ *d_queries, const AnchorOut &d) {
             const size_t w0 = (size_t)word_offsets[r0], nw = (size_t)word_offsets[r0 + m] - w0;
             if (nw == 0) return anchored_fill_dev(c, m, d, err);
             if (int st = ensure_scratch(c, 0, nw * 8, err)) return st;
@@ -2132,41 +2154,44 @@ int bitnuc_reads_hdist_anchored_batch_packed(bitnuc_ctx *c, const uint64_t *word
 }
 
 // ---- the best match per read of a ragged batch ------------------------------------------------------------------------------------
-int bitnuc_reads_hdist_best_batch_async(bitnuc_ctx *c, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k,
-                                        const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err) {
+template <class HQ>
+int reads_best_batch_async(bitnuc_ctx *c, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k,
+                           const HQ *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err) {
     clear_err(err);
     if (int st = check_ctx(c, err)) return st;
     bool done;
-    if (int st = check_reads_batch(total_bases, total_bases, count, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist, d_offsets, nullptr, false, &done, err)) return st;
+    if (int st = check_reads_batch(total_bases, total_bases, count, k, d_queries, reads_qmask<HQ>(), n_queries, d_best_query, d_best_pos, d_best_dist, d_offsets, nullptr, false, &done, err)) return st;
     if (done) return BITNUC_OK;
     DeviceGuard g(c->device);
     if (k == 0 || n_queries == 0 || total_bases < k) return reads_fill_dev(c, count, d_best_query, d_best_pos, d_best_dist, err);
     if (!d_seq) return fail(err, BITNUC_UNSUPPORTED);
     unsigned long long *slot;
     if (int st = take_slot(c, 0, &slot, err)) return st;
-    return launch_reads_batch(c, d_seq, d_offsets, count, total_bases, k, ReadsArgs{d_queries, n_queries, d_best_query, d_best_pos, d_best_dist}, slot, err);
+    return launch_reads_batch(c, d_seq, d_offsets, count, total_bases, k, ReadsArgsT<HQ>{d_queries, n_queries, d_best_query, d_best_pos, d_best_dist}, slot, err);
 }
 
-int bitnuc_reads_hdist_best_batch_packed_async(bitnuc_ctx *c, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
-                                               size_t total_words, size_t k, const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query,
+template <class HQ>
+int reads_best_batch_packed_async(bitnuc_ctx *c, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
+                                  size_t total_words, size_t k, const HQ *d_queries, size_t n_queries, uint32_t *d_best_query,
                                                uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err) {
     clear_err(err);
     if (int st = check_ctx(c, err)) return st;
     bool done;
     const uint64_t as_bases = total_words >= ((uint64_t)1 << 53) ? ~(uint64_t)0 : 32 * (uint64_t)total_words;
-    if (int st = check_reads_batch(as_bases, total_words, count, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist, d_word_offsets, d_offsets, true, &done, err)) return st;
+    if (int st = check_reads_batch(as_bases, total_words, count, k, d_queries, reads_qmask<HQ>(), n_queries, d_best_query, d_best_pos, d_best_dist, d_word_offsets, d_offsets, true, &done, err)) return st;
     if (done) return BITNUC_OK;
     DeviceGuard g(c->device);
     if (k == 0 || n_queries == 0 || total_words == 0) return reads_fill_dev(c, count, d_best_query, d_best_pos, d_best_dist, err);
     if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    return launch_reads_batch_packed(c, d_words, d_word_offsets, d_offsets, count, total_words, k, ReadsArgs{d_queries, n_queries, d_best_query, d_best_pos, d_best_dist}, err);
+    return launch_reads_batch_packed(c, d_words, d_word_offsets, d_offsets, count, total_words, k, ReadsArgsT<HQ>{d_queries, n_queries, d_best_query, d_best_pos, d_best_dist}, err);
 }
 
-int bitnuc_reads_hdist_best_batch(bitnuc_ctx *c, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
-                                  uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err) {
+template <class HQ>
+int reads_best_batch_host(bitnuc_ctx *c, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, const HQ *queries, size_t n_queries,
+                          uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err) {
     clear_err(err);
     bool done;
-    if (int st = check_reads_batch(0, 0, count, k, queries, n_queries, best_query, best_pos, best_dist, offsets, nullptr, false, &done, err)) return st;
+    if (int st = check_reads_batch(0, 0, count, k, queries, reads_qmask<HQ>(), n_queries, best_query, best_pos, best_dist, offsets, nullptr, false, &done, err)) return st;
     if (done) return BITNUC_OK;
     const BatchFault f = batch_check_tables(offsets, nullptr, count);
     if (f.kind) return fail_batch_tables(f, err);
@@ -2174,7 +2199,7 @@ int bitnuc_reads_hdist_best_batch(bitnuc_ctx *c, const uint8_t *seq, const uint6
     if (k == 0 || n_queries == 0 || total < k) { bitnuc_host::reads_best_fill(count, best_query, best_pos, best_dist); return BITNUC_OK; }
     if (!seq) return fail(err, BITNUC_UNSUPPORTED);
     if (on_host(c, multi_work(batch_windows(offsets, count, k), n_queries))) {
-        const long long bad = bitnuc_host::reads_hdist_best_batch_small(seq, offsets, count, k, queries, n_queries, best_query, best_pos, best_dist);
+        const long long bad = bitnuc_host::reads_hdist_best_batch_small(seq, offsets, count, k, host_queries(queries), n_queries, best_query, best_pos, best_dist);
         if (bad >= 0) {
             if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = seq[bad]; err->index = (uint64_t)bad; }
             return BITNUC_INVALID_BASE;
@@ -2188,7 +2213,7 @@ int bitnuc_reads_hdist_best_batch(bitnuc_ctx *c, const uint8_t *seq, const uint6
     return reads_batch_host_loop(
         c, count, queries, n_queries, best_query, best_pos, best_dist, err,
         [&](size_t r0) { return batch_chunk_end(r0, count, kHostChunk, [&](size_t a, size_t b) { return offsets[b] - offsets[a]; }); },
-        [&](size_t r0, size_t m, const ReadsArgs &a) {
+        [&](size_t r0, size_t m, const ReadsArgsT<HQ> &a) {
             const size_t b0 = (size_t)offsets[r0], bytes = (size_t)offsets[r0 + m] - b0;
             if (bytes < k) { // no window in the chunk and nothing to launch: its bytes are still validated, here
                 for (size_t i = 0; i < bytes; ++i) {
@@ -2212,18 +2237,19 @@ int bitnuc_reads_hdist_best_batch(bitnuc_ctx *c, const uint8_t *seq, const uint6
         });
 }
 
-int bitnuc_reads_hdist_best_batch_packed(bitnuc_ctx *c, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
-                                         const uint64_t *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err) {
+template <class HQ>
+int reads_best_batch_packed_host(bitnuc_ctx *c, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
+                                 const HQ *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err) {
     clear_err(err);
     bool done;
-    if (int st = check_reads_batch(0, 0, count, k, queries, n_queries, best_query, best_pos, best_dist, word_offsets, offsets, true, &done, err)) return st;
+    if (int st = check_reads_batch(0, 0, count, k, queries, reads_qmask<HQ>(), n_queries, best_query, best_pos, best_dist, word_offsets, offsets, true, &done, err)) return st;
     if (done) return BITNUC_OK;
     const BatchFault f = batch_check_tables(offsets, word_offsets, count);
     if (f.kind) return fail_batch_tables(f, err);
     if (k == 0 || n_queries == 0 || offsets[count] < k) { bitnuc_host::reads_best_fill(count, best_query, best_pos, best_dist); return BITNUC_OK; }
     if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
     if (on_host(c, multi_work(batch_windows(offsets, count, k), n_queries))) {
-        bitnuc_host::reads_hdist_best_batch_packed_small(words, word_offsets, offsets, count, k, queries, n_queries, best_query, best_pos, best_dist);
+        bitnuc_host::reads_hdist_best_batch_packed_small(words, word_offsets, offsets, count, k, host_queries(queries), n_queries, best_query, best_pos, best_dist);
         return BITNUC_OK;
     }
     if (int st = check_ctx(c, err)) return st;
@@ -2233,7 +2259,7 @@ int bitnuc_reads_hdist_best_batch_packed(bitnuc_ctx *c, const uint64_t *words, c
     return reads_batch_host_loop(
         c, count, queries, n_queries, best_query, best_pos, best_dist, err,
         [&](size_t r0) { return batch_chunk_end(r0, count, kPackedChunkWords, [&](size_t a, size_t b) { return word_offsets[b] - word_offsets[a]; }); },
-        [&](size_t r0, size_t m, const ReadsArgs &a) {
+        [&](size_t r0, size_t m, const ReadsArgsT<HQ> &a) {
             const size_t w0 = (size_t)word_offsets[r0], nw = (size_t)word_offsets[r0 + m] - w0;
             if (nw == 0) return reads_fill_dev(c, m, a.query, a.pos, a.dist, err);
             if (int st = ensure_scratch(c, 0, nw * 8, err)) return st;
@@ -2245,6 +2271,225 @@ int bitnuc_reads_hdist_best_batch_packed(bitnuc_ctx *c, const uint64_t *words, c
             const uint64_t *d_tab = reinterpret_cast<const uint64_t *>(c->scratch[4]);
             return launch_reads_batch_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), d_tab, d_tab + m + 1, m, nw, k, a, err);
         });
+}
+
+} // namespace
+
+extern "C" {
+
+// ---- the per-read entry points: every form once per query kind, each naming its instantiation of the templates above ----
+// exact queries
+int bitnuc_reads_hdist_best_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const uint64_t *d_queries, size_t n_queries,
+                                  uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err) {
+    return reads_best_async(c, d_reads, read_len, count, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist, err);
+}
+int bitnuc_reads_hdist_best_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, const uint64_t *d_queries,
+                                         size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err) {
+    return reads_best_packed_async(c, d_words, read_len, count, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist, err);
+}
+int bitnuc_reads_hdist_best(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
+                            uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err) {
+    return reads_best_host(c, reads, read_len, count, k, queries, n_queries, best_query, best_pos, best_dist, err);
+}
+int bitnuc_reads_hdist_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
+                                   uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err) {
+    return reads_best_packed_host(c, words, read_len, count, k, queries, n_queries, best_query, best_pos, best_dist, err);
+}
+int bitnuc_reads_hdist_best2_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const uint64_t *d_queries, size_t n_queries,
+                                   uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_pos,
+                                   uint8_t *d_second_dist, bitnuc_err *err) {
+    return reads_best2_async(c, d_reads, read_len, count, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist, d_second_query, d_second_pos, d_second_dist, err);
+}
+int bitnuc_reads_hdist_best2_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, const uint64_t *d_queries,
+                                          size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, uint32_t *d_second_query,
+                                          uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err) {
+    return reads_best2_packed_async(c, d_words, read_len, count, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist, d_second_query, d_second_pos,
+                                    d_second_dist, err);
+}
+int bitnuc_reads_hdist_best2(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
+                             uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos, uint8_t *second_dist,
+                             bitnuc_err *err) {
+    return reads_best2_host(c, reads, read_len, count, k, queries, n_queries, best_query, best_pos, best_dist, second_query, second_pos, second_dist, err);
+}
+int bitnuc_reads_hdist_best2_packed(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
+                                    uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos,
+                                    uint8_t *second_dist, bitnuc_err *err) {
+    return reads_best2_packed_host(c, words, read_len, count, k, queries, n_queries, best_query, best_pos, best_dist, second_query, second_pos, second_dist, err);
+}
+int bitnuc_reads_hdist_anchored_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                      const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist,
+                                      uint32_t *d_second_query, uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err) {
+    return reads_anchored_async(c, d_reads, read_len, count, k, pos_lo, pos_hi, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist, d_second_query,
+                                d_second_pos, d_second_dist, err);
+}
+int bitnuc_reads_hdist_anchored_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                             const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist,
+                                             uint32_t *d_second_query, uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err) {
+    return reads_anchored_packed_async(c, d_words, read_len, count, k, pos_lo, pos_hi, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist, d_second_query,
+                                       d_second_pos, d_second_dist, err);
+}
+int bitnuc_reads_hdist_anchored(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi, const uint64_t *queries,
+                                size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos,
+                                uint8_t *second_dist, bitnuc_err *err) {
+    return reads_anchored_host(c, reads, read_len, count, k, pos_lo, pos_hi, queries, n_queries, best_query, best_pos, best_dist, second_query, second_pos,
+                               second_dist, err);
+}
+int bitnuc_reads_hdist_anchored_packed(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                       const uint64_t *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query,
+                                       uint32_t *second_pos, uint8_t *second_dist, bitnuc_err *err) {
+    return reads_anchored_packed_host(c, words, read_len, count, k, pos_lo, pos_hi, queries, n_queries, best_query, best_pos, best_dist, second_query, second_pos,
+                                      second_dist, err);
+}
+int bitnuc_reads_hdist_anchored_batch_async(bitnuc_ctx *c, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k, int anchor,
+                                            size_t pos_lo, size_t pos_hi, const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos,
+                                            uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err) {
+    return reads_anchored_batch_async(c, d_seq, d_offsets, count, total_bases, k, anchor, pos_lo, pos_hi, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist,
+                                      d_second_query, d_second_pos, d_second_dist, err);
+}
+int bitnuc_reads_hdist_anchored_batch_packed_async(bitnuc_ctx *c, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
+                                                   size_t total_words, size_t k, int anchor, size_t pos_lo, size_t pos_hi, const uint64_t *d_queries, size_t n_queries,
+                                                   uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, uint32_t *d_second_query,
+                                                   uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err) {
+    return reads_anchored_batch_packed_async(c, d_words, d_word_offsets, d_offsets, count, total_words, k, anchor, pos_lo, pos_hi, d_queries, n_queries, d_best_query,
+                                             d_best_pos, d_best_dist, d_second_query, d_second_pos, d_second_dist, err);
+}
+int bitnuc_reads_hdist_anchored_batch(bitnuc_ctx *c, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, int anchor, size_t pos_lo, size_t pos_hi,
+                                      const uint64_t *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query,
+                                      uint32_t *second_pos, uint8_t *second_dist, bitnuc_err *err) {
+    return reads_anchored_batch_host(c, seq, offsets, count, k, anchor, pos_lo, pos_hi, queries, n_queries, best_query, best_pos, best_dist, second_query, second_pos,
+                                     second_dist, err);
+}
+int bitnuc_reads_hdist_anchored_batch_packed(bitnuc_ctx *c, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
+                                             int anchor, size_t pos_lo, size_t pos_hi, const uint64_t *queries, size_t n_queries, uint32_t *best_query,
+                                             uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos, uint8_t *second_dist, bitnuc_err *err) {
+    return reads_anchored_batch_packed_host(c, words, word_offsets, offsets, count, k, anchor, pos_lo, pos_hi, queries, n_queries, best_query, best_pos, best_dist,
+                                            second_query, second_pos, second_dist, err);
+}
+int bitnuc_reads_hdist_best_batch_async(bitnuc_ctx *c, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k,
+                                        const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err) {
+    return reads_best_batch_async(c, d_seq, d_offsets, count, total_bases, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist, err);
+}
+int bitnuc_reads_hdist_best_batch_packed_async(bitnuc_ctx *c, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
+                                               size_t total_words, size_t k, const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query,
+                                               uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err) {
+    return reads_best_batch_packed_async(c, d_words, d_word_offsets, d_offsets, count, total_words, k, d_queries, n_queries, d_best_query, d_best_pos, d_best_dist, err);
+}
+int bitnuc_reads_hdist_best_batch(bitnuc_ctx *c, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
+                                  uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err) {
+    return reads_best_batch_host(c, seq, offsets, count, k, queries, n_queries, best_query, best_pos, best_dist, err);
+}
+int bitnuc_reads_hdist_best_batch_packed(bitnuc_ctx *c, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
+                                         const uint64_t *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err) {
+    return reads_best_batch_packed_host(c, words, word_offsets, offsets, count, k, queries, n_queries, best_query, best_pos, best_dist, err);
+}
+
+// pattern queries: the twins of the twenty above
+int bitnuc_reads_pattern_best_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries,
+                                    uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err) {
+    return reads_best_async(c, d_reads, read_len, count, k, d_patterns, n_queries, d_best_query, d_best_pos, d_best_dist, err);
+}
+int bitnuc_reads_pattern_best_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, const bitnuc_pattern *d_patterns,
+                                           size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err) {
+    return reads_best_packed_async(c, d_words, read_len, count, k, d_patterns, n_queries, d_best_query, d_best_pos, d_best_dist, err);
+}
+int bitnuc_reads_pattern_best(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, const bitnuc_pattern *patterns, size_t n_queries,
+                              uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err) {
+    return reads_best_host(c, reads, read_len, count, k, patterns, n_queries, best_query, best_pos, best_dist, err);
+}
+int bitnuc_reads_pattern_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, const bitnuc_pattern *patterns, size_t n_queries,
+                                     uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err) {
+    return reads_best_packed_host(c, words, read_len, count, k, patterns, n_queries, best_query, best_pos, best_dist, err);
+}
+int bitnuc_reads_pattern_best2_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries,
+                                     uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_pos,
+                                     uint8_t *d_second_dist, bitnuc_err *err) {
+    return reads_best2_async(c, d_reads, read_len, count, k, d_patterns, n_queries, d_best_query, d_best_pos, d_best_dist, d_second_query, d_second_pos, d_second_dist, err);
+}
+int bitnuc_reads_pattern_best2_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, const bitnuc_pattern *d_patterns,
+                                            size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, uint32_t *d_second_query,
+                                            uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err) {
+    return reads_best2_packed_async(c, d_words, read_len, count, k, d_patterns, n_queries, d_best_query, d_best_pos, d_best_dist, d_second_query, d_second_pos,
+                                    d_second_dist, err);
+}
+int bitnuc_reads_pattern_best2(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, const bitnuc_pattern *patterns, size_t n_queries,
+                               uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos, uint8_t *second_dist,
+                               bitnuc_err *err) {
+    return reads_best2_host(c, reads, read_len, count, k, patterns, n_queries, best_query, best_pos, best_dist, second_query, second_pos, second_dist, err);
+}
+int bitnuc_reads_pattern_best2_packed(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, const bitnuc_pattern *patterns, size_t n_queries,
+                                      uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos,
+                                      uint8_t *second_dist, bitnuc_err *err) {
+    return reads_best2_packed_host(c, words, read_len, count, k, patterns, n_queries, best_query, best_pos, best_dist, second_query, second_pos, second_dist, err);
+}
+int bitnuc_reads_pattern_anchored_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                        const bitnuc_pattern *d_patterns, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist,
+                                        uint32_t *d_second_query, uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err) {
+    return reads_anchored_async(c, d_reads, read_len, count, k, pos_lo, pos_hi, d_patterns, n_queries, d_best_query, d_best_pos, d_best_dist, d_second_query,
+                                d_second_pos, d_second_dist, err);
+}
+int bitnuc_reads_pattern_anchored_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                               const bitnuc_pattern *d_patterns, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist,
+                                               uint32_t *d_second_query, uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err) {
+    return reads_anchored_packed_async(c, d_words, read_len, count, k, pos_lo, pos_hi, d_patterns, n_queries, d_best_query, d_best_pos, d_best_dist, d_second_query,
+                                       d_second_pos, d_second_dist, err);
+}
+int bitnuc_reads_pattern_anchored(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                  const bitnuc_pattern *patterns, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query,
+                                  uint32_t *second_pos, uint8_t *second_dist, bitnuc_err *err) {
+    return reads_anchored_host(c, reads, read_len, count, k, pos_lo, pos_hi, patterns, n_queries, best_query, best_pos, best_dist, second_query, second_pos,
+                               second_dist, err);
+}
+int bitnuc_reads_pattern_anchored_packed(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                         const bitnuc_pattern *patterns, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist,
+                                         uint32_t *second_query, uint32_t *second_pos, uint8_t *second_dist, bitnuc_err *err) {
+    return reads_anchored_packed_host(c, words, read_len, count, k, pos_lo, pos_hi, patterns, n_queries, best_query, best_pos, best_dist, second_query, second_pos,
+                                      second_dist, err);
+}
+int bitnuc_reads_pattern_anchored_batch_async(bitnuc_ctx *c, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k, int anchor,
+                                              size_t pos_lo, size_t pos_hi, const bitnuc_pattern *d_patterns, size_t n_queries, uint32_t *d_best_query,
+                                              uint32_t *d_best_pos, uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_pos, uint8_t *d_second_dist,
+                                              bitnuc_err *err) {
+    return reads_anchored_batch_async(c, d_seq, d_offsets, count, total_bases, k, anchor, pos_lo, pos_hi, d_patterns, n_queries, d_best_query, d_best_pos, d_best_dist,
+                                      d_second_query, d_second_pos, d_second_dist, err);
+}
+int bitnuc_reads_pattern_anchored_batch_packed_async(bitnuc_ctx *c, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
+                                                     size_t total_words, size_t k, int anchor, size_t pos_lo, size_t pos_hi, const bitnuc_pattern *d_patterns,
+                                                     size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, uint32_t *d_second_query,
+                                                     uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err) {
+    return reads_anchored_batch_packed_async(c, d_words, d_word_offsets, d_offsets, count, total_words, k, anchor, pos_lo, pos_hi, d_patterns, n_queries, d_best_query,
+                                             d_best_pos, d_best_dist, d_second_query, d_second_pos, d_second_dist, err);
+}
+int bitnuc_reads_pattern_anchored_batch(bitnuc_ctx *c, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, int anchor, size_t pos_lo, size_t pos_hi,
+                                        const bitnuc_pattern *patterns, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist,
+                                        uint32_t *second_query, uint32_t *second_pos, uint8_t *second_dist, bitnuc_err *err) {
+    return reads_anchored_batch_host(c, seq, offsets, count, k, anchor, pos_lo, pos_hi, patterns, n_queries, best_query, best_pos, best_dist, second_query, second_pos,
+                                     second_dist, err);
+}
+int bitnuc_reads_pattern_anchored_batch_packed(bitnuc_ctx *c, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
+                                               int anchor, size_t pos_lo, size_t pos_hi, const bitnuc_pattern *patterns, size_t n_queries, uint32_t *best_query,
+                                               uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos, uint8_t *second_dist,
+                                               bitnuc_err *err) {
+    return reads_anchored_batch_packed_host(c, words, word_offsets, offsets, count, k, anchor, pos_lo, pos_hi, patterns, n_queries, best_query, best_pos, best_dist,
+                                            second_query, second_pos, second_dist, err);
+}
+int bitnuc_reads_pattern_best_batch_async(bitnuc_ctx *c, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k,
+                                          const bitnuc_pattern *d_patterns, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist,
+                                          bitnuc_err *err) {
+    return reads_best_batch_async(c, d_seq, d_offsets, count, total_bases, k, d_patterns, n_queries, d_best_query, d_best_pos, d_best_dist, err);
+}
+int bitnuc_reads_pattern_best_batch_packed_async(bitnuc_ctx *c, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
+                                                 size_t total_words, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries, uint32_t *d_best_query,
+                                                 uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err) {
+    return reads_best_batch_packed_async(c, d_words, d_word_offsets, d_offsets, count, total_words, k, d_patterns, n_queries, d_best_query, d_best_pos, d_best_dist, err);
+}
+int bitnuc_reads_pattern_best_batch(bitnuc_ctx *c, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, const bitnuc_pattern *patterns,
+                                    size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err) {
+    return reads_best_batch_host(c, seq, offsets, count, k, patterns, n_queries, best_query, best_pos, best_dist, err);
+}
+int bitnuc_reads_pattern_best_batch_packed(bitnuc_ctx *c, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
+                                           const bitnuc_pattern *patterns, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist,
+                                           bitnuc_err *err) {
+    return reads_best_batch_packed_host(c, words, word_offsets, offsets, count, k, patterns, n_queries, best_query, best_pos, best_dist, err);
 }
 
 // ---- pattern queries: a set of bases per position (bitnuc_pattern).  The twelve entry points below are the twins of the exact ones above: the same checks

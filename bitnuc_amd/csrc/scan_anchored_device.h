@@ -23,6 +23,8 @@
 // query tiles once for both: a tile's A operand is four 16-byte loads per lane from a per-query table in context scratch (256 bytes per query: the
 // query's one-hot at entries 64 .. 64 + k - 1 of 128, so that every shift of every K-step is one unaligned 16-byte piece of it; built in-stream by
 // anchored_tables_kernel, L2-resident), and with two groups those 4 KiB feed eight matrix instructions instead of four.
+// Pattern queries (a set of bases per position, bitnuc_reads_pattern_anchored*) differ in the table alone: an entry holds -1.0 in every channel of its
+// position's set (anchored_entry), the kernel below is the same instantiations.
 // Channels: four per base (16 bases per K-step, ceil(span / 16) MFMAs per tile and group).  Three channels (T = 0, 21 bases per K-step) would save one
 // MFMA of four at spans of 49 .. 63 and one of two at 17 .. 21, at the price of a second table and operand form; not shipped.
 // Invalid ASCII bytes: ascii_residue's LUT on every piece, restricted to the span's bytes; a lane that sees one latches its first (atomicMin: the first
@@ -65,6 +67,10 @@ struct AnchorBatchGeom {
 // stays there.  Ragged: a row that is inadmissible for one read of the tile is admissible for its neighbours and has a LIVE A -- up to 32 matches would
 // take 63 down to 31, a real distance --, so the field is seven bits at bit 16 (bits 6 .. 16 were unused) and such a row starts at 127: it ends at 95 or
 // above, no real distance (<= 32) and behind every real row in the unsigned minimum.  Costs nothing in the tile loop: only constants differ.
+// Pattern queries (bitnuc_reads_pattern_anchored*): an entry may hold -1.0 in several channels, but B has ONE non-zero nibble per read base, so a
+// position still subtracts at most 1 << kShift and a row at most k <= 32 of them: the same bound.  An all-N pattern at k = 32 matches at every position
+// of every read, so its live inadmissible rows end at exactly 127 - 32 = 95: the bound is reached, not exceeded (tests/test_gpu_reads_pattern.py).
+// Bases behind a short read's span read as 'A' (anchored_piece_ascii, _packed) and match like any other: they are counted in the 32.
 template <bool RAGGED> struct AnchorField {
     static constexpr unsigned kShift = RAGGED ? 16u : 17u;        // a match subtracts 1 << kShift
     static constexpr unsigned kNone = RAGGED ? 127u : 63u;        // where an inadmissible row starts
@@ -73,14 +79,27 @@ template <bool RAGGED> struct AnchorField {
     static constexpr int kScale = 127 + (int)kShift;              // A's E8M0 scale
 };
 
-// entry i of query q: base i - 64 of the query as -1.0 in its channel's nibble (A, C, G, T from bit 0), zero outside [0, k)
-__global__ void __launch_bounds__(64) anchored_tables_kernel(const unsigned long long *__restrict__ queries, unsigned k, uint32_t *__restrict__ tabs) {
-    const unsigned long long q = queries[blockIdx.x];
+// position d < k of a query as a table entry: -1.0 (fp4 0b1010) in the nibble of every channel (A, C, G, T from bit 0) the query takes there.  An exact
+// query: its base's one nibble.  A pattern (read as four dwords): the channels c whose allow[c] has bit d set -- B is one-hot, so the product of a
+// position is -[base in S_d] and a position matches at most once; an empty set is an all-zero entry.  Bits of allow[c] at positions >= k are never
+// looked at (the caller's d < k), d = 31 is an unsigned shift.
+__device__ __forceinline__ uint32_t anchored_entry(unsigned long long q, unsigned d) { return 0xAu << (4u * (unsigned)((q >> (2u * d)) & 3u)); }
+__device__ __forceinline__ uint32_t anchored_entry(const PatternSets &p, unsigned d) {
+    uint32_t v = 0;
+#pragma unroll
+    for (unsigned c = 0; c < 4; ++c) v |= ((p.allow[c] >> d) & 1u) * (0xAu << (4u * c));
+    return v;
+}
+
+// entry i of query q: position i - 64 of the query (anchored_entry), zero outside [0, k).  Q: the query kind (QueryKind, scan_mfma_device.h)
+template <class Q>
+__global__ void __launch_bounds__(64) anchored_tables_kernel(const Q *__restrict__ queries, unsigned k, uint32_t *__restrict__ tabs) {
+    const Q q = queries[blockIdx.x];
     uint32_t v = 0;
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
         const int d = 2 * (int)threadIdx.x + e - 64;
-        if (d >= 0 && d < (int)k) v |= (0xAu << (4u * (unsigned)((q >> (2 * d)) & 3u))) << (16 * e);
+        if (d >= 0 && d < (int)k) v |= anchored_entry(q, (unsigned)d) << (16 * e);
     }
     tabs[(size_t)blockIdx.x * (kAnchorEntry / 4) + threadIdx.x] = v;
 }

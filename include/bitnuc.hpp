@@ -428,6 +428,107 @@ class Context {
             return NucleotideError::from_c(e);
         return b;
     }
+    // the per-read matchers under PATTERN queries (a set of bases per position: bitnuc_pattern_from_iupac / _from_2bit): the ten methods above with
+    // `patterns` where `queries` stood and pdist where the Hamming distance stood; ties, fills, runner-up rule and the validation of the reads unchanged
+    static ReadsBest reads_outputs(size_t count) { return ReadsBest{std::vector<uint32_t>(count), std::vector<uint32_t>(count), std::vector<uint8_t>(count)}; }
+    Result<ReadsBest> reads_pattern_best(Bytes reads, size_t read_len, size_t k, const std::vector<bitnuc_pattern> &patterns) const {
+        const size_t count = read_len ? reads.len / read_len : 0;
+        ReadsBest b = reads_outputs(count);
+        bitnuc_err e;
+        if (bitnuc_reads_pattern_best(ctx_, reads.ptr, read_len, count, k, patterns.data(), patterns.size(), b.query.data(), b.pos.data(), b.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
+    Result<ReadsBest> reads_pattern_best_packed(Words words, size_t read_len, size_t count, size_t k, const std::vector<bitnuc_pattern> &patterns) const {
+        ReadsBest b = reads_outputs(count);
+        bitnuc_err e;
+        if (bitnuc_reads_pattern_best_packed(ctx_, words.ptr, read_len, count, k, patterns.data(), patterns.size(), b.query.data(), b.pos.data(), b.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
+    Result<ReadsBest2> reads_pattern_best2(Bytes reads, size_t read_len, size_t k, const std::vector<bitnuc_pattern> &patterns) const {
+        const size_t count = read_len ? reads.len / read_len : 0;
+        ReadsBest2 b{reads_outputs(count), reads_outputs(count)};
+        bitnuc_err e;
+        if (bitnuc_reads_pattern_best2(ctx_, reads.ptr, read_len, count, k, patterns.data(), patterns.size(), b.best.query.data(), b.best.pos.data(), b.best.dist.data(),
+                                       b.second.query.data(), b.second.pos.data(), b.second.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
+    Result<ReadsBest2> reads_pattern_best2_packed(Words words, size_t read_len, size_t count, size_t k, const std::vector<bitnuc_pattern> &patterns) const {
+        ReadsBest2 b{reads_outputs(count), reads_outputs(count)};
+        bitnuc_err e;
+        if (bitnuc_reads_pattern_best2_packed(ctx_, words.ptr, read_len, count, k, patterns.data(), patterns.size(), b.best.query.data(), b.best.pos.data(),
+                                              b.best.dist.data(), b.second.query.data(), b.second.pos.data(), b.second.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
+    Result<ReadsBest2> reads_pattern_anchored(Bytes reads, size_t read_len, size_t k, const std::vector<bitnuc_pattern> &patterns, size_t pos_lo = 0,
+                                              size_t pos_hi = SIZE_MAX) const {
+        const size_t count = read_len ? reads.len / read_len : 0;
+        ReadsBest2 b{reads_outputs(count), reads_outputs(count)};
+        bitnuc_err e;
+        if (bitnuc_reads_pattern_anchored(ctx_, reads.ptr, read_len, count, k, pos_lo, pos_hi, patterns.data(), patterns.size(), b.best.query.data(), b.best.pos.data(),
+                                          b.best.dist.data(), b.second.query.data(), b.second.pos.data(), b.second.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
+    Result<ReadsBest2> reads_pattern_anchored_packed(Words words, size_t read_len, size_t count, size_t k, const std::vector<bitnuc_pattern> &patterns,
+                                                     size_t pos_lo = 0, size_t pos_hi = SIZE_MAX) const {
+        ReadsBest2 b{reads_outputs(count), reads_outputs(count)};
+        bitnuc_err e;
+        if (bitnuc_reads_pattern_anchored_packed(ctx_, words.ptr, read_len, count, k, pos_lo, pos_hi, patterns.data(), patterns.size(), b.best.query.data(),
+                                                 b.best.pos.data(), b.best.dist.data(), b.second.query.data(), b.second.pos.data(), b.second.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
+    Result<ReadsBest> reads_pattern_best_batch(Bytes seq, const std::vector<uint64_t> &offsets, size_t k, const std::vector<bitnuc_pattern> &patterns) const {
+        const size_t count = offsets.empty() ? 0 : offsets.size() - 1;
+        if (count && seq.len < offsets.back()) return NucleotideError::invalid_length(seq.len);
+        ReadsBest b = reads_outputs(count);
+        bitnuc_err e;
+        if (bitnuc_reads_pattern_best_batch(ctx_, seq.ptr, offsets.data(), count, k, patterns.data(), patterns.size(), b.query.data(), b.pos.data(), b.dist.data(), &e) !=
+            BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
+    Result<ReadsBest> reads_pattern_best_batch_packed(Words words, const std::vector<uint64_t> &word_offsets, const std::vector<uint64_t> &offsets, size_t k,
+                                                      const std::vector<bitnuc_pattern> &patterns) const {
+        const size_t count = offsets.empty() ? 0 : offsets.size() - 1;
+        if (word_offsets.size() != offsets.size()) return NucleotideError::unsupported();
+        if (count && words.len < word_offsets.back()) return NucleotideError::invalid_length(words.len);
+        ReadsBest b = reads_outputs(count);
+        bitnuc_err e;
+        if (bitnuc_reads_pattern_best_batch_packed(ctx_, words.ptr, word_offsets.data(), offsets.data(), count, k, patterns.data(), patterns.size(), b.query.data(),
+                                                   b.pos.data(), b.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
+    Result<ReadsBest2> reads_pattern_anchored_batch(Bytes seq, const std::vector<uint64_t> &offsets, size_t k, const std::vector<bitnuc_pattern> &patterns,
+                                                    size_t pos_lo = 0, size_t pos_hi = 0, int anchor = BITNUC_ANCHOR_START) const {
+        const size_t count = offsets.empty() ? 0 : offsets.size() - 1;
+        if (count && seq.len < offsets.back()) return NucleotideError::invalid_length(seq.len);
+        ReadsBest2 b{reads_outputs(count), reads_outputs(count)};
+        bitnuc_err e;
+        if (bitnuc_reads_pattern_anchored_batch(ctx_, seq.ptr, offsets.data(), count, k, anchor, pos_lo, pos_hi, patterns.data(), patterns.size(), b.best.query.data(),
+                                                b.best.pos.data(), b.best.dist.data(), b.second.query.data(), b.second.pos.data(), b.second.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
+    Result<ReadsBest2> reads_pattern_anchored_batch_packed(Words words, const std::vector<uint64_t> &word_offsets, const std::vector<uint64_t> &offsets, size_t k,
+                                                           const std::vector<bitnuc_pattern> &patterns, size_t pos_lo = 0, size_t pos_hi = 0,
+                                                           int anchor = BITNUC_ANCHOR_START) const {
+        const size_t count = offsets.empty() ? 0 : offsets.size() - 1;
+        if (word_offsets.size() != offsets.size()) return NucleotideError::unsupported();
+        if (count && words.len < word_offsets.back()) return NucleotideError::invalid_length(words.len);
+        ReadsBest2 b{reads_outputs(count), reads_outputs(count)};
+        bitnuc_err e;
+        if (bitnuc_reads_pattern_anchored_batch_packed(ctx_, words.ptr, word_offsets.data(), offsets.data(), count, k, anchor, pos_lo, pos_hi, patterns.data(),
+                                                       patterns.size(), b.best.query.data(), b.best.pos.data(), b.best.dist.data(), b.second.query.data(),
+                                                       b.second.pos.data(), b.second.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
     Result<std::vector<uint64_t>> kmer_hdist_hits_packed(Words words, size_t n, size_t k, uint64_t query, unsigned tau, std::vector<uint8_t> *hit_dist = nullptr) const {
         uint64_t total = 0;
         bitnuc_err e;

@@ -451,7 +451,7 @@ int bitnuc_reads_hdist_best_packed(bitnuc_ctx *ctx, const uint64_t *words, size_
  * Cost: two passes over the reads in one call (the best match's kernels, then their exclusion form that leaves out each read's winning query, then
  * one kernel for the six outputs), none with one query.  Measured against bitnuc_reads_hdist_best*_async on the same data (6,666,667 x 150-base
  * reads, k = 31, one MI355X; profiles/r14_reads_best2.json): 2.02 - 2.03 x its time at 8, 64 and 512 queries, 1.05 x at one.
- * Out of scope: the ragged twins (*_best_batch*), pattern twins, a per-read exclusion list as an argument, more than two ranks. */
+ * The pattern twins: bitnuc_reads_pattern_best2* below.  Out of scope: the ragged twins (*_best_batch*), a per-read exclusion list as an argument, more than two ranks. */
 int bitnuc_reads_hdist_best2_async(bitnuc_ctx *ctx, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const uint64_t *d_queries, size_t n_queries,
                                    uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_pos,
                                    uint8_t *d_second_dist, bitnuc_err *err);
@@ -503,7 +503,7 @@ int bitnuc_reads_hdist_best2_packed(bitnuc_ctx *ctx, const uint64_t *words, size
  * (profiles/r15_reads_anchored.json), ASCII / packed with the second triple: k = 16, four offsets: 0.28 / 0.20 ms at 1 query, 0.27 / 0.19 at 8, 0.56 /
  * 0.46 at 64, 2.8 / 2.6 at 512; one offset: 0.25 / 0.17, 0.25 / 0.17, 0.27 / 0.20, 0.90 / 0.77 ms; 0.003 - 0.84 x the time of a copy of the spans plus
  * bitnuc_reads_hdist_best2*_async on it.
- * The ragged twins: bitnuc_reads_hdist_anchored_batch* below.  Out of scope: pattern (IUPAC) queries, a per-read offset table, spans above 64 bases, reverse-complement queries (callers add the
+ * The ragged twins: bitnuc_reads_hdist_anchored_batch* below; the pattern (IUPAC) twins: bitnuc_reads_pattern_anchored*.  Out of scope: a per-read offset table, spans above 64 bases, reverse-complement queries (callers add the
  * reverse complements to the query list themselves). */
 #define BITNUC_ANCHOR_MAX_SPAN 64
 int bitnuc_reads_hdist_anchored_async(bitnuc_ctx *ctx, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
@@ -559,8 +559,8 @@ int bitnuc_reads_hdist_anchored_packed(bitnuc_ctx *ctx, const uint64_t *words, s
  * 0.32 / 0.28 at 64, 0.95 / 0.91 at 512; four offsets: 0.33 / 0.29, 0.30 / 0.27, 0.62 / 0.58, 2.90 / 2.88 ms; 0.17 - 0.83 x the time of a device gather of the
  * spans into a compact batch plus bitnuc_reads_hdist_anchored*_async on it, at every measured point.  On equal-length reads the fixed form above gives the
  * same answers in less time (this form takes 1.02 - 1.45 x of it, 0.03 - 0.27 ms more): a fixed-length batch belongs there.
- * Out of scope: pattern (IUPAC) queries, a per-read offset table as an argument, spans above 64 bases, reverse-complement queries, a whole-read ragged
- * best2. */
+ * The pattern (IUPAC) twins: bitnuc_reads_pattern_anchored_batch* below.  Out of scope: a per-read offset table as an argument, spans above 64 bases,
+ * reverse-complement queries, a whole-read ragged best2. */
 #define BITNUC_ANCHOR_START 0
 #define BITNUC_ANCHOR_END 1
 int bitnuc_reads_hdist_anchored_batch_async(bitnuc_ctx *ctx, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k, int anchor,
@@ -619,6 +619,83 @@ int bitnuc_reads_hdist_best_batch(bitnuc_ctx *ctx, const uint8_t *seq, const uin
                                   uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err);
 int bitnuc_reads_hdist_best_batch_packed(bitnuc_ctx *ctx, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
                                          const uint64_t *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err);
+
+/* ---- PATTERN (IUPAC) queries for the per-read matchers: inline barcodes with N (UMI) positions, degenerate primers (R Y M K W ...), index reads with a
+ * masked cycle, guide + NGG -- one pattern per barcode / primer instead of all its exact instances ----
+ * pdist(window) = #{ i < k : window[i] not in S_i } for a pattern with sets S_i: bitnuc_pattern's definition, unchanged (bits of allow[c] at positions
+ * >= k are ignored; an empty set mismatches every base and is legal; an all-N pattern has distance 0 at every window).
+ * Each of the twenty entry points below is its exact twin's contract WORD FOR WORD with three substitutions: `const bitnuc_pattern *patterns`
+ * (n_queries of them) stands where `const uint64_t *queries` stood; "patterns NULL with n_queries > 0, or not 4-byte aligned" where "queries NULL ... or
+ * not 8-byte aligned" stood; pdist where hdist_scalar stood.  Everything else is the twin's: the checks in the same order, the same fills (UINT32_MAX,
+ * UINT32_MAX, 0xFF), the same BITNUC_MAX_QUERIES, ties by the smallest query index and then the smallest offset, the same validation of the READS (the
+ * sets are on the query's side only: an N in a read is still INVALID_BASE), the same chunking of the host forms above the host cutoff, the same context
+ * scratch and hipGraph contract of the _async forms (d_patterns is read on the device at every replay).  Runner-up: two equal patterns are two
+ * queries (the one at the higher index is the runner-up at the same distance); a second window of the winner never is.  A list of singleton patterns
+ * (bitnuc_pattern_from_2bit) gives the exact twin's outputs byte for byte.
+ * Cost: the twins' kernels; only the per-query tables are built from 16 instead of 8 bytes per query (profiles/r17_reads_pattern.json). */
+/* the twins of bitnuc_reads_hdist_best* */
+int bitnuc_reads_pattern_best_async(bitnuc_ctx *ctx, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries,
+                                    uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_best_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t read_len, size_t count, size_t k, const bitnuc_pattern *d_patterns,
+                                           size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_best(bitnuc_ctx *ctx, const uint8_t *reads, size_t read_len, size_t count, size_t k, const bitnuc_pattern *patterns, size_t n_queries,
+                              uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_best_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t read_len, size_t count, size_t k, const bitnuc_pattern *patterns, size_t n_queries,
+                                     uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err);
+/* the twins of bitnuc_reads_hdist_best2* */
+int bitnuc_reads_pattern_best2_async(bitnuc_ctx *ctx, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries,
+                                     uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_pos,
+                                     uint8_t *d_second_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_best2_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t read_len, size_t count, size_t k, const bitnuc_pattern *d_patterns,
+                                            size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, uint32_t *d_second_query,
+                                            uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_best2(bitnuc_ctx *ctx, const uint8_t *reads, size_t read_len, size_t count, size_t k, const bitnuc_pattern *patterns, size_t n_queries,
+                               uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos, uint8_t *second_dist,
+                               bitnuc_err *err);
+int bitnuc_reads_pattern_best2_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t read_len, size_t count, size_t k, const bitnuc_pattern *patterns, size_t n_queries,
+                                      uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos,
+                                      uint8_t *second_dist, bitnuc_err *err);
+/* the twins of bitnuc_reads_hdist_anchored*: the same matrix-core GEMM; a pattern's table entry holds -1.0 in every channel of its position's set */
+int bitnuc_reads_pattern_anchored_async(bitnuc_ctx *ctx, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                        const bitnuc_pattern *d_patterns, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist,
+                                        uint32_t *d_second_query, uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_anchored_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                               const bitnuc_pattern *d_patterns, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist,
+                                               uint32_t *d_second_query, uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_anchored(bitnuc_ctx *ctx, const uint8_t *reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                  const bitnuc_pattern *patterns, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query,
+                                  uint32_t *second_pos, uint8_t *second_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_anchored_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                         const bitnuc_pattern *patterns, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist,
+                                         uint32_t *second_query, uint32_t *second_pos, uint8_t *second_dist, bitnuc_err *err);
+/* the twins of bitnuc_reads_hdist_anchored_batch* */
+int bitnuc_reads_pattern_anchored_batch_async(bitnuc_ctx *ctx, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k, int anchor,
+                                              size_t pos_lo, size_t pos_hi, const bitnuc_pattern *d_patterns, size_t n_queries, uint32_t *d_best_query,
+                                              uint32_t *d_best_pos, uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_pos, uint8_t *d_second_dist,
+                                              bitnuc_err *err);
+int bitnuc_reads_pattern_anchored_batch_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
+                                                     size_t total_words, size_t k, int anchor, size_t pos_lo, size_t pos_hi, const bitnuc_pattern *d_patterns,
+                                                     size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, uint32_t *d_second_query,
+                                                     uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_anchored_batch(bitnuc_ctx *ctx, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, int anchor, size_t pos_lo, size_t pos_hi,
+                                        const bitnuc_pattern *patterns, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist,
+                                        uint32_t *second_query, uint32_t *second_pos, uint8_t *second_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_anchored_batch_packed(bitnuc_ctx *ctx, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
+                                               int anchor, size_t pos_lo, size_t pos_hi, const bitnuc_pattern *patterns, size_t n_queries, uint32_t *best_query,
+                                               uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos, uint8_t *second_dist,
+                                               bitnuc_err *err);
+/* the twins of bitnuc_reads_hdist_best_batch* */
+int bitnuc_reads_pattern_best_batch_async(bitnuc_ctx *ctx, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k,
+                                          const bitnuc_pattern *d_patterns, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist,
+                                          bitnuc_err *err);
+int bitnuc_reads_pattern_best_batch_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
+                                                 size_t total_words, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries, uint32_t *d_best_query,
+                                                 uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_best_batch(bitnuc_ctx *ctx, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, const bitnuc_pattern *patterns,
+                                    size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_best_batch_packed(bitnuc_ctx *ctx, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
+                                           const bitnuc_pattern *patterns, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist,
+                                           bitnuc_err *err);
 
 /* ---- analysis on packed words (the callers just above the codec) ------ */
 /* BaseCount::base_counts / GCContent::gc_content of a packed sequence

@@ -506,6 +506,136 @@ pub fn pattern_from_2bit(query: u64, k: usize) -> Result<Pattern, NucleotideErro
     if st == ffi::BITNUC_OK { Ok(p) } else { Err(to_err(&e)) }
 }
 
+/// `reads_hdist_best` under pattern queries: the distance of a window is `pdist`, the number of positions whose base is not in the pattern's set.
+/// Ties go to the smallest pattern index, then the smallest offset; an `N` in a read is still an invalid base.
+pub fn reads_pattern_best(reads: &[u8], read_len: usize, k: usize, patterns: &[Pattern]) -> Result<(Vec<u32>, Vec<u32>, Vec<u8>), NucleotideError> {
+    let count = if read_len == 0 { 0 } else { reads.len() / read_len };
+    let (mut query, mut pos, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_pattern_best(c, reads.as_ptr(), read_len, count, k, patterns.as_ptr(), patterns.len(), query.as_mut_ptr(), pos.as_mut_ptr(), dist.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok((query, pos, dist)) } else { Err(to_err(&e)) }
+}
+
+/// `reads_pattern_best` of the packed words `encode_fixed` writes (`ceil(read_len / 32)` words per read), without decoding them.
+pub fn reads_pattern_best_packed(words: &[u64], read_len: usize, count: usize, k: usize, patterns: &[Pattern]) -> Result<(Vec<u32>, Vec<u32>, Vec<u8>), NucleotideError> {
+    assert!(words.len() >= count * ((read_len + 31) / 32), "count reads of ceil(read_len / 32) words each");
+    let (mut query, mut pos, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_pattern_best_packed(c, words.as_ptr(), read_len, count, k, patterns.as_ptr(), patterns.len(), query.as_mut_ptr(), pos.as_mut_ptr(), dist.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok((query, pos, dist)) } else { Err(to_err(&e)) }
+}
+
+/// `reads_hdist_best2` under pattern queries: two equal patterns are two queries (the second is the runner-up), another window of the winner never is.
+pub fn reads_pattern_best2(reads: &[u8], read_len: usize, k: usize, patterns: &[Pattern]) -> Result<ReadsBest2, NucleotideError> {
+    let count = if read_len == 0 { 0 } else { reads.len() / read_len };
+    let (mut query, mut pos, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let (mut query2, mut pos2, mut dist2) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_pattern_best2(c, reads.as_ptr(), read_len, count, k, patterns.as_ptr(), patterns.len(), query.as_mut_ptr(), pos.as_mut_ptr(), dist.as_mut_ptr(),
+                                        query2.as_mut_ptr(), pos2.as_mut_ptr(), dist2.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(((query, pos, dist), (query2, pos2, dist2))) } else { Err(to_err(&e)) }
+}
+
+/// `reads_pattern_best2` of the packed words `encode_fixed` writes, without decoding them.
+pub fn reads_pattern_best2_packed(words: &[u64], read_len: usize, count: usize, k: usize, patterns: &[Pattern]) -> Result<ReadsBest2, NucleotideError> {
+    assert!(words.len() >= count * ((read_len + 31) / 32), "count reads of ceil(read_len / 32) words each");
+    let (mut query, mut pos, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let (mut query2, mut pos2, mut dist2) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_pattern_best2_packed(c, words.as_ptr(), read_len, count, k, patterns.as_ptr(), patterns.len(), query.as_mut_ptr(), pos.as_mut_ptr(), dist.as_mut_ptr(),
+                                               query2.as_mut_ptr(), pos2.as_mut_ptr(), dist2.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(((query, pos, dist), (query2, pos2, dist2))) } else { Err(to_err(&e)) }
+}
+
+/// `reads_hdist_anchored` under pattern queries (the offsets `pos_lo <= i <= min(pos_hi, read_len - k)`; `pos_hi = None`: to the end of the read).
+pub fn reads_pattern_anchored(reads: &[u8], read_len: usize, k: usize, pos_lo: usize, pos_hi: Option<usize>, patterns: &[Pattern]) -> Result<ReadsBest2, NucleotideError> {
+    let count = if read_len == 0 { 0 } else { reads.len() / read_len };
+    let (mut query, mut pos, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let (mut query2, mut pos2, mut dist2) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_pattern_anchored(c, reads.as_ptr(), read_len, count, k, pos_lo, pos_hi.unwrap_or(usize::MAX), patterns.as_ptr(), patterns.len(), query.as_mut_ptr(),
+                                           pos.as_mut_ptr(), dist.as_mut_ptr(), query2.as_mut_ptr(), pos2.as_mut_ptr(), dist2.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(((query, pos, dist), (query2, pos2, dist2))) } else { Err(to_err(&e)) }
+}
+
+/// `reads_pattern_anchored` of the packed words `encode_fixed` writes, without decoding them.
+pub fn reads_pattern_anchored_packed(words: &[u64], read_len: usize, count: usize, k: usize, pos_lo: usize, pos_hi: Option<usize>, patterns: &[Pattern]) -> Result<ReadsBest2, NucleotideError> {
+    assert!(words.len() >= count * ((read_len + 31) / 32), "count reads of ceil(read_len / 32) words each");
+    let (mut query, mut pos, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let (mut query2, mut pos2, mut dist2) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_pattern_anchored_packed(c, words.as_ptr(), read_len, count, k, pos_lo, pos_hi.unwrap_or(usize::MAX), patterns.as_ptr(), patterns.len(),
+                                                  query.as_mut_ptr(), pos.as_mut_ptr(), dist.as_mut_ptr(), query2.as_mut_ptr(), pos2.as_mut_ptr(), dist2.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(((query, pos, dist), (query2, pos2, dist2))) } else { Err(to_err(&e)) }
+}
+
+/// `reads_hdist_anchored_batch` under pattern queries.
+pub fn reads_pattern_anchored_batch(seq: &[u8], offsets: &[u64], k: usize, anchor: Anchor, pos_lo: usize, pos_hi: usize, patterns: &[Pattern]) -> Result<ReadsBest2, NucleotideError> {
+    let count = offsets.len().saturating_sub(1);
+    assert!(count == 0 || seq.len() as u64 >= offsets[count], "seq holds offsets[count] bases");
+    let (mut query, mut pos, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let (mut query2, mut pos2, mut dist2) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_pattern_anchored_batch(c, seq.as_ptr(), offsets.as_ptr(), count, k, anchor.raw(), pos_lo, pos_hi, patterns.as_ptr(), patterns.len(), query.as_mut_ptr(),
+                                                 pos.as_mut_ptr(), dist.as_mut_ptr(), query2.as_mut_ptr(), pos2.as_mut_ptr(), dist2.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(((query, pos, dist), (query2, pos2, dist2))) } else { Err(to_err(&e)) }
+}
+
+/// `reads_pattern_anchored_batch` of the packed words `encode_batch` writes, without decoding them.
+pub fn reads_pattern_anchored_batch_packed(words: &[u64], word_offsets: &[u64], offsets: &[u64], k: usize, anchor: Anchor, pos_lo: usize, pos_hi: usize, patterns: &[Pattern]) -> Result<ReadsBest2, NucleotideError> {
+    let count = offsets.len().saturating_sub(1);
+    assert!(word_offsets.len() == offsets.len(), "one word offset per base offset");
+    assert!(count == 0 || words.len() as u64 >= word_offsets[count], "words holds word_offsets[count] words");
+    let (mut query, mut pos, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let (mut query2, mut pos2, mut dist2) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_pattern_anchored_batch_packed(c, words.as_ptr(), word_offsets.as_ptr(), offsets.as_ptr(), count, k, anchor.raw(), pos_lo, pos_hi, patterns.as_ptr(),
+                                                        patterns.len(), query.as_mut_ptr(), pos.as_mut_ptr(), dist.as_mut_ptr(), query2.as_mut_ptr(), pos2.as_mut_ptr(),
+                                                        dist2.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(((query, pos, dist), (query2, pos2, dist2))) } else { Err(to_err(&e)) }
+}
+
+/// `reads_hdist_best_batch` under pattern queries.
+pub fn reads_pattern_best_batch(seq: &[u8], offsets: &[u64], k: usize, patterns: &[Pattern]) -> Result<(Vec<u32>, Vec<u32>, Vec<u8>), NucleotideError> {
+    let count = offsets.len().saturating_sub(1);
+    assert!(count == 0 || seq.len() as u64 >= offsets[count], "seq holds offsets[count] bases");
+    let (mut query, mut pos, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_pattern_best_batch(c, seq.as_ptr(), offsets.as_ptr(), count, k, patterns.as_ptr(), patterns.len(), query.as_mut_ptr(), pos.as_mut_ptr(), dist.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok((query, pos, dist)) } else { Err(to_err(&e)) }
+}
+
+/// `reads_pattern_best_batch` of the packed words `encode_batch` writes, without decoding them.
+pub fn reads_pattern_best_batch_packed(words: &[u64], word_offsets: &[u64], offsets: &[u64], k: usize, patterns: &[Pattern]) -> Result<(Vec<u32>, Vec<u32>, Vec<u8>), NucleotideError> {
+    let count = offsets.len().saturating_sub(1);
+    assert!(word_offsets.len() == offsets.len(), "one word offset per base offset");
+    assert!(count == 0 || words.len() as u64 >= word_offsets[count], "words holds word_offsets[count] words");
+    let (mut query, mut pos, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_pattern_best_batch_packed(c, words.as_ptr(), word_offsets.as_ptr(), offsets.as_ptr(), count, k, patterns.as_ptr(), patterns.len(), query.as_mut_ptr(), pos.as_mut_ptr(), dist.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok((query, pos, dist)) } else { Err(to_err(&e)) }
+}
+
 /// `counts[q]` = the number of windows `j` of `reference` with `pdist(j) = #{ i < k : reference[j+i] not in S_i of patterns[q] } <= taus[q]`, every
 /// pattern in one pass (`taus.len()` must equal `patterns.len()`).
 pub fn kmer_pattern_count_multi(reference: &[u8], k: usize, patterns: &[Pattern], taus: &[u32]) -> Result<Vec<u64>, NucleotideError> {
