@@ -686,6 +686,31 @@ class Context:
         return self._reads_anchored(self._lib.bitnuc_reads_pattern_anchored_packed, (_ptr(w), read_len, count, int(k)), count, patterns, pos_lo, pos_hi, second,
                                     int(k))
 
+    def reads_edist_anchored(self, reads, read_len, k, queries, pos_lo=0, pos_hi=None, count=None, second=True):
+        """The indel-tolerant anchored match: as reads_hdist_anchored, with the EDIT (Levenshtein) distance of each query to the best substring of the
+        read's span [pos_lo, min(pos_hi, read_len - k) + k) (at most 64 bases; the substring starts and ends anywhere in it).  (query, end, dist,
+        second_query, second_end, second_dist): the smallest (dist, query, end) and the smallest over the other queries; end is an offset in the read,
+        one past the last aligned base (the start is not reported).  dist is never above reads_hdist_anchored's.  second=False: the best triple only."""
+        s, read_len, count = self._fixed_reads(reads, read_len, count)
+        return self._reads_anchored(self._lib.bitnuc_reads_edist_anchored, (_ptr(s), read_len, count, int(k)), count, queries, pos_lo, pos_hi, second)
+
+    def reads_edist_anchored_packed(self, words, read_len, count, k, queries, pos_lo=0, pos_hi=None, second=True):
+        """reads_edist_anchored of the packed words encode_fixed writes (ceil(read_len / 32) words per read), without decoding them."""
+        w, read_len, count = self._fixed_words(words, read_len, count)
+        return self._reads_anchored(self._lib.bitnuc_reads_edist_anchored_packed, (_ptr(w), read_len, count, int(k)), count, queries, pos_lo, pos_hi, second)
+
+    def reads_pattern_edist_anchored(self, reads, read_len, k, patterns, pos_lo=0, pos_hi=None, count=None, second=True):
+        """reads_edist_anchored under pattern queries: a read base matches query position i when it is in the position's set."""
+        s, read_len, count = self._fixed_reads(reads, read_len, count)
+        return self._reads_anchored(self._lib.bitnuc_reads_pattern_edist_anchored, (_ptr(s), read_len, count, int(k)), count, patterns, pos_lo, pos_hi, second,
+                                    int(k))
+
+    def reads_pattern_edist_anchored_packed(self, words, read_len, count, k, patterns, pos_lo=0, pos_hi=None, second=True):
+        """reads_pattern_edist_anchored of the packed words encode_fixed writes, without decoding them."""
+        w, read_len, count = self._fixed_words(words, read_len, count)
+        return self._reads_anchored(self._lib.bitnuc_reads_pattern_edist_anchored_packed, (_ptr(w), read_len, count, int(k)), count, patterns, pos_lo, pos_hi,
+                                    second, int(k))
+
     def reads_pattern_anchored_batch(self, seq, offsets, k, patterns, pos_lo=0, pos_hi=0, anchor="start", second=True):
         """reads_hdist_anchored_batch under pattern queries (a ragged batch; the range counted from each read's start or end)."""
         s, off, count = self._ragged_reads(seq, offsets)
@@ -1101,6 +1126,35 @@ class Context:
         self._call_dev(self._lib.bitnuc_reads_pattern_anchored_packed_async, _dev_ptr(d_words), int(read_len), int(count), int(k), int(pos_lo),
                        _SIZE_MAX if pos_hi is None else int(pos_hi), _dev_ptr(d_patterns), int(n_queries), _dev_ptr(d_best_query), _dev_ptr(d_best_pos),
                        _dev_ptr(d_best_dist), *(_dev_ptr(a) for a in (d_second_query, d_second_pos, d_second_dist)))
+
+    def _reads_edist_async(self, fn, d_data, read_len, count, k, d_queries, n_queries, d_best, d_second, pos_lo, pos_hi):
+        self._call_dev(fn, _dev_ptr(d_data), int(read_len), int(count), int(k), int(pos_lo), _SIZE_MAX if pos_hi is None else int(pos_hi), _dev_ptr(d_queries),
+                       int(n_queries), *(_dev_ptr(a) for a in d_best), *(_dev_ptr(a) for a in d_second))
+
+    def reads_edist_anchored_async(self, d_reads, read_len, count, k, d_queries, n_queries, d_best_query, d_best_end, d_best_dist, d_second_query=None,
+                                   d_second_end=None, d_second_dist=None, pos_lo=0, pos_hi=None):
+        """reads_edist_anchored on device tensors, asynchronous on the context's stream (d_second_*: all three or none); an invalid span byte is
+        reported by the next sync()."""
+        self._reads_edist_async(self._lib.bitnuc_reads_edist_anchored_async, d_reads, read_len, count, k, d_queries, n_queries,
+                                (d_best_query, d_best_end, d_best_dist), (d_second_query, d_second_end, d_second_dist), pos_lo, pos_hi)
+
+    def reads_edist_anchored_packed_async(self, d_words, read_len, count, k, d_queries, n_queries, d_best_query, d_best_end, d_best_dist, d_second_query=None,
+                                          d_second_end=None, d_second_dist=None, pos_lo=0, pos_hi=None):
+        """reads_edist_anchored_async of packed words (ceil(read_len / 32) per read)."""
+        self._reads_edist_async(self._lib.bitnuc_reads_edist_anchored_packed_async, d_words, read_len, count, k, d_queries, n_queries,
+                                (d_best_query, d_best_end, d_best_dist), (d_second_query, d_second_end, d_second_dist), pos_lo, pos_hi)
+
+    def reads_pattern_edist_anchored_async(self, d_reads, read_len, count, k, d_patterns, n_queries, d_best_query, d_best_end, d_best_dist, d_second_query=None,
+                                           d_second_end=None, d_second_dist=None, pos_lo=0, pos_hi=None):
+        """reads_edist_anchored_async under pattern queries."""
+        self._reads_edist_async(self._lib.bitnuc_reads_pattern_edist_anchored_async, d_reads, read_len, count, k, d_patterns, n_queries,
+                                (d_best_query, d_best_end, d_best_dist), (d_second_query, d_second_end, d_second_dist), pos_lo, pos_hi)
+
+    def reads_pattern_edist_anchored_packed_async(self, d_words, read_len, count, k, d_patterns, n_queries, d_best_query, d_best_end, d_best_dist,
+                                                  d_second_query=None, d_second_end=None, d_second_dist=None, pos_lo=0, pos_hi=None):
+        """reads_edist_anchored_packed_async under pattern queries."""
+        self._reads_edist_async(self._lib.bitnuc_reads_pattern_edist_anchored_packed_async, d_words, read_len, count, k, d_patterns, n_queries,
+                                (d_best_query, d_best_end, d_best_dist), (d_second_query, d_second_end, d_second_dist), pos_lo, pos_hi)
 
     def reads_pattern_anchored_batch_async(self, d_seq, d_offsets, count, total_bases, k, d_patterns, n_queries, d_best_query, d_best_pos, d_best_dist,
                                            d_second_query=None, d_second_pos=None, d_second_dist=None, pos_lo=0, pos_hi=0, anchor="start"):

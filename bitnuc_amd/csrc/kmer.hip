@@ -14,6 +14,7 @@
 #include "scan_reads_device.h"
 #include "scan_reads_batch_device.h"
 #include "scan_anchored_device.h"
+#include "scan_edist_device.h"
 #include "scan_hist_device.h"
 #include "scan_mfma_host.h"
 #include "scan_hits_host.h"
@@ -23,6 +24,7 @@
 #include "reads_best2_host.h"
 #include "reads_anchored_host.h"
 #include "reads_anchored_batch_host.h"
+#include "reads_edist_host.h"
 #include "reads_batch_host.h"
 #include "scan_hist_host.h"
 #include "pattern_host.h"
@@ -976,6 +978,25 @@ int anchored_host_loop(bitnuc_ctx *c, size_t count, size_t per, const HQ *querie
         bitnuc_err e;
         if (int st = drain(c, &e)) { if (err) *err = e; return st; }
     }
+    return BITNUC_OK;
+}
+
+// ---- the INDEL-TOLERANT anchored best match and runner-up per read (scan_edist_device.h): a vector-ALU kernel, one read per lane, writes the six outputs.
+// Context scratch: 16 bytes per query (scratch 10, shared with the other per-read forms in stream order).  The checks, the fills, the cutoff and the
+// host forms' chunk loop are the anchored forms' (check_anchored, anchored_fill_*, anchored_work, anchored_host_loop); o.pos / o.pos2 hold the ends.
+// data: ASCII reads at any alignment (stride = read_len bytes) or 8-byte aligned packed words (stride = words per read); count, nq >= 1, k <= n <= 64
+template <bool PACKED, class HQ>
+int launch_reads_edist(bitnuc_ctx *c, const void *data, size_t stride, size_t count, size_t k, size_t pos_lo, size_t n, const HQ *d_queries, size_t nq,
+                       const AnchorOut &o, unsigned long long *slot, bitnuc_err *err) {
+    if (int st = ensure_scratch(c, 10, nq * kEdistEntry, err)) return st;
+    u32x4 *tabs = reinterpret_cast<u32x4 *>(c->scratch[10]);
+    edist_tables_kernel<<<(unsigned)((nq + 63) / 64), 64, 0, c->stream>>>(dev_queries(d_queries), (unsigned)nq, (unsigned)k, tabs);
+    HIPCHK(hipGetLastError());
+    const EdistGeom g{(unsigned long long)stride, (unsigned)pos_lo, (unsigned)n, (unsigned)k, (unsigned)nq};
+    const size_t want = (count + kEdistBlock - 1) / kEdistBlock, cap = (size_t)c->num_cu * kEdistBlocksPerCu;
+    reads_edist_kernel<PACKED><<<(unsigned)(want < cap ? want : cap), kEdistBlock, 0, c->stream>>>(
+        static_cast<const uint8_t *>(data), (unsigned long long)count, g, tabs, o.query, o.pos, o.dist, o.query2, o.pos2, o.dist2, slot);
+    HIPCHK(hipGetLastError());
     return BITNUC_OK;
 }
 
@@ -2025,6 +2046,108 @@ int reads_anchored_packed_host(bitnuc_ctx *c, const uint64_t *words, size_t read
     });
 }
 
+// ---- the indel-tolerant anchored best match and runner-up per read of a fixed-length batch: the anchored forms above with the edit distance -------------
+template <class HQ>
+int reads_edist_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi, const HQ *d_queries,
+                      size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_end,
+                      uint8_t *d_second_dist, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    const AnchorOut o{d_best_query, d_best_end, d_best_dist, d_second_dist, d_second_query, d_second_end};
+    bool done;
+    size_t offsets;
+    if (int st = check_anchored(read_len, count, k, pos_lo, pos_hi, d_queries, reads_qmask<HQ>(), n_queries, o, &done, &offsets, err)) return st;
+    if (done) return BITNUC_OK;
+    DeviceGuard g(c->device);
+    if (!offsets) return anchored_fill_dev(c, count, o, err);
+    if (!d_reads) return fail(err, BITNUC_UNSUPPORTED);
+    unsigned long long *slot;
+    if (int st = take_slot(c, 0, &slot, err)) return st;
+    return launch_reads_edist<false>(c, d_reads, read_len, count, k, pos_lo, offsets + k - 1, d_queries, n_queries, o, slot, err);
+}
+
+template <class HQ>
+int reads_edist_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi, const HQ *d_queries,
+                             size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist, uint32_t *d_second_query,
+                             uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    const AnchorOut o{d_best_query, d_best_end, d_best_dist, d_second_dist, d_second_query, d_second_end};
+    bool done;
+    size_t offsets;
+    if (int st = check_anchored(read_len, count, k, pos_lo, pos_hi, d_queries, reads_qmask<HQ>(), n_queries, o, &done, &offsets, err)) return st;
+    if (done) return BITNUC_OK;
+    DeviceGuard g(c->device);
+    if (!offsets) return anchored_fill_dev(c, count, o, err);
+    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    return launch_reads_edist<true>(c, d_words, words_for(read_len), count, k, pos_lo, offsets + k - 1, d_queries, n_queries, o, nullptr, err);
+}
+
+template <class HQ>
+int reads_edist_host(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi, const HQ *queries,
+                     size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_end,
+                     uint8_t *second_dist, bitnuc_err *err) {
+    clear_err(err);
+    const AnchorOut o{best_query, best_end, best_dist, second_dist, second_query, second_end};
+    bool done;
+    size_t offsets;
+    if (int st = check_anchored(read_len, count, k, pos_lo, pos_hi, queries, reads_qmask<HQ>(), n_queries, o, &done, &offsets, err)) return st;
+    if (done) return BITNUC_OK;
+    if (!offsets) { anchored_fill_host(count, o); return BITNUC_OK; }
+    if (!reads) return fail(err, BITNUC_UNSUPPORTED);
+    const size_t n = offsets + k - 1; // the span: what the cutoff is judged on, count x n x n_queries
+    if (on_host(c, anchored_work(n, count, n_queries))) {
+        const long long bad = bitnuc_host::reads_edist_anchored_small(reads, read_len, count, k, pos_lo, n, host_queries(queries), n_queries, best_query, best_end, best_dist,
+                                                                      second_query, second_end, second_dist);
+        if (bad >= 0) {
+            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = reads[bad]; err->index = (uint64_t)bad; }
+            return BITNUC_INVALID_BASE;
+        }
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    const size_t per = read_len < kHostChunk ? kHostChunk / read_len : 1, pm = count < per ? count : per; // whole reads per chunk
+    if (int st = ensure_scratch(c, 0, pm * read_len + 64, err)) return st;
+    return anchored_host_loop(c, count, per, queries, n_queries, o, err, [&](size_t r0, size_t m, const HQ *d_queries, const AnchorOut &d) {
+        HIPCHK(hipMemcpyAsync(c->scratch[0], reads + r0 * read_len, m * read_len, hipMemcpyHostToDevice, c->stream));
+        unsigned long long *slot;
+        if (int st = take_slot(c, r0 * read_len, &slot, err)) return st;
+        return launch_reads_edist<false>(c, c->scratch[0], read_len, m, k, pos_lo, n, d_queries, n_queries, d, slot, err);
+    });
+}
+
+template <class HQ>
+int reads_edist_packed_host(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi, const HQ *queries,
+                            size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_end,
+                            uint8_t *second_dist, bitnuc_err *err) {
+    clear_err(err);
+    const AnchorOut o{best_query, best_end, best_dist, second_dist, second_query, second_end};
+    bool done;
+    size_t offsets;
+    if (int st = check_anchored(read_len, count, k, pos_lo, pos_hi, queries, reads_qmask<HQ>(), n_queries, o, &done, &offsets, err)) return st;
+    if (done) return BITNUC_OK;
+    if (!offsets) { anchored_fill_host(count, o); return BITNUC_OK; }
+    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    const size_t n = offsets + k - 1;
+    if (on_host(c, anchored_work(n, count, n_queries))) {
+        bitnuc_host::reads_edist_anchored_packed_small(words, read_len, count, k, pos_lo, n, host_queries(queries), n_queries, best_query, best_end, best_dist, second_query,
+                                                       second_end, second_dist);
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    const size_t wpr = words_for(read_len);
+    const size_t per = wpr < kPackedChunkWords ? kPackedChunkWords / wpr : 1, pm = count < per ? count : per; // whole reads per chunk
+    if (int st = ensure_scratch(c, 0, pm * wpr * 8, err)) return st;
+    return anchored_host_loop(c, count, per, queries, n_queries, o, err, [&](size_t r0, size_t m, const HQ *d_queries, const AnchorOut &d) {
+        HIPCHK(hipMemcpyAsync(c->scratch[0], words + r0 * wpr, m * wpr * 8, hipMemcpyHostToDevice, c->stream));
+        return launch_reads_edist<true>(c, c->scratch[0], wpr, m, k, pos_lo, n, d_queries, n_queries, d, nullptr, err);
+    });
+}
+
 // ---- the anchored best match and runner-up per read of a ragged batch ----------------------------------------------------------------
 template <class HQ>
 int reads_anchored_batch_async(bitnuc_ctx *c, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k, int anchor,
@@ -2490,6 +2613,56 @@ int bitnuc_reads_pattern_best_batch_packed(bitnuc_ctx *c, const uint64_t *words,
                                            const bitnuc_pattern *patterns, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist,
                                            bitnuc_err *err) {
     return reads_best_batch_packed_host(c, words, word_offsets, offsets, count, k, patterns, n_queries, best_query, best_pos, best_dist, err);
+}
+
+// the indel-tolerant anchored forms (edit distance): exact queries and their pattern twins
+int bitnuc_reads_edist_anchored_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                      const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist,
+                                      uint32_t *d_second_query, uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err) {
+    return reads_edist_async(c, d_reads, read_len, count, k, pos_lo, pos_hi, d_queries, n_queries, d_best_query, d_best_end, d_best_dist, d_second_query,
+                             d_second_end, d_second_dist, err);
+}
+int bitnuc_reads_edist_anchored_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                             const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist,
+                                             uint32_t *d_second_query, uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err) {
+    return reads_edist_packed_async(c, d_words, read_len, count, k, pos_lo, pos_hi, d_queries, n_queries, d_best_query, d_best_end, d_best_dist, d_second_query,
+                                    d_second_end, d_second_dist, err);
+}
+int bitnuc_reads_edist_anchored(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                const uint64_t *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist,
+                                uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err) {
+    return reads_edist_host(c, reads, read_len, count, k, pos_lo, pos_hi, queries, n_queries, best_query, best_end, best_dist, second_query,
+                            second_end, second_dist, err);
+}
+int bitnuc_reads_edist_anchored_packed(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                       const uint64_t *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist,
+                                       uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err) {
+    return reads_edist_packed_host(c, words, read_len, count, k, pos_lo, pos_hi, queries, n_queries, best_query, best_end, best_dist, second_query,
+                                   second_end, second_dist, err);
+}
+int bitnuc_reads_pattern_edist_anchored_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                              const bitnuc_pattern *d_patterns, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist,
+                                              uint32_t *d_second_query, uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err) {
+    return reads_edist_async(c, d_reads, read_len, count, k, pos_lo, pos_hi, d_patterns, n_queries, d_best_query, d_best_end, d_best_dist, d_second_query,
+                             d_second_end, d_second_dist, err);
+}
+int bitnuc_reads_pattern_edist_anchored_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                                     const bitnuc_pattern *d_patterns, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist,
+                                                     uint32_t *d_second_query, uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err) {
+    return reads_edist_packed_async(c, d_words, read_len, count, k, pos_lo, pos_hi, d_patterns, n_queries, d_best_query, d_best_end, d_best_dist, d_second_query,
+                                    d_second_end, d_second_dist, err);
+}
+int bitnuc_reads_pattern_edist_anchored(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                        const bitnuc_pattern *patterns, size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist,
+                                        uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err) {
+    return reads_edist_host(c, reads, read_len, count, k, pos_lo, pos_hi, patterns, n_queries, best_query, best_end, best_dist, second_query,
+                            second_end, second_dist, err);
+}
+int bitnuc_reads_pattern_edist_anchored_packed(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                               const bitnuc_pattern *patterns, size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist,
+                                               uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err) {
+    return reads_edist_packed_host(c, words, read_len, count, k, pos_lo, pos_hi, patterns, n_queries, best_query, best_end, best_dist, second_query,
+                                   second_end, second_dist, err);
 }
 
 // ---- pattern queries: a set of bases per position (bitnuc_pattern).  The twelve entry points below are the twins of the exact ones above: the same checks

@@ -1,0 +1,104 @@
+// reads_edist_host.h -- the indel-tolerant anchored best match and runner-up per read below the host cutoff (bitnuc_reads_edist_anchored / _packed and
+// their pattern twins): per read the smallest (edit distance, query, end) over the queries, the edit distance being the Levenshtein distance of the query
+// to the best substring of the read's span [pos_lo, pos_lo + n), and the smallest over the queries other than the winner's.  The same bit-parallel
+// recurrence as the kernel (scan_edist_device.h: Myers 1999 in Hyyro's form, one 32-bit column per (read, query)), in plain C++ for both layouts and both
+// query kinds; the tests' oracle is the plain DP, so the two are independent.  Only the span bytes of each read are read and validated.  Plain C++ (no
+// HIP): tests/c/reads_edist_host_sanitize.cpp runs them under ASan + UBSan.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "reads_best2_host.h" // ReadsTop2, reads_best2_store, reads_best_fill; PatternSets, pattern_of_2bit through scan_mfma_host.h
+
+namespace bitnuc_host {
+
+// Peq[c]: the positions < k of the query that base code c matches, by the query's kind
+struct EdistPeq { uint32_t m[4]; };
+static inline EdistPeq edist_peq(const PatternSets &p, size_t k) {
+    const uint32_t ones = k >= 32 ? ~0u : ((1u << k) - 1u);
+    return EdistPeq{{p.allow[0] & ones, p.allow[1] & ones, p.allow[2] & ones, p.allow[3] & ones}};
+}
+static inline EdistPeq edist_peq(uint64_t q, size_t k) { return edist_peq(pattern_of_2bit(q, k), k); }
+
+// the span's n <= 64 bases (codes[j] in 0 .. 3) against one query of 1 <= k <= 32 positions: dist << 6 | (j - 1) of the smallest D[k][j], 1 <= j <= n, and
+// its first j.  Bits at and above k of the column words are junk that never travels down; only bit k - 1 is tested.
+static inline uint32_t edist_span(const uint8_t *codes, size_t n, size_t k, const EdistPeq &p) {
+    uint32_t pv = ~0u, mv = 0u, score = (uint32_t)k, best = ~0u;
+    const unsigned top = (unsigned)k - 1u;
+    for (size_t j = 0; j < n; ++j) {
+        const uint32_t eq = p.m[codes[j]];
+        const uint32_t xv = eq | mv;
+        const uint32_t xh = (((eq & pv) + pv) ^ pv) | eq;
+        uint32_t ph = mv | ~(xh | pv);
+        uint32_t mh = pv & xh;
+        score += (ph >> top) & 1u;
+        score -= (mh >> top) & 1u;
+        const uint32_t key = (score << 6) | (uint32_t)j;
+        if (key < best) best = key;
+        ph <<= 1; // no carry-in: D[0][j] = 0
+        mh <<= 1;
+        pv = mh | ~(xv | ph);
+        mv = ph & xv;
+    }
+    return best;
+}
+
+// one read's span codes against every query: the running top-2 over distinct queries (queries come in ascending order, one key each)
+template <class Q>
+static inline ReadsTop2 edist_read(const uint8_t *codes, size_t n, size_t k, size_t pos_lo, const Q *queries, size_t nq) {
+    ReadsTop2 t{kReadsTop2None, kReadsTop2None};
+    for (size_t q = 0; q < nq; ++q) {
+        const uint32_t m = edist_span(codes, n, k, edist_peq(queries[q], k));
+        const uint64_t c = ((uint64_t)(m >> 6) << 58) | ((uint64_t)q << 32) | (uint64_t)(pos_lo + (m & 63u) + 1u); // the end: one past the last aligned base
+        if (c < t.best) {
+            t.second = t.best;
+            t.best = c;
+        } else if (c < t.second) {
+            t.second = c;
+        }
+    }
+    return t;
+}
+
+static inline void edist_store_top2(const ReadsTop2 &t, size_t r, uint32_t *query, uint32_t *end, uint8_t *dist, uint32_t *query2, uint32_t *end2, uint8_t *dist2) {
+    reads_best2_store(t.best, query + r, end + r, dist + r);
+    if (query2) reads_best2_store(t.second, query2 + r, end2 + r, dist2 + r);
+}
+
+// packed reads of read_len bases, ceil(read_len / 32) words each (1 <= k <= 32, k <= n <= 64, pos_lo + n <= read_len, nq >= 1); query2 / end2 / dist2 all
+// NULL: the best triple only
+template <class Q>
+static inline void reads_edist_anchored_packed_small(const uint64_t *words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t n, const Q *queries, size_t nq,
+                                                     uint32_t *query, uint32_t *end, uint8_t *dist, uint32_t *query2, uint32_t *end2, uint8_t *dist2) {
+    const size_t wpr = read_len / 32 + (read_len % 32 != 0);
+    reads_best_fill(count, query, end, dist);
+    if (query2) reads_best_fill(count, query2, end2, dist2);
+    for (size_t r = 0; r < count; ++r) {
+        uint8_t codes[64];
+        for (size_t j = 0; j < n; ++j) codes[j] = (uint8_t)((words[r * wpr + (pos_lo + j) / 32] >> (2 * ((pos_lo + j) % 32))) & 3u);
+        edist_store_top2(edist_read(codes, n, k, pos_lo, queries, nq), r, query, end, dist, query2, end2, dist2);
+    }
+}
+
+// back-to-back ASCII reads of read_len bytes (the same conditions): -1 with the outputs written, or the index of the first invalid byte, in buffer order,
+// among the span bytes (outputs untouched).  Bytes outside the spans are never read.
+template <class Q>
+static inline long long reads_edist_anchored_small(const uint8_t *reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t n, const Q *queries, size_t nq,
+                                                   uint32_t *query, uint32_t *end, uint8_t *dist, uint32_t *query2, uint32_t *end2, uint8_t *dist2) {
+    for (size_t r = 0; r < count; ++r)
+        for (size_t j = 0; j < n; ++j) {
+            const unsigned u = reads[r * read_len + pos_lo + j] & 0xDFu;
+            if (u != 'A' && u != 'C' && u != 'G' && u != 'T') return (long long)(r * read_len + pos_lo + j);
+        }
+    reads_best_fill(count, query, end, dist);
+    if (query2) reads_best_fill(count, query2, end2, dist2);
+    for (size_t r = 0; r < count; ++r) {
+        const uint8_t *s = reads + r * read_len + pos_lo;
+        uint8_t codes[64];
+        for (size_t j = 0; j < n; ++j) codes[j] = (uint8_t)(((s[j] >> 1) ^ (s[j] >> 2)) & 3u); // A 0, C 1, G 2, T 3, either case
+        edist_store_top2(edist_read(codes, n, k, pos_lo, queries, nq), r, query, end, dist, query2, end2, dist2);
+    }
+    return -1;
+}
+
+} // namespace bitnuc_host

@@ -482,6 +482,47 @@ class Context {
             return NucleotideError::from_c(e);
         return b;
     }
+    // the indel-tolerant anchored match (bitnuc_reads_edist_anchored*): the edit distance of each query to the best substring of the read's span
+    // [pos_lo, min(pos_hi, read_len - k) + k); ReadsBest::pos holds the END of the alignment, an offset in the read one past its last aligned base
+    Result<ReadsBest2> reads_edist_anchored(Bytes reads, size_t read_len, size_t k, const std::vector<uint64_t> &queries, size_t pos_lo = 0,
+                                            size_t pos_hi = SIZE_MAX) const {
+        const size_t count = read_len ? reads.len / read_len : 0;
+        ReadsBest2 b{reads_outputs(count), reads_outputs(count)};
+        bitnuc_err e;
+        if (bitnuc_reads_edist_anchored(ctx_, reads.ptr, read_len, count, k, pos_lo, pos_hi, queries.data(), queries.size(), b.best.query.data(), b.best.pos.data(),
+                                        b.best.dist.data(), b.second.query.data(), b.second.pos.data(), b.second.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
+    Result<ReadsBest2> reads_edist_anchored_packed(Words words, size_t read_len, size_t count, size_t k, const std::vector<uint64_t> &queries, size_t pos_lo = 0,
+                                                   size_t pos_hi = SIZE_MAX) const {
+        ReadsBest2 b{reads_outputs(count), reads_outputs(count)};
+        bitnuc_err e;
+        if (bitnuc_reads_edist_anchored_packed(ctx_, words.ptr, read_len, count, k, pos_lo, pos_hi, queries.data(), queries.size(), b.best.query.data(),
+                                               b.best.pos.data(), b.best.dist.data(), b.second.query.data(), b.second.pos.data(), b.second.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
+    Result<ReadsBest2> reads_pattern_edist_anchored(Bytes reads, size_t read_len, size_t k, const std::vector<bitnuc_pattern> &patterns, size_t pos_lo = 0,
+                                                    size_t pos_hi = SIZE_MAX) const {
+        const size_t count = read_len ? reads.len / read_len : 0;
+        ReadsBest2 b{reads_outputs(count), reads_outputs(count)};
+        bitnuc_err e;
+        if (bitnuc_reads_pattern_edist_anchored(ctx_, reads.ptr, read_len, count, k, pos_lo, pos_hi, patterns.data(), patterns.size(), b.best.query.data(),
+                                                b.best.pos.data(), b.best.dist.data(), b.second.query.data(), b.second.pos.data(), b.second.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
+    Result<ReadsBest2> reads_pattern_edist_anchored_packed(Words words, size_t read_len, size_t count, size_t k, const std::vector<bitnuc_pattern> &patterns,
+                                                           size_t pos_lo = 0, size_t pos_hi = SIZE_MAX) const {
+        ReadsBest2 b{reads_outputs(count), reads_outputs(count)};
+        bitnuc_err e;
+        if (bitnuc_reads_pattern_edist_anchored_packed(ctx_, words.ptr, read_len, count, k, pos_lo, pos_hi, patterns.data(), patterns.size(), b.best.query.data(),
+                                                       b.best.pos.data(), b.best.dist.data(), b.second.query.data(), b.second.pos.data(), b.second.dist.data(), &e) !=
+            BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
     Result<ReadsBest> reads_pattern_best_batch(Bytes seq, const std::vector<uint64_t> &offsets, size_t k, const std::vector<bitnuc_pattern> &patterns) const {
         const size_t count = offsets.empty() ? 0 : offsets.size() - 1;
         if (count && seq.len < offsets.back()) return NucleotideError::invalid_length(seq.len);

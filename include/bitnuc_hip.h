@@ -503,7 +503,8 @@ int bitnuc_reads_hdist_best2_packed(bitnuc_ctx *ctx, const uint64_t *words, size
  * (profiles/r15_reads_anchored.json), ASCII / packed with the second triple: k = 16, four offsets: 0.28 / 0.20 ms at 1 query, 0.27 / 0.19 at 8, 0.56 /
  * 0.46 at 64, 2.8 / 2.6 at 512; one offset: 0.25 / 0.17, 0.25 / 0.17, 0.27 / 0.20, 0.90 / 0.77 ms; 0.003 - 0.84 x the time of a copy of the spans plus
  * bitnuc_reads_hdist_best2*_async on it.
- * The ragged twins: bitnuc_reads_hdist_anchored_batch* below; the pattern (IUPAC) twins: bitnuc_reads_pattern_anchored*.  Out of scope: a per-read offset table, spans above 64 bases, reverse-complement queries (callers add the
+ * The ragged twins: bitnuc_reads_hdist_anchored_batch* below; the pattern (IUPAC) twins: bitnuc_reads_pattern_anchored*.  Out of scope: indels (every window is compared base against base; the
+ * edit-distance form is bitnuc_reads_edist_anchored* below), a per-read offset table, spans above 64 bases, reverse-complement queries (callers add the
  * reverse complements to the query list themselves). */
 #define BITNUC_ANCHOR_MAX_SPAN 64
 int bitnuc_reads_hdist_anchored_async(bitnuc_ctx *ctx, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
@@ -696,6 +697,77 @@ int bitnuc_reads_pattern_best_batch(bitnuc_ctx *ctx, const uint8_t *seq, const u
 int bitnuc_reads_pattern_best_batch_packed(bitnuc_ctx *ctx, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
                                            const bitnuc_pattern *patterns, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist,
                                            bitnuc_err *err);
+
+/* ---- INDEL-TOLERANT anchored best match and runner-up per read of a fixed-length batch (a barcode, adapter or primer with an inserted or deleted base:
+ * long-read platforms, synthesised oligos) -- bitnuc_reads_hdist_anchored* with the EDIT (Levenshtein) distance instead of the Hamming distance ----
+ * Arguments: those of bitnuc_reads_hdist_anchored* (read_len, count, k, pos_lo, pos_hi, queries, n_queries; ASCII or packed), with best_end / second_end
+ * where best_pos / second_pos stood.
+ * Span.  hi_eff = min(pos_hi, read_len - k); the span of read r is its bases t_1 .. t_n = read_r[pos_lo .. hi_eff + k), n = hi_eff - pos_lo + k >= k --
+ * exactly the bases the Hamming form looks at.  pos_hi = SIZE_MAX: to the end of the read.  An empty range (pos_lo > hi_eff, k == 0, read_len < k,
+ * n_queries == 0) has no span: all written outputs get the fill (UINT32_MAX, UINT32_MAX, 0xFF).  n > BITNUC_ANCHOR_MAX_SPAN -> UNSUPPORTED (err.value =
+ * n), judged on (read_len, k, pos_lo, pos_hi) alone: with n_queries == 0 as well, although such a call would write only fills.
+ * Distance.  For a query q_1 .. q_k: D[0][j] = 0 (0 <= j <= n), D[i][0] = i, D[i][j] = min(D[i-1][j-1] + [t_j does not match q_i], D[i-1][j] + 1,
+ * D[i][j-1] + 1).  edist(r, q) = min over 1 <= j <= n of D[k][j]: the Levenshtein distance of the query to the best SUBSTRING of the span, which may
+ * start and end anywhere in the span.  end(r, q) = pos_lo + (the smallest such j): an offset in the read, one past the last aligned read base.  "Matches"
+ * is equality for an exact query and t_j in S_i for a pattern (bitnuc_reads_pattern_edist_anchored*; an empty set never matches).  edist <= k <= 32, so
+ * it fits the uint8_t outputs and never collides with the fill.  The START of the alignment is not reported: it would need a traceback.
+ * Results.  best_query / best_end / best_dist [r] is the lexicographically smallest (edist, query, end) over all queries; second_*[r] the smallest over
+ * the queries other than best_query[r]: an equal duplicate query at a higher index is the runner-up (at the same distance and end), one query gives the
+ * fill in the second triple.  For equal arguments best_dist here is <= bitnuc_reads_hdist_anchored*'s best_dist: every window is a substring of the
+ * span, and the Levenshtein distance is <= the Hamming distance.  Deterministic.  Exactly [0, count) of each output is written; the dist arrays may have
+ * any byte offset.
+ * Second triple.  second_query, second_end and second_dist may ALL be NULL: only the best triple is computed and written.  One or two of them NULL ->
+ * UNSUPPORTED.
+ * Input layouts: ASCII reads back to back, read r at reads + r * read_len, any alignment, either case; packed reads of ceil(read_len / 32) 64-bit words
+ * each (what bitnuc_encode_fixed writes), 8-byte aligned, base b of a read at bits 2 (b % 32) of its word b / 32, bits above a read's last base ignored.
+ * Limits: k <= 32; read_len < 2^32 - 1 and count x 32 ceil(read_len / 32) < 2^58 (UNSUPPORTED, value = read_len); n_queries <= BITNUC_MAX_QUERIES.
+ * Checks, in order: (1) ctx (_async forms, and the host forms above the cutoff), (2) k > 32 -> SEQUENCE_TOO_LONG (value = k), (3) the read_len / count
+ * limits, (4) n_queries > BITNUC_MAX_QUERIES -> UNSUPPORTED (value = n_queries), (5) n > BITNUC_ANCHOR_MAX_SPAN -> UNSUPPORTED (value = n), (6) count == 0
+ * -> OK, nothing written, (7) best_* NULL or best_query / best_end not 4-byte aligned, queries NULL with n_queries > 0 or not 8-byte aligned (patterns:
+ * not 4-byte aligned), the second triple partly NULL or second_query / second_end not 4-byte aligned -> UNSUPPORTED, (8) with a span: reads / words NULL
+ * (words not 8-byte aligned) -> UNSUPPORTED.  Nothing is written on an argument error.
+ * Validation.  Only the span bytes [pos_lo, hi_eff + k) of each read are read and validated; bytes outside are never examined.  The first invalid byte
+ * in buffer order among the span bytes -> INVALID_BASE with its absolute index.  The _async forms latch it once per call for bitnuc_ctx_sync() (one call
+ * leaves nothing for a second sync), the outputs are then unspecified; the host forms below the cutoff leave the outputs untouched.  A call with no span
+ * reads and validates nothing.  (The ASCII kernel loads aligned 4-byte words: at most 3 bytes before and after a span are touched, never examined.)
+ * The _async forms have the _dev contract (device pointers for everything, the context's stream, no host synchronisation but the growth of context
+ * scratch) and can be captured into a hipGraph after a warm-up of THIS call with the same or larger (count, n_queries); the reads and the queries are
+ * read at every replay.  Context scratch: 16 bytes per query; no per-read arrays -- one kernel writes the outputs itself.  The host forms are synchronous
+ * and judge count x n x n_queries (saturated) against the host cutoff: below it they run on the host (ctx may be NULL), above it through the context in
+ * chunks of whole reads, of the anchored forms' sizes; INVALID_BASE indices stay absolute.
+ * Cost: a vector-ALU kernel, one read per lane, n steps of the bit-parallel recurrence (Myers 1999 in Hyyro's form; one 32-bit add is the carry chain)
+ * per (read, query), 20 vector instructions a step; no matrix instructions, no LDS, no atomics but the invalid-byte latch.  Measured on 6,666,667 x
+ * 150-base reads, one MI355X (profiles/r18_reads_edist.json), ASCII / packed, six outputs, 3' anchor: k = 16, four offsets (n = 19): 0.28 / 0.10 ms at 1
+ * query, 0.55 / 0.50 at 8, 4.0 / 3.9 at 64, 31.5 / 30.8 at 512; k = 31, eight offsets (n = 38): 0.39 / 0.17, 1.04 / 0.98, 7.8 / 7.7, 62.3 / 61.7 ms:
+ * 0.47 - 1.2 x the time of bitnuc_reads_hdist_anchored*_async on the same arguments at 1 query, 2.0 - 3.5 x at 8, 5.5 - 12.3 x at 64, 7.1 - 18.9 x at 512
+ * (another answer: the price of indel tolerance); the pattern twins cost what the exact forms cost.
+ * Out of scope: the ragged twins (offsets tables), the whole-read (unanchored) form, reporting the alignment's start, k > 32 and spans above 64 bases,
+ * affine gaps, reverse-complement queries (callers add the reverse complements to the query list themselves). */
+int bitnuc_reads_edist_anchored_async(bitnuc_ctx *ctx, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                      const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist,
+                                      uint32_t *d_second_query, uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err);
+int bitnuc_reads_edist_anchored_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                             const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist,
+                                             uint32_t *d_second_query, uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err);
+int bitnuc_reads_edist_anchored(bitnuc_ctx *ctx, const uint8_t *reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi, const uint64_t *queries,
+                                size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_end,
+                                uint8_t *second_dist, bitnuc_err *err);
+int bitnuc_reads_edist_anchored_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                       const uint64_t *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query,
+                                       uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err);
+/* the pattern twins: a set of bases per query position (bitnuc_pattern), t_j matches position i when it is in S_i; everything else as above */
+int bitnuc_reads_pattern_edist_anchored_async(bitnuc_ctx *ctx, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                              const bitnuc_pattern *d_patterns, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist,
+                                              uint32_t *d_second_query, uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_edist_anchored_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                                     const bitnuc_pattern *d_patterns, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end,
+                                                     uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_edist_anchored(bitnuc_ctx *ctx, const uint8_t *reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                        const bitnuc_pattern *patterns, size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist,
+                                        uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_edist_anchored_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
+                                               const bitnuc_pattern *patterns, size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist,
+                                               uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err);
 
 /* ---- analysis on packed words (the callers just above the codec) ------ */
 /* BaseCount::base_counts / GCContent::gc_content of a packed sequence

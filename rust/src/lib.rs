@@ -581,6 +581,60 @@ pub fn reads_pattern_anchored_packed(words: &[u64], read_len: usize, count: usiz
     if st == ffi::BITNUC_OK { Ok(((query, pos, dist), (query2, pos2, dist2))) } else { Err(to_err(&e)) }
 }
 
+/// The indel-tolerant anchored match: as `reads_hdist_anchored`, with the EDIT distance of each query to the best substring of the read's span
+/// `[pos_lo, min(pos_hi, read_len - k) + k)` (at most 64 bases).  Per read `(query, end, dist)` of the best query and of the runner-up; `end` is an offset
+/// in the read, one past the last aligned base (the alignment's start is not reported).  `dist` is never above `reads_hdist_anchored`'s.
+pub fn reads_edist_anchored(reads: &[u8], read_len: usize, k: usize, pos_lo: usize, pos_hi: Option<usize>, queries: &[u64]) -> Result<ReadsBest2, NucleotideError> {
+    let count = if read_len == 0 { 0 } else { reads.len() / read_len };
+    let (mut query, mut end, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let (mut query2, mut end2, mut dist2) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_edist_anchored(c, reads.as_ptr(), read_len, count, k, pos_lo, pos_hi.unwrap_or(usize::MAX), queries.as_ptr(), queries.len(), query.as_mut_ptr(),
+                                         end.as_mut_ptr(), dist.as_mut_ptr(), query2.as_mut_ptr(), end2.as_mut_ptr(), dist2.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(((query, end, dist), (query2, end2, dist2))) } else { Err(to_err(&e)) }
+}
+
+/// `reads_edist_anchored` of the packed words `encode_fixed` writes (`ceil(read_len / 32)` words per read), without decoding them.
+pub fn reads_edist_anchored_packed(words: &[u64], read_len: usize, count: usize, k: usize, pos_lo: usize, pos_hi: Option<usize>, queries: &[u64]) -> Result<ReadsBest2, NucleotideError> {
+    assert!(words.len() >= count * ((read_len + 31) / 32), "count reads of ceil(read_len / 32) words each");
+    let (mut query, mut end, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let (mut query2, mut end2, mut dist2) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_edist_anchored_packed(c, words.as_ptr(), read_len, count, k, pos_lo, pos_hi.unwrap_or(usize::MAX), queries.as_ptr(), queries.len(),
+                                                query.as_mut_ptr(), end.as_mut_ptr(), dist.as_mut_ptr(), query2.as_mut_ptr(), end2.as_mut_ptr(), dist2.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(((query, end, dist), (query2, end2, dist2))) } else { Err(to_err(&e)) }
+}
+
+/// `reads_edist_anchored` under pattern queries: a read base matches query position `i` when it is in the position's set.
+pub fn reads_pattern_edist_anchored(reads: &[u8], read_len: usize, k: usize, pos_lo: usize, pos_hi: Option<usize>, patterns: &[Pattern]) -> Result<ReadsBest2, NucleotideError> {
+    let count = if read_len == 0 { 0 } else { reads.len() / read_len };
+    let (mut query, mut end, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let (mut query2, mut end2, mut dist2) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_pattern_edist_anchored(c, reads.as_ptr(), read_len, count, k, pos_lo, pos_hi.unwrap_or(usize::MAX), patterns.as_ptr(), patterns.len(),
+                                                 query.as_mut_ptr(), end.as_mut_ptr(), dist.as_mut_ptr(), query2.as_mut_ptr(), end2.as_mut_ptr(), dist2.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(((query, end, dist), (query2, end2, dist2))) } else { Err(to_err(&e)) }
+}
+
+/// `reads_pattern_edist_anchored` of the packed words `encode_fixed` writes, without decoding them.
+pub fn reads_pattern_edist_anchored_packed(words: &[u64], read_len: usize, count: usize, k: usize, pos_lo: usize, pos_hi: Option<usize>, patterns: &[Pattern]) -> Result<ReadsBest2, NucleotideError> {
+    assert!(words.len() >= count * ((read_len + 31) / 32), "count reads of ceil(read_len / 32) words each");
+    let (mut query, mut end, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let (mut query2, mut end2, mut dist2) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_pattern_edist_anchored_packed(c, words.as_ptr(), read_len, count, k, pos_lo, pos_hi.unwrap_or(usize::MAX), patterns.as_ptr(), patterns.len(),
+                                                        query.as_mut_ptr(), end.as_mut_ptr(), dist.as_mut_ptr(), query2.as_mut_ptr(), end2.as_mut_ptr(), dist2.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(((query, end, dist), (query2, end2, dist2))) } else { Err(to_err(&e)) }
+}
+
 /// `reads_hdist_anchored_batch` under pattern queries.
 pub fn reads_pattern_anchored_batch(seq: &[u8], offsets: &[u64], k: usize, anchor: Anchor, pos_lo: usize, pos_hi: usize, patterns: &[Pattern]) -> Result<ReadsBest2, NucleotideError> {
     let count = offsets.len().saturating_sub(1);
