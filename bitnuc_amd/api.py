@@ -711,6 +711,33 @@ class Context:
         return self._reads_anchored(self._lib.bitnuc_reads_pattern_edist_anchored_packed, (_ptr(w), read_len, count, int(k)), count, patterns, pos_lo, pos_hi,
                                     second, int(k))
 
+    def reads_edist_anchored_batch(self, seq, offsets, k, queries, pos_lo=0, pos_hi=0, anchor="start", second=True):
+        """reads_edist_anchored of a ragged batch (read r is seq[offsets[r]:offsets[r + 1]]): the EDIT distance of each query to the best substring of the
+        read's own span, the bases reads_hdist_anchored_batch looks at for the same (anchor, pos_lo, pos_hi) -- a short read gets its shortened span, a
+        read without a window the fill.  pos_hi - pos_lo + k may not exceed 64.  (query, end, dist, second_query, second_end, second_dist); end is
+        counted from the read's start in both anchor modes, one past the last aligned base.  second=False: the best triple only."""
+        s, off, count = self._ragged_reads(seq, offsets)
+        return self._reads_anchored(self._lib.bitnuc_reads_edist_anchored_batch, (_ptr(s), _ptr(off), count, int(k), self._anchor(anchor)), count, queries, pos_lo,
+                                    int(pos_hi), second)
+
+    def reads_edist_anchored_batch_packed(self, words, word_offsets, offsets, k, queries, pos_lo=0, pos_hi=0, anchor="start", second=True):
+        """reads_edist_anchored_batch of the packed words encode_batch writes (read r's ceil(len_r / 32) words start at words[word_offsets[r]])."""
+        w, woff, off, count = self._ragged_words(words, word_offsets, offsets)
+        return self._reads_anchored(self._lib.bitnuc_reads_edist_anchored_batch_packed, (_ptr(w), _ptr(woff), _ptr(off), count, int(k), self._anchor(anchor)), count,
+                                    queries, pos_lo, int(pos_hi), second)
+
+    def reads_pattern_edist_anchored_batch(self, seq, offsets, k, patterns, pos_lo=0, pos_hi=0, anchor="start", second=True):
+        """reads_edist_anchored_batch under pattern queries: a read base matches query position i when it is in the position's set."""
+        s, off, count = self._ragged_reads(seq, offsets)
+        return self._reads_anchored(self._lib.bitnuc_reads_pattern_edist_anchored_batch, (_ptr(s), _ptr(off), count, int(k), self._anchor(anchor)), count, patterns,
+                                    pos_lo, int(pos_hi), second, int(k))
+
+    def reads_pattern_edist_anchored_batch_packed(self, words, word_offsets, offsets, k, patterns, pos_lo=0, pos_hi=0, anchor="start", second=True):
+        """reads_pattern_edist_anchored_batch of the packed words encode_batch writes, without decoding them."""
+        w, woff, off, count = self._ragged_words(words, word_offsets, offsets)
+        return self._reads_anchored(self._lib.bitnuc_reads_pattern_edist_anchored_batch_packed, (_ptr(w), _ptr(woff), _ptr(off), count, int(k), self._anchor(anchor)),
+                                    count, patterns, pos_lo, int(pos_hi), second, int(k))
+
     def reads_pattern_anchored_batch(self, seq, offsets, k, patterns, pos_lo=0, pos_hi=0, anchor="start", second=True):
         """reads_hdist_anchored_batch under pattern queries (a ragged batch; the range counted from each read's start or end)."""
         s, off, count = self._ragged_reads(seq, offsets)
@@ -1155,6 +1182,40 @@ class Context:
         """reads_edist_anchored_packed_async under pattern queries."""
         self._reads_edist_async(self._lib.bitnuc_reads_pattern_edist_anchored_packed_async, d_words, read_len, count, k, d_patterns, n_queries,
                                 (d_best_query, d_best_end, d_best_dist), (d_second_query, d_second_end, d_second_dist), pos_lo, pos_hi)
+
+    def _reads_edist_batch_async(self, fn, head, k, d_queries, n_queries, d_best, d_second, pos_lo, pos_hi, anchor):
+        self._call_dev(fn, *head, int(k), self._anchor(anchor), int(pos_lo), int(pos_hi), _dev_ptr(d_queries), int(n_queries), *(_dev_ptr(a) for a in d_best),
+                       *(_dev_ptr(a) for a in d_second))
+
+    def reads_edist_anchored_batch_async(self, d_seq, d_offsets, count, total_bases, k, d_queries, n_queries, d_best_query, d_best_end, d_best_dist,
+                                         d_second_query=None, d_second_end=None, d_second_dist=None, pos_lo=0, pos_hi=0, anchor="start"):
+        """reads_edist_anchored_batch on device tensors (the arguments of reads_hdist_anchored_batch_async, ends where positions stood), asynchronous on
+        the context's stream; the table is trusted and read on the device; an invalid span byte is reported by the next sync()."""
+        self._reads_edist_batch_async(self._lib.bitnuc_reads_edist_anchored_batch_async, (_dev_ptr(d_seq), _dev_ptr(d_offsets), int(count), int(total_bases)), k,
+                                      d_queries, n_queries, (d_best_query, d_best_end, d_best_dist), (d_second_query, d_second_end, d_second_dist), pos_lo, pos_hi,
+                                      anchor)
+
+    def reads_edist_anchored_batch_packed_async(self, d_words, d_word_offsets, d_offsets, count, total_words, k, d_queries, n_queries, d_best_query, d_best_end,
+                                                d_best_dist, d_second_query=None, d_second_end=None, d_second_dist=None, pos_lo=0, pos_hi=0, anchor="start"):
+        """reads_edist_anchored_batch_async on the packed words encode_batch_dev writes (8-byte aligned; both tables u64 in device memory, trusted)."""
+        self._reads_edist_batch_async(self._lib.bitnuc_reads_edist_anchored_batch_packed_async,
+                                      (_dev_ptr(d_words), _dev_ptr(d_word_offsets), _dev_ptr(d_offsets), int(count), int(total_words)), k, d_queries, n_queries,
+                                      (d_best_query, d_best_end, d_best_dist), (d_second_query, d_second_end, d_second_dist), pos_lo, pos_hi, anchor)
+
+    def reads_pattern_edist_anchored_batch_async(self, d_seq, d_offsets, count, total_bases, k, d_patterns, n_queries, d_best_query, d_best_end, d_best_dist,
+                                                 d_second_query=None, d_second_end=None, d_second_dist=None, pos_lo=0, pos_hi=0, anchor="start"):
+        """reads_edist_anchored_batch_async under pattern queries."""
+        self._reads_edist_batch_async(self._lib.bitnuc_reads_pattern_edist_anchored_batch_async, (_dev_ptr(d_seq), _dev_ptr(d_offsets), int(count), int(total_bases)),
+                                      k, d_patterns, n_queries, (d_best_query, d_best_end, d_best_dist), (d_second_query, d_second_end, d_second_dist), pos_lo,
+                                      pos_hi, anchor)
+
+    def reads_pattern_edist_anchored_batch_packed_async(self, d_words, d_word_offsets, d_offsets, count, total_words, k, d_patterns, n_queries, d_best_query,
+                                                        d_best_end, d_best_dist, d_second_query=None, d_second_end=None, d_second_dist=None, pos_lo=0, pos_hi=0,
+                                                        anchor="start"):
+        """reads_edist_anchored_batch_packed_async under pattern queries."""
+        self._reads_edist_batch_async(self._lib.bitnuc_reads_pattern_edist_anchored_batch_packed_async,
+                                      (_dev_ptr(d_words), _dev_ptr(d_word_offsets), _dev_ptr(d_offsets), int(count), int(total_words)), k, d_patterns, n_queries,
+                                      (d_best_query, d_best_end, d_best_dist), (d_second_query, d_second_end, d_second_dist), pos_lo, pos_hi, anchor)
 
     def reads_pattern_anchored_batch_async(self, d_seq, d_offsets, count, total_bases, k, d_patterns, n_queries, d_best_query, d_best_pos, d_best_dist,
                                            d_second_query=None, d_second_pos=None, d_second_dist=None, pos_lo=0, pos_hi=0, anchor="start"):

@@ -1163,6 +1163,26 @@ int anchored_batch_host_loop(bitnuc_ctx *c, size_t count, const HQ *queries, siz
     return BITNUC_OK;
 }
 
+// ---- the INDEL-TOLERANT anchored best match and runner-up per read of a RAGGED batch: reads_edist_kernel under its other layout policy (AnchorBatchGeom),
+// the fixed form's tables and scratch (16 bytes per query), the ragged anchored forms' checks, tables and chunk loop; o.pos / o.pos2 hold the ends.
+// data: ASCII at any alignment, read r at bytes d_offsets[r] .. d_offsets[r + 1], or 8-byte aligned words, read r from word d_starts[r]; the tables in
+// device memory; count, nq, k >= 1, 1 <= offsets, offsets + k - 1 <= 64, pos_lo < 2^32 - 1
+template <bool PACKED, class HQ>
+int launch_reads_edist_batch(bitnuc_ctx *c, const void *data, const uint64_t *d_starts, const uint64_t *d_offsets, size_t count, size_t k, int anchor, size_t pos_lo,
+                             size_t offsets, const HQ *d_queries, size_t nq, const AnchorOut &o, unsigned long long *slot, bitnuc_err *err) {
+    if (int st = ensure_scratch(c, 10, nq * kEdistEntry, err)) return st;
+    u32x4 *tabs = reinterpret_cast<u32x4 *>(c->scratch[10]);
+    edist_tables_kernel<<<(unsigned)((nq + 63) / 64), 64, 0, c->stream>>>(dev_queries(d_queries), (unsigned)nq, (unsigned)k, tabs);
+    HIPCHK(hipGetLastError());
+    const AnchorBatchGeom g{reinterpret_cast<const unsigned long long *>(d_offsets), reinterpret_cast<const unsigned long long *>(d_starts), (unsigned)pos_lo,
+                            (unsigned)(anchor == BITNUC_ANCHOR_END), (unsigned)(offsets + k - 1), (unsigned)offsets, 0u, (unsigned)k, (unsigned)nq, 0u};
+    const size_t want = (count + kEdistBlock - 1) / kEdistBlock, cap = (size_t)c->num_cu * kEdistBlocksPerCu;
+    reads_edist_kernel<PACKED, AnchorBatchGeom><<<(unsigned)(want < cap ? want : cap), kEdistBlock, 0, c->stream>>>(
+        static_cast<const uint8_t *>(data), (unsigned long long)count, g, tabs, o.query, o.pos, o.dist, o.query2, o.pos2, o.dist2, slot);
+    HIPCHK(hipGetLastError());
+    return BITNUC_OK;
+}
+
 // ---- the mismatch histogram per query: the four forms, once for exact queries (uint64_t) and patterns (bitnuc_pattern) -----------------------------
 template <class HQ>
 int hist_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const HQ *d_queries, size_t n_queries, size_t n_bins, uint64_t *d_hist, bitnuc_err *err) {
@@ -2276,6 +2296,134 @@ int reads_anchored_batch_packed_host(bitnuc_ctx *c, const uint64_t *words, const
         });
 }
 
+// ---- the indel-tolerant anchored best match and runner-up per read of a ragged batch: the four forms above with the edit distance ----------------------
+template <class HQ>
+int reads_edist_batch_async(bitnuc_ctx *c, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k, int anchor, size_t pos_lo,
+                            size_t pos_hi, const HQ *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist,
+                            uint32_t *d_second_query, uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    const AnchorOut o{d_best_query, d_best_end, d_best_dist, d_second_dist, d_second_query, d_second_end};
+    bool done;
+    size_t offsets;
+    if (int st = check_anchored_batch(total_bases, total_bases, count, k, anchor, pos_lo, pos_hi, d_queries, reads_qmask<HQ>(), n_queries, o, d_offsets, nullptr, false, &done, &offsets, err))
+        return st;
+    if (done) return BITNUC_OK;
+    DeviceGuard g(c->device);
+    if (anchored_batch_no_window(total_bases, k, n_queries, offsets, pos_lo)) return anchored_fill_dev(c, count, o, err);
+    if (!d_seq) return fail(err, BITNUC_UNSUPPORTED);
+    unsigned long long *slot;
+    if (int st = take_slot(c, 0, &slot, err)) return st;
+    return launch_reads_edist_batch<false>(c, d_seq, nullptr, d_offsets, count, k, anchor, pos_lo, offsets, d_queries, n_queries, o, slot, err);
+}
+
+template <class HQ>
+int reads_edist_batch_packed_async(bitnuc_ctx *c, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
+                                   size_t total_words, size_t k, int anchor, size_t pos_lo, size_t pos_hi, const HQ *d_queries, size_t n_queries,
+                                   uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_end,
+                                   uint8_t *d_second_dist, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    const AnchorOut o{d_best_query, d_best_end, d_best_dist, d_second_dist, d_second_query, d_second_end};
+    bool done;
+    size_t offsets;
+    const uint64_t as_bases = total_words >= ((uint64_t)1 << 53) ? ~(uint64_t)0 : 32 * (uint64_t)total_words;
+    if (int st = check_anchored_batch(as_bases, total_words, count, k, anchor, pos_lo, pos_hi, d_queries, reads_qmask<HQ>(), n_queries, o, d_word_offsets, d_offsets, true, &done, &offsets,
+                                      err))
+        return st;
+    if (done) return BITNUC_OK;
+    DeviceGuard g(c->device);
+    if (anchored_batch_no_window(as_bases, k, n_queries, offsets, pos_lo)) return anchored_fill_dev(c, count, o, err);
+    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    return launch_reads_edist_batch<true>(c, d_words, d_word_offsets, d_offsets, count, k, anchor, pos_lo, offsets, d_queries, n_queries, o, nullptr, err);
+}
+
+template <class HQ>
+int reads_edist_batch_host(bitnuc_ctx *c, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, int anchor, size_t pos_lo, size_t pos_hi,
+                           const HQ *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query,
+                           uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err) {
+    clear_err(err);
+    const AnchorOut o{best_query, best_end, best_dist, second_dist, second_query, second_end};
+    bool done;
+    size_t width; // the range's offsets
+    if (int st = check_anchored_batch(0, 0, count, k, anchor, pos_lo, pos_hi, queries, reads_qmask<HQ>(), n_queries, o, offsets, nullptr, false, &done, &width, err)) return st;
+    if (done) return BITNUC_OK;
+    const BatchFault f = batch_check_tables(offsets, nullptr, count);
+    if (f.kind) return fail_batch_tables(f, err);
+    if (anchored_batch_no_window(offsets[count], k, n_queries, width, pos_lo)) { anchored_fill_host(count, o); return BITNUC_OK; }
+    if (!seq) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, anchored_work(width + k - 1, count, n_queries))) { // the widest span: what the cutoff is judged on
+        const long long bad = bitnuc_host::reads_edist_anchored_batch_small(seq, offsets, count, k, anchor, pos_lo, pos_hi, host_queries(queries), n_queries, best_query, best_end,
+                                                                            best_dist, second_query, second_end, second_dist);
+        if (bad >= 0) {
+            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = seq[bad]; err->index = (uint64_t)bad; }
+            return BITNUC_INVALID_BASE;
+        }
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    std::vector<uint64_t> tab; // the chunk's rebased table
+    return anchored_batch_host_loop(
+        c, count, queries, n_queries, o, err,
+        [&](size_t r0) { return batch_chunk_end(r0, count, kHostChunk, [&](size_t a, size_t b) { return offsets[b] - offsets[a]; }); },
+        [&](size_t r0, size_t m, const HQ *d_queries, const AnchorOut &d) {
+            const size_t b0 = (size_t)offsets[r0], bytes = (size_t)offsets[r0 + m] - b0;
+            if (anchored_batch_no_window(bytes, k, n_queries, width, pos_lo)) return anchored_fill_dev(c, m, d, err); // nothing to launch, nothing validated
+            if (int st = ensure_scratch(c, 0, bytes + 64, err)) return st;
+            if (int st = ensure_scratch(c, 4, (m + 1) * 8, err)) return st;
+            tab.resize(m + 1);
+            for (size_t i = 0; i <= m; ++i) tab[i] = offsets[r0 + i] - b0;
+            HIPCHK(hipMemcpyAsync(c->scratch[0], seq + b0, bytes, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(c->scratch[4], tab.data(), (m + 1) * 8, hipMemcpyHostToDevice, c->stream));
+            unsigned long long *slot;
+            if (int st = take_slot(c, b0, &slot, err)) return st;
+            return launch_reads_edist_batch<false>(c, c->scratch[0], nullptr, reinterpret_cast<const uint64_t *>(c->scratch[4]), m, k, anchor, pos_lo, width, d_queries,
+                                                   n_queries, d, slot, err);
+        });
+}
+
+template <class HQ>
+int reads_edist_batch_packed_host(bitnuc_ctx *c, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k, int anchor,
+                                  size_t pos_lo, size_t pos_hi, const HQ *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist,
+                                  uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err) {
+    clear_err(err);
+    const AnchorOut o{best_query, best_end, best_dist, second_dist, second_query, second_end};
+    bool done;
+    size_t width;
+    if (int st = check_anchored_batch(0, 0, count, k, anchor, pos_lo, pos_hi, queries, reads_qmask<HQ>(), n_queries, o, word_offsets, offsets, true, &done, &width, err)) return st;
+    if (done) return BITNUC_OK;
+    const BatchFault f = batch_check_tables(offsets, word_offsets, count);
+    if (f.kind) return fail_batch_tables(f, err);
+    if (anchored_batch_no_window(offsets[count], k, n_queries, width, pos_lo)) { anchored_fill_host(count, o); return BITNUC_OK; }
+    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, anchored_work(width + k - 1, count, n_queries))) {
+        bitnuc_host::reads_edist_anchored_batch_packed_small(words, word_offsets, offsets, count, k, anchor, pos_lo, pos_hi, host_queries(queries), n_queries, best_query, best_end,
+                                                             best_dist, second_query, second_end, second_dist);
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    std::vector<uint64_t> tab; // the chunk's two rebased tables: word_offsets, then offsets
+    return anchored_batch_host_loop(
+        c, count, queries, n_queries, o, err,
+        [&](size_t r0) { return batch_chunk_end(r0, count, kPackedChunkWords, [&](size_t a, size_t b) { return word_offsets[b] - word_offsets[a]; }); },
+        [&](size_t r0, size_t m, const HQ *d_queries, const AnchorOut &d) {
+            const size_t w0 = (size_t)word_offsets[r0], nw = (size_t)word_offsets[r0 + m] - w0;
+            if (nw == 0) return anchored_fill_dev(c, m, d, err);
+            if (int st = ensure_scratch(c, 0, nw * 8, err)) return st;
+            if (int st = ensure_scratch(c, 4, 2 * (m + 1) * 8, err)) return st;
+            tab.resize(2 * (m + 1));
+            for (size_t i = 0; i <= m; ++i) tab[i] = word_offsets[r0 + i] - w0, tab[m + 1 + i] = offsets[r0 + i] - offsets[r0];
+            HIPCHK(hipMemcpyAsync(c->scratch[0], words + w0, nw * 8, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(c->scratch[4], tab.data(), 2 * (m + 1) * 8, hipMemcpyHostToDevice, c->stream));
+            const uint64_t *d_tab = reinterpret_cast<const uint64_t *>(c->scratch[4]);
+            return launch_reads_edist_batch<true>(c, c->scratch[0], d_tab, d_tab + m + 1, m, k, anchor, pos_lo, width, d_queries, n_queries, d, nullptr, err);
+        });
+}
+
 // ---- the best match per read of a ragged batch ------------------------------------------------------------------------------------
 template <class HQ>
 int reads_best_batch_async(bitnuc_ctx *c, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k,
@@ -2663,6 +2811,59 @@ int bitnuc_reads_pattern_edist_anchored_packed(bitnuc_ctx *c, const uint64_t *wo
                                                uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err) {
     return reads_edist_packed_host(c, words, read_len, count, k, pos_lo, pos_hi, patterns, n_queries, best_query, best_end, best_dist, second_query,
                                    second_end, second_dist, err);
+}
+// the ragged twins
+int bitnuc_reads_edist_anchored_batch_async(bitnuc_ctx *c, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k, int anchor,
+                                            size_t pos_lo, size_t pos_hi, const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end,
+                                            uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err) {
+    return reads_edist_batch_async(c, d_seq, d_offsets, count, total_bases, k, anchor, pos_lo, pos_hi, d_queries, n_queries, d_best_query, d_best_end, d_best_dist,
+                                   d_second_query, d_second_end, d_second_dist, err);
+}
+int bitnuc_reads_edist_anchored_batch_packed_async(bitnuc_ctx *c, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
+                                                   size_t total_words, size_t k, int anchor, size_t pos_lo, size_t pos_hi, const uint64_t *d_queries, size_t n_queries,
+                                                   uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_end,
+                                                   uint8_t *d_second_dist, bitnuc_err *err) {
+    return reads_edist_batch_packed_async(c, d_words, d_word_offsets, d_offsets, count, total_words, k, anchor, pos_lo, pos_hi, d_queries, n_queries, d_best_query, d_best_end,
+                                          d_best_dist, d_second_query, d_second_end, d_second_dist, err);
+}
+int bitnuc_reads_edist_anchored_batch(bitnuc_ctx *c, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, int anchor, size_t pos_lo, size_t pos_hi,
+                                      const uint64_t *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query,
+                                      uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err) {
+    return reads_edist_batch_host(c, seq, offsets, count, k, anchor, pos_lo, pos_hi, queries, n_queries, best_query, best_end, best_dist, second_query, second_end, second_dist,
+                                  err);
+}
+int bitnuc_reads_edist_anchored_batch_packed(bitnuc_ctx *c, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k, int anchor,
+                                             size_t pos_lo, size_t pos_hi, const uint64_t *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_end,
+                                             uint8_t *best_dist, uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err) {
+    return reads_edist_batch_packed_host(c, words, word_offsets, offsets, count, k, anchor, pos_lo, pos_hi, queries, n_queries, best_query, best_end, best_dist, second_query,
+                                         second_end, second_dist, err);
+}
+int bitnuc_reads_pattern_edist_anchored_batch_async(bitnuc_ctx *c, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k, int anchor,
+                                                    size_t pos_lo, size_t pos_hi, const bitnuc_pattern *d_patterns, size_t n_queries, uint32_t *d_best_query,
+                                                    uint32_t *d_best_end, uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_end, uint8_t *d_second_dist,
+                                                    bitnuc_err *err) {
+    return reads_edist_batch_async(c, d_seq, d_offsets, count, total_bases, k, anchor, pos_lo, pos_hi, d_patterns, n_queries, d_best_query, d_best_end, d_best_dist,
+                                   d_second_query, d_second_end, d_second_dist, err);
+}
+int bitnuc_reads_pattern_edist_anchored_batch_packed_async(bitnuc_ctx *c, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
+                                                           size_t total_words, size_t k, int anchor, size_t pos_lo, size_t pos_hi, const bitnuc_pattern *d_patterns,
+                                                           size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist, uint32_t *d_second_query,
+                                                           uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err) {
+    return reads_edist_batch_packed_async(c, d_words, d_word_offsets, d_offsets, count, total_words, k, anchor, pos_lo, pos_hi, d_patterns, n_queries, d_best_query, d_best_end,
+                                          d_best_dist, d_second_query, d_second_end, d_second_dist, err);
+}
+int bitnuc_reads_pattern_edist_anchored_batch(bitnuc_ctx *c, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, int anchor, size_t pos_lo, size_t pos_hi,
+                                              const bitnuc_pattern *patterns, size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist,
+                                              uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err) {
+    return reads_edist_batch_host(c, seq, offsets, count, k, anchor, pos_lo, pos_hi, patterns, n_queries, best_query, best_end, best_dist, second_query, second_end,
+                                  second_dist, err);
+}
+int bitnuc_reads_pattern_edist_anchored_batch_packed(bitnuc_ctx *c, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
+                                                     int anchor, size_t pos_lo, size_t pos_hi, const bitnuc_pattern *patterns, size_t n_queries, uint32_t *best_query,
+                                                     uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist,
+                                                     bitnuc_err *err) {
+    return reads_edist_batch_packed_host(c, words, word_offsets, offsets, count, k, anchor, pos_lo, pos_hi, patterns, n_queries, best_query, best_end, best_dist, second_query,
+                                         second_end, second_dist, err);
 }
 
 // ---- pattern queries: a set of bases per position (bitnuc_pattern).  The twelve entry points below are the twins of the exact ones above: the same checks

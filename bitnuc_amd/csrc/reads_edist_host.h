@@ -8,7 +8,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "reads_best2_host.h" // ReadsTop2, reads_best2_store, reads_best_fill; PatternSets, pattern_of_2bit through scan_mfma_host.h
+#include "reads_anchored_batch_host.h" // the ragged forms' window rule: AnchorWindow, anchored_batch_window
+#include "reads_best2_host.h"          // ReadsTop2, reads_best2_store, reads_best_fill; PatternSets, pattern_of_2bit through scan_mfma_host.h
 
 namespace bitnuc_host {
 
@@ -97,6 +98,58 @@ static inline long long reads_edist_anchored_small(const uint8_t *reads, size_t 
         uint8_t codes[64];
         for (size_t j = 0; j < n; ++j) codes[j] = (uint8_t)(((s[j] >> 1) ^ (s[j] >> 2)) & 3u); // A 0, C 1, G 2, T 3, either case
         edist_store_top2(edist_read(codes, n, k, pos_lo, queries, nq), r, query, end, dist, query2, end2, dist2);
+    }
+    return -1;
+}
+
+// ---- the RAGGED batch (bitnuc_reads_edist_anchored_batch / _packed and their pattern twins): reads behind reads_batch_host.h's tables, a span per read.
+// Read r's span is the bases the ragged Hamming form looks at: with (first, n) = anchored_batch_window(len_r, ...), read_r[first, first + n + k - 1);
+// n == 0: no span, the fill, and the read is neither read nor validated.  Ends count from the read's start in both anchor modes.
+
+// packed reads behind validated tables (1 <= k <= 32, pos_lo <= pos_hi, pos_hi - pos_lo + k <= 64, nq >= 1); query2 / end2 / dist2 all NULL: the best
+// triple only
+template <class Q>
+static inline void reads_edist_anchored_batch_packed_small(const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
+                                                           int from_end, size_t pos_lo, size_t pos_hi, const Q *queries, size_t nq, uint32_t *query, uint32_t *end,
+                                                           uint8_t *dist, uint32_t *query2, uint32_t *end2, uint8_t *dist2) {
+    reads_best_fill(count, query, end, dist);
+    if (query2) reads_best_fill(count, query2, end2, dist2);
+    for (size_t r = 0; r < count; ++r) {
+        const AnchorWindow w = anchored_batch_window((size_t)(offsets[r + 1] - offsets[r]), k, from_end, pos_lo, pos_hi);
+        if (!w.n) continue;
+        const uint64_t *rw = words + word_offsets[r];
+        const size_t n = w.n + k - 1;
+        uint8_t codes[64];
+        for (size_t j = 0; j < n; ++j) codes[j] = (uint8_t)((rw[(w.first + j) / 32] >> (2 * ((w.first + j) % 32))) & 3u);
+        edist_store_top2(edist_read(codes, n, k, w.first, queries, nq), r, query, end, dist, query2, end2, dist2);
+    }
+}
+
+// back-to-back ASCII reads behind a validated table (the same conditions): -1 with the outputs written, or the index of the first invalid byte, in buffer
+// order, among the span bytes (outputs untouched).  Bytes outside the spans, and every byte of a read without a window, are never read.
+template <class Q>
+static inline long long reads_edist_anchored_batch_small(const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, int from_end, size_t pos_lo,
+                                                         size_t pos_hi, const Q *queries, size_t nq, uint32_t *query, uint32_t *end, uint8_t *dist, uint32_t *query2,
+                                                         uint32_t *end2, uint8_t *dist2) {
+    for (size_t r = 0; r < count; ++r) {
+        const AnchorWindow w = anchored_batch_window((size_t)(offsets[r + 1] - offsets[r]), k, from_end, pos_lo, pos_hi);
+        if (!w.n) continue;
+        const size_t at = (size_t)offsets[r] + w.first;
+        for (size_t i = 0; i < w.n + k - 1; ++i) {
+            const unsigned u = seq[at + i] & 0xDFu;
+            if (u != 'A' && u != 'C' && u != 'G' && u != 'T') return (long long)(at + i);
+        }
+    }
+    reads_best_fill(count, query, end, dist);
+    if (query2) reads_best_fill(count, query2, end2, dist2);
+    for (size_t r = 0; r < count; ++r) {
+        const AnchorWindow w = anchored_batch_window((size_t)(offsets[r + 1] - offsets[r]), k, from_end, pos_lo, pos_hi);
+        if (!w.n) continue;
+        const uint8_t *s = seq + offsets[r] + w.first;
+        const size_t n = w.n + k - 1;
+        uint8_t codes[64];
+        for (size_t j = 0; j < n; ++j) codes[j] = (uint8_t)(((s[j] >> 1) ^ (s[j] >> 2)) & 3u); // A 0, C 1, G 2, T 3, either case
+        edist_store_top2(edist_read(codes, n, k, w.first, queries, nq), r, query, end, dist, query2, end2, dist2);
     }
     return -1;
 }

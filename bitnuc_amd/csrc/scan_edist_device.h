@@ -26,9 +26,21 @@
 // ASCII: the lane loads the aligned dwords that hold a byte of its span (nothing outside such a dword is touched), aligns them (v_alignbyte), replaces the
 // bytes behind the span by 'A', validates with dword_residue (the first invalid span byte of the batch is latched by atomicMin) and packs four codes per
 // dword (enc4).  Packed: the one to three words that hold the span and a funnel shift; bits behind the span are never looked at.
+//
+// Two layouts, one kernel (the template parameter G, everything that differs under `if constexpr`), as reads_anchored_kernel has them.  Fixed (EdistGeom):
+// reads at a stride, one span for all of them -- the text above.  RAGGED (AnchorBatchGeom, bitnuc_reads_edist_anchored_batch*): reads behind an offsets
+// table, the range counted from each read's start or from its end.  A lane already is one read, so the layout is per-lane data: the lane loads its read's
+// table entries (AnchorEntries, one trip ahead) and derives a_r, its first span base, and n_r, its admissible offsets (anchored_lane); it loads and
+// validates its own n_r + k - 1 span bytes only (none when n_r == 0: such a lane writes the fill).  The recurrence loop stays wave-uniform, over the widest
+// span among the wave's lanes.  A lane with a shorter span is not disturbed by the steps behind it if their Eq is 0: such a column cannot lower D[k][j]
+// (D[i][j + 1] >= D[i][j] for every i when column j + 1 matches nowhere, by induction over i), and the running minimum keeps the first end.  So the
+// span sits at steps 0 .. len_r - 1 and Eq is ANDed with a per-step lane mask: one more vector instruction per (query, step), and none in a wave whose
+// lanes all have the widest span the arguments allow -- that case branches, wave-uniformly, to the fixed layout's loop.  The key's end field stays
+// relative to a_r; the store adds a_r.  The fixed instantiations' instructions are those of the kernel before it had a second layout.
 #pragma once
 #include "device_prims.h"
-#include "scan_mfma_device.h" // PatternSets, pattern_of_2bit, dword_residue, trip_invalid
+#include "scan_anchored_device.h" // the ragged layout: AnchorBatchGeom, AnchorEntries, anchored_entries, anchored_lane
+#include "scan_mfma_device.h"     // PatternSets, pattern_of_2bit, dword_residue, trip_invalid
 
 namespace bitnuc_dev {
 
@@ -38,7 +50,7 @@ constexpr unsigned kEdistEntry = 16;    // bytes of a query's table entry: Peq[4
 constexpr unsigned kEdistBlocksPerCu = 8; // the grid's bound: reads behind it are walked in a grid-stride loop
 
 // stride: bytes (ASCII) or words (packed) per read; n: the span's bases, k <= n <= 64
-struct EdistGeom { unsigned long long stride; unsigned pos_lo, n, k, nq; };
+struct EdistGeom { unsigned long long stride; unsigned pos_lo, n, k, nq; static constexpr bool kRagged = false; };
 
 // the match masks of a query, by its kind (the two QueryKind kinds): an exact query is the pattern of its singletons
 __device__ __forceinline__ PatternSets edist_sets(unsigned long long q, unsigned k) { return pattern_of_2bit(q, k); }
@@ -99,10 +111,11 @@ __device__ __forceinline__ void edist_span_packed(const uint64_t *__restrict__ w
     span[0] = (uint32_t)lo, span[1] = (uint32_t)(lo >> 32), span[2] = (uint32_t)hi, span[3] = (uint32_t)(hi >> 32);
 }
 
-// queries q0 .. q0 + U - 1 against the lane's span: every query's (dist, first end) merged into the running (best, second) keys
-template <int U>
+// queries q0 .. q0 + U - 1 against the lane's span: every query's (dist, first end) merged into the running (best, second) keys.  n: the steps, wave-uniform.
+// MASKED (the ragged layout's waves of unequal spans): the lane's span has len <= n bases, Eq is 0 at the steps behind them
+template <int U, bool MASKED = false>
 __device__ __forceinline__ void edist_queries(const uint32_t (&span)[4], unsigned n, unsigned k, const u32x4 *__restrict__ tabs, unsigned q0, uint32_t &b1,
-                                              uint32_t &b2) {
+                                              uint32_t &b2, unsigned len = 0) {
     uint32_t pa[U], pc[U], pg[U], pt[U], pv[U], mv[U], sc[U], key[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -124,10 +137,13 @@ __device__ __forceinline__ void edist_queries(const uint32_t (&span)[4], unsigne
             const bool hi = (codes & 2u) != 0u;
             codes >>= 2;
             const unsigned j = 16u * w + s; // the step's end is pos_lo + j + 1
+            uint32_t live = ~0u;
+            if constexpr (MASKED) live = j < len ? ~0u : 0u; // once per step, not per query
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const uint32_t eac = pa[u] ^ (pc[u] & lo), egt = pg[u] ^ (pt[u] & lo);
-                const uint32_t eq = hi ? egt : eac;
+                uint32_t eq = hi ? egt : eac;
+                if constexpr (MASKED) eq &= live;
                 const uint32_t xv = eq | mv[u];
                 const uint32_t xh = (((eq & pv[u]) + pv[u]) ^ pv[u]) | eq;
                 uint32_t ph = mv[u] | ~(xh | pv[u]);
@@ -150,39 +166,90 @@ __device__ __forceinline__ void edist_queries(const uint32_t (&span)[4], unsigne
     }
 }
 
-// a key -> the read's triple; all-ones (no query but the winner): the fill
-__device__ __forceinline__ void edist_store(uint32_t key, unsigned pos_lo, unsigned long long r, uint32_t *__restrict__ query, uint32_t *__restrict__ end,
+// a key -> the read's triple; all-ones (no query but the winner): the fill.  first: the offset in the read of the span's first base
+__device__ __forceinline__ void edist_store(uint32_t key, unsigned first, unsigned long long r, uint32_t *__restrict__ query, uint32_t *__restrict__ end,
                                             uint8_t *__restrict__ dist) {
     const bool none = key == ~0u;
     query[r] = none ? 0xFFFFFFFFu : (key >> 6) & 0xFFFFu;
-    end[r] = none ? 0xFFFFFFFFu : pos_lo + (key & 63u) + 1u;
+    end[r] = none ? 0xFFFFFFFFu : first + (key & 63u) + 1u;
     dist[r] = none ? (uint8_t)0xFF : (uint8_t)(key >> 22);
 }
 
+// every query against the lane's span (edist_queries' parameters): groups of kEdistInterleave, then of 2 and 1
+template <bool MASKED>
+__device__ __forceinline__ void edist_all_queries(const uint32_t (&span)[4], unsigned n, unsigned k, unsigned nq, const u32x4 *__restrict__ tabs, uint32_t &b1,
+                                                  uint32_t &b2, unsigned len) {
+    unsigned q = 0;
+#pragma unroll 1
+    for (; q + kEdistInterleave <= nq; q += kEdistInterleave) edist_queries<kEdistInterleave, MASKED>(span, n, k, tabs, q, b1, b2, len);
+    if (nq - q >= 2u) { edist_queries<2, MASKED>(span, n, k, tabs, q, b1, b2, len); q += 2u; }
+    if (nq - q >= 1u) edist_queries<1, MASKED>(span, n, k, tabs, q, b1, b2, len);
+}
+
+// the largest x <= 64 among the wave's active lanes, as a wave-uniform value: a binary search with seven ballots (no cross-lane data path)
+__device__ __forceinline__ unsigned edist_wave_max(unsigned x) {
+    unsigned m = 0;
+#pragma unroll
+    for (unsigned b = 64u; b; b >>= 1)
+        if (__builtin_amdgcn_ballot_w64(x >= (m | b))) m |= b;
+    return m;
+}
+
 // data: the reads (ASCII bytes at any alignment, or 8-byte aligned packed words); count >= 1, 1 <= k <= 32, k <= n <= 64, 1 <= nq <= 65536; tabs: nq entries
-// of edist_tables_kernel.  sq == nullptr: the best triple only.  A bounded grid; a lane walks reads at the grid's stride.
-template <bool PACKED>
+// of edist_tables_kernel.  sq == nullptr: the best triple only.  A bounded grid; a lane walks reads at the grid's stride.  G: the layout policy (EdistGeom:
+// a fixed stride, one span for all reads; AnchorBatchGeom: tables, a span per read, of at most g.span = g.offsets + k - 1 bases; its lg and ntiles are unused).
+template <bool PACKED, class G = EdistGeom>
 __global__ void __launch_bounds__(kEdistBlock)
-reads_edist_kernel(const uint8_t *__restrict__ data, unsigned long long count, const EdistGeom g, const u32x4 *__restrict__ tabs, uint32_t *__restrict__ bq,
+reads_edist_kernel(const uint8_t *__restrict__ data, unsigned long long count, const G g, const u32x4 *__restrict__ tabs, uint32_t *__restrict__ bq,
                    uint32_t *__restrict__ be, uint8_t *__restrict__ bd, uint32_t *__restrict__ sq, uint32_t *__restrict__ se, uint8_t *__restrict__ sd,
                    unsigned long long *__restrict__ slot) {
     const unsigned long long step = (unsigned long long)gridDim.x * kEdistBlock;
-    for (unsigned long long r = (unsigned long long)blockIdx.x * kEdistBlock + threadIdx.x; r < count; r += step) {
-        uint32_t span[4];
-        if constexpr (PACKED) {
-            edist_span_packed(reinterpret_cast<const uint64_t *>(data) + r * g.stride, g.pos_lo, g.n, span);
-        } else {
-            const unsigned long long at = r * g.stride + g.pos_lo;
-            if (__builtin_expect(trip_invalid(edist_span_ascii(data + at, g.n, span)), 0)) rescan_bytes(data, at, g.n, slot);
-        }
-        uint32_t b1 = ~0u, b2 = ~0u;
-        unsigned q = 0;
+    if constexpr (!G::kRagged) {
+        for (unsigned long long r = (unsigned long long)blockIdx.x * kEdistBlock + threadIdx.x; r < count; r += step) {
+            uint32_t span[4];
+            if constexpr (PACKED) {
+                edist_span_packed(reinterpret_cast<const uint64_t *>(data) + r * g.stride, g.pos_lo, g.n, span);
+            } else {
+                const unsigned long long at = r * g.stride + g.pos_lo;
+                if (__builtin_expect(trip_invalid(edist_span_ascii(data + at, g.n, span)), 0)) rescan_bytes(data, at, g.n, slot);
+            }
+            uint32_t b1 = ~0u, b2 = ~0u;
+            unsigned q = 0; // (spelled as before the kernel had a second layout, not through edist_all_queries: the generated code is the same)
 #pragma unroll 1
-        for (; q + kEdistInterleave <= g.nq; q += kEdistInterleave) edist_queries<kEdistInterleave>(span, g.n, g.k, tabs, q, b1, b2);
-        if (g.nq - q >= 2u) { edist_queries<2>(span, g.n, g.k, tabs, q, b1, b2); q += 2u; }
-        if (g.nq - q >= 1u) edist_queries<1>(span, g.n, g.k, tabs, q, b1, b2);
-        edist_store(b1, g.pos_lo, r, bq, be, bd);
-        if (sq) edist_store(b2, g.pos_lo, r, sq, se, sd);
+            for (; q + kEdistInterleave <= g.nq; q += kEdistInterleave) edist_queries<kEdistInterleave>(span, g.n, g.k, tabs, q, b1, b2);
+            if (g.nq - q >= 2u) { edist_queries<2>(span, g.n, g.k, tabs, q, b1, b2); q += 2u; }
+            if (g.nq - q >= 1u) edist_queries<1>(span, g.n, g.k, tabs, q, b1, b2);
+            edist_store(b1, g.pos_lo, r, bq, be, bd);
+            if (sq) edist_store(b2, g.pos_lo, r, sq, se, sd);
+        }
+    } else {
+        unsigned long long r = (unsigned long long)blockIdx.x * kEdistBlock + threadIdx.x;
+        AnchorEntries ahead{0, 0, 0}; // the table entries of the lane's next read
+        if (r < count) ahead = anchored_entries<PACKED>(g, r);
+        for (; r < count; r += step) {
+            const AnchorLane L = anchored_lane<PACKED>(g, ahead);
+            const unsigned len = L.n ? L.n + g.k - 1u : 0u; // the span bases of THIS read: nothing behind them is loaded or validated
+            uint32_t span[4] = {0u, 0u, 0u, 0u};
+            if (len) {
+                if constexpr (PACKED) {
+                    edist_span_packed(reinterpret_cast<const uint64_t *>(data) + L.base, L.a, len, span);
+                } else {
+                    const unsigned long long at = L.base + L.a;
+                    if (__builtin_expect(trip_invalid(edist_span_ascii(data + at, len, span)), 0)) rescan_bytes(data, at, len, slot);
+                }
+            }
+            if (r + step < count) ahead = anchored_entries<PACKED>(g, r + step); // behind this read's loads: the next read's entries
+            uint32_t b1 = ~0u, b2 = ~0u;
+            if (__builtin_amdgcn_ballot_w64(len != g.span) == 0ull) { // every lane has the widest span: the fixed layout's loop
+                edist_all_queries<false>(span, g.span, g.k, g.nq, tabs, b1, b2, 0u);
+            } else {
+                const unsigned widest = edist_wave_max(len); // wave-uniform; 0: no lane of the wave has a window
+                if (widest) edist_all_queries<true>(span, widest, g.k, g.nq, tabs, b1, b2, len);
+                if (!len) b1 = b2 = ~0u; // the masked steps of a lane without a span made keys of no window
+            }
+            edist_store(b1, L.a, r, bq, be, bd);
+            if (sq) edist_store(b2, L.a, r, sq, se, sd);
+        }
     }
 }
 

@@ -570,6 +570,58 @@ class Context {
             return NucleotideError::from_c(e);
         return b;
     }
+    // the indel-tolerant anchored match of a ragged batch (bitnuc_reads_edist_anchored_batch*): reads_hdist_anchored_batch's arguments and window rule, the
+    // edit distance of each query to the best substring of each read's own span; `pos` of the result holds the END, counted from the read's start
+    Result<ReadsBest2> reads_edist_anchored_batch(Bytes seq, const std::vector<uint64_t> &offsets, size_t k, const std::vector<uint64_t> &queries,
+                                                    size_t pos_lo = 0, size_t pos_hi = 0, int anchor = BITNUC_ANCHOR_START) const {
+        const size_t count = offsets.empty() ? 0 : offsets.size() - 1;
+        if (count && seq.len < offsets.back()) return NucleotideError::invalid_length(seq.len);
+        ReadsBest2 b{reads_outputs(count), reads_outputs(count)};
+        bitnuc_err e;
+        if (bitnuc_reads_edist_anchored_batch(ctx_, seq.ptr, offsets.data(), count, k, anchor, pos_lo, pos_hi, queries.data(), queries.size(), b.best.query.data(),
+                                                b.best.pos.data(), b.best.dist.data(), b.second.query.data(), b.second.pos.data(), b.second.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
+    Result<ReadsBest2> reads_edist_anchored_batch_packed(Words words, const std::vector<uint64_t> &word_offsets, const std::vector<uint64_t> &offsets, size_t k,
+                                                           const std::vector<uint64_t> &queries, size_t pos_lo = 0, size_t pos_hi = 0,
+                                                           int anchor = BITNUC_ANCHOR_START) const {
+        const size_t count = offsets.empty() ? 0 : offsets.size() - 1;
+        if (word_offsets.size() != offsets.size()) return NucleotideError::unsupported();
+        if (count && words.len < word_offsets.back()) return NucleotideError::invalid_length(words.len);
+        ReadsBest2 b{reads_outputs(count), reads_outputs(count)};
+        bitnuc_err e;
+        if (bitnuc_reads_edist_anchored_batch_packed(ctx_, words.ptr, word_offsets.data(), offsets.data(), count, k, anchor, pos_lo, pos_hi, queries.data(),
+                                                       queries.size(), b.best.query.data(), b.best.pos.data(), b.best.dist.data(), b.second.query.data(),
+                                                       b.second.pos.data(), b.second.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
+    Result<ReadsBest2> reads_pattern_edist_anchored_batch(Bytes seq, const std::vector<uint64_t> &offsets, size_t k, const std::vector<bitnuc_pattern> &patterns,
+                                                    size_t pos_lo = 0, size_t pos_hi = 0, int anchor = BITNUC_ANCHOR_START) const {
+        const size_t count = offsets.empty() ? 0 : offsets.size() - 1;
+        if (count && seq.len < offsets.back()) return NucleotideError::invalid_length(seq.len);
+        ReadsBest2 b{reads_outputs(count), reads_outputs(count)};
+        bitnuc_err e;
+        if (bitnuc_reads_pattern_edist_anchored_batch(ctx_, seq.ptr, offsets.data(), count, k, anchor, pos_lo, pos_hi, patterns.data(), patterns.size(), b.best.query.data(),
+                                                b.best.pos.data(), b.best.dist.data(), b.second.query.data(), b.second.pos.data(), b.second.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
+    Result<ReadsBest2> reads_pattern_edist_anchored_batch_packed(Words words, const std::vector<uint64_t> &word_offsets, const std::vector<uint64_t> &offsets, size_t k,
+                                                           const std::vector<bitnuc_pattern> &patterns, size_t pos_lo = 0, size_t pos_hi = 0,
+                                                           int anchor = BITNUC_ANCHOR_START) const {
+        const size_t count = offsets.empty() ? 0 : offsets.size() - 1;
+        if (word_offsets.size() != offsets.size()) return NucleotideError::unsupported();
+        if (count && words.len < word_offsets.back()) return NucleotideError::invalid_length(words.len);
+        ReadsBest2 b{reads_outputs(count), reads_outputs(count)};
+        bitnuc_err e;
+        if (bitnuc_reads_pattern_edist_anchored_batch_packed(ctx_, words.ptr, word_offsets.data(), offsets.data(), count, k, anchor, pos_lo, pos_hi, patterns.data(),
+                                                       patterns.size(), b.best.query.data(), b.best.pos.data(), b.best.dist.data(), b.second.query.data(),
+                                                       b.second.pos.data(), b.second.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
     Result<std::vector<uint64_t>> kmer_hdist_hits_packed(Words words, size_t n, size_t k, uint64_t query, unsigned tau, std::vector<uint8_t> *hit_dist = nullptr) const {
         uint64_t total = 0;
         bitnuc_err e;

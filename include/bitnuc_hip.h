@@ -741,8 +741,9 @@ int bitnuc_reads_pattern_best_batch_packed(bitnuc_ctx *ctx, const uint64_t *word
  * query, 0.55 / 0.50 at 8, 4.0 / 3.9 at 64, 31.5 / 30.8 at 512; k = 31, eight offsets (n = 38): 0.39 / 0.17, 1.04 / 0.98, 7.8 / 7.7, 62.3 / 61.7 ms:
  * 0.47 - 1.2 x the time of bitnuc_reads_hdist_anchored*_async on the same arguments at 1 query, 2.0 - 3.5 x at 8, 5.5 - 12.3 x at 64, 7.1 - 18.9 x at 512
  * (another answer: the price of indel tolerance); the pattern twins cost what the exact forms cost.
- * Out of scope: the ragged twins (offsets tables), the whole-read (unanchored) form, reporting the alignment's start, k > 32 and spans above 64 bases,
- * affine gaps, reverse-complement queries (callers add the reverse complements to the query list themselves). */
+ * The ragged twins (offsets tables): bitnuc_reads_edist_anchored_batch* below.  Out of scope: the whole-read (unanchored) form, reporting the
+ * alignment's start, k > 32 and spans above 64 bases, affine gaps, reverse-complement queries (callers add the reverse complements to the query list
+ * themselves). */
 int bitnuc_reads_edist_anchored_async(bitnuc_ctx *ctx, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
                                       const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist,
                                       uint32_t *d_second_query, uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err);
@@ -768,6 +769,82 @@ int bitnuc_reads_pattern_edist_anchored(bitnuc_ctx *ctx, const uint8_t *reads, s
 int bitnuc_reads_pattern_edist_anchored_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
                                                const bitnuc_pattern *patterns, size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist,
                                                uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err);
+
+/* ---- INDEL-TOLERANT anchored best match and runner-up per read of a RAGGED batch (a 3' barcode, adapter or primer with an inserted or deleted base in
+ * the last k (+ slack) bases of trimmed or long reads): the layout and window rule of bitnuc_reads_hdist_anchored_batch* with the distance and results
+ * of bitnuc_reads_edist_anchored* ----
+ * Arguments: exactly those of the corresponding bitnuc_reads_hdist_anchored_batch* / bitnuc_reads_pattern_anchored_batch* function, with best_end /
+ * second_end where best_pos / second_pos stood.
+ * Layout: that of bitnuc_reads_hdist_anchored_batch*, word for word: `offsets` has count + 1 entries, packed reads start at words[word_offsets[r]], bits
+ * above a read's last base are ignored, a zero-length read has no words.
+ * Span of read r.  len_r is its length, last_r = len_r - k.  The admissible window offsets are those of the ragged Hamming form: START: pos_lo <= i <=
+ * min(pos_hi, last_r); END: pos_lo <= last_r - i <= pos_hi and i >= 0.  With a_r the first admissible offset and n_r their number, the span is
+ * read_r[a_r .. a_r + n_r + k - 1): exactly the bases the Hamming form looks at.  A read with n_r == 0 (len_r < k, too short for pos_lo, empty) has no
+ * span and gets the fill (UINT32_MAX, UINT32_MAX, 0xFF) in all written outputs.  The widest span, pos_hi - pos_lo + k, is judged on the arguments alone
+ * (computed without overflow; a value that does not fit is reported as SIZE_MAX): above BITNUC_ANCHOR_MAX_SPAN -> UNSUPPORTED (err.value = that span).
+ * pos_hi = SIZE_MAX does NOT mean "to the end of the read" here -- the END anchor serves that purpose.  pos_hi < pos_lo is an empty range: every read
+ * gets the fill.
+ * Distance and results: the definition of the bitnuc_reads_edist_anchored* block, applied to each read's own span t_1 .. t_n, n = n_r + k - 1:
+ * D[0][j] = 0, so the substring starts and ends anywhere in the span; end = a_r + (the smallest j with the smallest D[k][j]), one past the last aligned
+ * base, counted from the read's START in both anchor modes.  The best triple is the lexicographic minimum of (edist, query, end), the second triple the
+ * minimum over the other queries (an equal duplicate query at a higher index is the runner-up, one query gives the fill in the second triple).  The
+ * second triple's pointers may be ALL NULL; one or two NULL -> UNSUPPORTED.  Exactly [0, count) of each output is written; the dist arrays may have any
+ * byte offset.  Deterministic.
+ * Identities.  On a batch of equal lengths L, START (lo, hi) equals bitnuc_reads_edist_anchored*(read_len = L, lo, hi) byte for byte, and END (e_lo,
+ * e_hi) equals it with pos_lo = L - k - e_hi, pos_hi = L - k - e_lo, provided L - k >= e_hi.  For equal arguments best_dist <= the best_dist of
+ * bitnuc_reads_hdist_anchored_batch* on every read.  The pattern forms on singleton patterns (bitnuc_pattern_from_2bit) equal the exact forms byte
+ * for byte.
+ * Validation.  Of a read with a span only its n_r + k - 1 span bytes are read and validated; a read without a span is neither read nor validated.  The
+ * first invalid span byte in buffer order -> INVALID_BASE with its absolute index, latched once per call for bitnuc_ctx_sync() by the _async forms
+ * (outputs then unspecified); the host forms below the cutoff leave the outputs untouched.  (The ASCII kernel loads aligned 4-byte words that hold a
+ * span byte: at most 3 bytes before and after a span are touched, never examined; a word that holds no span byte is never touched.)
+ * Checks, in order: (1) - (10) of the bitnuc_reads_hdist_anchored_batch* block, word for word.  Nothing is written on an argument error.
+ * The _async forms TRUST their tables (as bitnuc_reads_hdist_best_batch*_async), have the _dev contract, use the context's stream, do no host
+ * synchronisation but the growth of context scratch (16 bytes per query, as the fixed edit-distance form) and can be captured into a hipGraph after a
+ * warm-up; the tables, the reads and the queries are read on the device at every replay, so a replay after the lengths changed (same count and totals)
+ * gives the new answers.  The host forms judge count x the widest span x n_queries (saturated) against the host cutoff: below it they run on the host
+ * (ctx may be NULL), above it through the context in chunks of whole reads with rebased tables; INVALID_BASE indices stay absolute.
+ * Cost: the fixed form's kernel under a ragged layout policy -- every lane loads its own read's table entries (one trip ahead) and its own span; the
+ * recurrence loop runs, wave-uniformly, over the widest span among the wave's 64 reads, with Eq forced to 0 behind a shorter span (one more vector
+ * select per (query, step) and one compare per step: 21.25 vector instructions instead of 20); a wave whose reads all have the widest span the arguments allow runs the fixed form's loop.
+ * Measured on 6,666,667 reads of 100 .. 200 bases (10^9 bases), one MI355X (profiles/r19_reads_edist_batch.json), ASCII / packed, six outputs, END anchor:
+ * k = 16, four offsets: 0.26 / 0.12 ms at 1 query, 0.58 / 0.55 at 8, 4.0 / 4.2 at 64, 31.6 / 33.2 at 512; k = 31, eight offsets: 0.36 / 0.18, 1.07 / 1.05,
+ * 7.9 / 8.2, 62.5 / 65.5 ms: 0.11 - 0.89 x the time of a device gather of the spans into a compact batch plus bitnuc_reads_edist_anchored*_async on it up
+ * to 64 queries, 0.97 (ASCII) and 1.03 - 1.05 (packed) x at 512, where the recurrence is all there is.  On equal-length reads the fixed form above gives
+ * the same answers; this form takes 1.00 - 1.01 x (ASCII) and 1.06 - 1.08 x (packed) of its time at 64 queries and more: a fixed-length batch belongs
+ * there.
+ * Out of scope: a per-read offset table as an argument, spans above 64 bases, the whole-read (unanchored) form, reporting the alignment's start,
+ * reverse-complement queries. */
+int bitnuc_reads_edist_anchored_batch_async(bitnuc_ctx *ctx, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k, int anchor,
+                                            size_t pos_lo, size_t pos_hi, const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end,
+                                            uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err);
+int bitnuc_reads_edist_anchored_batch_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
+                                                   size_t total_words, size_t k, int anchor, size_t pos_lo, size_t pos_hi, const uint64_t *d_queries, size_t n_queries,
+                                                   uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist, uint32_t *d_second_query,
+                                                   uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err);
+int bitnuc_reads_edist_anchored_batch(bitnuc_ctx *ctx, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, int anchor, size_t pos_lo, size_t pos_hi,
+                                      const uint64_t *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query,
+                                      uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err);
+int bitnuc_reads_edist_anchored_batch_packed(bitnuc_ctx *ctx, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
+                                             int anchor, size_t pos_lo, size_t pos_hi, const uint64_t *queries, size_t n_queries, uint32_t *best_query,
+                                             uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err);
+/* the pattern twins: a set of bases per query position (bitnuc_pattern); everything else as above */
+int bitnuc_reads_pattern_edist_anchored_batch_async(bitnuc_ctx *ctx, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k,
+                                                    int anchor, size_t pos_lo, size_t pos_hi, const bitnuc_pattern *d_patterns, size_t n_queries, uint32_t *d_best_query,
+                                                    uint32_t *d_best_end, uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_end,
+                                                    uint8_t *d_second_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_edist_anchored_batch_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets,
+                                                           size_t count, size_t total_words, size_t k, int anchor, size_t pos_lo, size_t pos_hi,
+                                                           const bitnuc_pattern *d_patterns, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end,
+                                                           uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_end, uint8_t *d_second_dist,
+                                                           bitnuc_err *err);
+int bitnuc_reads_pattern_edist_anchored_batch(bitnuc_ctx *ctx, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, int anchor, size_t pos_lo,
+                                              size_t pos_hi, const bitnuc_pattern *patterns, size_t n_queries, uint32_t *best_query, uint32_t *best_end,
+                                              uint8_t *best_dist, uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_edist_anchored_batch_packed(bitnuc_ctx *ctx, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count,
+                                                     size_t k, int anchor, size_t pos_lo, size_t pos_hi, const bitnuc_pattern *patterns, size_t n_queries,
+                                                     uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_end,
+                                                     uint8_t *second_dist, bitnuc_err *err);
 
 /* ---- analysis on packed words (the callers just above the codec) ------ */
 /* BaseCount::base_counts / GCContent::gc_content of a packed sequence

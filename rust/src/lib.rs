@@ -665,6 +665,67 @@ pub fn reads_pattern_anchored_batch_packed(words: &[u64], word_offsets: &[u64], 
     if st == ffi::BITNUC_OK { Ok(((query, pos, dist), (query2, pos2, dist2))) } else { Err(to_err(&e)) }
 }
 
+/// `reads_edist_anchored` of a ragged batch (read `r` is `seq[offsets[r]..offsets[r + 1]]`): the edit distance of each query to the best substring of each
+/// read's own span, the bases `reads_hdist_anchored_batch` looks at for the same `(anchor, pos_lo, pos_hi)`; ends count from the read's start.
+pub fn reads_edist_anchored_batch(seq: &[u8], offsets: &[u64], k: usize, anchor: Anchor, pos_lo: usize, pos_hi: usize, queries: &[u64]) -> Result<ReadsBest2, NucleotideError> {
+    let count = offsets.len().saturating_sub(1);
+    assert!(count == 0 || seq.len() as u64 >= offsets[count], "seq holds offsets[count] bases");
+    let (mut query, mut end, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let (mut query2, mut end2, mut dist2) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_edist_anchored_batch(c, seq.as_ptr(), offsets.as_ptr(), count, k, anchor.raw(), pos_lo, pos_hi, queries.as_ptr(), queries.len(), query.as_mut_ptr(),
+                                                 end.as_mut_ptr(), dist.as_mut_ptr(), query2.as_mut_ptr(), end2.as_mut_ptr(), dist2.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(((query, end, dist), (query2, end2, dist2))) } else { Err(to_err(&e)) }
+}
+
+/// `reads_edist_anchored_batch` of the packed words `encode_batch` writes (read `r`'s words start at `words[word_offsets[r]]`), without decoding them.
+pub fn reads_edist_anchored_batch_packed(words: &[u64], word_offsets: &[u64], offsets: &[u64], k: usize, anchor: Anchor, pos_lo: usize, pos_hi: usize, queries: &[u64]) -> Result<ReadsBest2, NucleotideError> {
+    let count = offsets.len().saturating_sub(1);
+    assert!(word_offsets.len() == offsets.len(), "one word offset per base offset");
+    assert!(count == 0 || words.len() as u64 >= word_offsets[count], "words holds word_offsets[count] words");
+    let (mut query, mut end, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let (mut query2, mut end2, mut dist2) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_edist_anchored_batch_packed(c, words.as_ptr(), word_offsets.as_ptr(), offsets.as_ptr(), count, k, anchor.raw(), pos_lo, pos_hi, queries.as_ptr(),
+                                                        queries.len(), query.as_mut_ptr(), end.as_mut_ptr(), dist.as_mut_ptr(), query2.as_mut_ptr(), end2.as_mut_ptr(),
+                                                        dist2.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(((query, end, dist), (query2, end2, dist2))) } else { Err(to_err(&e)) }
+}
+
+/// `reads_edist_anchored_batch` under pattern queries.
+pub fn reads_pattern_edist_anchored_batch(seq: &[u8], offsets: &[u64], k: usize, anchor: Anchor, pos_lo: usize, pos_hi: usize, patterns: &[Pattern]) -> Result<ReadsBest2, NucleotideError> {
+    let count = offsets.len().saturating_sub(1);
+    assert!(count == 0 || seq.len() as u64 >= offsets[count], "seq holds offsets[count] bases");
+    let (mut query, mut end, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let (mut query2, mut end2, mut dist2) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_pattern_edist_anchored_batch(c, seq.as_ptr(), offsets.as_ptr(), count, k, anchor.raw(), pos_lo, pos_hi, patterns.as_ptr(), patterns.len(), query.as_mut_ptr(),
+                                                 end.as_mut_ptr(), dist.as_mut_ptr(), query2.as_mut_ptr(), end2.as_mut_ptr(), dist2.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(((query, end, dist), (query2, end2, dist2))) } else { Err(to_err(&e)) }
+}
+
+/// `reads_pattern_edist_anchored_batch` of the packed words `encode_batch` writes, without decoding them.
+pub fn reads_pattern_edist_anchored_batch_packed(words: &[u64], word_offsets: &[u64], offsets: &[u64], k: usize, anchor: Anchor, pos_lo: usize, pos_hi: usize, patterns: &[Pattern]) -> Result<ReadsBest2, NucleotideError> {
+    let count = offsets.len().saturating_sub(1);
+    assert!(word_offsets.len() == offsets.len(), "one word offset per base offset");
+    assert!(count == 0 || words.len() as u64 >= word_offsets[count], "words holds word_offsets[count] words");
+    let (mut query, mut end, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let (mut query2, mut end2, mut dist2) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_reads_pattern_edist_anchored_batch_packed(c, words.as_ptr(), word_offsets.as_ptr(), offsets.as_ptr(), count, k, anchor.raw(), pos_lo, pos_hi, patterns.as_ptr(),
+                                                        patterns.len(), query.as_mut_ptr(), end.as_mut_ptr(), dist.as_mut_ptr(), query2.as_mut_ptr(), end2.as_mut_ptr(),
+                                                        dist2.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(((query, end, dist), (query2, end2, dist2))) } else { Err(to_err(&e)) }
+}
+
 /// `reads_hdist_best_batch` under pattern queries.
 pub fn reads_pattern_best_batch(seq: &[u8], offsets: &[u64], k: usize, patterns: &[Pattern]) -> Result<(Vec<u32>, Vec<u32>, Vec<u8>), NucleotideError> {
     let count = offsets.len().saturating_sub(1);
