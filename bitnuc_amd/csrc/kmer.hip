@@ -3,7 +3,7 @@
 // Hamming scan (config 5: packing/mod.rs:80-110 o hamming/scalar.rs:11-48) and bulk hdist (hamming/multi.rs:121-160).
 // Kernels: kmer_device.h; config 5 on the matrix cores: scan_mfma_device.h; the same scan and count on packed words: scan_packed_device.h; the hit
 // lists of both: scan_hits_device.h; the count for many queries at once: scan_multi_device.h; the best match per query: scan_best_device.h; the mismatch histogram per query: scan_hist_device.h; the best match per read of a
-// fixed-length batch: scan_reads_device.h; ... of a ragged batch: scan_reads_batch_device.h.
+// fixed-length batch: scan_reads_device.h; ... of a ragged batch: scan_reads_batch_device.h.  The host side of every per-read matcher: reads_dispatch.h.
 #include "runtime.h"
 #include "kmer_device.h"
 #include "scan_mfma_device.h"
@@ -36,6 +36,12 @@ using namespace bitnuc_rt;
 using namespace bitnuc_host;
 
 namespace {
+// a host-pointer call's first invalid byte as its error
+inline int fail_invalid_base(bitnuc_err *err, uint8_t byte, uint64_t index) {
+    if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = byte; err->index = index; }
+    return BITNUC_INVALID_BASE;
+}
+
 // ---- the legs of a k-mer batch: templates the product instantiates with the shipped values (ShippedLegs) and the evidence build with others
 template <bool AL, bool NL, bool NS, int U>
 hipError_t dense_t(bitnuc_ctx *c, const uint8_t *kmers, size_t k, unsigned long long items, unsigned long long *o, unsigned long long *slot, int kb) {
@@ -704,485 +710,6 @@ struct ScanJob {
     }
 };
 
-// ---- the best match per read of a fixed-length batch (scan_reads_device.h).  Context scratch 10 holds the per-read keys (one u64 per read, all-ones = no
-// admissible window yet) and behind them the tables (one BestTable per query, built in-stream from d_queries); a launch recorded into a hipGraph keeps
-// it (ensure_scratch: warm up with the same or larger (count, n_queries) before capturing).  The keys are set to all-ones first in the same stream,
-// the waves take their per-read minima into them and reads_finish_kernel writes query[] / pos[] / dist[].  The grid: the best match's (one workgroup
-// per CU at most x the query blocks); a batch whose period is below a segment, or too small for a round, spreads its windows over more workgroups.
-// The runner-up (bitnuc_reads_hdist_best2*) keeps two key arrays there: keys1 with one spare entry (count + 1: the exclusion form's loads), then keys2,
-// both set to all-ones by one memset; the second pass reads keys1 and fills keys2, reads_finish2_kernel writes the six outputs.
-template <class HQ> struct ReadsArgsT { const HQ *queries; size_t nq; uint32_t *query, *pos; uint8_t *dist; };
-template <class HQ> constexpr uintptr_t reads_qmask() { return sizeof(HQ) == 8 ? 7 : 3; } // the queries' alignment: 8 bytes exact, 4 bytes patterns
-struct ReadsSecond { uint32_t *query, *pos; uint8_t *dist; }; // the runner-up's outputs
-
-inline ReadsGeom reads_geom(size_t period, size_t read_len, size_t k) { return ReadsGeom{period, (unsigned)(read_len - k), 1.0f / (float)period}; }
-
-template <bool PACKED, class HQ>
-int reads_setup(bitnuc_ctx *c, size_t k, size_t count, unsigned long long n, unsigned long long rounds, const ReadsArgsT<HQ> &a, unsigned long long **keys,
-                const BestTable **tabs, dim3 *grid, bitnuc_err *err, unsigned long long **keys2 = nullptr) {
-    const size_t nkeys = keys2 ? 2 * count + 1 : count;
-    const size_t kbytes = (nkeys * 8 + 255) & ~(size_t)255;
-    if (int st = ensure_scratch(c, 10, kbytes + a.nq * sizeof(BestTable), err)) return st;
-    *keys = reinterpret_cast<unsigned long long *>(c->scratch[10]);
-    if (keys2) *keys2 = *keys + count + 1;
-    BestTable *t = reinterpret_cast<BestTable *>(c->scratch[10] + kbytes);
-    HIPCHK(hipMemsetAsync(*keys, 0xFF, nkeys * sizeof(uint64_t), c->stream));
-    best_tables_kernel<PACKED><<<(unsigned)a.nq, 64, 0, c->stream>>>(dev_queries(a.queries), (unsigned)k, t);
-    HIPCHK(hipGetLastError());
-    *tabs = t;
-    unsigned gx = bounded_grid(c, rounds, (kMultiBlock / 64) * kMultiRounds, kMultiGrid);
-    const unsigned long long single = (n - (rounds << 10)) / (4ull * kMultiBlock) + 1; // one-window-per-thread windows: four per thread
-    const unsigned want = (unsigned)(single < (unsigned long long)c->num_cu ? single : (unsigned long long)c->num_cu);
-    if (want > gx) gx = want;
-    *grid = dim3(gx, (unsigned)((a.nq + kMultiQB - 1) / kMultiQB), 1);
-    return BITNUC_OK;
-}
-
-template <class HQ>
-int reads_finish(bitnuc_ctx *c, const unsigned long long *keys, size_t count, const ReadsArgsT<HQ> &a, bitnuc_err *err) {
-    HIPCHK(hipGetLastError());
-    const size_t want = (count + 255) / 256, cap = (size_t)c->num_cu * 8;
-    reads_finish_kernel<<<(unsigned)(want < cap ? want : cap), 256, 0, c->stream>>>(keys, count, a.query, a.pos, a.dist);
-    HIPCHK(hipGetLastError());
-    return BITNUC_OK;
-}
-
-template <class HQ>
-int reads_finish2(bitnuc_ctx *c, const unsigned long long *keys, const unsigned long long *keys2, size_t count, const ReadsArgsT<HQ> &a, const ReadsSecond &b,
-                  bitnuc_err *err) {
-    HIPCHK(hipGetLastError());
-    const size_t want = (count + 255) / 256, cap = (size_t)c->num_cu * 8;
-    reads_finish2_kernel<<<(unsigned)(want < cap ? want : cap), 256, 0, c->stream>>>(keys, keys2, count, a.query, a.pos, a.dist, b.query, b.pos, b.dist);
-    HIPCHK(hipGetLastError());
-    return BITNUC_OK;
-}
-
-// d_reads at any alignment (ascii_skip); 1 <= k <= read_len, count >= 1, nq >= 1.  second: the runner-up's outputs as well -- the exclusion pass over
-// the same reads (none with one query: keys2 stays all-ones, the fill)
-template <class HQ>
-int launch_reads_best(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, const ReadsArgsT<HQ> &a, unsigned long long *slot, bitnuc_err *err,
-                      const ReadsSecond *second = nullptr) {
-    const unsigned skip = ascii_skip(reads);
-    const unsigned long long n = (unsigned long long)count * read_len;
-    const unsigned long long rounds = read_len >= kReadsMinPeriod ? scan_rounds(n, skip) : 0;
-    unsigned long long *keys, *keys2 = nullptr;
-    const BestTable *tabs;
-    dim3 grid;
-    if (int st = reads_setup<false>(c, k, count, n, rounds, a, &keys, &tabs, &grid, err, second ? &keys2 : nullptr)) return st;
-    const ReadsGeom g = reads_geom(read_len, read_len, k);
-    reads_best_kernel<kMultiRounds, false><<<grid, kMultiBlock, 0, c->stream>>>(reads, n, skip, rounds, (unsigned)k, g, dev_queries(a.queries), (unsigned)a.nq, tabs, keys,
-                                                                               slot);
-    if (!second) return reads_finish(c, keys, count, a, err);
-    if (a.nq > 1) {
-        HIPCHK(hipGetLastError());
-        reads_best_kernel<kMultiRounds, true><<<grid, kMultiBlock, 0, c->stream>>>(reads, n, skip, rounds, (unsigned)k, g, dev_queries(a.queries), (unsigned)a.nq, tabs,
-                                                                                  keys, nullptr); // (keys2 == keys + count + 1: the kernel's own sum)
-    }
-    return reads_finish2(c, keys, keys2, count, a, *second, err);
-}
-
-// d_words 8-byte aligned (packed_skip): the period is a whole number of words
-template <class HQ>
-int launch_reads_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, const ReadsArgsT<HQ> &a, bitnuc_err *err,
-                             const ReadsSecond *second = nullptr) {
-    const unsigned skip = packed_skip(words);
-    const size_t period = 32 * words_for(read_len);
-    const unsigned long long n = (unsigned long long)count * period;
-    const unsigned long long rounds = scan_rounds(n, skip);
-    unsigned long long *keys, *keys2 = nullptr;
-    const BestTable *tabs;
-    dim3 grid;
-    if (int st = reads_setup<true>(c, k, count, n, rounds, a, &keys, &tabs, &grid, err, second ? &keys2 : nullptr)) return st;
-    const ReadsGeom g = reads_geom(period, read_len, k);
-    reads_best_packed_kernel<false><<<grid, kMultiBlock, 0, c->stream>>>(words, n, skip, rounds, (unsigned)k, g, dev_queries(a.queries), (unsigned)a.nq, tabs, keys);
-    if (!second) return reads_finish(c, keys, count, a, err);
-    if (a.nq > 1) {
-        HIPCHK(hipGetLastError());
-        reads_best_packed_kernel<true><<<grid, kMultiBlock, 0, c->stream>>>(words, n, skip, rounds, (unsigned)k, g, dev_queries(a.queries), (unsigned)a.nq, tabs, keys);
-    }
-    return reads_finish2(c, keys, keys2, count, a, *second, err);
-}
-
-// the reads calls' checks 2 - 6 (after ctx): *done = nothing to do (count == 0)
-int check_reads(size_t read_len, size_t count, size_t k, const void *queries, uintptr_t qmask, size_t nq, const void *query, const void *pos, const void *dist,
-                bool *done, bitnuc_err *err) {
-    *done = false;
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    constexpr size_t kLimit = (size_t)1 << 58;
-    if (read_len >= 0xFFFFFFFFull) return fail(err, BITNUC_UNSUPPORTED, read_len);
-    const size_t period = 32 * words_for(read_len); // >= read_len, < 2^33
-    if (period && count > (kLimit - 1) / period) return fail(err, BITNUC_UNSUPPORTED, read_len);
-    if (nq > BITNUC_MAX_QUERIES) return fail(err, BITNUC_UNSUPPORTED, nq);
-    *done = count == 0;
-    if (*done) return BITNUC_OK;
-    if (!query || !pos || !dist || (reinterpret_cast<uintptr_t>(query) & 3) || (reinterpret_cast<uintptr_t>(pos) & 3) || (!queries && nq) ||
-        (reinterpret_cast<uintptr_t>(queries) & qmask))
-        return fail(err, BITNUC_UNSUPPORTED);
-    return BITNUC_OK;
-}
-
-// check 6 of the runner-up calls: its three outputs as well (after check_reads, count > 0)
-int check_reads_second(const void *query, const void *pos, const void *dist, bitnuc_err *err) {
-    if (!query || !pos || !dist || (reinterpret_cast<uintptr_t>(query) & 3) || (reinterpret_cast<uintptr_t>(pos) & 3)) return fail(err, BITNUC_UNSUPPORTED);
-    return BITNUC_OK;
-}
-
-inline bool reads_no_windows(size_t read_len, size_t k, size_t nq) { return k == 0 || read_len < k || nq == 0; }
-
-// no windows: every read UINT32_MAX, UINT32_MAX, 0xFF
-int reads_fill_dev(bitnuc_ctx *c, size_t count, uint32_t *d_query, uint32_t *d_pos, uint8_t *d_dist, bitnuc_err *err) {
-    HIPCHK(hipMemsetAsync(d_query, 0xFF, count * sizeof(uint32_t), c->stream));
-    HIPCHK(hipMemsetAsync(d_pos, 0xFF, count * sizeof(uint32_t), c->stream));
-    HIPCHK(hipMemsetAsync(d_dist, 0xFF, count, c->stream));
-    return BITNUC_OK;
-}
-
-// windows x queries of a batch, saturated: what the host forms' cutoff is judged on
-inline size_t reads_work(size_t read_len, size_t count, size_t k, size_t nq) { return multi_work(multi_work(read_len - k + 1, count), nq); }
-
-// The host forms' chunk loop: whole reads, `per` of them per chunk (no overlap: no window crosses a read); the queries copied once into scratch 2, a
-// chunk's query / pos arrays in scratch 1, its distances in scratch 3, copied straight to their place in the outputs.  `launch(r0, m, a)` runs the
-// reads [r0, r0 + m) with a's device arrays.  Stops at the first failing chunk (drain: its first invalid byte, absolute through the slot's base).
-template <class HQ, class Launch>
-int reads_host_loop(bitnuc_ctx *c, size_t count, size_t per, const HQ *queries, size_t nq, uint32_t *query, uint32_t *pos, uint8_t *dist, bitnuc_err *err,
-                    Launch launch) {
-    const size_t pm = count < per ? count : per;
-    if (int st = ensure_scratch(c, 1, pm * 8, err)) return st;
-    if (int st = ensure_scratch(c, 2, nq * sizeof(HQ), err)) return st; // 8: exact queries, 16: patterns
-    if (int st = ensure_scratch(c, 3, pm < 64 ? 64 : pm, err)) return st;
-    HIPCHK(hipMemcpyAsync(c->scratch[2], queries, nq * sizeof(HQ), hipMemcpyHostToDevice, c->stream));
-    uint32_t *d_query = reinterpret_cast<uint32_t *>(c->scratch[1]), *d_pos = d_query + pm;
-    const ReadsArgsT<HQ> a{reinterpret_cast<const HQ *>(c->scratch[2]), nq, d_query, d_pos, c->scratch[3]};
-    for (size_t r0 = 0; r0 < count; r0 += per) {
-        const size_t m = count - r0 < per ? count - r0 : per;
-        if (int st = launch(r0, m, a)) return st;
-        HIPCHK(hipMemcpyAsync(query + r0, d_query, m * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(pos + r0, d_pos, m * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(dist + r0, c->scratch[3], m, hipMemcpyDeviceToHost, c->stream));
-        bitnuc_err e;
-        if (int st = drain(c, &e)) { if (err) *err = e; return st; }
-    }
-    return BITNUC_OK;
-}
-
-// reads_host_loop with the runner-up's outputs: four query / pos arrays in scratch 1, two distance arrays in scratch 3.  A chunk holds whole reads, so
-// both triples are the chunk's own: nothing is merged across chunks.
-template <class HQ, class Launch>
-int reads_host_loop2(bitnuc_ctx *c, size_t count, size_t per, const HQ *queries, size_t nq, uint32_t *query, uint32_t *pos, uint8_t *dist, uint32_t *query2,
-                     uint32_t *pos2, uint8_t *dist2, bitnuc_err *err, Launch launch) {
-    const size_t pm = count < per ? count : per;
-    if (int st = ensure_scratch(c, 1, pm * 16, err)) return st;
-    if (int st = ensure_scratch(c, 2, nq * sizeof(HQ), err)) return st;
-    if (int st = ensure_scratch(c, 3, 2 * pm < 64 ? 64 : 2 * pm, err)) return st;
-    HIPCHK(hipMemcpyAsync(c->scratch[2], queries, nq * sizeof(HQ), hipMemcpyHostToDevice, c->stream));
-    uint32_t *d_query = reinterpret_cast<uint32_t *>(c->scratch[1]), *d_pos = d_query + pm, *d_query2 = d_pos + pm, *d_pos2 = d_query2 + pm;
-    uint8_t *d_dist = c->scratch[3], *d_dist2 = d_dist + pm;
-    const ReadsArgsT<HQ> a{reinterpret_cast<const HQ *>(c->scratch[2]), nq, d_query, d_pos, d_dist};
-    const ReadsSecond b{d_query2, d_pos2, d_dist2};
-    for (size_t r0 = 0; r0 < count; r0 += per) {
-        const size_t m = count - r0 < per ? count - r0 : per;
-        if (int st = launch(r0, m, a, b)) return st;
-        HIPCHK(hipMemcpyAsync(query + r0, d_query, m * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(pos + r0, d_pos, m * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(dist + r0, d_dist, m, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(query2 + r0, d_query2, m * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(pos2 + r0, d_pos2, m * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(dist2 + r0, d_dist2, m, hipMemcpyDeviceToHost, c->stream));
-        bitnuc_err e;
-        if (int st = drain(c, &e)) { if (err) *err = e; return st; }
-    }
-    return BITNUC_OK;
-}
-
-// ---- the ANCHORED best match and runner-up per read (scan_anchored_device.h): one kernel writes the six outputs.  Context scratch: the per-query
-// tables only (256 bytes per query, after the per-read forms' in scratch 10, shared with them in stream order).
-struct AnchorOut { uint32_t *query, *pos; uint8_t *dist, *dist2; uint32_t *query2, *pos2; }; // query2 == nullptr: the best triple only
-
-// the calls' checks 2 - 7 (after ctx).  *done: nothing to do (count == 0); *offsets == 0: no window (fill), otherwise the offsets per read
-int check_anchored(size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi, const void *queries, uintptr_t qmask, size_t nq, const AnchorOut &o,
-                   bool *done, size_t *offsets, bitnuc_err *err) {
-    *done = false;
-    *offsets = 0;
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    constexpr size_t kLimit = (size_t)1 << 58;
-    if (read_len >= 0xFFFFFFFFull) return fail(err, BITNUC_UNSUPPORTED, read_len);
-    const size_t period = 32 * words_for(read_len); // >= read_len, < 2^33
-    if (period && count > (kLimit - 1) / period) return fail(err, BITNUC_UNSUPPORTED, read_len);
-    if (nq > BITNUC_MAX_QUERIES) return fail(err, BITNUC_UNSUPPORTED, nq);
-    size_t m = 0;
-    if (anchored_offsets(read_len, k, pos_lo, pos_hi, &m) && m + k - 1 > BITNUC_ANCHOR_MAX_SPAN) return fail(err, BITNUC_UNSUPPORTED, m + k - 1);
-    *done = count == 0;
-    if (*done) return BITNUC_OK;
-    if (!o.query || !o.pos || !o.dist || (reinterpret_cast<uintptr_t>(o.query) & 3) || (reinterpret_cast<uintptr_t>(o.pos) & 3) || (!queries && nq) ||
-        (reinterpret_cast<uintptr_t>(queries) & qmask))
-        return fail(err, BITNUC_UNSUPPORTED);
-    const int n2 = (o.query2 != nullptr) + (o.pos2 != nullptr) + (o.dist2 != nullptr);
-    if ((n2 != 0 && n2 != 3) || (reinterpret_cast<uintptr_t>(o.query2) & 3) || (reinterpret_cast<uintptr_t>(o.pos2) & 3)) return fail(err, BITNUC_UNSUPPORTED);
-    if (nq) *offsets = m;
-    return BITNUC_OK;
-}
-
-void anchored_fill_host(size_t count, const AnchorOut &o) {
-    bitnuc_host::reads_best_fill(count, o.query, o.pos, o.dist);
-    if (o.query2) bitnuc_host::reads_best_fill(count, o.query2, o.pos2, o.dist2);
-}
-
-int anchored_fill_dev(bitnuc_ctx *c, size_t count, const AnchorOut &o, bitnuc_err *err) {
-    if (int st = reads_fill_dev(c, count, o.query, o.pos, o.dist, err)) return st;
-    return o.query2 ? reads_fill_dev(c, count, o.query2, o.pos2, o.dist2, err) : BITNUC_OK;
-}
-
-// data: ASCII reads at any alignment (stride = read_len bytes) or 8-byte aligned packed words (stride = words per read); count, nq, offsets >= 1
-template <bool PACKED, class HQ>
-int launch_reads_anchored(bitnuc_ctx *c, const void *data, size_t stride, size_t count, size_t k, size_t pos_lo, size_t offsets, const HQ *d_queries, size_t nq,
-                          const AnchorOut &o, unsigned long long *slot, bitnuc_err *err) {
-    if (int st = ensure_scratch(c, 10, nq * kAnchorEntry, err)) return st;
-    anchored_tables_kernel<<<(unsigned)nq, 64, 0, c->stream>>>(dev_queries(d_queries), (unsigned)k, reinterpret_cast<uint32_t *>(c->scratch[10]));
-    HIPCHK(hipGetLastError());
-    unsigned lg = 0;
-    while (((size_t)1 << lg) < offsets) ++lg;
-    const AnchorGeom g{(unsigned long long)stride, (unsigned)pos_lo, (unsigned)(offsets + k - 1), (unsigned)offsets, lg, (unsigned)k, (unsigned)nq,
-                       (unsigned)(((nq << lg) + 31) >> 5)};
-    const size_t want = (count + 255) / 256, cap = (size_t)c->num_cu * 4; // 64 reads per wave and trip
-    reads_anchored_kernel<PACKED, AnchorGeom><<<(unsigned)(want < cap ? want : cap), kAnchorBlock, 0, c->stream>>>(
-        static_cast<const uint8_t *>(data), (unsigned long long)count, g, c->scratch[10], o.query, o.pos, o.dist, o.query2, o.pos2, o.dist2, slot);
-    HIPCHK(hipGetLastError());
-    return BITNUC_OK;
-}
-
-// offsets x queries of a batch, saturated: what the anchored host forms' cutoff is judged on
-inline size_t anchored_work(size_t offsets, size_t count, size_t nq) { return multi_work(multi_work(offsets, count), nq); }
-
-// The anchored host forms' chunk loop: reads_host_loop2's scratch and copies; without the second triple its three arrays are neither computed nor copied.
-template <class HQ, class Launch>
-int anchored_host_loop(bitnuc_ctx *c, size_t count, size_t per, const HQ *queries, size_t nq, const AnchorOut &o, bitnuc_err *err, Launch launch) {
-    const size_t pm = count < per ? count : per;
-    if (int st = ensure_scratch(c, 1, pm * 16, err)) return st;
-    if (int st = ensure_scratch(c, 2, nq * sizeof(HQ), err)) return st;
-    if (int st = ensure_scratch(c, 3, 2 * pm < 64 ? 64 : 2 * pm, err)) return st;
-    HIPCHK(hipMemcpyAsync(c->scratch[2], queries, nq * sizeof(HQ), hipMemcpyHostToDevice, c->stream));
-    uint32_t *d_query = reinterpret_cast<uint32_t *>(c->scratch[1]), *d_pos = d_query + pm, *d_query2 = d_pos + pm, *d_pos2 = d_query2 + pm;
-    uint8_t *d_dist = c->scratch[3], *d_dist2 = d_dist + pm;
-    const AnchorOut d = o.query2 ? AnchorOut{d_query, d_pos, d_dist, d_dist2, d_query2, d_pos2} : AnchorOut{d_query, d_pos, d_dist, nullptr, nullptr, nullptr};
-    for (size_t r0 = 0; r0 < count; r0 += per) {
-        const size_t m = count - r0 < per ? count - r0 : per;
-        if (int st = launch(r0, m, reinterpret_cast<const HQ *>(c->scratch[2]), d)) return st;
-        HIPCHK(hipMemcpyAsync(o.query + r0, d_query, m * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(o.pos + r0, d_pos, m * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(o.dist + r0, d_dist, m, hipMemcpyDeviceToHost, c->stream));
-        if (o.query2) {
-            HIPCHK(hipMemcpyAsync(o.query2 + r0, d_query2, m * 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(o.pos2 + r0, d_pos2, m * 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(o.dist2 + r0, d_dist2, m, hipMemcpyDeviceToHost, c->stream));
-        }
-        bitnuc_err e;
-        if (int st = drain(c, &e)) { if (err) *err = e; return st; }
-    }
-    return BITNUC_OK;
-}
-
-// ---- the INDEL-TOLERANT anchored best match and runner-up per read (scan_edist_device.h): a vector-ALU kernel, one read per lane, writes the six outputs.
-// Context scratch: 16 bytes per query (scratch 10, shared with the other per-read forms in stream order).  The checks, the fills, the cutoff and the
-// host forms' chunk loop are the anchored forms' (check_anchored, anchored_fill_*, anchored_work, anchored_host_loop); o.pos / o.pos2 hold the ends.
-// data: ASCII reads at any alignment (stride = read_len bytes) or 8-byte aligned packed words (stride = words per read); count, nq >= 1, k <= n <= 64
-template <bool PACKED, class HQ>
-int launch_reads_edist(bitnuc_ctx *c, const void *data, size_t stride, size_t count, size_t k, size_t pos_lo, size_t n, const HQ *d_queries, size_t nq,
-                       const AnchorOut &o, unsigned long long *slot, bitnuc_err *err) {
-    if (int st = ensure_scratch(c, 10, nq * kEdistEntry, err)) return st;
-    u32x4 *tabs = reinterpret_cast<u32x4 *>(c->scratch[10]);
-    edist_tables_kernel<<<(unsigned)((nq + 63) / 64), 64, 0, c->stream>>>(dev_queries(d_queries), (unsigned)nq, (unsigned)k, tabs);
-    HIPCHK(hipGetLastError());
-    const EdistGeom g{(unsigned long long)stride, (unsigned)pos_lo, (unsigned)n, (unsigned)k, (unsigned)nq};
-    const size_t want = (count + kEdistBlock - 1) / kEdistBlock, cap = (size_t)c->num_cu * kEdistBlocksPerCu;
-    reads_edist_kernel<PACKED><<<(unsigned)(want < cap ? want : cap), kEdistBlock, 0, c->stream>>>(
-        static_cast<const uint8_t *>(data), (unsigned long long)count, g, tabs, o.query, o.pos, o.dist, o.query2, o.pos2, o.dist2, slot);
-    HIPCHK(hipGetLastError());
-    return BITNUC_OK;
-}
-
-// ---- the best match per read of a RAGGED batch (scan_reads_batch_device.h): the fixed-length form's scratch, keys, tables, grid and finish; the
-// kernels take the run's length and the layout's two tables instead of a period.
-inline BatchTables batch_tables(const uint64_t *starts, const uint64_t *offsets, size_t count, unsigned shift) {
-    return BatchTables{reinterpret_cast<const unsigned long long *>(starts), reinterpret_cast<const unsigned long long *>(offsets), count, shift};
-}
-
-// d_seq at any alignment (ascii_skip); 1 <= k <= total, count >= 1, nq >= 1
-template <class HQ>
-int launch_reads_batch(bitnuc_ctx *c, const uint8_t *seq, const uint64_t *d_offsets, size_t count, size_t total, size_t k, const ReadsArgsT<HQ> &a,
-                       unsigned long long *slot, bitnuc_err *err) {
-    const unsigned skip = ascii_skip(seq);
-    const unsigned long long n = total, rounds = scan_rounds(n, skip);
-    unsigned long long *keys;
-    const BestTable *tabs;
-    dim3 grid;
-    if (int st = reads_setup<false>(c, k, count, n, rounds, a, &keys, &tabs, &grid, err)) return st;
-    reads_batch_kernel<kMultiRounds><<<grid, kMultiBlock, 0, c->stream>>>(seq, batch_tables(d_offsets, d_offsets, count, 0), n, skip, rounds, (unsigned)k,
-                                                                         dev_queries(a.queries), (unsigned)a.nq, tabs, keys, slot);
-    return reads_finish(c, keys, count, a, err);
-}
-
-// d_words 8-byte aligned (packed_skip); total_words >= 1
-template <class HQ>
-int launch_reads_batch_packed(bitnuc_ctx *c, const uint64_t *words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count, size_t total_words,
-                              size_t k, const ReadsArgsT<HQ> &a, bitnuc_err *err) {
-    const unsigned skip = packed_skip(words);
-    const unsigned long long n = 32ull * total_words, rounds = scan_rounds(n, skip);
-    unsigned long long *keys;
-    const BestTable *tabs;
-    dim3 grid;
-    if (int st = reads_setup<true>(c, k, count, n, rounds, a, &keys, &tabs, &grid, err)) return st;
-    reads_batch_packed_kernel<<<grid, kMultiBlock, 0, c->stream>>>(words, batch_tables(d_word_offsets, d_offsets, count, 5), n, skip, rounds, (unsigned)k,
-                                                                   dev_queries(a.queries), (unsigned)a.nq, tabs, keys);
-    return reads_finish(c, keys, count, a, err);
-}
-
-// the ragged reads calls' checks 2 - 6 (after ctx): `total` is what check 3 bounds (bases, or 32 x words; the host forms pass 0 and bound their tables'
-// totals with the table validation); tab2: the second table of the packed forms.  *done = nothing to do (count == 0)
-int check_reads_batch(uint64_t total, uint64_t total_value, size_t count, size_t k, const void *queries, uintptr_t qmask, size_t nq, const void *query, const void *pos,
-                      const void *dist, const void *tab1, const void *tab2, bool two_tables, bool *done, bitnuc_err *err) {
-    *done = false;
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    if (total >= ((uint64_t)1 << 58)) return fail(err, BITNUC_UNSUPPORTED, total_value);
-    if (nq > BITNUC_MAX_QUERIES) return fail(err, BITNUC_UNSUPPORTED, nq);
-    *done = count == 0;
-    if (*done) return BITNUC_OK;
-    if (!query || !pos || !dist || (reinterpret_cast<uintptr_t>(query) & 3) || (reinterpret_cast<uintptr_t>(pos) & 3) || (!queries && nq) ||
-        (reinterpret_cast<uintptr_t>(queries) & qmask) || !tab1 || (reinterpret_cast<uintptr_t>(tab1) & 7) ||
-        (two_tables && (!tab2 || (reinterpret_cast<uintptr_t>(tab2) & 7))))
-        return fail(err, BITNUC_UNSUPPORTED);
-    return BITNUC_OK;
-}
-
-// check 7 of the host forms: batch_check_tables' finding as the call's error
-int fail_batch_tables(const BatchFault &f, bitnuc_err *err) {
-    return fail(err, f.kind >= 4 ? BITNUC_UNSUPPORTED : BITNUC_INVALID_RANGE, f.value);
-}
-
-// The ragged host forms' chunk loop: reads_host_loop with chunks of whole reads of any number: chunk_end(r0) is the read after the chunk's last;
-// `launch(r0, m, a)` runs the reads [r0, r0 + m) with a's device arrays.
-template <class HQ, class ChunkEnd, class Launch>
-int reads_batch_host_loop(bitnuc_ctx *c, size_t count, const HQ *queries, size_t nq, uint32_t *query, uint32_t *pos, uint8_t *dist, bitnuc_err *err,
-                          ChunkEnd chunk_end, Launch launch) {
-    if (int st = ensure_scratch(c, 2, nq * sizeof(HQ), err)) return st;
-    HIPCHK(hipMemcpyAsync(c->scratch[2], queries, nq * sizeof(HQ), hipMemcpyHostToDevice, c->stream));
-    for (size_t r0 = 0; r0 < count;) {
-        const size_t m = chunk_end(r0) - r0;
-        if (int st = ensure_scratch(c, 1, m * 8, err)) return st;
-        if (int st = ensure_scratch(c, 3, m < 64 ? 64 : m, err)) return st;
-        uint32_t *d_query = reinterpret_cast<uint32_t *>(c->scratch[1]), *d_pos = d_query + m;
-        const ReadsArgsT<HQ> a{reinterpret_cast<const HQ *>(c->scratch[2]), nq, d_query, d_pos, c->scratch[3]};
-        if (int st = launch(r0, m, a)) return st;
-        HIPCHK(hipMemcpyAsync(query + r0, d_query, m * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(pos + r0, d_pos, m * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(dist + r0, c->scratch[3], m, hipMemcpyDeviceToHost, c->stream));
-        bitnuc_err e;
-        if (int st = drain(c, &e)) { if (err) *err = e; return st; }
-        r0 += m;
-    }
-    return BITNUC_OK;
-}
-
-// ---- the ANCHORED best match and runner-up per read of a RAGGED batch: reads_anchored_kernel under its other layout policy (AnchorBatchGeom), the
-// fixed form's tables and scratch (256 bytes per query), the ragged forms' tables and chunk cut.
-// the calls' checks 2 - 7 (after ctx): `total` is what check 3 bounds (the host forms pass 0: their tables' validation bounds the totals).  *done:
-// nothing to do (count == 0); *offsets: pos_hi - pos_lo + 1, 0 for an empty range
-int check_anchored_batch(uint64_t total, uint64_t total_value, size_t count, size_t k, int anchor, size_t pos_lo, size_t pos_hi, const void *queries, uintptr_t qmask,
-                         size_t nq, const AnchorOut &o, const void *tab1, const void *tab2, bool two_tables, bool *done, size_t *offsets, bitnuc_err *err) {
-    *done = false;
-    *offsets = 0;
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    if (total >= ((uint64_t)1 << 58)) return fail(err, BITNUC_UNSUPPORTED, total_value);
-    if (nq > BITNUC_MAX_QUERIES) return fail(err, BITNUC_UNSUPPORTED, nq);
-    if (anchor != BITNUC_ANCHOR_START && anchor != BITNUC_ANCHOR_END) return fail(err, BITNUC_UNSUPPORTED, (uint64_t)(unsigned)anchor);
-    size_t span;
-    anchored_batch_span(k, pos_lo, pos_hi, offsets, &span);
-    if (span > BITNUC_ANCHOR_MAX_SPAN) return fail(err, BITNUC_UNSUPPORTED, span);
-    *done = count == 0;
-    if (*done) return BITNUC_OK;
-    if (!o.query || !o.pos || !o.dist || (reinterpret_cast<uintptr_t>(o.query) & 3) || (reinterpret_cast<uintptr_t>(o.pos) & 3) || (!queries && nq) ||
-        (reinterpret_cast<uintptr_t>(queries) & qmask))
-        return fail(err, BITNUC_UNSUPPORTED);
-    const int n2 = (o.query2 != nullptr) + (o.pos2 != nullptr) + (o.dist2 != nullptr);
-    if ((n2 != 0 && n2 != 3) || (reinterpret_cast<uintptr_t>(o.query2) & 3) || (reinterpret_cast<uintptr_t>(o.pos2) & 3)) return fail(err, BITNUC_UNSUPPORTED);
-    if (!tab1 || (reinterpret_cast<uintptr_t>(tab1) & 7) || (two_tables && (!tab2 || (reinterpret_cast<uintptr_t>(tab2) & 7)))) return fail(err, BITNUC_UNSUPPORTED);
-    return BITNUC_OK;
-}
-
-// check 9: no read of a batch of `total` bases can hold a window (a window at offset pos_lo, or pos_lo bases in front of the end, needs k + pos_lo bases;
-// reads are below 2^32 - 1 bases)
-inline bool anchored_batch_no_window(uint64_t total, size_t k, size_t nq, size_t offsets, size_t pos_lo) {
-    return k == 0 || nq == 0 || offsets == 0 || total < k || total - k < pos_lo || pos_lo >= 0xFFFFFFFFull;
-}
-
-// data: ASCII at any alignment, read r at bytes d_offsets[r] .. d_offsets[r + 1], or 8-byte aligned words, read r from word d_starts[r]; the tables in
-// device memory; count, nq >= 1, 1 <= offsets, offsets + k - 1 <= 64, pos_lo < 2^32 - 1
-template <bool PACKED, class HQ>
-int launch_reads_anchored_batch(bitnuc_ctx *c, const void *data, const uint64_t *d_starts, const uint64_t *d_offsets, size_t count, size_t k, int anchor, size_t pos_lo,
-                                size_t offsets, const HQ *d_queries, size_t nq, const AnchorOut &o, unsigned long long *slot, bitnuc_err *err) {
-    if (int st = ensure_scratch(c, 10, nq * kAnchorEntry, err)) return st;
-    anchored_tables_kernel<<<(unsigned)nq, 64, 0, c->stream>>>(dev_queries(d_queries), (unsigned)k, reinterpret_cast<uint32_t *>(c->scratch[10]));
-    HIPCHK(hipGetLastError());
-    unsigned lg = 0;
-    while (((size_t)1 << lg) < offsets) ++lg;
-    const AnchorBatchGeom g{reinterpret_cast<const unsigned long long *>(d_offsets), reinterpret_cast<const unsigned long long *>(d_starts), (unsigned)pos_lo,
-                            (unsigned)(anchor == BITNUC_ANCHOR_END), (unsigned)(offsets + k - 1), (unsigned)offsets, lg, (unsigned)k, (unsigned)nq,
-                            (unsigned)(((nq << lg) + 31) >> 5)};
-    const size_t want = (count + 255) / 256, cap = (size_t)c->num_cu * 4; // 64 reads per wave and trip
-    reads_anchored_kernel<PACKED, AnchorBatchGeom><<<(unsigned)(want < cap ? want : cap), kAnchorBlock, 0, c->stream>>>(
-        static_cast<const uint8_t *>(data), (unsigned long long)count, g, c->scratch[10], o.query, o.pos, o.dist, o.query2, o.pos2, o.dist2, slot);
-    HIPCHK(hipGetLastError());
-    return BITNUC_OK;
-}
-
-// The ragged anchored host forms' chunk loop: reads_batch_host_loop's chunks (chunk_end(r0) is the read after the chunk's last) with anchored_host_loop's
-// outputs: six arrays, or three without the second triple.  `launch(r0, m, d_queries, d)` runs the reads [r0, r0 + m) into d's device arrays.
-template <class HQ, class ChunkEnd, class Launch>
-int anchored_batch_host_loop(bitnuc_ctx *c, size_t count, const HQ *queries, size_t nq, const AnchorOut &o, bitnuc_err *err, ChunkEnd chunk_end, Launch launch) {
-    if (int st = ensure_scratch(c, 2, nq * sizeof(HQ), err)) return st;
-    HIPCHK(hipMemcpyAsync(c->scratch[2], queries, nq * sizeof(HQ), hipMemcpyHostToDevice, c->stream));
-    for (size_t r0 = 0; r0 < count;) {
-        const size_t m = chunk_end(r0) - r0;
-        if (int st = ensure_scratch(c, 1, m * 16, err)) return st;
-        if (int st = ensure_scratch(c, 3, 2 * m < 64 ? 64 : 2 * m, err)) return st;
-        uint32_t *d_query = reinterpret_cast<uint32_t *>(c->scratch[1]), *d_pos = d_query + m, *d_query2 = d_pos + m, *d_pos2 = d_query2 + m;
-        uint8_t *d_dist = c->scratch[3], *d_dist2 = d_dist + m;
-        const AnchorOut d = o.query2 ? AnchorOut{d_query, d_pos, d_dist, d_dist2, d_query2, d_pos2} : AnchorOut{d_query, d_pos, d_dist, nullptr, nullptr, nullptr};
-        if (int st = launch(r0, m, reinterpret_cast<const HQ *>(c->scratch[2]), d)) return st;
-        HIPCHK(hipMemcpyAsync(o.query + r0, d_query, m * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(o.pos + r0, d_pos, m * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(o.dist + r0, d_dist, m, hipMemcpyDeviceToHost, c->stream));
-        if (o.query2) {
-            HIPCHK(hipMemcpyAsync(o.query2 + r0, d_query2, m * 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(o.pos2 + r0, d_pos2, m * 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(o.dist2 + r0, d_dist2, m, hipMemcpyDeviceToHost, c->stream));
-        }
-        bitnuc_err e;
-        if (int st = drain(c, &e)) { if (err) *err = e; return st; }
-        r0 += m;
-    }
-    return BITNUC_OK;
-}
-
-// ---- the INDEL-TOLERANT anchored best match and runner-up per read of a RAGGED batch: reads_edist_kernel under its other layout policy (AnchorBatchGeom),
-// the fixed form's tables and scratch (16 bytes per query), the ragged anchored forms' checks, tables and chunk loop; o.pos / o.pos2 hold the ends.
-// data: ASCII at any alignment, read r at bytes d_offsets[r] .. d_offsets[r + 1], or 8-byte aligned words, read r from word d_starts[r]; the tables in
-// device memory; count, nq, k >= 1, 1 <= offsets, offsets + k - 1 <= 64, pos_lo < 2^32 - 1
-template <bool PACKED, class HQ>
-int launch_reads_edist_batch(bitnuc_ctx *c, const void *data, const uint64_t *d_starts, const uint64_t *d_offsets, size_t count, size_t k, int anchor, size_t pos_lo,
-                             size_t offsets, const HQ *d_queries, size_t nq, const AnchorOut &o, unsigned long long *slot, bitnuc_err *err) {
-    if (int st = ensure_scratch(c, 10, nq * kEdistEntry, err)) return st;
-    u32x4 *tabs = reinterpret_cast<u32x4 *>(c->scratch[10]);
-    edist_tables_kernel<<<(unsigned)((nq + 63) / 64), 64, 0, c->stream>>>(dev_queries(d_queries), (unsigned)nq, (unsigned)k, tabs);
-    HIPCHK(hipGetLastError());
-    const AnchorBatchGeom g{reinterpret_cast<const unsigned long long *>(d_offsets), reinterpret_cast<const unsigned long long *>(d_starts), (unsigned)pos_lo,
-                            (unsigned)(anchor == BITNUC_ANCHOR_END), (unsigned)(offsets + k - 1), (unsigned)offsets, 0u, (unsigned)k, (unsigned)nq, 0u};
-    const size_t want = (count + kEdistBlock - 1) / kEdistBlock, cap = (size_t)c->num_cu * kEdistBlocksPerCu;
-    reads_edist_kernel<PACKED, AnchorBatchGeom><<<(unsigned)(want < cap ? want : cap), kEdistBlock, 0, c->stream>>>(
-        static_cast<const uint8_t *>(data), (unsigned long long)count, g, tabs, o.query, o.pos, o.dist, o.query2, o.pos2, o.dist2, slot);
-    HIPCHK(hipGetLastError());
-    return BITNUC_OK;
-}
-
 // ---- the mismatch histogram per query: the four forms, once for exact queries (uint64_t) and patterns (bitnuc_pattern) -----------------------------
 template <class HQ>
 int hist_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const HQ *d_queries, size_t n_queries, size_t n_bins, uint64_t *d_hist, bitnuc_err *err) {
@@ -1233,11 +760,7 @@ int hist_host(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const HQ *q
     if (!ref) return fail(err, BITNUC_UNSUPPORTED);
     if (on_host(c, multi_work(n - k + 1, n_queries))) {
         const long long bad = bitnuc_host::kmer_hdist_hist_small(ref, n, k, host_queries(queries), n_queries, n_bins, hist);
-        if (bad >= 0) {
-            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = ref[bad]; err->index = (uint64_t)bad; }
-            return BITNUC_INVALID_BASE;
-        }
-        return BITNUC_OK;
+        return bad >= 0 ? fail_invalid_base(err, ref[bad], (uint64_t)bad) : BITNUC_OK;
     }
     if (int st = check_ctx(c, err)) return st;
     DeviceGuard g(c->device);
@@ -1535,11 +1058,7 @@ int bitnuc_kmer_hdist_hits(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k
     if (!ref) return fail(err, BITNUC_UNSUPPORTED);
     if (on_host(c, n)) {
         const long long bad = bitnuc_host::kmer_hdist_hits_small(ref, n, k, query, tau, pos, hit_dist, cap, n_hits);
-        if (bad >= 0) {
-            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = ref[bad]; err->index = (uint64_t)bad; }
-            return BITNUC_INVALID_BASE;
-        }
-        return BITNUC_OK;
+        return bad >= 0 ? fail_invalid_base(err, ref[bad], (uint64_t)bad) : BITNUC_OK;
     }
     if (int st = check_ctx(c, err)) return st;
     DeviceGuard g(c->device);
@@ -1623,11 +1142,7 @@ int bitnuc_kmer_hdist_count_multi(bitnuc_ctx *c, const uint8_t *ref, size_t n, s
     if (!ref) return fail(err, BITNUC_UNSUPPORTED);
     if (on_host(c, multi_work(n - k + 1, n_queries))) {
         const long long bad = bitnuc_host::kmer_hdist_count_multi_small(ref, n, k, queries, taus, n_queries, counts);
-        if (bad >= 0) {
-            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = ref[bad]; err->index = (uint64_t)bad; }
-            return BITNUC_INVALID_BASE;
-        }
-        return BITNUC_OK;
+        return bad >= 0 ? fail_invalid_base(err, ref[bad], (uint64_t)bad) : BITNUC_OK;
     }
     if (int st = check_ctx(c, err)) return st;
     DeviceGuard g(c->device);
@@ -1713,11 +1228,7 @@ int bitnuc_kmer_hdist_best(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k
     if (!ref) return fail(err, BITNUC_UNSUPPORTED);
     if (on_host(c, multi_work(n - k + 1, n_queries))) {
         const long long bad = bitnuc_host::kmer_hdist_best_small(ref, n, k, queries, n_queries, pos, dist);
-        if (bad >= 0) {
-            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = ref[bad]; err->index = (uint64_t)bad; }
-            return BITNUC_INVALID_BASE;
-        }
-        return BITNUC_OK;
+        return bad >= 0 ? fail_invalid_base(err, ref[bad], (uint64_t)bad) : BITNUC_OK;
     }
     if (int st = check_ctx(c, err)) return st;
     DeviceGuard g(c->device);
@@ -1762,793 +1273,12 @@ int bitnuc_kmer_hdist_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t n
 
 } // extern "C"
 
-// ---- the per-read matchers, written once for both query kinds (HQ: uint64_t, bitnuc_reads_hdist_*; bitnuc_pattern, bitnuc_reads_pattern_*): the entry
-// points behind them only name the instantiation, so a twin's checks, fills, chunking and launches are its exact form's line for line.
-namespace {
-
-// ---- the best match per read of a fixed-length batch ---------------------------------------------------------------------------
-template <class HQ>
-int reads_best_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const HQ *d_queries, size_t n_queries,
-                     uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    bool done;
-    if (int st = check_reads(read_len, count, k, d_queries, reads_qmask<HQ>(), n_queries, d_best_query, d_best_pos, d_best_dist, &done, err)) return st;
-    if (done) return BITNUC_OK;
-    DeviceGuard g(c->device);
-    if (reads_no_windows(read_len, k, n_queries)) return reads_fill_dev(c, count, d_best_query, d_best_pos, d_best_dist, err);
-    if (!d_reads) return fail(err, BITNUC_UNSUPPORTED);
-    unsigned long long *slot;
-    if (int st = take_slot(c, 0, &slot, err)) return st;
-    return launch_reads_best(c, d_reads, read_len, count, k, ReadsArgsT<HQ>{d_queries, n_queries, d_best_query, d_best_pos, d_best_dist}, slot, err);
-}
-
-template <class HQ>
-int reads_best_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, const HQ *d_queries,
-                            size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    bool done;
-    if (int st = check_reads(read_len, count, k, d_queries, reads_qmask<HQ>(), n_queries, d_best_query, d_best_pos, d_best_dist, &done, err)) return st;
-    if (done) return BITNUC_OK;
-    DeviceGuard g(c->device);
-    if (reads_no_windows(read_len, k, n_queries)) return reads_fill_dev(c, count, d_best_query, d_best_pos, d_best_dist, err);
-    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    return launch_reads_best_packed(c, d_words, read_len, count, k, ReadsArgsT<HQ>{d_queries, n_queries, d_best_query, d_best_pos, d_best_dist}, err);
-}
-
-template <class HQ>
-int reads_best_host(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, const HQ *queries, size_t n_queries,
-                    uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err) {
-    clear_err(err);
-    bool done;
-    if (int st = check_reads(read_len, count, k, queries, reads_qmask<HQ>(), n_queries, best_query, best_pos, best_dist, &done, err)) return st;
-    if (done) return BITNUC_OK;
-    if (reads_no_windows(read_len, k, n_queries)) { bitnuc_host::reads_best_fill(count, best_query, best_pos, best_dist); return BITNUC_OK; }
-    if (!reads) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, reads_work(read_len, count, k, n_queries))) {
-        const long long bad = bitnuc_host::reads_hdist_best_small(reads, read_len, count, k, host_queries(queries), n_queries, best_query, best_pos, best_dist);
-        if (bad >= 0) {
-            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = reads[bad]; err->index = (uint64_t)bad; }
-            return BITNUC_INVALID_BASE;
-        }
-        return BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    const size_t per = read_len < kHostChunk ? kHostChunk / read_len : 1, pm = count < per ? count : per; // whole reads per chunk
-    if (int st = ensure_scratch(c, 0, pm * read_len + 64, err)) return st;
-    return reads_host_loop(c, count, per, queries, n_queries, best_query, best_pos, best_dist, err, [&](size_t r0, size_t m, const ReadsArgsT<HQ> &a) {
-        HIPCHK(hipMemcpyAsync(c->scratch[0], reads + r0 * read_len, m * read_len, hipMemcpyHostToDevice, c->stream));
-        unsigned long long *slot;
-        if (int st = take_slot(c, r0 * read_len, &slot, err)) return st;
-        return launch_reads_best(c, c->scratch[0], read_len, m, k, a, slot, err);
-    });
-}
-
-template <class HQ>
-int reads_best_packed_host(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, const HQ *queries, size_t n_queries,
-                           uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err) {
-    clear_err(err);
-    bool done;
-    if (int st = check_reads(read_len, count, k, queries, reads_qmask<HQ>(), n_queries, best_query, best_pos, best_dist, &done, err)) return st;
-    if (done) return BITNUC_OK;
-    if (reads_no_windows(read_len, k, n_queries)) { bitnuc_host::reads_best_fill(count, best_query, best_pos, best_dist); return BITNUC_OK; }
-    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, reads_work(read_len, count, k, n_queries))) {
-        bitnuc_host::reads_hdist_best_packed_small(words, read_len, count, k, host_queries(queries), n_queries, best_query, best_pos, best_dist);
-        return BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    const size_t wpr = words_for(read_len);
-    const size_t per = wpr < kPackedChunkWords ? kPackedChunkWords / wpr : 1, pm = count < per ? count : per; // whole reads per chunk
-    if (int st = ensure_scratch(c, 0, pm * wpr * 8, err)) return st;
-    return reads_host_loop(c, count, per, queries, n_queries, best_query, best_pos, best_dist, err, [&](size_t r0, size_t m, const ReadsArgsT<HQ> &a) {
-        HIPCHK(hipMemcpyAsync(c->scratch[0], words + r0 * wpr, m * wpr * 8, hipMemcpyHostToDevice, c->stream));
-        return launch_reads_best_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), read_len, m, k, a, err);
-    });
-}
-
-// ---- the best match and the runner-up per read of a fixed-length batch ---------------------------------------------------------------
-template <class HQ>
-int reads_best2_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const HQ *d_queries, size_t n_queries,
-                      uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_pos,
-                                   uint8_t *d_second_dist, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    bool done;
-    if (int st = check_reads(read_len, count, k, d_queries, reads_qmask<HQ>(), n_queries, d_best_query, d_best_pos, d_best_dist, &done, err)) return st;
-    if (done) return BITNUC_OK;
-    if (int st = check_reads_second(d_second_query, d_second_pos, d_second_dist, err)) return st;
-    DeviceGuard g(c->device);
-    if (reads_no_windows(read_len, k, n_queries)) {
-        if (int st = reads_fill_dev(c, count, d_best_query, d_best_pos, d_best_dist, err)) return st;
-        return reads_fill_dev(c, count, d_second_query, d_second_pos, d_second_dist, err);
-    }
-    if (!d_reads) return fail(err, BITNUC_UNSUPPORTED);
-    unsigned long long *slot;
-    if (int st = take_slot(c, 0, &slot, err)) return st;
-    const ReadsSecond b{d_second_query, d_second_pos, d_second_dist};
-    return launch_reads_best(c, d_reads, read_len, count, k, ReadsArgsT<HQ>{d_queries, n_queries, d_best_query, d_best_pos, d_best_dist}, slot, err, &b);
-}
-
-template <class HQ>
-int reads_best2_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, const HQ *d_queries,
-                             size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, uint32_t *d_second_query,
-                                          uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    bool done;
-    if (int st = check_reads(read_len, count, k, d_queries, reads_qmask<HQ>(), n_queries, d_best_query, d_best_pos, d_best_dist, &done, err)) return st;
-    if (done) return BITNUC_OK;
-    if (int st = check_reads_second(d_second_query, d_second_pos, d_second_dist, err)) return st;
-    DeviceGuard g(c->device);
-    if (reads_no_windows(read_len, k, n_queries)) {
-        if (int st = reads_fill_dev(c, count, d_best_query, d_best_pos, d_best_dist, err)) return st;
-        return reads_fill_dev(c, count, d_second_query, d_second_pos, d_second_dist, err);
-    }
-    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    const ReadsSecond b{d_second_query, d_second_pos, d_second_dist};
-    return launch_reads_best_packed(c, d_words, read_len, count, k, ReadsArgsT<HQ>{d_queries, n_queries, d_best_query, d_best_pos, d_best_dist}, err, &b);
-}
-
-template <class HQ>
-int reads_best2_host(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, const HQ *queries, size_t n_queries,
-                     uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos, uint8_t *second_dist,
-                             bitnuc_err *err) {
-    clear_err(err);
-    bool done;
-    if (int st = check_reads(read_len, count, k, queries, reads_qmask<HQ>(), n_queries, best_query, best_pos, best_dist, &done, err)) return st;
-    if (done) return BITNUC_OK;
-    if (int st = check_reads_second(second_query, second_pos, second_dist, err)) return st;
-    if (reads_no_windows(read_len, k, n_queries)) {
-        bitnuc_host::reads_best_fill(count, best_query, best_pos, best_dist);
-        bitnuc_host::reads_best_fill(count, second_query, second_pos, second_dist);
-        return BITNUC_OK;
-    }
-    if (!reads) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, reads_work(read_len, count, k, n_queries))) {
-        const long long bad = bitnuc_host::reads_hdist_best2_small(reads, read_len, count, k, host_queries(queries), n_queries, best_query, best_pos, best_dist, second_query,
-                                                                   second_pos, second_dist);
-        if (bad >= 0) {
-            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = reads[bad]; err->index = (uint64_t)bad; }
-            return BITNUC_INVALID_BASE;
-        }
-        return BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    const size_t per = read_len < kHostChunk ? kHostChunk / read_len : 1, pm = count < per ? count : per; // whole reads per chunk
-    if (int st = ensure_scratch(c, 0, pm * read_len + 64, err)) return st;
-    return reads_host_loop2(c, count, per, queries, n_queries, best_query, best_pos, best_dist, second_query, second_pos, second_dist, err,
-                            [&](size_t r0, size_t m, const ReadsArgsT<HQ> &a, const ReadsSecond &b) {
-        HIPCHK(hipMemcpyAsync(c->scratch[0], reads + r0 * read_len, m * read_len, hipMemcpyHostToDevice, c->stream));
-        unsigned long long *slot;
-        if (int st = take_slot(c, r0 * read_len, &slot, err)) return st;
-        return launch_reads_best(c, c->scratch[0], read_len, m, k, a, slot, err, &b);
-    });
-}
-
-template <class HQ>
-int reads_best2_packed_host(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, const HQ *queries, size_t n_queries,
-                            uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos,
-                                    uint8_t *second_dist, bitnuc_err *err) {
-    clear_err(err);
-    bool done;
-    if (int st = check_reads(read_len, count, k, queries, reads_qmask<HQ>(), n_queries, best_query, best_pos, best_dist, &done, err)) return st;
-    if (done) return BITNUC_OK;
-    if (int st = check_reads_second(second_query, second_pos, second_dist, err)) return st;
-    if (reads_no_windows(read_len, k, n_queries)) {
-        bitnuc_host::reads_best_fill(count, best_query, best_pos, best_dist);
-        bitnuc_host::reads_best_fill(count, second_query, second_pos, second_dist);
-        return BITNUC_OK;
-    }
-    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, reads_work(read_len, count, k, n_queries))) {
-        bitnuc_host::reads_hdist_best2_packed_small(words, read_len, count, k, host_queries(queries), n_queries, best_query, best_pos, best_dist, second_query, second_pos,
-                                                    second_dist);
-        return BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    const size_t wpr = words_for(read_len);
-    const size_t per = wpr < kPackedChunkWords ? kPackedChunkWords / wpr : 1, pm = count < per ? count : per; // whole reads per chunk
-    if (int st = ensure_scratch(c, 0, pm * wpr * 8, err)) return st;
-    return reads_host_loop2(c, count, per, queries, n_queries, best_query, best_pos, best_dist, second_query, second_pos, second_dist, err,
-                            [&](size_t r0, size_t m, const ReadsArgsT<HQ> &a, const ReadsSecond &b) {
-        HIPCHK(hipMemcpyAsync(c->scratch[0], words + r0 * wpr, m * wpr * 8, hipMemcpyHostToDevice, c->stream));
-        return launch_reads_best_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), read_len, m, k, a, err, &b);
-    });
-}
-
-// ---- the anchored best match and runner-up per read of a fixed-length batch -------------------------------------------------------------
-template <class HQ>
-int reads_anchored_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
-                         const HQ *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist,
-                                      uint32_t *d_second_query, uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    const AnchorOut o{d_best_query, d_best_pos, d_best_dist, d_second_dist, d_second_query, d_second_pos};
-    bool done;
-    size_t offsets;
-    if (int st = check_anchored(read_len, count, k, pos_lo, pos_hi, d_queries, reads_qmask<HQ>(), n_queries, o, &done, &offsets, err)) return st;
-    if (done) return BITNUC_OK;
-    DeviceGuard g(c->device);
-    if (!offsets) return anchored_fill_dev(c, count, o, err);
-    if (!d_reads) return fail(err, BITNUC_UNSUPPORTED);
-    unsigned long long *slot;
-    if (int st = take_slot(c, 0, &slot, err)) return st;
-    return launch_reads_anchored<false>(c, d_reads, read_len, count, k, pos_lo, offsets, d_queries, n_queries, o, slot, err);
-}
-
-template <class HQ>
-int reads_anchored_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
-                                const HQ *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist,
-                                             uint32_t *d_second_query, uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    const AnchorOut o{d_best_query, d_best_pos, d_best_dist, d_second_dist, d_second_query, d_second_pos};
-    bool done;
-    size_t offsets;
-    if (int st = check_anchored(read_len, count, k, pos_lo, pos_hi, d_queries, reads_qmask<HQ>(), n_queries, o, &done, &offsets, err)) return st;
-    if (done) return BITNUC_OK;
-    DeviceGuard g(c->device);
-    if (!offsets) return anchored_fill_dev(c, count, o, err);
-    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    return launch_reads_anchored<true>(c, d_words, words_for(read_len), count, k, pos_lo, offsets, d_queries, n_queries, o, nullptr, err);
-}
-
-template <class HQ>
-int reads_anchored_host(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi, const HQ *queries,
-                        size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos,
-                                uint8_t *second_dist, bitnuc_err *err) {
-    clear_err(err);
-    const AnchorOut o{best_query, best_pos, best_dist, second_dist, second_query, second_pos};
-    bool done;
-    size_t offsets;
-    if (int st = check_anchored(read_len, count, k, pos_lo, pos_hi, queries, reads_qmask<HQ>(), n_queries, o, &done, &offsets, err)) return st;
-    if (done) return BITNUC_OK;
-    if (!offsets) { anchored_fill_host(count, o); return BITNUC_OK; }
-    if (!reads) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, anchored_work(offsets, count, n_queries))) {
-        const long long bad = bitnuc_host::reads_hdist_anchored_small(reads, read_len, count, k, pos_lo, offsets, host_queries(queries), n_queries, best_query, best_pos, best_dist,
-                                                                      second_query, second_pos, second_dist);
-        if (bad >= 0) {
-            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = reads[bad]; err->index = (uint64_t)bad; }
-            return BITNUC_INVALID_BASE;
-        }
-        return BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    const size_t per = read_len < kHostChunk ? kHostChunk / read_len : 1, pm = count < per ? count : per; // whole reads per chunk
-    if (int st = ensure_scratch(c, 0, pm * read_len + 64, err)) return st;
-    return anchored_host_loop(c, count, per, queries, n_queries, o, err, [&](size_t r0, size_t m, const HQ *d_queries, const AnchorOut &d) {
-        HIPCHK(hipMemcpyAsync(c->scratch[0], reads + r0 * read_len, m * read_len, hipMemcpyHostToDevice, c->stream));
-        unsigned long long *slot;
-        if (int st = take_slot(c, r0 * read_len, &slot, err)) return st;
-        return launch_reads_anchored<false>(c, c->scratch[0], read_len, m, k, pos_lo, offsets, d_queries, n_queries, d, slot, err);
-    });
-}
-
-template <class HQ>
-int reads_anchored_packed_host(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
-                               const HQ *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query,
-                                       uint32_t *second_pos, uint8_t *second_dist, bitnuc_err *err) {
-    clear_err(err);
-    const AnchorOut o{best_query, best_pos, best_dist, second_dist, second_query, second_pos};
-    bool done;
-    size_t offsets;
-    if (int st = check_anchored(read_len, count, k, pos_lo, pos_hi, queries, reads_qmask<HQ>(), n_queries, o, &done, &offsets, err)) return st;
-    if (done) return BITNUC_OK;
-    if (!offsets) { anchored_fill_host(count, o); return BITNUC_OK; }
-    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, anchored_work(offsets, count, n_queries))) {
-        bitnuc_host::reads_hdist_anchored_packed_small(words, read_len, count, k, pos_lo, offsets, host_queries(queries), n_queries, best_query, best_pos, best_dist, second_query,
-                                                       second_pos, second_dist);
-        return BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    const size_t wpr = words_for(read_len);
-    const size_t per = wpr < kPackedChunkWords ? kPackedChunkWords / wpr : 1, pm = count < per ? count : per; // whole reads per chunk
-    if (int st = ensure_scratch(c, 0, pm * wpr * 8, err)) return st;
-    return anchored_host_loop(c, count, per, queries, n_queries, o, err, [&](size_t r0, size_t m, const HQ *d_queries, const AnchorOut &d) {
-        HIPCHK(hipMemcpyAsync(c->scratch[0], words + r0 * wpr, m * wpr * 8, hipMemcpyHostToDevice, c->stream));
-        return launch_reads_anchored<true>(c, c->scratch[0], wpr, m, k, pos_lo, offsets, d_queries, n_queries, d, nullptr, err);
-    });
-}
-
-// ---- the indel-tolerant anchored best match and runner-up per read of a fixed-length batch: the anchored forms above with the edit distance -------------
-template <class HQ>
-int reads_edist_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi, const HQ *d_queries,
-                      size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_end,
-                      uint8_t *d_second_dist, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    const AnchorOut o{d_best_query, d_best_end, d_best_dist, d_second_dist, d_second_query, d_second_end};
-    bool done;
-    size_t offsets;
-    if (int st = check_anchored(read_len, count, k, pos_lo, pos_hi, d_queries, reads_qmask<HQ>(), n_queries, o, &done, &offsets, err)) return st;
-    if (done) return BITNUC_OK;
-    DeviceGuard g(c->device);
-    if (!offsets) return anchored_fill_dev(c, count, o, err);
-    if (!d_reads) return fail(err, BITNUC_UNSUPPORTED);
-    unsigned long long *slot;
-    if (int st = take_slot(c, 0, &slot, err)) return st;
-    return launch_reads_edist<false>(c, d_reads, read_len, count, k, pos_lo, offsets + k - 1, d_queries, n_queries, o, slot, err);
-}
-
-template <class HQ>
-int reads_edist_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi, const HQ *d_queries,
-                             size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist, uint32_t *d_second_query,
-                             uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    const AnchorOut o{d_best_query, d_best_end, d_best_dist, d_second_dist, d_second_query, d_second_end};
-    bool done;
-    size_t offsets;
-    if (int st = check_anchored(read_len, count, k, pos_lo, pos_hi, d_queries, reads_qmask<HQ>(), n_queries, o, &done, &offsets, err)) return st;
-    if (done) return BITNUC_OK;
-    DeviceGuard g(c->device);
-    if (!offsets) return anchored_fill_dev(c, count, o, err);
-    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    return launch_reads_edist<true>(c, d_words, words_for(read_len), count, k, pos_lo, offsets + k - 1, d_queries, n_queries, o, nullptr, err);
-}
-
-template <class HQ>
-int reads_edist_host(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi, const HQ *queries,
-                     size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_end,
-                     uint8_t *second_dist, bitnuc_err *err) {
-    clear_err(err);
-    const AnchorOut o{best_query, best_end, best_dist, second_dist, second_query, second_end};
-    bool done;
-    size_t offsets;
-    if (int st = check_anchored(read_len, count, k, pos_lo, pos_hi, queries, reads_qmask<HQ>(), n_queries, o, &done, &offsets, err)) return st;
-    if (done) return BITNUC_OK;
-    if (!offsets) { anchored_fill_host(count, o); return BITNUC_OK; }
-    if (!reads) return fail(err, BITNUC_UNSUPPORTED);
-    const size_t n = offsets + k - 1; // the span: what the cutoff is judged on, count x n x n_queries
-    if (on_host(c, anchored_work(n, count, n_queries))) {
-        const long long bad = bitnuc_host::reads_edist_anchored_small(reads, read_len, count, k, pos_lo, n, host_queries(queries), n_queries, best_query, best_end, best_dist,
-                                                                      second_query, second_end, second_dist);
-        if (bad >= 0) {
-            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = reads[bad]; err->index = (uint64_t)bad; }
-            return BITNUC_INVALID_BASE;
-        }
-        return BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    const size_t per = read_len < kHostChunk ? kHostChunk / read_len : 1, pm = count < per ? count : per; // whole reads per chunk
-    if (int st = ensure_scratch(c, 0, pm * read_len + 64, err)) return st;
-    return anchored_host_loop(c, count, per, queries, n_queries, o, err, [&](size_t r0, size_t m, const HQ *d_queries, const AnchorOut &d) {
-        HIPCHK(hipMemcpyAsync(c->scratch[0], reads + r0 * read_len, m * read_len, hipMemcpyHostToDevice, c->stream));
-        unsigned long long *slot;
-        if (int st = take_slot(c, r0 * read_len, &slot, err)) return st;
-        return launch_reads_edist<false>(c, c->scratch[0], read_len, m, k, pos_lo, n, d_queries, n_queries, d, slot, err);
-    });
-}
-
-template <class HQ>
-int reads_edist_packed_host(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi, const HQ *queries,
-                            size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_end,
-                            uint8_t *second_dist, bitnuc_err *err) {
-    clear_err(err);
-    const AnchorOut o{best_query, best_end, best_dist, second_dist, second_query, second_end};
-    bool done;
-    size_t offsets;
-    if (int st = check_anchored(read_len, count, k, pos_lo, pos_hi, queries, reads_qmask<HQ>(), n_queries, o, &done, &offsets, err)) return st;
-    if (done) return BITNUC_OK;
-    if (!offsets) { anchored_fill_host(count, o); return BITNUC_OK; }
-    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    const size_t n = offsets + k - 1;
-    if (on_host(c, anchored_work(n, count, n_queries))) {
-        bitnuc_host::reads_edist_anchored_packed_small(words, read_len, count, k, pos_lo, n, host_queries(queries), n_queries, best_query, best_end, best_dist, second_query,
-                                                       second_end, second_dist);
-        return BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    const size_t wpr = words_for(read_len);
-    const size_t per = wpr < kPackedChunkWords ? kPackedChunkWords / wpr : 1, pm = count < per ? count : per; // whole reads per chunk
-    if (int st = ensure_scratch(c, 0, pm * wpr * 8, err)) return st;
-    return anchored_host_loop(c, count, per, queries, n_queries, o, err, [&](size_t r0, size_t m, const HQ *d_queries, const AnchorOut &d) {
-        HIPCHK(hipMemcpyAsync(c->scratch[0], words + r0 * wpr, m * wpr * 8, hipMemcpyHostToDevice, c->stream));
-        return launch_reads_edist<true>(c, c->scratch[0], wpr, m, k, pos_lo, n, d_queries, n_queries, d, nullptr, err);
-    });
-}
-
-// ---- the anchored best match and runner-up per read of a ragged batch ----------------------------------------------------------------
-template <class HQ>
-int reads_anchored_batch_async(bitnuc_ctx *c, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k, int anchor,
-                               size_t pos_lo, size_t pos_hi, const HQ *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos,
-                                            uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    const AnchorOut o{d_best_query, d_best_pos, d_best_dist, d_second_dist, d_second_query, d_second_pos};
-    bool done;
-    size_t offsets;
-    if (int st = check_anchored_batch(total_bases, total_bases, count, k, anchor, pos_lo, pos_hi, d_queries, reads_qmask<HQ>(), n_queries, o, d_offsets, nullptr, false, &done, &offsets, err))
-        return st;
-    if (done) return BITNUC_OK;
-    DeviceGuard g(c->device);
-    if (anchored_batch_no_window(total_bases, k, n_queries, offsets, pos_lo)) return anchored_fill_dev(c, count, o, err);
-    if (!d_seq) return fail(err, BITNUC_UNSUPPORTED);
-    unsigned long long *slot;
-    if (int st = take_slot(c, 0, &slot, err)) return st;
-    return launch_reads_anchored_batch<false>(c, d_seq, nullptr, d_offsets, count, k, anchor, pos_lo, offsets, d_queries, n_queries, o, slot, err);
-}
-
-template <class HQ>
-int reads_anchored_batch_packed_async(bitnuc_ctx *c, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
-                                      size_t total_words, size_t k, int anchor, size_t pos_lo, size_t pos_hi, const HQ *d_queries, size_t n_queries,
-                                                   uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, uint32_t *d_second_query,
-                                                   uint32_t *d_second_pos, uint8_t *d_second_dist, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    const AnchorOut o{d_best_query, d_best_pos, d_best_dist, d_second_dist, d_second_query, d_second_pos};
-    bool done;
-    size_t offsets;
-    const uint64_t as_bases = total_words >= ((uint64_t)1 << 53) ? ~(uint64_t)0 : 32 * (uint64_t)total_words;
-    if (int st = check_anchored_batch(as_bases, total_words, count, k, anchor, pos_lo, pos_hi, d_queries, reads_qmask<HQ>(), n_queries, o, d_word_offsets, d_offsets, true, &done, &offsets,
-                                      err))
-        return st;
-    if (done) return BITNUC_OK;
-    DeviceGuard g(c->device);
-    if (anchored_batch_no_window(as_bases, k, n_queries, offsets, pos_lo)) return anchored_fill_dev(c, count, o, err);
-    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    return launch_reads_anchored_batch<true>(c, d_words, d_word_offsets, d_offsets, count, k, anchor, pos_lo, offsets, d_queries, n_queries, o, nullptr, err);
-}
-
-template <class HQ>
-int reads_anchored_batch_host(bitnuc_ctx *c, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, int anchor, size_t pos_lo, size_t pos_hi,
-                              const HQ *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query,
-                                      uint32_t *second_pos, uint8_t *second_dist, bitnuc_err *err) {
-    clear_err(err);
-    const AnchorOut o{best_query, best_pos, best_dist, second_dist, second_query, second_pos};
-    bool done;
-    size_t width; // the range's offsets
-    if (int st = check_anchored_batch(0, 0, count, k, anchor, pos_lo, pos_hi, queries, reads_qmask<HQ>(), n_queries, o, offsets, nullptr, false, &done, &width, err)) return st;
-    if (done) return BITNUC_OK;
-    const BatchFault f = batch_check_tables(offsets, nullptr, count);
-    if (f.kind) return fail_batch_tables(f, err);
-    if (anchored_batch_no_window(offsets[count], k, n_queries, width, pos_lo)) { anchored_fill_host(count, o); return BITNUC_OK; }
-    if (!seq) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, anchored_work(width, count, n_queries))) {
-        const long long bad = bitnuc_host::reads_hdist_anchored_batch_small(seq, offsets, count, k, anchor, pos_lo, pos_hi, host_queries(queries), n_queries, best_query, best_pos,
-                                                                            best_dist, second_query, second_pos, second_dist);
-        if (bad >= 0) {
-            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = seq[bad]; err->index = (uint64_t)bad; }
-            return BITNUC_INVALID_BASE;
-        }
-        return BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    std::vector<uint64_t> tab; // the chunk's rebased table
-    return anchored_batch_host_loop(
-        c, count, queries, n_queries, o, err,
-        [&](size_t r0) { return batch_chunk_end(r0, count, kHostChunk, [&](size_t a, size_t b) { return offsets[b] - offsets[a]; }); },
-        [&](size_t r0, size_t m, const HQ *d_queries, const AnchorOut &d) {
-            const size_t b0 = (size_t)offsets[r0], bytes = (size_t)offsets[r0 + m] - b0;
-            if (anchored_batch_no_window(bytes, k, n_queries, width, pos_lo)) return anchored_fill_dev(c, m, d, err); // nothing to launch, nothing validated
-            if (int st = ensure_scratch(c, 0, bytes + 64, err)) return st;
-            if (int st = ensure_scratch(c, 4, (m + 1) * 8, err)) return st;
-            tab.resize(m + 1);
-            for (size_t i = 0; i <= m; ++i) tab[i] = offsets[r0 + i] - b0;
-            HIPCHK(hipMemcpyAsync(c->scratch[0], seq + b0, bytes, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(c->scratch[4], tab.data(), (m + 1) * 8, hipMemcpyHostToDevice, c->stream));
-            unsigned long long *slot;
-            if (int st = take_slot(c, b0, &slot, err)) return st;
-            return launch_reads_anchored_batch<false>(c, c->scratch[0], nullptr, reinterpret_cast<const uint64_t *>(c->scratch[4]), m, k, anchor, pos_lo, width, d_queries,
-                                                      n_queries, d, slot, err);
-        });
-}
-
-template <class HQ>
-int reads_anchored_batch_packed_host(bitnuc_ctx *c, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
-                                     int anchor, size_t pos_lo, size_t pos_hi, const HQ *queries, size_t n_queries, uint32_t *best_query,
-                                             uint32_t *best_pos, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_pos, uint8_t *second_dist, bitnuc_err *err) {
-    clear_err(err);
-    const AnchorOut o{best_query, best_pos, best_dist, second_dist, second_query, second_pos};
-    bool done;
-    size_t width;
-    if (int st = check_anchored_batch(0, 0, count, k, anchor, pos_lo, pos_hi, queries, reads_qmask<HQ>(), n_queries, o, word_offsets, offsets, true, &done, &width, err)) return st;
-    if (done) return BITNUC_OK;
-    const BatchFault f = batch_check_tables(offsets, word_offsets, count);
-    if (f.kind) return fail_batch_tables(f, err);
-    if (anchored_batch_no_window(offsets[count], k, n_queries, width, pos_lo)) { anchored_fill_host(count, o); return BITNUC_OK; }
-    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, anchored_work(width, count, n_queries))) {
-        bitnuc_host::reads_hdist_anchored_batch_packed_small(words, word_offsets, offsets, count, k, anchor, pos_lo, pos_hi, host_queries(queries), n_queries, best_query, best_pos,
-                                                             best_dist, second_query, second_pos, second_dist);
-        return BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    std::vector<uint64_t> tab; // the chunk's two rebased tables: word_offsets, then offsets
-    return anchored_batch_host_loop(
-        c, count, queries, n_queries, o, err,
-        [&](size_t r0) { return batch_chunk_end(r0, count, kPackedChunkWords, [&](size_t a, size_t b) { return word_offsets[b] - word_offsets[a]; }); },
-        [&](size_t r0, size_t m, const HQ *d_queries, const AnchorOut &d) {
-            const size_t w0 = (size_t)word_offsets[r0], nw = (size_t)word_offsets[r0 + m] - w0;
-            if (nw == 0) return anchored_fill_dev(c, m, d, err);
-            if (int st = ensure_scratch(c, 0, nw * 8, err)) return st;
-            if (int st = ensure_scratch(c, 4, 2 * (m + 1) * 8, err)) return st;
-            tab.resize(2 * (m + 1));
-            for (size_t i = 0; i <= m; ++i) tab[i] = word_offsets[r0 + i] - w0, tab[m + 1 + i] = offsets[r0 + i] - offsets[r0];
-            HIPCHK(hipMemcpyAsync(c->scratch[0], words + w0, nw * 8, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(c->scratch[4], tab.data(), 2 * (m + 1) * 8, hipMemcpyHostToDevice, c->stream));
-            const uint64_t *d_tab = reinterpret_cast<const uint64_t *>(c->scratch[4]);
-            return launch_reads_anchored_batch<true>(c, c->scratch[0], d_tab, d_tab + m + 1, m, k, anchor, pos_lo, width, d_queries, n_queries, d, nullptr, err);
-        });
-}
-
-// ---- the indel-tolerant anchored best match and runner-up per read of a ragged batch: the four forms above with the edit distance ----------------------
-template <class HQ>
-int reads_edist_batch_async(bitnuc_ctx *c, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k, int anchor, size_t pos_lo,
-                            size_t pos_hi, const HQ *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist,
-                            uint32_t *d_second_query, uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    const AnchorOut o{d_best_query, d_best_end, d_best_dist, d_second_dist, d_second_query, d_second_end};
-    bool done;
-    size_t offsets;
-    if (int st = check_anchored_batch(total_bases, total_bases, count, k, anchor, pos_lo, pos_hi, d_queries, reads_qmask<HQ>(), n_queries, o, d_offsets, nullptr, false, &done, &offsets, err))
-        return st;
-    if (done) return BITNUC_OK;
-    DeviceGuard g(c->device);
-    if (anchored_batch_no_window(total_bases, k, n_queries, offsets, pos_lo)) return anchored_fill_dev(c, count, o, err);
-    if (!d_seq) return fail(err, BITNUC_UNSUPPORTED);
-    unsigned long long *slot;
-    if (int st = take_slot(c, 0, &slot, err)) return st;
-    return launch_reads_edist_batch<false>(c, d_seq, nullptr, d_offsets, count, k, anchor, pos_lo, offsets, d_queries, n_queries, o, slot, err);
-}
-
-template <class HQ>
-int reads_edist_batch_packed_async(bitnuc_ctx *c, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
-                                   size_t total_words, size_t k, int anchor, size_t pos_lo, size_t pos_hi, const HQ *d_queries, size_t n_queries,
-                                   uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_end,
-                                   uint8_t *d_second_dist, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    const AnchorOut o{d_best_query, d_best_end, d_best_dist, d_second_dist, d_second_query, d_second_end};
-    bool done;
-    size_t offsets;
-    const uint64_t as_bases = total_words >= ((uint64_t)1 << 53) ? ~(uint64_t)0 : 32 * (uint64_t)total_words;
-    if (int st = check_anchored_batch(as_bases, total_words, count, k, anchor, pos_lo, pos_hi, d_queries, reads_qmask<HQ>(), n_queries, o, d_word_offsets, d_offsets, true, &done, &offsets,
-                                      err))
-        return st;
-    if (done) return BITNUC_OK;
-    DeviceGuard g(c->device);
-    if (anchored_batch_no_window(as_bases, k, n_queries, offsets, pos_lo)) return anchored_fill_dev(c, count, o, err);
-    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    return launch_reads_edist_batch<true>(c, d_words, d_word_offsets, d_offsets, count, k, anchor, pos_lo, offsets, d_queries, n_queries, o, nullptr, err);
-}
-
-template <class HQ>
-int reads_edist_batch_host(bitnuc_ctx *c, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, int anchor, size_t pos_lo, size_t pos_hi,
-                           const HQ *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query,
-                           uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err) {
-    clear_err(err);
-    const AnchorOut o{best_query, best_end, best_dist, second_dist, second_query, second_end};
-    bool done;
-    size_t width; // the range's offsets
-    if (int st = check_anchored_batch(0, 0, count, k, anchor, pos_lo, pos_hi, queries, reads_qmask<HQ>(), n_queries, o, offsets, nullptr, false, &done, &width, err)) return st;
-    if (done) return BITNUC_OK;
-    const BatchFault f = batch_check_tables(offsets, nullptr, count);
-    if (f.kind) return fail_batch_tables(f, err);
-    if (anchored_batch_no_window(offsets[count], k, n_queries, width, pos_lo)) { anchored_fill_host(count, o); return BITNUC_OK; }
-    if (!seq) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, anchored_work(width + k - 1, count, n_queries))) { // the widest span: what the cutoff is judged on
-        const long long bad = bitnuc_host::reads_edist_anchored_batch_small(seq, offsets, count, k, anchor, pos_lo, pos_hi, host_queries(queries), n_queries, best_query, best_end,
-                                                                            best_dist, second_query, second_end, second_dist);
-        if (bad >= 0) {
-            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = seq[bad]; err->index = (uint64_t)bad; }
-            return BITNUC_INVALID_BASE;
-        }
-        return BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    std::vector<uint64_t> tab; // the chunk's rebased table
-    return anchored_batch_host_loop(
-        c, count, queries, n_queries, o, err,
-        [&](size_t r0) { return batch_chunk_end(r0, count, kHostChunk, [&](size_t a, size_t b) { return offsets[b] - offsets[a]; }); },
-        [&](size_t r0, size_t m, const HQ *d_queries, const AnchorOut &d) {
-            const size_t b0 = (size_t)offsets[r0], bytes = (size_t)offsets[r0 + m] - b0;
-            if (anchored_batch_no_window(bytes, k, n_queries, width, pos_lo)) return anchored_fill_dev(c, m, d, err); // nothing to launch, nothing validated
-            if (int st = ensure_scratch(c, 0, bytes + 64, err)) return st;
-            if (int st = ensure_scratch(c, 4, (m + 1) * 8, err)) return st;
-            tab.resize(m + 1);
-            for (size_t i = 0; i <= m; ++i) tab[i] = offsets[r0 + i] - b0;
-            HIPCHK(hipMemcpyAsync(c->scratch[0], seq + b0, bytes, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(c->scratch[4], tab.data(), (m + 1) * 8, hipMemcpyHostToDevice, c->stream));
-            unsigned long long *slot;
-            if (int st = take_slot(c, b0, &slot, err)) return st;
-            return launch_reads_edist_batch<false>(c, c->scratch[0], nullptr, reinterpret_cast<const uint64_t *>(c->scratch[4]), m, k, anchor, pos_lo, width, d_queries,
-                                                   n_queries, d, slot, err);
-        });
-}
-
-template <class HQ>
-int reads_edist_batch_packed_host(bitnuc_ctx *c, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k, int anchor,
-                                  size_t pos_lo, size_t pos_hi, const HQ *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist,
-                                  uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err) {
-    clear_err(err);
-    const AnchorOut o{best_query, best_end, best_dist, second_dist, second_query, second_end};
-    bool done;
-    size_t width;
-    if (int st = check_anchored_batch(0, 0, count, k, anchor, pos_lo, pos_hi, queries, reads_qmask<HQ>(), n_queries, o, word_offsets, offsets, true, &done, &width, err)) return st;
-    if (done) return BITNUC_OK;
-    const BatchFault f = batch_check_tables(offsets, word_offsets, count);
-    if (f.kind) return fail_batch_tables(f, err);
-    if (anchored_batch_no_window(offsets[count], k, n_queries, width, pos_lo)) { anchored_fill_host(count, o); return BITNUC_OK; }
-    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, anchored_work(width + k - 1, count, n_queries))) {
-        bitnuc_host::reads_edist_anchored_batch_packed_small(words, word_offsets, offsets, count, k, anchor, pos_lo, pos_hi, host_queries(queries), n_queries, best_query, best_end,
-                                                             best_dist, second_query, second_end, second_dist);
-        return BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    std::vector<uint64_t> tab; // the chunk's two rebased tables: word_offsets, then offsets
-    return anchored_batch_host_loop(
-        c, count, queries, n_queries, o, err,
-        [&](size_t r0) { return batch_chunk_end(r0, count, kPackedChunkWords, [&](size_t a, size_t b) { return word_offsets[b] - word_offsets[a]; }); },
-        [&](size_t r0, size_t m, const HQ *d_queries, const AnchorOut &d) {
-            const size_t w0 = (size_t)word_offsets[r0], nw = (size_t)word_offsets[r0 + m] - w0;
-            if (nw == 0) return anchored_fill_dev(c, m, d, err);
-            if (int st = ensure_scratch(c, 0, nw * 8, err)) return st;
-            if (int st = ensure_scratch(c, 4, 2 * (m + 1) * 8, err)) return st;
-            tab.resize(2 * (m + 1));
-            for (size_t i = 0; i <= m; ++i) tab[i] = word_offsets[r0 + i] - w0, tab[m + 1 + i] = offsets[r0 + i] - offsets[r0];
-            HIPCHK(hipMemcpyAsync(c->scratch[0], words + w0, nw * 8, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(c->scratch[4], tab.data(), 2 * (m + 1) * 8, hipMemcpyHostToDevice, c->stream));
-            const uint64_t *d_tab = reinterpret_cast<const uint64_t *>(c->scratch[4]);
-            return launch_reads_edist_batch<true>(c, c->scratch[0], d_tab, d_tab + m + 1, m, k, anchor, pos_lo, width, d_queries, n_queries, d, nullptr, err);
-        });
-}
-
-// ---- the best match per read of a ragged batch ------------------------------------------------------------------------------------
-template <class HQ>
-int reads_best_batch_async(bitnuc_ctx *c, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k,
-                           const HQ *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    bool done;
-    if (int st = check_reads_batch(total_bases, total_bases, count, k, d_queries, reads_qmask<HQ>(), n_queries, d_best_query, d_best_pos, d_best_dist, d_offsets, nullptr, false, &done, err)) return st;
-    if (done) return BITNUC_OK;
-    DeviceGuard g(c->device);
-    if (k == 0 || n_queries == 0 || total_bases < k) return reads_fill_dev(c, count, d_best_query, d_best_pos, d_best_dist, err);
-    if (!d_seq) return fail(err, BITNUC_UNSUPPORTED);
-    unsigned long long *slot;
-    if (int st = take_slot(c, 0, &slot, err)) return st;
-    return launch_reads_batch(c, d_seq, d_offsets, count, total_bases, k, ReadsArgsT<HQ>{d_queries, n_queries, d_best_query, d_best_pos, d_best_dist}, slot, err);
-}
-
-template <class HQ>
-int reads_best_batch_packed_async(bitnuc_ctx *c, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
-                                  size_t total_words, size_t k, const HQ *d_queries, size_t n_queries, uint32_t *d_best_query,
-                                               uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    bool done;
-    const uint64_t as_bases = total_words >= ((uint64_t)1 << 53) ? ~(uint64_t)0 : 32 * (uint64_t)total_words;
-    if (int st = check_reads_batch(as_bases, total_words, count, k, d_queries, reads_qmask<HQ>(), n_queries, d_best_query, d_best_pos, d_best_dist, d_word_offsets, d_offsets, true, &done, err)) return st;
-    if (done) return BITNUC_OK;
-    DeviceGuard g(c->device);
-    if (k == 0 || n_queries == 0 || total_words == 0) return reads_fill_dev(c, count, d_best_query, d_best_pos, d_best_dist, err);
-    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    return launch_reads_batch_packed(c, d_words, d_word_offsets, d_offsets, count, total_words, k, ReadsArgsT<HQ>{d_queries, n_queries, d_best_query, d_best_pos, d_best_dist}, err);
-}
-
-template <class HQ>
-int reads_best_batch_host(bitnuc_ctx *c, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, const HQ *queries, size_t n_queries,
-                          uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err) {
-    clear_err(err);
-    bool done;
-    if (int st = check_reads_batch(0, 0, count, k, queries, reads_qmask<HQ>(), n_queries, best_query, best_pos, best_dist, offsets, nullptr, false, &done, err)) return st;
-    if (done) return BITNUC_OK;
-    const BatchFault f = batch_check_tables(offsets, nullptr, count);
-    if (f.kind) return fail_batch_tables(f, err);
-    const size_t total = (size_t)offsets[count];
-    if (k == 0 || n_queries == 0 || total < k) { bitnuc_host::reads_best_fill(count, best_query, best_pos, best_dist); return BITNUC_OK; }
-    if (!seq) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, multi_work(batch_windows(offsets, count, k), n_queries))) {
-        const long long bad = bitnuc_host::reads_hdist_best_batch_small(seq, offsets, count, k, host_queries(queries), n_queries, best_query, best_pos, best_dist);
-        if (bad >= 0) {
-            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = seq[bad]; err->index = (uint64_t)bad; }
-            return BITNUC_INVALID_BASE;
-        }
-        return BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    std::vector<uint64_t> tab; // the chunk's rebased table
-    return reads_batch_host_loop(
-        c, count, queries, n_queries, best_query, best_pos, best_dist, err,
-        [&](size_t r0) { return batch_chunk_end(r0, count, kHostChunk, [&](size_t a, size_t b) { return offsets[b] - offsets[a]; }); },
-        [&](size_t r0, size_t m, const ReadsArgsT<HQ> &a) {
-            const size_t b0 = (size_t)offsets[r0], bytes = (size_t)offsets[r0 + m] - b0;
-            if (bytes < k) { // no window in the chunk and nothing to launch: its bytes are still validated, here
-                for (size_t i = 0; i < bytes; ++i) {
-                    const unsigned u = seq[b0 + i] & 0xDFu;
-                    if (u != 'A' && u != 'C' && u != 'G' && u != 'T') {
-                        if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = seq[b0 + i]; err->index = (uint64_t)(b0 + i); }
-                        return (int)BITNUC_INVALID_BASE;
-                    }
-                }
-                return reads_fill_dev(c, m, a.query, a.pos, a.dist, err);
-            }
-            if (int st = ensure_scratch(c, 0, bytes + 64, err)) return st;
-            if (int st = ensure_scratch(c, 4, (m + 1) * 8, err)) return st;
-            tab.resize(m + 1);
-            for (size_t i = 0; i <= m; ++i) tab[i] = offsets[r0 + i] - b0;
-            HIPCHK(hipMemcpyAsync(c->scratch[0], seq + b0, bytes, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(c->scratch[4], tab.data(), (m + 1) * 8, hipMemcpyHostToDevice, c->stream));
-            unsigned long long *slot;
-            if (int st = take_slot(c, b0, &slot, err)) return st;
-            return launch_reads_batch(c, c->scratch[0], reinterpret_cast<const uint64_t *>(c->scratch[4]), m, bytes, k, a, slot, err);
-        });
-}
-
-template <class HQ>
-int reads_best_batch_packed_host(bitnuc_ctx *c, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
-                                 const HQ *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err) {
-    clear_err(err);
-    bool done;
-    if (int st = check_reads_batch(0, 0, count, k, queries, reads_qmask<HQ>(), n_queries, best_query, best_pos, best_dist, word_offsets, offsets, true, &done, err)) return st;
-    if (done) return BITNUC_OK;
-    const BatchFault f = batch_check_tables(offsets, word_offsets, count);
-    if (f.kind) return fail_batch_tables(f, err);
-    if (k == 0 || n_queries == 0 || offsets[count] < k) { bitnuc_host::reads_best_fill(count, best_query, best_pos, best_dist); return BITNUC_OK; }
-    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, multi_work(batch_windows(offsets, count, k), n_queries))) {
-        bitnuc_host::reads_hdist_best_batch_packed_small(words, word_offsets, offsets, count, k, host_queries(queries), n_queries, best_query, best_pos, best_dist);
-        return BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    std::vector<uint64_t> tab; // the chunk's two rebased tables: word_offsets, then offsets
-    return reads_batch_host_loop(
-        c, count, queries, n_queries, best_query, best_pos, best_dist, err,
-        [&](size_t r0) { return batch_chunk_end(r0, count, kPackedChunkWords, [&](size_t a, size_t b) { return word_offsets[b] - word_offsets[a]; }); },
-        [&](size_t r0, size_t m, const ReadsArgsT<HQ> &a) {
-            const size_t w0 = (size_t)word_offsets[r0], nw = (size_t)word_offsets[r0 + m] - w0;
-            if (nw == 0) return reads_fill_dev(c, m, a.query, a.pos, a.dist, err);
-            if (int st = ensure_scratch(c, 0, nw * 8, err)) return st;
-            if (int st = ensure_scratch(c, 4, 2 * (m + 1) * 8, err)) return st;
-            tab.resize(2 * (m + 1));
-            for (size_t i = 0; i <= m; ++i) tab[i] = word_offsets[r0 + i] - w0, tab[m + 1 + i] = offsets[r0 + i] - offsets[r0];
-            HIPCHK(hipMemcpyAsync(c->scratch[0], words + w0, nw * 8, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(c->scratch[4], tab.data(), 2 * (m + 1) * 8, hipMemcpyHostToDevice, c->stream));
-            const uint64_t *d_tab = reinterpret_cast<const uint64_t *>(c->scratch[4]);
-            return launch_reads_batch_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), d_tab, d_tab + m + 1, m, nw, k, a, err);
-        });
-}
-
-} // namespace
+// ---- the per-read matchers: layouts, matchers, the chunk loop, the two skeletons and the forms the entry points below name
+#include "reads_dispatch.h"
 
 extern "C" {
 
-// ---- the per-read entry points: every form once per query kind, each naming its instantiation of the templates above ----
+// ---- the per-read entry points: every form once per query kind, each naming its instantiation of the templates in reads_dispatch.h ----
 // exact queries
 int bitnuc_reads_hdist_best_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const uint64_t *d_queries, size_t n_queries,
                                   uint32_t *d_best_query, uint32_t *d_best_pos, uint8_t *d_best_dist, bitnuc_err *err) {
@@ -2874,10 +1604,7 @@ int bitnuc_pattern_from_iupac(const uint8_t *letters, size_t k, bitnuc_pattern *
     if (!out || (!letters && k)) return fail(err, BITNUC_UNSUPPORTED);
     PatternSets p;
     const long long bad = bitnuc_host::pattern_from_iupac(letters, k, &p);
-    if (bad >= 0) {
-        if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = letters[bad]; err->index = (uint64_t)bad; }
-        return BITNUC_INVALID_BASE;
-    }
+    if (bad >= 0) return fail_invalid_base(err, letters[bad], (uint64_t)bad);
     memcpy(out, &p, sizeof p);
     return BITNUC_OK;
 }
@@ -2939,11 +1666,7 @@ int bitnuc_kmer_pattern_count_multi(bitnuc_ctx *c, const uint8_t *ref, size_t n,
     if (!ref) return fail(err, BITNUC_UNSUPPORTED);
     if (on_host(c, multi_work(n - k + 1, n_queries))) {
         const long long bad = bitnuc_host::kmer_hdist_count_multi_small(ref, n, k, dev_queries(patterns), taus, n_queries, counts);
-        if (bad >= 0) {
-            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = ref[bad]; err->index = (uint64_t)bad; }
-            return BITNUC_INVALID_BASE;
-        }
-        return BITNUC_OK;
+        return bad >= 0 ? fail_invalid_base(err, ref[bad], (uint64_t)bad) : BITNUC_OK;
     }
     if (int st = check_ctx(c, err)) return st;
     DeviceGuard g(c->device);
@@ -3028,11 +1751,7 @@ int bitnuc_kmer_pattern_best(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t
     if (!ref) return fail(err, BITNUC_UNSUPPORTED);
     if (on_host(c, multi_work(n - k + 1, n_queries))) {
         const long long bad = bitnuc_host::kmer_hdist_best_small(ref, n, k, dev_queries(patterns), n_queries, pos, dist);
-        if (bad >= 0) {
-            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = ref[bad]; err->index = (uint64_t)bad; }
-            return BITNUC_INVALID_BASE;
-        }
-        return BITNUC_OK;
+        return bad >= 0 ? fail_invalid_base(err, ref[bad], (uint64_t)bad) : BITNUC_OK;
     }
     if (int st = check_ctx(c, err)) return st;
     DeviceGuard g(c->device);
@@ -3154,11 +1873,7 @@ int bitnuc_kmer_pattern_hits(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t
     if (!ref) return fail(err, BITNUC_UNSUPPORTED);
     if (on_host(c, n)) {
         const long long bad = bitnuc_host::kmer_hdist_hits_small(ref, n, k, dev_query(*pattern), tau, pos, hit_dist, cap, n_hits);
-        if (bad >= 0) {
-            if (err) { memset(err, 0, sizeof *err); err->status = BITNUC_INVALID_BASE; err->byte = ref[bad]; err->index = (uint64_t)bad; }
-            return BITNUC_INVALID_BASE;
-        }
-        return BITNUC_OK;
+        return bad >= 0 ? fail_invalid_base(err, ref[bad], (uint64_t)bad) : BITNUC_OK;
     }
     if (int st = check_ctx(c, err)) return st;
     DeviceGuard g(c->device);
