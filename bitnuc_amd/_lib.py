@@ -133,6 +133,22 @@ SIGNATURES = {
     "bitnuc_kmer_pattern_best_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _ERR]),
     "bitnuc_kmer_pattern_best": (C.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _ERR]),
     "bitnuc_kmer_pattern_best_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _ERR]),
+    "bitnuc_kmer_edist_best_async": (C.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _ERR]),
+    "bitnuc_kmer_edist_best_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _ERR]),
+    "bitnuc_kmer_edist_best": (C.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _ERR]),
+    "bitnuc_kmer_edist_best_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _ERR]),
+    "bitnuc_kmer_edist_count_multi_async": (C.c_int, [_P, _P, _SZ, _SZ, _P, _P, _SZ, _P, _ERR]),
+    "bitnuc_kmer_edist_count_multi_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _P, _SZ, _P, _ERR]),
+    "bitnuc_kmer_edist_count_multi": (C.c_int, [_P, _P, _SZ, _SZ, _P, _P, _SZ, _P, _ERR]),
+    "bitnuc_kmer_edist_count_multi_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _P, _SZ, _P, _ERR]),
+    "bitnuc_kmer_pattern_edist_best_async": (C.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _ERR]),
+    "bitnuc_kmer_pattern_edist_best_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _ERR]),
+    "bitnuc_kmer_pattern_edist_best": (C.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _ERR]),
+    "bitnuc_kmer_pattern_edist_best_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _ERR]),
+    "bitnuc_kmer_pattern_edist_count_multi_async": (C.c_int, [_P, _P, _SZ, _SZ, _P, _P, _SZ, _P, _ERR]),
+    "bitnuc_kmer_pattern_edist_count_multi_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _P, _SZ, _P, _ERR]),
+    "bitnuc_kmer_pattern_edist_count_multi": (C.c_int, [_P, _P, _SZ, _SZ, _P, _P, _SZ, _P, _ERR]),
+    "bitnuc_kmer_pattern_edist_count_multi_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _P, _SZ, _P, _ERR]),
     "bitnuc_kmer_hdist_hist_async": (C.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _P, _ERR]),
     "bitnuc_kmer_hdist_hist_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _SZ, _P, _ERR]),
     "bitnuc_kmer_hdist_hist": (C.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _P, _ERR]),

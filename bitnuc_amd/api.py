@@ -610,6 +610,61 @@ class Context:
         w = _as_u64(words)
         return self._pattern_best(self._lib.bitnuc_kmer_pattern_best_packed, (_ptr(w), w.size, int(n_bases), int(k)), patterns, k)
 
+    # -- the indel-tolerant search along a reference: E(j) = the edit distance of a query to the best substring of `ref` that ends at base j (1 <= j <= n,
+    # the substring starts anywhere); `end` is one past the last aligned base, as reads_edist_anchored's --
+    def _edist_count(self, fn, head, q, nq, taus):
+        _, t = self._multi_args(np.zeros(nq, dtype=np.uint64), taus)
+        out = np.empty(nq, dtype=np.uint64)
+        err = L.BitnucErr()
+        if fn(self._h, *head, _ptr(q), _ptr(t), nq, _ptr(out), C.byref(err)) != L.OK:
+            _raise(err)
+        return out
+
+    def kmer_edist_best(self, ref, k, queries):
+        """The best match per query by EDIT distance: (end, dist) with dist[q] = the smallest E_q(j) over the ends j of `ref` (np.uint8) and end[q] = the
+        smallest j that attains it (np.uint64); with k == 0 or len(ref) < k every end is 2^64 - 1 and every dist 255."""
+        s = _as_u8(ref)
+        return self._best(self._lib.bitnuc_kmer_edist_best, (_ptr(s), s.size, int(k)), queries)
+
+    def kmer_edist_best_packed(self, words, n_bases, k, queries):
+        """kmer_edist_best of the packed sequence `words` holding `n_bases` bases, without decoding it."""
+        w = _as_u64(words)
+        return self._best(self._lib.bitnuc_kmer_edist_best_packed, (_ptr(w), w.size, int(n_bases), int(k)), queries)
+
+    def kmer_edist_count_multi(self, ref, k, queries, taus):
+        """counts[q] = the number of ends j of `ref` with E_q(j) <= taus[q] (the end positions of approximate occurrences) -> np.uint64"""
+        s = _as_u8(ref)
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.uint64).reshape(-1))
+        return self._edist_count(self._lib.bitnuc_kmer_edist_count_multi, (_ptr(s), s.size, int(k)), q, q.size, taus)
+
+    def kmer_edist_count_multi_packed(self, words, n_bases, k, queries, taus):
+        """kmer_edist_count_multi of the packed sequence `words` holding `n_bases` bases, without decoding it."""
+        w = _as_u64(words)
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.uint64).reshape(-1))
+        return self._edist_count(self._lib.bitnuc_kmer_edist_count_multi_packed, (_ptr(w), w.size, int(n_bases), int(k)), q, q.size, taus)
+
+    def kmer_pattern_edist_best(self, ref, k, patterns):
+        """kmer_edist_best under pattern queries ((Q, 4) np.uint32, or IUPAC strings of length k): a base matches a position when it is in its set."""
+        s = _as_u8(ref)
+        return self._pattern_best(self._lib.bitnuc_kmer_pattern_edist_best, (_ptr(s), s.size, int(k)), patterns, k)
+
+    def kmer_pattern_edist_best_packed(self, words, n_bases, k, patterns):
+        """kmer_pattern_edist_best of the packed sequence `words` holding `n_bases` bases."""
+        w = _as_u64(words)
+        return self._pattern_best(self._lib.bitnuc_kmer_pattern_edist_best_packed, (_ptr(w), w.size, int(n_bases), int(k)), patterns, k)
+
+    def kmer_pattern_edist_count_multi(self, ref, k, patterns, taus):
+        """kmer_edist_count_multi under pattern queries."""
+        s = _as_u8(ref)
+        p = self._patterns(patterns, k)
+        return self._edist_count(self._lib.bitnuc_kmer_pattern_edist_count_multi, (_ptr(s), s.size, int(k)), p, p.shape[0], taus)
+
+    def kmer_pattern_edist_count_multi_packed(self, words, n_bases, k, patterns, taus):
+        """kmer_pattern_edist_count_multi of the packed sequence `words` holding `n_bases` bases."""
+        w = _as_u64(words)
+        p = self._patterns(patterns, k)
+        return self._edist_count(self._lib.bitnuc_kmer_pattern_edist_count_multi_packed, (_ptr(w), w.size, int(n_bases), int(k)), p, p.shape[0], taus)
+
     # -- pattern queries for the per-read matchers: the reads_hdist_* methods with `patterns` ((Q, 4) np.uint32, or IUPAC strings of length k) where
     # `queries` stood and pdist where the Hamming distance stood; everything else as their exact twins --
     @staticmethod
@@ -1263,6 +1318,48 @@ class Context:
         """The best match per pattern on packed words in device memory (8-byte aligned)."""
         self._call_dev(self._lib.bitnuc_kmer_pattern_best_packed_async, _dev_ptr(d_words), int(n_words), int(n), int(k), _dev_ptr(d_patterns), int(n_queries),
                        _dev_ptr(d_pos), _dev_ptr(d_dist))
+
+    # the indel-tolerant search along a reference: d_end[q] (u64) one past the last aligned base, d_dist[q] (u8); d_counts[q] (u64) = ends j with
+    # E_q(j) <= d_taus[q] (u32).  Asynchronous on the context's stream, as the _dev calls
+    def kmer_edist_best_async(self, d_ref, n, k, d_queries, n_queries, d_end, d_dist):
+        """The best match per query by edit distance: d_dist[q] = min over the ends j of E_q(j), d_end[q] = the smallest j that attains it."""
+        self._call_dev(self._lib.bitnuc_kmer_edist_best_async, _dev_ptr(d_ref), int(n), int(k), _dev_ptr(d_queries), int(n_queries), _dev_ptr(d_end),
+                       _dev_ptr(d_dist))
+
+    def kmer_edist_best_packed_async(self, d_words, n_words, n, k, d_queries, n_queries, d_end, d_dist):
+        """kmer_edist_best_async on packed words in device memory (8-byte aligned)."""
+        self._call_dev(self._lib.bitnuc_kmer_edist_best_packed_async, _dev_ptr(d_words), int(n_words), int(n), int(k), _dev_ptr(d_queries), int(n_queries),
+                       _dev_ptr(d_end), _dev_ptr(d_dist))
+
+    def kmer_edist_count_multi_async(self, d_ref, n, k, d_queries, d_taus, n_queries, d_counts):
+        """d_counts[q] = the ends j with E_q(j) <= d_taus[q]."""
+        self._call_dev(self._lib.bitnuc_kmer_edist_count_multi_async, _dev_ptr(d_ref), int(n), int(k), _dev_ptr(d_queries), _dev_ptr(d_taus), int(n_queries),
+                       _dev_ptr(d_counts))
+
+    def kmer_edist_count_multi_packed_async(self, d_words, n_words, n, k, d_queries, d_taus, n_queries, d_counts):
+        """kmer_edist_count_multi_async on packed words in device memory (8-byte aligned)."""
+        self._call_dev(self._lib.bitnuc_kmer_edist_count_multi_packed_async, _dev_ptr(d_words), int(n_words), int(n), int(k), _dev_ptr(d_queries),
+                       _dev_ptr(d_taus), int(n_queries), _dev_ptr(d_counts))
+
+    def kmer_pattern_edist_best_async(self, d_ref, n, k, d_patterns, n_queries, d_end, d_dist):
+        """kmer_edist_best_async under pattern queries."""
+        self._call_dev(self._lib.bitnuc_kmer_pattern_edist_best_async, _dev_ptr(d_ref), int(n), int(k), _dev_ptr(d_patterns), int(n_queries), _dev_ptr(d_end),
+                       _dev_ptr(d_dist))
+
+    def kmer_pattern_edist_best_packed_async(self, d_words, n_words, n, k, d_patterns, n_queries, d_end, d_dist):
+        """kmer_edist_best_packed_async under pattern queries."""
+        self._call_dev(self._lib.bitnuc_kmer_pattern_edist_best_packed_async, _dev_ptr(d_words), int(n_words), int(n), int(k), _dev_ptr(d_patterns),
+                       int(n_queries), _dev_ptr(d_end), _dev_ptr(d_dist))
+
+    def kmer_pattern_edist_count_multi_async(self, d_ref, n, k, d_patterns, d_taus, n_queries, d_counts):
+        """kmer_edist_count_multi_async under pattern queries."""
+        self._call_dev(self._lib.bitnuc_kmer_pattern_edist_count_multi_async, _dev_ptr(d_ref), int(n), int(k), _dev_ptr(d_patterns), _dev_ptr(d_taus),
+                       int(n_queries), _dev_ptr(d_counts))
+
+    def kmer_pattern_edist_count_multi_packed_async(self, d_words, n_words, n, k, d_patterns, d_taus, n_queries, d_counts):
+        """kmer_edist_count_multi_packed_async under pattern queries."""
+        self._call_dev(self._lib.bitnuc_kmer_pattern_edist_count_multi_packed_async, _dev_ptr(d_words), int(n_words), int(n), int(k), _dev_ptr(d_patterns),
+                       _dev_ptr(d_taus), int(n_queries), _dev_ptr(d_counts))
 
     def kmer_hdist_hist_async(self, d_ref, n, k, d_queries, n_queries, n_bins, d_hist):
         """The mismatch histogram of n_queries queries at once: d_hist[q * n_bins + d] (u64) = windows at distance exactly d < n_bins from d_queries[q]

@@ -3,8 +3,11 @@
 // Hamming scan (config 5: packing/mod.rs:80-110 o hamming/scalar.rs:11-48) and bulk hdist (hamming/multi.rs:121-160).
 // Kernels: kmer_device.h; config 5 on the matrix cores: scan_mfma_device.h; the same scan and count on packed words: scan_packed_device.h; the hit
 // lists of both: scan_hits_device.h; the count for many queries at once: scan_multi_device.h; the best match per query: scan_best_device.h; the mismatch histogram per query: scan_hist_device.h; the best match per read of a
-// fixed-length batch: scan_reads_device.h; ... of a ragged batch: scan_reads_batch_device.h.  The host side of every per-read matcher: reads_dispatch.h.
+// fixed-length batch: scan_reads_device.h; ... of a ragged batch: scan_reads_batch_device.h; the indel-tolerant search along a reference: scan_edist_ref_device.h.  The host side of every per-read matcher: reads_dispatch.h.
 #include "runtime.h"
+
+#include <type_traits>
+
 #include "kmer_device.h"
 #include "scan_mfma_device.h"
 #include "scan_packed_device.h"
@@ -15,6 +18,7 @@
 #include "scan_reads_batch_device.h"
 #include "scan_anchored_device.h"
 #include "scan_edist_device.h"
+#include "scan_edist_ref_device.h"
 #include "scan_hist_device.h"
 #include "scan_mfma_host.h"
 #include "scan_hits_host.h"
@@ -25,6 +29,7 @@
 #include "reads_anchored_host.h"
 #include "reads_anchored_batch_host.h"
 #include "reads_edist_host.h"
+#include "kmer_edist_host.h"
 #include "reads_batch_host.h"
 #include "scan_hist_host.h"
 #include "pattern_host.h"
@@ -801,6 +806,160 @@ int hist_packed_host(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_
         const PackedChunk ch = packed_chunk(i0 / 32, n, k);
         HIPCHK(hipMemcpyAsync(c->scratch[0], words + ch.w0, ch.words * 8, hipMemcpyHostToDevice, c->stream));
         return launch_hist_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), ch.bases, k, a, err);
+    });
+}
+
+// ---- the indel-tolerant search along a reference (scan_edist_ref_device.h): the best match and the count per query by EDIT distance, the four forms of
+// each once for exact queries and patterns.  Context scratch 9 (the Hamming best match's, shared in stream order) holds one 8-byte key per query and
+// behind them one 16-byte table per query (edist_tables_kernel: one form for both kinds); a launch recorded into a hipGraph keeps it (ensure_scratch:
+// warm up with the same n_queries before capturing).  `lead`: the columns at the start of the buffer that are run but not reported (the host chunk
+// loops' overlap, at most kEdistRefLead and, packed, whole words); the best match's ends come back counted from column `lead`.
+template <bool PACKED, bool COUNT, class HQ>
+int launch_kmer_edist(bitnuc_ctx *c, const void *data, size_t n, size_t lead, size_t k, const HQ *d_queries, const uint32_t *d_taus, size_t nq,
+                      unsigned long long *out, uint8_t *dist, unsigned long long *slot, bitnuc_err *err) {
+    if (lead >= n || lead > kEdistRefLead || (PACKED && lead % 32)) return fail(err, BITNUC_UNSUPPORTED, lead);
+    const size_t kbytes = (nq * 8 + 255) & ~(size_t)255;
+    if (int st = ensure_scratch(c, 9, kbytes + nq * kEdistEntry, err)) return st;
+    unsigned long long *keys = reinterpret_cast<unsigned long long *>(c->scratch[9]);
+    u32x4 *tabs = reinterpret_cast<u32x4 *>(c->scratch[9] + kbytes);
+    if constexpr (COUNT) HIPCHK(hipMemsetAsync(out, 0, nq * sizeof(uint64_t), c->stream));
+    else HIPCHK(hipMemsetAsync(keys, 0xFF, nq * sizeof(uint64_t), c->stream));
+    edist_tables_kernel<<<(unsigned)((nq + 63) / 64), 64, 0, c->stream>>>(dev_queries(d_queries), (unsigned)nq, (unsigned)k, tabs);
+    HIPCHK(hipGetLastError());
+    const unsigned long long lanes = (n - lead + kEdistRefChunk - 1) / kEdistRefChunk, want = (lanes + kEdistRefBlock - 1) / kEdistRefBlock,
+                             cap = (unsigned long long)c->num_cu * kEdistRefBlocksPerCu;
+    kmer_edist_kernel<PACKED, COUNT><<<(unsigned)(want < cap ? want : cap), kEdistRefBlock, 0, c->stream>>>(
+        reinterpret_cast<const uint8_t *>(data), (unsigned long long)n, (unsigned)lead, (unsigned)k, (unsigned)nq, tabs, d_taus, COUNT ? out : keys, slot);
+    HIPCHK(hipGetLastError());
+    if constexpr (!COUNT) {
+        edist_ref_finish_kernel<<<(unsigned)((nq + 255) / 256), 256, 0, c->stream>>>(keys, (unsigned)nq, (unsigned long long)lead, out, dist);
+        HIPCHK(hipGetLastError());
+    }
+    return BITNUC_OK;
+}
+
+// the two outputs as one policy each: the checks after ctx, k and the packed word count, the no-windows fill, the host forms, the chunk loop
+template <class HQ> struct EdistBest {
+    const HQ *queries; size_t nq; uint64_t *end; uint8_t *dist;
+    static constexpr bool count = false;
+    int check(bool *none, bitnuc_err *err) const { return check_best(queries, nq, end, dist, none, err, hist_qmask<HQ>()); }
+    int fill_dev(bitnuc_ctx *c, bitnuc_err *err) const { return best_fill_dev(c, end, dist, nq, err); }
+    void fill_host() const { memset(end, 0xFF, nq * sizeof(uint64_t)); memset(dist, 0xFF, nq); }
+    template <bool PACKED> int launch(bitnuc_ctx *c, const void *data, size_t n, unsigned long long *slot, size_t k, bitnuc_err *err) const {
+        return launch_kmer_edist<PACKED, false>(c, data, n, 0, k, queries, nullptr, nq, reinterpret_cast<unsigned long long *>(end), dist, slot, err);
+    }
+    long long small(const uint8_t *ref, size_t n, size_t k) const { return bitnuc_host::kmer_edist_best_small(ref, n, k, host_queries(queries), nq, end, dist); }
+    void small(const uint64_t *words, size_t n, size_t k) const { bitnuc_host::kmer_edist_best_packed_small(words, n, k, host_queries(queries), nq, end, dist); }
+    // launch(i0, lead, slot base known to the caller): the chunk that reports columns [i0, ...) behind `lead` columns of overlap
+    template <class Chunk> int host_loop(bitnuc_ctx *c, size_t n, size_t per, bitnuc_err *err, Chunk chunk) const {
+        return best_host_loop(c, n, per, queries, nq, end, dist, err, [&](size_t i0, const BestArgsT<HQ> &a) {
+            return chunk(i0, [&](auto packed, const void *data, size_t bases, size_t lead, size_t k, unsigned long long *slot) {
+                return launch_kmer_edist<decltype(packed)::value, false>(c, data, bases, lead, k, a.queries, nullptr, a.nq, a.pos, a.dist, slot, err);
+            });
+        });
+    }
+};
+
+template <class HQ> struct EdistCount {
+    const HQ *queries; const uint32_t *taus; size_t nq; uint64_t *counts;
+    static constexpr bool count = true;
+    int check(bool *none, bitnuc_err *err) const { return check_multi(queries, taus, nq, counts, none, err, hist_qmask<HQ>()); }
+    int fill_dev(bitnuc_ctx *c, bitnuc_err *err) const { HIPCHK(hipMemsetAsync(counts, 0, nq * sizeof(uint64_t), c->stream)); return BITNUC_OK; }
+    void fill_host() const { memset(counts, 0, nq * sizeof(uint64_t)); }
+    template <bool PACKED> int launch(bitnuc_ctx *c, const void *data, size_t n, unsigned long long *slot, size_t k, bitnuc_err *err) const {
+        return launch_kmer_edist<PACKED, true>(c, data, n, 0, k, queries, taus, nq, reinterpret_cast<unsigned long long *>(counts), nullptr, slot, err);
+    }
+    long long small(const uint8_t *ref, size_t n, size_t k) const { return bitnuc_host::kmer_edist_count_multi_small(ref, n, k, host_queries(queries), taus, nq, counts); }
+    void small(const uint64_t *words, size_t n, size_t k) const { bitnuc_host::kmer_edist_count_multi_packed_small(words, n, k, host_queries(queries), taus, nq, counts); }
+    template <class Chunk> int host_loop(bitnuc_ctx *c, size_t n, size_t per, bitnuc_err *err, Chunk chunk) const {
+        return multi_host_loop(c, n, per, queries, taus, nq, counts, err, [&](size_t i0, const MultiArgsT<HQ> &a) {
+            return chunk(i0, [&](auto packed, const void *data, size_t bases, size_t lead, size_t k, unsigned long long *slot) {
+                return launch_kmer_edist<decltype(packed)::value, true>(c, data, bases, lead, k, a.queries, a.taus, a.nq, a.counts, nullptr, slot, err);
+            });
+        });
+    }
+};
+
+// For k == 0 or n < k the family's rule holds (no windows: the fill, nothing validated), although E(j) is defined for n < k.
+template <class Out>
+int kmer_edist_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const Out &o, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    bool none;
+    if (int st = o.check(&none, err)) return st;
+    if (none) return BITNUC_OK;
+    DeviceGuard g(c->device);
+    if (k == 0 || n < k) return o.fill_dev(c, err);
+    if (!d_ref) return fail(err, BITNUC_UNSUPPORTED);
+    unsigned long long *slot;
+    if (int st = take_slot(c, 0, &slot, err)) return st;
+    return o.template launch<false>(c, d_ref, n, slot, k, err);
+}
+
+template <class Out>
+int kmer_edist_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const Out &o, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
+    bool none;
+    if (int st = o.check(&none, err)) return st;
+    if (none) return BITNUC_OK;
+    DeviceGuard g(c->device);
+    if (k == 0 || n < k) return o.fill_dev(c, err);
+    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    return o.template launch<true>(c, d_words, n, nullptr, k, err);
+}
+
+template <class Out>
+int kmer_edist_host(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const Out &o, bitnuc_err *err) {
+    clear_err(err);
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    bool none;
+    if (int st = o.check(&none, err)) return st;
+    if (none) return BITNUC_OK;
+    if (k == 0 || n < k) { o.fill_host(); return BITNUC_OK; }
+    if (!ref) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, multi_work(n, o.nq))) { // judged on columns x queries
+        const long long bad = o.small(ref, n, k);
+        return bad >= 0 ? fail_invalid_base(err, ref[bad], (uint64_t)bad) : BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    // chunks of kHostChunk reported columns behind 2k bases of the chunk before (where the Hamming forms copy k - 1 halo bases)
+    if (int st = ensure_scratch(c, 0, kHostChunk + 64, err)) return st;
+    return o.host_loop(c, n, kHostChunk, err, [&](size_t i0, auto launch) {
+        const size_t m = n - i0 < kHostChunk ? n - i0 : kHostChunk, lead = i0 ? 2 * k : 0; // i0 is 0 or at least kHostChunk
+        HIPCHK(hipMemcpyAsync(c->scratch[0], ref + i0 - lead, lead + m, hipMemcpyHostToDevice, c->stream));
+        unsigned long long *slot;
+        if (int st = take_slot(c, i0 - lead, &slot, err)) return st;
+        return launch(std::false_type{}, c->scratch[0], lead + m, lead, k, slot);
+    });
+}
+
+template <class Out>
+int kmer_edist_packed_host(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const Out &o, bitnuc_err *err) {
+    clear_err(err);
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
+    bool none;
+    if (int st = o.check(&none, err)) return st;
+    if (none) return BITNUC_OK;
+    if (k == 0 || n < k) { o.fill_host(); return BITNUC_OK; }
+    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, multi_work(n, o.nq))) { o.small(words, n, k); return BITNUC_OK; }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    if (int st = ensure_scratch(c, 0, (kPackedChunkWords + 2) * 8, err)) return st;
+    // chunk i0 / 32 of whole words (packed_chunk with k = 1: its columns), behind the words that hold the 2k bases before it: the lead, rounded up to the word
+    return o.host_loop(c, n, 32 * kPackedChunkWords, err, [&](size_t i0, auto launch) {
+        const PackedChunk ch = packed_chunk(i0 / 32, n, 1);
+        const size_t lw = i0 ? (2 * k + 31) / 32 : 0;
+        HIPCHK(hipMemcpyAsync(c->scratch[0], words + ch.w0 - lw, (lw + ch.words) * 8, hipMemcpyHostToDevice, c->stream));
+        return launch(std::true_type{}, c->scratch[0], 32 * lw + ch.bases, 32 * lw, k, nullptr);
     });
 }
 
@@ -1906,6 +2065,72 @@ int bitnuc_kmer_pattern_hits_packed(bitnuc_ctx *c, const uint64_t *words, size_t
         HIPCHK(hipMemcpyAsync(c->scratch[0], words + ch.w0, ch.words * 8, hipMemcpyHostToDevice, c->stream));
         return launch_hits_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), ch.bases, k, a, err);
     });
+}
+
+
+// ---- the indel-tolerant search along a reference: best match and count per query by edit distance (kmer_edist_async ... kmer_edist_packed_host above),
+// each form once per query kind
+int bitnuc_kmer_edist_best_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const uint64_t *d_queries, size_t n_queries, uint64_t *d_end, uint8_t *d_dist,
+                                 bitnuc_err *err) {
+    return kmer_edist_async(c, d_ref, n, k, EdistBest<uint64_t>{d_queries, n_queries, d_end, d_dist}, err);
+}
+int bitnuc_kmer_edist_best_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const uint64_t *d_queries, size_t n_queries,
+                                        uint64_t *d_end, uint8_t *d_dist, bitnuc_err *err) {
+    return kmer_edist_packed_async(c, d_words, n_words, n, k, EdistBest<uint64_t>{d_queries, n_queries, d_end, d_dist}, err);
+}
+int bitnuc_kmer_edist_best(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const uint64_t *queries, size_t n_queries, uint64_t *end, uint8_t *dist, bitnuc_err *err) {
+    return kmer_edist_host(c, ref, n, k, EdistBest<uint64_t>{queries, n_queries, end, dist}, err);
+}
+int bitnuc_kmer_edist_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const uint64_t *queries, size_t n_queries, uint64_t *end,
+                                  uint8_t *dist, bitnuc_err *err) {
+    return kmer_edist_packed_host(c, words, n_words, n, k, EdistBest<uint64_t>{queries, n_queries, end, dist}, err);
+}
+int bitnuc_kmer_edist_count_multi_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const uint64_t *d_queries, const uint32_t *d_taus, size_t n_queries,
+                                        uint64_t *d_counts, bitnuc_err *err) {
+    return kmer_edist_async(c, d_ref, n, k, EdistCount<uint64_t>{d_queries, d_taus, n_queries, d_counts}, err);
+}
+int bitnuc_kmer_edist_count_multi_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const uint64_t *d_queries,
+                                               const uint32_t *d_taus, size_t n_queries, uint64_t *d_counts, bitnuc_err *err) {
+    return kmer_edist_packed_async(c, d_words, n_words, n, k, EdistCount<uint64_t>{d_queries, d_taus, n_queries, d_counts}, err);
+}
+int bitnuc_kmer_edist_count_multi(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const uint64_t *queries, const uint32_t *taus, size_t n_queries, uint64_t *counts,
+                                  bitnuc_err *err) {
+    return kmer_edist_host(c, ref, n, k, EdistCount<uint64_t>{queries, taus, n_queries, counts}, err);
+}
+int bitnuc_kmer_edist_count_multi_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const uint64_t *queries, const uint32_t *taus,
+                                         size_t n_queries, uint64_t *counts, bitnuc_err *err) {
+    return kmer_edist_packed_host(c, words, n_words, n, k, EdistCount<uint64_t>{queries, taus, n_queries, counts}, err);
+}
+int bitnuc_kmer_pattern_edist_best_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries, uint64_t *d_end, uint8_t *d_dist,
+                                         bitnuc_err *err) {
+    return kmer_edist_async(c, d_ref, n, k, EdistBest<bitnuc_pattern>{d_patterns, n_queries, d_end, d_dist}, err);
+}
+int bitnuc_kmer_pattern_edist_best_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries,
+                                                uint64_t *d_end, uint8_t *d_dist, bitnuc_err *err) {
+    return kmer_edist_packed_async(c, d_words, n_words, n, k, EdistBest<bitnuc_pattern>{d_patterns, n_queries, d_end, d_dist}, err);
+}
+int bitnuc_kmer_pattern_edist_best(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const bitnuc_pattern *patterns, size_t n_queries, uint64_t *end, uint8_t *dist, bitnuc_err *err) {
+    return kmer_edist_host(c, ref, n, k, EdistBest<bitnuc_pattern>{patterns, n_queries, end, dist}, err);
+}
+int bitnuc_kmer_pattern_edist_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *patterns, size_t n_queries, uint64_t *end,
+                                          uint8_t *dist, bitnuc_err *err) {
+    return kmer_edist_packed_host(c, words, n_words, n, k, EdistBest<bitnuc_pattern>{patterns, n_queries, end, dist}, err);
+}
+int bitnuc_kmer_pattern_edist_count_multi_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const bitnuc_pattern *d_patterns, const uint32_t *d_taus, size_t n_queries,
+                                                uint64_t *d_counts, bitnuc_err *err) {
+    return kmer_edist_async(c, d_ref, n, k, EdistCount<bitnuc_pattern>{d_patterns, d_taus, n_queries, d_counts}, err);
+}
+int bitnuc_kmer_pattern_edist_count_multi_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *d_patterns,
+                                                       const uint32_t *d_taus, size_t n_queries, uint64_t *d_counts, bitnuc_err *err) {
+    return kmer_edist_packed_async(c, d_words, n_words, n, k, EdistCount<bitnuc_pattern>{d_patterns, d_taus, n_queries, d_counts}, err);
+}
+int bitnuc_kmer_pattern_edist_count_multi(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const bitnuc_pattern *patterns, const uint32_t *taus, size_t n_queries, uint64_t *counts,
+                                          bitnuc_err *err) {
+    return kmer_edist_host(c, ref, n, k, EdistCount<bitnuc_pattern>{patterns, taus, n_queries, counts}, err);
+}
+int bitnuc_kmer_pattern_edist_count_multi_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *patterns, const uint32_t *taus,
+                                                 size_t n_queries, uint64_t *counts, bitnuc_err *err) {
+    return kmer_edist_packed_host(c, words, n_words, n, k, EdistCount<bitnuc_pattern>{patterns, taus, n_queries, counts}, err);
 }
 
 } // extern "C"

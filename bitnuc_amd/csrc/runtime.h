@@ -127,7 +127,8 @@ struct bitnuc_ctx {
     std::vector<bitnuc_err> deferred; // data errors found by implicit drains (host-pointer calls start from an empty ring), oldest first: one per bitnuc_ctx_sync
     // ---- scratch ----
     // [8]: the multi-query count's per-query tables (kmer.hip launch_count_multi); [9]: the best match's keys and per-query tables (kmer.hip best_setup), shared in
-    // stream order with the mismatch histogram's per-query tables (kmer.hip hist_setup: the same tables at the same offset);
+    // stream order with the mismatch histogram's per-query tables (kmer.hip hist_setup: the same tables at the same offset) and with the edit-distance search
+    // along a reference (kmer.hip launch_kmer_edist: its keys at the same place, 16-byte tables behind them);
     // [10]: the per-read best match's keys (one per read; two arrays with the runner-up) and per-query tables (kmer.hip reads_setup: the fixed-length and the ragged forms);
     // shared in stream order with the anchored per-read calls' per-query tables (kmer.hip launch_reads_anchored: 256 bytes per query, nothing per read);
     // [4]: a chunk's rebased offsets tables of the ragged forms' host loop (as the ragged codec's host calls use it)

@@ -682,6 +682,53 @@ class Context {
             return NucleotideError::from_c(e);
         return std::make_pair(std::move(pos), std::move(dist));
     }
+    // the indel-tolerant search along a reference (bitnuc_kmer_edist_*): E(j) = the edit distance of a query to the best substring of the reference
+    // that ends at base j.  _best: (end[q], dist[q]) = the smallest j with the smallest E_q(j) and that distance, end one past the last aligned base
+    // (k == 0 or n < k: UINT64_MAX / 0xFF); _count_multi: counts[q] = the ends j with E_q(j) <= taus[q] (taus.size() == queries.size())
+    using EndDist = std::pair<std::vector<uint64_t>, std::vector<uint8_t>>;
+    Result<EndDist> kmer_edist_best(Bytes ref, size_t k, const std::vector<uint64_t> &queries) const {
+        return edist_best_(queries.size(), [&](uint64_t *end, uint8_t *dist, bitnuc_err *e) {
+            return bitnuc_kmer_edist_best(ctx_, ref.ptr, ref.len, k, queries.data(), queries.size(), end, dist, e);
+        });
+    }
+    Result<EndDist> kmer_edist_best_packed(Words words, size_t n, size_t k, const std::vector<uint64_t> &queries) const {
+        return edist_best_(queries.size(), [&](uint64_t *end, uint8_t *dist, bitnuc_err *e) {
+            return bitnuc_kmer_edist_best_packed(ctx_, words.ptr, words.len, n, k, queries.data(), queries.size(), end, dist, e);
+        });
+    }
+    Result<EndDist> kmer_pattern_edist_best(Bytes ref, size_t k, const std::vector<bitnuc_pattern> &patterns) const {
+        return edist_best_(patterns.size(), [&](uint64_t *end, uint8_t *dist, bitnuc_err *e) {
+            return bitnuc_kmer_pattern_edist_best(ctx_, ref.ptr, ref.len, k, patterns.data(), patterns.size(), end, dist, e);
+        });
+    }
+    Result<EndDist> kmer_pattern_edist_best_packed(Words words, size_t n, size_t k, const std::vector<bitnuc_pattern> &patterns) const {
+        return edist_best_(patterns.size(), [&](uint64_t *end, uint8_t *dist, bitnuc_err *e) {
+            return bitnuc_kmer_pattern_edist_best_packed(ctx_, words.ptr, words.len, n, k, patterns.data(), patterns.size(), end, dist, e);
+        });
+    }
+    Result<std::vector<uint64_t>> kmer_edist_count_multi(Bytes ref, size_t k, const std::vector<uint64_t> &queries, const std::vector<uint32_t> &taus) const {
+        return edist_count_(queries.size(), taus.size(), [&](uint64_t *counts, bitnuc_err *e) {
+            return bitnuc_kmer_edist_count_multi(ctx_, ref.ptr, ref.len, k, queries.data(), taus.data(), queries.size(), counts, e);
+        });
+    }
+    Result<std::vector<uint64_t>> kmer_edist_count_multi_packed(Words words, size_t n, size_t k, const std::vector<uint64_t> &queries,
+                                                                const std::vector<uint32_t> &taus) const {
+        return edist_count_(queries.size(), taus.size(), [&](uint64_t *counts, bitnuc_err *e) {
+            return bitnuc_kmer_edist_count_multi_packed(ctx_, words.ptr, words.len, n, k, queries.data(), taus.data(), queries.size(), counts, e);
+        });
+    }
+    Result<std::vector<uint64_t>> kmer_pattern_edist_count_multi(Bytes ref, size_t k, const std::vector<bitnuc_pattern> &patterns,
+                                                                 const std::vector<uint32_t> &taus) const {
+        return edist_count_(patterns.size(), taus.size(), [&](uint64_t *counts, bitnuc_err *e) {
+            return bitnuc_kmer_pattern_edist_count_multi(ctx_, ref.ptr, ref.len, k, patterns.data(), taus.data(), patterns.size(), counts, e);
+        });
+    }
+    Result<std::vector<uint64_t>> kmer_pattern_edist_count_multi_packed(Words words, size_t n, size_t k, const std::vector<bitnuc_pattern> &patterns,
+                                                                        const std::vector<uint32_t> &taus) const {
+        return edist_count_(patterns.size(), taus.size(), [&](uint64_t *counts, bitnuc_err *e) {
+            return bitnuc_kmer_pattern_edist_count_multi_packed(ctx_, words.ptr, words.len, n, k, patterns.data(), taus.data(), patterns.size(), counts, e);
+        });
+    }
     // hist[q * n_bins + d] = the windows with pdist exactly d < n_bins under patterns[q]
     Result<std::vector<uint64_t>> kmer_pattern_hist(Bytes ref, size_t k, const std::vector<bitnuc_pattern> &patterns, size_t n_bins) const {
         std::vector<uint64_t> hist(patterns.size() * (n_bins < BITNUC_HIST_MAX_BINS ? n_bins : BITNUC_HIST_MAX_BINS));
@@ -760,6 +807,21 @@ class Context {
 
   private:
     bitnuc_ctx *ctx_ = nullptr;
+    // the output vectors of the kmer_*edist_* methods around one C call
+    template <class Call> static Result<EndDist> edist_best_(size_t nq, Call call) {
+        std::vector<uint64_t> end(nq);
+        std::vector<uint8_t> dist(nq);
+        bitnuc_err e;
+        if (call(end.data(), dist.data(), &e) != BITNUC_OK) return NucleotideError::from_c(e);
+        return std::make_pair(std::move(end), std::move(dist));
+    }
+    template <class Call> static Result<std::vector<uint64_t>> edist_count_(size_t nq, size_t ntaus, Call call) {
+        if (ntaus != nq) return NucleotideError::unsupported();
+        std::vector<uint64_t> counts(nq);
+        bitnuc_err e;
+        if (call(counts.data(), &e) != BITNUC_OK) return NucleotideError::from_c(e);
+        return counts;
+    }
 };
 
 // Free functions with the reference's names, on a per-thread default context (device 0).

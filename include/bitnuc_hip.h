@@ -58,7 +58,7 @@
  *     "_dev" entry points take device pointers, are enqueued
  *     on the context's stream and return immediately -- data-dependent errors
  *     (InvalidBase) are latched on the device and reported by bitnuc_ctx_sync(); the "_async" entry points
- *     (bitnuc_kmer_hdist_best[_packed]_async, bitnuc_kmer_pattern_*_async) have exactly the "_dev" contract under another suffix;
+ *     (bitnuc_kmer_hdist_best[_packed]_async, bitnuc_kmer_pattern_*_async, bitnuc_kmer_edist_*_async, bitnuc_reads_*_async) have exactly the "_dev" contract under another suffix;
  *   - a bitnuc_ctx owns one device + stream + scratch and must not be used from
  *     two threads at once; separate contexts are independent.
  */
@@ -845,6 +845,73 @@ int bitnuc_reads_pattern_edist_anchored_batch_packed(bitnuc_ctx *ctx, const uint
                                                      size_t k, int anchor, size_t pos_lo, size_t pos_hi, const bitnuc_pattern *patterns, size_t n_queries,
                                                      uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_end,
                                                      uint8_t *second_dist, bitnuc_err *err);
+/* The INDEL-TOLERANT search ALONG A REFERENCE: the best match and the count per query by EDIT distance, where bitnuc_kmer_hdist_best* and
+ * bitnuc_kmer_hdist_count_multi* use the Hamming distance.  A guide or primer that sits in the reference with one bulge (one inserted or deleted base)
+ * is at distance 1 here and at about 3k/4 there.
+ * Definition.  The reference is t_1 .. t_n, a query has 1 <= k <= 32 positions.  D[0][j] = 0, D[i][0] = i, D[i][j] = min(D[i-1][j-1] + [t_j does not
+ * match position i], D[i-1][j] + 1, D[i][j-1] + 1); E(j) = D[k][j] is the edit distance of the query to the best substring of the reference that ends at
+ * base j (the substring may start anywhere and may be empty, so E(j) <= k).  "Matches" is equality of the 2-bit codes for an exact query (query bits
+ * above 2k are ignored) and membership in position i's set for a bitnuc_pattern (the bitnuc_kmer_pattern_edist_* twins; an empty set matches no base and
+ * is legal).  This is bitnuc_reads_edist_anchored's distance with the whole reference as the span, and `end` follows its convention: one past the last
+ * aligned base, 1 <= end <= n.  The start of the alignment is not reported.
+ * _best:        dist[q] = the minimum over 1 <= j <= n of E_q(j), end[q] = the smallest j that attains it.  end[0 .. n_queries) and
+ *               dist[0 .. n_queries) are written and nothing after them; dist may have any byte offset.  dist[q] <= bitnuc_kmer_hdist_best's.
+ * _count_multi: counts[q] = #{ 1 <= j <= n : E_q(j) <= taus[q] }, the number of END POSITIONS of approximate occurrences (one occurrence usually ends
+ *               at several neighbouring j); any uint32_t tau is valid, tau >= k counts every j (n).  counts[0 .. n_queries) is written and nothing
+ *               after it.  counts[q] >= bitnuc_kmer_hdist_count_multi's at the same tau.
+ * The results are deterministic.  With k == 0 or n < k the family's rule holds although E(j) is defined for n < k: OK, every end UINT64_MAX and every
+ * dist 0xFF, every count 0, and nothing is validated.
+ * Checks, in this order (those of bitnuc_kmer_hdist_best* / _count_multi*): (1) ctx NULL -> UNSUPPORTED (_async forms; the host forms below the cutoff
+ * accept NULL); (2) k > 32 -> SEQUENCE_TOO_LONG(k); (3) packed: n_words < ceil(n/32) -> INVALID_LENGTH(n); (4) n_queries == 0 -> OK, nothing written;
+ * (5) n_queries > BITNUC_MAX_QUERIES -> UNSUPPORTED (err.value = n_queries); (6) _best: end or queries NULL or not 8-byte aligned, or dist NULL;
+ * _count_multi: counts, queries or taus NULL or not 8-, 8-, 4-byte aligned -> UNSUPPORTED (patterns: 4-byte aligned); (7) k == 0 or n < k -> OK with
+ * the values above; (8) a NULL reference, or packed words not 8-byte aligned -> UNSUPPORTED.
+ * ASCII: bytes in either letter case at any byte alignment; an invalid base -> INVALID_BASE with the first invalid byte of all n in sequence order (the
+ * _async forms latch it once per call for bitnuc_ctx_sync(); the outputs are then unspecified; the host forms leave them untouched below the cutoff).
+ * Packed words 8-byte aligned; bits above 2n of the last word do not matter.
+ * The _async forms have the _dev contract: device pointers (queries / patterns, taus and outputs included), enqueued on the context's stream, InvalidBase
+ * latched for bitnuc_ctx_sync().  They keep one 8-byte key and one 16-byte table per query in context scratch (where the Hamming best match keeps its
+ * own, under the same growth rule: a call that needs more than the context holds waits for the stream before it replaces the allocation) and can be
+ * captured into a hipGraph after a warm-up with the same (or a larger) n_queries; during a capture scratch cannot grow (BITNUC_UNSUPPORTED, err.value =
+ * the bytes needed).
+ * The host forms are synchronous.  When n x n_queries is below the host cutoff they run on the host and ctx may be NULL; above it they run through the
+ * context in chunks of 128 M end positions, each behind the 2k bases before it (packed: rounded up to whole words), which are run but not reported:
+ * every end position is reported by exactly one chunk.  Best merges by the smallest (dist, end), count sums per query. */
+int bitnuc_kmer_edist_best_async(bitnuc_ctx *ctx, const uint8_t *d_ref, size_t n, size_t k, const uint64_t *d_queries, size_t n_queries, uint64_t *d_end,
+                                 uint8_t *d_dist, bitnuc_err *err);
+int bitnuc_kmer_edist_best_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const uint64_t *d_queries,
+                                        size_t n_queries, uint64_t *d_end, uint8_t *d_dist, bitnuc_err *err);
+int bitnuc_kmer_edist_best(bitnuc_ctx *ctx, const uint8_t *ref, size_t n, size_t k, const uint64_t *queries, size_t n_queries, uint64_t *end, uint8_t *dist,
+                           bitnuc_err *err);
+int bitnuc_kmer_edist_best_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t n_words, size_t n, size_t k, const uint64_t *queries, size_t n_queries,
+                                  uint64_t *end, uint8_t *dist, bitnuc_err *err);
+int bitnuc_kmer_edist_count_multi_async(bitnuc_ctx *ctx, const uint8_t *d_ref, size_t n, size_t k, const uint64_t *d_queries, const uint32_t *d_taus,
+                                        size_t n_queries, uint64_t *d_counts, bitnuc_err *err);
+int bitnuc_kmer_edist_count_multi_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const uint64_t *d_queries,
+                                               const uint32_t *d_taus, size_t n_queries, uint64_t *d_counts, bitnuc_err *err);
+int bitnuc_kmer_edist_count_multi(bitnuc_ctx *ctx, const uint8_t *ref, size_t n, size_t k, const uint64_t *queries, const uint32_t *taus, size_t n_queries,
+                                  uint64_t *counts, bitnuc_err *err);
+int bitnuc_kmer_edist_count_multi_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t n_words, size_t n, size_t k, const uint64_t *queries,
+                                         const uint32_t *taus, size_t n_queries, uint64_t *counts, bitnuc_err *err);
+/* ... and under PATTERN queries: `const bitnuc_pattern *patterns` where `const uint64_t *queries` stood (4-byte aligned), everything else word for word.
+ * One main kernel serves both kinds (the 16-byte table IS the pattern's sets), so a pattern costs what an exact query costs. */
+int bitnuc_kmer_pattern_edist_best_async(bitnuc_ctx *ctx, const uint8_t *d_ref, size_t n, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries,
+                                         uint64_t *d_end, uint8_t *d_dist, bitnuc_err *err);
+int bitnuc_kmer_pattern_edist_best_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *d_patterns,
+                                                size_t n_queries, uint64_t *d_end, uint8_t *d_dist, bitnuc_err *err);
+int bitnuc_kmer_pattern_edist_best(bitnuc_ctx *ctx, const uint8_t *ref, size_t n, size_t k, const bitnuc_pattern *patterns, size_t n_queries, uint64_t *end,
+                                   uint8_t *dist, bitnuc_err *err);
+int bitnuc_kmer_pattern_edist_best_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *patterns,
+                                          size_t n_queries, uint64_t *end, uint8_t *dist, bitnuc_err *err);
+int bitnuc_kmer_pattern_edist_count_multi_async(bitnuc_ctx *ctx, const uint8_t *d_ref, size_t n, size_t k, const bitnuc_pattern *d_patterns,
+                                                const uint32_t *d_taus, size_t n_queries, uint64_t *d_counts, bitnuc_err *err);
+int bitnuc_kmer_pattern_edist_count_multi_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t n_words, size_t n, size_t k,
+                                                       const bitnuc_pattern *d_patterns, const uint32_t *d_taus, size_t n_queries, uint64_t *d_counts,
+                                                       bitnuc_err *err);
+int bitnuc_kmer_pattern_edist_count_multi(bitnuc_ctx *ctx, const uint8_t *ref, size_t n, size_t k, const bitnuc_pattern *patterns, const uint32_t *taus,
+                                          size_t n_queries, uint64_t *counts, bitnuc_err *err);
+int bitnuc_kmer_pattern_edist_count_multi_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *patterns,
+                                                 const uint32_t *taus, size_t n_queries, uint64_t *counts, bitnuc_err *err);
 
 /* ---- analysis on packed words (the callers just above the codec) ------ */
 /* BaseCount::base_counts / GCContent::gc_content of a packed sequence

@@ -224,6 +224,23 @@ extern "C" {
     pub fn bitnuc_kmer_pattern_hits_packed_async(ctx: *mut bitnuc_ctx, d_words: *const u64, n_words: usize, n: usize, k: usize, pattern: *const bitnuc_pattern, tau: c_uint, d_pos: *mut u64, d_hit_dist: *mut u8, cap: usize, d_n_hits: *mut u64, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_kmer_pattern_hits(ctx: *mut bitnuc_ctx, reference: *const u8, n: usize, k: usize, pattern: *const bitnuc_pattern, tau: c_uint, pos: *mut u64, hit_dist: *mut u8, cap: usize, n_hits: *mut u64, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_kmer_pattern_hits_packed(ctx: *mut bitnuc_ctx, words: *const u64, n_words: usize, n: usize, k: usize, pattern: *const bitnuc_pattern, tau: c_uint, pos: *mut u64, hit_dist: *mut u8, cap: usize, n_hits: *mut u64, err: *mut bitnuc_err) -> c_int;
+    // the indel-tolerant search along a reference: best match and count per query by edit distance
+    pub fn bitnuc_kmer_edist_best_async(ctx: *mut bitnuc_ctx, d_ref: *const u8, n: usize, k: usize, d_queries: *const u64, n_queries: usize, d_end: *mut u64, d_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_edist_best_packed_async(ctx: *mut bitnuc_ctx, d_words: *const u64, n_words: usize, n: usize, k: usize, d_queries: *const u64, n_queries: usize, d_end: *mut u64, d_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_edist_best(ctx: *mut bitnuc_ctx, reference: *const u8, n: usize, k: usize, queries: *const u64, n_queries: usize, end: *mut u64, dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_edist_best_packed(ctx: *mut bitnuc_ctx, words: *const u64, n_words: usize, n: usize, k: usize, queries: *const u64, n_queries: usize, end: *mut u64, dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_edist_count_multi_async(ctx: *mut bitnuc_ctx, d_ref: *const u8, n: usize, k: usize, d_queries: *const u64, d_taus: *const u32, n_queries: usize, d_counts: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_edist_count_multi_packed_async(ctx: *mut bitnuc_ctx, d_words: *const u64, n_words: usize, n: usize, k: usize, d_queries: *const u64, d_taus: *const u32, n_queries: usize, d_counts: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_edist_count_multi(ctx: *mut bitnuc_ctx, reference: *const u8, n: usize, k: usize, queries: *const u64, taus: *const u32, n_queries: usize, counts: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_edist_count_multi_packed(ctx: *mut bitnuc_ctx, words: *const u64, n_words: usize, n: usize, k: usize, queries: *const u64, taus: *const u32, n_queries: usize, counts: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_edist_best_async(ctx: *mut bitnuc_ctx, d_ref: *const u8, n: usize, k: usize, d_patterns: *const bitnuc_pattern, n_queries: usize, d_end: *mut u64, d_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_edist_best_packed_async(ctx: *mut bitnuc_ctx, d_words: *const u64, n_words: usize, n: usize, k: usize, d_patterns: *const bitnuc_pattern, n_queries: usize, d_end: *mut u64, d_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_edist_best(ctx: *mut bitnuc_ctx, reference: *const u8, n: usize, k: usize, patterns: *const bitnuc_pattern, n_queries: usize, end: *mut u64, dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_edist_best_packed(ctx: *mut bitnuc_ctx, words: *const u64, n_words: usize, n: usize, k: usize, patterns: *const bitnuc_pattern, n_queries: usize, end: *mut u64, dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_edist_count_multi_async(ctx: *mut bitnuc_ctx, d_ref: *const u8, n: usize, k: usize, d_patterns: *const bitnuc_pattern, d_taus: *const u32, n_queries: usize, d_counts: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_edist_count_multi_packed_async(ctx: *mut bitnuc_ctx, d_words: *const u64, n_words: usize, n: usize, k: usize, d_patterns: *const bitnuc_pattern, d_taus: *const u32, n_queries: usize, d_counts: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_edist_count_multi(ctx: *mut bitnuc_ctx, reference: *const u8, n: usize, k: usize, patterns: *const bitnuc_pattern, taus: *const u32, n_queries: usize, counts: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_edist_count_multi_packed(ctx: *mut bitnuc_ctx, words: *const u64, n_words: usize, n: usize, k: usize, patterns: *const bitnuc_pattern, taus: *const u32, n_queries: usize, counts: *mut u64, err: *mut bitnuc_err) -> c_int;
     // diagnostics
     pub fn bitnuc_selftime_small(op: c_int, n: usize, iters: usize) -> f64;
 }

@@ -797,6 +797,99 @@ pub fn kmer_pattern_best_packed(words: &[u64], n: usize, k: usize, patterns: &[P
     if st == ffi::BITNUC_OK { Ok((pos, dist)) } else { Err(to_err(&e)) }
 }
 
+// ---- the indel-tolerant search along a reference: E(j) = the edit distance of a query to the best substring of the reference that ends at base j
+// (1 <= j <= n; the substring starts anywhere); `end` is one past the last aligned base, as `reads_edist_anchored`'s.
+
+/// The best match per query by EDIT distance: `(end, dist)` with `dist[q]` = the smallest E(j) of `queries[q]` over the ends j of `reference` and
+/// `end[q]` = the smallest j that attains it (`k == 0` or `n < k`: `u64::MAX` / `0xFF`).
+pub fn kmer_edist_best(reference: &[u8], k: usize, queries: &[u64]) -> Result<(Vec<u64>, Vec<u8>), NucleotideError> {
+    let mut end = vec![0u64; queries.len()];
+    let mut dist = vec![0u8; queries.len()];
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_edist_best(c, reference.as_ptr(), reference.len(), k, queries.as_ptr(), queries.len(), end.as_mut_ptr(), dist.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok((end, dist)) } else { Err(to_err(&e)) }
+}
+
+/// `kmer_edist_best` of the packed sequence `words` holding `n` bases, without decoding it.
+pub fn kmer_edist_best_packed(words: &[u64], n: usize, k: usize, queries: &[u64]) -> Result<(Vec<u64>, Vec<u8>), NucleotideError> {
+    let mut end = vec![0u64; queries.len()];
+    let mut dist = vec![0u8; queries.len()];
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_edist_best_packed(c, words.as_ptr(), words.len(), n, k, queries.as_ptr(), queries.len(), end.as_mut_ptr(), dist.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok((end, dist)) } else { Err(to_err(&e)) }
+}
+
+/// `counts[q]` = the number of ends j of `reference` with E(j) <= `taus[q]` for `queries[q]`: the end positions of approximate occurrences.
+pub fn kmer_edist_count_multi(reference: &[u8], k: usize, queries: &[u64], taus: &[u32]) -> Result<Vec<u64>, NucleotideError> {
+    if taus.len() != queries.len() { return Err(NucleotideError::Unsupported); }
+    let mut counts = vec![0u64; queries.len()];
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_edist_count_multi(c, reference.as_ptr(), reference.len(), k, queries.as_ptr(), taus.as_ptr(), queries.len(), counts.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(counts) } else { Err(to_err(&e)) }
+}
+
+/// `kmer_edist_count_multi` of the packed sequence `words` holding `n` bases, without decoding it.
+pub fn kmer_edist_count_multi_packed(words: &[u64], n: usize, k: usize, queries: &[u64], taus: &[u32]) -> Result<Vec<u64>, NucleotideError> {
+    if taus.len() != queries.len() { return Err(NucleotideError::Unsupported); }
+    let mut counts = vec![0u64; queries.len()];
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_edist_count_multi_packed(c, words.as_ptr(), words.len(), n, k, queries.as_ptr(), taus.as_ptr(), queries.len(), counts.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(counts) } else { Err(to_err(&e)) }
+}
+
+/// The best match per query by EDIT distance: `(end, dist)` with `dist[q]` = the smallest E(j) of `patterns[q]` over the ends j of `reference` and
+/// `end[q]` = the smallest j that attains it (`k == 0` or `n < k`: `u64::MAX` / `0xFF`).
+pub fn kmer_pattern_edist_best(reference: &[u8], k: usize, patterns: &[Pattern]) -> Result<(Vec<u64>, Vec<u8>), NucleotideError> {
+    let mut end = vec![0u64; patterns.len()];
+    let mut dist = vec![0u8; patterns.len()];
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_pattern_edist_best(c, reference.as_ptr(), reference.len(), k, patterns.as_ptr(), patterns.len(), end.as_mut_ptr(), dist.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok((end, dist)) } else { Err(to_err(&e)) }
+}
+
+/// `kmer_pattern_edist_best` of the packed sequence `words` holding `n` bases, without decoding it.
+pub fn kmer_pattern_edist_best_packed(words: &[u64], n: usize, k: usize, patterns: &[Pattern]) -> Result<(Vec<u64>, Vec<u8>), NucleotideError> {
+    let mut end = vec![0u64; patterns.len()];
+    let mut dist = vec![0u8; patterns.len()];
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_pattern_edist_best_packed(c, words.as_ptr(), words.len(), n, k, patterns.as_ptr(), patterns.len(), end.as_mut_ptr(), dist.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok((end, dist)) } else { Err(to_err(&e)) }
+}
+
+/// `counts[q]` = the number of ends j of `reference` with E(j) <= `taus[q]` for `patterns[q]`: the end positions of approximate occurrences.
+pub fn kmer_pattern_edist_count_multi(reference: &[u8], k: usize, patterns: &[Pattern], taus: &[u32]) -> Result<Vec<u64>, NucleotideError> {
+    if taus.len() != patterns.len() { return Err(NucleotideError::Unsupported); }
+    let mut counts = vec![0u64; patterns.len()];
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_pattern_edist_count_multi(c, reference.as_ptr(), reference.len(), k, patterns.as_ptr(), taus.as_ptr(), patterns.len(), counts.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(counts) } else { Err(to_err(&e)) }
+}
+
+/// `kmer_pattern_edist_count_multi` of the packed sequence `words` holding `n` bases, without decoding it.
+pub fn kmer_pattern_edist_count_multi_packed(words: &[u64], n: usize, k: usize, patterns: &[Pattern], taus: &[u32]) -> Result<Vec<u64>, NucleotideError> {
+    if taus.len() != patterns.len() { return Err(NucleotideError::Unsupported); }
+    let mut counts = vec![0u64; patterns.len()];
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_pattern_edist_count_multi_packed(c, words.as_ptr(), words.len(), n, k, patterns.as_ptr(), taus.as_ptr(), patterns.len(), counts.as_mut_ptr(), &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok(counts) } else { Err(to_err(&e)) }
+}
+
 /// The mismatch histogram per pattern in one pass: `hist[q * n_bins + d]` = the number of windows with pdist exactly `d` under `patterns[q]`,
 /// `d < n_bins <= 16`.
 pub fn kmer_pattern_hist(reference: &[u8], k: usize, patterns: &[Pattern], n_bins: usize) -> Result<Vec<u64>, NucleotideError> {
