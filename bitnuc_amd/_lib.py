@@ -149,6 +149,14 @@ SIGNATURES = {
     "bitnuc_kmer_pattern_edist_count_multi_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _P, _SZ, _P, _ERR]),
     "bitnuc_kmer_pattern_edist_count_multi": (C.c_int, [_P, _P, _SZ, _SZ, _P, _P, _SZ, _P, _ERR]),
     "bitnuc_kmer_pattern_edist_count_multi_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _P, _SZ, _P, _ERR]),
+    "bitnuc_kmer_edist_hits_async": (C.c_int, [_P, _P, _SZ, _SZ, _U64, C.c_uint, _P, _P, _SZ, _P, _ERR]),
+    "bitnuc_kmer_edist_hits_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _U64, C.c_uint, _P, _P, _SZ, _P, _ERR]),
+    "bitnuc_kmer_edist_hits": (C.c_int, [_P, _P, _SZ, _SZ, _U64, C.c_uint, _P, _P, _SZ, C.POINTER(_U64), _ERR]),
+    "bitnuc_kmer_edist_hits_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _U64, C.c_uint, _P, _P, _SZ, C.POINTER(_U64), _ERR]),
+    "bitnuc_kmer_pattern_edist_hits_async": (C.c_int, [_P, _P, _SZ, _SZ, _P, C.c_uint, _P, _P, _SZ, _P, _ERR]),
+    "bitnuc_kmer_pattern_edist_hits_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, C.c_uint, _P, _P, _SZ, _P, _ERR]),
+    "bitnuc_kmer_pattern_edist_hits": (C.c_int, [_P, _P, _SZ, _SZ, _P, C.c_uint, _P, _P, _SZ, C.POINTER(_U64), _ERR]),
+    "bitnuc_kmer_pattern_edist_hits_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, C.c_uint, _P, _P, _SZ, C.POINTER(_U64), _ERR]),
     "bitnuc_kmer_hdist_hist_async": (C.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _P, _ERR]),
     "bitnuc_kmer_hdist_hist_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _SZ, _P, _ERR]),
     "bitnuc_kmer_hdist_hist": (C.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _P, _ERR]),

@@ -665,6 +665,29 @@ class Context:
         p = self._patterns(patterns, k)
         return self._edist_count(self._lib.bitnuc_kmer_pattern_edist_count_multi_packed, (_ptr(w), w.size, int(n_bases), int(k)), p, p.shape[0], taus)
 
+    def kmer_edist_hits(self, ref, k, query, tau, with_dist=False):
+        """Ends (np.uint64, ascending, 1 <= end <= n: one past the last aligned base) of the substrings of `ref` within edit distance tau of the query: the
+        j with E(j) <= tau; with_dist: (ends, np.uint8 distances).  Neighbouring ends of a good match are hits too: the list is not collapsed to minima."""
+        s = _as_u8(ref)
+        return self._hits(self._lib.bitnuc_kmer_edist_hits, (_ptr(s), s.size, int(k), C.c_uint64(query), int(tau)), with_dist)
+
+    def kmer_edist_hits_packed(self, words, n_bases, k, query, tau, with_dist=False):
+        """kmer_edist_hits of the packed sequence `words` holding `n_bases` bases, without decoding it."""
+        w = _as_u64(words)
+        return self._hits(self._lib.bitnuc_kmer_edist_hits_packed, (_ptr(w), w.size, int(n_bases), int(k), C.c_uint64(query), int(tau)), with_dist)
+
+    def kmer_pattern_edist_hits(self, ref, k, pattern, tau, with_dist=False):
+        """kmer_edist_hits under a pattern query (a (4,) np.uint32 array or an IUPAC string of length k)."""
+        s = _as_u8(ref)
+        p = self._patterns(pattern, k)[:1]
+        return self._hits(self._lib.bitnuc_kmer_pattern_edist_hits, (_ptr(s), s.size, int(k), _ptr(p), int(tau)), with_dist)
+
+    def kmer_pattern_edist_hits_packed(self, words, n_bases, k, pattern, tau, with_dist=False):
+        """kmer_pattern_edist_hits of the packed sequence `words` holding `n_bases` bases."""
+        w = _as_u64(words)
+        p = self._patterns(pattern, k)[:1]
+        return self._hits(self._lib.bitnuc_kmer_pattern_edist_hits_packed, (_ptr(w), w.size, int(n_bases), int(k), _ptr(p), int(tau)), with_dist)
+
     # -- pattern queries for the per-read matchers: the reads_hdist_* methods with `patterns` ((Q, 4) np.uint32, or IUPAC strings of length k) where
     # `queries` stood and pdist where the Hamming distance stood; everything else as their exact twins --
     @staticmethod
@@ -1360,6 +1383,29 @@ class Context:
         """kmer_edist_count_multi_packed_async under pattern queries."""
         self._call_dev(self._lib.bitnuc_kmer_pattern_edist_count_multi_packed_async, _dev_ptr(d_words), int(n_words), int(n), int(k), _dev_ptr(d_patterns),
                        _dev_ptr(d_taus), int(n_queries), _dev_ptr(d_counts))
+
+    def kmer_edist_hits_async(self, d_ref, n, k, query, tau, d_end, d_hit_dist, cap, d_n_hits):
+        """The ends j with E(j) <= tau -> d_end[0 .. min(cap, total)) (u64, ascending), their distances at d_hit_dist (None: not written), total ->
+        *d_n_hits (u64).  query: a host value.  Asynchronous on the context's stream, as the _dev calls."""
+        self._call_dev(self._lib.bitnuc_kmer_edist_hits_async, _dev_ptr(d_ref), int(n), int(k), C.c_uint64(query), int(tau), _dev_ptr(d_end),
+                       _dev_ptr(d_hit_dist), int(cap), _dev_ptr(d_n_hits))
+
+    def kmer_edist_hits_packed_async(self, d_words, n_words, n, k, query, tau, d_end, d_hit_dist, cap, d_n_hits):
+        """kmer_edist_hits_async on packed words in device memory (8-byte aligned)."""
+        self._call_dev(self._lib.bitnuc_kmer_edist_hits_packed_async, _dev_ptr(d_words), int(n_words), int(n), int(k), C.c_uint64(query), int(tau),
+                       _dev_ptr(d_end), _dev_ptr(d_hit_dist), int(cap), _dev_ptr(d_n_hits))
+
+    def kmer_pattern_edist_hits_async(self, d_ref, n, k, pattern, tau, d_end, d_hit_dist, cap, d_n_hits):
+        """kmer_edist_hits_async under a pattern query.  pattern: host memory ((4,) np.uint32) or None (the library refuses it)."""
+        p = None if pattern is None else np.ascontiguousarray(np.asarray(pattern, dtype=np.uint32).reshape(4))
+        self._call_dev(self._lib.bitnuc_kmer_pattern_edist_hits_async, _dev_ptr(d_ref), int(n), int(k), None if p is None else _ptr(p), int(tau),
+                       _dev_ptr(d_end), _dev_ptr(d_hit_dist), int(cap), _dev_ptr(d_n_hits))
+
+    def kmer_pattern_edist_hits_packed_async(self, d_words, n_words, n, k, pattern, tau, d_end, d_hit_dist, cap, d_n_hits):
+        """kmer_pattern_edist_hits_async on packed words in device memory (8-byte aligned)."""
+        p = None if pattern is None else np.ascontiguousarray(np.asarray(pattern, dtype=np.uint32).reshape(4))
+        self._call_dev(self._lib.bitnuc_kmer_pattern_edist_hits_packed_async, _dev_ptr(d_words), int(n_words), int(n), int(k), None if p is None else _ptr(p),
+                       int(tau), _dev_ptr(d_end), _dev_ptr(d_hit_dist), int(cap), _dev_ptr(d_n_hits))
 
     def kmer_hdist_hist_async(self, d_ref, n, k, d_queries, n_queries, n_bins, d_hist):
         """The mismatch histogram of n_queries queries at once: d_hist[q * n_bins + d] (u64) = windows at distance exactly d < n_bins from d_queries[q]

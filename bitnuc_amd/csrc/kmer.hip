@@ -3,7 +3,7 @@
 // Hamming scan (config 5: packing/mod.rs:80-110 o hamming/scalar.rs:11-48) and bulk hdist (hamming/multi.rs:121-160).
 // Kernels: kmer_device.h; config 5 on the matrix cores: scan_mfma_device.h; the same scan and count on packed words: scan_packed_device.h; the hit
 // lists of both: scan_hits_device.h; the count for many queries at once: scan_multi_device.h; the best match per query: scan_best_device.h; the mismatch histogram per query: scan_hist_device.h; the best match per read of a
-// fixed-length batch: scan_reads_device.h; ... of a ragged batch: scan_reads_batch_device.h; the indel-tolerant search along a reference: scan_edist_ref_device.h.  The host side of every per-read matcher: reads_dispatch.h.
+// fixed-length batch: scan_reads_device.h; ... of a ragged batch: scan_reads_batch_device.h; the indel-tolerant search along a reference: scan_edist_ref_device.h, its hit list: scan_edist_hits_device.h.  The host side of every per-read matcher: reads_dispatch.h.
 #include "runtime.h"
 
 #include <type_traits>
@@ -19,6 +19,7 @@
 #include "scan_anchored_device.h"
 #include "scan_edist_device.h"
 #include "scan_edist_ref_device.h"
+#include "scan_edist_hits_device.h"
 #include "scan_hist_device.h"
 #include "scan_mfma_host.h"
 #include "scan_hits_host.h"
@@ -960,6 +961,131 @@ int kmer_edist_packed_host(bitnuc_ctx *c, const uint64_t *words, size_t n_words,
         const size_t lw = i0 ? (2 * k + 31) / 32 : 0;
         HIPCHK(hipMemcpyAsync(c->scratch[0], words + ch.w0 - lw, (lw + ch.words) * 8, hipMemcpyHostToDevice, c->stream));
         return launch(std::true_type{}, c->scratch[0], 32 * lw + ch.bases, 32 * lw, k, nullptr);
+    });
+}
+
+// ---- the indel-tolerant hit list (scan_edist_hits_device.h): count pass per chunk of kEdistRefChunk ends, the Hamming hit list's scan over the chunks'
+// counts, emit pass.  Context scratch 7 (the Hamming hit list's, shared in stream order) holds the scanned counts, the tiles' offsets and, behind them,
+// the raw counts; a launch recorded into a hipGraph keeps it (ensure_scratch).  The query's table entry is built here and passed by value.  `lead` as
+// in launch_kmer_edist; a.pos_base is the end of the first reported column minus one.
+template <bool PACKED, class HQ>
+int launch_edist_hits(bitnuc_ctx *c, const void *data, size_t n, size_t lead, size_t k, const HitsArgsT<HQ> &a, unsigned long long *slot, bitnuc_err *err) {
+    if (lead >= n || lead > kEdistRefLead || (PACKED && lead % 32)) return fail(err, BITNUC_UNSUPPORTED, lead);
+    const unsigned long long nch = (n - lead + kEdistRefChunk - 1) / kEdistRefChunk, ntiles = (nch + kHitsTile - 1) / kHitsTile;
+    const unsigned long long cbytes = (4 * nch + 255) & ~255ull, tbytes = (8 * ntiles + 255) & ~255ull;
+    if (int st = ensure_scratch(c, 7, 2 * cbytes + tbytes, err)) return st;
+    unsigned *counts = reinterpret_cast<unsigned *>(c->scratch[7]);
+    unsigned long long *tiles = reinterpret_cast<unsigned long long *>(c->scratch[7] + cbytes);
+    unsigned *raw = reinterpret_cast<unsigned *>(c->scratch[7] + cbytes + tbytes);
+    const bitnuc_host::EdistPeq p = bitnuc_host::edist_peq(dev_query(a.query), k);
+    const u32x4 tab{p.m[0], p.m[1], p.m[2], p.m[3]};
+    const unsigned long long want = (nch + kEdistRefBlock - 1) / kEdistRefBlock, bound = (unsigned long long)c->num_cu * kEdistRefBlocksPerCu;
+    const unsigned grid = (unsigned)(want < bound ? want : bound);
+    const uint8_t *bytes = reinterpret_cast<const uint8_t *>(data);
+    kmer_edist_hits_kernel<PACKED, false><<<grid, kEdistRefBlock, 0, c->stream>>>(bytes, (unsigned long long)n, (unsigned)lead, (unsigned)k, tab, a.tau, counts, raw,
+                                                                                   nullptr, nullptr, nullptr, 0, 0, slot);
+    HIPCHK(hits_scan(c, counts, nch, tiles, a.n_hits));
+    if (a.cap)
+        kmer_edist_hits_kernel<PACKED, true><<<grid, kEdistRefBlock, 0, c->stream>>>(bytes, (unsigned long long)n, (unsigned)lead, (unsigned)k, tab, a.tau, counts, raw,
+                                                                                      tiles, a.pos, a.hd, a.cap, a.pos_base, slot);
+    HIPCHK(hipGetLastError());
+    return BITNUC_OK;
+}
+
+// the single query's check: what check_multi asks of a queries array of one (an exact query is a host value: q points at the caller's argument)
+template <class HQ> int check_edist_hits_query(const HQ *q, bitnuc_err *err) {
+    if (!q || (reinterpret_cast<uintptr_t>(q) & hist_qmask<HQ>())) return fail(err, BITNUC_UNSUPPORTED);
+    return BITNUC_OK;
+}
+
+// For k == 0 or n < k the family's rule holds (no windows: *n_hits = 0, nothing validated).
+template <class HQ>
+int kmer_edist_hits_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const HQ *q, unsigned tau, uint64_t *d_end, uint8_t *d_hit_dist, size_t cap,
+                          uint64_t *d_n_hits, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    if (int st = check_edist_hits_query(q, err)) return st;
+    if (int st = check_hits_out(d_end, cap, d_n_hits, err)) return st;
+    DeviceGuard g(c->device);
+    if (k == 0 || n < k) {
+        HIPCHK(hipMemsetAsync(d_n_hits, 0, sizeof(uint64_t), c->stream));
+        return BITNUC_OK;
+    }
+    if (!d_ref) return fail(err, BITNUC_UNSUPPORTED);
+    unsigned long long *slot;
+    if (int st = take_slot(c, 0, &slot, err)) return st;
+    const HitsArgsT<HQ> a{*q, tau, reinterpret_cast<unsigned long long *>(d_end), d_hit_dist, cap, reinterpret_cast<unsigned long long *>(d_n_hits), 0};
+    return launch_edist_hits<false>(c, d_ref, n, 0, k, a, slot, err);
+}
+
+template <class HQ>
+int kmer_edist_hits_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const HQ *q, unsigned tau, uint64_t *d_end,
+                                 uint8_t *d_hit_dist, size_t cap, uint64_t *d_n_hits, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
+    if (int st = check_edist_hits_query(q, err)) return st;
+    if (int st = check_hits_out(d_end, cap, d_n_hits, err)) return st;
+    DeviceGuard g(c->device);
+    if (k == 0 || n < k) {
+        HIPCHK(hipMemsetAsync(d_n_hits, 0, sizeof(uint64_t), c->stream));
+        return BITNUC_OK;
+    }
+    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    const HitsArgsT<HQ> a{*q, tau, reinterpret_cast<unsigned long long *>(d_end), d_hit_dist, cap, reinterpret_cast<unsigned long long *>(d_n_hits), 0};
+    return launch_edist_hits<true>(c, d_words, n, 0, k, a, nullptr, err);
+}
+
+template <class HQ>
+int kmer_edist_hits_host(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const HQ *q, unsigned tau, uint64_t *end, uint8_t *hit_dist, size_t cap,
+                         uint64_t *n_hits, bitnuc_err *err) {
+    clear_err(err);
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    if (int st = check_edist_hits_query(q, err)) return st;
+    if (int st = check_hits_out(end, cap, n_hits, err)) return st;
+    if (k == 0 || n < k) { *n_hits = 0; return BITNUC_OK; }
+    if (!ref) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, n)) { // one query: judged on the columns
+        const long long bad = bitnuc_host::kmer_edist_hits_small(ref, n, k, dev_query(*q), tau, end, hit_dist, cap, n_hits);
+        return bad >= 0 ? fail_invalid_base(err, ref[bad], (uint64_t)bad) : BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    // chunks of kHostChunk reported columns behind 2k bases of the chunk before, as kmer_edist_host copies them
+    if (int st = ensure_scratch(c, 0, kHostChunk + 64, err)) return st;
+    return hits_host_loop(c, n, kHostChunk, tau, *q, end, hit_dist, cap, n_hits, err, [&](size_t i0, size_t m, const HitsArgsT<HQ> &a) {
+        const size_t lead = i0 ? 2 * k : 0; // i0 is 0 or at least kHostChunk
+        HIPCHK(hipMemcpyAsync(c->scratch[0], ref + i0 - lead, lead + m, hipMemcpyHostToDevice, c->stream));
+        unsigned long long *slot;
+        if (int st = take_slot(c, i0 - lead, &slot, err)) return st;
+        return launch_edist_hits<false>(c, c->scratch[0], lead + m, lead, k, a, slot, err);
+    });
+}
+
+template <class HQ>
+int kmer_edist_hits_packed_host(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const HQ *q, unsigned tau, uint64_t *end,
+                                uint8_t *hit_dist, size_t cap, uint64_t *n_hits, bitnuc_err *err) {
+    clear_err(err);
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
+    if (int st = check_edist_hits_query(q, err)) return st;
+    if (int st = check_hits_out(end, cap, n_hits, err)) return st;
+    if (k == 0 || n < k) { *n_hits = 0; return BITNUC_OK; }
+    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, n)) { *n_hits = bitnuc_host::kmer_edist_hits_packed_small(words, n, k, dev_query(*q), tau, end, hit_dist, cap); return BITNUC_OK; }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    if (int st = ensure_scratch(c, 0, (kPackedChunkWords + 2) * 8, err)) return st;
+    // chunk i0 / 32 of whole words behind the words that hold the 2k bases before it, as kmer_edist_packed_host copies them
+    return hits_host_loop(c, n, 32 * kPackedChunkWords, tau, *q, end, hit_dist, cap, n_hits, err, [&](size_t i0, size_t, const HitsArgsT<HQ> &a) {
+        const PackedChunk ch = packed_chunk(i0 / 32, n, 1);
+        const size_t lw = i0 ? (2 * k + 31) / 32 : 0;
+        HIPCHK(hipMemcpyAsync(c->scratch[0], words + ch.w0 - lw, (lw + ch.words) * 8, hipMemcpyHostToDevice, c->stream));
+        return launch_edist_hits<true>(c, c->scratch[0], 32 * lw + ch.bases, 32 * lw, k, a, nullptr, err);
     });
 }
 
@@ -2131,6 +2257,40 @@ int bitnuc_kmer_pattern_edist_count_multi(bitnuc_ctx *c, const uint8_t *ref, siz
 int bitnuc_kmer_pattern_edist_count_multi_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *patterns, const uint32_t *taus,
                                                  size_t n_queries, uint64_t *counts, bitnuc_err *err) {
     return kmer_edist_packed_host(c, words, n_words, n, k, EdistCount<bitnuc_pattern>{patterns, taus, n_queries, counts}, err);
+}
+
+// ---- the indel-tolerant hit list: the ends within tau along a reference (kmer_edist_hits_async ... kmer_edist_hits_packed_host above)
+int bitnuc_kmer_edist_hits_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *d_end, uint8_t *d_hit_dist, size_t cap,
+                                 uint64_t *d_n_hits, bitnuc_err *err) {
+    return kmer_edist_hits_async(c, d_ref, n, k, &query, tau, d_end, d_hit_dist, cap, d_n_hits, err);
+}
+int bitnuc_kmer_edist_hits_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *d_end,
+                                        uint8_t *d_hit_dist, size_t cap, uint64_t *d_n_hits, bitnuc_err *err) {
+    return kmer_edist_hits_packed_async(c, d_words, n_words, n, k, &query, tau, d_end, d_hit_dist, cap, d_n_hits, err);
+}
+int bitnuc_kmer_edist_hits(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *end, uint8_t *hit_dist, size_t cap, uint64_t *n_hits,
+                           bitnuc_err *err) {
+    return kmer_edist_hits_host(c, ref, n, k, &query, tau, end, hit_dist, cap, n_hits, err);
+}
+int bitnuc_kmer_edist_hits_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *end, uint8_t *hit_dist,
+                                  size_t cap, uint64_t *n_hits, bitnuc_err *err) {
+    return kmer_edist_hits_packed_host(c, words, n_words, n, k, &query, tau, end, hit_dist, cap, n_hits, err);
+}
+int bitnuc_kmer_pattern_edist_hits_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const bitnuc_pattern *pattern, unsigned tau, uint64_t *d_end, uint8_t *d_hit_dist,
+                                         size_t cap, uint64_t *d_n_hits, bitnuc_err *err) {
+    return kmer_edist_hits_async(c, d_ref, n, k, pattern, tau, d_end, d_hit_dist, cap, d_n_hits, err);
+}
+int bitnuc_kmer_pattern_edist_hits_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *pattern, unsigned tau,
+                                                uint64_t *d_end, uint8_t *d_hit_dist, size_t cap, uint64_t *d_n_hits, bitnuc_err *err) {
+    return kmer_edist_hits_packed_async(c, d_words, n_words, n, k, pattern, tau, d_end, d_hit_dist, cap, d_n_hits, err);
+}
+int bitnuc_kmer_pattern_edist_hits(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const bitnuc_pattern *pattern, unsigned tau, uint64_t *end, uint8_t *hit_dist, size_t cap,
+                                   uint64_t *n_hits, bitnuc_err *err) {
+    return kmer_edist_hits_host(c, ref, n, k, pattern, tau, end, hit_dist, cap, n_hits, err);
+}
+int bitnuc_kmer_pattern_edist_hits_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *pattern, unsigned tau, uint64_t *end,
+                                          uint8_t *hit_dist, size_t cap, uint64_t *n_hits, bitnuc_err *err) {
+    return kmer_edist_hits_packed_host(c, words, n_words, n, k, pattern, tau, end, hit_dist, cap, n_hits, err);
 }
 
 } // extern "C"

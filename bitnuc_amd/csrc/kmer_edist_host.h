@@ -1,4 +1,4 @@
-// kmer_edist_host.h -- the indel-tolerant k-mer search along a reference below the host cutoff (bitnuc_kmer_edist_best / _count_multi, their _packed
+// kmer_edist_host.h -- the indel-tolerant k-mer search along a reference below the host cutoff (bitnuc_kmer_edist_best / _count_multi / _hits, their _packed
 // forms and their pattern twins): with E_q(j) the edit distance of query q to the best substring of the sequence that ends at base j (1 <= j <= n, the
 // substring starts anywhere), dist[q] = min_j E_q(j) and end[q] = the first j that attains it; counts[q] = #{ j : E_q(j) <= taus[q] }.  The recurrence
 // is reads_edist_host.h's (edist_peq, the same column step) with 64-bit ends and no 64-column limit; the tests' oracle is the plain DP, so the two are
@@ -93,6 +93,39 @@ static inline long long kmer_edist_count_multi_small(const uint8_t *ref, size_t 
     const long long bad = kmer_edist_first_invalid(ref, n);
     if (bad >= 0) return bad;
     kmer_edist_count_codes([&](size_t j) { return kmer_edist_ascii_code(ref[j]); }, n, k, queries, taus, nq, counts);
+    return -1;
+}
+
+// the hit list of one query: the ends j with D[k][j] <= tau in ascending order, the first `cap` of them kept (dist may be NULL); returns their number
+template <class Q, class CodeAt>
+static inline uint64_t kmer_edist_hits_codes(CodeAt code_at, size_t n, size_t k, const Q &query, unsigned tau, uint64_t *end, uint8_t *dist, size_t cap) {
+    uint64_t hits = 0;
+    kmer_edist_walk(code_at, n, k, edist_peq(query, k), [&](size_t j, uint32_t d) {
+        if (d > tau) return;
+        if (hits < cap) {
+            const uint64_t e = j;
+            memcpy(end + hits, &e, 8);
+            if (dist) dist[hits] = (uint8_t)d;
+        }
+        ++hits;
+    });
+    return hits;
+}
+
+// packed sequence of n bases (1 <= k <= min(n, 32)): the number of hits; nothing is written at or beyond cap
+template <class Q>
+static inline uint64_t kmer_edist_hits_packed_small(const uint64_t *words, size_t n, size_t k, const Q &query, unsigned tau, uint64_t *end, uint8_t *dist,
+                                                    size_t cap) {
+    return kmer_edist_hits_codes([&](size_t j) { return (unsigned)((words[j / 32] >> (2 * (j % 32))) & 3u); }, n, k, query, tau, end, dist, cap);
+}
+
+// ASCII sequence of n bytes (the same conditions): -1 with *n_hits set, or the index of the first invalid byte among all n (outputs untouched)
+template <class Q>
+static inline long long kmer_edist_hits_small(const uint8_t *ref, size_t n, size_t k, const Q &query, unsigned tau, uint64_t *end, uint8_t *dist, size_t cap,
+                                              uint64_t *n_hits) {
+    const long long bad = kmer_edist_first_invalid(ref, n);
+    if (bad >= 0) return bad;
+    *n_hits = kmer_edist_hits_codes([&](size_t j) { return kmer_edist_ascii_code(ref[j]); }, n, k, query, tau, end, dist, cap);
     return -1;
 }
 

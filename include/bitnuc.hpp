@@ -729,6 +729,28 @@ class Context {
             return bitnuc_kmer_pattern_edist_count_multi_packed(ctx_, words.ptr, words.len, n, k, patterns.data(), taus.data(), patterns.size(), counts, e);
         });
     }
+    // the ends j (ascending, one past the last aligned base) with E(j) <= tau, sized by a first call with cap 0; hit_dist, when given, gets E(end[r]).
+    // Neighbouring ends of a good match are hits too: the list is not collapsed to local minima
+    Result<std::vector<uint64_t>> kmer_edist_hits(Bytes ref, size_t k, uint64_t query, unsigned tau, std::vector<uint8_t> *hit_dist = nullptr) const {
+        return edist_hits_(hit_dist, [&](uint64_t *end, uint8_t *hd, size_t cap, uint64_t *total, bitnuc_err *e) {
+            return bitnuc_kmer_edist_hits(ctx_, ref.ptr, ref.len, k, query, tau, end, hd, cap, total, e);
+        });
+    }
+    Result<std::vector<uint64_t>> kmer_edist_hits_packed(Words words, size_t n, size_t k, uint64_t query, unsigned tau, std::vector<uint8_t> *hit_dist = nullptr) const {
+        return edist_hits_(hit_dist, [&](uint64_t *end, uint8_t *hd, size_t cap, uint64_t *total, bitnuc_err *e) {
+            return bitnuc_kmer_edist_hits_packed(ctx_, words.ptr, words.len, n, k, query, tau, end, hd, cap, total, e);
+        });
+    }
+    Result<std::vector<uint64_t>> kmer_pattern_edist_hits(Bytes ref, size_t k, const bitnuc_pattern &pattern, unsigned tau, std::vector<uint8_t> *hit_dist = nullptr) const {
+        return edist_hits_(hit_dist, [&](uint64_t *end, uint8_t *hd, size_t cap, uint64_t *total, bitnuc_err *e) {
+            return bitnuc_kmer_pattern_edist_hits(ctx_, ref.ptr, ref.len, k, &pattern, tau, end, hd, cap, total, e);
+        });
+    }
+    Result<std::vector<uint64_t>> kmer_pattern_edist_hits_packed(Words words, size_t n, size_t k, const bitnuc_pattern &pattern, unsigned tau, std::vector<uint8_t> *hit_dist = nullptr) const {
+        return edist_hits_(hit_dist, [&](uint64_t *end, uint8_t *hd, size_t cap, uint64_t *total, bitnuc_err *e) {
+            return bitnuc_kmer_pattern_edist_hits_packed(ctx_, words.ptr, words.len, n, k, &pattern, tau, end, hd, cap, total, e);
+        });
+    }
     // hist[q * n_bins + d] = the windows with pdist exactly d < n_bins under patterns[q]
     Result<std::vector<uint64_t>> kmer_pattern_hist(Bytes ref, size_t k, const std::vector<bitnuc_pattern> &patterns, size_t n_bins) const {
         std::vector<uint64_t> hist(patterns.size() * (n_bins < BITNUC_HIST_MAX_BINS ? n_bins : BITNUC_HIST_MAX_BINS));
@@ -821,6 +843,16 @@ class Context {
         bitnuc_err e;
         if (call(counts.data(), &e) != BITNUC_OK) return NucleotideError::from_c(e);
         return counts;
+    }
+    // a hit list around two C calls: the first with cap 0 sizes the vectors
+    template <class Call> static Result<std::vector<uint64_t>> edist_hits_(std::vector<uint8_t> *hit_dist, Call call) {
+        uint64_t total = 0;
+        bitnuc_err e;
+        if (call(nullptr, nullptr, 0, &total, &e) != BITNUC_OK) return NucleotideError::from_c(e);
+        std::vector<uint64_t> end((size_t)total);
+        if (hit_dist) hit_dist->assign((size_t)total, 0);
+        if (total && call(end.data(), hit_dist ? hit_dist->data() : nullptr, end.size(), &total, &e) != BITNUC_OK) return NucleotideError::from_c(e);
+        return end;
     }
 };
 

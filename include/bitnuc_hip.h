@@ -912,6 +912,38 @@ int bitnuc_kmer_pattern_edist_count_multi(bitnuc_ctx *ctx, const uint8_t *ref, s
                                           size_t n_queries, uint64_t *counts, bitnuc_err *err);
 int bitnuc_kmer_pattern_edist_count_multi_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *patterns,
                                                  const uint32_t *taus, size_t n_queries, uint64_t *counts, bitnuc_err *err);
+/* The indel-tolerant HIT LIST: WHERE the ends within tau are, for one query per call (a host value, as in bitnuc_kmer_hdist_hits*).  With E(j) as above:
+ *   *n_hits = #{ 1 <= j <= n : E(j) <= tau }, exactly what bitnuc_kmer_edist_count_multi* returns for the same single query and tau; it may exceed cap;
+ *   end[0 .. min(cap, *n_hits)) = those j in ascending order; hit_dist[r] = E(end[r]); hit_dist may be NULL and is then not written.
+ * Nothing is written at or beyond cap; cap == 0 with end == NULL is valid and gives the count only.  Any unsigned tau is valid; tau >= k makes every end a
+ * hit.  Neighbouring ends of a good match are hits too (E(j +- 1) <= E(j) + 1), so an exact copy shows as a run of up to 2 tau + 1 ends; the list is not
+ * collapsed to local minima.  With k == 0 or n < k: OK, *n_hits = 0, nothing validated.  The result is deterministic.
+ * Checks, in this order: (1) ctx NULL -> UNSUPPORTED (_async forms; the host forms below the cutoff accept NULL); (2) k > 32 -> SEQUENCE_TOO_LONG(k);
+ * (3) packed: n_words < ceil(n/32) -> INVALID_LENGTH(n); (4) patterns: pattern NULL or not 4-byte aligned -> UNSUPPORTED; (5) n_hits NULL or not 8-byte
+ * aligned, end not 8-byte aligned, or end NULL with cap > 0 -> UNSUPPORTED; (6) k == 0 or n < k -> OK, *n_hits = 0; (7) a NULL reference, or packed words
+ * not 8-byte aligned -> UNSUPPORTED.  ASCII: an invalid base -> INVALID_BASE with the first invalid byte of all n in sequence order (the _async forms latch
+ * it once per call for bitnuc_ctx_sync(); the outputs are then unspecified; the host forms leave them untouched below the cutoff).
+ * The _async forms have the _dev contract for the reference and the outputs (device pointers, the context's stream); `pattern` is read from HOST memory
+ * during the call.  Three launches (count per chunk of 1024 ends, scan, emit; the emit pass is skipped for cap == 0 and walks only chunks that hold a
+ * hit); the per-chunk counts live in context scratch, shared with the Hamming hit list in stream order; capturable into a hipGraph after a warm-up with
+ * the same (or a larger) n.  The host forms are synchronous; below the host cutoff (judged on n) they run on the host and ctx may be NULL, above it in
+ * chunks of 128 M ends behind their 2k lead bases: every end is reported by exactly one chunk. */
+int bitnuc_kmer_edist_hits_async(bitnuc_ctx *ctx, const uint8_t *d_ref, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *d_end, uint8_t *d_hit_dist,
+                                 size_t cap, uint64_t *d_n_hits, bitnuc_err *err);
+int bitnuc_kmer_edist_hits_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t n_words, size_t n, size_t k, uint64_t query, unsigned tau,
+                                        uint64_t *d_end, uint8_t *d_hit_dist, size_t cap, uint64_t *d_n_hits, bitnuc_err *err);
+int bitnuc_kmer_edist_hits(bitnuc_ctx *ctx, const uint8_t *ref, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *end, uint8_t *hit_dist, size_t cap,
+                           uint64_t *n_hits, bitnuc_err *err);
+int bitnuc_kmer_edist_hits_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t n_words, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *end,
+                                  uint8_t *hit_dist, size_t cap, uint64_t *n_hits, bitnuc_err *err);
+int bitnuc_kmer_pattern_edist_hits_async(bitnuc_ctx *ctx, const uint8_t *d_ref, size_t n, size_t k, const bitnuc_pattern *pattern, unsigned tau, uint64_t *d_end,
+                                         uint8_t *d_hit_dist, size_t cap, uint64_t *d_n_hits, bitnuc_err *err);
+int bitnuc_kmer_pattern_edist_hits_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *pattern,
+                                                unsigned tau, uint64_t *d_end, uint8_t *d_hit_dist, size_t cap, uint64_t *d_n_hits, bitnuc_err *err);
+int bitnuc_kmer_pattern_edist_hits(bitnuc_ctx *ctx, const uint8_t *ref, size_t n, size_t k, const bitnuc_pattern *pattern, unsigned tau, uint64_t *end,
+                                   uint8_t *hit_dist, size_t cap, uint64_t *n_hits, bitnuc_err *err);
+int bitnuc_kmer_pattern_edist_hits_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *pattern,
+                                          unsigned tau, uint64_t *end, uint8_t *hit_dist, size_t cap, uint64_t *n_hits, bitnuc_err *err);
 
 /* ---- analysis on packed words (the callers just above the codec) ------ */
 /* BaseCount::base_counts / GCContent::gc_content of a packed sequence

@@ -241,6 +241,15 @@ extern "C" {
     pub fn bitnuc_kmer_pattern_edist_count_multi_packed_async(ctx: *mut bitnuc_ctx, d_words: *const u64, n_words: usize, n: usize, k: usize, d_patterns: *const bitnuc_pattern, d_taus: *const u32, n_queries: usize, d_counts: *mut u64, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_kmer_pattern_edist_count_multi(ctx: *mut bitnuc_ctx, reference: *const u8, n: usize, k: usize, patterns: *const bitnuc_pattern, taus: *const u32, n_queries: usize, counts: *mut u64, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_kmer_pattern_edist_count_multi_packed(ctx: *mut bitnuc_ctx, words: *const u64, n_words: usize, n: usize, k: usize, patterns: *const bitnuc_pattern, taus: *const u32, n_queries: usize, counts: *mut u64, err: *mut bitnuc_err) -> c_int;
+    // the indel-tolerant hit list: the ends within tau, one query per call
+    pub fn bitnuc_kmer_edist_hits_async(ctx: *mut bitnuc_ctx, d_ref: *const u8, n: usize, k: usize, query: u64, tau: c_uint, d_end: *mut u64, d_hit_dist: *mut u8, cap: usize, d_n_hits: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_edist_hits_packed_async(ctx: *mut bitnuc_ctx, d_words: *const u64, n_words: usize, n: usize, k: usize, query: u64, tau: c_uint, d_end: *mut u64, d_hit_dist: *mut u8, cap: usize, d_n_hits: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_edist_hits(ctx: *mut bitnuc_ctx, reference: *const u8, n: usize, k: usize, query: u64, tau: c_uint, end: *mut u64, hit_dist: *mut u8, cap: usize, n_hits: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_edist_hits_packed(ctx: *mut bitnuc_ctx, words: *const u64, n_words: usize, n: usize, k: usize, query: u64, tau: c_uint, end: *mut u64, hit_dist: *mut u8, cap: usize, n_hits: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_edist_hits_async(ctx: *mut bitnuc_ctx, d_ref: *const u8, n: usize, k: usize, pattern: *const bitnuc_pattern, tau: c_uint, d_end: *mut u64, d_hit_dist: *mut u8, cap: usize, d_n_hits: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_edist_hits_packed_async(ctx: *mut bitnuc_ctx, d_words: *const u64, n_words: usize, n: usize, k: usize, pattern: *const bitnuc_pattern, tau: c_uint, d_end: *mut u64, d_hit_dist: *mut u8, cap: usize, d_n_hits: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_edist_hits(ctx: *mut bitnuc_ctx, reference: *const u8, n: usize, k: usize, pattern: *const bitnuc_pattern, tau: c_uint, end: *mut u64, hit_dist: *mut u8, cap: usize, n_hits: *mut u64, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_kmer_pattern_edist_hits_packed(ctx: *mut bitnuc_ctx, words: *const u64, n_words: usize, n: usize, k: usize, pattern: *const bitnuc_pattern, tau: c_uint, end: *mut u64, hit_dist: *mut u8, cap: usize, n_hits: *mut u64, err: *mut bitnuc_err) -> c_int;
     // diagnostics
     pub fn bitnuc_selftime_small(op: c_int, n: usize, iters: usize) -> f64;
 }

@@ -890,6 +890,71 @@ pub fn kmer_pattern_edist_count_multi_packed(words: &[u64], n: usize, k: usize, 
     if st == ffi::BITNUC_OK { Ok(counts) } else { Err(to_err(&e)) }
 }
 
+/// The ends j (ascending, one past the last aligned base) of `reference` with E(j) <= `tau` for `query`, and E at each: a first call with cap 0
+/// returns their number, a second fills the lists.  Neighbouring ends of a good match are hits too; the list is not collapsed to local minima.
+pub fn kmer_edist_hits(reference: &[u8], k: usize, query: u64, tau: u32) -> Result<(Vec<u64>, Vec<u8>), NucleotideError> {
+    let mut total = 0u64;
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_edist_hits(c, reference.as_ptr(), reference.len(), k, query, tau, std::ptr::null_mut(), std::ptr::null_mut(), 0, &mut total, &mut e)
+    });
+    if st != ffi::BITNUC_OK { return Err(to_err(&e)); }
+    let mut end = vec![0u64; total as usize];
+    let mut dist = vec![0u8; total as usize];
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_edist_hits(c, reference.as_ptr(), reference.len(), k, query, tau, end.as_mut_ptr(), dist.as_mut_ptr(), end.len(), &mut total, &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok((end, dist)) } else { Err(to_err(&e)) }
+}
+
+/// `kmer_edist_hits` of the packed sequence `words` holding `n` bases, without decoding it.
+pub fn kmer_edist_hits_packed(words: &[u64], n: usize, k: usize, query: u64, tau: u32) -> Result<(Vec<u64>, Vec<u8>), NucleotideError> {
+    let mut total = 0u64;
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_edist_hits_packed(c, words.as_ptr(), words.len(), n, k, query, tau, std::ptr::null_mut(), std::ptr::null_mut(), 0, &mut total, &mut e)
+    });
+    if st != ffi::BITNUC_OK { return Err(to_err(&e)); }
+    let mut end = vec![0u64; total as usize];
+    let mut dist = vec![0u8; total as usize];
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_edist_hits_packed(c, words.as_ptr(), words.len(), n, k, query, tau, end.as_mut_ptr(), dist.as_mut_ptr(), end.len(), &mut total, &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok((end, dist)) } else { Err(to_err(&e)) }
+}
+
+/// `kmer_edist_hits` under a pattern query.
+pub fn kmer_pattern_edist_hits(reference: &[u8], k: usize, pattern: &Pattern, tau: u32) -> Result<(Vec<u64>, Vec<u8>), NucleotideError> {
+    let mut total = 0u64;
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_pattern_edist_hits(c, reference.as_ptr(), reference.len(), k, pattern, tau, std::ptr::null_mut(), std::ptr::null_mut(), 0, &mut total, &mut e)
+    });
+    if st != ffi::BITNUC_OK { return Err(to_err(&e)); }
+    let mut end = vec![0u64; total as usize];
+    let mut dist = vec![0u8; total as usize];
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_pattern_edist_hits(c, reference.as_ptr(), reference.len(), k, pattern, tau, end.as_mut_ptr(), dist.as_mut_ptr(), end.len(), &mut total, &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok((end, dist)) } else { Err(to_err(&e)) }
+}
+
+/// `kmer_pattern_edist_hits` of the packed sequence `words` holding `n` bases, without decoding it.
+pub fn kmer_pattern_edist_hits_packed(words: &[u64], n: usize, k: usize, pattern: &Pattern, tau: u32) -> Result<(Vec<u64>, Vec<u8>), NucleotideError> {
+    let mut total = 0u64;
+    let mut e = ffi::bitnuc_err::default();
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_pattern_edist_hits_packed(c, words.as_ptr(), words.len(), n, k, pattern, tau, std::ptr::null_mut(), std::ptr::null_mut(), 0, &mut total, &mut e)
+    });
+    if st != ffi::BITNUC_OK { return Err(to_err(&e)); }
+    let mut end = vec![0u64; total as usize];
+    let mut dist = vec![0u8; total as usize];
+    let st = with_ctx(|c| unsafe {
+        ffi::bitnuc_kmer_pattern_edist_hits_packed(c, words.as_ptr(), words.len(), n, k, pattern, tau, end.as_mut_ptr(), dist.as_mut_ptr(), end.len(), &mut total, &mut e)
+    });
+    if st == ffi::BITNUC_OK { Ok((end, dist)) } else { Err(to_err(&e)) }
+}
+
 /// The mismatch histogram per pattern in one pass: `hist[q * n_bins + d]` = the number of windows with pdist exactly `d` under `patterns[q]`,
 /// `d < n_bins <= 16`.
 pub fn kmer_pattern_hist(reference: &[u8], k: usize, patterns: &[Pattern], n_bins: usize) -> Result<Vec<u64>, NucleotideError> {
