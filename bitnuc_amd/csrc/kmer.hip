@@ -3,7 +3,8 @@
 // Hamming scan (config 5: packing/mod.rs:80-110 o hamming/scalar.rs:11-48) and bulk hdist (hamming/multi.rs:121-160).
 // Kernels: kmer_device.h; config 5 on the matrix cores: scan_mfma_device.h; the same scan and count on packed words: scan_packed_device.h; the hit
 // lists of both: scan_hits_device.h; the count for many queries at once: scan_multi_device.h; the best match per query: scan_best_device.h; the mismatch histogram per query: scan_hist_device.h; the best match per read of a
-// fixed-length batch: scan_reads_device.h; ... of a ragged batch: scan_reads_batch_device.h; the indel-tolerant search along a reference: scan_edist_ref_device.h, its hit list: scan_edist_hits_device.h.  The host side of every per-read matcher: reads_dispatch.h.
+// fixed-length batch: scan_reads_device.h; ... of a ragged batch: scan_reads_batch_device.h; the indel-tolerant search along a reference: scan_edist_ref_device.h, its hit list: scan_edist_hits_device.h.  The launchers, their argument checks and the host forms' chunk loops are here; the host side of the searches
+// along a reference -- inputs, searches, the two skeletons -- is ref_dispatch.h, that of every per-read matcher reads_dispatch.h.
 #include "runtime.h"
 
 #include <type_traits>
@@ -159,6 +160,7 @@ template <> struct DevQuery<bitnuc_pattern> { using type = PatternSets; };
 template <class HQ> const typename DevQuery<HQ>::type *dev_queries(const HQ *q) { return reinterpret_cast<const typename DevQuery<HQ>::type *>(q); }
 inline unsigned long long dev_query(uint64_t q) { return q; }
 inline PatternSets dev_query(const bitnuc_pattern &p) { return *dev_queries(&p); }
+template <class HQ> constexpr uintptr_t query_mask() { return sizeof(HQ) == 8 ? 7 : 3; } // a queries array's alignment: 8 bytes exact, 4 bytes patterns
 
 // the four-channel table of the distance bytes (the scan, the hit lists): no threshold, the accumulators start at the 2^23 pack bias
 template <class DQ>
@@ -271,12 +273,16 @@ hipError_t launch_count_packed(bitnuc_ctx *c, const uint64_t *words, size_t n, s
     return hipGetLastError();
 }
 
-// the packed calls' argument checks, in the header's order: k, the word count, no windows (*no_windows), then pointers
-int check_packed(const void *words, size_t n_words, size_t n, size_t k, bool *no_windows, bitnuc_err *err) {
+// no windows: nothing of the reference is looked at, the outputs get the family's fill
+inline bool no_windows(size_t n, size_t k) { return k == 0 || n < k; }
+
+// the single-query packed scan's and count's argument checks, in the header's order: k, the word count, no windows (*none), then the words (the
+// searches of ref_dispatch.h look at the words after their own arguments: the two orders answer alike)
+int check_packed(const void *words, size_t n_words, size_t n, size_t k, bool *none, bitnuc_err *err) {
     if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
     if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
-    *no_windows = k == 0 || n < k;
-    if (*no_windows) return BITNUC_OK;
+    *none = no_windows(n, k);
+    if (*none) return BITNUC_OK;
     if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
     return BITNUC_OK;
 }
@@ -428,7 +434,7 @@ int launch_count_multi_packed(bitnuc_ctx *c, const uint64_t *words, size_t n, si
 
 // the multi-query calls' checks 4 - 6 (after ctx, k and the packed word count): n_queries == 0 -> OK (*none), too many queries, the three arrays
 // (qmask: 7 for exact queries, 3 for patterns)
-int check_multi(const void *queries, const void *taus, size_t nq, const void *counts, bool *none, bitnuc_err *err, uintptr_t qmask = 7) {
+int check_multi(const void *queries, const void *taus, size_t nq, const void *counts, bool *none, bitnuc_err *err, uintptr_t qmask) {
     *none = nq == 0;
     if (*none) return BITNUC_OK;
     if (nq > BITNUC_MAX_QUERIES) return fail(err, BITNUC_UNSUPPORTED, nq);
@@ -524,7 +530,7 @@ int launch_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t n, size_t k,
 
 // the best-match calls' checks 4 - 6 (after ctx, k and the packed word count): n_queries == 0 -> OK (*none), too many queries, the three arrays
 // (qmask: 7 for exact queries, 3 for patterns)
-int check_best(const void *queries, size_t nq, const void *pos, const void *dist, bool *none, bitnuc_err *err, uintptr_t qmask = 7) {
+int check_best(const void *queries, size_t nq, const void *pos, const void *dist, bool *none, bitnuc_err *err, uintptr_t qmask) {
     *none = nq == 0;
     if (*none) return BITNUC_OK;
     if (nq > BITNUC_MAX_QUERIES) return fail(err, BITNUC_UNSUPPORTED, nq);
@@ -628,7 +634,6 @@ int check_hist(const void *queries, size_t nq, size_t n_bins, const void *hist, 
     if (!hist || (reinterpret_cast<uintptr_t>(hist) & 7) || !queries || (reinterpret_cast<uintptr_t>(queries) & qmask)) return fail(err, BITNUC_UNSUPPORTED);
     return BITNUC_OK;
 }
-template <class HQ> constexpr uintptr_t hist_qmask() { return sizeof(HQ) == 8 ? 7 : 3; }
 // the queries as the host code takes them (scan_hist_host.h: window_dist's two kinds)
 inline const uint64_t *host_queries(const uint64_t *q) { return q; }
 inline const PatternSets *host_queries(const bitnuc_pattern *q) { return reinterpret_cast<const PatternSets *>(q); }
@@ -716,102 +721,8 @@ struct ScanJob {
     }
 };
 
-// ---- the mismatch histogram per query: the four forms, once for exact queries (uint64_t) and patterns (bitnuc_pattern) -----------------------------
-template <class HQ>
-int hist_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const HQ *d_queries, size_t n_queries, size_t n_bins, uint64_t *d_hist, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    bool none;
-    if (int st = check_hist(d_queries, n_queries, n_bins, d_hist, &none, err, hist_qmask<HQ>())) return st;
-    if (none) return BITNUC_OK;
-    DeviceGuard g(c->device);
-    if (k == 0 || n < k) { // no windows
-        HIPCHK(hipMemsetAsync(d_hist, 0, n_queries * n_bins * sizeof(uint64_t), c->stream));
-        return BITNUC_OK;
-    }
-    if (!d_ref) return fail(err, BITNUC_UNSUPPORTED);
-    unsigned long long *slot;
-    if (int st = take_slot(c, 0, &slot, err)) return st;
-    return launch_hist(c, d_ref, n, k, HistArgsT<HQ>{d_queries, n_queries, n_bins, reinterpret_cast<unsigned long long *>(d_hist)}, slot, err);
-}
-
-template <class HQ>
-int hist_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const HQ *d_queries, size_t n_queries, size_t n_bins,
-                      uint64_t *d_hist, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
-    bool none;
-    if (int st = check_hist(d_queries, n_queries, n_bins, d_hist, &none, err, hist_qmask<HQ>())) return st;
-    if (none) return BITNUC_OK;
-    DeviceGuard g(c->device);
-    if (k == 0 || n < k) {
-        HIPCHK(hipMemsetAsync(d_hist, 0, n_queries * n_bins * sizeof(uint64_t), c->stream));
-        return BITNUC_OK;
-    }
-    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    return launch_hist_packed(c, d_words, n, k, HistArgsT<HQ>{d_queries, n_queries, n_bins, reinterpret_cast<unsigned long long *>(d_hist)}, err);
-}
-
-template <class HQ>
-int hist_host(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const HQ *queries, size_t n_queries, size_t n_bins, uint64_t *hist, bitnuc_err *err) {
-    clear_err(err);
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    bool none;
-    if (int st = check_hist(queries, n_queries, n_bins, hist, &none, err, hist_qmask<HQ>())) return st;
-    if (none) return BITNUC_OK;
-    if (k == 0 || n < k) { memset(hist, 0, n_queries * n_bins * sizeof(uint64_t)); return BITNUC_OK; }
-    if (!ref) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, multi_work(n - k + 1, n_queries))) {
-        const long long bad = bitnuc_host::kmer_hdist_hist_small(ref, n, k, host_queries(queries), n_queries, n_bins, hist);
-        return bad >= 0 ? fail_invalid_base(err, ref[bad], (uint64_t)bad) : BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    // chunks of kHostChunk windows + their k - 1 halo bases
-    if (int st = ensure_scratch(c, 0, kHostChunk + 64, err)) return st;
-    const size_t nwin = n - k + 1;
-    return hist_host_loop(c, nwin, kHostChunk, queries, n_queries, n_bins, hist, err, [&](size_t i0, const HistArgsT<HQ> &a) {
-        const size_t m = nwin - i0 < kHostChunk ? nwin - i0 : kHostChunk;
-        HIPCHK(hipMemcpyAsync(c->scratch[0], ref + i0, m + k - 1, hipMemcpyHostToDevice, c->stream));
-        unsigned long long *slot;
-        if (int st = take_slot(c, i0, &slot, err)) return st;
-        return launch_hist(c, c->scratch[0], m + k - 1, k, a, slot, err);
-    });
-}
-
-template <class HQ>
-int hist_packed_host(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const HQ *queries, size_t n_queries, size_t n_bins, uint64_t *hist,
-                     bitnuc_err *err) {
-    clear_err(err);
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
-    bool none;
-    if (int st = check_hist(queries, n_queries, n_bins, hist, &none, err, hist_qmask<HQ>())) return st;
-    if (none) return BITNUC_OK;
-    if (k == 0 || n < k) { memset(hist, 0, n_queries * n_bins * sizeof(uint64_t)); return BITNUC_OK; }
-    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, multi_work(n - k + 1, n_queries))) {
-        bitnuc_host::kmer_hdist_hist_packed_small(words, n, k, host_queries(queries), n_queries, n_bins, hist);
-        return BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    if (int st = ensure_scratch(c, 0, (kPackedChunkWords + 1) * 8, err)) return st;
-    // chunk w0 / 32 of whole words (packed_chunk): its windows start at base i0 = 32 w0
-    return hist_host_loop(c, n - k + 1, 32 * kPackedChunkWords, queries, n_queries, n_bins, hist, err, [&](size_t i0, const HistArgsT<HQ> &a) {
-        const PackedChunk ch = packed_chunk(i0 / 32, n, k);
-        HIPCHK(hipMemcpyAsync(c->scratch[0], words + ch.w0, ch.words * 8, hipMemcpyHostToDevice, c->stream));
-        return launch_hist_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), ch.bases, k, a, err);
-    });
-}
-
-// ---- the indel-tolerant search along a reference (scan_edist_ref_device.h): the best match and the count per query by EDIT distance, the four forms of
-// each once for exact queries and patterns.  Context scratch 9 (the Hamming best match's, shared in stream order) holds one 8-byte key per query and
+// ---- the indel-tolerant search along a reference (scan_edist_ref_device.h): the best match and the count per query by EDIT distance, one
+// launcher for both query kinds.  Context scratch 9 (the Hamming best match's, shared in stream order) holds one 8-byte key per query and
 // behind them one 16-byte table per query (edist_tables_kernel: one form for both kinds); a launch recorded into a hipGraph keeps it (ensure_scratch:
 // warm up with the same n_queries before capturing).  `lead`: the columns at the start of the buffer that are run but not reported (the host chunk
 // loops' overlap, at most kEdistRefLead and, packed, whole words); the best match's ends come back counted from column `lead`.
@@ -837,131 +748,6 @@ int launch_kmer_edist(bitnuc_ctx *c, const void *data, size_t n, size_t lead, si
         HIPCHK(hipGetLastError());
     }
     return BITNUC_OK;
-}
-
-// the two outputs as one policy each: the checks after ctx, k and the packed word count, the no-windows fill, the host forms, the chunk loop
-template <class HQ> struct EdistBest {
-    const HQ *queries; size_t nq; uint64_t *end; uint8_t *dist;
-    static constexpr bool count = false;
-    int check(bool *none, bitnuc_err *err) const { return check_best(queries, nq, end, dist, none, err, hist_qmask<HQ>()); }
-    int fill_dev(bitnuc_ctx *c, bitnuc_err *err) const { return best_fill_dev(c, end, dist, nq, err); }
-    void fill_host() const { memset(end, 0xFF, nq * sizeof(uint64_t)); memset(dist, 0xFF, nq); }
-    template <bool PACKED> int launch(bitnuc_ctx *c, const void *data, size_t n, unsigned long long *slot, size_t k, bitnuc_err *err) const {
-        return launch_kmer_edist<PACKED, false>(c, data, n, 0, k, queries, nullptr, nq, reinterpret_cast<unsigned long long *>(end), dist, slot, err);
-    }
-    long long small(const uint8_t *ref, size_t n, size_t k) const { return bitnuc_host::kmer_edist_best_small(ref, n, k, host_queries(queries), nq, end, dist); }
-    void small(const uint64_t *words, size_t n, size_t k) const { bitnuc_host::kmer_edist_best_packed_small(words, n, k, host_queries(queries), nq, end, dist); }
-    // launch(i0, lead, slot base known to the caller): the chunk that reports columns [i0, ...) behind `lead` columns of overlap
-    template <class Chunk> int host_loop(bitnuc_ctx *c, size_t n, size_t per, bitnuc_err *err, Chunk chunk) const {
-        return best_host_loop(c, n, per, queries, nq, end, dist, err, [&](size_t i0, const BestArgsT<HQ> &a) {
-            return chunk(i0, [&](auto packed, const void *data, size_t bases, size_t lead, size_t k, unsigned long long *slot) {
-                return launch_kmer_edist<decltype(packed)::value, false>(c, data, bases, lead, k, a.queries, nullptr, a.nq, a.pos, a.dist, slot, err);
-            });
-        });
-    }
-};
-
-template <class HQ> struct EdistCount {
-    const HQ *queries; const uint32_t *taus; size_t nq; uint64_t *counts;
-    static constexpr bool count = true;
-    int check(bool *none, bitnuc_err *err) const { return check_multi(queries, taus, nq, counts, none, err, hist_qmask<HQ>()); }
-    int fill_dev(bitnuc_ctx *c, bitnuc_err *err) const { HIPCHK(hipMemsetAsync(counts, 0, nq * sizeof(uint64_t), c->stream)); return BITNUC_OK; }
-    void fill_host() const { memset(counts, 0, nq * sizeof(uint64_t)); }
-    template <bool PACKED> int launch(bitnuc_ctx *c, const void *data, size_t n, unsigned long long *slot, size_t k, bitnuc_err *err) const {
-        return launch_kmer_edist<PACKED, true>(c, data, n, 0, k, queries, taus, nq, reinterpret_cast<unsigned long long *>(counts), nullptr, slot, err);
-    }
-    long long small(const uint8_t *ref, size_t n, size_t k) const { return bitnuc_host::kmer_edist_count_multi_small(ref, n, k, host_queries(queries), taus, nq, counts); }
-    void small(const uint64_t *words, size_t n, size_t k) const { bitnuc_host::kmer_edist_count_multi_packed_small(words, n, k, host_queries(queries), taus, nq, counts); }
-    template <class Chunk> int host_loop(bitnuc_ctx *c, size_t n, size_t per, bitnuc_err *err, Chunk chunk) const {
-        return multi_host_loop(c, n, per, queries, taus, nq, counts, err, [&](size_t i0, const MultiArgsT<HQ> &a) {
-            return chunk(i0, [&](auto packed, const void *data, size_t bases, size_t lead, size_t k, unsigned long long *slot) {
-                return launch_kmer_edist<decltype(packed)::value, true>(c, data, bases, lead, k, a.queries, a.taus, a.nq, a.counts, nullptr, slot, err);
-            });
-        });
-    }
-};
-
-// For k == 0 or n < k the family's rule holds (no windows: the fill, nothing validated), although E(j) is defined for n < k.
-template <class Out>
-int kmer_edist_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const Out &o, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    bool none;
-    if (int st = o.check(&none, err)) return st;
-    if (none) return BITNUC_OK;
-    DeviceGuard g(c->device);
-    if (k == 0 || n < k) return o.fill_dev(c, err);
-    if (!d_ref) return fail(err, BITNUC_UNSUPPORTED);
-    unsigned long long *slot;
-    if (int st = take_slot(c, 0, &slot, err)) return st;
-    return o.template launch<false>(c, d_ref, n, slot, k, err);
-}
-
-template <class Out>
-int kmer_edist_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const Out &o, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
-    bool none;
-    if (int st = o.check(&none, err)) return st;
-    if (none) return BITNUC_OK;
-    DeviceGuard g(c->device);
-    if (k == 0 || n < k) return o.fill_dev(c, err);
-    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    return o.template launch<true>(c, d_words, n, nullptr, k, err);
-}
-
-template <class Out>
-int kmer_edist_host(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const Out &o, bitnuc_err *err) {
-    clear_err(err);
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    bool none;
-    if (int st = o.check(&none, err)) return st;
-    if (none) return BITNUC_OK;
-    if (k == 0 || n < k) { o.fill_host(); return BITNUC_OK; }
-    if (!ref) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, multi_work(n, o.nq))) { // judged on columns x queries
-        const long long bad = o.small(ref, n, k);
-        return bad >= 0 ? fail_invalid_base(err, ref[bad], (uint64_t)bad) : BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    // chunks of kHostChunk reported columns behind 2k bases of the chunk before (where the Hamming forms copy k - 1 halo bases)
-    if (int st = ensure_scratch(c, 0, kHostChunk + 64, err)) return st;
-    return o.host_loop(c, n, kHostChunk, err, [&](size_t i0, auto launch) {
-        const size_t m = n - i0 < kHostChunk ? n - i0 : kHostChunk, lead = i0 ? 2 * k : 0; // i0 is 0 or at least kHostChunk
-        HIPCHK(hipMemcpyAsync(c->scratch[0], ref + i0 - lead, lead + m, hipMemcpyHostToDevice, c->stream));
-        unsigned long long *slot;
-        if (int st = take_slot(c, i0 - lead, &slot, err)) return st;
-        return launch(std::false_type{}, c->scratch[0], lead + m, lead, k, slot);
-    });
-}
-
-template <class Out>
-int kmer_edist_packed_host(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const Out &o, bitnuc_err *err) {
-    clear_err(err);
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
-    bool none;
-    if (int st = o.check(&none, err)) return st;
-    if (none) return BITNUC_OK;
-    if (k == 0 || n < k) { o.fill_host(); return BITNUC_OK; }
-    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, multi_work(n, o.nq))) { o.small(words, n, k); return BITNUC_OK; }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    if (int st = ensure_scratch(c, 0, (kPackedChunkWords + 2) * 8, err)) return st;
-    // chunk i0 / 32 of whole words (packed_chunk with k = 1: its columns), behind the words that hold the 2k bases before it: the lead, rounded up to the word
-    return o.host_loop(c, n, 32 * kPackedChunkWords, err, [&](size_t i0, auto launch) {
-        const PackedChunk ch = packed_chunk(i0 / 32, n, 1);
-        const size_t lw = i0 ? (2 * k + 31) / 32 : 0;
-        HIPCHK(hipMemcpyAsync(c->scratch[0], words + ch.w0 - lw, (lw + ch.words) * 8, hipMemcpyHostToDevice, c->stream));
-        return launch(std::true_type{}, c->scratch[0], 32 * lw + ch.bases, 32 * lw, k, nullptr);
-    });
 }
 
 // ---- the indel-tolerant hit list (scan_edist_hits_device.h): count pass per chunk of kEdistRefChunk ends, the Hamming hit list's scan over the chunks'
@@ -992,104 +778,10 @@ int launch_edist_hits(bitnuc_ctx *c, const void *data, size_t n, size_t lead, si
     return BITNUC_OK;
 }
 
-// the single query's check: what check_multi asks of a queries array of one (an exact query is a host value: q points at the caller's argument)
-template <class HQ> int check_edist_hits_query(const HQ *q, bitnuc_err *err) {
-    if (!q || (reinterpret_cast<uintptr_t>(q) & hist_qmask<HQ>())) return fail(err, BITNUC_UNSUPPORTED);
-    return BITNUC_OK;
-}
-
-// For k == 0 or n < k the family's rule holds (no windows: *n_hits = 0, nothing validated).
-template <class HQ>
-int kmer_edist_hits_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const HQ *q, unsigned tau, uint64_t *d_end, uint8_t *d_hit_dist, size_t cap,
-                          uint64_t *d_n_hits, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    if (int st = check_edist_hits_query(q, err)) return st;
-    if (int st = check_hits_out(d_end, cap, d_n_hits, err)) return st;
-    DeviceGuard g(c->device);
-    if (k == 0 || n < k) {
-        HIPCHK(hipMemsetAsync(d_n_hits, 0, sizeof(uint64_t), c->stream));
-        return BITNUC_OK;
-    }
-    if (!d_ref) return fail(err, BITNUC_UNSUPPORTED);
-    unsigned long long *slot;
-    if (int st = take_slot(c, 0, &slot, err)) return st;
-    const HitsArgsT<HQ> a{*q, tau, reinterpret_cast<unsigned long long *>(d_end), d_hit_dist, cap, reinterpret_cast<unsigned long long *>(d_n_hits), 0};
-    return launch_edist_hits<false>(c, d_ref, n, 0, k, a, slot, err);
-}
-
-template <class HQ>
-int kmer_edist_hits_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const HQ *q, unsigned tau, uint64_t *d_end,
-                                 uint8_t *d_hit_dist, size_t cap, uint64_t *d_n_hits, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
-    if (int st = check_edist_hits_query(q, err)) return st;
-    if (int st = check_hits_out(d_end, cap, d_n_hits, err)) return st;
-    DeviceGuard g(c->device);
-    if (k == 0 || n < k) {
-        HIPCHK(hipMemsetAsync(d_n_hits, 0, sizeof(uint64_t), c->stream));
-        return BITNUC_OK;
-    }
-    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    const HitsArgsT<HQ> a{*q, tau, reinterpret_cast<unsigned long long *>(d_end), d_hit_dist, cap, reinterpret_cast<unsigned long long *>(d_n_hits), 0};
-    return launch_edist_hits<true>(c, d_words, n, 0, k, a, nullptr, err);
-}
-
-template <class HQ>
-int kmer_edist_hits_host(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const HQ *q, unsigned tau, uint64_t *end, uint8_t *hit_dist, size_t cap,
-                         uint64_t *n_hits, bitnuc_err *err) {
-    clear_err(err);
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    if (int st = check_edist_hits_query(q, err)) return st;
-    if (int st = check_hits_out(end, cap, n_hits, err)) return st;
-    if (k == 0 || n < k) { *n_hits = 0; return BITNUC_OK; }
-    if (!ref) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, n)) { // one query: judged on the columns
-        const long long bad = bitnuc_host::kmer_edist_hits_small(ref, n, k, dev_query(*q), tau, end, hit_dist, cap, n_hits);
-        return bad >= 0 ? fail_invalid_base(err, ref[bad], (uint64_t)bad) : BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    // chunks of kHostChunk reported columns behind 2k bases of the chunk before, as kmer_edist_host copies them
-    if (int st = ensure_scratch(c, 0, kHostChunk + 64, err)) return st;
-    return hits_host_loop(c, n, kHostChunk, tau, *q, end, hit_dist, cap, n_hits, err, [&](size_t i0, size_t m, const HitsArgsT<HQ> &a) {
-        const size_t lead = i0 ? 2 * k : 0; // i0 is 0 or at least kHostChunk
-        HIPCHK(hipMemcpyAsync(c->scratch[0], ref + i0 - lead, lead + m, hipMemcpyHostToDevice, c->stream));
-        unsigned long long *slot;
-        if (int st = take_slot(c, i0 - lead, &slot, err)) return st;
-        return launch_edist_hits<false>(c, c->scratch[0], lead + m, lead, k, a, slot, err);
-    });
-}
-
-template <class HQ>
-int kmer_edist_hits_packed_host(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const HQ *q, unsigned tau, uint64_t *end,
-                                uint8_t *hit_dist, size_t cap, uint64_t *n_hits, bitnuc_err *err) {
-    clear_err(err);
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
-    if (int st = check_edist_hits_query(q, err)) return st;
-    if (int st = check_hits_out(end, cap, n_hits, err)) return st;
-    if (k == 0 || n < k) { *n_hits = 0; return BITNUC_OK; }
-    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, n)) { *n_hits = bitnuc_host::kmer_edist_hits_packed_small(words, n, k, dev_query(*q), tau, end, hit_dist, cap); return BITNUC_OK; }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    if (int st = ensure_scratch(c, 0, (kPackedChunkWords + 2) * 8, err)) return st;
-    // chunk i0 / 32 of whole words behind the words that hold the 2k bases before it, as kmer_edist_packed_host copies them
-    return hits_host_loop(c, n, 32 * kPackedChunkWords, tau, *q, end, hit_dist, cap, n_hits, err, [&](size_t i0, size_t, const HitsArgsT<HQ> &a) {
-        const PackedChunk ch = packed_chunk(i0 / 32, n, 1);
-        const size_t lw = i0 ? (2 * k + 31) / 32 : 0;
-        HIPCHK(hipMemcpyAsync(c->scratch[0], words + ch.w0 - lw, (lw + ch.words) * 8, hipMemcpyHostToDevice, c->stream));
-        return launch_edist_hits<true>(c, c->scratch[0], 32 * lw + ch.bases, 32 * lw, k, a, nullptr, err);
-    });
-}
-
 } // namespace
+
+// ---- the searches along a reference: inputs, searches and the two skeletons the entry points below name
+#include "ref_dispatch.h"
 
 extern "C" {
 
@@ -1115,7 +807,7 @@ int bitnuc_kmer_hdist_scan_dev(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, si
     clear_err(err);
     if (int st = check_ctx(c, err)) return st;
     if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    if (k == 0 || n < k) return BITNUC_OK; // no windows
+    if (no_windows(n, k)) return BITNUC_OK;
     if (!d_ref || !d_dist) return fail(err, BITNUC_UNSUPPORTED);
     DeviceGuard g(c->device);
     unsigned long long *slot;
@@ -1130,7 +822,7 @@ int bitnuc_kmer_hdist_count_dev(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, s
     if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
     if (!d_count || (reinterpret_cast<uintptr_t>(d_count) & 7)) return fail(err, BITNUC_UNSUPPORTED);
     DeviceGuard g(c->device);
-    if (k == 0 || n < k) { // no windows
+    if (no_windows(n, k)) {
         HIPCHK(hipMemsetAsync(d_count, 0, sizeof(uint64_t), c->stream));
         return BITNUC_OK;
     }
@@ -1179,7 +871,7 @@ int bitnuc_kmer_hdist_scan(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k
     clear_err(err);
     if (int st = check_ctx(c, err)) return st;
     if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    if (k == 0 || n < k) return BITNUC_OK;
+    if (no_windows(n, k)) return BITNUC_OK;
     if (!ref || !dist) return fail(err, BITNUC_UNSUPPORTED);
     DeviceGuard g(c->device);
     if (int st = flush_pending(c, err)) return st;
@@ -1299,261 +991,59 @@ int bitnuc_kmer_hdist_count_packed(bitnuc_ctx *c, const uint64_t *words, size_t 
     return BITNUC_OK;
 }
 
-// ---- the hit lists -------------------------------------------------------------------------------------------------------
+// ---- the searches along a reference: every entry point names a skeleton, an input and a search of ref_dispatch.h --------------------------------------
+// the hit lists
 int bitnuc_kmer_hdist_hits_dev(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *d_pos, uint8_t *d_hit_dist,
                                size_t cap, uint64_t *d_n_hits, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    if (int st = check_hits_out(d_pos, cap, d_n_hits, err)) return st;
-    DeviceGuard g(c->device);
-    if (k == 0 || n < k) { // no windows
-        HIPCHK(hipMemsetAsync(d_n_hits, 0, sizeof(uint64_t), c->stream));
-        return BITNUC_OK;
-    }
-    if (!d_ref) return fail(err, BITNUC_UNSUPPORTED);
-    unsigned long long *slot;
-    if (int st = take_slot(c, 0, &slot, err)) return st;
-    const HitsArgs a{query, tau, reinterpret_cast<unsigned long long *>(d_pos), d_hit_dist, cap, reinterpret_cast<unsigned long long *>(d_n_hits), 0};
-    return launch_hits(c, d_ref, n, k, a, slot, err);
+    return ref_async(c, AsciiRef{d_ref, n}, k, HdistHits<uint64_t>{&query, tau, d_pos, d_hit_dist, cap, d_n_hits}, err);
 }
-
 int bitnuc_kmer_hdist_hits_packed_dev(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *d_pos,
                                       uint8_t *d_hit_dist, size_t cap, uint64_t *d_n_hits, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    bool none;
-    if (int st = check_packed(d_words, n_words, n, k, &none, err)) return st;
-    if (int st = check_hits_out(d_pos, cap, d_n_hits, err)) return st;
-    DeviceGuard g(c->device);
-    if (none) {
-        HIPCHK(hipMemsetAsync(d_n_hits, 0, sizeof(uint64_t), c->stream));
-        return BITNUC_OK;
-    }
-    const HitsArgs a{query, tau, reinterpret_cast<unsigned long long *>(d_pos), d_hit_dist, cap, reinterpret_cast<unsigned long long *>(d_n_hits), 0};
-    return launch_hits_packed(c, d_words, n, k, a, err);
+    return ref_async(c, PackedRef{d_words, n_words, n}, k, HdistHits<uint64_t>{&query, tau, d_pos, d_hit_dist, cap, d_n_hits}, err);
 }
-
 int bitnuc_kmer_hdist_hits(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *pos, uint8_t *hit_dist, size_t cap,
                            uint64_t *n_hits, bitnuc_err *err) {
-    clear_err(err);
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    if (!n_hits || (!pos && cap)) return fail(err, BITNUC_UNSUPPORTED);
-    if (k == 0 || n < k) { *n_hits = 0; return BITNUC_OK; }
-    if (!ref) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, n)) {
-        const long long bad = bitnuc_host::kmer_hdist_hits_small(ref, n, k, query, tau, pos, hit_dist, cap, n_hits);
-        return bad >= 0 ? fail_invalid_base(err, ref[bad], (uint64_t)bad) : BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    // chunks of kHostChunk windows + their k - 1 halo bases
-    if (int st = ensure_scratch(c, 0, kHostChunk + 64, err)) return st;
-    return hits_host_loop(c, n - k + 1, kHostChunk, tau, query, pos, hit_dist, cap, n_hits, err, [&](size_t i0, size_t m, const HitsArgs &a) {
-        HIPCHK(hipMemcpyAsync(c->scratch[0], ref + i0, m + k - 1, hipMemcpyHostToDevice, c->stream));
-        unsigned long long *slot;
-        if (int st = take_slot(c, i0, &slot, err)) return st;
-        return launch_hits(c, c->scratch[0], m + k - 1, k, a, slot, err);
-    });
+    return ref_host(c, AsciiRef{ref, n}, k, HdistHits<uint64_t>{&query, tau, pos, hit_dist, cap, n_hits}, err);
 }
-
 int bitnuc_kmer_hdist_hits_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *pos,
                                   uint8_t *hit_dist, size_t cap, uint64_t *n_hits, bitnuc_err *err) {
-    clear_err(err);
-    bool none;
-    if (int st = check_packed(words, n_words, n, k, &none, err)) return st;
-    if (!n_hits || (!pos && cap)) return fail(err, BITNUC_UNSUPPORTED);
-    if (none) { *n_hits = 0; return BITNUC_OK; }
-    if (on_host(c, n)) { *n_hits = bitnuc_host::kmer_hdist_hits_packed_small(words, n, k, query, tau, pos, hit_dist, cap); return BITNUC_OK; }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    if (int st = ensure_scratch(c, 0, (kPackedChunkWords + 1) * 8, err)) return st;
-    // chunk w0 / 32 of whole words (packed_chunk): its windows start at base i0 = 32 w0
-    return hits_host_loop(c, n - k + 1, 32 * kPackedChunkWords, tau, query, pos, hit_dist, cap, n_hits, err, [&](size_t i0, size_t, const HitsArgs &a) {
-        const PackedChunk ch = packed_chunk(i0 / 32, n, k);
-        HIPCHK(hipMemcpyAsync(c->scratch[0], words + ch.w0, ch.words * 8, hipMemcpyHostToDevice, c->stream));
-        return launch_hits_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), ch.bases, k, a, err);
-    });
+    return ref_host(c, PackedRef{words, n_words, n}, k, HdistHits<uint64_t>{&query, tau, pos, hit_dist, cap, n_hits}, err);
 }
 
-// ---- the count for many queries -----------------------------------------------------------------------------------------
+// the count for many queries
 int bitnuc_kmer_hdist_count_multi_dev(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const uint64_t *d_queries, const uint32_t *d_taus, size_t n_queries,
                                       uint64_t *d_counts, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    bool none;
-    if (int st = check_multi(d_queries, d_taus, n_queries, d_counts, &none, err)) return st;
-    if (none) return BITNUC_OK;
-    DeviceGuard g(c->device);
-    if (k == 0 || n < k) { // no windows
-        HIPCHK(hipMemsetAsync(d_counts, 0, n_queries * sizeof(uint64_t), c->stream));
-        return BITNUC_OK;
-    }
-    if (!d_ref) return fail(err, BITNUC_UNSUPPORTED);
-    unsigned long long *slot;
-    if (int st = take_slot(c, 0, &slot, err)) return st;
-    return launch_count_multi(c, d_ref, n, k, MultiArgs{d_queries, d_taus, n_queries, reinterpret_cast<unsigned long long *>(d_counts)}, slot, err);
+    return ref_async(c, AsciiRef{d_ref, n}, k, HdistCount<uint64_t>{d_queries, d_taus, n_queries, d_counts}, err);
 }
-
 int bitnuc_kmer_hdist_count_multi_packed_dev(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const uint64_t *d_queries,
                                              const uint32_t *d_taus, size_t n_queries, uint64_t *d_counts, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
-    bool none;
-    if (int st = check_multi(d_queries, d_taus, n_queries, d_counts, &none, err)) return st;
-    if (none) return BITNUC_OK;
-    DeviceGuard g(c->device);
-    if (k == 0 || n < k) {
-        HIPCHK(hipMemsetAsync(d_counts, 0, n_queries * sizeof(uint64_t), c->stream));
-        return BITNUC_OK;
-    }
-    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    return launch_count_multi_packed(c, d_words, n, k, MultiArgs{d_queries, d_taus, n_queries, reinterpret_cast<unsigned long long *>(d_counts)}, err);
+    return ref_async(c, PackedRef{d_words, n_words, n}, k, HdistCount<uint64_t>{d_queries, d_taus, n_queries, d_counts}, err);
 }
-
 int bitnuc_kmer_hdist_count_multi(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const uint64_t *queries, const uint32_t *taus, size_t n_queries,
                                   uint64_t *counts, bitnuc_err *err) {
-    clear_err(err);
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    bool none;
-    if (int st = check_multi(queries, taus, n_queries, counts, &none, err)) return st;
-    if (none) return BITNUC_OK;
-    if (k == 0 || n < k) { memset(counts, 0, n_queries * sizeof(uint64_t)); return BITNUC_OK; }
-    if (!ref) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, multi_work(n - k + 1, n_queries))) {
-        const long long bad = bitnuc_host::kmer_hdist_count_multi_small(ref, n, k, queries, taus, n_queries, counts);
-        return bad >= 0 ? fail_invalid_base(err, ref[bad], (uint64_t)bad) : BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    // chunks of kHostChunk windows + their k - 1 halo bases
-    if (int st = ensure_scratch(c, 0, kHostChunk + 64, err)) return st;
-    const size_t nwin = n - k + 1;
-    return multi_host_loop(c, nwin, kHostChunk, queries, taus, n_queries, counts, err, [&](size_t i0, const MultiArgs &a) {
-        const size_t m = nwin - i0 < kHostChunk ? nwin - i0 : kHostChunk;
-        HIPCHK(hipMemcpyAsync(c->scratch[0], ref + i0, m + k - 1, hipMemcpyHostToDevice, c->stream));
-        unsigned long long *slot;
-        if (int st = take_slot(c, i0, &slot, err)) return st;
-        return launch_count_multi(c, c->scratch[0], m + k - 1, k, a, slot, err);
-    });
+    return ref_host(c, AsciiRef{ref, n}, k, HdistCount<uint64_t>{queries, taus, n_queries, counts}, err);
 }
-
 int bitnuc_kmer_hdist_count_multi_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const uint64_t *queries, const uint32_t *taus,
                                          size_t n_queries, uint64_t *counts, bitnuc_err *err) {
-    clear_err(err);
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
-    bool none;
-    if (int st = check_multi(queries, taus, n_queries, counts, &none, err)) return st;
-    if (none) return BITNUC_OK;
-    if (k == 0 || n < k) { memset(counts, 0, n_queries * sizeof(uint64_t)); return BITNUC_OK; }
-    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, multi_work(n - k + 1, n_queries))) {
-        bitnuc_host::kmer_hdist_count_multi_packed_small(words, n, k, queries, taus, n_queries, counts);
-        return BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    if (int st = ensure_scratch(c, 0, (kPackedChunkWords + 1) * 8, err)) return st;
-    // chunk w0 / 32 of whole words (packed_chunk): its windows start at base i0 = 32 w0
-    return multi_host_loop(c, n - k + 1, 32 * kPackedChunkWords, queries, taus, n_queries, counts, err, [&](size_t i0, const MultiArgs &a) {
-        const PackedChunk ch = packed_chunk(i0 / 32, n, k);
-        HIPCHK(hipMemcpyAsync(c->scratch[0], words + ch.w0, ch.words * 8, hipMemcpyHostToDevice, c->stream));
-        return launch_count_multi_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), ch.bases, k, a, err);
-    });
+    return ref_host(c, PackedRef{words, n_words, n}, k, HdistCount<uint64_t>{queries, taus, n_queries, counts}, err);
 }
 
-// ---- the best match per query -------------------------------------------------------------------------------------------
+// the best match per query
 int bitnuc_kmer_hdist_best_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const uint64_t *d_queries, size_t n_queries, uint64_t *d_pos,
                                  uint8_t *d_dist, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    bool none;
-    if (int st = check_best(d_queries, n_queries, d_pos, d_dist, &none, err)) return st;
-    if (none) return BITNUC_OK;
-    DeviceGuard g(c->device);
-    if (k == 0 || n < k) return best_fill_dev(c, d_pos, d_dist, n_queries, err); // no windows
-    if (!d_ref) return fail(err, BITNUC_UNSUPPORTED);
-    unsigned long long *slot;
-    if (int st = take_slot(c, 0, &slot, err)) return st;
-    return launch_best(c, d_ref, n, k, BestArgs{d_queries, n_queries, reinterpret_cast<unsigned long long *>(d_pos), d_dist}, slot, err);
+    return ref_async(c, AsciiRef{d_ref, n}, k, HdistBest<uint64_t>{d_queries, n_queries, d_pos, d_dist}, err);
 }
-
 int bitnuc_kmer_hdist_best_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const uint64_t *d_queries, size_t n_queries,
                                         uint64_t *d_pos, uint8_t *d_dist, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
-    bool none;
-    if (int st = check_best(d_queries, n_queries, d_pos, d_dist, &none, err)) return st;
-    if (none) return BITNUC_OK;
-    DeviceGuard g(c->device);
-    if (k == 0 || n < k) return best_fill_dev(c, d_pos, d_dist, n_queries, err);
-    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    return launch_best_packed(c, d_words, n, k, BestArgs{d_queries, n_queries, reinterpret_cast<unsigned long long *>(d_pos), d_dist}, err);
+    return ref_async(c, PackedRef{d_words, n_words, n}, k, HdistBest<uint64_t>{d_queries, n_queries, d_pos, d_dist}, err);
 }
-
 int bitnuc_kmer_hdist_best(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const uint64_t *queries, size_t n_queries, uint64_t *pos, uint8_t *dist,
                            bitnuc_err *err) {
-    clear_err(err);
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    bool none;
-    if (int st = check_best(queries, n_queries, pos, dist, &none, err)) return st;
-    if (none) return BITNUC_OK;
-    if (k == 0 || n < k) { memset(pos, 0xFF, n_queries * sizeof(uint64_t)); memset(dist, 0xFF, n_queries); return BITNUC_OK; }
-    if (!ref) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, multi_work(n - k + 1, n_queries))) {
-        const long long bad = bitnuc_host::kmer_hdist_best_small(ref, n, k, queries, n_queries, pos, dist);
-        return bad >= 0 ? fail_invalid_base(err, ref[bad], (uint64_t)bad) : BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    // chunks of kHostChunk windows + their k - 1 halo bases
-    if (int st = ensure_scratch(c, 0, kHostChunk + 64, err)) return st;
-    const size_t nwin = n - k + 1;
-    return best_host_loop(c, nwin, kHostChunk, queries, n_queries, pos, dist, err, [&](size_t i0, const BestArgs &a) {
-        const size_t m = nwin - i0 < kHostChunk ? nwin - i0 : kHostChunk;
-        HIPCHK(hipMemcpyAsync(c->scratch[0], ref + i0, m + k - 1, hipMemcpyHostToDevice, c->stream));
-        unsigned long long *slot;
-        if (int st = take_slot(c, i0, &slot, err)) return st;
-        return launch_best(c, c->scratch[0], m + k - 1, k, a, slot, err);
-    });
+    return ref_host(c, AsciiRef{ref, n}, k, HdistBest<uint64_t>{queries, n_queries, pos, dist}, err);
 }
-
 int bitnuc_kmer_hdist_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const uint64_t *queries, size_t n_queries, uint64_t *pos,
                                   uint8_t *dist, bitnuc_err *err) {
-    clear_err(err);
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
-    bool none;
-    if (int st = check_best(queries, n_queries, pos, dist, &none, err)) return st;
-    if (none) return BITNUC_OK;
-    if (k == 0 || n < k) { memset(pos, 0xFF, n_queries * sizeof(uint64_t)); memset(dist, 0xFF, n_queries); return BITNUC_OK; }
-    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, multi_work(n - k + 1, n_queries))) {
-        bitnuc_host::kmer_hdist_best_packed_small(words, n, k, queries, n_queries, pos, dist);
-        return BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    if (int st = ensure_scratch(c, 0, (kPackedChunkWords + 1) * 8, err)) return st;
-    // chunk w0 / 32 of whole words (packed_chunk): its windows start at base i0 = 32 w0
-    return best_host_loop(c, n - k + 1, 32 * kPackedChunkWords, queries, n_queries, pos, dist, err, [&](size_t i0, const BestArgs &a) {
-        const PackedChunk ch = packed_chunk(i0 / 32, n, k);
-        HIPCHK(hipMemcpyAsync(c->scratch[0], words + ch.w0, ch.words * 8, hipMemcpyHostToDevice, c->stream));
-        return launch_best_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), ch.bases, k, a, err);
-    });
+    return ref_host(c, PackedRef{words, n_words, n}, k, HdistBest<uint64_t>{queries, n_queries, pos, dist}, err);
 }
 
 } // extern "C"
@@ -1881,8 +1371,8 @@ int bitnuc_reads_pattern_edist_anchored_batch_packed(bitnuc_ctx *c, const uint64
                                          second_end, second_dist, err);
 }
 
-// ---- pattern queries: a set of bases per position (bitnuc_pattern).  The twelve entry points below are the twins of the exact ones above: the same checks
-// in the same order, the same launchers, loops and kernels under the other query kind.
+// ---- pattern queries: a set of bases per position (bitnuc_pattern).  The converters are host code; the twelve entry points behind them are
+// the twins of the exact hit lists, counts and best matches above: the same skeleton, input and search under the other query kind.
 int bitnuc_pattern_from_iupac(const uint8_t *letters, size_t k, bitnuc_pattern *out, bitnuc_err *err) {
     clear_err(err);
     if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k); // before any letter is read
@@ -1905,392 +1395,183 @@ int bitnuc_pattern_from_2bit(uint64_t query, size_t k, bitnuc_pattern *out, bitn
 
 int bitnuc_kmer_pattern_count_multi_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const bitnuc_pattern *d_patterns, const uint32_t *d_taus, size_t n_queries,
                                           uint64_t *d_counts, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    bool none;
-    if (int st = check_multi(d_patterns, d_taus, n_queries, d_counts, &none, err, 3)) return st;
-    if (none) return BITNUC_OK;
-    DeviceGuard g(c->device);
-    if (k == 0 || n < k) { // no windows
-        HIPCHK(hipMemsetAsync(d_counts, 0, n_queries * sizeof(uint64_t), c->stream));
-        return BITNUC_OK;
-    }
-    if (!d_ref) return fail(err, BITNUC_UNSUPPORTED);
-    unsigned long long *slot;
-    if (int st = take_slot(c, 0, &slot, err)) return st;
-    return launch_count_multi(c, d_ref, n, k, MultiArgsT<bitnuc_pattern>{d_patterns, d_taus, n_queries, reinterpret_cast<unsigned long long *>(d_counts)}, slot, err);
+    return ref_async(c, AsciiRef{d_ref, n}, k, HdistCount<bitnuc_pattern>{d_patterns, d_taus, n_queries, d_counts}, err);
 }
-
 int bitnuc_kmer_pattern_count_multi_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *d_patterns,
                                                  const uint32_t *d_taus, size_t n_queries, uint64_t *d_counts, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
-    bool none;
-    if (int st = check_multi(d_patterns, d_taus, n_queries, d_counts, &none, err, 3)) return st;
-    if (none) return BITNUC_OK;
-    DeviceGuard g(c->device);
-    if (k == 0 || n < k) {
-        HIPCHK(hipMemsetAsync(d_counts, 0, n_queries * sizeof(uint64_t), c->stream));
-        return BITNUC_OK;
-    }
-    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    return launch_count_multi_packed(c, d_words, n, k, MultiArgsT<bitnuc_pattern>{d_patterns, d_taus, n_queries, reinterpret_cast<unsigned long long *>(d_counts)}, err);
+    return ref_async(c, PackedRef{d_words, n_words, n}, k, HdistCount<bitnuc_pattern>{d_patterns, d_taus, n_queries, d_counts}, err);
 }
-
 int bitnuc_kmer_pattern_count_multi(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const bitnuc_pattern *patterns, const uint32_t *taus, size_t n_queries,
                                     uint64_t *counts, bitnuc_err *err) {
-    clear_err(err);
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    bool none;
-    if (int st = check_multi(patterns, taus, n_queries, counts, &none, err, 3)) return st;
-    if (none) return BITNUC_OK;
-    if (k == 0 || n < k) { memset(counts, 0, n_queries * sizeof(uint64_t)); return BITNUC_OK; }
-    if (!ref) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, multi_work(n - k + 1, n_queries))) {
-        const long long bad = bitnuc_host::kmer_hdist_count_multi_small(ref, n, k, dev_queries(patterns), taus, n_queries, counts);
-        return bad >= 0 ? fail_invalid_base(err, ref[bad], (uint64_t)bad) : BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    // chunks of kHostChunk windows + their k - 1 halo bases
-    if (int st = ensure_scratch(c, 0, kHostChunk + 64, err)) return st;
-    const size_t nwin = n - k + 1;
-    return multi_host_loop(c, nwin, kHostChunk, patterns, taus, n_queries, counts, err, [&](size_t i0, const MultiArgsT<bitnuc_pattern> &a) {
-        const size_t m = nwin - i0 < kHostChunk ? nwin - i0 : kHostChunk;
-        HIPCHK(hipMemcpyAsync(c->scratch[0], ref + i0, m + k - 1, hipMemcpyHostToDevice, c->stream));
-        unsigned long long *slot;
-        if (int st = take_slot(c, i0, &slot, err)) return st;
-        return launch_count_multi(c, c->scratch[0], m + k - 1, k, a, slot, err);
-    });
+    return ref_host(c, AsciiRef{ref, n}, k, HdistCount<bitnuc_pattern>{patterns, taus, n_queries, counts}, err);
 }
-
 int bitnuc_kmer_pattern_count_multi_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *patterns, const uint32_t *taus,
                                            size_t n_queries, uint64_t *counts, bitnuc_err *err) {
-    clear_err(err);
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
-    bool none;
-    if (int st = check_multi(patterns, taus, n_queries, counts, &none, err, 3)) return st;
-    if (none) return BITNUC_OK;
-    if (k == 0 || n < k) { memset(counts, 0, n_queries * sizeof(uint64_t)); return BITNUC_OK; }
-    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, multi_work(n - k + 1, n_queries))) {
-        bitnuc_host::kmer_hdist_count_multi_packed_small(words, n, k, dev_queries(patterns), taus, n_queries, counts);
-        return BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    if (int st = ensure_scratch(c, 0, (kPackedChunkWords + 1) * 8, err)) return st;
-    // chunk w0 / 32 of whole words (packed_chunk): its windows start at base i0 = 32 w0
-    return multi_host_loop(c, n - k + 1, 32 * kPackedChunkWords, patterns, taus, n_queries, counts, err, [&](size_t i0, const MultiArgsT<bitnuc_pattern> &a) {
-        const PackedChunk ch = packed_chunk(i0 / 32, n, k);
-        HIPCHK(hipMemcpyAsync(c->scratch[0], words + ch.w0, ch.words * 8, hipMemcpyHostToDevice, c->stream));
-        return launch_count_multi_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), ch.bases, k, a, err);
-    });
+    return ref_host(c, PackedRef{words, n_words, n}, k, HdistCount<bitnuc_pattern>{patterns, taus, n_queries, counts}, err);
 }
-
 int bitnuc_kmer_pattern_best_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries, uint64_t *d_pos,
                                    uint8_t *d_dist, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    bool none;
-    if (int st = check_best(d_patterns, n_queries, d_pos, d_dist, &none, err, 3)) return st;
-    if (none) return BITNUC_OK;
-    DeviceGuard g(c->device);
-    if (k == 0 || n < k) return best_fill_dev(c, d_pos, d_dist, n_queries, err); // no windows
-    if (!d_ref) return fail(err, BITNUC_UNSUPPORTED);
-    unsigned long long *slot;
-    if (int st = take_slot(c, 0, &slot, err)) return st;
-    return launch_best(c, d_ref, n, k, BestArgsT<bitnuc_pattern>{d_patterns, n_queries, reinterpret_cast<unsigned long long *>(d_pos), d_dist}, slot, err);
+    return ref_async(c, AsciiRef{d_ref, n}, k, HdistBest<bitnuc_pattern>{d_patterns, n_queries, d_pos, d_dist}, err);
 }
-
 int bitnuc_kmer_pattern_best_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries,
                                           uint64_t *d_pos, uint8_t *d_dist, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
-    bool none;
-    if (int st = check_best(d_patterns, n_queries, d_pos, d_dist, &none, err, 3)) return st;
-    if (none) return BITNUC_OK;
-    DeviceGuard g(c->device);
-    if (k == 0 || n < k) return best_fill_dev(c, d_pos, d_dist, n_queries, err);
-    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    return launch_best_packed(c, d_words, n, k, BestArgsT<bitnuc_pattern>{d_patterns, n_queries, reinterpret_cast<unsigned long long *>(d_pos), d_dist}, err);
+    return ref_async(c, PackedRef{d_words, n_words, n}, k, HdistBest<bitnuc_pattern>{d_patterns, n_queries, d_pos, d_dist}, err);
 }
-
 int bitnuc_kmer_pattern_best(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const bitnuc_pattern *patterns, size_t n_queries, uint64_t *pos, uint8_t *dist,
                              bitnuc_err *err) {
-    clear_err(err);
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    bool none;
-    if (int st = check_best(patterns, n_queries, pos, dist, &none, err, 3)) return st;
-    if (none) return BITNUC_OK;
-    if (k == 0 || n < k) { memset(pos, 0xFF, n_queries * sizeof(uint64_t)); memset(dist, 0xFF, n_queries); return BITNUC_OK; }
-    if (!ref) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, multi_work(n - k + 1, n_queries))) {
-        const long long bad = bitnuc_host::kmer_hdist_best_small(ref, n, k, dev_queries(patterns), n_queries, pos, dist);
-        return bad >= 0 ? fail_invalid_base(err, ref[bad], (uint64_t)bad) : BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    // chunks of kHostChunk windows + their k - 1 halo bases
-    if (int st = ensure_scratch(c, 0, kHostChunk + 64, err)) return st;
-    const size_t nwin = n - k + 1;
-    return best_host_loop(c, nwin, kHostChunk, patterns, n_queries, pos, dist, err, [&](size_t i0, const BestArgsT<bitnuc_pattern> &a) {
-        const size_t m = nwin - i0 < kHostChunk ? nwin - i0 : kHostChunk;
-        HIPCHK(hipMemcpyAsync(c->scratch[0], ref + i0, m + k - 1, hipMemcpyHostToDevice, c->stream));
-        unsigned long long *slot;
-        if (int st = take_slot(c, i0, &slot, err)) return st;
-        return launch_best(c, c->scratch[0], m + k - 1, k, a, slot, err);
-    });
+    return ref_host(c, AsciiRef{ref, n}, k, HdistBest<bitnuc_pattern>{patterns, n_queries, pos, dist}, err);
 }
-
 int bitnuc_kmer_pattern_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *patterns, size_t n_queries, uint64_t *pos,
                                     uint8_t *dist, bitnuc_err *err) {
-    clear_err(err);
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    if (n_words < words_for(n)) return fail(err, BITNUC_INVALID_LENGTH, n);
-    bool none;
-    if (int st = check_best(patterns, n_queries, pos, dist, &none, err, 3)) return st;
-    if (none) return BITNUC_OK;
-    if (k == 0 || n < k) { memset(pos, 0xFF, n_queries * sizeof(uint64_t)); memset(dist, 0xFF, n_queries); return BITNUC_OK; }
-    if (!words || (reinterpret_cast<uintptr_t>(words) & 7)) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, multi_work(n - k + 1, n_queries))) {
-        bitnuc_host::kmer_hdist_best_packed_small(words, n, k, dev_queries(patterns), n_queries, pos, dist);
-        return BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    if (int st = ensure_scratch(c, 0, (kPackedChunkWords + 1) * 8, err)) return st;
-    // chunk w0 / 32 of whole words (packed_chunk): its windows start at base i0 = 32 w0
-    return best_host_loop(c, n - k + 1, 32 * kPackedChunkWords, patterns, n_queries, pos, dist, err, [&](size_t i0, const BestArgsT<bitnuc_pattern> &a) {
-        const PackedChunk ch = packed_chunk(i0 / 32, n, k);
-        HIPCHK(hipMemcpyAsync(c->scratch[0], words + ch.w0, ch.words * 8, hipMemcpyHostToDevice, c->stream));
-        return launch_best_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), ch.bases, k, a, err);
-    });
+    return ref_host(c, PackedRef{words, n_words, n}, k, HdistBest<bitnuc_pattern>{patterns, n_queries, pos, dist}, err);
 }
 
-// ---- the mismatch histogram per query (hist_async ... hist_packed_host above) ------------------------------------------------------------------
+// ---- the mismatch histogram per query, each form once per query kind
 int bitnuc_kmer_hdist_hist_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const uint64_t *d_queries, size_t n_queries, size_t n_bins,
                                  uint64_t *d_hist, bitnuc_err *err) {
-    return hist_async(c, d_ref, n, k, d_queries, n_queries, n_bins, d_hist, err);
+    return ref_async(c, AsciiRef{d_ref, n}, k, HdistHist<uint64_t>{d_queries, n_queries, n_bins, d_hist}, err);
 }
 int bitnuc_kmer_hdist_hist_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const uint64_t *d_queries, size_t n_queries,
                                         size_t n_bins, uint64_t *d_hist, bitnuc_err *err) {
-    return hist_packed_async(c, d_words, n_words, n, k, d_queries, n_queries, n_bins, d_hist, err);
+    return ref_async(c, PackedRef{d_words, n_words, n}, k, HdistHist<uint64_t>{d_queries, n_queries, n_bins, d_hist}, err);
 }
 int bitnuc_kmer_hdist_hist(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const uint64_t *queries, size_t n_queries, size_t n_bins, uint64_t *hist,
                            bitnuc_err *err) {
-    return hist_host(c, ref, n, k, queries, n_queries, n_bins, hist, err);
+    return ref_host(c, AsciiRef{ref, n}, k, HdistHist<uint64_t>{queries, n_queries, n_bins, hist}, err);
 }
 int bitnuc_kmer_hdist_hist_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const uint64_t *queries, size_t n_queries, size_t n_bins,
                                   uint64_t *hist, bitnuc_err *err) {
-    return hist_packed_host(c, words, n_words, n, k, queries, n_queries, n_bins, hist, err);
+    return ref_host(c, PackedRef{words, n_words, n}, k, HdistHist<uint64_t>{queries, n_queries, n_bins, hist}, err);
 }
 int bitnuc_kmer_pattern_hist_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries, size_t n_bins,
                                    uint64_t *d_hist, bitnuc_err *err) {
-    return hist_async(c, d_ref, n, k, d_patterns, n_queries, n_bins, d_hist, err);
+    return ref_async(c, AsciiRef{d_ref, n}, k, HdistHist<bitnuc_pattern>{d_patterns, n_queries, n_bins, d_hist}, err);
 }
 int bitnuc_kmer_pattern_hist_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *d_patterns,
                                           size_t n_queries, size_t n_bins, uint64_t *d_hist, bitnuc_err *err) {
-    return hist_packed_async(c, d_words, n_words, n, k, d_patterns, n_queries, n_bins, d_hist, err);
+    return ref_async(c, PackedRef{d_words, n_words, n}, k, HdistHist<bitnuc_pattern>{d_patterns, n_queries, n_bins, d_hist}, err);
 }
 int bitnuc_kmer_pattern_hist(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const bitnuc_pattern *patterns, size_t n_queries, size_t n_bins, uint64_t *hist,
                              bitnuc_err *err) {
-    return hist_host(c, ref, n, k, patterns, n_queries, n_bins, hist, err);
+    return ref_host(c, AsciiRef{ref, n}, k, HdistHist<bitnuc_pattern>{patterns, n_queries, n_bins, hist}, err);
 }
 int bitnuc_kmer_pattern_hist_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *patterns, size_t n_queries,
                                     size_t n_bins, uint64_t *hist, bitnuc_err *err) {
-    return hist_packed_host(c, words, n_words, n, k, patterns, n_queries, n_bins, hist, err);
+    return ref_host(c, PackedRef{words, n_words, n}, k, HdistHist<bitnuc_pattern>{patterns, n_queries, n_bins, hist}, err);
 }
-
 int bitnuc_kmer_pattern_hits_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const bitnuc_pattern *pattern, unsigned tau, uint64_t *d_pos, uint8_t *d_hit_dist,
                                    size_t cap, uint64_t *d_n_hits, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    if (int st = check_hits_out(d_pos, cap, d_n_hits, err)) return st;
-    if (!pattern) return fail(err, BITNUC_UNSUPPORTED);
-    DeviceGuard g(c->device);
-    if (k == 0 || n < k) { // no windows
-        HIPCHK(hipMemsetAsync(d_n_hits, 0, sizeof(uint64_t), c->stream));
-        return BITNUC_OK;
-    }
-    if (!d_ref) return fail(err, BITNUC_UNSUPPORTED);
-    unsigned long long *slot;
-    if (int st = take_slot(c, 0, &slot, err)) return st;
-    const HitsArgsT<bitnuc_pattern> a{*pattern, tau, reinterpret_cast<unsigned long long *>(d_pos), d_hit_dist, cap, reinterpret_cast<unsigned long long *>(d_n_hits), 0};
-    return launch_hits(c, d_ref, n, k, a, slot, err);
+    return ref_async(c, AsciiRef{d_ref, n}, k, HdistHits<bitnuc_pattern>{pattern, tau, d_pos, d_hit_dist, cap, d_n_hits}, err);
 }
-
 int bitnuc_kmer_pattern_hits_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *pattern, unsigned tau, uint64_t *d_pos,
                                           uint8_t *d_hit_dist, size_t cap, uint64_t *d_n_hits, bitnuc_err *err) {
-    clear_err(err);
-    if (int st = check_ctx(c, err)) return st;
-    bool none;
-    if (int st = check_packed(d_words, n_words, n, k, &none, err)) return st;
-    if (int st = check_hits_out(d_pos, cap, d_n_hits, err)) return st;
-    if (!pattern) return fail(err, BITNUC_UNSUPPORTED);
-    DeviceGuard g(c->device);
-    if (none) {
-        HIPCHK(hipMemsetAsync(d_n_hits, 0, sizeof(uint64_t), c->stream));
-        return BITNUC_OK;
-    }
-    const HitsArgsT<bitnuc_pattern> a{*pattern, tau, reinterpret_cast<unsigned long long *>(d_pos), d_hit_dist, cap, reinterpret_cast<unsigned long long *>(d_n_hits), 0};
-    return launch_hits_packed(c, d_words, n, k, a, err);
+    return ref_async(c, PackedRef{d_words, n_words, n}, k, HdistHits<bitnuc_pattern>{pattern, tau, d_pos, d_hit_dist, cap, d_n_hits}, err);
 }
-
 int bitnuc_kmer_pattern_hits(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const bitnuc_pattern *pattern, unsigned tau, uint64_t *pos, uint8_t *hit_dist, size_t cap,
                              uint64_t *n_hits, bitnuc_err *err) {
-    clear_err(err);
-    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
-    if (!n_hits || (!pos && cap) || !pattern) return fail(err, BITNUC_UNSUPPORTED);
-    if (k == 0 || n < k) { *n_hits = 0; return BITNUC_OK; }
-    if (!ref) return fail(err, BITNUC_UNSUPPORTED);
-    if (on_host(c, n)) {
-        const long long bad = bitnuc_host::kmer_hdist_hits_small(ref, n, k, dev_query(*pattern), tau, pos, hit_dist, cap, n_hits);
-        return bad >= 0 ? fail_invalid_base(err, ref[bad], (uint64_t)bad) : BITNUC_OK;
-    }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    // chunks of kHostChunk windows + their k - 1 halo bases
-    if (int st = ensure_scratch(c, 0, kHostChunk + 64, err)) return st;
-    return hits_host_loop(c, n - k + 1, kHostChunk, tau, *pattern, pos, hit_dist, cap, n_hits, err, [&](size_t i0, size_t m, const HitsArgsT<bitnuc_pattern> &a) {
-        HIPCHK(hipMemcpyAsync(c->scratch[0], ref + i0, m + k - 1, hipMemcpyHostToDevice, c->stream));
-        unsigned long long *slot;
-        if (int st = take_slot(c, i0, &slot, err)) return st;
-        return launch_hits(c, c->scratch[0], m + k - 1, k, a, slot, err);
-    });
+    return ref_host(c, AsciiRef{ref, n}, k, HdistHits<bitnuc_pattern>{pattern, tau, pos, hit_dist, cap, n_hits}, err);
 }
-
 int bitnuc_kmer_pattern_hits_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *pattern, unsigned tau, uint64_t *pos,
                                     uint8_t *hit_dist, size_t cap, uint64_t *n_hits, bitnuc_err *err) {
-    clear_err(err);
-    bool none;
-    if (int st = check_packed(words, n_words, n, k, &none, err)) return st;
-    if (!n_hits || (!pos && cap) || !pattern) return fail(err, BITNUC_UNSUPPORTED);
-    if (none) { *n_hits = 0; return BITNUC_OK; }
-    if (on_host(c, n)) { *n_hits = bitnuc_host::kmer_hdist_hits_packed_small(words, n, k, dev_query(*pattern), tau, pos, hit_dist, cap); return BITNUC_OK; }
-    if (int st = check_ctx(c, err)) return st;
-    DeviceGuard g(c->device);
-    if (int st = flush_pending(c, err)) return st;
-    if (int st = ensure_scratch(c, 0, (kPackedChunkWords + 1) * 8, err)) return st;
-    // chunk w0 / 32 of whole words (packed_chunk): its windows start at base i0 = 32 w0
-    return hits_host_loop(c, n - k + 1, 32 * kPackedChunkWords, tau, *pattern, pos, hit_dist, cap, n_hits, err, [&](size_t i0, size_t, const HitsArgsT<bitnuc_pattern> &a) {
-        const PackedChunk ch = packed_chunk(i0 / 32, n, k);
-        HIPCHK(hipMemcpyAsync(c->scratch[0], words + ch.w0, ch.words * 8, hipMemcpyHostToDevice, c->stream));
-        return launch_hits_packed(c, reinterpret_cast<const uint64_t *>(c->scratch[0]), ch.bases, k, a, err);
-    });
+    return ref_host(c, PackedRef{words, n_words, n}, k, HdistHits<bitnuc_pattern>{pattern, tau, pos, hit_dist, cap, n_hits}, err);
 }
 
-
-// ---- the indel-tolerant search along a reference: best match and count per query by edit distance (kmer_edist_async ... kmer_edist_packed_host above),
-// each form once per query kind
+// ---- the indel-tolerant search along a reference: best match and count per query by edit distance, each form once per query kind
 int bitnuc_kmer_edist_best_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const uint64_t *d_queries, size_t n_queries, uint64_t *d_end, uint8_t *d_dist,
                                  bitnuc_err *err) {
-    return kmer_edist_async(c, d_ref, n, k, EdistBest<uint64_t>{d_queries, n_queries, d_end, d_dist}, err);
+    return ref_async(c, AsciiRef{d_ref, n}, k, EdistBest<uint64_t>{d_queries, n_queries, d_end, d_dist}, err);
 }
 int bitnuc_kmer_edist_best_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const uint64_t *d_queries, size_t n_queries,
                                         uint64_t *d_end, uint8_t *d_dist, bitnuc_err *err) {
-    return kmer_edist_packed_async(c, d_words, n_words, n, k, EdistBest<uint64_t>{d_queries, n_queries, d_end, d_dist}, err);
+    return ref_async(c, PackedRef{d_words, n_words, n}, k, EdistBest<uint64_t>{d_queries, n_queries, d_end, d_dist}, err);
 }
 int bitnuc_kmer_edist_best(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const uint64_t *queries, size_t n_queries, uint64_t *end, uint8_t *dist, bitnuc_err *err) {
-    return kmer_edist_host(c, ref, n, k, EdistBest<uint64_t>{queries, n_queries, end, dist}, err);
+    return ref_host(c, AsciiRef{ref, n}, k, EdistBest<uint64_t>{queries, n_queries, end, dist}, err);
 }
 int bitnuc_kmer_edist_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const uint64_t *queries, size_t n_queries, uint64_t *end,
                                   uint8_t *dist, bitnuc_err *err) {
-    return kmer_edist_packed_host(c, words, n_words, n, k, EdistBest<uint64_t>{queries, n_queries, end, dist}, err);
+    return ref_host(c, PackedRef{words, n_words, n}, k, EdistBest<uint64_t>{queries, n_queries, end, dist}, err);
 }
 int bitnuc_kmer_edist_count_multi_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const uint64_t *d_queries, const uint32_t *d_taus, size_t n_queries,
                                         uint64_t *d_counts, bitnuc_err *err) {
-    return kmer_edist_async(c, d_ref, n, k, EdistCount<uint64_t>{d_queries, d_taus, n_queries, d_counts}, err);
+    return ref_async(c, AsciiRef{d_ref, n}, k, EdistCount<uint64_t>{d_queries, d_taus, n_queries, d_counts}, err);
 }
 int bitnuc_kmer_edist_count_multi_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const uint64_t *d_queries,
                                                const uint32_t *d_taus, size_t n_queries, uint64_t *d_counts, bitnuc_err *err) {
-    return kmer_edist_packed_async(c, d_words, n_words, n, k, EdistCount<uint64_t>{d_queries, d_taus, n_queries, d_counts}, err);
+    return ref_async(c, PackedRef{d_words, n_words, n}, k, EdistCount<uint64_t>{d_queries, d_taus, n_queries, d_counts}, err);
 }
 int bitnuc_kmer_edist_count_multi(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const uint64_t *queries, const uint32_t *taus, size_t n_queries, uint64_t *counts,
                                   bitnuc_err *err) {
-    return kmer_edist_host(c, ref, n, k, EdistCount<uint64_t>{queries, taus, n_queries, counts}, err);
+    return ref_host(c, AsciiRef{ref, n}, k, EdistCount<uint64_t>{queries, taus, n_queries, counts}, err);
 }
 int bitnuc_kmer_edist_count_multi_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const uint64_t *queries, const uint32_t *taus,
                                          size_t n_queries, uint64_t *counts, bitnuc_err *err) {
-    return kmer_edist_packed_host(c, words, n_words, n, k, EdistCount<uint64_t>{queries, taus, n_queries, counts}, err);
+    return ref_host(c, PackedRef{words, n_words, n}, k, EdistCount<uint64_t>{queries, taus, n_queries, counts}, err);
 }
 int bitnuc_kmer_pattern_edist_best_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries, uint64_t *d_end, uint8_t *d_dist,
                                          bitnuc_err *err) {
-    return kmer_edist_async(c, d_ref, n, k, EdistBest<bitnuc_pattern>{d_patterns, n_queries, d_end, d_dist}, err);
+    return ref_async(c, AsciiRef{d_ref, n}, k, EdistBest<bitnuc_pattern>{d_patterns, n_queries, d_end, d_dist}, err);
 }
 int bitnuc_kmer_pattern_edist_best_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries,
                                                 uint64_t *d_end, uint8_t *d_dist, bitnuc_err *err) {
-    return kmer_edist_packed_async(c, d_words, n_words, n, k, EdistBest<bitnuc_pattern>{d_patterns, n_queries, d_end, d_dist}, err);
+    return ref_async(c, PackedRef{d_words, n_words, n}, k, EdistBest<bitnuc_pattern>{d_patterns, n_queries, d_end, d_dist}, err);
 }
 int bitnuc_kmer_pattern_edist_best(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const bitnuc_pattern *patterns, size_t n_queries, uint64_t *end, uint8_t *dist, bitnuc_err *err) {
-    return kmer_edist_host(c, ref, n, k, EdistBest<bitnuc_pattern>{patterns, n_queries, end, dist}, err);
+    return ref_host(c, AsciiRef{ref, n}, k, EdistBest<bitnuc_pattern>{patterns, n_queries, end, dist}, err);
 }
 int bitnuc_kmer_pattern_edist_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *patterns, size_t n_queries, uint64_t *end,
                                           uint8_t *dist, bitnuc_err *err) {
-    return kmer_edist_packed_host(c, words, n_words, n, k, EdistBest<bitnuc_pattern>{patterns, n_queries, end, dist}, err);
+    return ref_host(c, PackedRef{words, n_words, n}, k, EdistBest<bitnuc_pattern>{patterns, n_queries, end, dist}, err);
 }
 int bitnuc_kmer_pattern_edist_count_multi_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const bitnuc_pattern *d_patterns, const uint32_t *d_taus, size_t n_queries,
                                                 uint64_t *d_counts, bitnuc_err *err) {
-    return kmer_edist_async(c, d_ref, n, k, EdistCount<bitnuc_pattern>{d_patterns, d_taus, n_queries, d_counts}, err);
+    return ref_async(c, AsciiRef{d_ref, n}, k, EdistCount<bitnuc_pattern>{d_patterns, d_taus, n_queries, d_counts}, err);
 }
 int bitnuc_kmer_pattern_edist_count_multi_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *d_patterns,
                                                        const uint32_t *d_taus, size_t n_queries, uint64_t *d_counts, bitnuc_err *err) {
-    return kmer_edist_packed_async(c, d_words, n_words, n, k, EdistCount<bitnuc_pattern>{d_patterns, d_taus, n_queries, d_counts}, err);
+    return ref_async(c, PackedRef{d_words, n_words, n}, k, EdistCount<bitnuc_pattern>{d_patterns, d_taus, n_queries, d_counts}, err);
 }
 int bitnuc_kmer_pattern_edist_count_multi(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const bitnuc_pattern *patterns, const uint32_t *taus, size_t n_queries, uint64_t *counts,
                                           bitnuc_err *err) {
-    return kmer_edist_host(c, ref, n, k, EdistCount<bitnuc_pattern>{patterns, taus, n_queries, counts}, err);
+    return ref_host(c, AsciiRef{ref, n}, k, EdistCount<bitnuc_pattern>{patterns, taus, n_queries, counts}, err);
 }
 int bitnuc_kmer_pattern_edist_count_multi_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *patterns, const uint32_t *taus,
                                                  size_t n_queries, uint64_t *counts, bitnuc_err *err) {
-    return kmer_edist_packed_host(c, words, n_words, n, k, EdistCount<bitnuc_pattern>{patterns, taus, n_queries, counts}, err);
+    return ref_host(c, PackedRef{words, n_words, n}, k, EdistCount<bitnuc_pattern>{patterns, taus, n_queries, counts}, err);
 }
 
-// ---- the indel-tolerant hit list: the ends within tau along a reference (kmer_edist_hits_async ... kmer_edist_hits_packed_host above)
+// ---- the indel-tolerant hit list: the ends within tau along a reference
 int bitnuc_kmer_edist_hits_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *d_end, uint8_t *d_hit_dist, size_t cap,
                                  uint64_t *d_n_hits, bitnuc_err *err) {
-    return kmer_edist_hits_async(c, d_ref, n, k, &query, tau, d_end, d_hit_dist, cap, d_n_hits, err);
+    return ref_async(c, AsciiRef{d_ref, n}, k, EdistHits<uint64_t>{&query, tau, d_end, d_hit_dist, cap, d_n_hits}, err);
 }
 int bitnuc_kmer_edist_hits_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *d_end,
                                         uint8_t *d_hit_dist, size_t cap, uint64_t *d_n_hits, bitnuc_err *err) {
-    return kmer_edist_hits_packed_async(c, d_words, n_words, n, k, &query, tau, d_end, d_hit_dist, cap, d_n_hits, err);
+    return ref_async(c, PackedRef{d_words, n_words, n}, k, EdistHits<uint64_t>{&query, tau, d_end, d_hit_dist, cap, d_n_hits}, err);
 }
 int bitnuc_kmer_edist_hits(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *end, uint8_t *hit_dist, size_t cap, uint64_t *n_hits,
                            bitnuc_err *err) {
-    return kmer_edist_hits_host(c, ref, n, k, &query, tau, end, hit_dist, cap, n_hits, err);
+    return ref_host(c, AsciiRef{ref, n}, k, EdistHits<uint64_t>{&query, tau, end, hit_dist, cap, n_hits}, err);
 }
 int bitnuc_kmer_edist_hits_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, uint64_t query, unsigned tau, uint64_t *end, uint8_t *hit_dist,
                                   size_t cap, uint64_t *n_hits, bitnuc_err *err) {
-    return kmer_edist_hits_packed_host(c, words, n_words, n, k, &query, tau, end, hit_dist, cap, n_hits, err);
+    return ref_host(c, PackedRef{words, n_words, n}, k, EdistHits<uint64_t>{&query, tau, end, hit_dist, cap, n_hits}, err);
 }
 int bitnuc_kmer_pattern_edist_hits_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const bitnuc_pattern *pattern, unsigned tau, uint64_t *d_end, uint8_t *d_hit_dist,
                                          size_t cap, uint64_t *d_n_hits, bitnuc_err *err) {
-    return kmer_edist_hits_async(c, d_ref, n, k, pattern, tau, d_end, d_hit_dist, cap, d_n_hits, err);
+    return ref_async(c, AsciiRef{d_ref, n}, k, EdistHits<bitnuc_pattern>{pattern, tau, d_end, d_hit_dist, cap, d_n_hits}, err);
 }
 int bitnuc_kmer_pattern_edist_hits_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *pattern, unsigned tau,
                                                 uint64_t *d_end, uint8_t *d_hit_dist, size_t cap, uint64_t *d_n_hits, bitnuc_err *err) {
-    return kmer_edist_hits_packed_async(c, d_words, n_words, n, k, pattern, tau, d_end, d_hit_dist, cap, d_n_hits, err);
+    return ref_async(c, PackedRef{d_words, n_words, n}, k, EdistHits<bitnuc_pattern>{pattern, tau, d_end, d_hit_dist, cap, d_n_hits}, err);
 }
 int bitnuc_kmer_pattern_edist_hits(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const bitnuc_pattern *pattern, unsigned tau, uint64_t *end, uint8_t *hit_dist, size_t cap,
                                    uint64_t *n_hits, bitnuc_err *err) {
-    return kmer_edist_hits_host(c, ref, n, k, pattern, tau, end, hit_dist, cap, n_hits, err);
+    return ref_host(c, AsciiRef{ref, n}, k, EdistHits<bitnuc_pattern>{pattern, tau, end, hit_dist, cap, n_hits}, err);
 }
 int bitnuc_kmer_pattern_edist_hits_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *pattern, unsigned tau, uint64_t *end,
                                           uint8_t *hit_dist, size_t cap, uint64_t *n_hits, bitnuc_err *err) {
-    return kmer_edist_hits_packed_host(c, words, n_words, n, k, pattern, tau, end, hit_dist, cap, n_hits, err);
+    return ref_host(c, PackedRef{words, n_words, n}, k, EdistHits<bitnuc_pattern>{pattern, tau, end, hit_dist, cap, n_hits}, err);
 }
 
 } // extern "C"

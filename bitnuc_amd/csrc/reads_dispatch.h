@@ -6,7 +6,6 @@
 
 namespace {
 
-template <class HQ> constexpr uintptr_t reads_qmask() { return sizeof(HQ) == 8 ? 7 : 3; } // the queries' alignment: 8 bytes exact, 4 bytes patterns
 inline bool words_ok(const void *p) { return p && !(reinterpret_cast<uintptr_t>(p) & 7); } // packed words and offsets tables: there and 8-byte aligned
 
 // the outputs of a call, or of a chunk in scratch: the best triple and, where the runner-up is asked for, the second one
@@ -435,7 +434,7 @@ int check_reads(const L &in, size_t count, M &match, bool *done, bitnuc_err *err
     const ReadsOut &o = match.o;
     const auto odd = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; };
     if (!o.query || !o.pos || !o.dist || odd(o.query) || odd(o.pos) || (!match.queries && match.nq) ||
-        (reinterpret_cast<uintptr_t>(match.queries) & reads_qmask<typename M::Query>()))
+        (reinterpret_cast<uintptr_t>(match.queries) & query_mask<typename M::Query>()))
         return fail(err, BITNUC_UNSUPPORTED);
     const int n2 = (o.query2 != nullptr) + (o.pos2 != nullptr) + (o.dist2 != nullptr);
     if ((n2 != 3 && (n2 != 0 || match.needs_second())) || odd(o.query2) || odd(o.pos2)) return fail(err, BITNUC_UNSUPPORTED);

@@ -105,10 +105,16 @@ def test_kind_table_names_the_asynchronous_surface():
     assert {k.symbol for k in qp.KINDS if k.host} == {"bitnuc_encode", "bitnuc_kmer_hdist_hits", "bitnuc_kmer_hdist_count_multi_packed"} <= declared
     assert table <= declared
     # the host kinds go through the context: they drain what is pending and use the staging slots
+    # (each names the host skeleton of ref_dispatch.h, which drains after the host-cutoff return and before the chunk loop)
     kmer = _src("kmer.hip")
     for sym in ("bitnuc_kmer_hdist_hits", "bitnuc_kmer_hdist_count_multi_packed"):
         body = kmer[kmer.index(f"int {sym}("):]
-        assert "flush_pending(c, err)" in body[:body.index("\n}\n")], sym
+        assert "return ref_host(c, " in body[:body.index("\n}\n")], sym
+    ref = _src("ref_dispatch.h")
+    body = ref[ref.index("int ref_host("):]
+    body = body[:body.index("\n}\n")]
+    assert body.count("flush_pending(c, err)") == 1 and body.count("on_host(c, ") == 1 and body.count("host_loop(c, ") == 1
+    assert body.index("on_host(c, ") < body.index("return bad >= 0 ?") < body.index("flush_pending(c, err)") < body.index("host_loop(c, ")
     codec = _src("codec.hip")
     body = codec[codec.index("int bitnuc_encode("):]
     assert "flush_pending(c, err)" in body[:body.index("\n}\n")]
