@@ -123,6 +123,22 @@ SIGNATURES = {
     "bitnuc_reads_pattern_edist_anchored_batch_packed_async": (C.c_int, [_P, _P, _P, _P, _SZ, _SZ, _SZ, C.c_int, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
     "bitnuc_reads_pattern_edist_anchored_batch": (C.c_int, [_P, _P, _P, _SZ, _SZ, C.c_int, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
     "bitnuc_reads_pattern_edist_anchored_batch_packed": (C.c_int, [_P, _P, _P, _P, _SZ, _SZ, C.c_int, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_edist_best_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_edist_best_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_edist_best": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_edist_best_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_pattern_edist_best_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_pattern_edist_best_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_pattern_edist_best": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_pattern_edist_best_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_edist_best_batch_async": (C.c_int, [_P, _P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_edist_best_batch_packed_async": (C.c_int, [_P, _P, _P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_edist_best_batch": (C.c_int, [_P, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_edist_best_batch_packed": (C.c_int, [_P, _P, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_pattern_edist_best_batch_async": (C.c_int, [_P, _P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_pattern_edist_best_batch_packed_async": (C.c_int, [_P, _P, _P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_pattern_edist_best_batch": (C.c_int, [_P, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_pattern_edist_best_batch_packed": (C.c_int, [_P, _P, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
     "bitnuc_pattern_from_iupac": (C.c_int, [_P, _SZ, _P, _ERR]),
     "bitnuc_pattern_from_2bit": (C.c_int, [_U64, _SZ, _P, _ERR]),
     "bitnuc_kmer_pattern_count_multi_async": (C.c_int, [_P, _P, _SZ, _SZ, _P, _P, _SZ, _P, _ERR]),

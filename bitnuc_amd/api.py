@@ -816,6 +816,61 @@ class Context:
         return self._reads_anchored(self._lib.bitnuc_reads_pattern_edist_anchored_batch_packed, (_ptr(w), _ptr(woff), _ptr(off), count, int(k), self._anchor(anchor)),
                                     count, patterns, pos_lo, int(pos_hi), second, int(k))
 
+    def _reads_edist_best(self, fn, head, count, queries, second, pattern_k=None):
+        q, nq = self._reads_queries(queries, pattern_k)
+        types = (np.uint32, np.uint32, np.uint8) * (2 if second else 1)
+        out = [np.empty(count, dtype=t) for t in types]
+        ptrs = [_ptr(a) for a in out] + [None] * (6 - len(out))
+        err = L.BitnucErr()
+        if fn(self._h, *head, _ptr(q), nq, *ptrs, C.byref(err)) != L.OK:
+            _raise(err)
+        return tuple(out)
+
+    def reads_edist_best(self, reads, read_len, k, queries, count=None, second=True):
+        """The indel-tolerant best match over the WHOLE read: per read the smallest (edit distance, query, end) over the queries, the EDIT (Levenshtein)
+        distance of a query being that to the best substring of the read (it starts and ends anywhere; reads of up to 2^26 bases), and the smallest over
+        the other queries.  (query, end, dist, second_query, second_end, second_dist); end is one past the last aligned base, counted from the read's
+        start (the start is not reported).  dist is never above reads_hdist_best's.  second=False: the best triple only."""
+        s, read_len, count = self._fixed_reads(reads, read_len, count)
+        return self._reads_edist_best(self._lib.bitnuc_reads_edist_best, (_ptr(s), read_len, count, int(k)), count, queries, second)
+
+    def reads_edist_best_packed(self, words, read_len, count, k, queries, second=True):
+        """reads_edist_best of the packed words encode_fixed writes (ceil(read_len / 32) words per read), without decoding them."""
+        w, read_len, count = self._fixed_words(words, read_len, count)
+        return self._reads_edist_best(self._lib.bitnuc_reads_edist_best_packed, (_ptr(w), read_len, count, int(k)), count, queries, second)
+
+    def reads_pattern_edist_best(self, reads, read_len, k, patterns, count=None, second=True):
+        """reads_edist_best under pattern queries: a read base matches query position i when it is in the position's set."""
+        s, read_len, count = self._fixed_reads(reads, read_len, count)
+        return self._reads_edist_best(self._lib.bitnuc_reads_pattern_edist_best, (_ptr(s), read_len, count, int(k)), count, patterns, second, int(k))
+
+    def reads_pattern_edist_best_packed(self, words, read_len, count, k, patterns, second=True):
+        """reads_pattern_edist_best of the packed words encode_fixed writes, without decoding them."""
+        w, read_len, count = self._fixed_words(words, read_len, count)
+        return self._reads_edist_best(self._lib.bitnuc_reads_pattern_edist_best_packed, (_ptr(w), read_len, count, int(k)), count, patterns, second, int(k))
+
+    def reads_edist_best_batch(self, seq, offsets, k, queries, second=True):
+        """reads_edist_best of a ragged batch (read r is seq[offsets[r]:offsets[r + 1]]): each read against every query over its own whole length; a
+        read shorter than k gets the fill and is neither read nor validated.  Ends are counted from the read's start."""
+        s, off, count = self._ragged_reads(seq, offsets)
+        return self._reads_edist_best(self._lib.bitnuc_reads_edist_best_batch, (_ptr(s), _ptr(off), count, int(k)), count, queries, second)
+
+    def reads_edist_best_batch_packed(self, words, word_offsets, offsets, k, queries, second=True):
+        """reads_edist_best_batch of the packed words encode_batch writes (read r's ceil(len_r / 32) words start at words[word_offsets[r]])."""
+        w, woff, off, count = self._ragged_words(words, word_offsets, offsets)
+        return self._reads_edist_best(self._lib.bitnuc_reads_edist_best_batch_packed, (_ptr(w), _ptr(woff), _ptr(off), count, int(k)), count, queries, second)
+
+    def reads_pattern_edist_best_batch(self, seq, offsets, k, patterns, second=True):
+        """reads_edist_best_batch under pattern queries."""
+        s, off, count = self._ragged_reads(seq, offsets)
+        return self._reads_edist_best(self._lib.bitnuc_reads_pattern_edist_best_batch, (_ptr(s), _ptr(off), count, int(k)), count, patterns, second, int(k))
+
+    def reads_pattern_edist_best_batch_packed(self, words, word_offsets, offsets, k, patterns, second=True):
+        """reads_pattern_edist_best_batch of the packed words encode_batch writes, without decoding them."""
+        w, woff, off, count = self._ragged_words(words, word_offsets, offsets)
+        return self._reads_edist_best(self._lib.bitnuc_reads_pattern_edist_best_batch_packed, (_ptr(w), _ptr(woff), _ptr(off), count, int(k)), count, patterns,
+                                      second, int(k))
+
     def reads_pattern_anchored_batch(self, seq, offsets, k, patterns, pos_lo=0, pos_hi=0, anchor="start", second=True):
         """reads_hdist_anchored_batch under pattern queries (a ragged batch; the range counted from each read's start or end)."""
         s, off, count = self._ragged_reads(seq, offsets)
@@ -1294,6 +1349,61 @@ class Context:
         self._reads_edist_batch_async(self._lib.bitnuc_reads_pattern_edist_anchored_batch_packed_async,
                                       (_dev_ptr(d_words), _dev_ptr(d_word_offsets), _dev_ptr(d_offsets), int(count), int(total_words)), k, d_patterns, n_queries,
                                       (d_best_query, d_best_end, d_best_dist), (d_second_query, d_second_end, d_second_dist), pos_lo, pos_hi, anchor)
+
+    def _reads_edist_best_async(self, fn, head, k, d_queries, n_queries, d_best, d_second):
+        self._call_dev(fn, *head, int(k), _dev_ptr(d_queries), int(n_queries), *(_dev_ptr(a) for a in d_best), *(_dev_ptr(a) for a in d_second))
+
+    def reads_edist_best_async(self, d_reads, read_len, count, k, d_queries, n_queries, d_best_query, d_best_end, d_best_dist, d_second_query=None,
+                               d_second_end=None, d_second_dist=None):
+        """reads_edist_best on device tensors, asynchronous on the context's stream (d_second_*: all three or none); an invalid byte is reported by the
+        next sync()."""
+        self._reads_edist_best_async(self._lib.bitnuc_reads_edist_best_async, (_dev_ptr(d_reads), int(read_len), int(count)), k, d_queries, n_queries,
+                                     (d_best_query, d_best_end, d_best_dist), (d_second_query, d_second_end, d_second_dist))
+
+    def reads_edist_best_packed_async(self, d_words, read_len, count, k, d_queries, n_queries, d_best_query, d_best_end, d_best_dist, d_second_query=None,
+                                      d_second_end=None, d_second_dist=None):
+        """reads_edist_best_async of packed words (ceil(read_len / 32) per read)."""
+        self._reads_edist_best_async(self._lib.bitnuc_reads_edist_best_packed_async, (_dev_ptr(d_words), int(read_len), int(count)), k, d_queries, n_queries,
+                                     (d_best_query, d_best_end, d_best_dist), (d_second_query, d_second_end, d_second_dist))
+
+    def reads_pattern_edist_best_async(self, d_reads, read_len, count, k, d_patterns, n_queries, d_best_query, d_best_end, d_best_dist, d_second_query=None,
+                                       d_second_end=None, d_second_dist=None):
+        """reads_edist_best_async under pattern queries."""
+        self._reads_edist_best_async(self._lib.bitnuc_reads_pattern_edist_best_async, (_dev_ptr(d_reads), int(read_len), int(count)), k, d_patterns, n_queries,
+                                     (d_best_query, d_best_end, d_best_dist), (d_second_query, d_second_end, d_second_dist))
+
+    def reads_pattern_edist_best_packed_async(self, d_words, read_len, count, k, d_patterns, n_queries, d_best_query, d_best_end, d_best_dist,
+                                              d_second_query=None, d_second_end=None, d_second_dist=None):
+        """reads_edist_best_packed_async under pattern queries."""
+        self._reads_edist_best_async(self._lib.bitnuc_reads_pattern_edist_best_packed_async, (_dev_ptr(d_words), int(read_len), int(count)), k, d_patterns,
+                                     n_queries, (d_best_query, d_best_end, d_best_dist), (d_second_query, d_second_end, d_second_dist))
+
+    def reads_edist_best_batch_async(self, d_seq, d_offsets, count, total_bases, k, d_queries, n_queries, d_best_query, d_best_end, d_best_dist,
+                                     d_second_query=None, d_second_end=None, d_second_dist=None):
+        """reads_edist_best_batch on device tensors (the arguments of reads_hdist_best_batch_async and six outputs), asynchronous on the context's stream;
+        the table is trusted and read on the device; an invalid byte is reported by the next sync()."""
+        self._reads_edist_best_async(self._lib.bitnuc_reads_edist_best_batch_async, (_dev_ptr(d_seq), _dev_ptr(d_offsets), int(count), int(total_bases)), k,
+                                     d_queries, n_queries, (d_best_query, d_best_end, d_best_dist), (d_second_query, d_second_end, d_second_dist))
+
+    def reads_edist_best_batch_packed_async(self, d_words, d_word_offsets, d_offsets, count, total_words, k, d_queries, n_queries, d_best_query, d_best_end,
+                                            d_best_dist, d_second_query=None, d_second_end=None, d_second_dist=None):
+        """reads_edist_best_batch_async on the packed words encode_batch_dev writes (8-byte aligned; both tables u64 in device memory, trusted)."""
+        self._reads_edist_best_async(self._lib.bitnuc_reads_edist_best_batch_packed_async,
+                                     (_dev_ptr(d_words), _dev_ptr(d_word_offsets), _dev_ptr(d_offsets), int(count), int(total_words)), k, d_queries, n_queries,
+                                     (d_best_query, d_best_end, d_best_dist), (d_second_query, d_second_end, d_second_dist))
+
+    def reads_pattern_edist_best_batch_async(self, d_seq, d_offsets, count, total_bases, k, d_patterns, n_queries, d_best_query, d_best_end, d_best_dist,
+                                             d_second_query=None, d_second_end=None, d_second_dist=None):
+        """reads_edist_best_batch_async under pattern queries."""
+        self._reads_edist_best_async(self._lib.bitnuc_reads_pattern_edist_best_batch_async, (_dev_ptr(d_seq), _dev_ptr(d_offsets), int(count), int(total_bases)), k,
+                                     d_patterns, n_queries, (d_best_query, d_best_end, d_best_dist), (d_second_query, d_second_end, d_second_dist))
+
+    def reads_pattern_edist_best_batch_packed_async(self, d_words, d_word_offsets, d_offsets, count, total_words, k, d_patterns, n_queries, d_best_query,
+                                                    d_best_end, d_best_dist, d_second_query=None, d_second_end=None, d_second_dist=None):
+        """reads_edist_best_batch_packed_async under pattern queries."""
+        self._reads_edist_best_async(self._lib.bitnuc_reads_pattern_edist_best_batch_packed_async,
+                                     (_dev_ptr(d_words), _dev_ptr(d_word_offsets), _dev_ptr(d_offsets), int(count), int(total_words)), k, d_patterns, n_queries,
+                                     (d_best_query, d_best_end, d_best_dist), (d_second_query, d_second_end, d_second_dist))
 
     def reads_pattern_anchored_batch_async(self, d_seq, d_offsets, count, total_bases, k, d_patterns, n_queries, d_best_query, d_best_pos, d_best_dist,
                                            d_second_query=None, d_second_pos=None, d_second_dist=None, pos_lo=0, pos_hi=0, anchor="start"):

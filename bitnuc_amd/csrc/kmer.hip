@@ -19,6 +19,7 @@
 #include "scan_reads_batch_device.h"
 #include "scan_anchored_device.h"
 #include "scan_edist_device.h"
+#include "scan_edist_best_device.h"
 #include "scan_edist_ref_device.h"
 #include "scan_edist_hits_device.h"
 #include "scan_hist_device.h"
@@ -31,6 +32,7 @@
 #include "reads_anchored_host.h"
 #include "reads_anchored_batch_host.h"
 #include "reads_edist_host.h"
+#include "reads_edist_best_host.h"
 #include "kmer_edist_host.h"
 #include "reads_batch_host.h"
 #include "scan_hist_host.h"
@@ -1369,6 +1371,98 @@ int bitnuc_reads_pattern_edist_anchored_batch_packed(bitnuc_ctx *c, const uint64
                                                      bitnuc_err *err) {
     return reads_edist_batch_packed_host(c, words, word_offsets, offsets, count, k, anchor, pos_lo, pos_hi, patterns, n_queries, best_query, best_end, best_dist, second_query,
                                          second_end, second_dist, err);
+}
+
+// the indel-tolerant best match and runner-up over the whole read (edit distance): fixed, exact queries and their pattern twins; then ragged
+int bitnuc_reads_edist_best_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const uint64_t *d_queries, size_t n_queries,
+                                  uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_end,
+                                  uint8_t *d_second_dist, bitnuc_err *err) {
+    return reads_edist_best_async(c, d_reads, read_len, count, k, d_queries, n_queries, d_best_query, d_best_end, d_best_dist, d_second_query, d_second_end,
+                                  d_second_dist, err);
+}
+int bitnuc_reads_edist_best_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, const uint64_t *d_queries, size_t n_queries,
+                                         uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_end,
+                                         uint8_t *d_second_dist, bitnuc_err *err) {
+    return reads_edist_best_packed_async(c, d_words, read_len, count, k, d_queries, n_queries, d_best_query, d_best_end, d_best_dist, d_second_query, d_second_end,
+                                         d_second_dist, err);
+}
+int bitnuc_reads_edist_best(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, const uint64_t *queries, size_t n_queries, uint32_t *best_query,
+                            uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err) {
+    return reads_edist_best_host(c, reads, read_len, count, k, queries, n_queries, best_query, best_end, best_dist, second_query, second_end, second_dist, err);
+}
+int bitnuc_reads_edist_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
+                                   uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist,
+                                   bitnuc_err *err) {
+    return reads_edist_best_packed_host(c, words, read_len, count, k, queries, n_queries, best_query, best_end, best_dist, second_query, second_end, second_dist, err);
+}
+int bitnuc_reads_pattern_edist_best_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const bitnuc_pattern *d_patterns,
+                                          size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist, uint32_t *d_second_query,
+                                          uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err) {
+    return reads_edist_best_async(c, d_reads, read_len, count, k, d_patterns, n_queries, d_best_query, d_best_end, d_best_dist, d_second_query, d_second_end,
+                                  d_second_dist, err);
+}
+int bitnuc_reads_pattern_edist_best_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, const bitnuc_pattern *d_patterns,
+                                                 size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist, uint32_t *d_second_query,
+                                                 uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err) {
+    return reads_edist_best_packed_async(c, d_words, read_len, count, k, d_patterns, n_queries, d_best_query, d_best_end, d_best_dist, d_second_query, d_second_end,
+                                         d_second_dist, err);
+}
+int bitnuc_reads_pattern_edist_best(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, const bitnuc_pattern *patterns, size_t n_queries,
+                                    uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist,
+                                    bitnuc_err *err) {
+    return reads_edist_best_host(c, reads, read_len, count, k, patterns, n_queries, best_query, best_end, best_dist, second_query, second_end, second_dist, err);
+}
+int bitnuc_reads_pattern_edist_best_packed(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, const bitnuc_pattern *patterns,
+                                           size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_end,
+                                           uint8_t *second_dist, bitnuc_err *err) {
+    return reads_edist_best_packed_host(c, words, read_len, count, k, patterns, n_queries, best_query, best_end, best_dist, second_query, second_end, second_dist, err);
+}
+int bitnuc_reads_edist_best_batch_async(bitnuc_ctx *c, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k,
+                                        const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist,
+                                        uint32_t *d_second_query, uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err) {
+    return reads_edist_best_batch_async(c, d_seq, d_offsets, count, total_bases, k, d_queries, n_queries, d_best_query, d_best_end, d_best_dist, d_second_query,
+                                        d_second_end, d_second_dist, err);
+}
+int bitnuc_reads_edist_best_batch_packed_async(bitnuc_ctx *c, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
+                                               size_t total_words, size_t k, const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end,
+                                               uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err) {
+    return reads_edist_best_batch_packed_async(c, d_words, d_word_offsets, d_offsets, count, total_words, k, d_queries, n_queries, d_best_query, d_best_end, d_best_dist,
+                                               d_second_query, d_second_end, d_second_dist, err);
+}
+int bitnuc_reads_edist_best_batch(bitnuc_ctx *c, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
+                                  uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist,
+                                  bitnuc_err *err) {
+    return reads_edist_best_batch_host(c, seq, offsets, count, k, queries, n_queries, best_query, best_end, best_dist, second_query, second_end, second_dist, err);
+}
+int bitnuc_reads_edist_best_batch_packed(bitnuc_ctx *c, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
+                                         const uint64_t *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query,
+                                         uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err) {
+    return reads_edist_best_batch_packed_host(c, words, word_offsets, offsets, count, k, queries, n_queries, best_query, best_end, best_dist, second_query, second_end,
+                                              second_dist, err);
+}
+int bitnuc_reads_pattern_edist_best_batch_async(bitnuc_ctx *c, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k,
+                                                const bitnuc_pattern *d_patterns, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist,
+                                                uint32_t *d_second_query, uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err) {
+    return reads_edist_best_batch_async(c, d_seq, d_offsets, count, total_bases, k, d_patterns, n_queries, d_best_query, d_best_end, d_best_dist, d_second_query,
+                                        d_second_end, d_second_dist, err);
+}
+int bitnuc_reads_pattern_edist_best_batch_packed_async(bitnuc_ctx *c, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
+                                                       size_t total_words, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries, uint32_t *d_best_query,
+                                                       uint32_t *d_best_end, uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_end,
+                                                       uint8_t *d_second_dist, bitnuc_err *err) {
+    return reads_edist_best_batch_packed_async(c, d_words, d_word_offsets, d_offsets, count, total_words, k, d_patterns, n_queries, d_best_query, d_best_end, d_best_dist,
+                                               d_second_query, d_second_end, d_second_dist, err);
+}
+int bitnuc_reads_pattern_edist_best_batch(bitnuc_ctx *c, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, const bitnuc_pattern *patterns,
+                                          size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_end,
+                                          uint8_t *second_dist, bitnuc_err *err) {
+    return reads_edist_best_batch_host(c, seq, offsets, count, k, patterns, n_queries, best_query, best_end, best_dist, second_query, second_end, second_dist, err);
+}
+int bitnuc_reads_pattern_edist_best_batch_packed(bitnuc_ctx *c, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
+                                                 const bitnuc_pattern *patterns, size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist,
+                                                 uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err) {
+    return reads_edist_best_batch_packed_host(c, words, word_offsets, offsets, count, k, patterns, n_queries, best_query, best_end, best_dist, second_query, second_end,
+                                              second_dist, err);
 }
 
 // ---- pattern queries: a set of bases per position (bitnuc_pattern).  The converters are host code; the twelve entry points behind them are

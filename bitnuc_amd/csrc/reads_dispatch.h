@@ -1,7 +1,8 @@
 // reads_dispatch.h -- the host side of the per-read matchers (bitnuc_reads_*), written once: WHERE the reads are (four layouts), WHAT is computed
-// (three matchers), one chunk loop, and the two skeletons every entry point is an instantiation of (reads_async, reads_host).  Part of kmer.hip, which
+// (four matchers), one chunk loop, and the two skeletons every entry point is an instantiation of (reads_async, reads_host).  Part of kmer.hip, which
 // includes it once, behind its own helpers (dev_queries, host_queries, multi_work, ascii_skip, packed_skip, bounded_grid, fail_invalid_base, ...).
-// Kernels: scan_reads_device.h, scan_reads_batch_device.h, scan_anchored_device.h, scan_edist_device.h; below the host cutoff: reads_*_host.h.
+// Kernels: scan_reads_device.h, scan_reads_batch_device.h, scan_anchored_device.h, scan_edist_device.h, scan_edist_best_device.h; below the host cutoff:
+// reads_*_host.h.
 #pragma once
 
 namespace {
@@ -317,8 +318,34 @@ int launch_reads_edist(bitnuc_ctx *c, const L &in, size_t count, size_t k, int a
     return BITNUC_OK;
 }
 
+// The INDEL-TOLERANT best match and runner-up per read over the WHOLE read (scan_edist_best_device.h): the kernel above with the span's bound lifted, the
+// lane walks its read in pieces of 64 bases.  Context scratch: 16 bytes per query (scratch 10 again).  The ragged policy is the anchored kernel's geometry
+// with the whole read as the window (START, pos_lo = 0, every offset).  count, nq, k >= 1; reads of at most kEdistBestMaxRead bases; fixed: k <= read_len
+template <class L>
+auto edist_best_geom(const L &in, size_t k, size_t nq) {
+    if constexpr (L::ragged)
+        return AnchorBatchGeom{reinterpret_cast<const unsigned long long *>(in.offsets), reinterpret_cast<const unsigned long long *>(in.starts()), 0u, 0u, 0xFFFFFFFFu,
+                               0xFFFFFFFFu, 0u, (unsigned)k, (unsigned)nq, 0u};
+    else return EdistBestGeom{(unsigned long long)in.stride(), (unsigned)in.read_len, (unsigned)k, (unsigned)nq};
+}
+
+template <class L, class HQ>
+int launch_reads_edist_best(bitnuc_ctx *c, const L &in, size_t count, size_t k, const HQ *d_queries, size_t nq, const ReadsOut &o, unsigned long long *slot,
+                            bitnuc_err *err) {
+    if (int st = ensure_scratch(c, 10, nq * kEdistEntry, err)) return st;
+    u32x4 *tabs = reinterpret_cast<u32x4 *>(c->scratch[10]);
+    edist_tables_kernel<<<(unsigned)((nq + 63) / 64), 64, 0, c->stream>>>(dev_queries(d_queries), (unsigned)nq, (unsigned)k, tabs);
+    HIPCHK(hipGetLastError());
+    auto g = edist_best_geom(in, k, nq);
+    const size_t want = (count + kEdistBlock - 1) / kEdistBlock, cap = (size_t)c->num_cu * kEdistBlocksPerCu;
+    reads_edist_best_kernel<L::packed, decltype(g)><<<(unsigned)(want < cap ? want : cap), kEdistBlock, 0, c->stream>>>(
+        reinterpret_cast<const uint8_t *>(in.data), (unsigned long long)count, g, tabs, o.query, o.pos, o.dist, o.query2, o.pos2, o.dist2, slot);
+    HIPCHK(hipGetLastError());
+    return BITNUC_OK;
+}
+
 // ---- what is computed: the matchers.  A matcher holds the call's k, queries and outputs and owns its part of the checks (needs_second, check_range), its
-// no-window rule (no_window, on the layout's longest()), the work its host cutoff is judged on, its host form below the cutoff (small: the index of the
+// no-window rule (no_window, on the layout's longest()), its bound on a validated table's lengths (check_lengths: the ragged host forms), the work its host cutoff is judged on, its host form below the cutoff (small: the index of the
 // first invalid byte, or -1) and its launch over a layout in device memory.  whole_reads: every byte of every read is examined, also in a chunk that
 // holds no window.
 
@@ -329,6 +356,7 @@ template <class HQ> struct BestMatch {
     size_t k; const HQ *queries; size_t nq; ReadsOut o; bool second;
     bool needs_second() const { return second; }
     template <class L> int check_range(const L &, bitnuc_err *) { return BITNUC_OK; }
+    template <class L> int check_lengths(const L &, size_t, bitnuc_err *) const { return BITNUC_OK; }
     bool no_window(uint64_t longest) const { return k == 0 || nq == 0 || longest < k; }
     template <class L> size_t work(const L &in, size_t count) const { return multi_work(in.windows(count, k), nq); } // windows x queries, saturated
     long long small(const FixedAscii &in, size_t count) const {
@@ -374,6 +402,7 @@ template <class HQ, bool EDIT> struct AnchoredMatch {
         if (!L::ragged && nq == 0) offsets = 0;
         return BITNUC_OK;
     }
+    template <class L> int check_lengths(const L &, size_t, bitnuc_err *) const { return BITNUC_OK; }
     // no read of at most `longest` bases can hold a window: a window at offset pos_lo, or pos_lo bases in front of the end, needs k + pos_lo bases; reads
     // are below 2^32 - 1 bases.  (A fixed batch's offsets are 0 exactly when the other terms say so.)
     bool no_window(uint64_t longest) const {
@@ -415,6 +444,58 @@ template <class HQ, bool EDIT> struct AnchoredMatch {
     int launch(bitnuc_ctx *c, const L &dev, size_t count, const HQ *d_queries, const ReadsOut &d, unsigned long long *slot, bitnuc_err *err) const {
         if constexpr (EDIT) return launch_reads_edist(c, dev, count, k, anchor, pos_lo, offsets, d_queries, nq, d, slot, err);
         else return launch_reads_anchored(c, dev, count, k, anchor, pos_lo, offsets, d_queries, nq, d, slot, err);
+    }
+};
+
+// The indel-tolerant best match and runner-up over the WHOLE read: every read of at least k bases has a window, its whole length; a shorter read is neither
+// read nor validated (whole_reads is false: a ragged ASCII chunk without a read of k bases is filled, not validated).  A read of more than
+// BITNUC_EDIST_MAX_READ bases -> UNSUPPORTED (value = its length): fixed on read_len (check_range), ragged host forms at the table check (check_lengths)
+template <class HQ> struct EditBestMatch {
+    using Query = HQ;
+    static constexpr bool whole_reads = false;
+    size_t k; const HQ *queries; size_t nq; ReadsOut o;
+    bool needs_second() const { return false; }
+    template <class L> int check_range(const L &in, bitnuc_err *err) {
+        if constexpr (!L::ragged)
+            if (in.read_len > BITNUC_EDIST_MAX_READ) return fail(err, BITNUC_UNSUPPORTED, in.read_len);
+        return BITNUC_OK;
+    }
+    template <class L> int check_lengths(const L &in, size_t count, bitnuc_err *err) const {
+        for (size_t r = 0; r < count; ++r)
+            if (in.offsets[r + 1] - in.offsets[r] > BITNUC_EDIST_MAX_READ) return fail(err, BITNUC_UNSUPPORTED, in.offsets[r + 1] - in.offsets[r]);
+        return BITNUC_OK;
+    }
+    bool no_window(uint64_t longest) const { return k == 0 || nq == 0 || longest < k; }
+    // (the bases of the reads with a window) x queries, saturated
+    template <class L> size_t work(const L &in, size_t count) const {
+        size_t bases = 0;
+        if constexpr (L::ragged) {
+            for (size_t r = 0; r < count; ++r) {
+                const uint64_t len = in.offsets[r + 1] - in.offsets[r];
+                if (len >= k) bases += (size_t)len; // below 2^58 in all
+            }
+        } else {
+            bases = multi_work(in.read_len, count);
+        }
+        return multi_work(bases, nq);
+    }
+    long long small(const FixedAscii &in, size_t count) const {
+        return reads_edist_best_small(in.data, in.read_len, count, k, host_queries(queries), nq, o.query, o.pos, o.dist, o.query2, o.pos2, o.dist2);
+    }
+    long long small(const FixedPacked &in, size_t count) const {
+        reads_edist_best_packed_small(in.data, in.read_len, count, k, host_queries(queries), nq, o.query, o.pos, o.dist, o.query2, o.pos2, o.dist2);
+        return -1;
+    }
+    long long small(const RaggedAscii &in, size_t count) const {
+        return reads_edist_best_batch_small(in.data, in.offsets, count, k, host_queries(queries), nq, o.query, o.pos, o.dist, o.query2, o.pos2, o.dist2);
+    }
+    long long small(const RaggedPacked &in, size_t count) const {
+        reads_edist_best_batch_packed_small(in.data, in.word_offsets, in.offsets, count, k, host_queries(queries), nq, o.query, o.pos, o.dist, o.query2, o.pos2, o.dist2);
+        return -1;
+    }
+    template <class L>
+    int launch(bitnuc_ctx *c, const L &dev, size_t count, const HQ *d_queries, const ReadsOut &d, unsigned long long *slot, bitnuc_err *err) const {
+        return launch_reads_edist_best(c, dev, count, k, d_queries, nq, d, slot, err);
     }
 };
 
@@ -520,6 +601,7 @@ int reads_host(bitnuc_ctx *c, L in, size_t count, M match, bitnuc_err *err) {
     if constexpr (L::ragged) {
         const BatchFault f = in.check_tables(count);
         if (f.kind) return fail_batch_tables(f, err);
+        if (int st = match.check_lengths(in, count, err)) return st;
         in.bases = in.offsets[count];
     }
     if (match.no_window(in.longest())) { reads_fill_host(count, match.o); return BITNUC_OK; }
@@ -757,6 +839,65 @@ template <class HQ>
 int reads_best_batch_packed_host(bitnuc_ctx *c, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
                                  const HQ *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_pos, uint8_t *best_dist, bitnuc_err *err) {
     return reads_host(c, RaggedPacked{words, word_offsets, offsets}, count, BestMatch<HQ>{k, queries, n_queries, {best_query, best_pos, best_dist}, false}, err);
+}
+
+// the indel-tolerant best match and runner-up over the whole read: fixed ...
+template <class HQ>
+int reads_edist_best_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const HQ *d_queries, size_t n_queries,
+                           uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_end,
+                           uint8_t *d_second_dist, bitnuc_err *err) {
+    const ReadsOut o{d_best_query, d_best_end, d_best_dist, d_second_dist, d_second_query, d_second_end};
+    return reads_async(c, FixedAscii{d_reads, read_len}, count, EditBestMatch<HQ>{k, d_queries, n_queries, o}, err);
+}
+template <class HQ>
+int reads_edist_best_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, const HQ *d_queries, size_t n_queries,
+                                  uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_end,
+                                  uint8_t *d_second_dist, bitnuc_err *err) {
+    const ReadsOut o{d_best_query, d_best_end, d_best_dist, d_second_dist, d_second_query, d_second_end};
+    return reads_async(c, FixedPacked{d_words, read_len}, count, EditBestMatch<HQ>{k, d_queries, n_queries, o}, err);
+}
+template <class HQ>
+int reads_edist_best_host(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, const HQ *queries, size_t n_queries, uint32_t *best_query,
+                          uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err) {
+    const ReadsOut o{best_query, best_end, best_dist, second_dist, second_query, second_end};
+    return reads_host(c, FixedAscii{reads, read_len}, count, EditBestMatch<HQ>{k, queries, n_queries, o}, err);
+}
+template <class HQ>
+int reads_edist_best_packed_host(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, const HQ *queries, size_t n_queries,
+                                 uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist,
+                                 bitnuc_err *err) {
+    const ReadsOut o{best_query, best_end, best_dist, second_dist, second_query, second_end};
+    return reads_host(c, FixedPacked{words, read_len}, count, EditBestMatch<HQ>{k, queries, n_queries, o}, err);
+}
+
+// ... and ragged
+template <class HQ>
+int reads_edist_best_batch_async(bitnuc_ctx *c, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k, const HQ *d_queries,
+                                 size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist, uint32_t *d_second_query,
+                                 uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err) {
+    const ReadsOut o{d_best_query, d_best_end, d_best_dist, d_second_dist, d_second_query, d_second_end};
+    return reads_async(c, RaggedAscii{d_seq, d_offsets, total_bases, total_bases}, count, EditBestMatch<HQ>{k, d_queries, n_queries, o}, err);
+}
+template <class HQ>
+int reads_edist_best_batch_packed_async(bitnuc_ctx *c, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
+                                        size_t total_words, size_t k, const HQ *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end,
+                                        uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err) {
+    const ReadsOut o{d_best_query, d_best_end, d_best_dist, d_second_dist, d_second_query, d_second_end};
+    return reads_async(c, RaggedPacked::on_device(d_words, d_word_offsets, d_offsets, total_words), count, EditBestMatch<HQ>{k, d_queries, n_queries, o}, err);
+}
+template <class HQ>
+int reads_edist_best_batch_host(bitnuc_ctx *c, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, const HQ *queries, size_t n_queries,
+                                uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist,
+                                bitnuc_err *err) {
+    const ReadsOut o{best_query, best_end, best_dist, second_dist, second_query, second_end};
+    return reads_host(c, RaggedAscii{seq, offsets}, count, EditBestMatch<HQ>{k, queries, n_queries, o}, err);
+}
+template <class HQ>
+int reads_edist_best_batch_packed_host(bitnuc_ctx *c, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
+                                       const HQ *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query,
+                                       uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err) {
+    const ReadsOut o{best_query, best_end, best_dist, second_dist, second_query, second_end};
+    return reads_host(c, RaggedPacked{words, word_offsets, offsets}, count, EditBestMatch<HQ>{k, queries, n_queries, o}, err);
 }
 
 } // namespace

@@ -622,6 +622,85 @@ class Context {
             return NucleotideError::from_c(e);
         return b;
     }
+    // the indel-tolerant best match over the WHOLE read (bitnuc_reads_edist_best*, _best_batch*): the edit distance of each query to the best substring of the
+    // read, of any length up to BITNUC_EDIST_MAX_READ bases; ReadsBest::pos holds the END of the alignment, counted from the read's start, one past its last
+    // aligned base; a read shorter than k gets the fill
+    Result<ReadsBest2> reads_edist_best(Bytes reads, size_t read_len, size_t k, const std::vector<uint64_t> &queries) const {
+        const size_t count = read_len ? reads.len / read_len : 0;
+        ReadsBest2 b{reads_outputs(count), reads_outputs(count)};
+        bitnuc_err e;
+        if (bitnuc_reads_edist_best(ctx_, reads.ptr, read_len, count, k, queries.data(), queries.size(), b.best.query.data(), b.best.pos.data(), b.best.dist.data(),
+            b.second.query.data(), b.second.pos.data(), b.second.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
+    Result<ReadsBest2> reads_edist_best_packed(Words words, size_t read_len, size_t count, size_t k, const std::vector<uint64_t> &queries) const {
+        ReadsBest2 b{reads_outputs(count), reads_outputs(count)};
+        bitnuc_err e;
+        if (bitnuc_reads_edist_best_packed(ctx_, words.ptr, read_len, count, k, queries.data(), queries.size(), b.best.query.data(), b.best.pos.data(), b.best.dist.data(),
+            b.second.query.data(), b.second.pos.data(), b.second.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
+    Result<ReadsBest2> reads_pattern_edist_best(Bytes reads, size_t read_len, size_t k, const std::vector<bitnuc_pattern> &patterns) const {
+        const size_t count = read_len ? reads.len / read_len : 0;
+        ReadsBest2 b{reads_outputs(count), reads_outputs(count)};
+        bitnuc_err e;
+        if (bitnuc_reads_pattern_edist_best(ctx_, reads.ptr, read_len, count, k, patterns.data(), patterns.size(), b.best.query.data(), b.best.pos.data(), b.best.dist.data(),
+            b.second.query.data(), b.second.pos.data(), b.second.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
+    Result<ReadsBest2> reads_pattern_edist_best_packed(Words words, size_t read_len, size_t count, size_t k, const std::vector<bitnuc_pattern> &patterns) const {
+        ReadsBest2 b{reads_outputs(count), reads_outputs(count)};
+        bitnuc_err e;
+        if (bitnuc_reads_pattern_edist_best_packed(ctx_, words.ptr, read_len, count, k, patterns.data(), patterns.size(), b.best.query.data(), b.best.pos.data(), b.best.dist.data(),
+            b.second.query.data(), b.second.pos.data(), b.second.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
+    Result<ReadsBest2> reads_edist_best_batch(Bytes seq, const std::vector<uint64_t> &offsets, size_t k, const std::vector<uint64_t> &queries) const {
+        const size_t count = offsets.empty() ? 0 : offsets.size() - 1;
+        if (count && seq.len < offsets.back()) return NucleotideError::invalid_length(seq.len);
+        ReadsBest2 b{reads_outputs(count), reads_outputs(count)};
+        bitnuc_err e;
+        if (bitnuc_reads_edist_best_batch(ctx_, seq.ptr, offsets.data(), count, k, queries.data(), queries.size(), b.best.query.data(), b.best.pos.data(), b.best.dist.data(),
+            b.second.query.data(), b.second.pos.data(), b.second.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
+    Result<ReadsBest2> reads_edist_best_batch_packed(Words words, const std::vector<uint64_t> &word_offsets, const std::vector<uint64_t> &offsets, size_t k, const std::vector<uint64_t> &queries) const {
+        const size_t count = offsets.empty() ? 0 : offsets.size() - 1;
+        if (word_offsets.size() != offsets.size()) return NucleotideError::unsupported();
+        if (count && words.len < word_offsets.back()) return NucleotideError::invalid_length(words.len);
+        ReadsBest2 b{reads_outputs(count), reads_outputs(count)};
+        bitnuc_err e;
+        if (bitnuc_reads_edist_best_batch_packed(ctx_, words.ptr, word_offsets.data(), offsets.data(), count, k, queries.data(), queries.size(), b.best.query.data(), b.best.pos.data(), b.best.dist.data(),
+            b.second.query.data(), b.second.pos.data(), b.second.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
+    Result<ReadsBest2> reads_pattern_edist_best_batch(Bytes seq, const std::vector<uint64_t> &offsets, size_t k, const std::vector<bitnuc_pattern> &patterns) const {
+        const size_t count = offsets.empty() ? 0 : offsets.size() - 1;
+        if (count && seq.len < offsets.back()) return NucleotideError::invalid_length(seq.len);
+        ReadsBest2 b{reads_outputs(count), reads_outputs(count)};
+        bitnuc_err e;
+        if (bitnuc_reads_pattern_edist_best_batch(ctx_, seq.ptr, offsets.data(), count, k, patterns.data(), patterns.size(), b.best.query.data(), b.best.pos.data(), b.best.dist.data(),
+            b.second.query.data(), b.second.pos.data(), b.second.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
+    Result<ReadsBest2> reads_pattern_edist_best_batch_packed(Words words, const std::vector<uint64_t> &word_offsets, const std::vector<uint64_t> &offsets, size_t k, const std::vector<bitnuc_pattern> &patterns) const {
+        const size_t count = offsets.empty() ? 0 : offsets.size() - 1;
+        if (word_offsets.size() != offsets.size()) return NucleotideError::unsupported();
+        if (count && words.len < word_offsets.back()) return NucleotideError::invalid_length(words.len);
+        ReadsBest2 b{reads_outputs(count), reads_outputs(count)};
+        bitnuc_err e;
+        if (bitnuc_reads_pattern_edist_best_batch_packed(ctx_, words.ptr, word_offsets.data(), offsets.data(), count, k, patterns.data(), patterns.size(), b.best.query.data(), b.best.pos.data(), b.best.dist.data(),
+            b.second.query.data(), b.second.pos.data(), b.second.dist.data(), &e) != BITNUC_OK)
+            return NucleotideError::from_c(e);
+        return b;
+    }
     Result<std::vector<uint64_t>> kmer_hdist_hits_packed(Words words, size_t n, size_t k, uint64_t query, unsigned tau, std::vector<uint8_t> *hit_dist = nullptr) const {
         uint64_t total = 0;
         bitnuc_err e;

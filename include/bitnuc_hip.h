@@ -741,8 +741,8 @@ int bitnuc_reads_pattern_best_batch_packed(bitnuc_ctx *ctx, const uint64_t *word
  * query, 0.55 / 0.50 at 8, 4.0 / 3.9 at 64, 31.5 / 30.8 at 512; k = 31, eight offsets (n = 38): 0.39 / 0.17, 1.04 / 0.98, 7.8 / 7.7, 62.3 / 61.7 ms:
  * 0.47 - 1.2 x the time of bitnuc_reads_hdist_anchored*_async on the same arguments at 1 query, 2.0 - 3.5 x at 8, 5.5 - 12.3 x at 64, 7.1 - 18.9 x at 512
  * (another answer: the price of indel tolerance); the pattern twins cost what the exact forms cost.
- * The ragged twins (offsets tables): bitnuc_reads_edist_anchored_batch* below.  Out of scope: the whole-read (unanchored) form, reporting the
- * alignment's start, k > 32 and spans above 64 bases, affine gaps, reverse-complement queries (callers add the reverse complements to the query list
+ * The ragged twins (offsets tables): bitnuc_reads_edist_anchored_batch* below.  The whole-read (unanchored) form, for reads of any length: bitnuc_reads_edist_best* below.  Out of scope: reporting the
+ * alignment's start, k > 32, anchored spans above 64 bases, affine gaps, reverse-complement queries (callers add the reverse complements to the query list
  * themselves). */
 int bitnuc_reads_edist_anchored_async(bitnuc_ctx *ctx, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
                                       const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist,
@@ -813,7 +813,7 @@ int bitnuc_reads_pattern_edist_anchored_packed(bitnuc_ctx *ctx, const uint64_t *
  * to 64 queries, 0.97 (ASCII) and 1.03 - 1.05 (packed) x at 512, where the recurrence is all there is.  On equal-length reads the fixed form above gives
  * the same answers; this form takes 1.00 - 1.01 x (ASCII) and 1.06 - 1.08 x (packed) of its time at 64 queries and more: a fixed-length batch belongs
  * there.
- * Out of scope: a per-read offset table as an argument, spans above 64 bases, the whole-read (unanchored) form, reporting the alignment's start,
+ * Out of scope: a per-read offset table as an argument, anchored spans above 64 bases (the whole read: bitnuc_reads_edist_best_batch* below), reporting the alignment's start,
  * reverse-complement queries. */
 int bitnuc_reads_edist_anchored_batch_async(bitnuc_ctx *ctx, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k, int anchor,
                                             size_t pos_lo, size_t pos_hi, const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end,
@@ -845,6 +845,123 @@ int bitnuc_reads_pattern_edist_anchored_batch_packed(bitnuc_ctx *ctx, const uint
                                                      size_t k, int anchor, size_t pos_lo, size_t pos_hi, const bitnuc_pattern *patterns, size_t n_queries,
                                                      uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_end,
                                                      uint8_t *second_dist, bitnuc_err *err);
+/* ---- INDEL-TOLERANT best match and runner-up per read over the WHOLE read of a fixed-length batch (which of Q adapters, primers or linkers a read carries,
+ * where it ends and with how many edits: an adapter inside a long or merged read, a linker between two barcodes, a primer at an unknown offset, read-through
+ * into the 3' adapter) -- the twin of bitnuc_reads_hdist_best* / _best2* with the EDIT distance of bitnuc_reads_edist_anchored*, the span being the whole
+ * read ----
+ * Arguments: those of bitnuc_reads_hdist_best* (read_len, count, k, queries, n_queries; ASCII or packed) with the six outputs of
+ * bitnuc_reads_edist_anchored*: best_end / second_end hold ends.  Each function below is the twin of the bitnuc_reads_hdist_best* function of the same
+ * suffix (bitnuc_reads_pattern_edist_best*: of bitnuc_reads_pattern_best*).
+ * Distance and results: the definition of the bitnuc_reads_edist_anchored* block with t_1 .. t_n = read_r and n = read_len: D[0][j] = 0, D[i][0] = i,
+ * edist(r, q) = min over 1 <= j <= n of D[k][j], end(r, q) = the smallest such j: one past the last aligned base, counted from the read's start.  The best
+ * triple is the lexicographic minimum of (edist, query, end); the second triple the minimum over the other queries (an equal duplicate query at a higher
+ * index is the runner-up, one query gives the fill in the second triple).  second_query, second_end and second_dist may ALL be NULL: only the best triple
+ * is written; one or two of them NULL -> UNSUPPORTED.  read_len < k, k == 0 or n_queries == 0: every read gets the fill (UINT32_MAX, UINT32_MAX, 0xFF) in
+ * all written outputs (the family's rule, although the distance is defined there).  Deterministic.  Exactly [0, count) of each output is written; the dist
+ * arrays may have any byte offset.
+ * Identities.  On reads of k <= read_len <= 64 bases this form equals bitnuc_reads_edist_anchored*(pos_lo = 0, pos_hi = SIZE_MAX) byte for byte.  The
+ * pattern forms on singleton patterns (bitnuc_pattern_from_2bit) equal the exact forms byte for byte.  best_dist <= the best_dist of
+ * bitnuc_reads_hdist_best* on every read (every window is a substring).  Truncating every read to its first m >= k bases never lowers best_dist.
+ * Validation.  Every byte of every read is validated (read_len >= k); the first invalid byte in buffer order -> INVALID_BASE with its absolute index,
+ * latched once per call for bitnuc_ctx_sync() by the _async forms (outputs then unspecified); the host forms below the cutoff leave the outputs untouched.
+ * A call that writes only fills reads and validates nothing.  (The ASCII kernel loads aligned 4-byte words that hold a byte of a read: at most 3 bytes
+ * before and after the batch are touched, never examined.)  Packed: bits above a read's last base are ignored.
+ * Limits: k <= 32; read_len < 2^32 - 1 and count x 32 ceil(read_len / 32) < 2^58 (UNSUPPORTED, value = read_len); n_queries <= BITNUC_MAX_QUERIES;
+ * read_len > BITNUC_EDIST_MAX_READ -> UNSUPPORTED (value = read_len): the bound keeps (distance, end - 1) one 32-bit running minimum in the kernel's step.
+ * Checks, in order: those of the bitnuc_reads_edist_anchored* block with (5) read as: read_len > BITNUC_EDIST_MAX_READ -> UNSUPPORTED (value = read_len).
+ * Nothing is written on an argument error.
+ * The _async forms have the contract of bitnuc_reads_edist_anchored*_async: device pointers for everything, the context's stream, no host synchronisation
+ * but the growth of context scratch (16 bytes per query; no per-read scratch, no finish kernel), capturable into a hipGraph after a warm-up of THIS call
+ * with the same or larger n_queries; reads and queries are read at every replay.  The host forms are synchronous and judge count x read_len x n_queries
+ * (saturated) against the host cutoff: below it they run on the host (ctx may be NULL), above it through the context in chunks of whole reads; INVALID_BASE
+ * indices stay absolute.
+ * Cost: the vector-ALU kernel of bitnuc_reads_edist_anchored*, one read per lane, the same step of 20 vector instructions per (read, query, base); the lane
+ * walks its read in pieces of 64 bases and carries the columns of four queries from piece to piece; the read is re-read once per four queries.  No LDS, no
+ * atomics but the invalid-byte latch.  Measured on 6,666,667 x 150-base reads, one MI355X (profiles/r22_reads_edist_best.json), ASCII / packed, six
+ * outputs, k = 16 and 31 alike: 0.87 / 0.64 ms at 1 query, 4.03 / 3.91 at 8, 32.0 / 31.1 at 64, 255.7 / 248.7 at 512: 0.499 / 0.486 ps per (read, query,
+ * base), 1.040 - 1.044 (ASCII) and 1.030 - 1.032 (packed) x that of bitnuc_reads_edist_anchored*_async at span 64 in the same queues; 3.8 - 4.2 x the time
+ * of bitnuc_reads_hdist_best*_async on the same arguments at 64 queries and more, 3.1 - 3.4 x at 8, 1.1 - 1.6 x at 1 (another answer: the price of indel
+ * tolerance); the pattern twins cost what the exact forms cost (0.995 - 1.002 x).
+ * Out of scope: the alignment's start (traceback), partial adapters overhanging the 3' end with a minimum-overlap rule, k > 32, affine gaps,
+ * reverse-complement queries. */
+#define BITNUC_EDIST_MAX_READ 67108864 /* 2^26 bases */
+int bitnuc_reads_edist_best_async(bitnuc_ctx *ctx, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const uint64_t *d_queries, size_t n_queries,
+                                  uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_end,
+                                  uint8_t *d_second_dist, bitnuc_err *err);
+int bitnuc_reads_edist_best_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t read_len, size_t count, size_t k, const uint64_t *d_queries, size_t n_queries,
+                                         uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_end,
+                                         uint8_t *d_second_dist, bitnuc_err *err);
+int bitnuc_reads_edist_best(bitnuc_ctx *ctx, const uint8_t *reads, size_t read_len, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
+                            uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist,
+                            bitnuc_err *err);
+int bitnuc_reads_edist_best_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t read_len, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
+                                   uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist,
+                                   bitnuc_err *err);
+/* the pattern twins: a set of bases per query position (bitnuc_pattern); everything else as above */
+int bitnuc_reads_pattern_edist_best_async(bitnuc_ctx *ctx, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const bitnuc_pattern *d_patterns,
+                                          size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist, uint32_t *d_second_query,
+                                          uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_edist_best_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t read_len, size_t count, size_t k, const bitnuc_pattern *d_patterns,
+                                                 size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist, uint32_t *d_second_query,
+                                                 uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_edist_best(bitnuc_ctx *ctx, const uint8_t *reads, size_t read_len, size_t count, size_t k, const bitnuc_pattern *patterns, size_t n_queries,
+                                    uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist,
+                                    bitnuc_err *err);
+int bitnuc_reads_pattern_edist_best_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t read_len, size_t count, size_t k, const bitnuc_pattern *patterns,
+                                           size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_end,
+                                           uint8_t *second_dist, bitnuc_err *err);
+
+/* ---- ... of a RAGGED batch: the layout, tables and checks of bitnuc_reads_hdist_best_batch* with the distance and results of the block above, per read ----
+ * Arguments: those of the bitnuc_reads_hdist_best_batch* / bitnuc_reads_pattern_best_batch* function of the same suffix, which each function below is the
+ * twin of, with the six outputs of the block above.
+ * Distance and results: as above with t_1 .. t_n = read_r, n = len_r = offsets[r + 1] - offsets[r]; ends count from the read's start.  A read with
+ * len_r < k gets the fill, and so does every read when k == 0 or n_queries == 0.
+ * Identities.  On a batch of equal lengths this form equals the fixed form above byte for byte; the other identities of the block above hold per read.
+ * Validation.  A read with len_r >= k has all its bytes validated; the first invalid byte in buffer order -> INVALID_BASE with its absolute index (latched
+ * once per call by the _async forms; the host forms leave the outputs untouched).  A read shorter than k is neither read nor validated (the rule of
+ * bitnuc_reads_edist_anchored_batch*, not that of bitnuc_reads_hdist_best_batch*).  No aligned 4-byte word (packed: 8-byte word) that holds no base of a
+ * read of at least k bases is touched.
+ * Limits: k <= 32, n_queries <= BITNUC_MAX_QUERIES, the totals below 2^58 as in bitnuc_reads_hdist_best_batch*; a read of more than BITNUC_EDIST_MAX_READ
+ * bases -> UNSUPPORTED (value = its length): the host forms judge it when they validate the tables (after the tables' own checks, before the fill and
+ * before any data pointer is looked at); the _async forms TRUST their tables, as their twins do.
+ * Checks, in order: those of the bitnuc_reads_hdist_best_batch* block, with the second triple's rule (all three NULL or none) at the pointer check.
+ * Nothing is written on an argument error.
+ * The _async forms: as above; the tables, the reads and the queries are read on the device at every replay.  The host forms judge (the sum of len_r over
+ * the reads with len_r >= k) x n_queries (saturated) against the host cutoff; above it: chunks of whole reads with rebased tables, absolute indices.
+ * Cost: the kernel above under the ragged layout policy: every lane loads its own read's table entries one trip ahead; the loop over the bases is
+ * wave-uniform over the LONGEST read among the wave's 64, with Eq forced to 0 behind a lane's own length (21.25 vector instructions a step instead of 20);
+ * a wave of equal lengths runs the fixed form's loop.  Measured on one MI355X (the same profile): on 6,666,667 equal-length reads 1.035 - 1.037 (ASCII)
+ * and 1.009 - 1.010 (packed) x the fixed form's time at 64 queries and more; on reads of 100 .. 200 bases (10^9 bases) 1.40 - 1.43 x the time of equal-length
+ * reads of the same total, where the longest read of each wave of 64 consecutive reads predicts 1.41: 46.5 / 44.8 ms at 64 queries, 372 / 359 at 512; 4.6 -
+ * 5.1 x bitnuc_reads_hdist_best_batch*_async there.  Sorting or binning reads by length is the caller's.
+ * Out of scope: as above, and per-read offset tables. */
+int bitnuc_reads_edist_best_batch_async(bitnuc_ctx *ctx, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k,
+                                        const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist,
+                                        uint32_t *d_second_query, uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err);
+int bitnuc_reads_edist_best_batch_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
+                                               size_t total_words, size_t k, const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end,
+                                               uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err);
+int bitnuc_reads_edist_best_batch(bitnuc_ctx *ctx, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
+                                  uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist,
+                                  bitnuc_err *err);
+int bitnuc_reads_edist_best_batch_packed(bitnuc_ctx *ctx, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
+                                         const uint64_t *queries, size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query,
+                                         uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err);
+/* the pattern twins: a set of bases per query position (bitnuc_pattern); everything else as above */
+int bitnuc_reads_pattern_edist_best_batch_async(bitnuc_ctx *ctx, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k,
+                                                const bitnuc_pattern *d_patterns, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist,
+                                                uint32_t *d_second_query, uint32_t *d_second_end, uint8_t *d_second_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_edist_best_batch_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
+                                                       size_t total_words, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries, uint32_t *d_best_query,
+                                                       uint32_t *d_best_end, uint8_t *d_best_dist, uint32_t *d_second_query, uint32_t *d_second_end,
+                                                       uint8_t *d_second_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_edist_best_batch(bitnuc_ctx *ctx, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, const bitnuc_pattern *patterns,
+                                          size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist, uint32_t *second_query, uint32_t *second_end,
+                                          uint8_t *second_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_edist_best_batch_packed(bitnuc_ctx *ctx, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
+                                                 const bitnuc_pattern *patterns, size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist,
+                                                 uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err);
+
 /* The INDEL-TOLERANT search ALONG A REFERENCE: the best match and the count per query by EDIT distance, where bitnuc_kmer_hdist_best* and
  * bitnuc_kmer_hdist_count_multi* use the Hamming distance.  A guide or primer that sits in the reference with one bulge (one inserted or deleted base)
  * is at distance 1 here and at about 3k/4 there.

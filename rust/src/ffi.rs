@@ -201,6 +201,22 @@ extern "C" {
     pub fn bitnuc_reads_pattern_edist_anchored_batch_packed_async(ctx: *mut bitnuc_ctx, d_words: *const u64, d_word_offsets: *const u64, d_offsets: *const u64, count: usize, total_words: usize, k: usize, anchor: c_int, pos_lo: usize, pos_hi: usize, d_patterns: *const bitnuc_pattern, n_queries: usize, d_best_query: *mut u32, d_best_end: *mut u32, d_best_dist: *mut u8, d_second_query: *mut u32, d_second_end: *mut u32, d_second_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_reads_pattern_edist_anchored_batch(ctx: *mut bitnuc_ctx, seq: *const u8, offsets: *const u64, count: usize, k: usize, anchor: c_int, pos_lo: usize, pos_hi: usize, patterns: *const bitnuc_pattern, n_queries: usize, best_query: *mut u32, best_end: *mut u32, best_dist: *mut u8, second_query: *mut u32, second_end: *mut u32, second_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_reads_pattern_edist_anchored_batch_packed(ctx: *mut bitnuc_ctx, words: *const u64, word_offsets: *const u64, offsets: *const u64, count: usize, k: usize, anchor: c_int, pos_lo: usize, pos_hi: usize, patterns: *const bitnuc_pattern, n_queries: usize, best_query: *mut u32, best_end: *mut u32, best_dist: *mut u8, second_query: *mut u32, second_end: *mut u32, second_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_reads_edist_best_async(ctx: *mut bitnuc_ctx, d_reads: *const u8, read_len: usize, count: usize, k: usize, d_queries: *const u64, n_queries: usize, d_best_query: *mut u32, d_best_end: *mut u32, d_best_dist: *mut u8, d_second_query: *mut u32, d_second_end: *mut u32, d_second_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_reads_edist_best_packed_async(ctx: *mut bitnuc_ctx, d_words: *const u64, read_len: usize, count: usize, k: usize, d_queries: *const u64, n_queries: usize, d_best_query: *mut u32, d_best_end: *mut u32, d_best_dist: *mut u8, d_second_query: *mut u32, d_second_end: *mut u32, d_second_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_reads_edist_best(ctx: *mut bitnuc_ctx, reads: *const u8, read_len: usize, count: usize, k: usize, queries: *const u64, n_queries: usize, best_query: *mut u32, best_end: *mut u32, best_dist: *mut u8, second_query: *mut u32, second_end: *mut u32, second_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_reads_edist_best_packed(ctx: *mut bitnuc_ctx, words: *const u64, read_len: usize, count: usize, k: usize, queries: *const u64, n_queries: usize, best_query: *mut u32, best_end: *mut u32, best_dist: *mut u8, second_query: *mut u32, second_end: *mut u32, second_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_reads_pattern_edist_best_async(ctx: *mut bitnuc_ctx, d_reads: *const u8, read_len: usize, count: usize, k: usize, d_patterns: *const bitnuc_pattern, n_queries: usize, d_best_query: *mut u32, d_best_end: *mut u32, d_best_dist: *mut u8, d_second_query: *mut u32, d_second_end: *mut u32, d_second_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_reads_pattern_edist_best_packed_async(ctx: *mut bitnuc_ctx, d_words: *const u64, read_len: usize, count: usize, k: usize, d_patterns: *const bitnuc_pattern, n_queries: usize, d_best_query: *mut u32, d_best_end: *mut u32, d_best_dist: *mut u8, d_second_query: *mut u32, d_second_end: *mut u32, d_second_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_reads_pattern_edist_best(ctx: *mut bitnuc_ctx, reads: *const u8, read_len: usize, count: usize, k: usize, patterns: *const bitnuc_pattern, n_queries: usize, best_query: *mut u32, best_end: *mut u32, best_dist: *mut u8, second_query: *mut u32, second_end: *mut u32, second_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_reads_pattern_edist_best_packed(ctx: *mut bitnuc_ctx, words: *const u64, read_len: usize, count: usize, k: usize, patterns: *const bitnuc_pattern, n_queries: usize, best_query: *mut u32, best_end: *mut u32, best_dist: *mut u8, second_query: *mut u32, second_end: *mut u32, second_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_reads_edist_best_batch_async(ctx: *mut bitnuc_ctx, d_seq: *const u8, d_offsets: *const u64, count: usize, total_bases: usize, k: usize, d_queries: *const u64, n_queries: usize, d_best_query: *mut u32, d_best_end: *mut u32, d_best_dist: *mut u8, d_second_query: *mut u32, d_second_end: *mut u32, d_second_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_reads_edist_best_batch_packed_async(ctx: *mut bitnuc_ctx, d_words: *const u64, d_word_offsets: *const u64, d_offsets: *const u64, count: usize, total_words: usize, k: usize, d_queries: *const u64, n_queries: usize, d_best_query: *mut u32, d_best_end: *mut u32, d_best_dist: *mut u8, d_second_query: *mut u32, d_second_end: *mut u32, d_second_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_reads_edist_best_batch(ctx: *mut bitnuc_ctx, seq: *const u8, offsets: *const u64, count: usize, k: usize, queries: *const u64, n_queries: usize, best_query: *mut u32, best_end: *mut u32, best_dist: *mut u8, second_query: *mut u32, second_end: *mut u32, second_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_reads_edist_best_batch_packed(ctx: *mut bitnuc_ctx, words: *const u64, word_offsets: *const u64, offsets: *const u64, count: usize, k: usize, queries: *const u64, n_queries: usize, best_query: *mut u32, best_end: *mut u32, best_dist: *mut u8, second_query: *mut u32, second_end: *mut u32, second_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_reads_pattern_edist_best_batch_async(ctx: *mut bitnuc_ctx, d_seq: *const u8, d_offsets: *const u64, count: usize, total_bases: usize, k: usize, d_patterns: *const bitnuc_pattern, n_queries: usize, d_best_query: *mut u32, d_best_end: *mut u32, d_best_dist: *mut u8, d_second_query: *mut u32, d_second_end: *mut u32, d_second_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_reads_pattern_edist_best_batch_packed_async(ctx: *mut bitnuc_ctx, d_words: *const u64, d_word_offsets: *const u64, d_offsets: *const u64, count: usize, total_words: usize, k: usize, d_patterns: *const bitnuc_pattern, n_queries: usize, d_best_query: *mut u32, d_best_end: *mut u32, d_best_dist: *mut u8, d_second_query: *mut u32, d_second_end: *mut u32, d_second_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_reads_pattern_edist_best_batch(ctx: *mut bitnuc_ctx, seq: *const u8, offsets: *const u64, count: usize, k: usize, patterns: *const bitnuc_pattern, n_queries: usize, best_query: *mut u32, best_end: *mut u32, best_dist: *mut u8, second_query: *mut u32, second_end: *mut u32, second_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
+    pub fn bitnuc_reads_pattern_edist_best_batch_packed(ctx: *mut bitnuc_ctx, words: *const u64, word_offsets: *const u64, offsets: *const u64, count: usize, k: usize, patterns: *const bitnuc_pattern, n_queries: usize, best_query: *mut u32, best_end: *mut u32, best_dist: *mut u8, second_query: *mut u32, second_end: *mut u32, second_dist: *mut u8, err: *mut bitnuc_err) -> c_int;
     // pattern queries (a set of bases per position): the converters and the twins of count_multi / best / hits
     pub fn bitnuc_pattern_from_iupac(letters: *const u8, k: usize, out: *mut bitnuc_pattern, err: *mut bitnuc_err) -> c_int;
     pub fn bitnuc_pattern_from_2bit(query: u64, k: usize, out: *mut bitnuc_pattern, err: *mut bitnuc_err) -> c_int;
