@@ -723,15 +723,28 @@ struct ScanJob {
     }
 };
 
+// ---- the chunks of an indel-tolerant walk along a reference and the bounded grid that walks them (scan_edist_ref_device.h), for the two launchers
+// below.  `lead`: the columns at the start of the buffer that are run but not reported (the host chunk loops' overlap): at most kEdistRefLead and,
+// packed, whole words; false for any other
+struct EdistRefGrid { unsigned long long nchunks; unsigned blocks; };
+template <bool PACKED>
+bool edist_ref_grid(const bitnuc_ctx *c, size_t n, size_t lead, EdistRefGrid &g) {
+    if (lead >= n || lead > kEdistRefLead || (PACKED && lead % 32)) return false;
+    g.nchunks = (n - lead + kEdistRefChunk - 1) / kEdistRefChunk;
+    const unsigned long long want = (g.nchunks + kEdistRefBlock - 1) / kEdistRefBlock, bound = (unsigned long long)c->num_cu * kEdistRefBlocksPerCu;
+    g.blocks = (unsigned)(want < bound ? want : bound);
+    return true;
+}
+
 // ---- the indel-tolerant search along a reference (scan_edist_ref_device.h): the best match and the count per query by EDIT distance, one
 // launcher for both query kinds.  Context scratch 9 (the Hamming best match's, shared in stream order) holds one 8-byte key per query and
 // behind them one 16-byte table per query (edist_tables_kernel: one form for both kinds); a launch recorded into a hipGraph keeps it (ensure_scratch:
-// warm up with the same n_queries before capturing).  `lead`: the columns at the start of the buffer that are run but not reported (the host chunk
-// loops' overlap, at most kEdistRefLead and, packed, whole words); the best match's ends come back counted from column `lead`.
+// warm up with the same n_queries before capturing).  `lead` as edist_ref_grid takes it; the best match's ends come back counted from column `lead`.
 template <bool PACKED, bool COUNT, class HQ>
 int launch_kmer_edist(bitnuc_ctx *c, const void *data, size_t n, size_t lead, size_t k, const HQ *d_queries, const uint32_t *d_taus, size_t nq,
                       unsigned long long *out, uint8_t *dist, unsigned long long *slot, bitnuc_err *err) {
-    if (lead >= n || lead > kEdistRefLead || (PACKED && lead % 32)) return fail(err, BITNUC_UNSUPPORTED, lead);
+    EdistRefGrid g;
+    if (!edist_ref_grid<PACKED>(c, n, lead, g)) return fail(err, BITNUC_UNSUPPORTED, lead);
     const size_t kbytes = (nq * 8 + 255) & ~(size_t)255;
     if (int st = ensure_scratch(c, 9, kbytes + nq * kEdistEntry, err)) return st;
     unsigned long long *keys = reinterpret_cast<unsigned long long *>(c->scratch[9]);
@@ -740,9 +753,7 @@ int launch_kmer_edist(bitnuc_ctx *c, const void *data, size_t n, size_t lead, si
     else HIPCHK(hipMemsetAsync(keys, 0xFF, nq * sizeof(uint64_t), c->stream));
     edist_tables_kernel<<<(unsigned)((nq + 63) / 64), 64, 0, c->stream>>>(dev_queries(d_queries), (unsigned)nq, (unsigned)k, tabs);
     HIPCHK(hipGetLastError());
-    const unsigned long long lanes = (n - lead + kEdistRefChunk - 1) / kEdistRefChunk, want = (lanes + kEdistRefBlock - 1) / kEdistRefBlock,
-                             cap = (unsigned long long)c->num_cu * kEdistRefBlocksPerCu;
-    kmer_edist_kernel<PACKED, COUNT><<<(unsigned)(want < cap ? want : cap), kEdistRefBlock, 0, c->stream>>>(
+    kmer_edist_kernel<PACKED, COUNT><<<g.blocks, kEdistRefBlock, 0, c->stream>>>(
         reinterpret_cast<const uint8_t *>(data), (unsigned long long)n, (unsigned)lead, (unsigned)k, (unsigned)nq, tabs, d_taus, COUNT ? out : keys, slot);
     HIPCHK(hipGetLastError());
     if constexpr (!COUNT) {
@@ -755,11 +766,12 @@ int launch_kmer_edist(bitnuc_ctx *c, const void *data, size_t n, size_t lead, si
 // ---- the indel-tolerant hit list (scan_edist_hits_device.h): count pass per chunk of kEdistRefChunk ends, the Hamming hit list's scan over the chunks'
 // counts, emit pass.  Context scratch 7 (the Hamming hit list's, shared in stream order) holds the scanned counts, the tiles' offsets and, behind them,
 // the raw counts; a launch recorded into a hipGraph keeps it (ensure_scratch).  The query's table entry is built here and passed by value.  `lead` as
-// in launch_kmer_edist; a.pos_base is the end of the first reported column minus one.
+// edist_ref_grid takes it; a.pos_base is the end of the first reported column minus one.
 template <bool PACKED, class HQ>
 int launch_edist_hits(bitnuc_ctx *c, const void *data, size_t n, size_t lead, size_t k, const HitsArgsT<HQ> &a, unsigned long long *slot, bitnuc_err *err) {
-    if (lead >= n || lead > kEdistRefLead || (PACKED && lead % 32)) return fail(err, BITNUC_UNSUPPORTED, lead);
-    const unsigned long long nch = (n - lead + kEdistRefChunk - 1) / kEdistRefChunk, ntiles = (nch + kHitsTile - 1) / kHitsTile;
+    EdistRefGrid g;
+    if (!edist_ref_grid<PACKED>(c, n, lead, g)) return fail(err, BITNUC_UNSUPPORTED, lead);
+    const unsigned long long nch = g.nchunks, ntiles = (nch + kHitsTile - 1) / kHitsTile;
     const unsigned long long cbytes = (4 * nch + 255) & ~255ull, tbytes = (8 * ntiles + 255) & ~255ull;
     if (int st = ensure_scratch(c, 7, 2 * cbytes + tbytes, err)) return st;
     unsigned *counts = reinterpret_cast<unsigned *>(c->scratch[7]);
@@ -767,14 +779,12 @@ int launch_edist_hits(bitnuc_ctx *c, const void *data, size_t n, size_t lead, si
     unsigned *raw = reinterpret_cast<unsigned *>(c->scratch[7] + cbytes + tbytes);
     const bitnuc_host::EdistPeq p = bitnuc_host::edist_peq(dev_query(a.query), k);
     const u32x4 tab{p.m[0], p.m[1], p.m[2], p.m[3]};
-    const unsigned long long want = (nch + kEdistRefBlock - 1) / kEdistRefBlock, bound = (unsigned long long)c->num_cu * kEdistRefBlocksPerCu;
-    const unsigned grid = (unsigned)(want < bound ? want : bound);
     const uint8_t *bytes = reinterpret_cast<const uint8_t *>(data);
-    kmer_edist_hits_kernel<PACKED, false><<<grid, kEdistRefBlock, 0, c->stream>>>(bytes, (unsigned long long)n, (unsigned)lead, (unsigned)k, tab, a.tau, counts, raw,
+    kmer_edist_hits_kernel<PACKED, false><<<g.blocks, kEdistRefBlock, 0, c->stream>>>(bytes, (unsigned long long)n, (unsigned)lead, (unsigned)k, tab, a.tau, counts, raw,
                                                                                    nullptr, nullptr, nullptr, 0, 0, slot);
     HIPCHK(hits_scan(c, counts, nch, tiles, a.n_hits));
     if (a.cap)
-        kmer_edist_hits_kernel<PACKED, true><<<grid, kEdistRefBlock, 0, c->stream>>>(bytes, (unsigned long long)n, (unsigned)lead, (unsigned)k, tab, a.tau, counts, raw,
+        kmer_edist_hits_kernel<PACKED, true><<<g.blocks, kEdistRefBlock, 0, c->stream>>>(bytes, (unsigned long long)n, (unsigned)lead, (unsigned)k, tab, a.tau, counts, raw,
                                                                                       tiles, a.pos, a.hd, a.cap, a.pos_base, slot);
     HIPCHK(hipGetLastError());
     return BITNUC_OK;

@@ -1,44 +1,23 @@
 // kmer_edist_host.h -- the indel-tolerant k-mer search along a reference below the host cutoff (bitnuc_kmer_edist_best / _count_multi / _hits, their _packed
 // forms and their pattern twins): with E_q(j) the edit distance of query q to the best substring of the sequence that ends at base j (1 <= j <= n, the
 // substring starts anywhere), dist[q] = min_j E_q(j) and end[q] = the first j that attains it; counts[q] = #{ j : E_q(j) <= taus[q] }.  The recurrence
-// is reads_edist_host.h's (edist_peq, the same column step) with 64-bit ends and no 64-column limit; the tests' oracle is the plain DP, so the two are
-// independent.  Plain C++ (no HIP): tests/c/kmer_edist_host_sanitize.cpp runs them under ASan + UBSan.
+// is reads_edist_host.h's edist_walk (with edist_peq and the code and validity helpers next to it), whose ends are size_t; the tests' oracle is the
+// plain DP, so the two are independent.  Plain C++ (no HIP): tests/c/kmer_edist_host_sanitize.cpp runs them under ASan + UBSan.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
 
-#include "reads_edist_host.h" // EdistPeq, edist_peq: the match masks of both query kinds
+#include "reads_edist_host.h" // edist_peq, edist_walk, edist_ascii_code, edist_packed_code, edist_first_invalid
 
 namespace bitnuc_host {
-
-// one query along n >= 1 bases (code_at(j) in 0 .. 3, 0-based), 1 <= k <= 32: on_end(j + 1, D[k][j + 1]) for every j in ascending order
-template <class CodeAt, class OnEnd>
-static inline void kmer_edist_walk(CodeAt code_at, size_t n, size_t k, const EdistPeq &p, OnEnd on_end) {
-    uint32_t pv = ~0u, mv = 0u, score = (uint32_t)k;
-    const unsigned top = (unsigned)k - 1u;
-    for (size_t j = 0; j < n; ++j) {
-        const uint32_t eq = p.m[code_at(j)];
-        const uint32_t xv = eq | mv;
-        const uint32_t xh = (((eq & pv) + pv) ^ pv) | eq;
-        uint32_t ph = mv | ~(xh | pv);
-        uint32_t mh = pv & xh;
-        score += (ph >> top) & 1u;
-        score -= (mh >> top) & 1u;
-        on_end(j + 1, score);
-        ph <<= 1; // no carry-in: D[0][j] = 0
-        mh <<= 1;
-        pv = mh | ~(xv | ph);
-        mv = ph & xv;
-    }
-}
 
 template <class Q, class CodeAt>
 static inline void kmer_edist_best_codes(CodeAt code_at, size_t n, size_t k, const Q *queries, size_t nq, uint64_t *end, uint8_t *dist) {
     for (size_t q = 0; q < nq; ++q) {
         uint32_t bd = ~0u;
         uint64_t be = ~0ull;
-        kmer_edist_walk(code_at, n, k, edist_peq(queries[q], k), [&](size_t j, uint32_t d) {
+        edist_walk(code_at, n, k, edist_peq(queries[q], k), [&](size_t j, uint32_t d) {
             if (d < bd) bd = d, be = j; // ends come in ascending order: the smallest stays
         });
         memcpy(end + q, &be, 8);
@@ -51,48 +30,38 @@ static inline void kmer_edist_count_codes(CodeAt code_at, size_t n, size_t k, co
     for (size_t q = 0; q < nq; ++q) {
         uint64_t cnt = 0;
         const uint32_t tau = taus[q];
-        kmer_edist_walk(code_at, n, k, edist_peq(queries[q], k), [&](size_t, uint32_t d) { cnt += d <= tau; });
+        edist_walk(code_at, n, k, edist_peq(queries[q], k), [&](size_t, uint32_t d) { cnt += d <= tau; });
         counts[q] = cnt;
     }
 }
 
-// the index of the first byte outside ACGTacgt, or -1
-static inline long long kmer_edist_first_invalid(const uint8_t *ref, size_t n) {
-    for (size_t i = 0; i < n; ++i) {
-        const unsigned u = ref[i] & 0xDFu;
-        if (u != 'A' && u != 'C' && u != 'G' && u != 'T') return (long long)i;
-    }
-    return -1;
-}
-static inline unsigned kmer_edist_ascii_code(uint8_t b) { return ((b >> 1) ^ (b >> 2)) & 3u; } // A 0, C 1, G 2, T 3, either case
-
 // packed sequence of n bases (1 <= k <= min(n, 32), nq >= 1): end[0 .. nq) and dist[0 .. nq) overwritten; bits above 2n of the last word are never read
 template <class Q>
 static inline void kmer_edist_best_packed_small(const uint64_t *words, size_t n, size_t k, const Q *queries, size_t nq, uint64_t *end, uint8_t *dist) {
-    kmer_edist_best_codes([&](size_t j) { return (unsigned)((words[j / 32] >> (2 * (j % 32))) & 3u); }, n, k, queries, nq, end, dist);
+    kmer_edist_best_codes([&](size_t j) { return edist_packed_code(words, j); }, n, k, queries, nq, end, dist);
 }
 
 // ASCII sequence of n bytes (the same conditions): -1 with the outputs overwritten, or the index of the first invalid byte among all n (outputs untouched)
 template <class Q>
 static inline long long kmer_edist_best_small(const uint8_t *ref, size_t n, size_t k, const Q *queries, size_t nq, uint64_t *end, uint8_t *dist) {
-    const long long bad = kmer_edist_first_invalid(ref, n);
+    const long long bad = edist_first_invalid(ref, n);
     if (bad >= 0) return bad;
-    kmer_edist_best_codes([&](size_t j) { return kmer_edist_ascii_code(ref[j]); }, n, k, queries, nq, end, dist);
+    kmer_edist_best_codes([&](size_t j) { return edist_ascii_code(ref[j]); }, n, k, queries, nq, end, dist);
     return -1;
 }
 
 template <class Q>
 static inline void kmer_edist_count_multi_packed_small(const uint64_t *words, size_t n, size_t k, const Q *queries, const uint32_t *taus, size_t nq,
                                                        uint64_t *counts) {
-    kmer_edist_count_codes([&](size_t j) { return (unsigned)((words[j / 32] >> (2 * (j % 32))) & 3u); }, n, k, queries, taus, nq, counts);
+    kmer_edist_count_codes([&](size_t j) { return edist_packed_code(words, j); }, n, k, queries, taus, nq, counts);
 }
 
 template <class Q>
 static inline long long kmer_edist_count_multi_small(const uint8_t *ref, size_t n, size_t k, const Q *queries, const uint32_t *taus, size_t nq,
                                                      uint64_t *counts) {
-    const long long bad = kmer_edist_first_invalid(ref, n);
+    const long long bad = edist_first_invalid(ref, n);
     if (bad >= 0) return bad;
-    kmer_edist_count_codes([&](size_t j) { return kmer_edist_ascii_code(ref[j]); }, n, k, queries, taus, nq, counts);
+    kmer_edist_count_codes([&](size_t j) { return edist_ascii_code(ref[j]); }, n, k, queries, taus, nq, counts);
     return -1;
 }
 
@@ -100,7 +69,7 @@ static inline long long kmer_edist_count_multi_small(const uint8_t *ref, size_t 
 template <class Q, class CodeAt>
 static inline uint64_t kmer_edist_hits_codes(CodeAt code_at, size_t n, size_t k, const Q &query, unsigned tau, uint64_t *end, uint8_t *dist, size_t cap) {
     uint64_t hits = 0;
-    kmer_edist_walk(code_at, n, k, edist_peq(query, k), [&](size_t j, uint32_t d) {
+    edist_walk(code_at, n, k, edist_peq(query, k), [&](size_t j, uint32_t d) {
         if (d > tau) return;
         if (hits < cap) {
             const uint64_t e = j;
@@ -116,16 +85,16 @@ static inline uint64_t kmer_edist_hits_codes(CodeAt code_at, size_t n, size_t k,
 template <class Q>
 static inline uint64_t kmer_edist_hits_packed_small(const uint64_t *words, size_t n, size_t k, const Q &query, unsigned tau, uint64_t *end, uint8_t *dist,
                                                     size_t cap) {
-    return kmer_edist_hits_codes([&](size_t j) { return (unsigned)((words[j / 32] >> (2 * (j % 32))) & 3u); }, n, k, query, tau, end, dist, cap);
+    return kmer_edist_hits_codes([&](size_t j) { return edist_packed_code(words, j); }, n, k, query, tau, end, dist, cap);
 }
 
 // ASCII sequence of n bytes (the same conditions): -1 with *n_hits set, or the index of the first invalid byte among all n (outputs untouched)
 template <class Q>
 static inline long long kmer_edist_hits_small(const uint8_t *ref, size_t n, size_t k, const Q &query, unsigned tau, uint64_t *end, uint8_t *dist, size_t cap,
                                               uint64_t *n_hits) {
-    const long long bad = kmer_edist_first_invalid(ref, n);
+    const long long bad = edist_first_invalid(ref, n);
     if (bad >= 0) return bad;
-    *n_hits = kmer_edist_hits_codes([&](size_t j) { return kmer_edist_ascii_code(ref[j]); }, n, k, query, tau, end, dist, cap);
+    *n_hits = kmer_edist_hits_codes([&](size_t j) { return edist_ascii_code(ref[j]); }, n, k, query, tau, end, dist, cap);
     return -1;
 }
 

@@ -1,8 +1,12 @@
-// reads_edist_host.h -- the indel-tolerant anchored best match and runner-up per read below the host cutoff (bitnuc_reads_edist_anchored / _packed and
-// their pattern twins): per read the smallest (edit distance, query, end) over the queries, the edit distance being the Levenshtein distance of the query
-// to the best substring of the read's span [pos_lo, pos_lo + n), and the smallest over the queries other than the winner's.  The same bit-parallel
-// recurrence as the kernel (scan_edist_device.h: Myers 1999 in Hyyro's form, one 32-bit column per (read, query)), in plain C++ for both layouts and both
-// query kinds; the tests' oracle is the plain DP, so the two are independent.  Only the span bytes of each read are read and validated.  Plain C++ (no
+// reads_edist_host.h -- the host side of the edit-distance family, and the indel-tolerant anchored best match and runner-up per read below the host cutoff
+// (bitnuc_reads_edist_anchored / _packed, their _batch forms and their pattern twins).
+// Shared by the three host headers of the family (this one, reads_edist_best_host.h, kmer_edist_host.h), each written once: edist_peq (a query's match
+// masks, for both query kinds), edist_walk (THE column step: the same bit-parallel recurrence as the kernels' edist_step_device.h, Myers 1999 in Hyyro's
+// form, one 32-bit column per (text, query), with a callback per end), edist_ascii_code / edist_packed_code, edist_first_invalid, and edist_read (one read's
+// bases against every query: the top-2 over distinct queries) with edist_store_top2.
+// The anchored match: per read the smallest (edit distance, query, end) over the queries, the edit distance being the Levenshtein distance of the query to
+// the best substring of the read's span [pos_lo, pos_lo + n), and the smallest over the queries other than the winner's.  Plain C++ for both layouts and
+// both query kinds; the tests' oracle is the plain DP, so the two are independent.  Only the span bytes of each read are read and validated.  Plain C++ (no
 // HIP): tests/c/reads_edist_host_sanitize.cpp runs them under ASan + UBSan.
 #pragma once
 #include <stddef.h>
@@ -21,36 +25,53 @@ static inline EdistPeq edist_peq(const PatternSets &p, size_t k) {
 }
 static inline EdistPeq edist_peq(uint64_t q, size_t k) { return edist_peq(pattern_of_2bit(q, k), k); }
 
-// the span's n <= 64 bases (codes[j] in 0 .. 3) against one query of 1 <= k <= 32 positions: dist << 6 | (j - 1) of the smallest D[k][j], 1 <= j <= n, and
-// its first j.  Bits at and above k of the column words are junk that never travels down; only bit k - 1 is tested.
-static inline uint32_t edist_span(const uint8_t *codes, size_t n, size_t k, const EdistPeq &p) {
-    uint32_t pv = ~0u, mv = 0u, score = (uint32_t)k, best = ~0u;
+// one query of 1 <= k <= 32 positions along n >= 1 bases (code_at(j) in 0 .. 3, 0-based): on_end(j + 1, D[k][j + 1]) for every j in ascending order -- THE
+// column step of the host side, whatever the text is (a read's span, a whole read, a reference).  Bits at and above k of the column words are junk that
+// never travels down; only bit k - 1 is tested.
+template <class CodeAt, class OnEnd>
+static inline void edist_walk(CodeAt code_at, size_t n, size_t k, const EdistPeq &p, OnEnd on_end) {
+    uint32_t pv = ~0u, mv = 0u, score = (uint32_t)k;
     const unsigned top = (unsigned)k - 1u;
     for (size_t j = 0; j < n; ++j) {
-        const uint32_t eq = p.m[codes[j]];
+        const uint32_t eq = p.m[code_at(j)];
         const uint32_t xv = eq | mv;
         const uint32_t xh = (((eq & pv) + pv) ^ pv) | eq;
         uint32_t ph = mv | ~(xh | pv);
         uint32_t mh = pv & xh;
         score += (ph >> top) & 1u;
         score -= (mh >> top) & 1u;
-        const uint32_t key = (score << 6) | (uint32_t)j;
-        if (key < best) best = key;
+        on_end(j + 1, score);
         ph <<= 1; // no carry-in: D[0][j] = 0
         mh <<= 1;
         pv = mh | ~(xv | ph);
         mv = ph & xv;
     }
-    return best;
 }
 
-// one read's span codes against every query: the running top-2 over distinct queries (queries come in ascending order, one key each)
-template <class Q>
-static inline ReadsTop2 edist_read(const uint8_t *codes, size_t n, size_t k, size_t pos_lo, const Q *queries, size_t nq) {
+static inline uint8_t edist_ascii_code(uint8_t b) { return (uint8_t)(((b >> 1) ^ (b >> 2)) & 3u); } // A 0, C 1, G 2, T 3, either case
+static inline uint8_t edist_packed_code(const uint64_t *words, size_t j) { return (uint8_t)((words[j / 32] >> (2 * (j % 32))) & 3u); }
+
+// the index of the first byte of s[0, n) outside ACGTacgt, or -1
+static inline long long edist_first_invalid(const uint8_t *s, size_t n) {
+    for (size_t j = 0; j < n; ++j) {
+        const unsigned u = s[j] & 0xDFu;
+        if (u != 'A' && u != 'C' && u != 'G' && u != 'T') return (long long)j;
+    }
+    return -1;
+}
+
+// n >= k bases of a read, the first of them its base `first`, against every query: the running top-2 over distinct queries (queries come in ascending
+// order, one key each: d << 58 | q << 32 | end, end = first + the smallest j with the smallest D[k][j], one past the last aligned base; end < 2^32)
+template <class Q, class CodeAt>
+static inline ReadsTop2 edist_read(CodeAt code_at, size_t n, size_t k, size_t first, const Q *queries, size_t nq) {
     ReadsTop2 t{kReadsTop2None, kReadsTop2None};
     for (size_t q = 0; q < nq; ++q) {
-        const uint32_t m = edist_span(codes, n, k, edist_peq(queries[q], k));
-        const uint64_t c = ((uint64_t)(m >> 6) << 58) | ((uint64_t)q << 32) | (uint64_t)(pos_lo + (m & 63u) + 1u); // the end: one past the last aligned base
+        uint32_t best = ~0u;
+        size_t end = 0;
+        edist_walk(code_at, n, k, edist_peq(queries[q], k), [&](size_t j, uint32_t d) {
+            if (d < best) best = d, end = j; // ends come in ascending order: the first stays
+        });
+        const uint64_t c = ((uint64_t)best << 58) | ((uint64_t)q << 32) | (uint64_t)(first + end);
         if (c < t.best) {
             t.second = t.best;
             t.best = c;
@@ -75,9 +96,8 @@ static inline void reads_edist_anchored_packed_small(const uint64_t *words, size
     reads_best_fill(count, query, end, dist);
     if (query2) reads_best_fill(count, query2, end2, dist2);
     for (size_t r = 0; r < count; ++r) {
-        uint8_t codes[64];
-        for (size_t j = 0; j < n; ++j) codes[j] = (uint8_t)((words[r * wpr + (pos_lo + j) / 32] >> (2 * ((pos_lo + j) % 32))) & 3u);
-        edist_store_top2(edist_read(codes, n, k, pos_lo, queries, nq), r, query, end, dist, query2, end2, dist2);
+        const uint64_t *rw = words + r * wpr;
+        edist_store_top2(edist_read([&](size_t j) { return edist_packed_code(rw, pos_lo + j); }, n, k, pos_lo, queries, nq), r, query, end, dist, query2, end2, dist2);
     }
 }
 
@@ -86,18 +106,15 @@ static inline void reads_edist_anchored_packed_small(const uint64_t *words, size
 template <class Q>
 static inline long long reads_edist_anchored_small(const uint8_t *reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t n, const Q *queries, size_t nq,
                                                    uint32_t *query, uint32_t *end, uint8_t *dist, uint32_t *query2, uint32_t *end2, uint8_t *dist2) {
-    for (size_t r = 0; r < count; ++r)
-        for (size_t j = 0; j < n; ++j) {
-            const unsigned u = reads[r * read_len + pos_lo + j] & 0xDFu;
-            if (u != 'A' && u != 'C' && u != 'G' && u != 'T') return (long long)(r * read_len + pos_lo + j);
-        }
+    for (size_t r = 0; r < count; ++r) {
+        const long long bad = edist_first_invalid(reads + r * read_len + pos_lo, n);
+        if (bad >= 0) return (long long)(r * read_len + pos_lo) + bad;
+    }
     reads_best_fill(count, query, end, dist);
     if (query2) reads_best_fill(count, query2, end2, dist2);
     for (size_t r = 0; r < count; ++r) {
         const uint8_t *s = reads + r * read_len + pos_lo;
-        uint8_t codes[64];
-        for (size_t j = 0; j < n; ++j) codes[j] = (uint8_t)(((s[j] >> 1) ^ (s[j] >> 2)) & 3u); // A 0, C 1, G 2, T 3, either case
-        edist_store_top2(edist_read(codes, n, k, pos_lo, queries, nq), r, query, end, dist, query2, end2, dist2);
+        edist_store_top2(edist_read([&](size_t j) { return edist_ascii_code(s[j]); }, n, k, pos_lo, queries, nq), r, query, end, dist, query2, end2, dist2);
     }
     return -1;
 }
@@ -118,10 +135,8 @@ static inline void reads_edist_anchored_batch_packed_small(const uint64_t *words
         const AnchorWindow w = anchored_batch_window((size_t)(offsets[r + 1] - offsets[r]), k, from_end, pos_lo, pos_hi);
         if (!w.n) continue;
         const uint64_t *rw = words + word_offsets[r];
-        const size_t n = w.n + k - 1;
-        uint8_t codes[64];
-        for (size_t j = 0; j < n; ++j) codes[j] = (uint8_t)((rw[(w.first + j) / 32] >> (2 * ((w.first + j) % 32))) & 3u);
-        edist_store_top2(edist_read(codes, n, k, w.first, queries, nq), r, query, end, dist, query2, end2, dist2);
+        edist_store_top2(edist_read([&](size_t j) { return edist_packed_code(rw, w.first + j); }, w.n + k - 1, k, w.first, queries, nq), r, query, end, dist, query2,
+                         end2, dist2);
     }
 }
 
@@ -135,10 +150,8 @@ static inline long long reads_edist_anchored_batch_small(const uint8_t *seq, con
         const AnchorWindow w = anchored_batch_window((size_t)(offsets[r + 1] - offsets[r]), k, from_end, pos_lo, pos_hi);
         if (!w.n) continue;
         const size_t at = (size_t)offsets[r] + w.first;
-        for (size_t i = 0; i < w.n + k - 1; ++i) {
-            const unsigned u = seq[at + i] & 0xDFu;
-            if (u != 'A' && u != 'C' && u != 'G' && u != 'T') return (long long)(at + i);
-        }
+        const long long bad = edist_first_invalid(seq + at, w.n + k - 1);
+        if (bad >= 0) return (long long)at + bad;
     }
     reads_best_fill(count, query, end, dist);
     if (query2) reads_best_fill(count, query2, end2, dist2);
@@ -146,10 +159,7 @@ static inline long long reads_edist_anchored_batch_small(const uint8_t *seq, con
         const AnchorWindow w = anchored_batch_window((size_t)(offsets[r + 1] - offsets[r]), k, from_end, pos_lo, pos_hi);
         if (!w.n) continue;
         const uint8_t *s = seq + offsets[r] + w.first;
-        const size_t n = w.n + k - 1;
-        uint8_t codes[64];
-        for (size_t j = 0; j < n; ++j) codes[j] = (uint8_t)(((s[j] >> 1) ^ (s[j] >> 2)) & 3u); // A 0, C 1, G 2, T 3, either case
-        edist_store_top2(edist_read(codes, n, k, w.first, queries, nq), r, query, end, dist, query2, end2, dist2);
+        edist_store_top2(edist_read([&](size_t j) { return edist_ascii_code(s[j]); }, w.n + k - 1, k, w.first, queries, nq), r, query, end, dist, query2, end2, dist2);
     }
     return -1;
 }

@@ -2,10 +2,10 @@
 // pattern twins): for every read the smallest (edit distance, query, end) over Q queries, where the edit distance of a query is the Levenshtein distance
 // to the best substring of the read (it starts and ends anywhere in the read), and the smallest over the queries other than the winner's.
 //
-// The kernel of scan_edist_device.h with the span's bound of 64 bases lifted: the same vector-ALU step (edist_queries': Eq from two levels of selects, the
+// The kernel of scan_edist_device.h with the span's bound of 64 bases lifted: the same vector-ALU step (edist_step_device.h's: Eq from two levels of selects, the
 // 32-bit add as the carry chain, one v_lshl_add + v_min for the running key; kEdistInterleave queries side by side, remainders in groups of 2 and 1), ONE
 // READ PER LANE, the lane writes its read's six outputs itself.  What is new: a lane walks its read in PIECES of 64 bases -- the four code registers of the
-// anchored form -- and the column state of the interleaved queries (Pv, Mv, score, running key: EdistCols) is carried from piece to piece instead of
+// anchored form -- and the column state of the interleaved queries (Pv, Mv, score, running key: EdistKeyCols) is carried from piece to piece instead of
 // starting fresh.  For each group of queries the lane walks its whole read again (the read is re-read per group: 64 bytes or two words per 64 x U steps);
 // ASCII bytes are validated in the first group's walk only.  The next piece's loads are issued ahead of the current piece's 64 steps and held raw (17
 // dwords, or two words), aligned and encoded when their turn comes.
@@ -19,7 +19,7 @@
 //
 // Two layouts, one kernel.  Fixed (EdistBestGeom): reads at a stride, all of g.len bases; the loop runs exactly g.len steps for every lane, nothing is
 // masked.  RAGGED (AnchorBatchGeom with pos_lo = 0, START, offsets = 2^32 - 1: the whole read is the window): the lane derives its read from the table
-// entries loaded one trip ahead (anchored_entries, anchored_lane); the loop is wave-uniform over the longest read of the wave (edist_wave_max27), Eq is 0
+// entries loaded one trip ahead (anchored_entries, anchored_lane); the loop is wave-uniform over the longest read of the wave (edist_wave_max<27>), Eq is 0
 // at the steps behind a lane's own length -- the MASKED form of scan_edist_device.h, whose monotonicity argument holds for any length: a column that
 // matches nowhere cannot lower D[k][j], and the running minimum keeps the first end.  A wave of equal lengths branches to the unmasked loop.  A lane whose
 // read is shorter than k loads nothing, runs masked steps on nothing and writes the fill.
@@ -35,8 +35,8 @@ constexpr unsigned long long kEdistBestMaxRead = 1ull << kEdistBestEndBits;
 // stride: bytes (ASCII) or words (packed) per read; len: the bases of every read, k <= len <= 2^26
 struct EdistBestGeom { unsigned long long stride; unsigned len, k, nq; static constexpr bool kRagged = false; };
 
-// the columns of U queries side by side: the match masks (as edist_queries holds them) and the state that travels from piece to piece
-template <int U> struct EdistCols { uint32_t pa[U], pc[U], pg[U], pt[U], pv[U], mv[U], sc[U], key[U]; };
+// the columns of U queries with each query's running key: (score << kEdistBestEndBits) + (the base's index), the smallest score and its first end
+template <int U> struct EdistKeyCols : EdistCols<U> { uint32_t key[U]; };
 
 // a piece's raw loads, held across the previous piece's steps
 struct EdistPieceAscii { uint32_t d[17]; };
@@ -83,10 +83,10 @@ __device__ __forceinline__ void edist_piece_load(const uint64_t *__restrict__ wo
     if (len > 64u * p + 32u) pc.w1 = words[2ull * p + 1ull];
 }
 
-// cnt <= 64 steps (wave-uniform) over a piece whose first base is base j0 of the read: edist_queries' step with the state in c.  MASKED: Eq is 0 at the
+// cnt <= 64 steps (wave-uniform) over a piece whose first base is base j0 of the read: the anchored kernel's loop (edist_eq, edist_step) with the state in c.  MASKED: Eq is 0 at the
 // steps at and behind base `len` of the lane's read
 template <int U, bool MASKED>
-__device__ __forceinline__ void edist_best_steps(const uint32_t (&span)[4], unsigned cnt, unsigned j0, unsigned top, EdistCols<U> &c, unsigned len) {
+__device__ __forceinline__ void edist_best_steps(const uint32_t (&span)[4], unsigned cnt, unsigned j0, unsigned top, EdistKeyCols<U> &c, unsigned len) {
 #pragma unroll
     for (unsigned w = 0; w < 4; ++w) {
         if (16u * w >= cnt) break; // wave-uniform
@@ -102,20 +102,9 @@ __device__ __forceinline__ void edist_best_steps(const uint32_t (&span)[4], unsi
             if constexpr (MASKED) live = j < len ? ~0u : 0u; // once per step, not per query
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                const uint32_t eac = c.pa[u] ^ (c.pc[u] & lo), egt = c.pg[u] ^ (c.pt[u] & lo);
-                uint32_t eq = hi ? egt : eac;
+                uint32_t eq = edist_eq(c, u, lo, hi);
                 if constexpr (MASKED) eq &= live;
-                const uint32_t xv = eq | c.mv[u];
-                const uint32_t xh = (((eq & c.pv[u]) + c.pv[u]) ^ c.pv[u]) | eq;
-                uint32_t ph = c.mv[u] | ~(xh | c.pv[u]);
-                uint32_t mh = c.pv[u] & xh;
-                c.sc[u] += (ph >> top) & 1u;
-                c.sc[u] -= (mh >> top) & 1u;
-                c.key[u] = min(c.key[u], (c.sc[u] << kEdistBestEndBits) + j);
-                ph <<= 1;
-                mh <<= 1;
-                c.pv[u] = mh | ~(xv | ph);
-                c.mv[u] = ph & xv;
+                edist_step(c, u, eq, top, [&](uint32_t sc) { c.key[u] = min(c.key[u], (sc << kEdistBestEndBits) + j); });
             }
         }
     }
@@ -128,13 +117,11 @@ template <int U, bool MASKED, bool PACKED>
 __device__ __forceinline__ void edist_best_queries(const uint8_t *__restrict__ data, unsigned long long base, unsigned len, unsigned nmax, unsigned k,
                                                    const u32x4 *__restrict__ tabs, unsigned q0, unsigned long long &b1, unsigned long long &b2,
                                                    unsigned long long *__restrict__ slot) {
-    EdistCols<U> c;
+    EdistKeyCols<U> c;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-        const u32x4 t = tabs[q0 + u]; // wave-uniform
-        c.pa[u] = t.x, c.pc[u] = t.x ^ t.y, c.pg[u] = t.z, c.pt[u] = t.z ^ t.w; // pc, pt: what the low code bit toggles (A -> C, G -> T)
-        asm volatile("" : "+v"(c.pa[u]), "+v"(c.pc[u]), "+v"(c.pg[u]), "+v"(c.pt[u])); // in VGPRs: a select of two of them is one three-input bit op
-        c.pv[u] = ~0u, c.mv[u] = 0u, c.sc[u] = k, c.key[u] = ~0u;
+        edist_cols_init(c, u, tabs[q0 + u], k);
+        c.key[u] = ~0u;
     }
     const unsigned top = k - 1u;
     const auto bases_of = [len](unsigned p) { return len > 64u * p ? (len - 64u * p < 64u ? len - 64u * p : 64u) : 0u; }; // the lane's bases in piece p
@@ -184,11 +171,7 @@ template <bool MASKED, bool PACKED>
 __device__ __forceinline__ void edist_best_all_queries(const uint8_t *__restrict__ data, unsigned long long base, unsigned len, unsigned nmax, unsigned k, unsigned nq,
                                                        const u32x4 *__restrict__ tabs, unsigned long long &b1, unsigned long long &b2,
                                                        unsigned long long *__restrict__ slot) {
-    unsigned q = 0;
-#pragma unroll 1
-    for (; q + kEdistInterleave <= nq; q += kEdistInterleave) edist_best_queries<kEdistInterleave, MASKED, PACKED>(data, base, len, nmax, k, tabs, q, b1, b2, slot);
-    if (nq - q >= 2u) { edist_best_queries<2, MASKED, PACKED>(data, base, len, nmax, k, tabs, q, b1, b2, slot); q += 2u; }
-    if (nq - q >= 1u) edist_best_queries<1, MASKED, PACKED>(data, base, len, nmax, k, tabs, q, b1, b2, slot);
+    edist_query_groups(nq, [&](auto U, unsigned q0) { edist_best_queries<decltype(U)::value, MASKED, PACKED>(data, base, len, nmax, k, tabs, q0, b1, b2, slot); });
 }
 
 // a key -> the read's triple; all-ones (no query but the winner, no window): the fill
@@ -198,15 +181,6 @@ __device__ __forceinline__ void edist_best_store(unsigned long long key, unsigne
     query[r] = none ? 0xFFFFFFFFu : (uint32_t)(key >> kEdistBestEndBits) & 0xFFFFu;
     end[r] = none ? 0xFFFFFFFFu : ((uint32_t)key & ((1u << kEdistBestEndBits) - 1u)) + 1u;
     dist[r] = none ? (uint8_t)0xFF : (uint8_t)(key >> 42);
-}
-
-// the largest x < 2^27 among the wave's active lanes, as a wave-uniform value: edist_wave_max's binary search over 27 bits, once per trip
-__device__ __forceinline__ unsigned edist_wave_max27(unsigned x) {
-    unsigned m = 0;
-#pragma unroll
-    for (unsigned b = 1u << kEdistBestEndBits; b; b >>= 1)
-        if (__builtin_amdgcn_ballot_w64(x >= (m | b))) m |= b;
-    return m;
 }
 
 // data: the reads (ASCII bytes at any alignment, or 8-byte aligned packed words); count >= 1, 1 <= k <= 32, 1 <= nq <= 65536; tabs: nq entries of
@@ -233,7 +207,7 @@ reads_edist_best_kernel(const uint8_t *__restrict__ data, unsigned long long cou
             const AnchorLane L = anchored_lane<PACKED>(g, ahead);
             const unsigned len = L.n ? L.n + g.k - 1u : 0u; // the read's bases; 0 where it is shorter than k: nothing of it is loaded or validated
             if (r + step < count) ahead = anchored_entries<PACKED>(g, r + step);
-            const unsigned nmax = edist_wave_max27(len); // wave-uniform; 0: no lane of the wave has a window
+            const unsigned nmax = edist_wave_max<kEdistBestEndBits + 1>(len); // wave-uniform; 0: no lane of the wave has a window
             unsigned long long b1 = ~0ull, b2 = ~0ull;
             if (__builtin_amdgcn_ballot_w64(len != nmax) == 0ull) { // a wave of equal lengths: the fixed layout's loop
                 if (nmax) edist_best_all_queries<false, PACKED>(data, L.base, len, nmax, g.k, g.nq, tabs, b1, b2, slot);

@@ -3,6 +3,8 @@
 // distance to the best substring of the read's span [pos_lo, hi_eff + k) (the substring starts and ends anywhere in the span), and the smallest over the
 // queries other than the winner's.
 //
+// A column's start from its table entry, Eq and THE STEP are edist_step_device.h's (the edist_col_* forms: this kernel keeps its columns in arrays of its
+// own), as are the query groups and the wave maximum; the three other kernels of the family share them.
 // A vector-ALU kernel, not a matrix-core product: the bit-parallel recurrence (Myers 1999 in Hyyro's form) carries a 32-bit add through the column of one
 // (read, query) pair at every span base; it is a carry chain, not a contraction.  k <= 32 keeps a column's vertical deltas in two 32-bit registers (Pv,
 // Mv), the span's n <= 64 bases are four registers of 2-bit codes per lane, a query's score and running key are two more.  No LDS, no spill, no atomics but the
@@ -39,14 +41,13 @@
 // relative to a_r; the store adds a_r.  The fixed instantiations' instructions are those of the kernel before it had a second layout.
 #pragma once
 #include "device_prims.h"
+#include "edist_step_device.h"    // edist_col_init, edist_col_eq, edist_col_step, edist_query_groups, edist_wave_max
 #include "scan_anchored_device.h" // the ragged layout: AnchorBatchGeom, AnchorEntries, anchored_entries, anchored_lane
 #include "scan_mfma_device.h"     // PatternSets, pattern_of_2bit, dword_residue, trip_invalid
 
 namespace bitnuc_dev {
 
 constexpr int kEdistBlock = 256;        // four waves, nothing shared between them
-constexpr int kEdistInterleave = 4;     // queries a lane runs side by side through one walk over its span
-constexpr unsigned kEdistEntry = 16;    // bytes of a query's table entry: Peq[4]
 constexpr unsigned kEdistBlocksPerCu = 8; // the grid's bound: reads behind it are walked in a grid-stride loop
 
 // stride: bytes (ASCII) or words (packed) per read; n: the span's bases, k <= n <= 64
@@ -84,7 +85,7 @@ __device__ __forceinline__ uint32_t edist_span_ascii(const uint8_t *a, unsigned 
 #pragma unroll
         for (unsigned e = 0; e < 4; ++e) {
             const unsigned i = 4u * w + e;
-            const unsigned len = n > 4u * i ? (n - 4u * i < 4u ? n - 4u * i : 4u) : 0u; // the span's bytes in this dword: wave-uniform
+            const unsigned len = n > 4u * i ? (n - 4u * i < 4u ? n - 4u * i : 4u) : 0u; // the span's bytes in this dword (wave-uniform in the fixed layout)
             uint32_t x = __builtin_amdgcn_alignbyte(d[i + 1], d[i], sh);
             const uint32_t keep = len >= 4u ? ~0u : (1u << (8u * len)) - 1u;
             x = (x & keep) | (0x41414141u & ~keep);
@@ -119,11 +120,8 @@ __device__ __forceinline__ void edist_queries(const uint32_t (&span)[4], unsigne
     uint32_t pa[U], pc[U], pg[U], pt[U], pv[U], mv[U], sc[U], key[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-        const u32x4 t = tabs[q0 + u]; // wave-uniform
-        pa[u] = t.x, pc[u] = t.x ^ t.y, pg[u] = t.z, pt[u] = t.z ^ t.w; // pc, pt: what the low code bit toggles (A -> C, G -> T)
-        // the masks are wave-uniform and would sit in SGPRs, of which a VALU instruction reads one: in VGPRs a select of two of them is one three-input bit op
-        asm volatile("" : "+v"(pa[u]), "+v"(pc[u]), "+v"(pg[u]), "+v"(pt[u]));
-        pv[u] = ~0u, mv[u] = 0u, sc[u] = k, key[u] = ~0u;
+        edist_col_init(tabs[q0 + u], k, pa[u], pc[u], pg[u], pt[u], pv[u], mv[u], sc[u]);
+        key[u] = ~0u;
     }
     const unsigned top = k - 1u;
 #pragma unroll
@@ -141,20 +139,10 @@ __device__ __forceinline__ void edist_queries(const uint32_t (&span)[4], unsigne
             if constexpr (MASKED) live = j < len ? ~0u : 0u; // once per step, not per query
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                const uint32_t eac = pa[u] ^ (pc[u] & lo), egt = pg[u] ^ (pt[u] & lo);
-                uint32_t eq = hi ? egt : eac;
+                uint32_t eq = edist_col_eq(pa[u], pc[u], pg[u], pt[u], lo, hi);
                 if constexpr (MASKED) eq &= live;
-                const uint32_t xv = eq | mv[u];
-                const uint32_t xh = (((eq & pv[u]) + pv[u]) ^ pv[u]) | eq;
-                uint32_t ph = mv[u] | ~(xh | pv[u]);
-                uint32_t mh = pv[u] & xh;
-                sc[u] += (ph >> top) & 1u;
-                sc[u] -= (mh >> top) & 1u;
-                key[u] = min(key[u], (sc[u] << 6) + j);
-                ph <<= 1;
-                mh <<= 1;
-                pv[u] = mh | ~(xv | ph);
-                mv[u] = ph & xv;
+                uint32_t &ku = key[u];
+                edist_col_step(eq, pv[u], mv[u], sc[u], top, [&ku, j](uint32_t d) { ku = min(ku, (d << 6) + j); });
             }
         }
     }
@@ -179,20 +167,7 @@ __device__ __forceinline__ void edist_store(uint32_t key, unsigned first, unsign
 template <bool MASKED>
 __device__ __forceinline__ void edist_all_queries(const uint32_t (&span)[4], unsigned n, unsigned k, unsigned nq, const u32x4 *__restrict__ tabs, uint32_t &b1,
                                                   uint32_t &b2, unsigned len) {
-    unsigned q = 0;
-#pragma unroll 1
-    for (; q + kEdistInterleave <= nq; q += kEdistInterleave) edist_queries<kEdistInterleave, MASKED>(span, n, k, tabs, q, b1, b2, len);
-    if (nq - q >= 2u) { edist_queries<2, MASKED>(span, n, k, tabs, q, b1, b2, len); q += 2u; }
-    if (nq - q >= 1u) edist_queries<1, MASKED>(span, n, k, tabs, q, b1, b2, len);
-}
-
-// the largest x <= 64 among the wave's active lanes, as a wave-uniform value: a binary search with seven ballots (no cross-lane data path)
-__device__ __forceinline__ unsigned edist_wave_max(unsigned x) {
-    unsigned m = 0;
-#pragma unroll
-    for (unsigned b = 64u; b; b >>= 1)
-        if (__builtin_amdgcn_ballot_w64(x >= (m | b))) m |= b;
-    return m;
+    edist_query_groups(nq, [&](auto U, unsigned q0) { edist_queries<decltype(U)::value, MASKED>(span, n, k, tabs, q0, b1, b2, len); });
 }
 
 // data: the reads (ASCII bytes at any alignment, or 8-byte aligned packed words); count >= 1, 1 <= k <= 32, k <= n <= 64, 1 <= nq <= 65536; tabs: nq entries
@@ -214,7 +189,7 @@ reads_edist_kernel(const uint8_t *__restrict__ data, unsigned long long count, c
                 if (__builtin_expect(trip_invalid(edist_span_ascii(data + at, g.n, span)), 0)) rescan_bytes(data, at, g.n, slot);
             }
             uint32_t b1 = ~0u, b2 = ~0u;
-            unsigned q = 0; // (spelled as before the kernel had a second layout, not through edist_all_queries: the generated code is the same)
+            unsigned q = 0; // (spelled here: through edist_all_queries the fixed instantiations compile to other code)
 #pragma unroll 1
             for (; q + kEdistInterleave <= g.nq; q += kEdistInterleave) edist_queries<kEdistInterleave>(span, g.n, g.k, tabs, q, b1, b2);
             if (g.nq - q >= 2u) { edist_queries<2>(span, g.n, g.k, tabs, q, b1, b2); q += 2u; }
@@ -243,7 +218,7 @@ reads_edist_kernel(const uint8_t *__restrict__ data, unsigned long long count, c
             if (__builtin_amdgcn_ballot_w64(len != g.span) == 0ull) { // every lane has the widest span: the fixed layout's loop
                 edist_all_queries<false>(span, g.span, g.k, g.nq, tabs, b1, b2, 0u);
             } else {
-                const unsigned widest = edist_wave_max(len); // wave-uniform; 0: no lane of the wave has a window
+                const unsigned widest = edist_wave_max<7>(len); // wave-uniform; 0: no lane of the wave has a window
                 if (widest) edist_all_queries<true>(span, widest, g.k, g.nq, tabs, b1, b2, len);
                 if (!len) b1 = b2 = ~0u; // the masked steps of a lane without a span made keys of no window
             }
@@ -254,3 +229,4 @@ reads_edist_kernel(const uint8_t *__restrict__ data, unsigned long long count, c
 }
 
 } // namespace bitnuc_dev
+

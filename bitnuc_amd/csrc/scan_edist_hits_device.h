@@ -26,33 +26,13 @@
 // All position arithmetic is 64-bit.  Deterministic (no atomics but the invalid byte's latch, no ticket, no LDS) and capturable.
 #pragma once
 #include "device_prims.h"
-#include "scan_edist_ref_device.h" // the chunks and trips: kEdistRefChunk ..., edist_ref_load, edist_ref_codes
+#include "scan_edist_ref_device.h" // the chunks and trips: kEdistRefChunk ..., edist_ref_load, edist_ref_codes; the step through edist_step_device.h
 #include "scan_hits_device.h"      // kHitsTile, the scan
 
 namespace bitnuc_dev {
 
-// the emit pass's ASCII codes: the count pass validated (and latched) these bytes
-__device__ __forceinline__ void edist_hits_codes_quiet(const EdistRefRawAscii &r, uint32_t (&codes)[4]) {
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        uint32_t c = 0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            uint32_t unused = 0;
-            c |= enc4(r.v[w][e], unused) << (8 * e);
-        }
-        codes[w] = c;
-    }
-}
-
-// one lane's column and what it reports.  Count: acc = the reported columns with score <= tau.  Emit: rank = where the next hit goes, ebase + (the
-// column's index in the buffer) = its end
-struct EdistHitsState {
-    uint32_t pa, pc, pg, pt; // the match masks: Peq[A], what the low code bit toggles (A -> C), Peq[G], (G -> T)
-    uint32_t pv, mv, sc, tau;
-    uint32_t acc;
-    unsigned long long rank;
-};
+// what one lane reports beside its column (EdistCols<1>).  Count: acc = the reported columns with score <= tau.  Emit: rank = where the next hit goes
+struct EdistHitsState : EdistCols<1> { uint32_t tau, acc; unsigned long long rank; };
 
 // the 64 steps of a trip whose first column has the end e0.  FAST: every column is reported; otherwise those with lo <= (index in the trip) < lo + width
 template <bool EMIT, bool FAST>
@@ -67,31 +47,24 @@ __device__ __forceinline__ void edist_hits_steps(const uint32_t (&codes)[4], uns
             const bool hi = (c & 2u) != 0u;
             c >>= 2;
             const unsigned tl = 16u * w + s;
-            const uint32_t eac = st.pa ^ (st.pc & lowm), egt = st.pg ^ (st.pt & lowm);
-            const uint32_t eq = hi ? egt : eac;
-            const uint32_t xv = eq | st.mv;
-            const uint32_t xh = (((eq & st.pv) + st.pv) ^ st.pv) | eq;
-            uint32_t ph = st.mv | ~(xh | st.pv);
-            uint32_t mh = st.pv & xh;
-            st.sc += (ph >> top) & 1u;
-            st.sc -= (mh >> top) & 1u;
-            bool hit = st.sc <= st.tau;
-            if constexpr (!FAST) hit = hit && (tl - lo) < width;
             if constexpr (EMIT) {
-                if (hit) {
-                    if (st.rank < cap) {
-                        pos[st.rank] = e0 + tl;
-                        if (hd) hd[st.rank] = (uint8_t)st.sc;
+                edist_step(st, 0, edist_eq(st, 0, lowm, hi), top, [&](uint32_t sc) {
+                    bool hit = sc <= st.tau;
+                    if constexpr (!FAST) hit = hit && (tl - lo) < width;
+                    if (hit) {
+                        if (st.rank < cap) {
+                            pos[st.rank] = e0 + tl;
+                            if (hd) hd[st.rank] = (uint8_t)sc;
+                        }
+                        ++st.rank;
                     }
-                    ++st.rank;
-                }
+                });
             } else {
+                edist_step(st, 0, edist_eq(st, 0, lowm, hi), top);
+                bool hit = st.sc[0] <= st.tau;
+                if constexpr (!FAST) hit = hit && (tl - lo) < width;
                 st.acc += hit ? 1u : 0u;
             }
-            ph <<= 1; // no carry-in: D[0][j] = 0
-            mh <<= 1;
-            st.pv = mh | ~(xv | ph);
-            st.mv = ph & xv;
         }
     }
 }
@@ -103,18 +76,15 @@ __device__ __forceinline__ uint32_t edist_hits_walk(const uint8_t *__restrict__ 
                                                     unsigned long long ebase, unsigned long long *__restrict__ pos, uint8_t *__restrict__ hd,
                                                     unsigned long long cap, unsigned long long *__restrict__ slot) {
     EdistHitsState st;
-    st.pa = tab.x, st.pc = tab.x ^ tab.y, st.pg = tab.z, st.pt = tab.z ^ tab.w;
-    // wave-uniform masks would sit in SGPRs, of which a VALU instruction reads one: in VGPRs a select of two of them is one three-input bit op
-    asm volatile("" : "+v"(st.pa), "+v"(st.pc), "+v"(st.pg), "+v"(st.pt));
-    st.pv = ~0u, st.mv = 0u, st.sc = k, st.tau = tau, st.acc = 0u, st.rank = rank;
+    edist_cols_init(st, 0, tab, k);
+    st.tau = tau, st.acc = 0u, st.rank = rank;
     const unsigned top = k - 1u;
     const unsigned units = (unsigned)((r1 - s + kEdistRefTrip - 1) / kEdistRefTrip);
     auto raw = edist_ref_load<PACKED>(data, s, n);
     for (unsigned u = 0; u < units; ++u) {
         const unsigned long long b = s + (unsigned long long)u * kEdistRefTrip;
         uint32_t codes[4];
-        if constexpr (EMIT && !PACKED) edist_hits_codes_quiet(raw, codes);
-        else edist_ref_codes(raw, data, b, n, slot, codes);
+        edist_ref_codes<!EMIT>(raw, data, b, n, slot, codes); // ASCII bytes are validated (and latched) by the count pass only
         if (u + 1u < units) raw = edist_ref_load<PACKED>(data, b + kEdistRefTrip, n); // b + 64 < r1 <= n
         if (b >= r0 && b + kEdistRefTrip <= r1) {
             edist_hits_steps<EMIT, true>(codes, top, st, 0u, 0u, b + ebase, pos, hd, cap);

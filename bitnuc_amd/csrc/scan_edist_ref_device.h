@@ -4,8 +4,8 @@
 //   best:   dist[q] = min over j of E_q(j), end[q] = the smallest j that attains it;
 //   count:  counts[q] = #{ j : E_q(j) <= taus[q] }.
 // This is scan_edist_device.h's distance with the whole reference as the span; the step is the same bit-parallel recurrence (Myers 1999 in Hyyro's
-// form: a column in Pv / Mv, one 32-bit add per base, bit k - 1 of Ph / Mh moves the score), written here a second time so that the per-read kernels
-// stay as they are.  A vector-ALU kernel: the recurrence is a carry chain, not a contraction.
+// form: a column in Pv / Mv, one 32-bit add per base, bit k - 1 of Ph / Mh moves the score): edist_step_device.h's, shared with the per-read kernels
+// and the hit list; the loops around it are this file's.  A vector-ALU kernel: the recurrence is a carry chain, not a contraction.
 //
 // CHUNKS.  The recurrence is sequential along the reference, so the end positions are cut into chunks of kEdistRefChunk = 1024 columns, ONE CHUNK PER
 // LANE.  The lane that owns the (0-based) columns [r0, r1) starts a FRESH column (Pv = ~0, Mv = 0, score = k) kEdistRefLead = 64 columns earlier, at
@@ -34,7 +34,8 @@
 // The grid is bounded (kEdistRefBlocksPerCu workgroups per CU); a lane walks chunks at the grid's stride: 2^29 bases per round of a 256-CU device.
 #pragma once
 #include "device_prims.h"
-#include "scan_edist_device.h" // kEdistInterleave, kEdistEntry, edist_tables_kernel
+#include "edist_step_device.h" // EdistCols, edist_cols_init, edist_eq, edist_step
+#include "scan_edist_device.h" // edist_tables_kernel
 #include "scan_mfma_device.h"  // dword_residue, trip_invalid
 
 namespace bitnuc_dev {
@@ -74,6 +75,7 @@ __device__ __forceinline__ EdistRefRawAscii edist_ref_load_ascii(const uint8_t *
     }
     return r;
 }
+template <bool VALIDATE = true>
 __device__ __forceinline__ void edist_ref_codes(const EdistRefRawAscii &r, const uint8_t *__restrict__ ref, unsigned long long b, unsigned long long n,
                                                 unsigned long long *__restrict__ slot, uint32_t (&codes)[4]) {
     uint32_t bad = 0;
@@ -83,13 +85,13 @@ __device__ __forceinline__ void edist_ref_codes(const EdistRefRawAscii &r, const
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const uint32_t x = r.v[w][e];
-            bad |= dword_residue(x);
+            if constexpr (VALIDATE) bad |= dword_residue(x);
             uint32_t unused = 0;
             c |= enc4(x, unused) << (8 * e);
         }
         codes[w] = c;
     }
-    if (__builtin_expect(trip_invalid(bad), 0)) rescan_bytes(ref, b, n - b < kEdistRefTrip ? (unsigned)(n - b) : kEdistRefTrip, slot);
+    if (VALIDATE && __builtin_expect(trip_invalid(bad), 0)) rescan_bytes(ref, b, n - b < kEdistRefTrip ? (unsigned)(n - b) : kEdistRefTrip, slot);
 }
 
 struct EdistRefRawPacked { unsigned long long w0, w1; };
@@ -101,6 +103,7 @@ __device__ __forceinline__ EdistRefRawPacked edist_ref_load_packed(const uint64_
     r.w1 = n - b > 32ull ? p[1] : 0ull;
     return r;
 }
+template <bool VALIDATE = true>
 __device__ __forceinline__ void edist_ref_codes(const EdistRefRawPacked &r, const uint8_t *, unsigned long long, unsigned long long, unsigned long long *,
                                                 uint32_t (&codes)[4]) {
     codes[0] = (uint32_t)r.w0, codes[1] = (uint32_t)(r.w0 >> 32), codes[2] = (uint32_t)r.w1, codes[3] = (uint32_t)(r.w1 >> 32);
@@ -114,13 +117,9 @@ __device__ __forceinline__ typename EdistRefRaw<PACKED>::type edist_ref_load(con
     else return edist_ref_load_ascii(data, b, n);
 }
 
-// ---- U queries' columns and results of one lane
-template <int U> struct EdistRefState {
-    uint32_t pa[U], pc[U], pg[U], pt[U]; // the match masks: Peq[A], what the low code bit toggles (A -> C), Peq[G], (G -> T)
-    uint32_t pv[U], mv[U], sc[U];
-    uint32_t acc[U]; // best: the smallest (score << kEdistRefStepBits | step) over the reported columns; count: the reported columns with score <= tau
-    uint32_t tau[U];
-};
+// U queries' columns and results of one lane.  acc: best: the smallest (score << kEdistRefStepBits | step) over the reported columns; count: the
+// reported columns with score <= tau
+template <int U> struct EdistRefState : EdistCols<U> { uint32_t acc[U], tau[U]; };
 
 // the 64 steps of a trip.  t0: the walk index of the trip's first step (wave-uniform).  FAST: every column is reported; otherwise those with
 // lo <= (index in the trip) < lo + width, per lane
@@ -139,24 +138,26 @@ __device__ __forceinline__ void edist_ref_steps(const uint32_t (&codes)[4], unsi
             if constexpr (!FAST) off = (tl - lo) < width ? 0u : ~0u;
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                const uint32_t eac = st.pa[u] ^ (st.pc[u] & lowm), egt = st.pg[u] ^ (st.pt[u] & lowm);
-                const uint32_t eq = hi ? egt : eac;
-                const uint32_t xv = eq | st.mv[u];
-                const uint32_t xh = (((eq & st.pv[u]) + st.pv[u]) ^ st.pv[u]) | eq;
-                uint32_t ph = st.mv[u] | ~(xh | st.pv[u]);
-                uint32_t mh = st.pv[u] & xh;
-                st.sc[u] += (ph >> top) & 1u;
-                st.sc[u] -= (mh >> top) & 1u;
                 if constexpr (COUNT) {
+                    // spelled here: through edist_step, in any of the forms tried, kmer_edist_kernel<packed, count> compiles to another order of its step loops
+                    // and measures 1 - 2 % slower
+                    const uint32_t eq = edist_eq(st, u, lowm, hi);
+                    const uint32_t xv = eq | st.mv[u];
+                    const uint32_t xh = (((eq & st.pv[u]) + st.pv[u]) ^ st.pv[u]) | eq;
+                    uint32_t ph = st.mv[u] | ~(xh | st.pv[u]);
+                    uint32_t mh = st.pv[u] & xh;
+                    st.sc[u] += (ph >> top) & 1u;
+                    st.sc[u] -= (mh >> top) & 1u;
                     const uint32_t hit = st.sc[u] <= st.tau[u] ? 1u : 0u;
                     st.acc[u] += FAST ? hit : (hit & ~off);
+                    ph <<= 1; // no carry-in: D[0][j] = 0
+                    mh <<= 1;
+                    st.pv[u] = mh | ~(xv | ph);
+                    st.mv[u] = ph & xv;
                 } else {
-                    st.acc[u] = min(st.acc[u], ((st.sc[u] << kEdistRefStepBits) + (t0 + tl)) | off);
+                    edist_step(st, u, edist_eq(st, u, lowm, hi), top,
+                               [&](uint32_t sc) { st.acc[u] = min(st.acc[u], ((sc << kEdistRefStepBits) + (t0 + tl)) | off); });
                 }
-                ph <<= 1; // no carry-in: D[0][j] = 0
-                mh <<= 1;
-                st.pv[u] = mh | ~(xv | ph);
-                st.mv[u] = ph & xv;
             }
         }
     }
@@ -172,11 +173,7 @@ __device__ __forceinline__ void edist_ref_queries(const uint8_t *__restrict__ da
     EdistRefState<U> st;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-        const u32x4 t = tabs[q0 + u]; // wave-uniform
-        st.pa[u] = t.x, st.pc[u] = t.x ^ t.y, st.pg[u] = t.z, st.pt[u] = t.z ^ t.w;
-        // the masks are wave-uniform and would sit in SGPRs, of which a VALU instruction reads one: in VGPRs a select of two of them is one three-input bit op
-        asm volatile("" : "+v"(st.pa[u]), "+v"(st.pc[u]), "+v"(st.pg[u]), "+v"(st.pt[u]));
-        st.pv[u] = ~0u, st.mv[u] = 0u, st.sc[u] = k;
+        edist_cols_init(st, u, tabs[q0 + u], k);
         st.acc[u] = COUNT ? 0u : ~0u;
         st.tau[u] = 0u;
         if constexpr (COUNT) st.tau[u] = taus[q0 + u];

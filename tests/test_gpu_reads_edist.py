@@ -24,7 +24,7 @@ GUARD = 8
 FILL32 = 0x5A5A5A5A
 DOFFS = (3, 5)
 OFFS = (0, 1, 7, 15)
-U = 4  # kEdistInterleave (bitnuc_amd/csrc/scan_edist_device.h)
+U = 4  # kEdistInterleave (bitnuc_amd/csrc/edist_step_device.h)
 
 
 def _dev_queries(queries, pattern=False):

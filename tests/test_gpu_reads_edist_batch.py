@@ -32,7 +32,7 @@ DOFFS = (3, 5)
 OFFS = (0, 1, 7, 15)
 START, END = 0, 1
 BOTH = (START, END)
-U = 4  # kEdistInterleave (bitnuc_amd/csrc/scan_edist_device.h)
+U = 4  # kEdistInterleave (bitnuc_amd/csrc/edist_step_device.h)
 
 
 def _dev_u64(a):
