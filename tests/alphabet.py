@@ -31,6 +31,15 @@ KERNEL_CONSTANTS = {
     "kMultiRounds": (4, "scan_multi_device.h"),
     "kMultiQB": (16, "scan_multi_device.h"),      # queries per query block (grid.y)
     "kBatchTile": (64, "batch_device.h"),         # words per wave tile of the read batches
+    # the search kernels of tests/test_gpu_alphabet_search.py (shapes and regions: tests/alphabet_search.py)
+    "kEdistRefChunk": (1024, "scan_edist_ref_device.h"),  # reported columns per lane of the edit-distance search along a reference
+    "kEdistRefLead": (64, "scan_edist_ref_device.h"),     # columns a lane runs in front of its chunk: the lane of the chunk before reads them too
+    "kEdistRefTrip": (64, "scan_edist_ref_device.h"),     # columns per trip: four 16-byte loads, byte by byte in the buffer's last trip
+    "kEdistBlock": (256, "scan_edist_device.h"),          # reads per workgroup of the per-read edit-distance kernels, one per lane
+    "kAnchorBlock": (256, "scan_anchored_device.h"),      # four waves of ...
+    "kAnchorGroups": (2, "scan_anchored_device.h"),       # ... two groups of 32 reads each: 64 reads per wave
+    "kReadsMinPeriod": (32, "scan_reads_device.h"),       # reads shorter than this run no rounds: one window per thread
+    "kEdistInterleave": (4, "edist_step_device.h"),       # queries a lane walks side by side: Q = 5 is a group of four and a group of one
 }
 GROUP = 16     # bytes per lane load: the unit every register-level validator flags and rescan_bytes re-reads
 ROUND = 1024   # bases per line-aligned round (scan_rounds in scan_mfma_host.h: round r reads bytes [1024 r, 1024 r + 1056))

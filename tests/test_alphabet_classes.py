@@ -44,6 +44,18 @@ def test_kernel_constants_match_the_sources():
     assert "nr >= 1056 ? (nr - 32) >> 10 : 0" in host  # scan_rounds
     assert [ab.scan_rounds(n, s) for n, s in ((1055, 0), (1056, 0), (1056, 7), (6509, 0), (6509 + 9, 9))] == [0, 1, 0, 6, 6]
     assert [ab.rounds992(n) for n in (1023, 1024, 2015, 2016, 2300)] == [0, 1, 1, 2, 2]
+    # the search kernels (tests/alphabet_search.py): the chunks, trips, waves and query groups its shapes rest on, and the header's span limit
+    import alphabet_search as als
+    kc = als.KC
+    assert kc["kEdistRefChunk"] % kc["kEdistRefTrip"] == 0 and kc["kEdistRefLead"] % kc["kEdistRefTrip"] == 0 and als.EDIST_REF_N % kc["kEdistRefTrip"]
+    assert kc["kAnchorBlock"] // 64 * als.WAVE == 256 and als.A_COUNT % als.WAVE and als.E_COUNT % kc["kEdistBlock"] and als.E_COUNT > kc["kEdistBlock"]
+    assert als.Q5 % kc["kEdistInterleave"] == 1 and als.Q17 == ab.KERNEL_CONSTANTS["kMultiQB"][0] + 1
+    assert 20 < kc["kReadsMinPeriod"] <= 150
+    header = open(os.path.join(os.path.dirname(csrc), "..", "include", "bitnuc_hip.h")).read()
+    assert int(re.search(r"#define\s+BITNUC_ANCHOR_MAX_SPAN\s+(\d+)", header).group(1)) == als.ANCHOR_MAX_SPAN
+    assert f"the piece of `len` <= {als.PIECE} span bytes" in open(os.path.join(csrc, "scan_anchored_device.h")).read()
+    dwords = re.search(r"struct EdistPieceAscii \{ uint32_t d\[(\d+)\]; \}", open(os.path.join(csrc, "scan_edist_best_device.h")).read()).group(1)
+    assert int(dwords) == als.EDIST_PIECE // 4 + 1  # the aligned dwords that hold a piece of 64 bytes at any alignment
 
 
 REGION_SETS = [
@@ -94,6 +106,69 @@ def test_every_batch_and_scan_path_of_the_gpu_file_has_a_full_plan():
     for k in ("kmer_dense_kernel", "kmer_slide2_kernel", "kmer_slide_any_kernel", "kmer_batch_kernel<true>", "kmer_batch_kernel<false>",
               *[f"kmer_slide_kernel<{s}>" for s in (1, 2, 4, 8, 16)]):
         assert k in kernels, k
+
+
+def _search_specs():
+    import alphabet_search as als
+    for path, (make, make_gap) in als.PATHS.items():
+        yield path, make(), False
+        if make_gap:
+            yield path, make_gap(), True  # (gap_fill asserts its own promise: every value before and behind an owned range at every byte lane)
+
+
+def test_every_search_path_has_a_full_plan():
+    """the paths of tests/test_gpu_alphabet_search.py: every region has a position at each byte lane, the regions partition the owned set, the
+    plan's 992 cases reach every region with every value, owned and foreign positions are disjoint, and the input is valid where it is owned"""
+    import alphabet_search as als
+    names = set()
+    for path, spec, is_gap in _search_specs():
+        assert spec.name not in names, spec.name
+        names.add(spec.name)
+        owned = spec.owned
+        assert owned.size and np.all(np.diff(owned) > 0) and owned[0] >= 0 and owned[-1] < spec.good.size, path
+        assert 1 <= len(spec.regions) <= 4, path
+        for rname, pos in spec.regions:
+            assert {int(p) % 4 for p in pos} == {0, 1, 2, 3}, (path, rname)
+        cat = np.concatenate([pos for _, pos in spec.regions])
+        assert cat.size == owned.size and np.array_equal(np.sort(cat), owned), path  # a partition: nothing twice, nothing left out
+        foreign = np.asarray(spec.foreign)
+        assert not np.intersect1d(foreign, owned).size and len(set(spec.foreign)) == foreign.size, path
+        assert foreign.min() == -16 and foreign.max() == spec.good.size + 31, path  # inside the Src's 256-byte pads
+        assert np.array_equal(np.sort(np.concatenate([foreign[(foreign >= 0) & (foreign < spec.good.size)], owned])), np.arange(spec.good.size)), path
+        assert np.isin(spec.unpolluted[owned], als.VALID).all() and np.array_equal(spec.good[owned], spec.unpolluted[owned]), path
+        if is_gap:
+            assert set(spec.good[foreign[(foreign >= 0) & (foreign < spec.good.size)]].tolist()) == set(range(256)), path
+            continue
+        plan = list(ab.reject_plan(spec.regions))
+        assert len(plan) == 992 and len({(b, p % 4) for b, p, _ in plan}) == 992, path
+        own = set(owned.tolist())
+        for rname, pos in spec.regions:
+            assert {b for b, _, n in plan if n == rname} == set(ab.INVALID), (path, rname)
+        assert all(p in own for _, p, _ in plan), path
+
+
+def test_search_paths_cover_the_entry_points_and_their_expected_values_see_only_owned_bytes(oracle):
+    """every entry point the GPU file promises has a path; want() reports the first invalid OWNED byte and ignores the foreign ones"""
+    import alphabet_search as als
+    fns = {spec.name.split()[0] for _, spec, _ in _search_specs()}
+    assert fns == {"kmer_hdist_best_async", "kmer_hdist_hist_async", "kmer_pattern_hits_async", "kmer_pattern_count_multi_async", "kmer_edist_best_async",
+                   "kmer_edist_count_multi_async", "kmer_edist_hits_async", "reads_hdist_best_async", "reads_hdist_best2_async",
+                   "reads_hdist_best_batch_async", "reads_hdist_anchored_async", "reads_hdist_anchored_batch_async", "reads_edist_anchored_async",
+                   "reads_edist_anchored_batch_async", "reads_pattern_anchored_async", "reads_edist_best_async", "reads_edist_best_batch_async",
+                   "reads_pattern_edist_best_async"}
+    for path in ("reads_edist_anchored_batch-end", "reads_edist_best_batch", "reads_hdist_anchored-span19", "kmer_edist_hits-cap-below-dist-ref+5"):
+        spec = als.PATHS[path][0]()
+        want = spec.want(oracle, spec.good)
+        assert [w.nbytes for w in want] == [nbytes for nbytes, _ in spec.outs][:len(want)] or "hits" in path
+        inside = [p for p in spec.foreign if 0 <= p < spec.good.size]
+        s = spec.good.copy()
+        s[inside] = ord("N")
+        assert all(np.array_equal(a, b) for a, b in zip(want, spec.want(oracle, s))), path
+        a, b = int(spec.owned[spec.owned.size // 3]), int(spec.owned[-1])
+        s[a], s[b] = ord("n"), 0
+        with pytest.raises(oracle.OracleError) as ei:
+            spec.want(oracle, s)
+        assert (ei.value.kind, ei.value.byte, ei.value.index) == ("InvalidBase", ord("n"), a), path
 
 
 def test_reject_plan_refuses_what_it_cannot_cover():

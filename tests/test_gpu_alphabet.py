@@ -125,7 +125,7 @@ def _run(ctx, P):
 def _check_outputs(P, want, tag, fails):
     for i, (o, w) in enumerate(zip(P.outs, want)):
         got, intact = o.read()
-        wb = np.ascontiguousarray(w).view(np.uint8)
+        wb = np.ascontiguousarray(w).reshape(-1).view(np.uint8)  # (an output of any element size and shape, as bytes)
         if not intact:
             fails.append(tag + f": guard bytes around output {i} overwritten")
         if not np.array_equal(got[:wb.size], wb):
