@@ -173,6 +173,30 @@ SIGNATURES = {
     "bitnuc_kmer_pattern_edist_hits_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, C.c_uint, _P, _P, _SZ, _P, _ERR]),
     "bitnuc_kmer_pattern_edist_hits": (C.c_int, [_P, _P, _SZ, _SZ, _P, C.c_uint, _P, _P, _SZ, C.POINTER(_U64), _ERR]),
     "bitnuc_kmer_pattern_edist_hits_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, C.c_uint, _P, _P, _SZ, C.POINTER(_U64), _ERR]),
+    "bitnuc_reads_edist_start_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, C.c_int, _SZ, _P, _SZ, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_edist_start_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, C.c_int, _SZ, _P, _SZ, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_edist_start_batch_async": (C.c_int, [_P, _P, _P, _SZ, _SZ, _SZ, C.c_int, _SZ, _P, _SZ, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_edist_start_batch_packed_async": (C.c_int, [_P, _P, _P, _P, _SZ, _SZ, _SZ, C.c_int, _SZ, _P, _SZ, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_edist_start": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, C.c_int, _SZ, _P, _SZ, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_edist_start_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, C.c_int, _SZ, _P, _SZ, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_edist_start_batch": (C.c_int, [_P, _P, _P, _SZ, _SZ, C.c_int, _SZ, _P, _SZ, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_edist_start_batch_packed": (C.c_int, [_P, _P, _P, _P, _SZ, _SZ, C.c_int, _SZ, _P, _SZ, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_pattern_edist_start_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, C.c_int, _SZ, _P, _SZ, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_pattern_edist_start_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, C.c_int, _SZ, _P, _SZ, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_pattern_edist_start_batch_async": (C.c_int, [_P, _P, _P, _SZ, _SZ, _SZ, C.c_int, _SZ, _P, _SZ, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_pattern_edist_start_batch_packed_async": (C.c_int, [_P, _P, _P, _P, _SZ, _SZ, _SZ, C.c_int, _SZ, _P, _SZ, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_pattern_edist_start": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, C.c_int, _SZ, _P, _SZ, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_pattern_edist_start_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, C.c_int, _SZ, _P, _SZ, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_pattern_edist_start_batch": (C.c_int, [_P, _P, _P, _SZ, _SZ, C.c_int, _SZ, _P, _SZ, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_pattern_edist_start_batch_packed": (C.c_int, [_P, _P, _P, _P, _SZ, _SZ, C.c_int, _SZ, _P, _SZ, _P, _P, _P, _P, _ERR]),
+    "bitnuc_ref_edist_start_async": (C.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _SZ, _P, _P, _P, _ERR]),
+    "bitnuc_ref_edist_start_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _SZ, _P, _P, _P, _ERR]),
+    "bitnuc_ref_edist_start": (C.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _SZ, _P, _P, _ERR]),
+    "bitnuc_ref_edist_start_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _SZ, _P, _P, _ERR]),
+    "bitnuc_ref_pattern_edist_start_async": (C.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _SZ, _P, _P, _P, _ERR]),
+    "bitnuc_ref_pattern_edist_start_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _SZ, _P, _P, _P, _ERR]),
+    "bitnuc_ref_pattern_edist_start": (C.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _SZ, _P, _P, _ERR]),
+    "bitnuc_ref_pattern_edist_start_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _SZ, _P, _P, _ERR]),
     "bitnuc_kmer_hdist_hist_async": (C.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _P, _ERR]),
     "bitnuc_kmer_hdist_hist_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _SZ, _P, _ERR]),
     "bitnuc_kmer_hdist_hist": (C.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _P, _ERR]),

@@ -620,16 +620,18 @@ class Context:
             _raise(err)
         return out
 
-    def kmer_edist_best(self, ref, k, queries):
+    def kmer_edist_best(self, ref, k, queries, with_start=False):
         """The best match per query by EDIT distance: (end, dist) with dist[q] = the smallest E_q(j) over the ends j of `ref` (np.uint8) and end[q] = the
         smallest j that attains it (np.uint64); with k == 0 or len(ref) < k every end is 2^64 - 1 and every dist 255."""
         s = _as_u8(ref)
-        return self._best(self._lib.bitnuc_kmer_edist_best, (_ptr(s), s.size, int(k)), queries)
+        res = self._best(self._lib.bitnuc_kmer_edist_best, (_ptr(s), s.size, int(k)), queries)
+        return res + (self.kmer_edist_start(s, k, queries, res[0], np.arange(len(res[0]), dtype=np.uint32))[0],) if with_start else res
 
-    def kmer_edist_best_packed(self, words, n_bases, k, queries):
+    def kmer_edist_best_packed(self, words, n_bases, k, queries, with_start=False):
         """kmer_edist_best of the packed sequence `words` holding `n_bases` bases, without decoding it."""
         w = _as_u64(words)
-        return self._best(self._lib.bitnuc_kmer_edist_best_packed, (_ptr(w), w.size, int(n_bases), int(k)), queries)
+        res = self._best(self._lib.bitnuc_kmer_edist_best_packed, (_ptr(w), w.size, int(n_bases), int(k)), queries)
+        return res + (self.kmer_edist_start_packed(w, n_bases, k, queries, res[0], np.arange(len(res[0]), dtype=np.uint32))[0],) if with_start else res
 
     def kmer_edist_count_multi(self, ref, k, queries, taus):
         """counts[q] = the number of ends j of `ref` with E_q(j) <= taus[q] (the end positions of approximate occurrences) -> np.uint64"""
@@ -643,15 +645,17 @@ class Context:
         q = np.ascontiguousarray(np.asarray(queries, dtype=np.uint64).reshape(-1))
         return self._edist_count(self._lib.bitnuc_kmer_edist_count_multi_packed, (_ptr(w), w.size, int(n_bases), int(k)), q, q.size, taus)
 
-    def kmer_pattern_edist_best(self, ref, k, patterns):
+    def kmer_pattern_edist_best(self, ref, k, patterns, with_start=False):
         """kmer_edist_best under pattern queries ((Q, 4) np.uint32, or IUPAC strings of length k): a base matches a position when it is in its set."""
         s = _as_u8(ref)
-        return self._pattern_best(self._lib.bitnuc_kmer_pattern_edist_best, (_ptr(s), s.size, int(k)), patterns, k)
+        res = self._pattern_best(self._lib.bitnuc_kmer_pattern_edist_best, (_ptr(s), s.size, int(k)), patterns, k)
+        return res + (self.kmer_pattern_edist_start(s, k, patterns, res[0], np.arange(len(res[0]), dtype=np.uint32))[0],) if with_start else res
 
-    def kmer_pattern_edist_best_packed(self, words, n_bases, k, patterns):
+    def kmer_pattern_edist_best_packed(self, words, n_bases, k, patterns, with_start=False):
         """kmer_pattern_edist_best of the packed sequence `words` holding `n_bases` bases."""
         w = _as_u64(words)
-        return self._pattern_best(self._lib.bitnuc_kmer_pattern_edist_best_packed, (_ptr(w), w.size, int(n_bases), int(k)), patterns, k)
+        res = self._pattern_best(self._lib.bitnuc_kmer_pattern_edist_best_packed, (_ptr(w), w.size, int(n_bases), int(k)), patterns, k)
+        return res + (self.kmer_pattern_edist_start_packed(w, n_bases, k, patterns, res[0], np.arange(len(res[0]), dtype=np.uint32))[0],) if with_start else res
 
     def kmer_pattern_edist_count_multi(self, ref, k, patterns, taus):
         """kmer_edist_count_multi under pattern queries."""
@@ -665,28 +669,44 @@ class Context:
         p = self._patterns(patterns, k)
         return self._edist_count(self._lib.bitnuc_kmer_pattern_edist_count_multi_packed, (_ptr(w), w.size, int(n_bases), int(k)), p, p.shape[0], taus)
 
-    def kmer_edist_hits(self, ref, k, query, tau, with_dist=False):
+    def kmer_edist_hits(self, ref, k, query, tau, with_dist=False, with_start=False):
         """Ends (np.uint64, ascending, 1 <= end <= n: one past the last aligned base) of the substrings of `ref` within edit distance tau of the query: the
         j with E(j) <= tau; with_dist: (ends, np.uint8 distances).  Neighbouring ends of a good match are hits too: the list is not collapsed to minima."""
         s = _as_u8(ref)
-        return self._hits(self._lib.bitnuc_kmer_edist_hits, (_ptr(s), s.size, int(k), C.c_uint64(query), int(tau)), with_dist)
+        res = self._hits(self._lib.bitnuc_kmer_edist_hits, (_ptr(s), s.size, int(k), C.c_uint64(query), int(tau)), with_dist)
+        if not with_start:
+            return res
+        start = self.kmer_edist_start(s, k, [query], res[0] if with_dist else res)[0]
+        return res + (start,) if with_dist else (res, start)
 
-    def kmer_edist_hits_packed(self, words, n_bases, k, query, tau, with_dist=False):
+    def kmer_edist_hits_packed(self, words, n_bases, k, query, tau, with_dist=False, with_start=False):
         """kmer_edist_hits of the packed sequence `words` holding `n_bases` bases, without decoding it."""
         w = _as_u64(words)
-        return self._hits(self._lib.bitnuc_kmer_edist_hits_packed, (_ptr(w), w.size, int(n_bases), int(k), C.c_uint64(query), int(tau)), with_dist)
+        res = self._hits(self._lib.bitnuc_kmer_edist_hits_packed, (_ptr(w), w.size, int(n_bases), int(k), C.c_uint64(query), int(tau)), with_dist)
+        if not with_start:
+            return res
+        start = self.kmer_edist_start_packed(w, n_bases, k, [query], res[0] if with_dist else res)[0]
+        return res + (start,) if with_dist else (res, start)
 
-    def kmer_pattern_edist_hits(self, ref, k, pattern, tau, with_dist=False):
+    def kmer_pattern_edist_hits(self, ref, k, pattern, tau, with_dist=False, with_start=False):
         """kmer_edist_hits under a pattern query (a (4,) np.uint32 array or an IUPAC string of length k)."""
         s = _as_u8(ref)
         p = self._patterns(pattern, k)[:1]
-        return self._hits(self._lib.bitnuc_kmer_pattern_edist_hits, (_ptr(s), s.size, int(k), _ptr(p), int(tau)), with_dist)
+        res = self._hits(self._lib.bitnuc_kmer_pattern_edist_hits, (_ptr(s), s.size, int(k), _ptr(p), int(tau)), with_dist)
+        if not with_start:
+            return res
+        start = self.kmer_pattern_edist_start(s, k, p, res[0] if with_dist else res)[0]
+        return res + (start,) if with_dist else (res, start)
 
-    def kmer_pattern_edist_hits_packed(self, words, n_bases, k, pattern, tau, with_dist=False):
+    def kmer_pattern_edist_hits_packed(self, words, n_bases, k, pattern, tau, with_dist=False, with_start=False):
         """kmer_pattern_edist_hits of the packed sequence `words` holding `n_bases` bases."""
         w = _as_u64(words)
         p = self._patterns(pattern, k)[:1]
-        return self._hits(self._lib.bitnuc_kmer_pattern_edist_hits_packed, (_ptr(w), w.size, int(n_bases), int(k), _ptr(p), int(tau)), with_dist)
+        res = self._hits(self._lib.bitnuc_kmer_pattern_edist_hits_packed, (_ptr(w), w.size, int(n_bases), int(k), _ptr(p), int(tau)), with_dist)
+        if not with_start:
+            return res
+        start = self.kmer_pattern_edist_start_packed(w, n_bases, k, p, res[0] if with_dist else res)[0]
+        return res + (start,) if with_dist else (res, start)
 
     # -- pattern queries for the per-read matchers: the reads_hdist_* methods with `patterns` ((Q, 4) np.uint32, or IUPAC strings of length k) where
     # `queries` stood and pdist where the Hamming distance stood; everything else as their exact twins --
@@ -764,57 +784,65 @@ class Context:
         return self._reads_anchored(self._lib.bitnuc_reads_pattern_anchored_packed, (_ptr(w), read_len, count, int(k)), count, patterns, pos_lo, pos_hi, second,
                                     int(k))
 
-    def reads_edist_anchored(self, reads, read_len, k, queries, pos_lo=0, pos_hi=None, count=None, second=True):
+    def reads_edist_anchored(self, reads, read_len, k, queries, pos_lo=0, pos_hi=None, count=None, second=True, with_start=False):
         """The indel-tolerant anchored match: as reads_hdist_anchored, with the EDIT (Levenshtein) distance of each query to the best substring of the
         read's span [pos_lo, min(pos_hi, read_len - k) + k) (at most 64 bases; the substring starts and ends anywhere in it).  (query, end, dist,
         second_query, second_end, second_dist): the smallest (dist, query, end) and the smallest over the other queries; end is an offset in the read,
-        one past the last aligned base (the start is not reported).  dist is never above reads_hdist_anchored's.  second=False: the best triple only."""
+        one past the last aligned base (with_start=True appends the start arrays: reads_edist_start).  dist is never above reads_hdist_anchored's.  second=False: the best triple only."""
         s, read_len, count = self._fixed_reads(reads, read_len, count)
-        return self._reads_anchored(self._lib.bitnuc_reads_edist_anchored, (_ptr(s), read_len, count, int(k)), count, queries, pos_lo, pos_hi, second)
+        res = self._reads_anchored(self._lib.bitnuc_reads_edist_anchored, (_ptr(s), read_len, count, int(k)), count, queries, pos_lo, pos_hi, second)
+        return self._append_starts(res, lambda q, e: self.reads_edist_start(s, read_len, k, queries, q, e, "start", pos_lo, count)) if with_start else res
 
-    def reads_edist_anchored_packed(self, words, read_len, count, k, queries, pos_lo=0, pos_hi=None, second=True):
+    def reads_edist_anchored_packed(self, words, read_len, count, k, queries, pos_lo=0, pos_hi=None, second=True, with_start=False):
         """reads_edist_anchored of the packed words encode_fixed writes (ceil(read_len / 32) words per read), without decoding them."""
         w, read_len, count = self._fixed_words(words, read_len, count)
-        return self._reads_anchored(self._lib.bitnuc_reads_edist_anchored_packed, (_ptr(w), read_len, count, int(k)), count, queries, pos_lo, pos_hi, second)
+        res = self._reads_anchored(self._lib.bitnuc_reads_edist_anchored_packed, (_ptr(w), read_len, count, int(k)), count, queries, pos_lo, pos_hi, second)
+        return self._append_starts(res, lambda q, e: self.reads_edist_start_packed(w, read_len, count, k, queries, q, e, "start", pos_lo)) if with_start else res
 
-    def reads_pattern_edist_anchored(self, reads, read_len, k, patterns, pos_lo=0, pos_hi=None, count=None, second=True):
+    def reads_pattern_edist_anchored(self, reads, read_len, k, patterns, pos_lo=0, pos_hi=None, count=None, second=True, with_start=False):
         """reads_edist_anchored under pattern queries: a read base matches query position i when it is in the position's set."""
         s, read_len, count = self._fixed_reads(reads, read_len, count)
-        return self._reads_anchored(self._lib.bitnuc_reads_pattern_edist_anchored, (_ptr(s), read_len, count, int(k)), count, patterns, pos_lo, pos_hi, second,
+        res = self._reads_anchored(self._lib.bitnuc_reads_pattern_edist_anchored, (_ptr(s), read_len, count, int(k)), count, patterns, pos_lo, pos_hi, second,
                                     int(k))
+        return self._append_starts(res, lambda q, e: self.reads_pattern_edist_start(s, read_len, k, patterns, q, e, "start", pos_lo, count)) if with_start else res
 
-    def reads_pattern_edist_anchored_packed(self, words, read_len, count, k, patterns, pos_lo=0, pos_hi=None, second=True):
+    def reads_pattern_edist_anchored_packed(self, words, read_len, count, k, patterns, pos_lo=0, pos_hi=None, second=True, with_start=False):
         """reads_pattern_edist_anchored of the packed words encode_fixed writes, without decoding them."""
         w, read_len, count = self._fixed_words(words, read_len, count)
-        return self._reads_anchored(self._lib.bitnuc_reads_pattern_edist_anchored_packed, (_ptr(w), read_len, count, int(k)), count, patterns, pos_lo, pos_hi,
+        res = self._reads_anchored(self._lib.bitnuc_reads_pattern_edist_anchored_packed, (_ptr(w), read_len, count, int(k)), count, patterns, pos_lo, pos_hi,
                                     second, int(k))
+        return self._append_starts(res, lambda q, e: self.reads_pattern_edist_start_packed(w, read_len, count, k, patterns, q, e, "start", pos_lo)) if with_start else res
 
-    def reads_edist_anchored_batch(self, seq, offsets, k, queries, pos_lo=0, pos_hi=0, anchor="start", second=True):
+    def reads_edist_anchored_batch(self, seq, offsets, k, queries, pos_lo=0, pos_hi=0, anchor="start", second=True, with_start=False):
         """reads_edist_anchored of a ragged batch (read r is seq[offsets[r]:offsets[r + 1]]): the EDIT distance of each query to the best substring of the
         read's own span, the bases reads_hdist_anchored_batch looks at for the same (anchor, pos_lo, pos_hi) -- a short read gets its shortened span, a
         read without a window the fill.  pos_hi - pos_lo + k may not exceed 64.  (query, end, dist, second_query, second_end, second_dist); end is
         counted from the read's start in both anchor modes, one past the last aligned base.  second=False: the best triple only."""
         s, off, count = self._ragged_reads(seq, offsets)
-        return self._reads_anchored(self._lib.bitnuc_reads_edist_anchored_batch, (_ptr(s), _ptr(off), count, int(k), self._anchor(anchor)), count, queries, pos_lo,
+        res = self._reads_anchored(self._lib.bitnuc_reads_edist_anchored_batch, (_ptr(s), _ptr(off), count, int(k), self._anchor(anchor)), count, queries, pos_lo,
                                     int(pos_hi), second)
+        return self._append_starts(res, lambda q, e: self.reads_edist_start_batch(s, off, k, queries, q, e, *self._start_floor(anchor, pos_lo, pos_hi))) if with_start else res
 
-    def reads_edist_anchored_batch_packed(self, words, word_offsets, offsets, k, queries, pos_lo=0, pos_hi=0, anchor="start", second=True):
+    def reads_edist_anchored_batch_packed(self, words, word_offsets, offsets, k, queries, pos_lo=0, pos_hi=0, anchor="start", second=True, with_start=False):
         """reads_edist_anchored_batch of the packed words encode_batch writes (read r's ceil(len_r / 32) words start at words[word_offsets[r]])."""
         w, woff, off, count = self._ragged_words(words, word_offsets, offsets)
-        return self._reads_anchored(self._lib.bitnuc_reads_edist_anchored_batch_packed, (_ptr(w), _ptr(woff), _ptr(off), count, int(k), self._anchor(anchor)), count,
+        res = self._reads_anchored(self._lib.bitnuc_reads_edist_anchored_batch_packed, (_ptr(w), _ptr(woff), _ptr(off), count, int(k), self._anchor(anchor)), count,
                                     queries, pos_lo, int(pos_hi), second)
+        return self._append_starts(res, lambda q, e: self.reads_edist_start_batch_packed(w, woff, off, k, queries, q, e, *self._start_floor(anchor, pos_lo, pos_hi))) if with_start else res
 
-    def reads_pattern_edist_anchored_batch(self, seq, offsets, k, patterns, pos_lo=0, pos_hi=0, anchor="start", second=True):
+    def reads_pattern_edist_anchored_batch(self, seq, offsets, k, patterns, pos_lo=0, pos_hi=0, anchor="start", second=True, with_start=False):
         """reads_edist_anchored_batch under pattern queries: a read base matches query position i when it is in the position's set."""
         s, off, count = self._ragged_reads(seq, offsets)
-        return self._reads_anchored(self._lib.bitnuc_reads_pattern_edist_anchored_batch, (_ptr(s), _ptr(off), count, int(k), self._anchor(anchor)), count, patterns,
+        res = self._reads_anchored(self._lib.bitnuc_reads_pattern_edist_anchored_batch, (_ptr(s), _ptr(off), count, int(k), self._anchor(anchor)), count, patterns,
                                     pos_lo, int(pos_hi), second, int(k))
+        return self._append_starts(res, lambda q, e: self.reads_pattern_edist_start_batch(s, off, k, patterns, q, e, *self._start_floor(anchor, pos_lo, pos_hi))) if with_start else res
 
-    def reads_pattern_edist_anchored_batch_packed(self, words, word_offsets, offsets, k, patterns, pos_lo=0, pos_hi=0, anchor="start", second=True):
+    def reads_pattern_edist_anchored_batch_packed(self, words, word_offsets, offsets, k, patterns, pos_lo=0, pos_hi=0, anchor="start", second=True, with_start=False):
         """reads_pattern_edist_anchored_batch of the packed words encode_batch writes, without decoding them."""
         w, woff, off, count = self._ragged_words(words, word_offsets, offsets)
-        return self._reads_anchored(self._lib.bitnuc_reads_pattern_edist_anchored_batch_packed, (_ptr(w), _ptr(woff), _ptr(off), count, int(k), self._anchor(anchor)),
+        res = self._reads_anchored(self._lib.bitnuc_reads_pattern_edist_anchored_batch_packed, (_ptr(w), _ptr(woff), _ptr(off), count, int(k), self._anchor(anchor)),
                                     count, patterns, pos_lo, int(pos_hi), second, int(k))
+        return self._append_starts(res, lambda q, e: self.reads_pattern_edist_start_batch_packed(w, woff, off, k, patterns, q, e, *self._start_floor(anchor, pos_lo, pos_hi))) if with_start else res
 
     def _reads_edist_best(self, fn, head, count, queries, second, pattern_k=None):
         q, nq = self._reads_queries(queries, pattern_k)
@@ -826,50 +854,167 @@ class Context:
             _raise(err)
         return tuple(out)
 
-    def reads_edist_best(self, reads, read_len, k, queries, count=None, second=True):
+    def reads_edist_best(self, reads, read_len, k, queries, count=None, second=True, with_start=False):
         """The indel-tolerant best match over the WHOLE read: per read the smallest (edit distance, query, end) over the queries, the EDIT (Levenshtein)
         distance of a query being that to the best substring of the read (it starts and ends anywhere; reads of up to 2^26 bases), and the smallest over
         the other queries.  (query, end, dist, second_query, second_end, second_dist); end is one past the last aligned base, counted from the read's
-        start (the start is not reported).  dist is never above reads_hdist_best's.  second=False: the best triple only."""
+        start (with_start=True appends the start arrays: reads_edist_start).  dist is never above reads_hdist_best's.  second=False: the best triple only."""
         s, read_len, count = self._fixed_reads(reads, read_len, count)
-        return self._reads_edist_best(self._lib.bitnuc_reads_edist_best, (_ptr(s), read_len, count, int(k)), count, queries, second)
+        res = self._reads_edist_best(self._lib.bitnuc_reads_edist_best, (_ptr(s), read_len, count, int(k)), count, queries, second)
+        return self._append_starts(res, lambda q, e: self.reads_edist_start(s, read_len, k, queries, q, e, "start", 0, count)) if with_start else res
 
-    def reads_edist_best_packed(self, words, read_len, count, k, queries, second=True):
+    def reads_edist_best_packed(self, words, read_len, count, k, queries, second=True, with_start=False):
         """reads_edist_best of the packed words encode_fixed writes (ceil(read_len / 32) words per read), without decoding them."""
         w, read_len, count = self._fixed_words(words, read_len, count)
-        return self._reads_edist_best(self._lib.bitnuc_reads_edist_best_packed, (_ptr(w), read_len, count, int(k)), count, queries, second)
+        res = self._reads_edist_best(self._lib.bitnuc_reads_edist_best_packed, (_ptr(w), read_len, count, int(k)), count, queries, second)
+        return self._append_starts(res, lambda q, e: self.reads_edist_start_packed(w, read_len, count, k, queries, q, e, "start", 0)) if with_start else res
 
-    def reads_pattern_edist_best(self, reads, read_len, k, patterns, count=None, second=True):
+    def reads_pattern_edist_best(self, reads, read_len, k, patterns, count=None, second=True, with_start=False):
         """reads_edist_best under pattern queries: a read base matches query position i when it is in the position's set."""
         s, read_len, count = self._fixed_reads(reads, read_len, count)
-        return self._reads_edist_best(self._lib.bitnuc_reads_pattern_edist_best, (_ptr(s), read_len, count, int(k)), count, patterns, second, int(k))
+        res = self._reads_edist_best(self._lib.bitnuc_reads_pattern_edist_best, (_ptr(s), read_len, count, int(k)), count, patterns, second, int(k))
+        return self._append_starts(res, lambda q, e: self.reads_pattern_edist_start(s, read_len, k, patterns, q, e, "start", 0, count)) if with_start else res
 
-    def reads_pattern_edist_best_packed(self, words, read_len, count, k, patterns, second=True):
+    def reads_pattern_edist_best_packed(self, words, read_len, count, k, patterns, second=True, with_start=False):
         """reads_pattern_edist_best of the packed words encode_fixed writes, without decoding them."""
         w, read_len, count = self._fixed_words(words, read_len, count)
-        return self._reads_edist_best(self._lib.bitnuc_reads_pattern_edist_best_packed, (_ptr(w), read_len, count, int(k)), count, patterns, second, int(k))
+        res = self._reads_edist_best(self._lib.bitnuc_reads_pattern_edist_best_packed, (_ptr(w), read_len, count, int(k)), count, patterns, second, int(k))
+        return self._append_starts(res, lambda q, e: self.reads_pattern_edist_start_packed(w, read_len, count, k, patterns, q, e, "start", 0)) if with_start else res
 
-    def reads_edist_best_batch(self, seq, offsets, k, queries, second=True):
+    def reads_edist_best_batch(self, seq, offsets, k, queries, second=True, with_start=False):
         """reads_edist_best of a ragged batch (read r is seq[offsets[r]:offsets[r + 1]]): each read against every query over its own whole length; a
         read shorter than k gets the fill and is neither read nor validated.  Ends are counted from the read's start."""
         s, off, count = self._ragged_reads(seq, offsets)
-        return self._reads_edist_best(self._lib.bitnuc_reads_edist_best_batch, (_ptr(s), _ptr(off), count, int(k)), count, queries, second)
+        res = self._reads_edist_best(self._lib.bitnuc_reads_edist_best_batch, (_ptr(s), _ptr(off), count, int(k)), count, queries, second)
+        return self._append_starts(res, lambda q, e: self.reads_edist_start_batch(s, off, k, queries, q, e, "start", 0)) if with_start else res
 
-    def reads_edist_best_batch_packed(self, words, word_offsets, offsets, k, queries, second=True):
+    def reads_edist_best_batch_packed(self, words, word_offsets, offsets, k, queries, second=True, with_start=False):
         """reads_edist_best_batch of the packed words encode_batch writes (read r's ceil(len_r / 32) words start at words[word_offsets[r]])."""
         w, woff, off, count = self._ragged_words(words, word_offsets, offsets)
-        return self._reads_edist_best(self._lib.bitnuc_reads_edist_best_batch_packed, (_ptr(w), _ptr(woff), _ptr(off), count, int(k)), count, queries, second)
+        res = self._reads_edist_best(self._lib.bitnuc_reads_edist_best_batch_packed, (_ptr(w), _ptr(woff), _ptr(off), count, int(k)), count, queries, second)
+        return self._append_starts(res, lambda q, e: self.reads_edist_start_batch_packed(w, woff, off, k, queries, q, e, "start", 0)) if with_start else res
 
-    def reads_pattern_edist_best_batch(self, seq, offsets, k, patterns, second=True):
+    def reads_pattern_edist_best_batch(self, seq, offsets, k, patterns, second=True, with_start=False):
         """reads_edist_best_batch under pattern queries."""
         s, off, count = self._ragged_reads(seq, offsets)
-        return self._reads_edist_best(self._lib.bitnuc_reads_pattern_edist_best_batch, (_ptr(s), _ptr(off), count, int(k)), count, patterns, second, int(k))
+        res = self._reads_edist_best(self._lib.bitnuc_reads_pattern_edist_best_batch, (_ptr(s), _ptr(off), count, int(k)), count, patterns, second, int(k))
+        return self._append_starts(res, lambda q, e: self.reads_pattern_edist_start_batch(s, off, k, patterns, q, e, "start", 0)) if with_start else res
 
-    def reads_pattern_edist_best_batch_packed(self, words, word_offsets, offsets, k, patterns, second=True):
+    def reads_pattern_edist_best_batch_packed(self, words, word_offsets, offsets, k, patterns, second=True, with_start=False):
         """reads_pattern_edist_best_batch of the packed words encode_batch writes, without decoding them."""
         w, woff, off, count = self._ragged_words(words, word_offsets, offsets)
-        return self._reads_edist_best(self._lib.bitnuc_reads_pattern_edist_best_batch_packed, (_ptr(w), _ptr(woff), _ptr(off), count, int(k)), count, patterns,
+        res = self._reads_edist_best(self._lib.bitnuc_reads_pattern_edist_best_batch_packed, (_ptr(w), _ptr(woff), _ptr(off), count, int(k)), count, patterns,
                                       second, int(k))
+        return self._append_starts(res, lambda q, e: self.reads_pattern_edist_start_batch_packed(w, woff, off, k, patterns, q, e, "start", 0)) if with_start else res
+
+    # -- the indel-tolerant family's second stage: WHERE the alignment that ends at end[r] starts.  Per item (query index, end) -> (start, dist): the smallest
+    # edit distance of the query to a substring t[s, end) with s at or behind the floor and, among those, the shortest; dist equals the forward form's when
+    # the floor is its span start.  A skipped item (query >= Q, end beyond the read or in front of the floor) gets 2^32 - 1 (2^64 - 1), 255 --
+    def _reads_start(self, fn, head, count, k, queries, query, end, anchor, pos, pattern_k=None):
+        q, nq = self._reads_queries(queries, pattern_k)
+        qi = np.ascontiguousarray(np.asarray(query, dtype=np.uint32).reshape(-1))
+        en = np.ascontiguousarray(np.asarray(end, dtype=np.uint32).reshape(-1))
+        if qi.size < count or en.size < count:
+            raise ValueError("query and end must hold one entry per read")
+        start = np.empty(count, dtype=np.uint32)
+        dist = np.empty(count, dtype=np.uint8)
+        err = L.BitnucErr()
+        if fn(self._h, *head, int(k), self._anchor(anchor), int(pos), _ptr(q), nq, _ptr(qi), _ptr(en), _ptr(start), _ptr(dist), C.byref(err)) != L.OK:
+            _raise(err)
+        return start, dist
+
+    def reads_edist_start(self, reads, read_len, k, queries, query, end, anchor="start", pos=0, count=None):
+        """(start, dist) per read of a fixed-length batch: the alignment of queries[query[r]] that ends at end[r] (one past its last base) starts at
+        start[r].  The floor: anchor="start": pos; "end": read_len - k - pos (at least 0).  After reads_edist_best: ("start", 0); after
+        reads_edist_anchored: ("start", pos_lo)."""
+        s, read_len, count = self._fixed_reads(reads, read_len, count)
+        return self._reads_start(self._lib.bitnuc_reads_edist_start, (_ptr(s), read_len, count), count, k, queries, query, end, anchor, pos)
+
+    def reads_edist_start_packed(self, words, read_len, count, k, queries, query, end, anchor="start", pos=0):
+        """reads_edist_start of the packed words encode_fixed writes."""
+        w, read_len, count = self._fixed_words(words, read_len, count)
+        return self._reads_start(self._lib.bitnuc_reads_edist_start_packed, (_ptr(w), read_len, count), count, k, queries, query, end, anchor, pos)
+
+    def reads_pattern_edist_start(self, reads, read_len, k, patterns, query, end, anchor="start", pos=0, count=None):
+        """reads_edist_start under pattern queries."""
+        s, read_len, count = self._fixed_reads(reads, read_len, count)
+        return self._reads_start(self._lib.bitnuc_reads_pattern_edist_start, (_ptr(s), read_len, count), count, k, patterns, query, end, anchor, pos, int(k))
+
+    def reads_pattern_edist_start_packed(self, words, read_len, count, k, patterns, query, end, anchor="start", pos=0):
+        """reads_pattern_edist_start of the packed words encode_fixed writes."""
+        w, read_len, count = self._fixed_words(words, read_len, count)
+        return self._reads_start(self._lib.bitnuc_reads_pattern_edist_start_packed, (_ptr(w), read_len, count), count, k, patterns, query, end, anchor, pos, int(k))
+
+    def reads_edist_start_batch(self, seq, offsets, k, queries, query, end, anchor="start", pos=0):
+        """reads_edist_start of a ragged batch; the floor of read r: "start": pos; "end": len_r - k - pos (at least 0).  After reads_edist_best_batch:
+        ("start", 0); after reads_edist_anchored_batch: ("start", pos_lo) or ("end", pos_hi)."""
+        s, off, count = self._ragged_reads(seq, offsets)
+        return self._reads_start(self._lib.bitnuc_reads_edist_start_batch, (_ptr(s), _ptr(off), count), count, k, queries, query, end, anchor, pos)
+
+    def reads_edist_start_batch_packed(self, words, word_offsets, offsets, k, queries, query, end, anchor="start", pos=0):
+        """reads_edist_start_batch of the packed words encode_batch writes."""
+        w, woff, off, count = self._ragged_words(words, word_offsets, offsets)
+        return self._reads_start(self._lib.bitnuc_reads_edist_start_batch_packed, (_ptr(w), _ptr(woff), _ptr(off), count), count, k, queries, query, end, anchor, pos)
+
+    def reads_pattern_edist_start_batch(self, seq, offsets, k, patterns, query, end, anchor="start", pos=0):
+        """reads_edist_start_batch under pattern queries."""
+        s, off, count = self._ragged_reads(seq, offsets)
+        return self._reads_start(self._lib.bitnuc_reads_pattern_edist_start_batch, (_ptr(s), _ptr(off), count), count, k, patterns, query, end, anchor, pos, int(k))
+
+    def reads_pattern_edist_start_batch_packed(self, words, word_offsets, offsets, k, patterns, query, end, anchor="start", pos=0):
+        """reads_pattern_edist_start_batch of the packed words encode_batch writes."""
+        w, woff, off, count = self._ragged_words(words, word_offsets, offsets)
+        return self._reads_start(self._lib.bitnuc_reads_pattern_edist_start_batch_packed, (_ptr(w), _ptr(woff), _ptr(off), count), count, k, patterns, query, end,
+                                 anchor, pos, int(k))
+
+    def _kmer_start(self, fn, head, q, nq, end, query_index):
+        en = np.ascontiguousarray(np.asarray(end, dtype=np.uint64).reshape(-1))
+        qi = None if query_index is None else np.ascontiguousarray(np.asarray(query_index, dtype=np.uint32).reshape(-1))
+        if qi is not None and qi.size < en.size:
+            raise ValueError("query_index must hold one entry per end")
+        start = np.empty(en.size, dtype=np.uint64)
+        dist = np.empty(en.size, dtype=np.uint8)
+        err = L.BitnucErr()
+        if fn(self._h, *head, _ptr(q), nq, None if qi is None else _ptr(qi), _ptr(en), en.size, _ptr(start), _ptr(dist), C.byref(err)) != L.OK:
+            _raise(err)
+        return start, dist
+
+    def kmer_edist_start(self, ref, k, queries, end, query_index=None):
+        """(start, dist) per item along `ref`: the alignment of queries[query_index[i]] (None: queries[0], the hit list's case) that ends at end[i] starts
+        at start[i] (np.uint64).  After kmer_edist_best pass query_index = arange(Q).  Always host code: an item reads at most 63 bases."""
+        s = _as_u8(ref)
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.uint64).reshape(-1))
+        return self._kmer_start(self._lib.bitnuc_ref_edist_start, (_ptr(s), s.size, int(k)), q, q.size, end, query_index)
+
+    def kmer_edist_start_packed(self, words, n_bases, k, queries, end, query_index=None):
+        """kmer_edist_start of the packed sequence `words` holding `n_bases` bases."""
+        w = _as_u64(words)
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.uint64).reshape(-1))
+        return self._kmer_start(self._lib.bitnuc_ref_edist_start_packed, (_ptr(w), w.size, int(n_bases), int(k)), q, q.size, end, query_index)
+
+    def kmer_pattern_edist_start(self, ref, k, patterns, end, query_index=None):
+        """kmer_edist_start under pattern queries."""
+        s = _as_u8(ref)
+        p = self._patterns(patterns, k)
+        return self._kmer_start(self._lib.bitnuc_ref_pattern_edist_start, (_ptr(s), s.size, int(k)), p, p.shape[0], end, query_index)
+
+    def kmer_pattern_edist_start_packed(self, words, n_bases, k, patterns, end, query_index=None):
+        """kmer_pattern_edist_start of the packed sequence `words` holding `n_bases` bases."""
+        w = _as_u64(words)
+        p = self._patterns(patterns, k)
+        return self._kmer_start(self._lib.bitnuc_ref_pattern_edist_start_packed, (_ptr(w), w.size, int(n_bases), int(k)), p, p.shape[0], end, query_index)
+
+    def _start_floor(self, anchor, pos_lo, pos_hi):
+        """the floor a ragged anchored form's span starts at, as (anchor, pos) of reads_edist_start_batch: its first admissible offset is pos_lo from the
+        read's start, or pos_hi (saturating) from its end"""
+        return ("end", int(pos_hi)) if self._anchor(anchor) == 1 else ("start", int(pos_lo))
+
+    @staticmethod
+    def _append_starts(res, starter):
+        """a per-read forward result (query, end, dist[, second_query, second_end, second_dist]) with the start arrays as extra trailing results: one
+        starter(query, end) -> (start, dist) call per triple"""
+        starts = tuple(starter(res[i], res[i + 1])[0] for i in range(0, len(res), 3))
+        return tuple(res) + starts
 
     def reads_pattern_anchored_batch(self, seq, offsets, k, patterns, pos_lo=0, pos_hi=0, anchor="start", second=True):
         """reads_hdist_anchored_batch under pattern queries (a ragged batch; the range counted from each read's start or end)."""
@@ -1516,6 +1661,79 @@ class Context:
         p = None if pattern is None else np.ascontiguousarray(np.asarray(pattern, dtype=np.uint32).reshape(4))
         self._call_dev(self._lib.bitnuc_kmer_pattern_edist_hits_packed_async, _dev_ptr(d_words), int(n_words), int(n), int(k), None if p is None else _ptr(p),
                        int(tau), _dev_ptr(d_end), _dev_ptr(d_hit_dist), int(cap), _dev_ptr(d_n_hits))
+
+    # the family's second stage on device tensors: d_query / d_end (u32; along a reference d_query_index u32 or None, d_end u64) -> d_start (u32 / u64),
+    # d_dist (u8, or None).  Asynchronous on the context's stream; they chain behind the forward call without a sync (one table slot, stream order)
+    def _reads_start_async(self, fn, head, k, d_queries, n_queries, d_query, d_end, d_start, d_dist, anchor, pos):
+        self._call_dev(fn, *head, int(k), self._anchor(anchor), int(pos), _dev_ptr(d_queries), int(n_queries), _dev_ptr(d_query), _dev_ptr(d_end),
+                       _dev_ptr(d_start), _dev_ptr(d_dist))
+
+    def reads_edist_start_async(self, d_reads, read_len, count, k, d_queries, n_queries, d_query, d_end, d_start, d_dist=None, anchor="start", pos=0):
+        """reads_edist_start on device tensors; an invalid byte in a walked range is reported by the next sync()."""
+        self._reads_start_async(self._lib.bitnuc_reads_edist_start_async, (_dev_ptr(d_reads), int(read_len), int(count)), k, d_queries, n_queries, d_query, d_end,
+                                d_start, d_dist, anchor, pos)
+
+    def reads_edist_start_packed_async(self, d_words, read_len, count, k, d_queries, n_queries, d_query, d_end, d_start, d_dist=None, anchor="start", pos=0):
+        """reads_edist_start_async of packed words (ceil(read_len / 32) per read)."""
+        self._reads_start_async(self._lib.bitnuc_reads_edist_start_packed_async, (_dev_ptr(d_words), int(read_len), int(count)), k, d_queries, n_queries, d_query,
+                                d_end, d_start, d_dist, anchor, pos)
+
+    def reads_pattern_edist_start_async(self, d_reads, read_len, count, k, d_patterns, n_queries, d_query, d_end, d_start, d_dist=None, anchor="start", pos=0):
+        """reads_edist_start_async under pattern queries."""
+        self._reads_start_async(self._lib.bitnuc_reads_pattern_edist_start_async, (_dev_ptr(d_reads), int(read_len), int(count)), k, d_patterns, n_queries, d_query,
+                                d_end, d_start, d_dist, anchor, pos)
+
+    def reads_pattern_edist_start_packed_async(self, d_words, read_len, count, k, d_patterns, n_queries, d_query, d_end, d_start, d_dist=None, anchor="start", pos=0):
+        """reads_edist_start_packed_async under pattern queries."""
+        self._reads_start_async(self._lib.bitnuc_reads_pattern_edist_start_packed_async, (_dev_ptr(d_words), int(read_len), int(count)), k, d_patterns, n_queries,
+                                d_query, d_end, d_start, d_dist, anchor, pos)
+
+    def reads_edist_start_batch_async(self, d_seq, d_offsets, count, total_bases, k, d_queries, n_queries, d_query, d_end, d_start, d_dist=None, anchor="start",
+                                      pos=0):
+        """reads_edist_start_batch on device tensors; the table is trusted and read on the device."""
+        self._reads_start_async(self._lib.bitnuc_reads_edist_start_batch_async, (_dev_ptr(d_seq), _dev_ptr(d_offsets), int(count), int(total_bases)), k, d_queries,
+                                n_queries, d_query, d_end, d_start, d_dist, anchor, pos)
+
+    def reads_edist_start_batch_packed_async(self, d_words, d_word_offsets, d_offsets, count, total_words, k, d_queries, n_queries, d_query, d_end, d_start,
+                                             d_dist=None, anchor="start", pos=0):
+        """reads_edist_start_batch_async on the packed words encode_batch_dev writes."""
+        self._reads_start_async(self._lib.bitnuc_reads_edist_start_batch_packed_async,
+                                (_dev_ptr(d_words), _dev_ptr(d_word_offsets), _dev_ptr(d_offsets), int(count), int(total_words)), k, d_queries, n_queries, d_query,
+                                d_end, d_start, d_dist, anchor, pos)
+
+    def reads_pattern_edist_start_batch_async(self, d_seq, d_offsets, count, total_bases, k, d_patterns, n_queries, d_query, d_end, d_start, d_dist=None,
+                                              anchor="start", pos=0):
+        """reads_edist_start_batch_async under pattern queries."""
+        self._reads_start_async(self._lib.bitnuc_reads_pattern_edist_start_batch_async, (_dev_ptr(d_seq), _dev_ptr(d_offsets), int(count), int(total_bases)), k,
+                                d_patterns, n_queries, d_query, d_end, d_start, d_dist, anchor, pos)
+
+    def reads_pattern_edist_start_batch_packed_async(self, d_words, d_word_offsets, d_offsets, count, total_words, k, d_patterns, n_queries, d_query, d_end,
+                                                     d_start, d_dist=None, anchor="start", pos=0):
+        """reads_edist_start_batch_packed_async under pattern queries."""
+        self._reads_start_async(self._lib.bitnuc_reads_pattern_edist_start_batch_packed_async,
+                                (_dev_ptr(d_words), _dev_ptr(d_word_offsets), _dev_ptr(d_offsets), int(count), int(total_words)), k, d_patterns, n_queries, d_query,
+                                d_end, d_start, d_dist, anchor, pos)
+
+    def kmer_edist_start_async(self, d_ref, n, k, d_queries, n_queries, d_query_index, d_end, m, d_start, d_dist=None, d_m=None):
+        """kmer_edist_start on device tensors: m items; d_m (a u64 device count, e.g. the hit list's d_n_hits) bounds them to min(m, *d_m) -- nothing at or
+        beyond it is written."""
+        self._call_dev(self._lib.bitnuc_ref_edist_start_async, _dev_ptr(d_ref), int(n), int(k), _dev_ptr(d_queries), int(n_queries), _dev_ptr(d_query_index),
+                       _dev_ptr(d_end), int(m), _dev_ptr(d_m), _dev_ptr(d_start), _dev_ptr(d_dist))
+
+    def kmer_edist_start_packed_async(self, d_words, n_words, n, k, d_queries, n_queries, d_query_index, d_end, m, d_start, d_dist=None, d_m=None):
+        """kmer_edist_start_async on packed words in device memory (8-byte aligned)."""
+        self._call_dev(self._lib.bitnuc_ref_edist_start_packed_async, _dev_ptr(d_words), int(n_words), int(n), int(k), _dev_ptr(d_queries), int(n_queries),
+                       _dev_ptr(d_query_index), _dev_ptr(d_end), int(m), _dev_ptr(d_m), _dev_ptr(d_start), _dev_ptr(d_dist))
+
+    def kmer_pattern_edist_start_async(self, d_ref, n, k, d_patterns, n_queries, d_query_index, d_end, m, d_start, d_dist=None, d_m=None):
+        """kmer_edist_start_async under pattern queries."""
+        self._call_dev(self._lib.bitnuc_ref_pattern_edist_start_async, _dev_ptr(d_ref), int(n), int(k), _dev_ptr(d_patterns), int(n_queries),
+                       _dev_ptr(d_query_index), _dev_ptr(d_end), int(m), _dev_ptr(d_m), _dev_ptr(d_start), _dev_ptr(d_dist))
+
+    def kmer_pattern_edist_start_packed_async(self, d_words, n_words, n, k, d_patterns, n_queries, d_query_index, d_end, m, d_start, d_dist=None, d_m=None):
+        """kmer_edist_start_packed_async under pattern queries."""
+        self._call_dev(self._lib.bitnuc_ref_pattern_edist_start_packed_async, _dev_ptr(d_words), int(n_words), int(n), int(k), _dev_ptr(d_patterns),
+                       int(n_queries), _dev_ptr(d_query_index), _dev_ptr(d_end), int(m), _dev_ptr(d_m), _dev_ptr(d_start), _dev_ptr(d_dist))
 
     def kmer_hdist_hist_async(self, d_ref, n, k, d_queries, n_queries, n_bins, d_hist):
         """The mismatch histogram of n_queries queries at once: d_hist[q * n_bins + d] (u64) = windows at distance exactly d < n_bins from d_queries[q]

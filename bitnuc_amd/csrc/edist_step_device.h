@@ -13,7 +13,8 @@
 // v_cndmask), not a lookup: the low bit toggles A -> C and G -> T by an xor, the high bit selects between the two pairs.  What a kernel does with the
 // score at each base (a running key, a count, a store) is its own; with the anchored kernel's key that is 20 vector instructions per (query, base)
 // (DESIGN.md 3.4 has the counts by opcode and what was tried).
-// Here: a column's start from a table entry, Eq and the step on the column's registers (edist_col_*), the column state of U interleaved queries
+// Here (the anchored forms of the start and the step, for the backward walk of scan_edist_start_device.h, stand beside them as functions of their own):
+// a column's start from a table entry, Eq and the step on the column's registers (edist_col_*), the column state of U interleaved queries
 // (EdistCols) with the same three on column u of it, the query groups and the wave maximum.  Every kernel that uses them compiles to the instructions
 // it had when it spelled them itself, and that is kept by these rules ("The edit-distance step, written once", has what each costs):
 //   - a kernel's own per-query values are members of a struct DERIVED from EdistCols, in the order its loops use them; the anchored kernel keeps arrays
@@ -62,6 +63,32 @@ template <class OnScore> __device__ __forceinline__ void edist_col_step(uint32_t
     sc -= (mh >> top) & 1u;
     on_score(sc);
     ph <<= 1; // no carry-in: D[0][j] = 0
+    mh <<= 1;
+    pv = mh | ~(xv | ph);
+    mv = ph & xv;
+}
+
+// ---- the same column ANCHORED at the text's first base (scan_edist_start_device.h: the backward walk from an alignment's end to its start): row 0 is
+// D[0][j] = j, a carry-in of 1 on the horizontal delta -- one v_or more than edist_col_step in the shipped code (ph << 1 is also an operand of the next
+// three-input bit op, so the shift and the or do not fuse).  The masks come from a table entry the LANE picked (its own query), reversed within k bits:
+// they are in VGPRs without being forced there.
+__device__ __forceinline__ void edist_col_init_reversed(const u32x4 &t, unsigned k, uint32_t &pa, uint32_t &pc, uint32_t &pg, uint32_t &pt, uint32_t &pv,
+                                                        uint32_t &mv, uint32_t &sc) {
+    const unsigned down = 32u - k;
+    pa = __builtin_bitreverse32(t.x) >> down, pc = __builtin_bitreverse32(t.x ^ t.y) >> down;
+    pg = __builtin_bitreverse32(t.z) >> down, pt = __builtin_bitreverse32(t.z ^ t.w) >> down;
+    pv = ~0u, mv = 0u, sc = k;
+}
+template <class OnScore>
+__device__ __forceinline__ void edist_col_step_anchored(uint32_t eq, uint32_t &pv, uint32_t &mv, uint32_t &sc, unsigned top, OnScore on_score) {
+    const uint32_t xv = eq | mv;
+    const uint32_t xh = (((eq & pv) + pv) ^ pv) | eq;
+    uint32_t ph = mv | ~(xh | pv);
+    uint32_t mh = pv & xh;
+    sc += (ph >> top) & 1u;
+    sc -= (mh >> top) & 1u;
+    on_score(sc);
+    ph = (ph << 1) | 1u; // the carry-in: D[0][j] = j
     mh <<= 1;
     pv = mh | ~(xv | ph);
     mv = ph & xv;

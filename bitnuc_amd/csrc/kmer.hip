@@ -3,7 +3,7 @@
 // Hamming scan (config 5: packing/mod.rs:80-110 o hamming/scalar.rs:11-48) and bulk hdist (hamming/multi.rs:121-160).
 // Kernels: kmer_device.h; config 5 on the matrix cores: scan_mfma_device.h; the same scan and count on packed words: scan_packed_device.h; the hit
 // lists of both: scan_hits_device.h; the count for many queries at once: scan_multi_device.h; the best match per query: scan_best_device.h; the mismatch histogram per query: scan_hist_device.h; the best match per read of a
-// fixed-length batch: scan_reads_device.h; ... of a ragged batch: scan_reads_batch_device.h; the indel-tolerant search along a reference: scan_edist_ref_device.h, its hit list: scan_edist_hits_device.h.  The launchers, their argument checks and the host forms' chunk loops are here; the host side of the searches
+// fixed-length batch: scan_reads_device.h; ... of a ragged batch: scan_reads_batch_device.h; the indel-tolerant search along a reference: scan_edist_ref_device.h, its hit list: scan_edist_hits_device.h; where an alignment starts: scan_edist_start_device.h.  The launchers, their argument checks and the host forms' chunk loops are here; the host side of the searches
 // along a reference -- inputs, searches, the two skeletons -- is ref_dispatch.h, that of every per-read matcher reads_dispatch.h.
 #include "runtime.h"
 
@@ -22,6 +22,7 @@
 #include "scan_edist_best_device.h"
 #include "scan_edist_ref_device.h"
 #include "scan_edist_hits_device.h"
+#include "scan_edist_start_device.h"
 #include "scan_hist_device.h"
 #include "scan_mfma_host.h"
 #include "scan_hits_host.h"
@@ -34,6 +35,7 @@
 #include "reads_edist_host.h"
 #include "reads_edist_best_host.h"
 #include "kmer_edist_host.h"
+#include "edist_start_host.h"
 #include "reads_batch_host.h"
 #include "scan_hist_host.h"
 #include "pattern_host.h"
@@ -788,6 +790,12 @@ int launch_edist_hits(bitnuc_ctx *c, const void *data, size_t n, size_t lead, si
                                                                                       tiles, a.pos, a.hd, a.cap, a.pos_base, slot);
     HIPCHK(hipGetLastError());
     return BITNUC_OK;
+}
+
+// ---- the grid of the indel-tolerant family's second stage (scan_edist_start_device.h): one item per lane, the family's bound on the workgroups
+inline unsigned start_grid(const bitnuc_ctx *c, size_t count) {
+    const size_t want = (count + kEdistBlock - 1) / kEdistBlock, cap = (size_t)c->num_cu * kEdistBlocksPerCu;
+    return (unsigned)(want < cap ? want : cap);
 }
 
 } // namespace
@@ -1676,6 +1684,84 @@ int bitnuc_kmer_pattern_edist_hits(bitnuc_ctx *c, const uint8_t *ref, size_t n, 
 int bitnuc_kmer_pattern_edist_hits_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *pattern, unsigned tau, uint64_t *end,
                                           uint8_t *hit_dist, size_t cap, uint64_t *n_hits, bitnuc_err *err) {
     return ref_host(c, PackedRef{words, n_words, n}, k, EdistHits<bitnuc_pattern>{pattern, tau, end, hit_dist, cap, n_hits}, err);
+}
+
+// ---- the indel-tolerant family's second stage: where the alignment that ends at a given base starts (reads_dispatch.h, ref_dispatch.h) ----
+int bitnuc_reads_edist_start_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, int anchor, size_t pos, const uint64_t *d_queries, size_t n_queries, const uint32_t *d_query, const uint32_t *d_end, uint32_t *d_start, uint8_t *d_dist, bitnuc_err *err) {
+    return reads_start_async(c, FixedAscii{d_reads, read_len}, count, StartArgs<uint64_t>{k, anchor, pos, d_queries, n_queries, d_query, d_end, d_start, d_dist}, err);
+}
+int bitnuc_reads_edist_start_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, int anchor, size_t pos, const uint64_t *d_queries, size_t n_queries, const uint32_t *d_query, const uint32_t *d_end, uint32_t *d_start, uint8_t *d_dist, bitnuc_err *err) {
+    return reads_start_async(c, FixedPacked{d_words, read_len}, count, StartArgs<uint64_t>{k, anchor, pos, d_queries, n_queries, d_query, d_end, d_start, d_dist}, err);
+}
+int bitnuc_reads_edist_start_batch_async(bitnuc_ctx *c, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k, int anchor, size_t pos, const uint64_t *d_queries, size_t n_queries, const uint32_t *d_query, const uint32_t *d_end, uint32_t *d_start, uint8_t *d_dist, bitnuc_err *err) {
+    return reads_start_async(c, RaggedAscii{d_seq, d_offsets, total_bases, total_bases}, count, StartArgs<uint64_t>{k, anchor, pos, d_queries, n_queries, d_query, d_end, d_start, d_dist}, err);
+}
+int bitnuc_reads_edist_start_batch_packed_async(bitnuc_ctx *c, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count, size_t total_words, size_t k, int anchor, size_t pos, const uint64_t *d_queries, size_t n_queries, const uint32_t *d_query, const uint32_t *d_end, uint32_t *d_start, uint8_t *d_dist, bitnuc_err *err) {
+    return reads_start_async(c, RaggedPacked::on_device(d_words, d_word_offsets, d_offsets, total_words), count, StartArgs<uint64_t>{k, anchor, pos, d_queries, n_queries, d_query, d_end, d_start, d_dist}, err);
+}
+int bitnuc_reads_edist_start(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, int anchor, size_t pos, const uint64_t *queries, size_t n_queries, const uint32_t *query, const uint32_t *end, uint32_t *start, uint8_t *dist, bitnuc_err *err) {
+    return reads_start_host(c, FixedAscii{reads, read_len}, count, StartArgs<uint64_t>{k, anchor, pos, queries, n_queries, query, end, start, dist}, err);
+}
+int bitnuc_reads_edist_start_packed(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, int anchor, size_t pos, const uint64_t *queries, size_t n_queries, const uint32_t *query, const uint32_t *end, uint32_t *start, uint8_t *dist, bitnuc_err *err) {
+    return reads_start_host(c, FixedPacked{words, read_len}, count, StartArgs<uint64_t>{k, anchor, pos, queries, n_queries, query, end, start, dist}, err);
+}
+int bitnuc_reads_edist_start_batch(bitnuc_ctx *c, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, int anchor, size_t pos, const uint64_t *queries, size_t n_queries, const uint32_t *query, const uint32_t *end, uint32_t *start, uint8_t *dist, bitnuc_err *err) {
+    return reads_start_host(c, RaggedAscii{seq, offsets}, count, StartArgs<uint64_t>{k, anchor, pos, queries, n_queries, query, end, start, dist}, err);
+}
+int bitnuc_reads_edist_start_batch_packed(bitnuc_ctx *c, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k, int anchor, size_t pos, const uint64_t *queries, size_t n_queries, const uint32_t *query, const uint32_t *end, uint32_t *start, uint8_t *dist, bitnuc_err *err) {
+    return reads_start_host(c, RaggedPacked{words, word_offsets, offsets}, count, StartArgs<uint64_t>{k, anchor, pos, queries, n_queries, query, end, start, dist}, err);
+}
+int bitnuc_reads_pattern_edist_start_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, int anchor, size_t pos, const bitnuc_pattern *d_patterns, size_t n_queries, const uint32_t *d_query, const uint32_t *d_end, uint32_t *d_start, uint8_t *d_dist, bitnuc_err *err) {
+    return reads_start_async(c, FixedAscii{d_reads, read_len}, count, StartArgs<bitnuc_pattern>{k, anchor, pos, d_patterns, n_queries, d_query, d_end, d_start, d_dist}, err);
+}
+int bitnuc_reads_pattern_edist_start_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, int anchor, size_t pos, const bitnuc_pattern *d_patterns, size_t n_queries, const uint32_t *d_query, const uint32_t *d_end, uint32_t *d_start, uint8_t *d_dist, bitnuc_err *err) {
+    return reads_start_async(c, FixedPacked{d_words, read_len}, count, StartArgs<bitnuc_pattern>{k, anchor, pos, d_patterns, n_queries, d_query, d_end, d_start, d_dist}, err);
+}
+int bitnuc_reads_pattern_edist_start_batch_async(bitnuc_ctx *c, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k, int anchor, size_t pos, const bitnuc_pattern *d_patterns, size_t n_queries, const uint32_t *d_query, const uint32_t *d_end, uint32_t *d_start, uint8_t *d_dist, bitnuc_err *err) {
+    return reads_start_async(c, RaggedAscii{d_seq, d_offsets, total_bases, total_bases}, count, StartArgs<bitnuc_pattern>{k, anchor, pos, d_patterns, n_queries, d_query, d_end, d_start, d_dist}, err);
+}
+int bitnuc_reads_pattern_edist_start_batch_packed_async(bitnuc_ctx *c, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count, size_t total_words, size_t k, int anchor, size_t pos, const bitnuc_pattern *d_patterns, size_t n_queries, const uint32_t *d_query, const uint32_t *d_end, uint32_t *d_start, uint8_t *d_dist, bitnuc_err *err) {
+    return reads_start_async(c, RaggedPacked::on_device(d_words, d_word_offsets, d_offsets, total_words), count, StartArgs<bitnuc_pattern>{k, anchor, pos, d_patterns, n_queries, d_query, d_end, d_start, d_dist}, err);
+}
+int bitnuc_reads_pattern_edist_start(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, int anchor, size_t pos, const bitnuc_pattern *patterns, size_t n_queries, const uint32_t *query, const uint32_t *end, uint32_t *start, uint8_t *dist, bitnuc_err *err) {
+    return reads_start_host(c, FixedAscii{reads, read_len}, count, StartArgs<bitnuc_pattern>{k, anchor, pos, patterns, n_queries, query, end, start, dist}, err);
+}
+int bitnuc_reads_pattern_edist_start_packed(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, int anchor, size_t pos, const bitnuc_pattern *patterns, size_t n_queries, const uint32_t *query, const uint32_t *end, uint32_t *start, uint8_t *dist, bitnuc_err *err) {
+    return reads_start_host(c, FixedPacked{words, read_len}, count, StartArgs<bitnuc_pattern>{k, anchor, pos, patterns, n_queries, query, end, start, dist}, err);
+}
+int bitnuc_reads_pattern_edist_start_batch(bitnuc_ctx *c, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, int anchor, size_t pos, const bitnuc_pattern *patterns, size_t n_queries, const uint32_t *query, const uint32_t *end, uint32_t *start, uint8_t *dist, bitnuc_err *err) {
+    return reads_start_host(c, RaggedAscii{seq, offsets}, count, StartArgs<bitnuc_pattern>{k, anchor, pos, patterns, n_queries, query, end, start, dist}, err);
+}
+int bitnuc_reads_pattern_edist_start_batch_packed(bitnuc_ctx *c, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k, int anchor, size_t pos, const bitnuc_pattern *patterns, size_t n_queries, const uint32_t *query, const uint32_t *end, uint32_t *start, uint8_t *dist, bitnuc_err *err) {
+    return reads_start_host(c, RaggedPacked{words, word_offsets, offsets}, count, StartArgs<bitnuc_pattern>{k, anchor, pos, patterns, n_queries, query, end, start, dist}, err);
+}
+int bitnuc_ref_edist_start_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const uint64_t *d_queries, size_t n_queries, const uint32_t *d_query_index, const uint64_t *d_end, size_t m, const uint64_t *d_m, uint64_t *d_start, uint8_t *d_dist, bitnuc_err *err) {
+    return ref_start_async(c, AsciiRef{d_ref, n}, k, RefStartArgs<uint64_t>{d_queries, n_queries, d_query_index, d_end, m, d_m, d_start, d_dist}, err);
+}
+int bitnuc_ref_edist_start_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const uint64_t *d_queries, size_t n_queries, const uint32_t *d_query_index, const uint64_t *d_end, size_t m, const uint64_t *d_m, uint64_t *d_start, uint8_t *d_dist, bitnuc_err *err) {
+    return ref_start_async(c, PackedRef{d_words, n_words, n}, k, RefStartArgs<uint64_t>{d_queries, n_queries, d_query_index, d_end, m, d_m, d_start, d_dist}, err);
+}
+int bitnuc_ref_edist_start(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const uint64_t *queries, size_t n_queries, const uint32_t *query_index, const uint64_t *end, size_t m, uint64_t *start, uint8_t *dist, bitnuc_err *err) {
+    (void)c; // an item reads at most 63 bases: always on the host
+    return ref_start_host(AsciiRef{ref, n}, k, RefStartArgs<uint64_t>{queries, n_queries, query_index, end, m, nullptr, start, dist}, err);
+}
+int bitnuc_ref_edist_start_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const uint64_t *queries, size_t n_queries, const uint32_t *query_index, const uint64_t *end, size_t m, uint64_t *start, uint8_t *dist, bitnuc_err *err) {
+    (void)c;
+    return ref_start_host(PackedRef{words, n_words, n}, k, RefStartArgs<uint64_t>{queries, n_queries, query_index, end, m, nullptr, start, dist}, err);
+}
+int bitnuc_ref_pattern_edist_start_async(bitnuc_ctx *c, const uint8_t *d_ref, size_t n, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries, const uint32_t *d_query_index, const uint64_t *d_end, size_t m, const uint64_t *d_m, uint64_t *d_start, uint8_t *d_dist, bitnuc_err *err) {
+    return ref_start_async(c, AsciiRef{d_ref, n}, k, RefStartArgs<bitnuc_pattern>{d_patterns, n_queries, d_query_index, d_end, m, d_m, d_start, d_dist}, err);
+}
+int bitnuc_ref_pattern_edist_start_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries, const uint32_t *d_query_index, const uint64_t *d_end, size_t m, const uint64_t *d_m, uint64_t *d_start, uint8_t *d_dist, bitnuc_err *err) {
+    return ref_start_async(c, PackedRef{d_words, n_words, n}, k, RefStartArgs<bitnuc_pattern>{d_patterns, n_queries, d_query_index, d_end, m, d_m, d_start, d_dist}, err);
+}
+int bitnuc_ref_pattern_edist_start(bitnuc_ctx *c, const uint8_t *ref, size_t n, size_t k, const bitnuc_pattern *patterns, size_t n_queries, const uint32_t *query_index, const uint64_t *end, size_t m, uint64_t *start, uint8_t *dist, bitnuc_err *err) {
+    (void)c; // an item reads at most 63 bases: always on the host
+    return ref_start_host(AsciiRef{ref, n}, k, RefStartArgs<bitnuc_pattern>{patterns, n_queries, query_index, end, m, nullptr, start, dist}, err);
+}
+int bitnuc_ref_pattern_edist_start_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *patterns, size_t n_queries, const uint32_t *query_index, const uint64_t *end, size_t m, uint64_t *start, uint8_t *dist, bitnuc_err *err) {
+    (void)c;
+    return ref_start_host(PackedRef{words, n_words, n}, k, RefStartArgs<bitnuc_pattern>{patterns, n_queries, query_index, end, m, nullptr, start, dist}, err);
 }
 
 } // extern "C"

@@ -2,7 +2,8 @@
 // (four matchers), one chunk loop, and the two skeletons every entry point is an instantiation of (reads_async, reads_host).  Part of kmer.hip, which
 // includes it once, behind its own helpers (dev_queries, host_queries, multi_work, ascii_skip, packed_skip, bounded_grid, fail_invalid_base, ...).
 // Kernels: scan_reads_device.h, scan_reads_batch_device.h, scan_anchored_device.h, scan_edist_device.h, scan_edist_best_device.h; below the host cutoff:
-// reads_*_host.h.
+// reads_*_host.h.  At the end: the indel-tolerant family's second stage (bitnuc_reads_edist_start*: scan_edist_start_device.h, edist_start_host.h), which
+// shares the layouts and has a skeleton of its own.
 #pragma once
 
 namespace {
@@ -898,6 +899,146 @@ int reads_edist_best_batch_packed_host(bitnuc_ctx *c, const uint64_t *words, con
                                        uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err) {
     const ReadsOut o{best_query, best_end, best_dist, second_dist, second_query, second_end};
     return reads_host(c, RaggedPacked{words, word_offsets, offsets}, count, EditBestMatch<HQ>{k, queries, n_queries, o}, err);
+}
+
+// ---- the indel-tolerant family's second stage: WHERE the alignment that ends at end[r] starts (bitnuc_reads_edist_start*; scan_edist_start_device.h,
+// below the host cutoff edist_start_host.h).  Not a fifth matcher of the skeletons above: it has two per-read INPUTS (query[], end[]) where a matcher has
+// none, its outputs are (start, dist) and not a triple, and a read without bases still has an answer (e = 0: start 0, dist k), so a chunk without data is
+// computed, not filled.  It shares the layouts -- their size check, pointer checks, chunks and staging -- and nothing of the four matchers changes.
+template <class HQ> struct StartArgs {
+    size_t k; int anchor; size_t pos; const HQ *queries; size_t nq; const uint32_t *query, *end; uint32_t *start; uint8_t *dist;
+    bool reads_any() const { return k != 0 && nq != 0; } // otherwise every item is skipped: fills, nothing read, no data pointer looked at
+    int from_end() const { return anchor == BITNUC_ANCHOR_END; }
+};
+
+// the checks after ctx, in the header's order: k, the layout's sizes, the query limit, the anchor, count == 0 (*done), then the pointers
+template <class L, class HQ>
+int check_reads_start(const L &in, size_t count, const StartArgs<HQ> &a, bool *done, bitnuc_err *err) {
+    *done = false;
+    if (a.k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, a.k);
+    if (int st = in.check_size(count, err)) return st;
+    if (a.nq > BITNUC_MAX_QUERIES) return fail(err, BITNUC_UNSUPPORTED, a.nq);
+    if (a.anchor != BITNUC_ANCHOR_START && a.anchor != BITNUC_ANCHOR_END) return fail(err, BITNUC_UNSUPPORTED, (uint64_t)(unsigned)a.anchor);
+    *done = count == 0;
+    if (*done) return BITNUC_OK;
+    const auto odd = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; };
+    if (!a.query || !a.end || !a.start || odd(a.query) || odd(a.end) || odd(a.start) || (!a.queries && a.nq) ||
+        (reinterpret_cast<uintptr_t>(a.queries) & query_mask<HQ>()))
+        return fail(err, BITNUC_UNSUPPORTED);
+    if (!in.tables_ok()) return fail(err, BITNUC_UNSUPPORTED);
+    return BITNUC_OK;
+}
+
+template <class L> auto start_geom(const L &in, int from_end, size_t pos, size_t k) {
+    const unsigned p = pos < 0xFFFFFFFFull ? (unsigned)pos : 0xFFFFFFFFu; // reads are below 2^32 - 1 bases: no end reaches such a floor
+    if constexpr (L::ragged)
+        return StartBatchGeom{reinterpret_cast<const unsigned long long *>(in.offsets), reinterpret_cast<const unsigned long long *>(in.starts()), p, (unsigned)from_end,
+                              (unsigned)k};
+    else return StartFixedGeom{(unsigned long long)in.stride(), (unsigned)in.read_len, p, (unsigned)from_end, (unsigned)k};
+}
+
+// Context scratch: 16 bytes per query (scratch 10, the family's table slot, shared in stream order).  Everything in device memory; count >= 1 (start_grid:
+// kmer.hip)
+template <class L, class HQ>
+int launch_reads_start(bitnuc_ctx *c, const L &in, size_t count, const StartArgs<HQ> &a, unsigned long long *slot, bitnuc_err *err) {
+    u32x4 *tabs = nullptr;
+    if (a.reads_any()) {
+        if (int st = ensure_scratch(c, 10, a.nq * kEdistEntry, err)) return st;
+        tabs = reinterpret_cast<u32x4 *>(c->scratch[10]);
+        edist_tables_kernel<<<(unsigned)((a.nq + 63) / 64), 64, 0, c->stream>>>(dev_queries(a.queries), (unsigned)a.nq, (unsigned)a.k, tabs);
+        HIPCHK(hipGetLastError());
+    }
+    auto g = start_geom(in, a.from_end(), a.pos, a.k ? a.k : 1);
+    edist_start_kernel<L::packed, decltype(g)><<<start_grid(c, count), kEdistBlock, 0, c->stream>>>(
+        reinterpret_cast<const uint8_t *>(in.data), (unsigned long long)count, g, tabs, a.reads_any() ? (unsigned)a.nq : 0u, a.query, a.end, a.start, a.dist, slot);
+    HIPCHK(hipGetLastError());
+    return BITNUC_OK;
+}
+
+template <class L, class HQ>
+int reads_start_async(bitnuc_ctx *c, const L &in, size_t count, const StartArgs<HQ> &a, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    bool done;
+    if (int st = check_reads_start(in, count, a, &done, err)) return st;
+    if (done) return BITNUC_OK;
+    if (a.reads_any() && !in.data_ok()) return fail(err, BITNUC_UNSUPPORTED);
+    DeviceGuard g(c->device);
+    unsigned long long *slot = nullptr;
+    if constexpr (!L::packed)
+        if (a.reads_any())
+            if (int st = take_slot(c, 0, &slot, err)) return st;
+    return launch_reads_start(c, in, count, a, slot, err);
+}
+
+// the host form on the reads [r0, r0 + m): the index of the first invalid walked byte, or -1
+template <class L, class HQ>
+long long reads_start_small(const L &in, size_t r0, size_t m, const StartArgs<HQ> &a) {
+    if constexpr (L::ragged) {
+        const uint64_t *starts = in.starts();
+        return reads_edist_start_batch_small<L::packed>(in.data, starts ? starts + r0 : nullptr, in.offsets + r0, m, a.k, a.from_end(), a.pos, host_queries(a.queries),
+                                                        a.nq, a.query + r0, a.end + r0, a.start + r0, a.dist ? a.dist + r0 : nullptr);
+    } else {
+        const long long bad = reads_edist_start_small<L::packed>(in.data + r0 * in.stride(), in.read_len, m, a.k, a.from_end(), a.pos, host_queries(a.queries), a.nq,
+                                                                 a.query + r0, a.end + r0, a.start + r0, a.dist ? a.dist + r0 : nullptr);
+        return bad < 0 ? bad : bad + (long long)(r0 * in.stride());
+    }
+}
+
+// Below the host cutoff (count x 2k, saturated) the host form runs and no context is needed; above it the layout's chunks of whole reads, with the
+// chunk's query / end staged into scratch 1 and its start / dist staged out of scratch 1 / 3; the queries once in scratch 2
+template <class L, class HQ>
+int reads_start_host(bitnuc_ctx *c, L in, size_t count, const StartArgs<HQ> &a, bitnuc_err *err) {
+    clear_err(err);
+    bool done;
+    if (int st = check_reads_start(in, count, a, &done, err)) return st;
+    if (done) return BITNUC_OK;
+    if constexpr (L::ragged) {
+        const BatchFault f = in.check_tables(count);
+        if (f.kind) return fail_batch_tables(f, err);
+        in.bases = in.offsets[count];
+    }
+    if (a.reads_any() && !in.data_ok()) return fail(err, BITNUC_UNSUPPORTED);
+    if (!a.reads_any() || on_host(c, multi_work(count, 2 * a.k))) {
+        const long long bad = reads_start_small(in, 0, count, a);
+        if constexpr (!L::packed)
+            if (bad >= 0) return fail_invalid_base(err, in.data[bad], (uint64_t)bad);
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    if (int st = ensure_scratch(c, 2, a.nq * sizeof(HQ), err)) return st;
+    HIPCHK(hipMemcpyAsync(c->scratch[2], a.queries, a.nq * sizeof(HQ), hipMemcpyHostToDevice, c->stream));
+    std::vector<uint64_t> tab;
+    for (size_t r0 = 0; r0 < count;) {
+        const size_t m = in.chunk_end(r0, count) - r0;
+        if constexpr (L::ragged) {
+            if (in.chunk_size(r0, m) == 0) { // reads without a base: nothing to stage, e = 0 is their only end
+                reads_start_small(in, r0, m, a);
+                r0 += m;
+                continue;
+            }
+        }
+        if (int st = ensure_scratch(c, 1, 3 * m * 4, err)) return st;
+        if (int st = ensure_scratch(c, 3, m < 64 ? 64 : m, err)) return st;
+        uint32_t *d_query = reinterpret_cast<uint32_t *>(c->scratch[1]), *d_end = d_query + m, *d_start = d_end + m;
+        HIPCHK(hipMemcpyAsync(d_query, a.query + r0, m * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(d_end, a.end + r0, m * 4, hipMemcpyHostToDevice, c->stream));
+        L dev{};
+        unsigned long long base, *slot = nullptr;
+        if (int st = in.stage(c, r0, m, tab, &dev, &base, err)) return st;
+        if constexpr (!L::packed)
+            if (int st = take_slot(c, base, &slot, err)) return st;
+        const StartArgs<HQ> d{a.k, a.anchor, a.pos, reinterpret_cast<const HQ *>(c->scratch[2]), a.nq, d_query, d_end, d_start, a.dist ? c->scratch[3] : nullptr};
+        if (int st = launch_reads_start(c, dev, m, d, slot, err)) return st;
+        HIPCHK(hipMemcpyAsync(a.start + r0, d_start, m * 4, hipMemcpyDeviceToHost, c->stream));
+        if (a.dist) HIPCHK(hipMemcpyAsync(a.dist + r0, c->scratch[3], m, hipMemcpyDeviceToHost, c->stream));
+        bitnuc_err e;
+        if (int st = drain(c, &e)) { if (err) *err = e; return st; }
+        r0 += m;
+    }
+    return BITNUC_OK;
 }
 
 } // namespace

@@ -239,4 +239,70 @@ int ref_host(bitnuc_ctx *c, const In &in, size_t k, const S &s, bitnuc_err *err)
     });
 }
 
+// ---- the indel-tolerant family's second stage along a reference: WHERE the alignments that end at end[0 .. m) start (bitnuc_ref_edist_start*;
+// scan_edist_start_device.h, edist_start_host.h).  Not a search of the skeletons above: its work is m items of at most 63 bases each, not the reference,
+// so there is no window rule, no chunking and no host cutoff -- the host forms always run on the host.  It shares the two inputs' checks.
+template <class HQ> struct RefStartArgs {
+    const HQ *queries; size_t nq; const uint32_t *query_index; const uint64_t *end; size_t m; const uint64_t *d_m; uint64_t *start; uint8_t *dist;
+};
+
+// the checks behind ctx, k and the word count: m == 0 (*done), the query limit, the pointers
+template <class HQ>
+int check_ref_start(const RefStartArgs<HQ> &a, bool *done, bitnuc_err *err) {
+    *done = a.m == 0;
+    if (*done) return BITNUC_OK;
+    if (a.nq > BITNUC_MAX_QUERIES) return fail(err, BITNUC_UNSUPPORTED, a.nq);
+    const auto off = [](const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
+    if (!a.end || !a.start || off(a.end, 7) || off(a.start, 7) || off(a.query_index, 3) || off(a.d_m, 7) || (!a.queries && a.nq) || off(a.queries, query_mask<HQ>()))
+        return fail(err, BITNUC_UNSUPPORTED);
+    return BITNUC_OK;
+}
+
+// Context scratch: 16 bytes per query in scratch 9, the slot the searches along a reference keep their tables in (shared in stream order)
+template <class In, class HQ>
+int ref_start_async(bitnuc_ctx *c, const In &in, size_t k, const RefStartArgs<HQ> &a, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    if (int st = in.check_len(err)) return st;
+    bool done;
+    if (int st = check_ref_start(a, &done, err)) return st;
+    if (done) return BITNUC_OK;
+    const bool reads_any = k != 0 && a.nq != 0; // otherwise every item is skipped: fills, nothing read
+    if (reads_any)
+        if (int st = in.check_ptr(err)) return st;
+    DeviceGuard g(c->device);
+    unsigned long long *slot = nullptr;
+    u32x4 *tabs = nullptr;
+    if (reads_any) {
+        if constexpr (!In::packed) if (int st = take_slot(c, 0, &slot, err)) return st;
+        if (int st = ensure_scratch(c, 9, a.nq * kEdistEntry, err)) return st;
+        tabs = reinterpret_cast<u32x4 *>(c->scratch[9]);
+        edist_tables_kernel<<<(unsigned)((a.nq + 63) / 64), 64, 0, c->stream>>>(dev_queries(a.queries), (unsigned)a.nq, (unsigned)k, tabs);
+        HIPCHK(hipGetLastError());
+    }
+    const StartRefGeom geom{(unsigned long long)in.n, reinterpret_cast<const unsigned long long *>(a.d_m), (unsigned)(k ? k : 1)};
+    edist_start_kernel<In::packed, StartRefGeom><<<start_grid(c, a.m), kEdistBlock, 0, c->stream>>>(
+        reinterpret_cast<const uint8_t *>(in.p), (unsigned long long)a.m, geom, tabs, reads_any ? (unsigned)a.nq : 0u, a.query_index,
+        reinterpret_cast<const unsigned long long *>(a.end), reinterpret_cast<unsigned long long *>(a.start), a.dist, slot);
+    HIPCHK(hipGetLastError());
+    return BITNUC_OK;
+}
+
+template <class In, class HQ>
+int ref_start_host(const In &in, size_t k, const RefStartArgs<HQ> &a, bitnuc_err *err) {
+    clear_err(err);
+    if (k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, k);
+    if (int st = in.check_len(err)) return st;
+    bool done;
+    if (int st = check_ref_start(a, &done, err)) return st;
+    if (done) return BITNUC_OK;
+    if (k != 0 && a.nq != 0)
+        if (int st = in.check_ptr(err)) return st;
+    const long long bad = bitnuc_host::kmer_edist_start_small<In::packed>(in.p, in.n, k, host_queries(a.queries), a.nq, a.query_index, a.end, a.m, a.start, a.dist);
+    if constexpr (!In::packed)
+        if (bad >= 0) return fail_invalid_base(err, in.p[bad], (uint64_t)bad);
+    return BITNUC_OK;
+}
+
 } // namespace

@@ -710,7 +710,7 @@ int bitnuc_reads_pattern_best_batch_packed(bitnuc_ctx *ctx, const uint64_t *word
  * D[i][j-1] + 1).  edist(r, q) = min over 1 <= j <= n of D[k][j]: the Levenshtein distance of the query to the best SUBSTRING of the span, which may
  * start and end anywhere in the span.  end(r, q) = pos_lo + (the smallest such j): an offset in the read, one past the last aligned read base.  "Matches"
  * is equality for an exact query and t_j in S_i for a pattern (bitnuc_reads_pattern_edist_anchored*; an empty set never matches).  edist <= k <= 32, so
- * it fits the uint8_t outputs and never collides with the fill.  The START of the alignment is not reported: it would need a traceback.
+ * it fits the uint8_t outputs and never collides with the fill.  The START of the alignment: bitnuc_reads_edist_start* (the family's second stage, below) with (START, pos_lo).
  * Results.  best_query / best_end / best_dist [r] is the lexicographically smallest (edist, query, end) over all queries; second_*[r] the smallest over
  * the queries other than best_query[r]: an equal duplicate query at a higher index is the runner-up (at the same distance and end), one query gives the
  * fill in the second triple.  For equal arguments best_dist here is <= bitnuc_reads_hdist_anchored*'s best_dist: every window is a substring of the
@@ -741,8 +741,8 @@ int bitnuc_reads_pattern_best_batch_packed(bitnuc_ctx *ctx, const uint64_t *word
  * query, 0.55 / 0.50 at 8, 4.0 / 3.9 at 64, 31.5 / 30.8 at 512; k = 31, eight offsets (n = 38): 0.39 / 0.17, 1.04 / 0.98, 7.8 / 7.7, 62.3 / 61.7 ms:
  * 0.47 - 1.2 x the time of bitnuc_reads_hdist_anchored*_async on the same arguments at 1 query, 2.0 - 3.5 x at 8, 5.5 - 12.3 x at 64, 7.1 - 18.9 x at 512
  * (another answer: the price of indel tolerance); the pattern twins cost what the exact forms cost.
- * The ragged twins (offsets tables): bitnuc_reads_edist_anchored_batch* below.  The whole-read (unanchored) form, for reads of any length: bitnuc_reads_edist_best* below.  Out of scope: reporting the
- * alignment's start, k > 32, anchored spans above 64 bases, affine gaps, reverse-complement queries (callers add the reverse complements to the query list
+ * The ragged twins (offsets tables): bitnuc_reads_edist_anchored_batch* below.  The whole-read (unanchored) form, for reads of any length: bitnuc_reads_edist_best* below.  The alignment's start: bitnuc_reads_edist_start* below.  Out of scope:
+ * k > 32, anchored spans above 64 bases, affine gaps, reverse-complement queries (callers add the reverse complements to the query list
  * themselves). */
 int bitnuc_reads_edist_anchored_async(bitnuc_ctx *ctx, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, size_t pos_lo, size_t pos_hi,
                                       const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end, uint8_t *d_best_dist,
@@ -813,7 +813,7 @@ int bitnuc_reads_pattern_edist_anchored_packed(bitnuc_ctx *ctx, const uint64_t *
  * to 64 queries, 0.97 (ASCII) and 1.03 - 1.05 (packed) x at 512, where the recurrence is all there is.  On equal-length reads the fixed form above gives
  * the same answers; this form takes 1.00 - 1.01 x (ASCII) and 1.06 - 1.08 x (packed) of its time at 64 queries and more: a fixed-length batch belongs
  * there.
- * Out of scope: a per-read offset table as an argument, anchored spans above 64 bases (the whole read: bitnuc_reads_edist_best_batch* below), reporting the alignment's start,
+ * Out of scope: a per-read offset table as an argument, anchored spans above 64 bases (the whole read: bitnuc_reads_edist_best_batch* below; the alignment's start: bitnuc_reads_edist_start_batch* below with (START, pos_lo) or (END, pos_hi)),
  * reverse-complement queries. */
 int bitnuc_reads_edist_anchored_batch_async(bitnuc_ctx *ctx, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k, int anchor,
                                             size_t pos_lo, size_t pos_hi, const uint64_t *d_queries, size_t n_queries, uint32_t *d_best_query, uint32_t *d_best_end,
@@ -882,7 +882,7 @@ int bitnuc_reads_pattern_edist_anchored_batch_packed(bitnuc_ctx *ctx, const uint
  * base), 1.040 - 1.044 (ASCII) and 1.030 - 1.032 (packed) x that of bitnuc_reads_edist_anchored*_async at span 64 in the same queues; 3.8 - 4.2 x the time
  * of bitnuc_reads_hdist_best*_async on the same arguments at 64 queries and more, 3.1 - 3.4 x at 8, 1.1 - 1.6 x at 1 (another answer: the price of indel
  * tolerance); the pattern twins cost what the exact forms cost (0.995 - 1.002 x).
- * Out of scope: the alignment's start (traceback), partial adapters overhanging the 3' end with a minimum-overlap rule, k > 32, affine gaps,
+ * The alignment's start: bitnuc_reads_edist_start* below with (START, 0).  Out of scope: partial adapters overhanging the 3' end with a minimum-overlap rule, k > 32, affine gaps,
  * reverse-complement queries. */
 #define BITNUC_EDIST_MAX_READ 67108864 /* 2^26 bases */
 int bitnuc_reads_edist_best_async(bitnuc_ctx *ctx, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const uint64_t *d_queries, size_t n_queries,
@@ -970,7 +970,7 @@ int bitnuc_reads_pattern_edist_best_batch_packed(bitnuc_ctx *ctx, const uint64_t
  * base j (the substring may start anywhere and may be empty, so E(j) <= k).  "Matches" is equality of the 2-bit codes for an exact query (query bits
  * above 2k are ignored) and membership in position i's set for a bitnuc_pattern (the bitnuc_kmer_pattern_edist_* twins; an empty set matches no base and
  * is legal).  This is bitnuc_reads_edist_anchored's distance with the whole reference as the span, and `end` follows its convention: one past the last
- * aligned base, 1 <= end <= n.  The start of the alignment is not reported.
+ * aligned base, 1 <= end <= n.  The start of the alignment: bitnuc_ref_edist_start* (the family's second stage, below).
  * _best:        dist[q] = the minimum over 1 <= j <= n of E_q(j), end[q] = the smallest j that attains it.  end[0 .. n_queries) and
  *               dist[0 .. n_queries) are written and nothing after them; dist may have any byte offset.  dist[q] <= bitnuc_kmer_hdist_best's.
  * _count_multi: counts[q] = #{ 1 <= j <= n : E_q(j) <= taus[q] }, the number of END POSITIONS of approximate occurrences (one occurrence usually ends
@@ -1061,6 +1061,138 @@ int bitnuc_kmer_pattern_edist_hits(bitnuc_ctx *ctx, const uint8_t *ref, size_t n
                                    uint8_t *hit_dist, size_t cap, uint64_t *n_hits, bitnuc_err *err);
 int bitnuc_kmer_pattern_edist_hits_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *pattern,
                                           unsigned tau, uint64_t *end, uint8_t *hit_dist, size_t cap, uint64_t *n_hits, bitnuc_err *err);
+
+/* ---- The INDEL-TOLERANT family's SECOND STAGE: WHERE the alignment that ends at a given base STARTS -- bitnuc_reads_edist_start*, bitnuc_ref_edist_start*
+ * and their pattern twins.  Every forward form of the family (the anchored, whole-read and ragged per-read forms; best match, count and hit list along a
+ * reference) reports a distance and an END, one past the last aligned base.  With indels the start does not follow from the end: the aligned substring has
+ * between k - dist and k + dist bases.  These calls take (query index, end) per item and write (start, dist); they compose with every forward form, and none
+ * of those changes.  Uses: cutting a read in front of a 3' adapter, cutting out the linker between two barcodes, reporting an off-target site as an
+ * interval, clipping a primer with a bulge.
+ * Definition.  An item has a text t of len bases, a floor a, a query q of 1 <= k <= 32 positions (exact 2-bit, or a bitnuc_pattern) and an end e with
+ * a <= e <= len.  Let w = min(e - a, 2k - 1).  (dist, start) = the lexicographic minimum over s in [e - w, e] of (Lev(q, t[s, e)), e - s), reported as
+ * start = s: the smallest distance and, among the substrings that attain it, the SHORTEST.  Lev is the family's distance (the Levenshtein distance of the
+ * query to that substring; "matches" is equality for an exact query and set membership for a pattern; an empty set matches nothing).  dist <= k;
+ * start == e is legal: the empty substring, dist = k.
+ * The window bound.  A substring of c bases costs at least |c - k| edits, so c >= 2k costs at least k -- what the empty substring (c = 0) costs already, and
+ * a tie goes to the shorter substring: no substring of more than 2k - 1 <= 63 bases can be the answer, and none is looked at.
+ * Identity.  If (q, e, d) is a triple that any forward form wrote and the floor is that form's span start (below), then dist == d: the forward
+ * E(e) = D[k][e] is the minimum over s of Lev(q, t[s, e)) with s at or behind the span's start, and by the window bound that minimum is attained inside
+ * the window.
+ * How it is computed.  No traceback matrix: the family's bit-parallel column step runs BACKWARDS from base e - 1, with the query reversed and a carry-in of 1
+ * on the horizontal delta (row 0 is D'[0][c] = c), so D'[k][c] = Lev(q, t[e - c, e)); the first minimum over c = 0 .. w is the answer.
+ * Reading and validation.  Only the w bases t[e - w, e) of an item are read.  ASCII bytes are validated under bitnuc_reads_edist_anchored*'s rule for span
+ * bytes: the first invalid walked byte in buffer order -> INVALID_BASE with its absolute index, latched once per call for bitnuc_ctx_sync() by the _async
+ * forms (outputs then unspecified; the host forms on the host leave the outputs untouched).  (The ASCII kernel loads the aligned 4-byte words that hold a
+ * walked byte: at most 3 bytes before or after a walked range are touched, never examined.)
+ * Skipped items.  An item is skipped when query >= n_queries (this covers the UINT32_MAX fill of the forward forms), e > len, or e < a; every item is
+ * skipped when k == 0 or n_queries == 0.  A skipped item writes the fill (start UINT32_MAX / UINT64_MAX, dist 0xFF), has nothing read or validated, and no
+ * address is formed from its values.  This is a rule of the contract: the hit list leaves end[*n_hits .. cap) unwritten, and the forward forms write fills
+ * for reads without a window.
+ *
+ * PER READ -- bitnuc_reads_edist_start[_packed], bitnuc_reads_edist_start_batch[_packed], each _async and host, and the bitnuc_reads_pattern_edist_start*
+ * twins.  Layout arguments: those of bitnuc_reads_edist_best* / bitnuc_reads_edist_best_batch* of the same suffix.  Then k, anchor, pos, the queries /
+ * patterns and n_queries of the forward call, and per read: query[r] (the query index, e.g. best_query or second_query), end[r] (e.g. best_end), start[r],
+ * dist[r].  dist may be NULL and is then not written; query, end and start are 4-byte aligned, dist may have any byte offset.  Exactly [0, count) of each
+ * output is written.  Ends and starts count from the read's start.  One (query, end) pair per read and call: the runner-up takes a second call.
+ * Floor of read r, with len its length: BITNUC_ANCHOR_START: a = pos; BITNUC_ANCHOR_END: a = len - k - pos, saturating at 0.  To get the forward form's span
+ * start pass: after the whole-read forms (START, 0); after the fixed anchored forms (START, pos_lo); after the ragged anchored forms (START, pos_lo) or
+ * (END, pos_hi) -- the ragged form's first admissible offset a_r is pos_lo counted from the start, and max(0, len_r - k - pos_hi) counted from the end.
+ * Checks, in order: (1) ctx (_async forms, and the host forms above the cutoff), (2) k > 32 -> SEQUENCE_TOO_LONG (value = k), (3) the layout's size limits
+ * (those of bitnuc_reads_edist_best* / _best_batch*: UNSUPPORTED), (4) n_queries > BITNUC_MAX_QUERIES -> UNSUPPORTED (value = n_queries), (5) anchor neither
+ * BITNUC_ANCHOR_START nor BITNUC_ANCHOR_END -> UNSUPPORTED (value = anchor), (6) count == 0 -> OK, nothing written, (7) query, end or start NULL or not
+ * 4-byte aligned, queries NULL with n_queries > 0 or not 8-byte aligned (patterns: 4-byte), an offsets table NULL or not 8-byte aligned -> UNSUPPORTED,
+ * (8) ragged host forms: the tables' validation, as in bitnuc_reads_hdist_best_batch*, (9) with k >= 1 and n_queries >= 1: reads / words NULL (words not
+ * 8-byte aligned) -> UNSUPPORTED.  Nothing is written on an argument error.
+ * The _async forms have the _dev contract of their family (device pointers for everything, the context's stream, no host synchronisation but the growth of
+ * context scratch; the ragged forms TRUST their tables) and can be captured into a hipGraph after a warm-up with the same or larger n_queries; reads,
+ * queries, query[] and end[] are read at every replay.  Context scratch: 16 bytes per query, in the per-read family's table slot under the same growth rule
+ * -- the forward call and this call share it in stream order.  The host forms are synchronous and judge count x 2k (saturated) against the host cutoff:
+ * below it they run on the host (ctx may be NULL), above it through the context in the layout's chunks of whole reads, with the chunk's query / end staged
+ * in and its start / dist staged out; INVALID_BASE indices stay absolute.
+ *
+ * ALONG A REFERENCE -- bitnuc_ref_edist_start[_packed], each _async and host, and the bitnuc_ref_pattern_edist_start* twins (bitnuc_ref_*, not
+ * bitnuc_kmer_*: those 56 names are the SEARCHES along a reference, one family of arguments and checks; these calls take items).  The text is the reference
+ * (ref, n | words, n_words, n), the floor is 0.  m items: query_index[i] (NULL: every item belongs to query 0 -- the hit list's case; after _best pass
+ * 0 .. n_queries - 1), end[i] (64-bit), start[i] (64-bit), dist[i] (may be NULL).  end and start are 8-byte aligned, query_index 4-byte aligned.  d_m (the
+ * _async forms only) is NULL or a DEVICE count: only the items below min(m, *d_m) are processed and written, nothing at or beyond it is touched -- so
+ * bitnuc_kmer_edist_hits*_async with d_n_hits, followed by this call with m = cap and d_m = d_n_hits, is one capturable chain with no host round trip.
+ * Checks, in order: (1) ctx (_async forms only), (2) k > 32 -> SEQUENCE_TOO_LONG (value = k), (3) packed: n_words < ceil(n / 32) -> INVALID_LENGTH (value =
+ * n), (4) m == 0 -> OK, nothing written, (5) n_queries > BITNUC_MAX_QUERIES -> UNSUPPORTED (value = n_queries), (6) end or start NULL or not 8-byte aligned,
+ * query_index not 4-byte aligned, d_m not 8-byte aligned, queries NULL with n_queries > 0 or not 8-byte aligned (patterns: 4-byte) -> UNSUPPORTED, (7) with
+ * k >= 1 and n_queries >= 1: a NULL reference, or packed words not 8-byte aligned -> UNSUPPORTED.  Nothing is written on an argument error.
+ * The _async forms: the _dev contract; 16 bytes per query of context scratch in the slot the searches along a reference keep their tables in; capturable
+ * after a warm-up with the same or larger n_queries.  The HOST forms always run on the host (ctx is not used and may be NULL): an item reads at most 63
+ * bases, so moving a reference to the device would cost more than the work.
+ * Cost: a vector-ALU kernel, ONE ITEM PER LANE: the lane loads its own query's 16-byte table entry, reverses the four masks within k bits, gathers its w
+ * bases as the anchored kernel gathers a span, and runs at most 63 steps of the recurrence; the loop is wave-uniform over the wave's largest w with Eq
+ * forced to 0 behind a lane's own w, and a wave of equal w runs the unmasked loop.  No LDS, no atomics but the invalid-byte latch.  Measured on 6,666,667
+ * reads (10^9 bases), one MI355X (profiles/r24_edist_start.json), ASCII / packed, against bitnuc_reads_edist_anchored*_async with one query and span 2k - 1
+ * on the same reads: k = 16: 0.29 / 0.16 ms (0.85 / 1.20 x), k = 31: 0.42 / 0.30 ms (0.82 / 1.15 x); behind a forward call of 64 queries the start adds 0.6 -
+ * 4.8 %, behind a hit list along 10^9 bases 0.9 - 1.9 %.
+ * Out of scope: a CIGAR or edit script, collapsing hit runs to local minima, k > 32, affine gaps, reverse-complement queries. */
+int bitnuc_reads_edist_start_async(bitnuc_ctx *ctx, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, int anchor, size_t pos, const uint64_t *d_queries,
+                                   size_t n_queries, const uint32_t *d_query, const uint32_t *d_end, uint32_t *d_start, uint8_t *d_dist, bitnuc_err *err);
+int bitnuc_reads_edist_start_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t read_len, size_t count, size_t k, int anchor, size_t pos, const uint64_t
+                                          *d_queries, size_t n_queries, const uint32_t *d_query, const uint32_t *d_end, uint32_t *d_start, uint8_t *d_dist, bitnuc_err
+                                          *err);
+int bitnuc_reads_edist_start_batch_async(bitnuc_ctx *ctx, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k, int anchor, size_t
+                                         pos, const uint64_t *d_queries, size_t n_queries, const uint32_t *d_query, const uint32_t *d_end, uint32_t *d_start, uint8_t
+                                         *d_dist, bitnuc_err *err);
+int bitnuc_reads_edist_start_batch_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count, size_t
+                                                total_words, size_t k, int anchor, size_t pos, const uint64_t *d_queries, size_t n_queries, const uint32_t *d_query, const
+                                                uint32_t *d_end, uint32_t *d_start, uint8_t *d_dist, bitnuc_err *err);
+int bitnuc_reads_edist_start(bitnuc_ctx *ctx, const uint8_t *reads, size_t read_len, size_t count, size_t k, int anchor, size_t pos, const uint64_t *queries, size_t
+                             n_queries, const uint32_t *query, const uint32_t *end, uint32_t *start, uint8_t *dist, bitnuc_err *err);
+int bitnuc_reads_edist_start_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t read_len, size_t count, size_t k, int anchor, size_t pos, const uint64_t *queries,
+                                    size_t n_queries, const uint32_t *query, const uint32_t *end, uint32_t *start, uint8_t *dist, bitnuc_err *err);
+int bitnuc_reads_edist_start_batch(bitnuc_ctx *ctx, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, int anchor, size_t pos, const uint64_t *queries,
+                                   size_t n_queries, const uint32_t *query, const uint32_t *end, uint32_t *start, uint8_t *dist, bitnuc_err *err);
+int bitnuc_reads_edist_start_batch_packed(bitnuc_ctx *ctx, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k, int
+                                          anchor, size_t pos, const uint64_t *queries, size_t n_queries, const uint32_t *query, const uint32_t *end, uint32_t *start,
+                                          uint8_t *dist, bitnuc_err *err);
+/* the pattern twins */
+int bitnuc_reads_pattern_edist_start_async(bitnuc_ctx *ctx, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, int anchor, size_t pos, const bitnuc_pattern
+                                           *d_patterns, size_t n_queries, const uint32_t *d_query, const uint32_t *d_end, uint32_t *d_start, uint8_t *d_dist, bitnuc_err
+                                           *err);
+int bitnuc_reads_pattern_edist_start_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t read_len, size_t count, size_t k, int anchor, size_t pos, const
+                                                  bitnuc_pattern *d_patterns, size_t n_queries, const uint32_t *d_query, const uint32_t *d_end, uint32_t *d_start, uint8_t
+                                                  *d_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_edist_start_batch_async(bitnuc_ctx *ctx, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k, int anchor,
+                                                 size_t pos, const bitnuc_pattern *d_patterns, size_t n_queries, const uint32_t *d_query, const uint32_t *d_end, uint32_t
+                                                 *d_start, uint8_t *d_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_edist_start_batch_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
+                                                        size_t total_words, size_t k, int anchor, size_t pos, const bitnuc_pattern *d_patterns, size_t n_queries, const
+                                                        uint32_t *d_query, const uint32_t *d_end, uint32_t *d_start, uint8_t *d_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_edist_start(bitnuc_ctx *ctx, const uint8_t *reads, size_t read_len, size_t count, size_t k, int anchor, size_t pos, const bitnuc_pattern
+                                     *patterns, size_t n_queries, const uint32_t *query, const uint32_t *end, uint32_t *start, uint8_t *dist, bitnuc_err *err);
+int bitnuc_reads_pattern_edist_start_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t read_len, size_t count, size_t k, int anchor, size_t pos, const bitnuc_pattern
+                                            *patterns, size_t n_queries, const uint32_t *query, const uint32_t *end, uint32_t *start, uint8_t *dist, bitnuc_err *err);
+int bitnuc_reads_pattern_edist_start_batch(bitnuc_ctx *ctx, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, int anchor, size_t pos, const
+                                           bitnuc_pattern *patterns, size_t n_queries, const uint32_t *query, const uint32_t *end, uint32_t *start, uint8_t *dist,
+                                           bitnuc_err *err);
+int bitnuc_reads_pattern_edist_start_batch_packed(bitnuc_ctx *ctx, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
+                                                  int anchor, size_t pos, const bitnuc_pattern *patterns, size_t n_queries, const uint32_t *query, const uint32_t *end,
+                                                  uint32_t *start, uint8_t *dist, bitnuc_err *err);
+/* ... along a reference */
+int bitnuc_ref_edist_start_async(bitnuc_ctx *ctx, const uint8_t *d_ref, size_t n, size_t k, const uint64_t *d_queries, size_t n_queries, const uint32_t *d_query_index,
+                                  const uint64_t *d_end, size_t m, const uint64_t *d_m, uint64_t *d_start, uint8_t *d_dist, bitnuc_err *err);
+int bitnuc_ref_edist_start_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const uint64_t *d_queries, size_t n_queries, const
+                                         uint32_t *d_query_index, const uint64_t *d_end, size_t m, const uint64_t *d_m, uint64_t *d_start, uint8_t *d_dist, bitnuc_err
+                                         *err);
+int bitnuc_ref_edist_start(bitnuc_ctx *ctx, const uint8_t *ref, size_t n, size_t k, const uint64_t *queries, size_t n_queries, const uint32_t *query_index, const
+                            uint64_t *end, size_t m, uint64_t *start, uint8_t *dist, bitnuc_err *err);
+int bitnuc_ref_edist_start_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t n_words, size_t n, size_t k, const uint64_t *queries, size_t n_queries, const uint32_t
+                                   *query_index, const uint64_t *end, size_t m, uint64_t *start, uint8_t *dist, bitnuc_err *err);
+/* the pattern twins */
+int bitnuc_ref_pattern_edist_start_async(bitnuc_ctx *ctx, const uint8_t *d_ref, size_t n, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries, const uint32_t
+                                          *d_query_index, const uint64_t *d_end, size_t m, const uint64_t *d_m, uint64_t *d_start, uint8_t *d_dist, bitnuc_err *err);
+int bitnuc_ref_pattern_edist_start_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *d_patterns, size_t
+                                                 n_queries, const uint32_t *d_query_index, const uint64_t *d_end, size_t m, const uint64_t *d_m, uint64_t *d_start,
+                                                 uint8_t *d_dist, bitnuc_err *err);
+int bitnuc_ref_pattern_edist_start(bitnuc_ctx *ctx, const uint8_t *ref, size_t n, size_t k, const bitnuc_pattern *patterns, size_t n_queries, const uint32_t
+                                    *query_index, const uint64_t *end, size_t m, uint64_t *start, uint8_t *dist, bitnuc_err *err);
+int bitnuc_ref_pattern_edist_start_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *patterns, size_t n_queries,
+                                           const uint32_t *query_index, const uint64_t *end, size_t m, uint64_t *start, uint8_t *dist, bitnuc_err *err);
 
 /* ---- analysis on packed words (the callers just above the codec) ------ */
 /* BaseCount::base_counts / GCContent::gc_content of a packed sequence

@@ -583,7 +583,7 @@ pub fn reads_pattern_anchored_packed(words: &[u64], read_len: usize, count: usiz
 
 /// The indel-tolerant anchored match: as `reads_hdist_anchored`, with the EDIT distance of each query to the best substring of the read's span
 /// `[pos_lo, min(pos_hi, read_len - k) + k)` (at most 64 bases).  Per read `(query, end, dist)` of the best query and of the runner-up; `end` is an offset
-/// in the read, one past the last aligned base (the alignment's start is not reported).  `dist` is never above `reads_hdist_anchored`'s.
+/// in the read, one past the last aligned base (the alignment's start: `bitnuc_reads_edist_start*` of the C ABI, declared in `ffi`).  `dist` is never above `reads_hdist_anchored`'s.
 pub fn reads_edist_anchored(reads: &[u8], read_len: usize, k: usize, pos_lo: usize, pos_hi: Option<usize>, queries: &[u64]) -> Result<ReadsBest2, NucleotideError> {
     let count = if read_len == 0 { 0 } else { reads.len() / read_len };
     let (mut query, mut end, mut dist) = (vec![0u32; count], vec![0u32; count], vec![0u8; count]);
