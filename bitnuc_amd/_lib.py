@@ -139,6 +139,22 @@ SIGNATURES = {
     "bitnuc_reads_pattern_edist_best_batch_packed_async": (C.c_int, [_P, _P, _P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
     "bitnuc_reads_pattern_edist_best_batch": (C.c_int, [_P, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
     "bitnuc_reads_pattern_edist_best_batch_packed": (C.c_int, [_P, _P, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_edist_adapter_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_edist_adapter_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_edist_adapter_batch_async": (C.c_int, [_P, _P, _P, _SZ, _SZ, _SZ, _P, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_edist_adapter_batch_packed_async": (C.c_int, [_P, _P, _P, _P, _SZ, _SZ, _SZ, _P, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_edist_adapter": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_edist_adapter_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_edist_adapter_batch": (C.c_int, [_P, _P, _P, _SZ, _SZ, _P, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_edist_adapter_batch_packed": (C.c_int, [_P, _P, _P, _P, _SZ, _SZ, _P, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_pattern_edist_adapter_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_pattern_edist_adapter_packed_async": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_pattern_edist_adapter_batch_async": (C.c_int, [_P, _P, _P, _SZ, _SZ, _SZ, _P, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_pattern_edist_adapter_batch_packed_async": (C.c_int, [_P, _P, _P, _P, _SZ, _SZ, _SZ, _P, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_pattern_edist_adapter": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_pattern_edist_adapter_packed": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_pattern_edist_adapter_batch": (C.c_int, [_P, _P, _P, _SZ, _SZ, _P, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _ERR]),
+    "bitnuc_reads_pattern_edist_adapter_batch_packed": (C.c_int, [_P, _P, _P, _P, _SZ, _SZ, _P, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _ERR]),
     "bitnuc_pattern_from_iupac": (C.c_int, [_P, _SZ, _P, _ERR]),
     "bitnuc_pattern_from_2bit": (C.c_int, [_U64, _SZ, _P, _ERR]),
     "bitnuc_kmer_pattern_count_multi_async": (C.c_int, [_P, _P, _SZ, _SZ, _P, _P, _SZ, _P, _ERR]),

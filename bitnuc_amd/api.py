@@ -907,6 +907,65 @@ class Context:
                                       second, int(k))
         return self._append_starts(res, lambda q, e: self.reads_pattern_edist_start_batch_packed(w, woff, off, k, patterns, q, e, "start", 0)) if with_start else res
 
+    # -- the 3' adapter per read: of Q adapters the one a read carries in full anywhere or as a prefix overhanging its end, within floor(i x num / den)
+    # edits over i matched-against adapter positions, and the base to cut at.  (adapter, cut, end, overlap, dist); no admissible candidate: 2^32 - 1 x 3, 255 x 2 --
+    def _reads_adapter(self, fn, head, count, queries, min_overlap, rate, pattern_k=None):  # rate: (err_num, err_den)
+        q, nq = self._reads_queries(queries, pattern_k)
+        num, den = rate
+        out = [np.empty(count, dtype=t) for t in (np.uint32, np.uint32, np.uint32, np.uint8, np.uint8)]
+        err = L.BitnucErr()
+        if fn(self._h, *head, _ptr(q), nq, int(min_overlap), int(num), int(den), *(_ptr(a) for a in out), C.byref(err)) != L.OK:
+            _raise(err)
+        return tuple(out)
+
+    def reads_edist_adapter(self, reads, read_len, k, queries, min_overlap=3, err_num=1, err_den=10, count=None):
+        """The 3' adapter per read of a fixed-length batch: (adapter, cut, end, overlap, dist).  A candidate is a FULL adapter ending at any base of the
+        read (overlap = k) or its first `overlap` positions, min_overlap <= overlap < k, aligned to the read's END; it is admissible within
+        floor(overlap x err_num / err_den) edits.  The winner has the most matched adapter positions, then the fewest edits, the lower index, the first
+        end; read[:cut] is what a trimmer keeps, dist the edit distance of the adapter's prefix to read[cut:end]."""
+        s, read_len, count = self._fixed_reads(reads, read_len, count)
+        return self._reads_adapter(self._lib.bitnuc_reads_edist_adapter, (_ptr(s), read_len, count, int(k)), count, queries, min_overlap, (err_num, err_den))
+
+    def reads_edist_adapter_packed(self, words, read_len, count, k, queries, min_overlap=3, err_num=1, err_den=10):
+        """reads_edist_adapter of the packed words encode_fixed writes (ceil(read_len / 32) words per read), without decoding them."""
+        w, read_len, count = self._fixed_words(words, read_len, count)
+        return self._reads_adapter(self._lib.bitnuc_reads_edist_adapter_packed, (_ptr(w), read_len, count, int(k)), count, queries, min_overlap, (err_num, err_den))
+
+    def reads_pattern_edist_adapter(self, reads, read_len, k, patterns, min_overlap=3, err_num=1, err_den=10, count=None):
+        """reads_edist_adapter under pattern queries: a read base matches adapter position i when it is in the position's set."""
+        s, read_len, count = self._fixed_reads(reads, read_len, count)
+        return self._reads_adapter(self._lib.bitnuc_reads_pattern_edist_adapter, (_ptr(s), read_len, count, int(k)), count, patterns, min_overlap, (err_num, err_den), int(k))
+
+    def reads_pattern_edist_adapter_packed(self, words, read_len, count, k, patterns, min_overlap=3, err_num=1, err_den=10):
+        """reads_pattern_edist_adapter of the packed words encode_fixed writes, without decoding them."""
+        w, read_len, count = self._fixed_words(words, read_len, count)
+        return self._reads_adapter(self._lib.bitnuc_reads_pattern_edist_adapter_packed, (_ptr(w), read_len, count, int(k)), count, patterns, min_overlap,
+                                   (err_num, err_den), int(k))
+
+    def reads_edist_adapter_batch(self, seq, offsets, k, queries, min_overlap=3, err_num=1, err_den=10):
+        """reads_edist_adapter of a ragged batch (read r is seq[offsets[r]:offsets[r + 1]]): each read over its own length; a read shorter than k gets
+        the fill and is neither read nor validated."""
+        s, off, count = self._ragged_reads(seq, offsets)
+        return self._reads_adapter(self._lib.bitnuc_reads_edist_adapter_batch, (_ptr(s), _ptr(off), count, int(k)), count, queries, min_overlap, (err_num, err_den))
+
+    def reads_edist_adapter_batch_packed(self, words, word_offsets, offsets, k, queries, min_overlap=3, err_num=1, err_den=10):
+        """reads_edist_adapter_batch of the packed words encode_batch writes (read r's ceil(len_r / 32) words start at words[word_offsets[r]])."""
+        w, woff, off, count = self._ragged_words(words, word_offsets, offsets)
+        return self._reads_adapter(self._lib.bitnuc_reads_edist_adapter_batch_packed, (_ptr(w), _ptr(woff), _ptr(off), count, int(k)), count, queries,
+                                   min_overlap, (err_num, err_den))
+
+    def reads_pattern_edist_adapter_batch(self, seq, offsets, k, patterns, min_overlap=3, err_num=1, err_den=10):
+        """reads_edist_adapter_batch under pattern queries."""
+        s, off, count = self._ragged_reads(seq, offsets)
+        return self._reads_adapter(self._lib.bitnuc_reads_pattern_edist_adapter_batch, (_ptr(s), _ptr(off), count, int(k)), count, patterns, min_overlap,
+                                   (err_num, err_den), int(k))
+
+    def reads_pattern_edist_adapter_batch_packed(self, words, word_offsets, offsets, k, patterns, min_overlap=3, err_num=1, err_den=10):
+        """reads_pattern_edist_adapter_batch of the packed words encode_batch writes, without decoding them."""
+        w, woff, off, count = self._ragged_words(words, word_offsets, offsets)
+        return self._reads_adapter(self._lib.bitnuc_reads_pattern_edist_adapter_batch_packed, (_ptr(w), _ptr(woff), _ptr(off), count, int(k)), count, patterns,
+                                   min_overlap, (err_num, err_den), int(k))
+
     # -- the indel-tolerant family's second stage: WHERE the alignment that ends at end[r] starts.  Per item (query index, end) -> (start, dist): the smallest
     # edit distance of the query to a substring t[s, end) with s at or behind the floor and, among those, the shortest; dist equals the forward form's when
     # the floor is its span start.  A skipped item (query >= Q, end beyond the read or in front of the floor) gets 2^32 - 1 (2^64 - 1), 255 --
@@ -1494,6 +1553,61 @@ class Context:
         self._reads_edist_batch_async(self._lib.bitnuc_reads_pattern_edist_anchored_batch_packed_async,
                                       (_dev_ptr(d_words), _dev_ptr(d_word_offsets), _dev_ptr(d_offsets), int(count), int(total_words)), k, d_patterns, n_queries,
                                       (d_best_query, d_best_end, d_best_dist), (d_second_query, d_second_end, d_second_dist), pos_lo, pos_hi, anchor)
+
+    def _reads_adapter_async(self, fn, head, k, d_queries, n_queries, min_overlap, rate, d_out):
+        self._call_dev(fn, *head, int(k), _dev_ptr(d_queries), int(n_queries), int(min_overlap), int(rate[0]), int(rate[1]), *(_dev_ptr(a) for a in d_out))
+
+    def reads_edist_adapter_async(self, d_reads, read_len, count, k, d_queries, n_queries, d_adapter, d_cut, d_end, d_overlap, d_dist, min_overlap=3,
+                                  err_num=1, err_den=10):
+        """reads_edist_adapter on device tensors, asynchronous on the context's stream (five outputs, all required); an invalid byte is reported by
+        the next sync()."""
+        self._reads_adapter_async(self._lib.bitnuc_reads_edist_adapter_async, (_dev_ptr(d_reads), int(read_len), int(count)), k, d_queries, n_queries,
+                                  min_overlap, (err_num, err_den), (d_adapter, d_cut, d_end, d_overlap, d_dist))
+
+    def reads_edist_adapter_packed_async(self, d_words, read_len, count, k, d_queries, n_queries, d_adapter, d_cut, d_end, d_overlap, d_dist, min_overlap=3,
+                                         err_num=1, err_den=10):
+        """reads_edist_adapter_async of packed words (ceil(read_len / 32) per read)."""
+        self._reads_adapter_async(self._lib.bitnuc_reads_edist_adapter_packed_async, (_dev_ptr(d_words), int(read_len), int(count)), k, d_queries, n_queries,
+                                  min_overlap, (err_num, err_den), (d_adapter, d_cut, d_end, d_overlap, d_dist))
+
+    def reads_pattern_edist_adapter_async(self, d_reads, read_len, count, k, d_patterns, n_queries, d_adapter, d_cut, d_end, d_overlap, d_dist, min_overlap=3,
+                                          err_num=1, err_den=10):
+        """reads_edist_adapter_async under pattern queries."""
+        self._reads_adapter_async(self._lib.bitnuc_reads_pattern_edist_adapter_async, (_dev_ptr(d_reads), int(read_len), int(count)), k, d_patterns, n_queries,
+                                  min_overlap, (err_num, err_den), (d_adapter, d_cut, d_end, d_overlap, d_dist))
+
+    def reads_pattern_edist_adapter_packed_async(self, d_words, read_len, count, k, d_patterns, n_queries, d_adapter, d_cut, d_end, d_overlap, d_dist,
+                                                 min_overlap=3, err_num=1, err_den=10):
+        """reads_edist_adapter_packed_async under pattern queries."""
+        self._reads_adapter_async(self._lib.bitnuc_reads_pattern_edist_adapter_packed_async, (_dev_ptr(d_words), int(read_len), int(count)), k, d_patterns,
+                                  n_queries, min_overlap, (err_num, err_den), (d_adapter, d_cut, d_end, d_overlap, d_dist))
+
+    def reads_edist_adapter_batch_async(self, d_seq, d_offsets, count, total_bases, k, d_queries, n_queries, d_adapter, d_cut, d_end, d_overlap, d_dist,
+                                        min_overlap=3, err_num=1, err_den=10):
+        """reads_edist_adapter_batch on device tensors (the layout arguments of reads_edist_best_batch_async), asynchronous on the context's stream; the
+        table is trusted and read on the device; an invalid byte is reported by the next sync()."""
+        self._reads_adapter_async(self._lib.bitnuc_reads_edist_adapter_batch_async, (_dev_ptr(d_seq), _dev_ptr(d_offsets), int(count), int(total_bases)), k,
+                                  d_queries, n_queries, min_overlap, (err_num, err_den), (d_adapter, d_cut, d_end, d_overlap, d_dist))
+
+    def reads_edist_adapter_batch_packed_async(self, d_words, d_word_offsets, d_offsets, count, total_words, k, d_queries, n_queries, d_adapter, d_cut, d_end,
+                                               d_overlap, d_dist, min_overlap=3, err_num=1, err_den=10):
+        """reads_edist_adapter_batch_async on the packed words encode_batch_dev writes (8-byte aligned; both tables u64 in device memory, trusted)."""
+        self._reads_adapter_async(self._lib.bitnuc_reads_edist_adapter_batch_packed_async,
+                                  (_dev_ptr(d_words), _dev_ptr(d_word_offsets), _dev_ptr(d_offsets), int(count), int(total_words)), k, d_queries, n_queries,
+                                  min_overlap, (err_num, err_den), (d_adapter, d_cut, d_end, d_overlap, d_dist))
+
+    def reads_pattern_edist_adapter_batch_async(self, d_seq, d_offsets, count, total_bases, k, d_patterns, n_queries, d_adapter, d_cut, d_end, d_overlap,
+                                                d_dist, min_overlap=3, err_num=1, err_den=10):
+        """reads_edist_adapter_batch_async under pattern queries."""
+        self._reads_adapter_async(self._lib.bitnuc_reads_pattern_edist_adapter_batch_async, (_dev_ptr(d_seq), _dev_ptr(d_offsets), int(count), int(total_bases)),
+                                  k, d_patterns, n_queries, min_overlap, (err_num, err_den), (d_adapter, d_cut, d_end, d_overlap, d_dist))
+
+    def reads_pattern_edist_adapter_batch_packed_async(self, d_words, d_word_offsets, d_offsets, count, total_words, k, d_patterns, n_queries, d_adapter, d_cut,
+                                                       d_end, d_overlap, d_dist, min_overlap=3, err_num=1, err_den=10):
+        """reads_edist_adapter_batch_packed_async under pattern queries."""
+        self._reads_adapter_async(self._lib.bitnuc_reads_pattern_edist_adapter_batch_packed_async,
+                                  (_dev_ptr(d_words), _dev_ptr(d_word_offsets), _dev_ptr(d_offsets), int(count), int(total_words)), k, d_patterns, n_queries,
+                                  min_overlap, (err_num, err_den), (d_adapter, d_cut, d_end, d_overlap, d_dist))
 
     def _reads_edist_best_async(self, fn, head, k, d_queries, n_queries, d_best, d_second):
         self._call_dev(fn, *head, int(k), _dev_ptr(d_queries), int(n_queries), *(_dev_ptr(a) for a in d_best), *(_dev_ptr(a) for a in d_second))

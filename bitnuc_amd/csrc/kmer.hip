@@ -3,7 +3,7 @@
 // Hamming scan (config 5: packing/mod.rs:80-110 o hamming/scalar.rs:11-48) and bulk hdist (hamming/multi.rs:121-160).
 // Kernels: kmer_device.h; config 5 on the matrix cores: scan_mfma_device.h; the same scan and count on packed words: scan_packed_device.h; the hit
 // lists of both: scan_hits_device.h; the count for many queries at once: scan_multi_device.h; the best match per query: scan_best_device.h; the mismatch histogram per query: scan_hist_device.h; the best match per read of a
-// fixed-length batch: scan_reads_device.h; ... of a ragged batch: scan_reads_batch_device.h; the indel-tolerant search along a reference: scan_edist_ref_device.h, its hit list: scan_edist_hits_device.h; where an alignment starts: scan_edist_start_device.h.  The launchers, their argument checks and the host forms' chunk loops are here; the host side of the searches
+// fixed-length batch: scan_reads_device.h; ... of a ragged batch: scan_reads_batch_device.h; the indel-tolerant search along a reference: scan_edist_ref_device.h, its hit list: scan_edist_hits_device.h; where an alignment starts: scan_edist_start_device.h; the 3' adapter per read: scan_edist_adapter_device.h.  The launchers, their argument checks and the host forms' chunk loops are here; the host side of the searches
 // along a reference -- inputs, searches, the two skeletons -- is ref_dispatch.h, that of every per-read matcher reads_dispatch.h.
 #include "runtime.h"
 
@@ -23,6 +23,7 @@
 #include "scan_edist_ref_device.h"
 #include "scan_edist_hits_device.h"
 #include "scan_edist_start_device.h"
+#include "scan_edist_adapter_device.h"
 #include "scan_hist_device.h"
 #include "scan_mfma_host.h"
 #include "scan_hits_host.h"
@@ -36,6 +37,7 @@
 #include "reads_edist_best_host.h"
 #include "kmer_edist_host.h"
 #include "edist_start_host.h"
+#include "reads_edist_adapter_host.h"
 #include "reads_batch_host.h"
 #include "scan_hist_host.h"
 #include "pattern_host.h"
@@ -1684,6 +1686,56 @@ int bitnuc_kmer_pattern_edist_hits(bitnuc_ctx *c, const uint8_t *ref, size_t n, 
 int bitnuc_kmer_pattern_edist_hits_packed(bitnuc_ctx *c, const uint64_t *words, size_t n_words, size_t n, size_t k, const bitnuc_pattern *pattern, unsigned tau, uint64_t *end,
                                           uint8_t *hit_dist, size_t cap, uint64_t *n_hits, bitnuc_err *err) {
     return ref_host(c, PackedRef{words, n_words, n}, k, EdistHits<bitnuc_pattern>{pattern, tau, end, hit_dist, cap, n_hits}, err);
+}
+
+// ---- the 3' adapter per read: full or overhanging match, with the cut point (reads_dispatch.h) ----
+int bitnuc_reads_edist_adapter_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const uint64_t *d_queries, size_t n_queries, size_t min_overlap, size_t err_num, size_t err_den, uint32_t *d_adapter, uint32_t *d_cut, uint32_t *d_end, uint8_t *d_overlap, uint8_t *d_dist, bitnuc_err *err) {
+    return reads_adapter_async(c, FixedAscii{d_reads, read_len}, count, AdapterArgs<uint64_t>{k, d_queries, n_queries, min_overlap, err_num, err_den, {d_adapter, d_cut, d_end, d_overlap, d_dist}}, err);
+}
+int bitnuc_reads_edist_adapter_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, const uint64_t *d_queries, size_t n_queries, size_t min_overlap, size_t err_num, size_t err_den, uint32_t *d_adapter, uint32_t *d_cut, uint32_t *d_end, uint8_t *d_overlap, uint8_t *d_dist, bitnuc_err *err) {
+    return reads_adapter_async(c, FixedPacked{d_words, read_len}, count, AdapterArgs<uint64_t>{k, d_queries, n_queries, min_overlap, err_num, err_den, {d_adapter, d_cut, d_end, d_overlap, d_dist}}, err);
+}
+int bitnuc_reads_edist_adapter_batch_async(bitnuc_ctx *c, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k, const uint64_t *d_queries, size_t n_queries, size_t min_overlap, size_t err_num, size_t err_den, uint32_t *d_adapter, uint32_t *d_cut, uint32_t *d_end, uint8_t *d_overlap, uint8_t *d_dist, bitnuc_err *err) {
+    return reads_adapter_async(c, RaggedAscii{d_seq, d_offsets, total_bases, total_bases}, count, AdapterArgs<uint64_t>{k, d_queries, n_queries, min_overlap, err_num, err_den, {d_adapter, d_cut, d_end, d_overlap, d_dist}}, err);
+}
+int bitnuc_reads_edist_adapter_batch_packed_async(bitnuc_ctx *c, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count, size_t total_words, size_t k, const uint64_t *d_queries, size_t n_queries, size_t min_overlap, size_t err_num, size_t err_den, uint32_t *d_adapter, uint32_t *d_cut, uint32_t *d_end, uint8_t *d_overlap, uint8_t *d_dist, bitnuc_err *err) {
+    return reads_adapter_async(c, RaggedPacked::on_device(d_words, d_word_offsets, d_offsets, total_words), count, AdapterArgs<uint64_t>{k, d_queries, n_queries, min_overlap, err_num, err_den, {d_adapter, d_cut, d_end, d_overlap, d_dist}}, err);
+}
+int bitnuc_reads_edist_adapter(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, const uint64_t *queries, size_t n_queries, size_t min_overlap, size_t err_num, size_t err_den, uint32_t *adapter, uint32_t *cut, uint32_t *end, uint8_t *overlap, uint8_t *dist, bitnuc_err *err) {
+    return reads_adapter_host(c, FixedAscii{reads, read_len}, count, AdapterArgs<uint64_t>{k, queries, n_queries, min_overlap, err_num, err_den, {adapter, cut, end, overlap, dist}}, err);
+}
+int bitnuc_reads_edist_adapter_packed(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, const uint64_t *queries, size_t n_queries, size_t min_overlap, size_t err_num, size_t err_den, uint32_t *adapter, uint32_t *cut, uint32_t *end, uint8_t *overlap, uint8_t *dist, bitnuc_err *err) {
+    return reads_adapter_host(c, FixedPacked{words, read_len}, count, AdapterArgs<uint64_t>{k, queries, n_queries, min_overlap, err_num, err_den, {adapter, cut, end, overlap, dist}}, err);
+}
+int bitnuc_reads_edist_adapter_batch(bitnuc_ctx *c, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, const uint64_t *queries, size_t n_queries, size_t min_overlap, size_t err_num, size_t err_den, uint32_t *adapter, uint32_t *cut, uint32_t *end, uint8_t *overlap, uint8_t *dist, bitnuc_err *err) {
+    return reads_adapter_host(c, RaggedAscii{seq, offsets}, count, AdapterArgs<uint64_t>{k, queries, n_queries, min_overlap, err_num, err_den, {adapter, cut, end, overlap, dist}}, err);
+}
+int bitnuc_reads_edist_adapter_batch_packed(bitnuc_ctx *c, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k, const uint64_t *queries, size_t n_queries, size_t min_overlap, size_t err_num, size_t err_den, uint32_t *adapter, uint32_t *cut, uint32_t *end, uint8_t *overlap, uint8_t *dist, bitnuc_err *err) {
+    return reads_adapter_host(c, RaggedPacked{words, word_offsets, offsets}, count, AdapterArgs<uint64_t>{k, queries, n_queries, min_overlap, err_num, err_den, {adapter, cut, end, overlap, dist}}, err);
+}
+int bitnuc_reads_pattern_edist_adapter_async(bitnuc_ctx *c, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries, size_t min_overlap, size_t err_num, size_t err_den, uint32_t *d_adapter, uint32_t *d_cut, uint32_t *d_end, uint8_t *d_overlap, uint8_t *d_dist, bitnuc_err *err) {
+    return reads_adapter_async(c, FixedAscii{d_reads, read_len}, count, AdapterArgs<bitnuc_pattern>{k, d_patterns, n_queries, min_overlap, err_num, err_den, {d_adapter, d_cut, d_end, d_overlap, d_dist}}, err);
+}
+int bitnuc_reads_pattern_edist_adapter_packed_async(bitnuc_ctx *c, const uint64_t *d_words, size_t read_len, size_t count, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries, size_t min_overlap, size_t err_num, size_t err_den, uint32_t *d_adapter, uint32_t *d_cut, uint32_t *d_end, uint8_t *d_overlap, uint8_t *d_dist, bitnuc_err *err) {
+    return reads_adapter_async(c, FixedPacked{d_words, read_len}, count, AdapterArgs<bitnuc_pattern>{k, d_patterns, n_queries, min_overlap, err_num, err_den, {d_adapter, d_cut, d_end, d_overlap, d_dist}}, err);
+}
+int bitnuc_reads_pattern_edist_adapter_batch_async(bitnuc_ctx *c, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries, size_t min_overlap, size_t err_num, size_t err_den, uint32_t *d_adapter, uint32_t *d_cut, uint32_t *d_end, uint8_t *d_overlap, uint8_t *d_dist, bitnuc_err *err) {
+    return reads_adapter_async(c, RaggedAscii{d_seq, d_offsets, total_bases, total_bases}, count, AdapterArgs<bitnuc_pattern>{k, d_patterns, n_queries, min_overlap, err_num, err_den, {d_adapter, d_cut, d_end, d_overlap, d_dist}}, err);
+}
+int bitnuc_reads_pattern_edist_adapter_batch_packed_async(bitnuc_ctx *c, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count, size_t total_words, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries, size_t min_overlap, size_t err_num, size_t err_den, uint32_t *d_adapter, uint32_t *d_cut, uint32_t *d_end, uint8_t *d_overlap, uint8_t *d_dist, bitnuc_err *err) {
+    return reads_adapter_async(c, RaggedPacked::on_device(d_words, d_word_offsets, d_offsets, total_words), count, AdapterArgs<bitnuc_pattern>{k, d_patterns, n_queries, min_overlap, err_num, err_den, {d_adapter, d_cut, d_end, d_overlap, d_dist}}, err);
+}
+int bitnuc_reads_pattern_edist_adapter(bitnuc_ctx *c, const uint8_t *reads, size_t read_len, size_t count, size_t k, const bitnuc_pattern *patterns, size_t n_queries, size_t min_overlap, size_t err_num, size_t err_den, uint32_t *adapter, uint32_t *cut, uint32_t *end, uint8_t *overlap, uint8_t *dist, bitnuc_err *err) {
+    return reads_adapter_host(c, FixedAscii{reads, read_len}, count, AdapterArgs<bitnuc_pattern>{k, patterns, n_queries, min_overlap, err_num, err_den, {adapter, cut, end, overlap, dist}}, err);
+}
+int bitnuc_reads_pattern_edist_adapter_packed(bitnuc_ctx *c, const uint64_t *words, size_t read_len, size_t count, size_t k, const bitnuc_pattern *patterns, size_t n_queries, size_t min_overlap, size_t err_num, size_t err_den, uint32_t *adapter, uint32_t *cut, uint32_t *end, uint8_t *overlap, uint8_t *dist, bitnuc_err *err) {
+    return reads_adapter_host(c, FixedPacked{words, read_len}, count, AdapterArgs<bitnuc_pattern>{k, patterns, n_queries, min_overlap, err_num, err_den, {adapter, cut, end, overlap, dist}}, err);
+}
+int bitnuc_reads_pattern_edist_adapter_batch(bitnuc_ctx *c, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, const bitnuc_pattern *patterns, size_t n_queries, size_t min_overlap, size_t err_num, size_t err_den, uint32_t *adapter, uint32_t *cut, uint32_t *end, uint8_t *overlap, uint8_t *dist, bitnuc_err *err) {
+    return reads_adapter_host(c, RaggedAscii{seq, offsets}, count, AdapterArgs<bitnuc_pattern>{k, patterns, n_queries, min_overlap, err_num, err_den, {adapter, cut, end, overlap, dist}}, err);
+}
+int bitnuc_reads_pattern_edist_adapter_batch_packed(bitnuc_ctx *c, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k, const bitnuc_pattern *patterns, size_t n_queries, size_t min_overlap, size_t err_num, size_t err_den, uint32_t *adapter, uint32_t *cut, uint32_t *end, uint8_t *overlap, uint8_t *dist, bitnuc_err *err) {
+    return reads_adapter_host(c, RaggedPacked{words, word_offsets, offsets}, count, AdapterArgs<bitnuc_pattern>{k, patterns, n_queries, min_overlap, err_num, err_den, {adapter, cut, end, overlap, dist}}, err);
 }
 
 // ---- the indel-tolerant family's second stage: where the alignment that ends at a given base starts (reads_dispatch.h, ref_dispatch.h) ----

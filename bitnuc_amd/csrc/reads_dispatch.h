@@ -3,7 +3,8 @@
 // includes it once, behind its own helpers (dev_queries, host_queries, multi_work, ascii_skip, packed_skip, bounded_grid, fail_invalid_base, ...).
 // Kernels: scan_reads_device.h, scan_reads_batch_device.h, scan_anchored_device.h, scan_edist_device.h, scan_edist_best_device.h; below the host cutoff:
 // reads_*_host.h.  At the end: the indel-tolerant family's second stage (bitnuc_reads_edist_start*: scan_edist_start_device.h, edist_start_host.h), which
-// shares the layouts and has a skeleton of its own.
+// shares the layouts and has a skeleton of its own, and the 3' adapter per read (bitnuc_reads_edist_adapter*: scan_edist_adapter_device.h,
+// reads_edist_adapter_host.h), which has five outputs and a rule and a skeleton of its own as well.
 #pragma once
 
 namespace {
@@ -1034,6 +1035,168 @@ int reads_start_host(bitnuc_ctx *c, L in, size_t count, const StartArgs<HQ> &a, 
         if (int st = launch_reads_start(c, dev, m, d, slot, err)) return st;
         HIPCHK(hipMemcpyAsync(a.start + r0, d_start, m * 4, hipMemcpyDeviceToHost, c->stream));
         if (a.dist) HIPCHK(hipMemcpyAsync(a.dist + r0, c->scratch[3], m, hipMemcpyDeviceToHost, c->stream));
+        bitnuc_err e;
+        if (int st = drain(c, &e)) { if (err) *err = e; return st; }
+        r0 += m;
+    }
+    return BITNUC_OK;
+}
+
+// ---- the 3' ADAPTER per read (bitnuc_reads_edist_adapter*; scan_edist_adapter_device.h, below the host cutoff reads_edist_adapter_host.h): the whole-read
+// matcher's layouts, limits, work and chunks with FIVE outputs and a rule (min_overlap, err_num / err_den).  A skeleton of its own, as the second stage
+// has: ReadsOut is a pair of triples and stays one.
+struct AdapterOut { uint32_t *adapter, *cut, *end; uint8_t *overlap, *dist; };
+
+template <class HQ> struct AdapterArgs {
+    size_t k; const HQ *queries; size_t nq, min_overlap, err_num, err_den; AdapterOut o;
+    EditBestMatch<HQ> whole() const { return EditBestMatch<HQ>{k, queries, nq, ReadsOut{nullptr, nullptr, nullptr}}; } // its limits, no-window rule and work
+};
+
+// the checks after ctx, in the header's order: k, the layout's sizes, the query limit, the rule (k >= 1), the read length, count == 0 (*done), the pointers
+template <class L, class HQ>
+int check_reads_adapter(const L &in, size_t count, const AdapterArgs<HQ> &a, bool *done, bitnuc_err *err) {
+    *done = false;
+    if (a.k > 32) return fail(err, BITNUC_SEQUENCE_TOO_LONG, a.k);
+    if (int st = in.check_size(count, err)) return st;
+    if (a.nq > BITNUC_MAX_QUERIES) return fail(err, BITNUC_UNSUPPORTED, a.nq);
+    if (a.k >= 1) {
+        if (a.min_overlap == 0 || a.min_overlap > a.k) return fail(err, BITNUC_UNSUPPORTED, a.min_overlap);
+        if (a.err_den == 0 || a.err_num > a.err_den) return fail(err, BITNUC_UNSUPPORTED, a.err_num);
+    }
+    if (int st = a.whole().check_range(in, err)) return st;
+    *done = count == 0;
+    if (*done) return BITNUC_OK;
+    const auto odd = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; };
+    const AdapterOut &o = a.o;
+    if (!o.adapter || !o.cut || !o.end || !o.overlap || !o.dist || odd(o.adapter) || odd(o.cut) || odd(o.end) || (!a.queries && a.nq) ||
+        (reinterpret_cast<uintptr_t>(a.queries) & query_mask<HQ>()))
+        return fail(err, BITNUC_UNSUPPORTED);
+    if (!in.tables_ok()) return fail(err, BITNUC_UNSUPPORTED);
+    return BITNUC_OK;
+}
+
+inline void adapter_fill_host(size_t count, const AdapterOut &o) { bitnuc_host::adapter_fill(count, o.adapter, o.cut, o.end, o.overlap, o.dist); }
+
+inline int adapter_fill_dev(bitnuc_ctx *c, size_t count, const AdapterOut &o, bitnuc_err *err) {
+    HIPCHK(hipMemsetAsync(o.adapter, 0xFF, count * sizeof(uint32_t), c->stream));
+    HIPCHK(hipMemsetAsync(o.cut, 0xFF, count * sizeof(uint32_t), c->stream));
+    HIPCHK(hipMemsetAsync(o.end, 0xFF, count * sizeof(uint32_t), c->stream));
+    HIPCHK(hipMemsetAsync(o.overlap, 0xFF, count, c->stream));
+    HIPCHK(hipMemsetAsync(o.dist, 0xFF, count, c->stream));
+    return BITNUC_OK;
+}
+
+// Context scratch: 16 bytes per query (scratch 10, the family's table slot).  Everything in device memory; count, nq, k >= 1, 1 <= min_overlap <= k, reads of
+// at most kEdistBestMaxRead bases; fixed: k <= read_len.  The rule travels by value in the geometry
+template <class L, class HQ>
+int launch_reads_adapter(bitnuc_ctx *c, const L &in, size_t count, const AdapterArgs<HQ> &a, const HQ *d_queries, const AdapterOut &o, unsigned long long *slot,
+                         bitnuc_err *err) {
+    if (int st = ensure_scratch(c, 10, a.nq * kEdistEntry, err)) return st;
+    u32x4 *tabs = reinterpret_cast<u32x4 *>(c->scratch[10]);
+    edist_tables_kernel<<<(unsigned)((a.nq + 63) / 64), 64, 0, c->stream>>>(dev_queries(d_queries), (unsigned)a.nq, (unsigned)a.k, tabs);
+    HIPCHK(hipGetLastError());
+    const bitnuc_host::AdapterRule rule = bitnuc_host::adapter_rule(a.min_overlap, a.err_num, a.err_den);
+    auto base = edist_best_geom(in, a.k, a.nq);
+    uint32_t steps = 0; // bit i - 1: allowed(i) - allowed(i - 1), 0 or 1 since err_num <= err_den
+    for (unsigned i = 1; i <= 32; ++i) steps |= (uint32_t)(rule.allowed[i] - rule.allowed[i - 1]) << (i - 1);
+    const EdistAdapterGeom<decltype(base)> g{base, (unsigned)a.min_overlap, rule.allowed[a.k], steps};
+    const size_t want = (count + kEdistBlock - 1) / kEdistBlock, cap = (size_t)c->num_cu * kEdistBlocksPerCu;
+    reads_edist_adapter_kernel<L::packed, decltype(base)><<<(unsigned)(want < cap ? want : cap), kEdistBlock, 0, c->stream>>>(
+        reinterpret_cast<const uint8_t *>(in.data), (unsigned long long)count, g, tabs, o.adapter, o.cut, o.end, o.overlap, o.dist, slot);
+    HIPCHK(hipGetLastError());
+    return BITNUC_OK;
+}
+
+// an asynchronous form: everything in device memory, slot base 0
+template <class L, class HQ>
+int reads_adapter_async(bitnuc_ctx *c, const L &in, size_t count, const AdapterArgs<HQ> &a, bitnuc_err *err) {
+    clear_err(err);
+    if (int st = check_ctx(c, err)) return st;
+    bool done;
+    if (int st = check_reads_adapter(in, count, a, &done, err)) return st;
+    if (done) return BITNUC_OK;
+    DeviceGuard g(c->device);
+    if (a.whole().no_window(in.longest())) return adapter_fill_dev(c, count, a.o, err);
+    if (!in.data_ok()) return fail(err, BITNUC_UNSUPPORTED);
+    unsigned long long *slot = nullptr;
+    if constexpr (!L::packed)
+        if (int st = take_slot(c, 0, &slot, err)) return st;
+    return launch_reads_adapter(c, in, count, a, a.queries, a.o, slot, err);
+}
+
+// the host form on all reads: the index of the first invalid byte, or -1
+template <class HQ> long long reads_adapter_small(const FixedAscii &in, size_t count, const AdapterArgs<HQ> &a, const bitnuc_host::AdapterRule &rule) {
+    return reads_edist_adapter_small(in.data, in.read_len, count, a.k, host_queries(a.queries), a.nq, rule, a.o.adapter, a.o.cut, a.o.end, a.o.overlap, a.o.dist);
+}
+template <class HQ> long long reads_adapter_small(const FixedPacked &in, size_t count, const AdapterArgs<HQ> &a, const bitnuc_host::AdapterRule &rule) {
+    reads_edist_adapter_packed_small(in.data, in.read_len, count, a.k, host_queries(a.queries), a.nq, rule, a.o.adapter, a.o.cut, a.o.end, a.o.overlap, a.o.dist);
+    return -1;
+}
+template <class HQ> long long reads_adapter_small(const RaggedAscii &in, size_t count, const AdapterArgs<HQ> &a, const bitnuc_host::AdapterRule &rule) {
+    return reads_edist_adapter_batch_small(in.data, in.offsets, count, a.k, host_queries(a.queries), a.nq, rule, a.o.adapter, a.o.cut, a.o.end, a.o.overlap, a.o.dist);
+}
+template <class HQ> long long reads_adapter_small(const RaggedPacked &in, size_t count, const AdapterArgs<HQ> &a, const bitnuc_host::AdapterRule &rule) {
+    reads_edist_adapter_batch_packed_small(in.data, in.word_offsets, in.offsets, count, a.k, host_queries(a.queries), a.nq, rule, a.o.adapter, a.o.cut, a.o.end,
+                                           a.o.overlap, a.o.dist);
+    return -1;
+}
+
+// A host form: everything in host memory; reads_host's order (ragged tables validated, with the read length limit, before the fill and the data pointer
+// check; below the cutoff the host form, ctx not needed; above it the layout's chunks of whole reads).  A chunk's adapter / cut / end live in scratch 1, its
+// overlap / dist in scratch 3; the queries once in scratch 2.  A ragged chunk without a read of k bases launches nothing and is filled
+template <class L, class HQ>
+int reads_adapter_host(bitnuc_ctx *c, L in, size_t count, const AdapterArgs<HQ> &a, bitnuc_err *err) {
+    clear_err(err);
+    bool done;
+    if (int st = check_reads_adapter(in, count, a, &done, err)) return st;
+    if (done) return BITNUC_OK;
+    const EditBestMatch<HQ> whole = a.whole();
+    if constexpr (L::ragged) {
+        const BatchFault f = in.check_tables(count);
+        if (f.kind) return fail_batch_tables(f, err);
+        if (int st = whole.check_lengths(in, count, err)) return st;
+        in.bases = in.offsets[count];
+    }
+    if (whole.no_window(in.longest())) { adapter_fill_host(count, a.o); return BITNUC_OK; }
+    if (!in.data_ok()) return fail(err, BITNUC_UNSUPPORTED);
+    if (on_host(c, whole.work(in, count))) {
+        const long long bad = reads_adapter_small(in, count, a, bitnuc_host::adapter_rule(a.min_overlap, a.err_num, a.err_den));
+        if constexpr (!L::packed)
+            if (bad >= 0) return fail_invalid_base(err, in.data[bad], (uint64_t)bad);
+        return BITNUC_OK;
+    }
+    if (int st = check_ctx(c, err)) return st;
+    DeviceGuard g(c->device);
+    if (int st = flush_pending(c, err)) return st;
+    if (int st = ensure_scratch(c, 2, a.nq * sizeof(HQ), err)) return st;
+    HIPCHK(hipMemcpyAsync(c->scratch[2], a.queries, a.nq * sizeof(HQ), hipMemcpyHostToDevice, c->stream));
+    std::vector<uint64_t> tab; // a ragged chunk's rebased tables on their way to scratch 4: alive until the chunk is drained
+    for (size_t r0 = 0; r0 < count;) {
+        const size_t m = in.chunk_end(r0, count) - r0;
+        const AdapterOut h{a.o.adapter + r0, a.o.cut + r0, a.o.end + r0, a.o.overlap + r0, a.o.dist + r0};
+        if constexpr (L::ragged) {
+            const size_t size = in.chunk_size(r0, m);
+            if (L::packed ? size == 0 : whole.no_window(size)) {
+                adapter_fill_host(m, h);
+                r0 += m;
+                continue;
+            }
+        }
+        if (int st = ensure_scratch(c, 1, 3 * m * 4, err)) return st;
+        if (int st = ensure_scratch(c, 3, 2 * m < 64 ? 64 : 2 * m, err)) return st;
+        uint32_t *d_adapter = reinterpret_cast<uint32_t *>(c->scratch[1]);
+        const AdapterOut d{d_adapter, d_adapter + m, d_adapter + 2 * m, c->scratch[3], c->scratch[3] + m};
+        L dev{};
+        unsigned long long base, *slot = nullptr;
+        if (int st = in.stage(c, r0, m, tab, &dev, &base, err)) return st;
+        if constexpr (!L::packed)
+            if (int st = take_slot(c, base, &slot, err)) return st;
+        if (int st = launch_reads_adapter(c, dev, m, a, reinterpret_cast<const HQ *>(c->scratch[2]), d, slot, err)) return st;
+        HIPCHK(hipMemcpyAsync(h.adapter, d.adapter, m * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(h.cut, d.cut, m * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(h.end, d.end, m * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(h.overlap, d.overlap, m, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(h.dist, d.dist, m, hipMemcpyDeviceToHost, c->stream));
         bitnuc_err e;
         if (int st = drain(c, &e)) { if (err) *err = e; return st; }
         r0 += m;

@@ -701,6 +701,78 @@ class Context {
             return NucleotideError::from_c(e);
         return b;
     }
+    // the 3' adapter per read (bitnuc_reads_edist_adapter*, _adapter_batch*): of the adapters the one a read carries in full anywhere or as a prefix of
+    // min_overlap <= overlap < k positions overhanging its end, within floor(overlap x err_num / err_den) edits; reads[0, cut) is what a trimmer keeps.  No
+    // admissible candidate, or a read shorter than k: UINT32_MAX x 3, 0xFF x 2
+    struct ReadsAdapter { std::vector<uint32_t> adapter, cut, end; std::vector<uint8_t> overlap, dist; };
+    Result<ReadsAdapter> reads_edist_adapter(Bytes reads, size_t read_len, size_t k, const std::vector<uint64_t> &queries, size_t min_overlap = 3, size_t err_num = 1,
+                                             size_t err_den = 10) const {
+        return adapter_(read_len ? reads.len / read_len : 0, [&](size_t count, ReadsAdapter &a, bitnuc_err *e) {
+            return bitnuc_reads_edist_adapter(ctx_, reads.ptr, read_len, count, k, queries.data(), queries.size(), min_overlap, err_num, err_den, a.adapter.data(),
+                                              a.cut.data(), a.end.data(), a.overlap.data(), a.dist.data(), e);
+        });
+    }
+    Result<ReadsAdapter> reads_edist_adapter_packed(Words words, size_t read_len, size_t count, size_t k, const std::vector<uint64_t> &queries, size_t min_overlap = 3,
+                                                    size_t err_num = 1, size_t err_den = 10) const {
+        return adapter_(count, [&](size_t count, ReadsAdapter &a, bitnuc_err *e) {
+            return bitnuc_reads_edist_adapter_packed(ctx_, words.ptr, read_len, count, k, queries.data(), queries.size(), min_overlap, err_num, err_den, a.adapter.data(),
+                                                     a.cut.data(), a.end.data(), a.overlap.data(), a.dist.data(), e);
+        });
+    }
+    Result<ReadsAdapter> reads_pattern_edist_adapter(Bytes reads, size_t read_len, size_t k, const std::vector<bitnuc_pattern> &patterns, size_t min_overlap = 3,
+                                                     size_t err_num = 1, size_t err_den = 10) const {
+        return adapter_(read_len ? reads.len / read_len : 0, [&](size_t count, ReadsAdapter &a, bitnuc_err *e) {
+            return bitnuc_reads_pattern_edist_adapter(ctx_, reads.ptr, read_len, count, k, patterns.data(), patterns.size(), min_overlap, err_num, err_den,
+                                                      a.adapter.data(), a.cut.data(), a.end.data(), a.overlap.data(), a.dist.data(), e);
+        });
+    }
+    Result<ReadsAdapter> reads_pattern_edist_adapter_packed(Words words, size_t read_len, size_t count, size_t k, const std::vector<bitnuc_pattern> &patterns,
+                                                            size_t min_overlap = 3, size_t err_num = 1, size_t err_den = 10) const {
+        return adapter_(count, [&](size_t count, ReadsAdapter &a, bitnuc_err *e) {
+            return bitnuc_reads_pattern_edist_adapter_packed(ctx_, words.ptr, read_len, count, k, patterns.data(), patterns.size(), min_overlap, err_num, err_den,
+                                                             a.adapter.data(), a.cut.data(), a.end.data(), a.overlap.data(), a.dist.data(), e);
+        });
+    }
+    Result<ReadsAdapter> reads_edist_adapter_batch(Bytes seq, const std::vector<uint64_t> &offsets, size_t k, const std::vector<uint64_t> &queries,
+                                                   size_t min_overlap = 3, size_t err_num = 1, size_t err_den = 10) const {
+        const size_t n = offsets.empty() ? 0 : offsets.size() - 1;
+        if (n && seq.len < offsets.back()) return NucleotideError::invalid_length(seq.len);
+        return adapter_(n, [&](size_t count, ReadsAdapter &a, bitnuc_err *e) {
+            return bitnuc_reads_edist_adapter_batch(ctx_, seq.ptr, offsets.data(), count, k, queries.data(), queries.size(), min_overlap, err_num, err_den,
+                                                    a.adapter.data(), a.cut.data(), a.end.data(), a.overlap.data(), a.dist.data(), e);
+        });
+    }
+    Result<ReadsAdapter> reads_edist_adapter_batch_packed(Words words, const std::vector<uint64_t> &word_offsets, const std::vector<uint64_t> &offsets, size_t k,
+                                                          const std::vector<uint64_t> &queries, size_t min_overlap = 3, size_t err_num = 1, size_t err_den = 10) const {
+        const size_t n = offsets.empty() ? 0 : offsets.size() - 1;
+        if (word_offsets.size() != offsets.size()) return NucleotideError::unsupported();
+        if (n && words.len < word_offsets.back()) return NucleotideError::invalid_length(words.len);
+        return adapter_(n, [&](size_t count, ReadsAdapter &a, bitnuc_err *e) {
+            return bitnuc_reads_edist_adapter_batch_packed(ctx_, words.ptr, word_offsets.data(), offsets.data(), count, k, queries.data(), queries.size(), min_overlap,
+                                                           err_num, err_den, a.adapter.data(), a.cut.data(), a.end.data(), a.overlap.data(), a.dist.data(), e);
+        });
+    }
+    Result<ReadsAdapter> reads_pattern_edist_adapter_batch(Bytes seq, const std::vector<uint64_t> &offsets, size_t k, const std::vector<bitnuc_pattern> &patterns,
+                                                           size_t min_overlap = 3, size_t err_num = 1, size_t err_den = 10) const {
+        const size_t n = offsets.empty() ? 0 : offsets.size() - 1;
+        if (n && seq.len < offsets.back()) return NucleotideError::invalid_length(seq.len);
+        return adapter_(n, [&](size_t count, ReadsAdapter &a, bitnuc_err *e) {
+            return bitnuc_reads_pattern_edist_adapter_batch(ctx_, seq.ptr, offsets.data(), count, k, patterns.data(), patterns.size(), min_overlap, err_num, err_den,
+                                                            a.adapter.data(), a.cut.data(), a.end.data(), a.overlap.data(), a.dist.data(), e);
+        });
+    }
+    Result<ReadsAdapter> reads_pattern_edist_adapter_batch_packed(Words words, const std::vector<uint64_t> &word_offsets, const std::vector<uint64_t> &offsets, size_t k,
+                                                                  const std::vector<bitnuc_pattern> &patterns, size_t min_overlap = 3, size_t err_num = 1,
+                                                                  size_t err_den = 10) const {
+        const size_t n = offsets.empty() ? 0 : offsets.size() - 1;
+        if (word_offsets.size() != offsets.size()) return NucleotideError::unsupported();
+        if (n && words.len < word_offsets.back()) return NucleotideError::invalid_length(words.len);
+        return adapter_(n, [&](size_t count, ReadsAdapter &a, bitnuc_err *e) {
+            return bitnuc_reads_pattern_edist_adapter_batch_packed(ctx_, words.ptr, word_offsets.data(), offsets.data(), count, k, patterns.data(), patterns.size(),
+                                                                   min_overlap, err_num, err_den, a.adapter.data(), a.cut.data(), a.end.data(), a.overlap.data(),
+                                                                   a.dist.data(), e);
+        });
+    }
     Result<std::vector<uint64_t>> kmer_hdist_hits_packed(Words words, size_t n, size_t k, uint64_t query, unsigned tau, std::vector<uint8_t> *hit_dist = nullptr) const {
         uint64_t total = 0;
         bitnuc_err e;
@@ -908,6 +980,13 @@ class Context {
 
   private:
     bitnuc_ctx *ctx_ = nullptr;
+    // the five output vectors of the reads_*edist_adapter* methods around one C call
+    template <class Call> static Result<ReadsAdapter> adapter_(size_t count, Call call) {
+        ReadsAdapter a{std::vector<uint32_t>(count), std::vector<uint32_t>(count), std::vector<uint32_t>(count), std::vector<uint8_t>(count), std::vector<uint8_t>(count)};
+        bitnuc_err e;
+        if (call(count, a, &e) != BITNUC_OK) return NucleotideError::from_c(e);
+        return a;
+    }
     // the output vectors of the kmer_*edist_* methods around one C call
     template <class Call> static Result<EndDist> edist_best_(size_t nq, Call call) {
         std::vector<uint64_t> end(nq);

@@ -882,7 +882,7 @@ int bitnuc_reads_pattern_edist_anchored_batch_packed(bitnuc_ctx *ctx, const uint
  * base), 1.040 - 1.044 (ASCII) and 1.030 - 1.032 (packed) x that of bitnuc_reads_edist_anchored*_async at span 64 in the same queues; 3.8 - 4.2 x the time
  * of bitnuc_reads_hdist_best*_async on the same arguments at 64 queries and more, 3.1 - 3.4 x at 8, 1.1 - 1.6 x at 1 (another answer: the price of indel
  * tolerance); the pattern twins cost what the exact forms cost (0.995 - 1.002 x).
- * The alignment's start: bitnuc_reads_edist_start* below with (START, 0).  Out of scope: partial adapters overhanging the 3' end with a minimum-overlap rule, k > 32, affine gaps,
+ * The alignment's start: bitnuc_reads_edist_start* below with (START, 0).  Partial adapters overhanging the 3' end with a minimum-overlap rule: bitnuc_reads_edist_adapter* below.  Out of scope: k > 32, affine gaps,
  * reverse-complement queries. */
 #define BITNUC_EDIST_MAX_READ 67108864 /* 2^26 bases */
 int bitnuc_reads_edist_best_async(bitnuc_ctx *ctx, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const uint64_t *d_queries, size_t n_queries,
@@ -961,6 +961,115 @@ int bitnuc_reads_pattern_edist_best_batch(bitnuc_ctx *ctx, const uint8_t *seq, c
 int bitnuc_reads_pattern_edist_best_batch_packed(bitnuc_ctx *ctx, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
                                                  const bitnuc_pattern *patterns, size_t n_queries, uint32_t *best_query, uint32_t *best_end, uint8_t *best_dist,
                                                  uint32_t *second_query, uint32_t *second_end, uint8_t *second_dist, bitnuc_err *err);
+
+/* ---- The 3' ADAPTER per read: of Q adapters, which one a read carries IN FULL anywhere or as a PREFIX OVERHANGING the read's end, with how many edits,
+ * and the base to cut at -- the search stage of an adapter trimmer in one call (bitnuc_reads_edist_best* finds only full adapters: a 150-base read that
+ * ends with the first 10 bases of a k-base adapter is at distance about k - 10 there) ----
+ * Arguments (fixed form): read_len, count, k, queries | patterns, n_queries as in bitnuc_reads_edist_best*, then size_t min_overlap, size_t err_num,
+ * size_t err_den and five outputs.  The ragged forms (_batch*) take the tables of bitnuc_reads_edist_best_batch* of the same suffix instead of read_len;
+ * there n = len_r = offsets[r + 1] - offsets[r] per read.
+ * Allowance: allowed(i) = floor(i x err_num / err_den), the trimmers' error-rate rule as an exact rational (1 / 10 with min_overlap = 3 is the usual
+ * default).
+ * Distance: D of the bitnuc_reads_edist_anchored* block over the whole read: D[0][j] = 0, D[i][0] = i, n = the read's bases; a pattern position matches
+ * when the base is in its set.
+ * Candidates of (read, query) are pairs (i, j).  FULL: i = k and any 1 <= j <= n.  OVERHANG: min_overlap <= i < k and j = n (the read ends inside the
+ * adapter: its last bases align to the adapter's first i positions).  A candidate is admissible when D[i][j] <= allowed(i); min_overlap <= k, so a full
+ * candidate always meets the overlap rule.  Per candidate d = D[i][j], matches = i - d, misses = k - matches.  The read's result is the admissible
+ * candidate, over all queries, with the lexicographically smallest (misses, d, query, j): most matched adapter positions, then fewest edits, then the
+ * lower query index, then the first end.  With i = k this is the family's (dist, query, end).
+ * Cut: with the winner's (q, i, e = j, d), cut = s is the lexicographic minimum over s in [e - min(e, 2i - 1), e] of (Lev(q_1 .. q_i, t[s, e)), e - s):
+ * the rule of bitnuc_reads_edist_start* applied to the prefix; its distance equals d.  read[0, cut) is what a trimmer keeps.
+ * Outputs, exactly [0, count) of each: adapter (u32, the query index), cut (u32), end (u32, = j), overlap (u8, = i), dist (u8, = d).  The fill is
+ * UINT32_MAX x 3 and 0xFF x 2: written when no candidate is admissible, and for every read when k == 0 or n_queries == 0.  Fixed form: every read gets it
+ * when read_len < k.  Ragged form: a read with len_r < k gets it and is neither read nor validated.  Deterministic.
+ * Identities.  With min_overlap = k and rate 1 / 1: (adapter, end, dist) equals the best triple of bitnuc_reads_edist_best* byte for byte, overlap = k, and
+ * (cut, dist) equals bitnuc_reads_edist_start* with (START, 0) on that triple.  With rate 0 / 1 and min_overlap = 1 the result is plain string matching:
+ * the first exact occurrence, else the longest i with the read ending in q_1 .. q_i; cut = end - overlap, dist = 0.  The pattern twins on singleton
+ * patterns equal the exact forms; the ragged forms on equal lengths equal the fixed forms; ASCII and packed agree; dist = Lev(q_1 .. q_overlap,
+ * read[cut, end)).
+ * Validation: that of bitnuc_reads_edist_best* / _best_batch*: every byte of every read of at least k bases; the first invalid byte in buffer order ->
+ * INVALID_BASE with its absolute index, latched once per call for bitnuc_ctx_sync() by the _async forms (outputs then unspecified); the host forms below
+ * the cutoff leave the outputs untouched.  A call that writes only fills reads and validates nothing.  Packed: bits above a read's last base are ignored.
+ * Limits: those of bitnuc_reads_edist_best* / _best_batch*, BITNUC_EDIST_MAX_READ included (the ragged host forms judge it at the table check, the ragged
+ * _async forms trust their tables).
+ * Checks, in order: (1) ctx (_async forms, and the host forms above the cutoff), (2) k > 32 -> SEQUENCE_TOO_LONG (value = k), (3) the layout's size limits
+ * (UNSUPPORTED), (4) n_queries > BITNUC_MAX_QUERIES -> UNSUPPORTED (value = n_queries), then with k >= 1: (5) min_overlap == 0 or min_overlap > k ->
+ * UNSUPPORTED (value = min_overlap), (6) err_den == 0 or err_num > err_den -> UNSUPPORTED (value = err_num); (7) fixed: read_len > BITNUC_EDIST_MAX_READ ->
+ * UNSUPPORTED (value = read_len), (8) count == 0 -> OK, nothing written, (9) any of the five outputs NULL, adapter, cut or end not 4-byte aligned (overlap
+ * and dist may have any byte offset), queries NULL with n_queries > 0 or not 8-byte aligned (patterns: 4-byte), an offsets table NULL or not 8-byte
+ * aligned -> UNSUPPORTED, (10) ragged host forms: the tables' validation and the read length limit, (11) where a read is looked at: reads / words NULL
+ * (words not 8-byte aligned) -> UNSUPPORTED.  Nothing is written on an argument error.
+ * The _async forms have the contract of bitnuc_reads_edist_best*_async: device pointers for everything, the context's stream, no host synchronisation but
+ * the growth of context scratch (16 bytes per query, the family's table slot; the allowances travel in the kernel's arguments), capturable into a
+ * hipGraph after a warm-up of THIS call with the same or larger n_queries; reads, tables and queries are read at every replay.  The host forms are
+ * synchronous and judge the work of bitnuc_reads_edist_best* / _best_batch* against the host cutoff: below it they run on the host (ctx may be NULL), above
+ * it through the context in chunks of whole reads; INVALID_BASE indices stay absolute.
+ * Cost: the kernel of bitnuc_reads_edist_best* (one read per lane, the same step of 20 vector instructions per (read, query, base)) with, per (read,
+ * query), a decode of the walk's LAST COLUMN -- after the read's last base the column (Pv, Mv) holds D[i][n] for every prefix length i at once, so the
+ * overhang costs no second pass over the read -- and per read one backward walk of at most 2 x overlap - 1 bases for the cut.  The ragged forms' masked
+ * loop snapshots the column at a lane's own last base (two selects per query and step).  No LDS, no atomics but the invalid-byte latch.
+ * Measured on 6,666,667 x 150-base reads and on reads of 100 .. 200 bases (10^9 bases each), one MI355X (profiles/r25_reads_edist_adapter.json), rate 1 / 10,
+ * min_overlap 3, against today's nearest route in the same queues -- bitnuc_reads_edist_best*_async with the second triple NULL followed by
+ * bitnuc_reads_edist_start*_async, which finds no overhang: a yardstick of cost only.  Fixed, ASCII / packed, k = 16: 0.92 / 0.68 ms at 1 adapter, 4.29 / 4.12
+ * at 8, 33.6 / 32.6 at 64, 268 / 260 at 512 (k = 31: 0.94 / 0.71, 4.47 / 4.31, 35.0 / 33.9, 279 / 270): 0.71 - 0.86 x the route at 1 adapter (one launch
+ * instead of two), 0.99 - 1.03 x at 8, 1.04 x (k = 16) and 1.08 - 1.09 x (k = 31) at 64 and 512, where the decode's 9 vector instructions per (read, query,
+ * prefix length) over the walk's 20 per base predict 1.045 and 1.09.  Ragged: 1.41 / 1.05 ms at 1 adapter, 6.9 / 6.6 at 8, 54 / 52 at 64, 434 / 416 at 512
+ * (k = 16): 0.88 - 1.04 x the ragged route at 1, 1.12 - 1.14 x at 8, 1.16 - 1.20 x at 64 and 512 -- the snapshot makes the masked step 24 vector instructions
+ * where the route's has 21.25 (predicted 1.16 at k = 16, 1.19 at k = 31).  26 of the 32 points are inside the bound from the disassembly, 6 outside it by at
+ * most 0.005.  Not tuned.
+ * Out of scope: reads shorter than k (the fill), a runner-up, 5' and anchored adapters, adapters that overhang the read's START, k > 32, per-adapter
+ * rates, reverse complements. */
+int bitnuc_reads_edist_adapter_async(bitnuc_ctx *ctx, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const uint64_t *d_queries, size_t n_queries,
+                                     size_t min_overlap, size_t err_num, size_t err_den, uint32_t *d_adapter, uint32_t *d_cut, uint32_t *d_end, uint8_t *d_overlap,
+                                     uint8_t *d_dist, bitnuc_err *err);
+int bitnuc_reads_edist_adapter_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t read_len, size_t count, size_t k, const uint64_t *d_queries,
+                                            size_t n_queries, size_t min_overlap, size_t err_num, size_t err_den, uint32_t *d_adapter, uint32_t *d_cut, uint32_t *d_end,
+                                            uint8_t *d_overlap, uint8_t *d_dist, bitnuc_err *err);
+int bitnuc_reads_edist_adapter_batch_async(bitnuc_ctx *ctx, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k,
+                                           const uint64_t *d_queries, size_t n_queries, size_t min_overlap, size_t err_num, size_t err_den, uint32_t *d_adapter,
+                                           uint32_t *d_cut, uint32_t *d_end, uint8_t *d_overlap, uint8_t *d_dist, bitnuc_err *err);
+int bitnuc_reads_edist_adapter_batch_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets, size_t count,
+                                                  size_t total_words, size_t k, const uint64_t *d_queries, size_t n_queries, size_t min_overlap, size_t err_num,
+                                                  size_t err_den, uint32_t *d_adapter, uint32_t *d_cut, uint32_t *d_end, uint8_t *d_overlap, uint8_t *d_dist,
+                                                  bitnuc_err *err);
+int bitnuc_reads_edist_adapter(bitnuc_ctx *ctx, const uint8_t *reads, size_t read_len, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
+                               size_t min_overlap, size_t err_num, size_t err_den, uint32_t *adapter, uint32_t *cut, uint32_t *end, uint8_t *overlap, uint8_t *dist,
+                               bitnuc_err *err);
+int bitnuc_reads_edist_adapter_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t read_len, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
+                                      size_t min_overlap, size_t err_num, size_t err_den, uint32_t *adapter, uint32_t *cut, uint32_t *end, uint8_t *overlap,
+                                      uint8_t *dist, bitnuc_err *err);
+int bitnuc_reads_edist_adapter_batch(bitnuc_ctx *ctx, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, const uint64_t *queries, size_t n_queries,
+                                     size_t min_overlap, size_t err_num, size_t err_den, uint32_t *adapter, uint32_t *cut, uint32_t *end, uint8_t *overlap,
+                                     uint8_t *dist, bitnuc_err *err);
+int bitnuc_reads_edist_adapter_batch_packed(bitnuc_ctx *ctx, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count, size_t k,
+                                            const uint64_t *queries, size_t n_queries, size_t min_overlap, size_t err_num, size_t err_den, uint32_t *adapter,
+                                            uint32_t *cut, uint32_t *end, uint8_t *overlap, uint8_t *dist, bitnuc_err *err);
+/* the pattern twins: a set of bases per adapter position (bitnuc_pattern); everything else as above */
+int bitnuc_reads_pattern_edist_adapter_async(bitnuc_ctx *ctx, const uint8_t *d_reads, size_t read_len, size_t count, size_t k, const bitnuc_pattern *d_patterns,
+                                             size_t n_queries, size_t min_overlap, size_t err_num, size_t err_den, uint32_t *d_adapter, uint32_t *d_cut, uint32_t *d_end,
+                                             uint8_t *d_overlap, uint8_t *d_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_edist_adapter_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, size_t read_len, size_t count, size_t k, const bitnuc_pattern *d_patterns,
+                                                    size_t n_queries, size_t min_overlap, size_t err_num, size_t err_den, uint32_t *d_adapter, uint32_t *d_cut,
+                                                    uint32_t *d_end, uint8_t *d_overlap, uint8_t *d_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_edist_adapter_batch_async(bitnuc_ctx *ctx, const uint8_t *d_seq, const uint64_t *d_offsets, size_t count, size_t total_bases, size_t k,
+                                                   const bitnuc_pattern *d_patterns, size_t n_queries, size_t min_overlap, size_t err_num, size_t err_den,
+                                                   uint32_t *d_adapter, uint32_t *d_cut, uint32_t *d_end, uint8_t *d_overlap, uint8_t *d_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_edist_adapter_batch_packed_async(bitnuc_ctx *ctx, const uint64_t *d_words, const uint64_t *d_word_offsets, const uint64_t *d_offsets,
+                                                          size_t count, size_t total_words, size_t k, const bitnuc_pattern *d_patterns, size_t n_queries,
+                                                          size_t min_overlap, size_t err_num, size_t err_den, uint32_t *d_adapter, uint32_t *d_cut, uint32_t *d_end,
+                                                          uint8_t *d_overlap, uint8_t *d_dist, bitnuc_err *err);
+int bitnuc_reads_pattern_edist_adapter(bitnuc_ctx *ctx, const uint8_t *reads, size_t read_len, size_t count, size_t k, const bitnuc_pattern *patterns, size_t n_queries,
+                                       size_t min_overlap, size_t err_num, size_t err_den, uint32_t *adapter, uint32_t *cut, uint32_t *end, uint8_t *overlap,
+                                       uint8_t *dist, bitnuc_err *err);
+int bitnuc_reads_pattern_edist_adapter_packed(bitnuc_ctx *ctx, const uint64_t *words, size_t read_len, size_t count, size_t k, const bitnuc_pattern *patterns,
+                                              size_t n_queries, size_t min_overlap, size_t err_num, size_t err_den, uint32_t *adapter, uint32_t *cut, uint32_t *end,
+                                              uint8_t *overlap, uint8_t *dist, bitnuc_err *err);
+int bitnuc_reads_pattern_edist_adapter_batch(bitnuc_ctx *ctx, const uint8_t *seq, const uint64_t *offsets, size_t count, size_t k, const bitnuc_pattern *patterns,
+                                             size_t n_queries, size_t min_overlap, size_t err_num, size_t err_den, uint32_t *adapter, uint32_t *cut, uint32_t *end,
+                                             uint8_t *overlap, uint8_t *dist, bitnuc_err *err);
+int bitnuc_reads_pattern_edist_adapter_batch_packed(bitnuc_ctx *ctx, const uint64_t *words, const uint64_t *word_offsets, const uint64_t *offsets, size_t count,
+                                                    size_t k, const bitnuc_pattern *patterns, size_t n_queries, size_t min_overlap, size_t err_num, size_t err_den,
+                                                    uint32_t *adapter, uint32_t *cut, uint32_t *end, uint8_t *overlap, uint8_t *dist, bitnuc_err *err);
 
 /* The INDEL-TOLERANT search ALONG A REFERENCE: the best match and the count per query by EDIT distance, where bitnuc_kmer_hdist_best* and
  * bitnuc_kmer_hdist_count_multi* use the Hamming distance.  A guide or primer that sits in the reference with one bulge (one inserted or deleted base)
